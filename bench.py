@@ -12,7 +12,13 @@ One process per GPU.  `python bench.py --gpus N` starts the N rank processes its
 GPU; like the reference's harness, tools/benchmark.py:269); under `python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N` the launcher's RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* are used as they are.  Collectives = bd_comm_* (RCCL over xGMI).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints ONE JSON line (rank 0)
+with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step) and the step-time percentiles of those same steps.
+`--dump-outputs DIR` then also writes what the last timed step computed (its losses and a fixed sample of every trainable parameter
+after its SGD update) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
+
+`--full` adds everything that costs runs or legs of its own, each switchable off by its own option:
+  reference_protocol -- above (--ref-protocol-steps)
   roofline     -- the kernel with the largest share of the step (per-kernel entries: roofline_others).  Each kernel is priced against
                   the roof its launches sit under: "mfma" (algorithmic FLOPs / time vs 2.5 PFLOP/s) when their arithmetic intensity
                   exceeds the machine balance, else "hbm" (algorithmic bytes -- every operand once -- / time vs 8 TB/s); durations
@@ -322,6 +328,30 @@ def cpu_baseline(cfg, params, seconds=25.0, batch=2, size=(800, 1344)):
     return out
 
 
+DUMP_SAMPLE = 65536              # elements kept of a larger parameter (the same seeded positions in every run)
+DUMP_LIMIT = 64 << 20             # bytes, all files together
+
+
+def dump_outputs(outdir, model, losses):
+    """What the last timed step hands its caller: every loss it returned, and the trainable parameters as that step's SGD update left
+    them (reference names and layouts, model.state_dict()).  A parameter of more than DUMP_SAMPLE elements is sampled at sorted
+    positions drawn by a generator seeded with 0, so two runs -- or two builds -- write the same positions.  float32 throughout."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray([float(v)], dtype=np.float32) for k, v in losses.items()}
+    sd = model.state_dict()
+    for name in model.reference_grads_names():
+        w = np.ascontiguousarray(sd[name], dtype=np.float32).reshape(-1)
+        if w.size > DUMP_SAMPLE:
+            w = w[np.sort(np.random.default_rng(0).choice(w.size, DUMP_SAMPLE, replace=False))]
+        arrays["param." + name] = w
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes would exceed the {DUMP_LIMIT}-byte limit")
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+    print(f"# --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MB in {outdir}", file=sys.stderr)
+
+
 def _stdout_to_stderr():
     """RCCL prints a version banner on the C stdout when the first communicator comes up (and it surfaces whenever that buffer is
     flushed -- after the JSON line, at exit): everything but the result line goes to stderr."""
@@ -514,7 +544,19 @@ def main():
                     help="ablation: bd_conv_desc.route[2], the weight-gradient bit mask (5 = the ring-staged weight-gradient kernels off: rounds 1-3 kernels)")
     ap.add_argument("--conv-knob", type=int, default=None,
                     help="ablation: bd_conv_desc.route[1] bit mask (include/basedet_hip.h) of every call of the run")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that cost runs of their own: roofline (per-kernel HIP events, in-run PMC passes, MFMA-rate and "
+                         "kernel-clock probes), reference_protocol, cpu_baseline; --no-roofline / --no-pmc / --no-cpu-baseline / "
+                         "--ref-protocol-steps 0 switch them off one by one.  Without it the run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed -- its losses and a fixed, seeded sample of every "
+                         "trainable parameter after its SGD update -- as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:           # a plain run: the headline only
+        args.no_roofline = args.no_pmc = args.no_cpu_baseline = True
+        args.ref_protocol_steps = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus)          # does not return
@@ -639,7 +681,7 @@ def worker(args):
         if ops.L().bd_probe_kernel_clock(kern.encode(), int(reset), _C.byref(mhz), _C.byref(busy)) != 0 or not mhz.value:
             return None
         return {"clock_mhz": round(mhz.value, 0), "probe_busy_ms": round(busy.value, 2)}
-    CLOCKED = ("conv3x3_pp_kernel", "conv_wgrad3x3_ring_kernel")
+    CLOCKED = ("conv3x3_pp_kernel", "conv_wgrad3x3_ring_kernel") if timer else ()      # (read for the roofline entries only)
     for kern_ in CLOCKED:
         _kernel_clock(kern_, True)               # (the device is idle: sync() above) the sums start with the timed region
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]       # step boundaries on the main stream (p50 / p95)
@@ -681,6 +723,8 @@ def worker(args):
     loss = float(last["total_loss"])
     assert np.isfinite(loss), "training diverged"
     step_ms = np.array([marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)])
+    if args.dump_outputs and rank == 0:           # before the reference-protocol leg, whose steps train on
+        dump_outputs(args.dump_outputs, model, last)
 
     # ---- the reference harness's own protocol (tools/benchmark.py:125-133): host batch in, full device sync around every step
     ref_proto = None
@@ -724,7 +768,8 @@ def worker(args):
                        **({"fp8_grad_scale": [(int(a), float(c), float(d_)) for a, b_, c, d_ in (model.fp8_scale_log[:1] + model.fp8_scale_log[-2:])]}
                           if getattr(model, "fp8_scale_log", None) else {})},
             "step_ms_p50": round(float(np.percentile(step_ms, 50)), 3), "step_ms_p95": round(float(np.percentile(step_ms, 95)), 3),
-            "step_ms_note": "device time between step boundaries on rank 0's main stream (HIP events), instrumented steps included",
+            "step_ms_note": "device time between step boundaries on rank 0's main stream (HIP events)"
+                            + (", instrumented steps included" if timer else ""),
         }
         if args.skip_s2_3x3_after_warmup:
             out["INVALID_AS_THROUGHPUT"] = "timing A/B: the 3x3 / stride-2 forward and data-gradient launches were skipped in the timed steps"

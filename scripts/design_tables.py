@@ -33,7 +33,7 @@ r101 = json.load(open(P("r06_bench_r101_fp8.json"))); r101b = json.load(open(P("
 fcos = json.load(open(P("r06_bench_fcos_r50.json"))); frc = json.load(open(P("r06_bench_faster_rcnn_r50.json")))
 pm = d.get("mfma_peak_measured") or {}
 t = []
-t.append("### Headline and protocol legs (`profiles/r06_bench.json`: the default `python bench.py`, 100 timed steps after 20 warm-up)\n")
+t.append("### Headline and protocol legs (`profiles/r06_bench.json`: `python bench.py --full` (the default before plain runs became lean), 100 timed steps after 20 warm-up)\n")
 t.append("| leg | img/s | ms/step (mean; p50 / p95) | note |\n|---|---|---|---|")
 t.append(f"| RetinaNet-R50-FPN, inputs resident in HBM (**`value`**) | **{d['value']:.1f}** (round 5: 638.5; driver-run 635.9) | {d['ms_per_step']:.2f}; {d['step_ms_p50']:.2f} / {d['step_ms_p95']:.2f} | `whole_step_mfma_frac` {d['config']['whole_step_mfma_frac']:.3f} |")
 rp = d["reference_protocol"]

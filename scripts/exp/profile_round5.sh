@@ -6,7 +6,7 @@ O=$R/gpurun_out/r5p
 mkdir -p $O
 rm -f $O/workloads.txt
 cd $R
-B="bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --ref-protocol-steps 0 --serial-wgrad"
+B="bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --ref-protocol-steps 0 --serial-wgrad"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $B > $O/r05_bench_under_rocprof.json 2> $O/kt.err
 find $O/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/r05_bench_kernel_stats.csv
 rm -rf $O/kt
@@ -17,12 +17,12 @@ python3 scripts/pmc_traffic.py $O/fetch $O/write $O/r05_pmc_traffic.json > $O/tr
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d $O/sq -- python3 $P --serial-wgrad > /dev/null 2> $O/sq.err
 python3 scripts/pmc_sq.py $O/sq $O/r05_pmc_sq.json > $O/sq.txt 2>&1
 rm -rf $O/fetch $O/write $O/sq
-python3 bench.py > $O/r05_bench.json 2> $O/bench.err
+python3 bench.py --full > $O/r05_bench.json 2> $O/bench.err
 for w in fcos_r50_800x1344 faster_rcnn_r50_800x1344; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$w -- python3 bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-pmc --ref-protocol-steps 0 --serial-wgrad > /dev/null 2> $O/kt_$w.err
   find $O/kt_$w -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/r05_${w}_kernel_stats.csv
   rm -rf $O/kt_$w
-  python3 bench.py --workload $w --steps 50 --warmup 10 --no-cpu-baseline --ref-protocol-steps 0 > $O/r05_bench_$w.json 2>/dev/null
+  python3 bench.py --full --workload $w --steps 50 --warmup 10 --no-cpu-baseline --ref-protocol-steps 0 > $O/r05_bench_$w.json 2>/dev/null
 done
 for w in fcos_r50_800x1344 faster_rcnn_r50_800x1344 atss_r50_800x1344 ota_r50_800x1344 freeanchor_r50_800x1344 retinanet_r101_800x1344; do
   python3 bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --ref-protocol-steps 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$w', d['value'], d['ms_per_step'])" >> $O/workloads.txt
@@ -30,8 +30,8 @@ done
 for a in "--model-opt RPN_TARGETS_EARLY=0" ""; do
   python3 bench.py --workload faster_rcnn_r50_800x1344 $a --steps 30 --warmup 8 --no-cpu-baseline --no-roofline --ref-protocol-steps 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('faster_rcnn_r50 $a', d['value'], d['ms_per_step'])" >> $O/workloads.txt
 done
-python3 bench.py --workload retinanet_r101_800x1344 --fp8 --steps 20 --warmup 5 --no-cpu-baseline --ref-protocol-steps 0 > $O/r05_bench_r101_fp8.json 2>/dev/null
-python3 bench.py --workload retinanet_r101_800x1344 --batch 32 --steps 20 --warmup 5 --no-cpu-baseline --ref-protocol-steps 0 > $O/r05_bench_r101_bf16_b32.json 2>/dev/null
+python3 bench.py --full --workload retinanet_r101_800x1344 --fp8 --steps 20 --warmup 5 --no-cpu-baseline --ref-protocol-steps 0 > $O/r05_bench_r101_fp8.json 2>/dev/null
+python3 bench.py --full --workload retinanet_r101_800x1344 --batch 32 --steps 20 --warmup 5 --no-cpu-baseline --ref-protocol-steps 0 > $O/r05_bench_r101_bf16_b32.json 2>/dev/null
 for a in "--batch 16" "--batch 32" "--batch 16 --fp8" "--batch 16 --model-opt WGRAD_QUEUE=layer" "--batch 16 --wgrad-knob 5" "--batch 16 --dense1x1 3" "--batch 16"; do
   python3 bench.py $a --steps 30 --warmup 8 --no-cpu-baseline --no-roofline --ref-protocol-steps 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('retinanet_r50 $a', d['value'], d['ms_per_step'])" >> $O/workloads.txt
 done

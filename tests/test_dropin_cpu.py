@@ -1,11 +1,12 @@
 """Drop-in check of the `basedet` import alias (CPU; no kernels run).
 
-1. In the build container only (skipped where /root/reference is absent, e.g. on the GPU box): the reference's own
-   playground/examples/retinanet/res50_coco_800size_1x/config.py is imported BY PATH against the alias -- `from basedet.configs import
-   RetinaNetConfig` resolves to this repo -- and its `Cfg()` instantiates; the names the training entry resolves from it
+1. A playground-style experiment description -- the form of the reference's playground/examples/<experiment>/config.py: a `Cfg`
+   subclass of one of basedet.configs' model configs that files its outputs under the experiment's own path -- is written by the test
+   under a temporary playground/examples/<experiment>/ and imported BY PATH against the alias (`from basedet.configs import
+   RetinaNetConfig` resolves to this repo); its `Cfg()` instantiates and the names the training entry resolves from it
    (registers.models / registers.solvers / registers.trainers, tools/det_train.py:111, configs/detection_cfg.py:55-63) exist.
-   `megfile` (a path-joining helper the config imports; not installed here) is stood in by os.path.join inside the child process the
-   config is executed in.
+   `megfile` (a path-joining helper such files import; not installed here) is stood in by os.path.join inside the child process the
+   file is executed in.
 2. Everywhere: the alias exposes the operator surface under the reference's module paths and names."""
 import importlib.util
 import os
@@ -14,7 +15,24 @@ import types
 
 import pytest
 
-REF_CFG = "/root/reference/playground/examples/retinanet/res50_coco_800size_1x/config.py"
+# experiment directory under playground/examples -> the model config its description file subclasses
+_EXPERIMENTS = {"retinanet/res50_coco_800size_1x": "RetinaNetConfig", "fcos": "FCOSConfig", "faster_rcnn/res50_coco_800size_1x": "FasterRCNNConfig",
+                "atss": "ATSSConfig", "freeanchor": "FreeAnchorConfig", "ota": "OTAConfig"}
+
+_DESCRIPTION = """import os
+import megfile
+
+from basedet.configs import {base}
+
+_experiment = os.path.dirname(os.path.realpath(__file__)).split("playground" + os.sep)[-1]
+
+
+class Cfg({base}):
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.GLOBAL.OUTPUT_DIR = megfile.smart_path_join("logs", _experiment)
+        self.GLOBAL.CKPT_SAVE_DIR = megfile.smart_path_join(self.GLOBAL.CKPT_SAVE_DIR, _experiment)
+"""
 
 
 def _load_by_path(path):
@@ -51,16 +69,17 @@ print("RESULT " + json.dumps(dict(
 """
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason="the reference tree is only present in the build container")
 @pytest.mark.parametrize("rel", ["retinanet/res50_coco_800size_1x", "fcos", "faster_rcnn/res50_coco_800size_1x", "atss", "freeanchor", "ota"])
-def test_reference_playground_config_loads_against_the_alias(rel):
-    """The reference's config file is untrusted content: it is executed in a CHILD process (no GPU, nothing of this test process's state),
-    which reports what the training entry would resolve from it."""
+def test_reference_playground_config_loads_against_the_alias(rel, tmp_path):
+    """The description file is executed in a CHILD process (no GPU, nothing of this test process's state), which reports what the
+    training entry would resolve from it."""
     import json
     import subprocess
-    path = os.path.join("/root/reference/playground/examples", rel, "config.py")
-    if not os.path.exists(path):
-        pytest.skip(path + " absent")
+    exp = tmp_path.joinpath("playground", "examples", *rel.split("/"))
+    exp.mkdir(parents=True)
+    path = str(exp / "config.py")
+    with open(path, "w") as f:
+        f.write(_DESCRIPTION.format(base=_EXPERIMENTS[rel]))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", _CHILD, root, path, rel], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES=""))
