@@ -56,6 +56,11 @@ SIGNATURES = {
     "bd_conv2d_wgrad": (_I, [_D, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "bd_conv2d_wgrad_bias_workspace_bytes": (_Z, [_D]),
     "bd_conv2d_wgrad_bias": (_I, [_D, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "bd_fpn_deconv_pack": (_I, [_P, _I, _P, _P, _P]),
+    "bd_fpn_deconv_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "bd_fpn_deconv_dgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "bd_fpn_deconv_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "bd_fpn_deconv_wgrad": (_I, [_P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
     "bd_wgrad_queue_create": (_I, [_P]),
     "bd_wgrad_queue_destroy": (_I, [_P]),
     "bd_wgrad_queue_pending": (_I, [_P]),

@@ -31,6 +31,7 @@ SOURCES = {
     "conv_wgrad3x3_fp8.hip": [],
     "conv_wgrad1x1.hip": [],
     "conv_wgrad1x1_ring.hip": [],
+    "fpn_deconv.hip": [],
     "stem.hip": [],
     "boxops.hip": ["-ffp-contract=off"],
     "rcnn_ops.hip": ["-ffp-contract=off"],

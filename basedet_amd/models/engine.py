@@ -351,3 +351,35 @@ class FCLayer(ConvLayer):
 
     def export_grad(self, out):
         self._split(self.gw, self.gb, out, False)
+
+
+class DeconvLayer(ConvLayer):
+    """The FPN's learned top-down upsampling, M.ConvTranspose2d(C, C, 4, stride=2, padding=1, bias=False) (fpn_backbone.py:92-103,
+    131-138).  The reference's (C_coarse, C_fine, 4, 4) weight is the OIHW weight of a fine -> coarse Conv2d(k4, s2, p1), so the master is
+    kept in that conv view (OHWI [C_coarse][4][4][C_fine]) and ConvLayer's bind / export / export_grad and arena slot apply unchanged;
+    forward / dgrad / wgrad run the dedicated kernels of csrc/fpn_deconv.hip (forward = the conv view's data gradient and back)."""
+
+    def __init__(self, name, ch, device):
+        super().__init__(name, ch, ch, 4, 2, 1, device)
+        self.ch = ch
+        # phase-major operands of bd_fpn_deconv_fwd ([4 classes][C_fine][4 taps][C_coarse]) and bd_fpn_deconv_dgrad ([C_coarse][16][C_fine])
+        self.w_fwd = torch.empty((4, ch, 4, ch), dtype=torch.bfloat16, device=device)
+        self.w_dgrad = torch.empty((ch, 16, ch), dtype=torch.bfloat16, device=device)
+
+    def pack(self):
+        ops.fpn_deconv_pack(self.w, self.ch, self.w_fwd, self.w_dgrad)
+
+    def forward(self, x, gc: Geom, y, add=None):
+        """y (fine level, 2H x 2W of gc) = bf16(add + conv_transpose(x)); add may be y (the merged lateral, in place)."""
+        return ops.fpn_deconv_fwd(x, self.w_fwd, y, gc.N, gc.H[0], gc.W[0], self.ch, add=add)
+
+    def dgrad(self, dy, gc: Geom, dx, add=None):
+        """dx (coarse level gc) = bf16(add + conv4x4s2p1(dy)); add = dx accumulates onto the output convolution's data gradient."""
+        return ops.fpn_deconv_dgrad(dy, self.w_dgrad, dx, gc.N, gc.H[0], gc.W[0], self.ch, add=add)
+
+    def wgrad(self, x, g, gin, gout, ws, colsum_ws=None, x8=None, g8=None, queue=None):
+        """x: the coarse input (gout: its geometry), g: the fine output's gradient (gin) -- the conv view's (g, x) roles."""
+        ops.fpn_deconv_wgrad(x, g, self.gw, ws, gout.N, gout.H[0], gout.W[0], self.ch)
+
+    def wgrad_ws_bytes(self, gin, gout):
+        return ops.fpn_deconv_wgrad_workspace_bytes(gout.N, gout.H[0], gout.W[0], self.ch)

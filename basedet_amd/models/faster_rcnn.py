@@ -24,6 +24,7 @@ from .fpn_base import FPNDetector, _round_up
 @registers.models.register()
 class FasterRCNN(FPNDetector):
     TOP_BLOCK = "pool"
+    READS_FPN_UPSAMPLE = False      # faster_rcnn.py:30-36 builds its FPN without `upsample`: the key is ignored, as there
 
     @staticmethod
     def init_params(cfg, seed=0):

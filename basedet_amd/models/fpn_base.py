@@ -19,7 +19,7 @@ import torch
 from .. import ops
 from ..ops import Geom
 from . import params as P
-from .engine import ConvLayer, FCLayer, ParamArena
+from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena
 
 
 def _round_up(v, m):
@@ -53,8 +53,25 @@ class FPNDetector:
     """Backbone + FPN forward/backward and the BaseNet module protocol; heads and losses live in subclasses."""
 
     TOP_BLOCK = "p6p7"      # LastLevelP6P7 (RetinaNet / FCOS); "pool" = FPNP6 (Faster R-CNN)
+    READS_FPN_UPSAMPLE = True   # MODEL.FPN.UPSAMPLE (retinanet.py:57, fcos.py:53); Faster R-CNN's FPN does not read it (faster_rcnn.py:30-36)
+
+    @classmethod
+    def check_config(cls, cfg):
+        """Refuse the config variants this build does not implement (ValueError naming the key), instead of training another network."""
+        m = cfg.MODEL
+        norm = m.BACKBONE.get("NORM", "FrozenBN")
+        if norm != "FrozenBN":
+            raise ValueError(f"MODEL.BACKBONE.NORM = {norm!r} is not supported: only 'FrozenBN' is implemented")
+        fnorm = m.FPN.get("NORM", None)
+        if fnorm is not None:
+            raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} is not supported: only None (no FPN norm) is implemented")
+        if cls.READS_FPN_UPSAMPLE:
+            up = m.FPN.get("UPSAMPLE", "resize")
+            if up not in ("resize", "deconv"):
+                raise ValueError(f"MODEL.FPN.UPSAMPLE = {up!r} is not supported: use 'resize' or 'deconv'")
 
     def __init__(self, cfg, params=None, device="cuda", seed=0):
+        self.check_config(cfg)
         self.cfg = cfg
         self.device = torch.device(device)
         m = cfg.MODEL
@@ -134,6 +151,12 @@ class FPNDetector:
         for s, ci in zip(self.fpn_stages, m.BACKBONE.OUT_FEATURE_CHANNELS):
             self.lateral[s] = add(f"backbone.fpn_lateral{s}", ci, ch, 1, 1, 0, bias=True)
             self.output[s] = add(f"backbone.fpn_output{s}", ch, ch, 3, 1, 1, bias=True)
+        # MODEL.FPN.UPSAMPLE = "deconv": a learned 2x upsampling per merge, named after the coarse stage it reads (fpn_backbone.py:92-103)
+        self.fpn_deconv = self.READS_FPN_UPSAMPLE and m.FPN.get("UPSAMPLE", "resize") == "deconv"
+        self.upsample = {}
+        if self.fpn_deconv:
+            for s in self.fpn_stages[1:]:
+                self.upsample[s] = self.convs[f"backbone.fpn_upsample{s}"] = DeconvLayer(f"backbone.fpn_upsample{s}", ch, dev)
         if self.TOP_BLOCK == "p6p7":
             self.p6 = add("backbone.top_block.p6", m.FPN.TOP_BLOCK_IN_CHANNELS, ch, 3, 2, 1, bias=True)
             self.p7 = add("backbone.top_block.p7", ch, ch, 3, 2, 1, bias=True)
@@ -368,9 +391,12 @@ class FPNDetector:
         tensors, which never move after _build_layers."""
         self._fp8_apply_staged()
         if getattr(self, "_pack_table", None) is None:
-            ent = [(c.w, c.row_scale, c.w_fwd, c.w_dgrad, c.cout, c.k * c.k, c.cin) for c in self.convs.values() if c.trainable]
+            ent = [(c.w, c.row_scale, c.w_fwd, c.w_dgrad, c.cout, c.k * c.k, c.cin) for c in self.convs.values()
+                   if c.trainable and not isinstance(c, DeconvLayer)]
             self._pack_table = ops.build_pack_table(ent, self.device)
         ops.weight_pack_multi(self._pack_table)
+        for c in self.upsample.values():         # phase-major operands of their own (bd_fpn_deconv_pack)
+            c.pack()
         for c in self.convs.values():
             if (c.fp8 or c.fp8_1x1 or c.fp8_1x1_dgrad) and c.trainable:
                 c.pack_fp8()
@@ -585,6 +611,9 @@ class FPNDetector:
         for s in self.fpn_stages:
             gl = pl.blk[pl.res[s]].gout
             need = max(need, self.lateral[s].wgrad_ws_bytes(gl, gl), self.output[s].wgrad_ws_bytes(gl, gl))
+        for li, s in enumerate(self.fpn_stages[1:]):
+            gc, gf = pl.blk[pl.res[s]].gout, pl.blk[pl.res[self.fpn_stages[li]]].gout
+            need = max(need, self.upsample[s].wgrad_ws_bytes(gf, gc)) if s in self.upsample else need
         g5 = pl.blk[pl.res[self.fpn_stages[-1]]].gout
         if self.TOP_BLOCK == "p6p7":
             need = max(need, self.p6.wgrad_ws_bytes(g5, g6), self.p7.wgrad_ws_bytes(pl.g_p6r, pl.pyr.level(len(self.fpn_stages) + 1)))
@@ -702,7 +731,9 @@ class FPNDetector:
             s = st[li]
             b = pl.blk[pl.res[s]]
             self.lateral[s].forward(b.out, b.gout, b.gout, pl.lat[s])
-            if prev is not None:
+            if prev is not None and self.fpn_deconv:     # lat_s = lateral + deconv(lat_{s+1}), one rounding, in place
+                self.upsample[st[li + 1]].forward(prev, prev_geo, pl.lat[s], add=pl.lat[s])
+            elif prev is not None:
                 ops.upsample2x_add_fwd(prev, prev_geo, pl.lat[s], b.gout, self.fpn_ch)
             self.output[s].forward(pl.lat[s], b.gout, pl.pyr.level(li), pl.P, y8=pl.P8)
             prev, prev_geo = pl.lat[s], b.gout
@@ -867,7 +898,14 @@ class FPNDetector:
             self.output[s].dgrad(pl.g_P, b.gout, lvl, pl.g_lat[s], first=True, g8=pl.g_P8 if pl.g_P8_ready else None)
             if li > 0:   # gradient arriving through the top-down path from the finer level
                 sf = st[li - 1]
-                ops.upsample2x_add_bwd(pl.g_lat[sf], pl.blk[pl.res[sf]].gout, pl.g_lat[s], b.gout, self.fpn_ch, accumulate=True)
+                if self.fpn_deconv:
+                    # fpn_upsample{s} took lat_s to the finer grid: its weight gradient (side stream) reads lat_s and the finished g_lat of
+                    # the finer level, its data gradient accumulates onto g_lat_s
+                    up, gf = self.upsample[s], pl.blk[pl.res[sf]].gout
+                    self._wgrad(up, pl.lat[s], pl.g_lat[sf], gf, b.gout, ws, cws)
+                    up.dgrad(pl.g_lat[sf], b.gout, pl.g_lat[s], add=pl.g_lat[s])
+                else:
+                    ops.upsample2x_add_bwd(pl.g_lat[sf], pl.blk[pl.res[sf]].gout, pl.g_lat[s], b.gout, self.fpn_ch, accumulate=True)
             self._wgrad(self.lateral[s], b.out, pl.g_lat[s], b.gout, b.gout, ws, cws)
             # res_s gradient: first contribution for res3/res4, second (after P6) and final for res5 -> mask there
             is_top = li == nl - 1

@@ -86,6 +86,20 @@ def init_fpn(p, rng, in_channels, stages, out_ch, top_in, top_convs=True):
         p[f"backbone.top_block.{nm}.bias"] = np.zeros(out_ch, np.float32)
 
 
+def fpn_upsample_deconv(cfg):
+    """MODEL.FPN.UPSAMPLE = "deconv" on a detector whose FPN reads it (retinanet.py:57, fcos.py:53; not faster_rcnn.py:30-36)."""
+    m = cfg.MODEL
+    return m.NAME != "FasterRCNN" and m.FPN.get("UPSAMPLE", "resize") == "deconv"
+
+
+def init_fpn_upsample(p, rng, stages, out_ch):
+    """fpn_backbone.py:92-103: ConvTranspose2d(C, C, 4, 2, 1, bias=False) for every input but the first, named after its (coarse) stage;
+    weight (C_in = coarse, C_out = fine, 4, 4), msra_normal fan_in: MegEngine's fan_in of that array is shape[1] * 16.  Drawn after every
+    other parameter, so the rest of the dict is the resize config's, bit for bit."""
+    for s in stages[1:]:
+        p[f"backbone.fpn_upsample{s}.weight"] = (rng.standard_normal((out_ch, out_ch, 4, 4)) * math.sqrt(2.0 / (out_ch * 16))).astype(np.float32)
+
+
 def init_retina_head(p, rng, ch, num_anchors, num_classes, num_convs, prior_prob):
     for tower in ("cls_subnet", "bbox_subnet"):
         for i in range(num_convs):
@@ -106,6 +120,8 @@ def init_retinanet_params(cfg, seed=0, residual_gamma=None):
     init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, m.FPN.OUT_CHANNELS, m.FPN.TOP_BLOCK_IN_CHANNELS)
     na = len(m.ANCHOR.SCALES[0]) * len(m.ANCHOR.RATIOS[0])
     init_retina_head(p, rng, m.FPN.OUT_CHANNELS, na, cfg.DATA.NUM_CLASSES, m.HEAD.NUM_CONVS, m.HEAD.CLS_PRIOR_PROB)
+    if fpn_upsample_deconv(cfg):
+        init_fpn_upsample(p, rng, stages, m.FPN.OUT_CHANNELS)
     return p
 
 
@@ -136,6 +152,8 @@ def init_fcos_params(cfg, seed=0, residual_gamma=None):
     init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, m.FPN.OUT_CHANNELS, m.FPN.TOP_BLOCK_IN_CHANNELS)
     init_point_head(p, rng, m.FPN.OUT_CHANNELS, m.ANCHOR.NUM_ANCHORS, cfg.DATA.NUM_CLASSES, m.HEAD.NUM_CONVS,
                     m.HEAD.CLS_PRIOR_PROB, len(m.FPN.STRIDES))
+    if fpn_upsample_deconv(cfg):
+        init_fpn_upsample(p, rng, stages, m.FPN.OUT_CHANNELS)
     return p
 
 
@@ -197,6 +215,7 @@ def oracle_arch(cfg):
                     rcnn_box_reg=(list(m.RCNN_BOX_REG.MEAN), list(m.RCNN_BOX_REG.STD)),
                     matcher=(list(m.MATCHER.THRESHOLDS), list(m.MATCHER.LABELS), m.MATCHER.ALLOW_LOW_QUALITY),
                     rpn_beta=m.LOSSES.RPN_SMOOTH_L1_BETA, rcnn_beta=m.LOSSES.RCNN_SMOOTH_L1_BETA)
+    up = dict(upsample="deconv") if fpn_upsample_deconv(cfg) else {}
     if m.NAME in ("FCOS", "ATSS", "OTA"):
         extra = dict(atss=dict(scale=m.ANCHOR.SCALE, topk=m.ANCHOR.TOPK), sizes_of_interest=None, center_sampling_radius=None) \
             if m.NAME == "ATSS" else dict(sizes_of_interest=[list(s) for s in m.HEAD.OBJECT_SIZES_OF_INTEREST],
@@ -204,14 +223,14 @@ def oracle_arch(cfg):
         if m.NAME == "OTA":
             extra["ota"] = dict(reg_weight=m.HEAD.get("COST_REG_WEIGHTS", 1.5), candidate_k=m.HEAD.get("CANDIDATE_K", 10),
                                 center_radius=2.5, matching=m.get("MATCHING", "topk"))
-        return dict(extra, backbone=m.BACKBONE.NAME, fpn_in=list(m.BACKBONE.OUT_FEATURES), num_convs=m.HEAD.NUM_CONVS,
+        return dict(extra, **up, backbone=m.BACKBONE.NAME, fpn_in=list(m.BACKBONE.OUT_FEATURES), num_convs=m.HEAD.NUM_CONVS,
                     num_classes=cfg.DATA.NUM_CLASSES, img_mean=list(m.BACKBONE.IMG_MEAN), img_std=list(m.BACKBONE.IMG_STD),
                     strides=list(m.FPN.STRIDES), anchor_offset=m.ANCHOR.OFFSET,
                     focal_alpha=m.LOSSES.FOCAL_LOSS_ALPHA, focal_gamma=m.LOSSES.FOCAL_LOSS_GAMMA,
                     iou_loss_type=m.LOSSES.IOU_LOSS_TYPE, reg_loss_weight=m.LOSSES.REG_LOSS_WEIGHT)
     extra = dict(freeanchor=dict(mean=list(m.BOX_REG.MEAN), std=list(m.BOX_REG.STD), iou_thresh=m.BUCKET.BOX_IOU_THRESH,
                                  bucket=m.BUCKET.BUCKET_SIZE)) if m.NAME == "FreeAnchor" else {}
-    return dict(extra, backbone=m.BACKBONE.NAME, fpn_in=list(m.BACKBONE.OUT_FEATURES), num_convs=m.HEAD.NUM_CONVS,
+    return dict(extra, **up, backbone=m.BACKBONE.NAME, fpn_in=list(m.BACKBONE.OUT_FEATURES), num_convs=m.HEAD.NUM_CONVS,
                 num_classes=cfg.DATA.NUM_CLASSES, img_mean=list(m.BACKBONE.IMG_MEAN), img_std=list(m.BACKBONE.IMG_STD),
                 strides=list(m.FPN.STRIDES), anchor_scales=[list(s) for s in m.ANCHOR.SCALES],
                 anchor_ratios=[list(r) for r in m.ANCHOR.RATIOS], anchor_offset=m.ANCHOR.OFFSET,

@@ -23,6 +23,13 @@ class RetinaNet(FPNDetector):
     def init_params(cfg, seed=0):
         return P.init_retinanet_params(cfg, seed)
 
+    @classmethod
+    def check_config(cls, cfg):
+        super().check_config(cfg)
+        if not cfg.MODEL.HEAD.get("WITH_NORM", True):
+            # retina_head.py:54-61: WITH_NORM = False drops the towers' ReLUs, which this head does not implement
+            raise ValueError("MODEL.HEAD.WITH_NORM = False is not supported for the RetinaNet family: only True (the default) is implemented")
+
     # ---- construction ------------------------------------------------------------------------------------
     def _build_head(self, add, params):
         """RetinaNetHead (layers/head/retina_head.py:9-70): two 4-conv towers + cls_score / bbox_pred, weights shared

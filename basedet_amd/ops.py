@@ -231,6 +231,34 @@ def conv2d_wgrad_bias(d, x, g, dw, dbias, ws, row_scale=None, accumulate=False):
     return dw
 
 
+def fpn_deconv_pack(w, C, w_fwd, w_dgrad):
+    """fp32 master [C][4][4][C] (conv view, OHWI) -> the bf16 operands of fpn_deconv_fwd / fpn_deconv_dgrad."""
+    check(L().bd_fpn_deconv_pack(ptr(w), C, ptr(w_fwd), ptr(w_dgrad), stream_ptr()), "bd_fpn_deconv_pack")
+
+
+def fpn_deconv_fwd(x, w_fwd, y, N, Hc, Wc, C, add=None):
+    """y [N][2Hc][2Wc][C] = bf16(add + conv_transpose(x [N][Hc][Wc][C], W, 4x4 / stride 2 / pad 1)); add may be y itself."""
+    check(L().bd_fpn_deconv_fwd(ptr(x), ptr(w_fwd), ptr(add), ptr(y), N, Hc, Wc, 2 * Hc, 2 * Wc, C, stream_ptr()), "bd_fpn_deconv_fwd")
+    return y
+
+
+def fpn_deconv_dgrad(dy, w_dgrad, dx, N, Hc, Wc, C, add=None):
+    """dx [N][Hc][Wc][C] = bf16(add + conv4x4s2p1(dy [N][2Hc][2Wc][C], W)); add may be dx itself."""
+    check(L().bd_fpn_deconv_dgrad(ptr(dy), ptr(w_dgrad), ptr(add), ptr(dx), N, Hc, Wc, 2 * Hc, 2 * Wc, C, stream_ptr()), "bd_fpn_deconv_dgrad")
+    return dx
+
+
+def fpn_deconv_wgrad_workspace_bytes(N, Hc, Wc, C):
+    return int(L().bd_fpn_deconv_wgrad_workspace_bytes(N, Hc, Wc, C))
+
+
+def fpn_deconv_wgrad(x, dy, dw, ws, N, Hc, Wc, C, accumulate=False):
+    """dw [C][4][4][C] fp32 (+)= the weight gradient of fpn_deconv_fwd (fixed-order split sums: reproducible)."""
+    check(L().bd_fpn_deconv_wgrad(ptr(x), ptr(dy), ptr(dw), int(accumulate), ptr(ws), ws.numel() * ws.element_size(), N, Hc, Wc,
+                                  2 * Hc, 2 * Wc, C, stream_ptr()), "bd_fpn_deconv_wgrad")
+    return dw
+
+
 def stem_conv7x7_fwd(N, H, W, x_halo, w_stem, bias, y):
     check(L().bd_stem_conv7x7_fwd(N, H, W, ptr(x_halo), ptr(w_stem), ptr(bias), ptr(y), stream_ptr()), "bd_stem_conv7x7_fwd")
     return y

@@ -275,6 +275,25 @@ int bd_upsample2x_add_bwd(const void* dlat, int64_t lat_pix_per_img, int64_t lat
                           int64_t top_pix_per_img, int64_t top_off, int N, int H, int W, int C,
                           int accumulate, bd_stream_t stream);
 
+/* FPN learned top-down upsampling, MODEL.FPN.UPSAMPLE = "deconv" (fpn_backbone.py:92-103,131-138): M.ConvTranspose2d(C, C, 4, stride 2,
+ * padding 1, bias=False) between two dense NHWC bf16 levels, x [N][Hc][Wc][C] (coarse) and y [N][Hf][Wf][C] (fine).  Every entry point
+ * requires C % 64 == 0, Hf == 2 Hc and Wf == 2 Wc (else BD_EINVAL with a message) and tensors < 2 GB.
+ * bd_fpn_deconv_pack: w = the fp32 master [C][4][4][C] = the reference's (C_coarse, C_fine, 4, 4) weight permuted to OHWI (the
+ * fine -> coarse Conv2d(k4, s2, p1) it is the OIHW weight of); writes the bf16 operands of the two data kernels, 16 C^2 elements each. */
+int bd_fpn_deconv_pack(const float* w, int C, void* w_fwd, void* w_dgrad, bd_stream_t stream);
+/* fpn_backbone.py:131-138: y = bf16(add + conv_transpose(x, W)); add may be NULL or equal to y (in place: the merged lateral). */
+int bd_fpn_deconv_fwd(const void* x, const void* w_fwd, const void* add, void* y, int N, int Hc, int Wc, int Hf, int Wf, int C,
+                      bd_stream_t stream);
+/* its data gradient (fpn_backbone.py:131-138 under GradManager.backward): dx = bf16(add + conv4x4s2p1(dy, W)); add may be NULL or
+ * equal to dx (accumulate onto the output convolution's data gradient of the coarse lateral). */
+int bd_fpn_deconv_dgrad(const void* dy, const void* w_dgrad, const void* add, void* dx, int N, int Hc, int Wc, int Hf, int Wf, int C,
+                        bd_stream_t stream);
+/* its weight gradient (fpn_backbone.py:92-103,131-138): dw [C][4][4][C] fp32 (the master's layout) (+)= sum x^T dy per tap; split
+ * over pixels with fp32 slabs in ws, reduced in a fixed order (bitwise reproducible).  accumulate != 0 adds to dw. */
+size_t bd_fpn_deconv_wgrad_workspace_bytes(int N, int Hc, int Wc, int C);
+int bd_fpn_deconv_wgrad(const void* x, const void* dy, float* dw, int accumulate, void* ws, size_t ws_bytes, int N, int Hc, int Wc,
+                        int Hf, int Wf, int C, bd_stream_t stream);
+
 /* elementwise helpers on bf16 buffers of n elements (n % 8 == 0) */
 int bd_relu_bf16(const void* x, void* y, int64_t n, bd_stream_t stream);
 /* y = (mask > 0 ? g : 0) [+ add] */
