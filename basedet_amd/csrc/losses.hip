@@ -17,21 +17,29 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// log(1 + e) for e = exp(-|x|) in (0, 1], given the logarithm of the ROUNDED sum 1 + e: that keeps only e's bits above 2^-24, so once
+// e < 2^-10 its relative error grows (to 100 % for |x| > 17) and reaches the gradient of every confidently classified logit, whose
+// q^2 (q + 2 ce (1 - q)) has ce ~ q there.  Below 2^-10 the series e - e^2/2 + e^3/3 is exact to fp32 (next term < 2^-42 relative).
+__device__ __forceinline__ float log1p_small(float e, float log_rounded) {
+    return e < 0x1p-10f ? e * (1.f - e * (0.5f - e * 0.33333334f)) : log_rounded;
+}
+
 // sigmoid_focal_loss (layers/losses/sigmoid_focal_loss.py:30-35) + binary_cross_entropy (cross_entropy.py:26)
 __device__ __forceinline__ void focal_elem(float x, bool t, float alpha, float gamma, float& loss, float& grad) {
     // hardware exp/log/rcp (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp): the kernel is HBM-bound only if the
-    // per-logit VALU work stays small; log(1 + e) with e in (0, 1] needs no log1p (absolute error < 1e-7)
+    // per-logit VALU work stays small; log(1 + e) with e in (0, 1] is the log of the rounded sum, corrected below 2^-10 (log1p_small)
     const float e = __expf(-fabsf(x));
-    const float l1p = __logf(1.f + e);
+    const float l1p = log1p_small(e, __logf(1.f + e));
     const float ls_pos = fminf(x, 0.f) - l1p;     // logsigmoid(x)
     const float ls_neg = fminf(-x, 0.f) - l1p;    // logsigmoid(-x)
     const float inv = __frcp_rn(1.f + e);
     const float p = x >= 0.f ? inv : e * inv;     // sigmoid(x)
+    const float pn = x >= 0.f ? e * inv : inv;    // sigmoid(-x): 1 - p without the cancellation that 1.f - p suffers for large x
     const float ce = t ? -ls_pos : -ls_neg;
-    const float pt = t ? 1.f - p : p;             // t*(1-p) + (1-t)*p
+    const float pt = t ? pn : p;                  // t*(1-p) + (1-t)*p
     const float a = alpha >= 0.f ? (t ? alpha : 1.f - alpha) : 1.f;
-    const float dce = p - (t ? 1.f : 0.f);
-    const float dpt = (t ? -1.f : 1.f) * p * (1.f - p);
+    const float dce = t ? -pn : p;                // p - t
+    const float dpt = (t ? -1.f : 1.f) * (e * inv * inv);     // -+ p (1 - p)
     float mod, dmod;
     if (gamma == 2.f) { mod = pt * pt; dmod = 2.f * pt; }
     else if (gamma == 0.f) { mod = 1.f; dmod = 0.f; }
@@ -52,7 +60,7 @@ __device__ __forceinline__ void focal_g2(float x, float z, float a_signed, float
     const float t1 = 1.f + e;
     const float inv = __builtin_amdgcn_rcpf(t1);
     const float q = z >= 0.f ? inv : e * inv;
-    const float ce = __builtin_amdgcn_logf(t1) * 0.6931471805599453f + fmaxf(z, 0.f);
+    const float ce = log1p_small(e, __builtin_amdgcn_logf(t1) * 0.6931471805599453f) + fmaxf(z, 0.f);
     const float q2 = q * q;
     loss = a_abs * ce * q2;
     grad = a_signed * q2 * (q + 2.f * ce * (1.f - q));
@@ -68,7 +76,8 @@ __device__ __forceinline__ void focal_g2_neg2(float x0, float x1, float a, f32x2
     const f32x2_l q = {x0 >= 0.f ? inv[0] : einv[0], x1 >= 0.f ? inv[1] : einv[1]};
     const f32x2_l l2 = {__builtin_amdgcn_logf(t1[0]), __builtin_amdgcn_logf(t1[1])};
     const f32x2_l mz = {fmaxf(x0, 0.f), fmaxf(x1, 0.f)};
-    const f32x2_l ce = l2 * 0.6931471805599453f + mz;
+    const f32x2_l ln = l2 * 0.6931471805599453f;
+    const f32x2_l ce = (f32x2_l){log1p_small(e[0], ln[0]), log1p_small(e[1], ln[1])} + mz;
     const f32x2_l aq2 = q * q * a;
     loss = aq2 * ce;
     grad = aq2 * ((ce + ce) * (1.f - q) + q);

@@ -38,3 +38,19 @@ def pack_weights(ops, w_oihw, row_scale=None):
     rs = None if row_scale is None else row_scale.cuda()
     ops.weight_pack(w, rs, wf, wd, co, r * s, ci)
     return wf, wd
+
+
+def bf16_ulps(got, ref):
+    """Distance in bf16 steps between a bf16 tensor and a high-precision reference rounded to bf16 (elementwise, int32).
+    The bit patterns are mapped to a monotone integer line on which +0 and -0 coincide."""
+    def key(t):
+        v = t.contiguous().view(torch.int16).to(torch.int32)
+        return torch.where(v < 0, -(v & 0x7FFF), v)
+    return (key(got) - key(ref.to(torch.bfloat16))).abs()
+
+
+def f32_ulps(got, ref):
+    """Distance of fp32 values from a float64 reference in units of the fp32 spacing at the reference (elementwise, float64)."""
+    r = ref.double()
+    e = torch.frexp(r.float().abs().clamp_min(torch.finfo(torch.float32).tiny))[1]
+    return (got.double() - r).abs() / torch.ldexp(torch.ones_like(r), (e - 24).to(torch.int32))
