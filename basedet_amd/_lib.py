@@ -28,6 +28,7 @@ class ConvDesc(C.Structure):
         ("in_off", C.c_int32 * BD_MAX_SEGS), ("out_off", C.c_int32 * BD_MAX_SEGS),
         ("in_pix_per_img", C.c_int32), ("out_pix_per_img", C.c_int32),
         ("route", C.c_int32 * 4), ("sr_seed", C.c_uint32),        # per-call kernel routing / e5m2 rounding seed (0 = the library's choice)
+        ("gskip", C.c_int32), ("gskip_ws", C.c_void_p), ("gskip_ws_bytes", C.c_size_t),   # gradient-skip hint + dgrad scratch (0 = dense)
     ]
 
 
@@ -48,6 +49,7 @@ SIGNATURES = {
     "bd_probe_kernel_clock": (_I, [C.c_char_p, _I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bd_conv2d_fwd": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
     "bd_conv2d_dgrad": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
+    "bd_conv2d_dgrad_gskip_bytes": (_Z, [_D]),
     "bd_conv2d_fwd_bits": (_I, [_D, _P, _P, _P, _P, _P, _P, _I, _P]),
     "bd_conv2d_fwd_ex": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "bd_conv2d_dgrad_ex": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),

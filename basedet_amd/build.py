@@ -18,6 +18,7 @@ SOURCES = {
     "conv_igemm.hip": [],
     "conv3x3.hip": [],
     "conv3x3_pp.hip": [],
+    "gskip.hip": [],
     "conv3x3_pp128.hip": [],
     "conv1x1.hip": [],
     "conv1x1_ring.hip": [],

@@ -58,6 +58,12 @@ struct PParams {
     float inv_ppi;           // 1 / patches_per_img (the patch indices are < 2^24: exact quotients by a float multiply and one correction)
     PSeg seg[MAX_SEG];
     float* gn_part;          // GNS instance only: per (patch, group of 8 channels) the (sum, sum of squares) of the fp32 results, [patch][32][2]
+    // SPARSE instance only (bd_conv_desc.gskip, gskip.hip): the tiles are cut from the live patches sp_list[0 .. *sp_count) in that order; the
+    // other patches (sp_live[q] == 0) are written as +0 behind the tiles, by every workgroup, or left as they are (sp_keep_dead: in-place accumulate)
+    const int* sp_live;
+    const int* sp_list;
+    const int* sp_count;
+    int sp_keep_dead;
 };
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -96,15 +102,15 @@ __device__ unsigned long long g_pp_clk[2];           // bd_probe_kernel_clock("c
 // and lane 0 of the row stores the pair -- gn_stats_final_kernel (norm.hip) then sums a level's patches exactly as it sums 128-pixel slots.
 // A separate instantiation: the plain forward / data-gradient instances are untouched.  (Round 5 built this on the 253-register kernel: the
 // sums spilled INSIDE the K loop and the launch lost what the statistics pass saved; the 16 address registers found in round 6 made room.)
-template <int MODE, bool GNS = false>
+template <int MODE, bool GNS = false, bool SPARSE = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if ((int)blockIdx.x >= p.main_grid) {       // tail tiles of a grid of 256 k + r pixel tiles (see bd_conv3x3_pp_launch): 4 r short workgroups
+    if (!SPARSE && (int)blockIdx.x >= p.main_grid) {       // tail tiles of a grid of 256 k + r pixel tiles (see bd_conv3x3_pp_launch): 4 r short workgroups
         pp128::body<MODE, TAIL_CO>(p, smem, (int)blockIdx.x - p.main_grid, (int)gridDim.x - p.main_grid, p.total_patches, p.tail_end,
                                    (p.CO + TAIL_CO - 1) / TAIL_CO);
         return;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) bd_clk_mark(g_pp_clk, false);
+    if (!SPARSE && blockIdx.x == 0 && threadIdx.x == 0) bd_clk_mark(g_pp_clk, false);     // (SPARSE: workgroup 0 may have no tile)
     unsigned char* wbuf = smem;                                   // [3][W_SLOT]
     unsigned char* xbuf = smem + W_BYTES;                         // [X_BYTES]
     float* sbias = reinterpret_cast<float*>(smem + W_BYTES + X_BYTES);      // [256]
@@ -137,6 +143,50 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
     const int pt_step = p.main_grid / p.n_tiles;
     const int co0 = ct * TILE_CO;
 
+    // SPARSE: +0 into the dead patches (stores only).  Workgroups without a live tile share them -- patch z0 + k zn, k = 0, 1, .. -- unless
+    // every workgroup has a tile; a wave takes 64 k's at a time, one flag per lane
+    auto zero_dead = [&](int z0, int zn) {
+        if (p.sp_keep_dead) return;
+        const int cpp = p.CO >> 3;
+        const int items = PH * PW * cpp;
+        for (int k0 = 0; z0 + k0 * zn < p.total_patches; k0 += 512) {
+            const int k = k0 + wave * 64 + lane;
+            const int q = z0 + k * zn;
+            const bool dead = q < p.total_patches && p.sp_live[q] == 0;
+            unsigned long long m = __ballot(dead);
+            while (m) {
+                const int l = __builtin_ctzll(m);
+                m &= m - 1;
+                const int qq = z0 + (k0 + wave * 64 + l) * zn;
+                const int n = qq / p.patches_per_img, rem = qq - n * p.patches_per_img;
+                int sgi = 0;
+#pragma unroll
+                for (int z = 1; z < MAX_SEG; ++z)
+                    if (z < p.nseg && rem >= p.seg[z].patch_start) sgi = z;
+                const int H = p.seg[sgi].H, W = p.seg[sgi].W, pwn = p.seg[sgi].pw;
+                const int local = rem - p.seg[sgi].patch_start, by = local / pwn, bx = local - by * pwn;
+                const long long img = (long long)n * p.dst_ppi + p.seg[sgi].dst_off;
+                for (int i = lane; i < items; i += 64) {
+                    const int px = i / cpp, ch = i - px * cpp;
+                    const int y = by * PH + px / PW, x = bx * PW + (px & (PW - 1));
+                    if (y < H && x < W)
+                        *reinterpret_cast<u32x4_t*>(p.dst + (img + (long long)y * W + x) * p.CO + ch * 8) = (u32x4_t){0u, 0u, 0u, 0u};
+                }
+            }
+        }
+    };
+    int n_px = p.px_tiles, n_live = p.total_patches;          // pixel tiles / patches this launch computes
+    int z_first = 0;                                           // SPARSE: the first workgroup without a tile (main_grid: none)
+    if constexpr (SPARSE) {
+        n_live = __builtin_amdgcn_readfirstlane(*p.sp_count);
+        n_px = (n_live + NPATCH - 1) / NPATCH;
+        z_first = n_px * p.n_tiles < p.main_grid ? n_px * p.n_tiles : p.main_grid;
+        if (pt >= n_px) {                                      // no live tile for this workgroup: bid >= z_first
+            zero_dead(bid - z_first, p.main_grid - z_first);
+            return;
+        }
+    }
+
     // ---- activation staging: chunk id c = tid + 512 k -> LDS row (tid >> 3) + 64 k, 16-byte chunk tid & 7 ----
     // buffer loads: 32-bit per-lane byte offset + scalar K-block offset, and an offset past the end of the tensor (X_NONE) returns
     // zeros: halo / out-of-image rows need no predication and no 64-bit per-lane addresses
@@ -153,9 +203,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
     auto build_table = [&](int k0) {
         const int k = k0 + (lane >> 2);
         const int ptile = pt_first + k * pt_step;
-        const int pid = ptile * NPATCH + (lane & (NPATCH - 1));
+        int pid = ptile * NPATCH + (lane & (NPATCH - 1));
+        if (SPARSE) pid = (ptile < n_px && pid < n_live) ? p.sp_list[pid] : p.total_patches;
         int vH = 0, vW = 0, vy = 0, vx = 0, vs = 0, vd = 0;
-        if (ptile < p.px_tiles && pid < p.total_patches) {
+        if (ptile < n_px && pid < p.total_patches) {
             const int n = pp_div(pid, p.patches_per_img, p.inv_ppi);
             const int rem = pid - n * p.patches_per_img;
             // level search as selects over the (scalar) level table: no per-lane table fetch
@@ -349,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
 #endif
     for (;;) {
     const int pt_next = pt + pt_step;
-    const bool more = pt_next < p.px_tiles;
+    const bool more = pt_next < n_px;
     int n_oy0 = 0, n_px0 = 0, n_H = 0, n_W = 0, n_dst = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
@@ -660,7 +711,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
     PP_FENCE();
     PP_STAMP();                    // next K loop starts
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) bd_clk_mark(g_pp_clk, true);
+    if constexpr (SPARSE) {
+        if (z_first == p.main_grid) zero_dead(bid, p.main_grid);
+    }
+    if (!SPARSE && blockIdx.x == 0 && threadIdx.x == 0) bd_clk_mark(g_pp_clk, true);
 #ifdef BD_PP_STAMP
     if (st_on) { g_pp_stamp[63] = __builtin_amdgcn_s_memrealtime(); g_pp_stamp[61] = __builtin_amdgcn_s_memtime(); }
     if (threadIdx.x == 0 && blockIdx.x < 1024) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); g_pp_span[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime(); }
@@ -673,6 +727,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
 BD_KNOB int g_pp_tail_split = 1;     // bd_conv_desc.route[1] bit 13 clears it
 BD_KNOB int g_pp_persistent = 1;     // bit 14 clears it: one workgroup per tile
 extern BD_KNOB int g_patch_pp;       // 0 = never, 1 = where the makespan estimate favours it, 2 = wherever the shape allows (default)
+int bd_gskip_patches(const bd_conv_desc* d, int ph, int pw);
+void bd_gskip_scan(const bd_conv_desc* d, const void* g, int ph, int pw, int* mask, hipStream_t stream);
+void bd_gskip_compact(const bd_conv_desc* d, int ph, int pw, const int* mask, int* live, int* list, int* count, hipStream_t stream);
+
+// scratch of a gradient-skipping data gradient (bd_conv_desc.gskip): per 4 x 16 patch of g its scan mask, per output patch its live flag,
+// the live list, the live count
+extern "C" size_t bd_conv2d_dgrad_gskip_bytes(const bd_conv_desc* d) {
+    if (!d || d->nseg < 1 || d->nseg > BD_MAX_SEGS || !(d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1)) return 0;
+    return ((size_t)3 * bd_gskip_patches(d, PH, PW) + 4) * sizeof(int);
+}
+
 static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const void* w, const float* bias, const void* add,
                      const void* mask, void* dst, int flags, float* gn_part, hipStream_t stream) {
     PParams p{};
@@ -710,7 +775,12 @@ static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const voi
     int px_tiles = cdiv(p.total_patches, NPATCH);
     p.tail_end = p.total_patches;
     const int num_cus = bd_num_cus();
-    if (g_pp_tail_split && !gn_part && p.n_tiles == 1 && px_tiles > num_cus) {          // (the tail body leaves no GroupNorm statistics)
+    // Gradient skip (bd_conv_desc.gskip; conv2d_dgrad_impl has checked the scratch): a data gradient whose dead output patches are +0
+    // (overwrite, BD_EPI_MASK) or keep dx (in-place accumulate without a gate).  Any other epilogue walks every patch.
+    const bool in_place = (flags & BD_EPI_ADD_BEFORE) && add && add == dst;
+    const bool sparse = mode == 1 && d->gskip && !gn_part && !(flags & BD_EPI_ADD_AFTER) &&
+                        (!((flags & BD_EPI_ADD_BEFORE) && add) || (in_place && !(flags & BD_EPI_MASK)));
+    if (g_pp_tail_split && !sparse && !gn_part && p.n_tiles == 1 && px_tiles > num_cus) {          // (the tail body leaves no GroupNorm statistics)
         const int r = px_tiles % num_cus;
         if (r > 0 && r * (TILE_CO / TAIL_CO) <= num_cus) {
             px_tiles -= r;
@@ -736,9 +806,21 @@ static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const voi
     }
     BD_ONCE_PER_DEVICE(
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  LDS_BYTES));
     bd_note_kernel("conv3x3_pp_kernel");
-    if (gn_part) {
+    if (sparse) {
+        // three launches on the call's stream: scan g, compact the live output patches (one workgroup), then the tiles of the live patches and
+        // the +0 stores of the dead ones (the grid is the dense plan's: workgroups past the live tiles only store zeros)
+        int* mk = (int*)d->gskip_ws;
+        const int tot = p.total_patches;
+        p.sp_live = mk + tot; p.sp_list = mk + 2 * tot; p.sp_count = mk + 3 * tot;
+        p.sp_keep_dead = in_place ? 1 : 0;
+        bd_gskip_scan(d, src, PH, PW, mk, stream);
+        bd_gskip_compact(d, PH, PW, mk, mk + tot, mk + 2 * tot, mk + 3 * tot, stream);
+        hipLaunchKernelGGL((conv3x3_pp_kernel<1, false, true>), dim3(p.main_grid), dim3(512), LDS_BYTES, stream, p);
+    } else if (gn_part) {
         BD_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         hipLaunchKernelGGL((conv3x3_pp_kernel<0, true>), dim3(p.main_grid), dim3(512), LDS_BYTES, stream, p);
     } else if (mode == 0) hipLaunchKernelGGL((conv3x3_pp_kernel<0>), dim3(p.main_grid + tail_wgs), dim3(512), LDS_BYTES, stream, p);

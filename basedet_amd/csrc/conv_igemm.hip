@@ -608,6 +608,11 @@ static int conv2d_dgrad_impl(const bd_conv_desc* d, const void* g, const void* w
                              const unsigned* maskbits, void* dx, void* dx8, float q_scale, int flags, bd_stream_t stream) {
     if (int e = check_desc(d)) return e;
     BD_REQUIRE(g && w_packed_t && dx, "conv2d_dgrad: null pointer");
+    if (d->gskip && is_3x3s1(d)) {
+        const size_t need = bd_conv2d_dgrad_gskip_bytes(d);
+        BD_REQUIRE(d->gskip_ws && d->gskip_ws_bytes >= need, "conv2d_dgrad: gskip scratch %zu < required %zu bytes (or NULL)",
+                   (size_t)d->gskip_ws_bytes, need);
+    }
     if (d->stride == 1) flags &= ~BD_EPI_SPARSE;          // every pixel of a stride-1 data gradient is reached
     BD_REQUIRE(d->Cout % 8 == 0, "conv2d_dgrad: Cout=%d must be a multiple of 8 (pad the gradient)", d->Cout);
     BD_REQUIRE(d->Cin % 8 == 0, "conv2d_dgrad: Cin=%d must be a multiple of 8", d->Cin);

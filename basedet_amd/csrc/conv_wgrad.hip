@@ -352,7 +352,10 @@ int bd_wgrad3x3_splits(const bd_conv_desc* d, int* total_patches_out, int* patch
 int bd_wgrad3x3_launch(const bd_conv_desc* d, const void* x, const void* g, float* slab, float* csum, int* splits_out, hipStream_t stream);
 bool bd_wgrad3x3r_eligible(const bd_conv_desc* d);
 size_t bd_wgrad3x3r_slab_bytes(const bd_conv_desc* d, int* splits_out);
-int bd_wgrad3x3r_launch(const bd_conv_desc* d, const void* x, const void* g, float* slab, float* csum, int* splits_out, hipStream_t stream);
+int bd_wgrad3x3r_launch(const bd_conv_desc* d, const void* x, const void* g, float* slab, float* csum, const int* gflags, int* splits_out,
+                        hipStream_t stream);
+int bd_wgrad3x3r_gskip_patches(const bd_conv_desc* d);
+void bd_gskip_scan(const bd_conv_desc* d, const void* g, int ph, int pw, int* mask, hipStream_t stream);
 void bd_wgrad3x3r_entry(const bd_conv_desc* d, BdRedEntry* e);
 bool bd_wgrad1x1r_eligible(const bd_conv_desc* d);
 size_t bd_wgrad1x1r_slab_bytes(const bd_conv_desc* d, int* splits_out);
@@ -379,10 +382,27 @@ void bd_wgrad_reduce_launch(const float* slab, int splits, long long n, int row_
     launch_batch(&e, 1, stream);
 }
 
+namespace {
+size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+// patches of the gradient-skip flags a hinted descriptor's ring walk reads (0: no sparse walk for it)
+int gskip_patches(const bd_conv_desc* d) {
+    return d->gskip && bd_wgrad3x3r_eligible(d) ? bd_wgrad3x3r_gskip_patches(d) : 0;
+}
+size_t wgrad_ws_base(const bd_conv_desc* d);
+}  // namespace
+
+// gskip (include/basedet_hip.h): the flags of the sparse ring walk sit behind the slabs, at align256(wgrad_ws_base(d))
 extern "C" size_t bd_conv2d_wgrad_workspace_bytes(const bd_conv_desc* d) {
     BdRouteScope rs__(d);
     if (rs__.rc != BD_OK) return 0;
     if (!d || d->nseg < 1 || d->nseg > BD_MAX_SEGS) return 0;
+    const size_t base = wgrad_ws_base(d);
+    const int gp = gskip_patches(d);
+    return gp > 0 ? align256(base) + (size_t)gp * sizeof(int) : base;
+}
+
+namespace {
+size_t wgrad_ws_base(const bd_conv_desc* d) {
     const Plan pl = make_plan(d);
     size_t splits = (size_t)pl.splits;
     if (is_3x3s1(d)) {
@@ -404,9 +424,6 @@ extern "C" size_t bd_conv2d_wgrad_workspace_bytes(const bd_conv_desc* d) {
     }
     return bytes;
 }
-
-namespace {
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 }  // namespace
 
 extern "C" size_t bd_colsum_workspace_bytes(int C);
@@ -533,7 +550,12 @@ static int wgrad_impl(const bd_conv_desc* d, const void* x, const void* g, const
     if (g_wgrad_use_3x3 && g_wgrad_use_ring && bd_wgrad3x3r_eligible(d)) {
         int splitsr = 1;
         bd_note_kernel("conv_wgrad3x3_ring_kernel");
-        bd_wgrad3x3r_launch(d, x, g, (float*)ws, dbias ? (float*)extra : nullptr, &splitsr, (hipStream_t)stream);
+        int* gflags = nullptr;
+        if (gskip_patches(d) > 0) {            // gradient skip: scan g in the ring's 8 x 8 patches, then walk only the flagged ones
+            gflags = (int*)((unsigned char*)ws + align256(wgrad_ws_base(d)));
+            bd_gskip_scan(d, g, 8, 8, gflags, (hipStream_t)stream);
+        }
+        bd_wgrad3x3r_launch(d, x, g, (float*)ws, dbias ? (float*)extra : nullptr, gflags, &splitsr, (hipStream_t)stream);
         BD_CHECK_LAUNCH("bd_conv2d_wgrad(3x3 ring)");
         BdRedEntry e{};
         bd_wgrad3x3r_entry(d, &e);

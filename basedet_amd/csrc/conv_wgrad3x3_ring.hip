@@ -35,6 +35,7 @@ constexpr int NSTAGE = 5;                        // (stage (t + 3) % 5 was last 
 constexpr int LDS_BYTES = NSTAGE * STAGE;        // 148 480 B: one workgroup per CU
 constexpr int REGS = 36;                         // f32x4 accumulators per lane = 1 KiB rows per wave in the slab
 constexpr unsigned X_NONE = 0x80000000u;
+constexpr int LIST_MAX = 3072;                   // SPARSE: live-patch list of one split in LDS behind the ring (12 KiB; longer splits stay dense)
 
 typedef __attribute__((address_space(3))) void lds_void_rk_t;
 
@@ -45,6 +46,7 @@ struct RParams {
     const bf16_raw* g;
     float* slab;             // [splits * tiles][8 waves][36][64 lanes] f32x4
     float* csum;             // optional [splits][Cout] partial column sums of g (bias gradient), written by the ci_tile 0 workgroups
+    const int* gflags;       // SPARSE instance: per 8 x 8 patch of g, nonzero iff it holds a nonzero bit (gskip.hip)
     int Cin, Cout, N, nseg;
     int in_ppi, out_ppi;
     unsigned x_bytes, g_bytes;
@@ -74,6 +76,9 @@ __device__ __forceinline__ void rk_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned l
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds" : : "v"(voff), "s"(lds_addr), "s"(rsrc), "s"(soff) : "memory");
 }
 
+// SPARSE (bd_conv_desc.gskip): the same split plan and the same per-split patch order, but a split walks only its patches whose g holds a
+// nonzero bit (all others add exact zeros): the bits of the slabs, and so of dW and the bias gradient, are those of the dense walk.
+template <bool SPARSE>
 __global__ __launch_bounds__(512) void conv_wgrad3x3_ring_kernel(const RParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -94,7 +99,30 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_ring_kernel(const RParams p
     const int pbeg = split * p.patches_per_split;
     int pend = pbeg + p.patches_per_split;
     if (pend > p.total_patches) pend = p.total_patches;
-    const int nsteps = pend > pbeg ? pend - pbeg : 0;
+    int nsteps = pend > pbeg ? pend - pbeg : 0;
+    int* live_list = reinterpret_cast<int*>(smem + LDS_BYTES);          // SPARSE: offsets (from pbeg) of this split's live patches, in order
+    if constexpr (SPARSE) {
+        __shared__ int wsum[8];
+        int base = 0;
+        for (int c0 = 0; c0 < nsteps; c0 += 512) {
+            const int i = c0 + tid;
+            const bool lv = i < nsteps && p.gflags[pbeg + i] != 0;
+            const unsigned long long bal = __ballot(lv);
+            const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+            if (lane == 0) wsum[wave] = __popcll(bal);
+            __syncthreads();
+            int off = base, tot = 0;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                off += w < wave ? wsum[w] : 0;
+                tot += wsum[w];
+            }
+            if (lv) live_list[off + pre] = i;
+            base += tot;
+            __syncthreads();
+        }
+        nsteps = base;
+    }
 
     // ---- DMA lane constants.  X piece pc = LDS rows 8 pc .. 8 pc + 7 (row R = image pixel (R / 10, R % 10)), lane -> row lane >> 3,
     // 16-byte position lane & 7, source chunk = position ^ 2 * ((ix >> 1) & 3).  This wave owns pieces wave and wave + 8 (< 13).
@@ -156,7 +184,12 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_ring_kernel(const RParams p
         c_rows = (sg.H + 7) >> 3;
         level_vectors();
     };
+    int c_li = 0;                     // SPARSE: list position of the cursor
     auto advance = [&]() {
+        if constexpr (SPARSE) {
+            if (++c_li < nsteps) seek(pbeg + __builtin_amdgcn_readfirstlane(live_list[c_li]));
+            return;
+        }
         if (++c_bx < sg.pw) return;
         c_bx = 0;
         if (++c_by < c_rows) return;
@@ -303,7 +336,7 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_ring_kernel(const RParams p
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #endif
     if (nsteps > 0) {
-        seek(pbeg);
+        seek(SPARSE ? pbeg + __builtin_amdgcn_readfirstlane(live_list[0]) : pbeg);
 #pragma unroll 1
         for (int d = 0; d < DEPTH; ++d) {          // prologue: DEPTH whole steps in flight
             issue_x(d, d >= nsteps);
@@ -447,10 +480,20 @@ size_t bd_wgrad3x3r_slab_bytes(const bd_conv_desc* d, int* splits_out) {
     return (size_t)pl.splits * pl.tiles * 8 * REGS * 1024;
 }
 
-// writes the slabs (and, with csum, [splits][Cout] partial column sums of g); the caller reduces with bd_wgrad3x3r_reduce
-int bd_wgrad3x3r_launch(const bd_conv_desc* d, const void* x, const void* g, float* slab, float* csum, int* splits_out, hipStream_t stream) {
+// patches of the gradient-skip flags this layer's sparse walk reads (bd_gskip_scan in 8 x 8 tiles), 0 if it stays dense (a split longer
+// than the LDS list)
+int bd_wgrad3x3r_gskip_patches(const bd_conv_desc* d) {
+    const RPlan pl = ring_plan(d);
+    return pl.per <= LIST_MAX ? pl.total : 0;
+}
+
+// writes the slabs (and, with csum, [splits][Cout] partial column sums of g); the caller reduces with bd_wgrad3x3r_reduce.
+// gflags != NULL: the SPARSE walk over the patches bd_gskip_scan flagged (same slabs, bit for bit)
+int bd_wgrad3x3r_launch(const bd_conv_desc* d, const void* x, const void* g, float* slab, float* csum, const int* gflags, int* splits_out,
+                        hipStream_t stream) {
     RParams p{};
     const RPlan pl = ring_plan(d);
+    p.gflags = gflags;
     p.x = (const bf16_raw*)x; p.g = (const bf16_raw*)g; p.slab = slab; p.csum = csum;
     p.Cin = d->Cin; p.Cout = d->Cout; p.N = d->N; p.nseg = d->nseg;
     p.in_ppi = d->in_pix_per_img; p.out_ppi = d->out_pix_per_img;
@@ -466,8 +509,14 @@ int bd_wgrad3x3r_launch(const bd_conv_desc* d, const void* x, const void* g, flo
         ps += cdiv(d->Ho[s], 8) * sg.pw;
     }
     BD_ONCE_PER_DEVICE(
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3x3_ring_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    hipLaunchKernelGGL(conv_wgrad3x3_ring_kernel, dim3(pl.splits * pl.tiles), dim3(512), LDS_BYTES, stream, p);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3x3_ring_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3x3_ring_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  LDS_BYTES + LIST_MAX * 4));
+    if (gflags && pl.per <= LIST_MAX)
+        hipLaunchKernelGGL(conv_wgrad3x3_ring_kernel<true>, dim3(pl.splits * pl.tiles), dim3(512), LDS_BYTES + LIST_MAX * 4, stream, p);
+    else
+        hipLaunchKernelGGL(conv_wgrad3x3_ring_kernel<false>, dim3(pl.splits * pl.tiles), dim3(512), LDS_BYTES, stream, p);
     *splits_out = pl.splits;
     return 0;
 }

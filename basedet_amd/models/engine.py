@@ -55,6 +55,10 @@ class ConvLayer:
         self.w_fwd = torch.empty((self.cout, k * k, cin), dtype=torch.bfloat16, device=device)
         self.w_dgrad = torch.empty((cin, k * k, self.cout), dtype=torch.bfloat16, device=device) if trainable else None
         self._desc_cache = {}
+        # gradient skip (MODEL.SPARSE_BOX_BWD): the bf16 backward launches carry bd_conv_desc.gskip and compute only the patches a nonzero
+        # gradient reaches (the same bits); forward launches keep the plain descriptor
+        self.gskip = False
+        self._gskip_cache = {}
         # fp8 forward (BASELINE config 5, enable_fp8): e4m3 weights with one scale per output channel + the input cast to e4m3
         self.fp8 = False
         self.fp8_dgrad = False          # data gradient on the fp8 patch kernel too (e5m2 gradients under a static gradient scale)
@@ -172,6 +176,18 @@ class ConvLayer:
             self._desc_cache[key] = d
         return d
 
+    def bwd_desc(self, gin: Geom, gout: Geom):
+        """desc() for the data and weight gradient: with self.gskip, a copy that carries the gradient-skip hint and this layer's scratch."""
+        d = self.desc(gin, gout)
+        if not self.gskip:
+            return d
+        h = self._gskip_cache.get(id(d))
+        if h is None:
+            nb = ops.conv2d_dgrad_gskip_bytes(d)
+            scratch = torch.empty((max(nb, 4) + 3) // 4, dtype=torch.int32, device=self.device)
+            h = self._gskip_cache[id(d)] = (ops.gskip_desc(d, scratch), scratch)
+        return h[0]
+
     def forward(self, x, gin, gout, y, add=None, relu=False, bits=None, x8=None, y8=None, q_scale=1.0):
         """x8: the e4m3 twin of x when a producing fp8 launch wrote one (else x is cast by bd_quantize_fp8); y8: twin of y to write
         for a following fp8 convolution.  Both are ignored on the bf16 path."""
@@ -216,7 +232,7 @@ class ConvLayer:
             flags |= ops.EPI_MASK
         if maskbits is not None:
             mask = None
-        d = self.desc(gin, gout)
+        d = self.bwd_desc(gin, gout)
         if self.amax_slot is not None and self.probe_ctl[0] and (self.fp8_1x1_dgrad or self.fp8_dgrad):
             ops.absmax_bf16(g, self.amax_slot)
         if self.fp8_1x1_dgrad and g8 is not None and ops.conv1x1_fp8_ok(d, 1):
@@ -240,7 +256,7 @@ class ConvLayer:
     def wgrad(self, x, g, gin, gout, ws, colsum_ws=None, x8=None, g8=None, queue=None):
         """x8 / g8: the e4m3 twin of x (x * act_scale) and the e5m2 twin of g (g * grad_scale) when their producers wrote them: the
         weight gradient then runs on the one-byte kernel (the bias gradient stays a column sum of the bf16 g)."""
-        d = self.desc(gin, gout)
+        d = self.bwd_desc(gin, gout)
         if self.fp8_wgrad and x8 is not None and g8 is not None:
             ops.conv2d_wgrad_fp8(d, x8, g8, 1.0 / (self.act_scale * self.grad_scale), self.gw, ws, row_scale=self.row_scale)
             if self.gb is not None:
@@ -270,7 +286,7 @@ class ConvLayer:
         ops.conv1x1_thin_bwd(x, g, self.w, gin.pixels, self.cin, self.cout, dx, self.gw, self.gb, self.cout_real, ws)
 
     def wgrad_ws_bytes(self, gin, gout):
-        d = self.desc(gin, gout)
+        d = self.bwd_desc(gin, gout)
         n = ops.conv2d_wgrad_bias_workspace_bytes(d) if self.gb is not None else ops.conv2d_wgrad_workspace_bytes(d)
         return max(n, ops.conv2d_wgrad_fp8_workspace_bytes(d)) if self.fp8_wgrad else n
 

@@ -45,6 +45,12 @@ class RetinaNet(FPNDetector):
         self.cls_score = add("head.cls_score", ch, A * K, 3, 1, 1, bias=True)
         self.box_ld = _round_up(A * 4, 8)                                          # 36 -> 40 channels (8-aligned rows)
         self.bbox_pred = add("head.bbox_pred", ch, A * 4, 3, 1, 1, bias=True, cout_pad=self.box_ld)
+        # MODEL.SPARSE_BOX_BWD (default on, bf16 only): the box branch's gradient is nonzero only around the foreground anchors (the
+        # regression loss writes +0 elsewhere), so its backward launches skip the all-zero patches (bd_conv_desc.gskip: same bits).  The
+        # class tower's focal gradient is dense and stays on the plain descriptors.
+        if bool(m.get("SPARSE_BOX_BWD", True)) and m.get("WEIGHT_DTYPE", "bf16") == "bf16":
+            for c in self.box_tower + [self.bbox_pred]:
+                c.gskip = True
         # base anchors: python float64 -> float32 (layers/common/anchor_generator.py:95-109)
         scales = np.asarray(m.ANCHOR.SCALES, np.float32).tolist()
         ratios = np.asarray(m.ANCHOR.RATIOS, np.float32).tolist()

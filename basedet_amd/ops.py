@@ -127,6 +127,23 @@ def conv2d_dgrad(d, g, w_packed_t, dx, add=None, mask=None, flags=0, maskbits=No
     return dx
 
 
+def conv2d_dgrad_gskip_bytes(d):
+    """Scratch bytes a gradient-skipping data gradient (bd_conv_desc.gskip) needs at d.gskip_ws; 0 where the hint does not apply."""
+    return int(L().bd_conv2d_dgrad_gskip_bytes(C.byref(d)))
+
+
+def gskip_desc(d, scratch=None):
+    """A copy of descriptor d with the gradient-skip hint set (include/basedet_hip.h, bd_conv_desc.gskip): its bf16 data and weight gradients
+    scan g and compute only the patches a nonzero g reaches (same bits).  scratch: device tensor of conv2d_dgrad_gskip_bytes(d) bytes for
+    the data gradient (the weight gradient keeps its flags in ws, sized from this descriptor)."""
+    h = ConvDesc.from_buffer_copy(d)
+    h.gskip = 1
+    if scratch is not None:
+        h.gskip_ws = scratch.data_ptr()
+        h.gskip_ws_bytes = scratch.numel() * scratch.element_size()
+    return h
+
+
 def quantize_fp8(x, scale, q):
     """q (uint8, same element count) = e4m3(clamp(x * scale)) of a bf16 tensor."""
     check(L().bd_quantize_fp8(ptr(x), x.numel(), float(scale), ptr(q), stream_ptr()), "bd_quantize_fp8")

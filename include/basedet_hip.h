@@ -76,6 +76,19 @@ typedef struct bd_conv_desc {
      * hyper-parameter of the fp8 configuration, not a route). */
     int32_t route[4];
     uint32_t sr_seed;
+    /* Gradient-skip hint (0 = off: every pixel is computed, the behaviour of a zeroed descriptor).  gskip = 1: the bf16 data and weight
+     * gradients of a 3x3 / stride-1 / pad-1 descriptor first scan their gradient operand g on the call's stream and compute only the
+     * patches it can reach (g nonzero bits in the patch's footprint); the results are the same bits as with gskip = 0 (an all-zero
+     * patch adds exact zeros).  Forward launches and the fp8 entry points ignore it.
+     *   bd_conv2d_dgrad (conv3x3_pp.hip's kernel, overwrite / BD_EPI_MASK / in-place BD_EPI_ADD_BEFORE): gskip_ws is caller-owned
+     *     device scratch of at least bd_conv2d_dgrad_gskip_bytes(d) bytes (NULL or smaller: BD_EINVAL).  Output patches that no nonzero
+     *     g reaches are written as +0, or, accumulating in place (add == dx), keep what dx holds (as BD_EPI_SPARSE).
+     *   bd_conv2d_wgrad / _bias / _queued (conv_wgrad3x3_ring.hip's kernel): the liveness flags live in ws, whose size
+     *     bd_conv2d_wgrad(_bias)_workspace_bytes reports for the hinted descriptor; gskip_ws is not read.
+     * Other kernels (e.g. the 40-channel weight gradient) ignore the hint. */
+    int32_t gskip;
+    void* gskip_ws;
+    size_t gskip_ws_bytes;
 } bd_conv_desc;
 
 const char* bd_last_error_string(void);
@@ -114,6 +127,8 @@ int bd_conv2d_fwd(const bd_conv_desc* d, const void* x, const void* w_packed, co
  * g has the conv's OUTPUT geometry, dx/add/mask the INPUT geometry. Requires Cout % 8 == 0, Cin % 8 == 0. */
 int bd_conv2d_dgrad(const bd_conv_desc* d, const void* g, const void* w_packed_t, const void* add,
                     const void* mask, void* dx, int flags, bd_stream_t stream);
+/* Scratch bytes bd_conv2d_dgrad needs at d->gskip_ws when d->gskip is set (0 for a descriptor the hint does not apply to). */
+size_t bd_conv2d_dgrad_gskip_bytes(const bd_conv_desc* d);
 
 /* Bit-packed ReLU masks for the HBM-bound 1x1 layers.  A forward launch with BD_EPI_RELU may also write ybits: one bit per output
  * element (y > 0), uint32 [Cout/32][M] (M = N * pixels of the level; word (g, m) holds channels 32g .. 32g+31 of pixel m, bit b =
