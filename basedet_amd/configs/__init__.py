@@ -6,6 +6,8 @@ the un-vendored `basecore`; this one supports attribute access, nested `merge`, 
 """
 import copy
 
+from ..utils.dummy import DUMMY_ORIG_SIZES as _DUMMY_ORIG_SIZES
+
 
 class ConfigDict(dict):
     def __init__(self, d=None, **kw):
@@ -65,7 +67,10 @@ class DetectionConfig(ConfigDict):
         self.DATA = dict(BUILDER_NAME="DataloaderBuilder", NUM_CLASSES=80, NUM_WORKERS=2, ENABLE_INFINITE_SAMPLER=True,
                          TRAIN=dict(name="coco_2017_train", remove_images_without_annotations=True,
                                     order=("image", "boxes", "boxes_category", "info")),
-                         TEST=dict(name="coco_2017_val", remove_images_without_annotations=False, order=("image", "info")))
+                         TEST=dict(name="coco_2017_val", remove_images_without_annotations=False, order=("image", "info")),
+                         # synthetic data (DATA.BUILDER_NAME = "DummyLoader"): DUMMY_MULTISCALE = True runs AUG.TRAIN_VALUE's multi-scale
+                         # shape stream over originals of DUMMY_ORIG_SIZES (utils/dummy.py) instead of one fixed DUMMY_SIZE
+                         DUMMY_MULTISCALE=False, DUMMY_ORIG_SIZES=[list(hw) for hw in _DUMMY_ORIG_SIZES])
         self.SOLVER = dict(BUILDER_NAME="DetSolver", OPTIMIZER_NAME="SGD", LR_SCHEDULER_NAME="MultiStepLR",
                            BASIC_LR=0.01 / 16.0, WEIGHT_DECAY=1e-4, EXTRA_OPT_ARGS=dict(momentum=0.9),
                            REDUCE_MODE="MEAN", EPOCHWISE_STEP=False, WARM_ITERS=500, NUM_IMAGE_PER_EPOCH=80000,
@@ -110,6 +115,7 @@ class DetectionConfig(ConfigDict):
         """The reference builds a COCO reader here (registers.dataloader, data/build.py) -- out of the hot-path scope.  The
         synthetic loader of the reference's own benchmark harness (utils/dummy.py, tools/benchmark.py:173) stands in."""
         from ..utils import DummyLoader
+        from ..utils.dummy import MultiScaleDummyLoader
         from .. import comm
         if self.DATA.get("BUILDER_NAME") != "DummyLoader":
             # a playground config names a COCO reader (DATA.TRAIN.name, AUG, NUM_WORKERS): silently training on noise instead would
@@ -118,6 +124,8 @@ class DetectionConfig(ConfigDict):
                 f"DATA.BUILDER_NAME = {self.DATA.get('BUILDER_NAME')!r}: this build has no dataset readers (hot-path scope, DESIGN.md); "
                 "the only data source is the synthetic DummyLoader of the reference's benchmark harness.  Set DATA.BUILDER_NAME = "
                 "'DummyLoader' (basedet_train: --synthetic) to train on it, or hand your own iterable of batch dicts to DetTrainer.")
+        if self.DATA.get("DUMMY_MULTISCALE", False):
+            return MultiScaleDummyLoader(self.MODEL.BATCHSIZE, self.AUG.TRAIN_VALUE, self.DATA.DUMMY_ORIG_SIZES, seed=comm.rank())
         return DummyLoader(self.MODEL.BATCHSIZE, tuple(self.DATA.get("DUMMY_SIZE", (800, 1344))), seed=comm.rank())
 
     def build_trainer(self):

@@ -1,6 +1,9 @@
 // Fused loss forward + gradient kernels (bf16 predictions in, bf16 gradients out, fp32 math).
 // They replace the dense one-hot target + boolean-mask gathers of the reference
 // (models/det/retinanet.py:144-162, models/det/fcos.py:146-170) by reading the int32 anchor labels directly.
+#include <utility>
+#include <vector>
+
 #include "common.h"
 
 namespace {
@@ -86,7 +89,7 @@ __device__ __forceinline__ void focal_g2_neg2(float x0, float x1, float a, f32x2
 // The 8 logits of a vector are treated as negatives; the (at most one) positive among them is recomputed in a rare branch.
 __global__ __launch_bounds__(256) void focal_g2_kernel(const bf16_raw* __restrict__ logits, const int* __restrict__ labels,
                                                        long long rows, int K, float alpha, const void* norm, int norm_is_float,
-                                                       float grad_scale, float* __restrict__ loss_sum, bf16_raw* __restrict__ dlogits) {
+                                                       float grad_scale, float* __restrict__ partial, bf16_raw* __restrict__ dlogits) {
     __shared__ float red[4];
     const float inv_norm = 1.f / load_norm(norm, norm_is_float);
     const float gs = grad_scale * inv_norm;
@@ -149,12 +152,12 @@ __global__ __launch_bounds__(256) void focal_g2_kernel(const bf16_raw* __restric
         }
     }
     const float s = block_sum_256(acc, red);
-    if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss_sum, s * inv_norm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s * inv_norm;
 }
 
 __global__ __launch_bounds__(256) void focal_kernel(const bf16_raw* __restrict__ logits, const int* __restrict__ labels,
                                                     long long rows, int K, float alpha, float gamma, const void* norm,
-                                                    int norm_is_float, float grad_scale, float* __restrict__ loss_sum,
+                                                    int norm_is_float, float grad_scale, float* __restrict__ partial,
                                                     bf16_raw* __restrict__ dlogits) {
     __shared__ float red[4];
     const float inv_norm = 1.f / load_norm(norm, norm_is_float);
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(256) void focal_kernel(const bf16_raw* __restrict__
         *reinterpret_cast<u32x4_t*>(dlogits + i * 8) = o;
     }
     const float s = block_sum_256(acc, red);
-    if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss_sum, s * inv_norm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s * inv_norm;
 }
 
 // smooth_l1_loss (layers/losses/smooth_l1_loss.py:26-33) on fg rows; prediction addressed as
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(256) void focal_kernel(const bf16_raw* __restrict__
 __global__ __launch_bounds__(256) void smooth_l1_kernel(const bf16_raw* __restrict__ pred, const float* __restrict__ target,
                                                         const int* __restrict__ labels, long long pixels, int A, int ld,
                                                         float beta, const void* norm, int norm_is_float, float weight,
-                                                        float* __restrict__ loss_sum, bf16_raw* __restrict__ dpred) {
+                                                        float* __restrict__ partial, bf16_raw* __restrict__ dpred) {
     __shared__ float red[4];
     const float inv_norm = 1.f / load_norm(norm, norm_is_float);
     const float gs = weight * inv_norm;
@@ -230,14 +233,14 @@ __global__ __launch_bounds__(256) void smooth_l1_kernel(const bf16_raw* __restri
         *reinterpret_cast<u32x2_t*>(dpred + pix * ld + a * 4) = o;
     }
     const float s = block_sum_256(acc, red);
-    if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss_sum, s * gs);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s * gs;
 }
 
 // iou_loss(box_mode="ltrb", loss_type="giou") (layers/losses/iou_loss.py:9-56, 59-105), weighted by centerness
 __global__ __launch_bounds__(256) void giou_ltrb_kernel(const bf16_raw* __restrict__ pred, const float* __restrict__ target,
                                                         const float* __restrict__ wgt, const int* __restrict__ labels,
                                                         long long rows, const float* __restrict__ norm, float loss_weight,
-                                                        float* __restrict__ loss_sum, bf16_raw* __restrict__ dpred) {
+                                                        float* __restrict__ partial, bf16_raw* __restrict__ dpred) {
     __shared__ float red[4];
     const float eps = 1e-8f;
     const float gs = loss_weight / fmaxf(*norm, 1.f);
@@ -292,13 +295,13 @@ __global__ __launch_bounds__(256) void giou_ltrb_kernel(const bf16_raw* __restri
         *reinterpret_cast<u32x2_t*>(dpred + i * 4) = o;
     }
     const float s = block_sum_256(acc, red);
-    if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss_sum, s * gs);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s * gs;
 }
 
 // binary_cross_entropy with logits on fg rows (layers/losses/cross_entropy.py:26)
 __global__ __launch_bounds__(256) void bce_kernel(const bf16_raw* __restrict__ pred, int ld, int off, const float* __restrict__ target,
                                                   const int* __restrict__ labels, long long rows, const float* __restrict__ norm,
-                                                  float* __restrict__ loss_sum, bf16_raw* __restrict__ dpred) {
+                                                  float* __restrict__ partial, bf16_raw* __restrict__ dpred) {
     __shared__ float red[4];
     const float gs = 1.f / fmaxf(*norm, 1.f);
     float acc = 0.f;
@@ -317,7 +320,7 @@ __global__ __launch_bounds__(256) void bce_kernel(const bf16_raw* __restrict__ p
         dpred[i] = f2bf(g);
     }
     const float s = block_sum_256(acc, red);
-    if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss_sum, s * gs);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s * gs;
 }
 
 // RPN losses (models/det/rpn.py:113-131): binary cross entropy with logits, mean over the sampled (label >= 0) anchors,
@@ -326,7 +329,7 @@ __global__ __launch_bounds__(256) void bce_kernel(const bf16_raw* __restrict__ p
 __global__ __launch_bounds__(256) void rpn_loss_kernel(const bf16_raw* __restrict__ raw, int ldc, int A, int cls_off, int box_off,
                                                        const int* __restrict__ labels, const float* __restrict__ targets,
                                                        long long rows, float beta, const int* __restrict__ num_valid,
-                                                       float* __restrict__ loss, bf16_raw* __restrict__ draw) {
+                                                       float* __restrict__ partial, bf16_raw* __restrict__ draw) {
     __shared__ float red[4];
     const float gs = 1.f / fmaxf((float)*num_valid, 1.f);
     float acc_c = 0.f, acc_b = 0.f;
@@ -370,8 +373,8 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(const bf16_raw* __restric
     __syncthreads();
     const float sb = block_sum_256(acc_b, red);
     if (threadIdx.x == 0) {
-        if (sc != 0.f) atomicAdd(loss, sc * gs);
-        if (sb != 0.f) atomicAdd(loss + 1, sb * gs);
+        partial[2 * blockIdx.x] = sc * gs;
+        partial[2 * blockIdx.x + 1] = sb * gs;
     }
 }
 
@@ -382,7 +385,7 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(const bf16_raw* __restric
 __global__ __launch_bounds__(256) void rcnn_loss_kernel(const bf16_raw* __restrict__ raw, int ld, int K, int box_off,
                                                         const int* __restrict__ labels, const float* __restrict__ targets,
                                                         int R, float beta, const int* __restrict__ num_samples,
-                                                        float* __restrict__ loss, bf16_raw* __restrict__ draw) {
+                                                        float* __restrict__ partial, bf16_raw* __restrict__ draw) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;
@@ -392,6 +395,7 @@ __global__ __launch_bounds__(256) void rcnn_loss_kernel(const bf16_raw* __restri
     const int l = labels[r];
     if (l < 0) {
         for (int c = lane; c < ld; c += 64) dp[c] = 0;
+        if (lane == 0) { partial[2 * r] = 0.f; partial[2 * r + 1] = 0.f; }
         return;
     }
     const int nc = K + 1;
@@ -420,9 +424,9 @@ __global__ __launch_bounds__(256) void rcnn_loss_kernel(const bf16_raw* __restri
         dp[c] = f2bf(g);
     }
     if (lane == 0) {
-        atomicAdd(loss, (lse - bf2f(rp[l])) * gs);
+        partial[2 * r] = (lse - bf2f(rp[l])) * gs;
+        float sb = 0.f;
         if (l > 0) {
-            float sb = 0.f;
             for (int k = 0; k < 4; ++k) {
                 const float x = bf2f(rp[box_off + (l - 1) * 4 + k]) - targets[(long long)r * 4 + k];
                 const float ax = fabsf(x);
@@ -430,8 +434,22 @@ __global__ __launch_bounds__(256) void rcnn_loss_kernel(const bf16_raw* __restri
                 else if (ax < beta) sb += 0.5f * x * x / beta;
                 else sb += ax - 0.5f * beta;
             }
-            atomicAdd(loss + 1, sb * gs);
         }
+        partial[2 * r + 1] = sb * gs;
+    }
+}
+
+// The loss sums in a fixed order (bit-reproducible: a float atomicAdd per workgroup made the last bits depend on the workgroups' finishing
+// order): the kernels above leave one partial per workgroup (rcnn: per RoI row) and slot, this one workgroup adds them up in index order
+// -- each thread a strided run, then the fixed wave / block tree -- and adds each slot's total to loss[slot].
+__global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ partial, int n, int slots, float* __restrict__ loss) {
+    __shared__ float red[4];
+    for (int k = 0; k < slots; ++k) {
+        float a = 0.f;
+        for (int b = threadIdx.x; b < n; b += 256) a += partial[(long long)b * slots + k];
+        const float s = block_sum_256(a, red);
+        if (threadIdx.x == 0) loss[k] += s;
+        __syncthreads();
     }
 }
 
@@ -443,19 +461,56 @@ inline int loss_grid(long long n) {
 
 }  // namespace
 
+// Scratch of the partial sums: one grow-only buffer per (device, stream) -- the launches of one stream run in order, so a loss call and its
+// finalize never share their partials with a call on another stream.  Growing frees the old buffer with hipFree, which waits for the device.
+static float* loss_partials(hipStream_t stream, size_t floats) {
+    struct Buf { float* p = nullptr; size_t n = 0; };
+    static std::mutex mu;
+    static std::vector<std::pair<std::pair<int, hipStream_t>, Buf>> bufs;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> g(mu);
+    Buf* b = nullptr;
+    for (auto& e : bufs)
+        if (e.first.first == dev && e.first.second == stream) b = &e.second;
+    if (!b) {
+        bufs.push_back({{dev, stream}, Buf{}});
+        b = &bufs.back().second;
+    }
+    if (b->n < floats) {
+        if (b->p) (void)hipFree(b->p);
+        b->p = nullptr; b->n = 0;
+        const size_t n = floats < 8192 ? 8192 : floats;
+        if (hipMalloc((void**)&b->p, n * sizeof(float)) != hipSuccess) return nullptr;
+        b->n = n;
+    }
+    return b->p;
+}
+
+#define BD_LOSS_PARTIALS(var, stream, floats, name)                                                                          \
+    float* var = loss_partials((hipStream_t)(stream), (size_t)(floats));                                                     \
+    BD_REQUIRE(var != nullptr, name ": cannot allocate %zu bytes of partial-sum scratch", (size_t)(floats) * sizeof(float))
+
+static void loss_finalize(const float* partial, int n, int slots, float* loss, bd_stream_t stream) {
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, n, slots, loss);
+}
+
 static int focal_launch(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha, float gamma, const void* norm,
                         int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, bool general, bd_stream_t stream) {
     BD_REQUIRE(logits && labels && norm && loss_sum && dlogits, "focal_loss: null pointer");
     BD_REQUIRE(K > 0 && K % 8 == 0, "focal_loss: K=%d must be a multiple of 8", K);
     if (rows == 0) return BD_OK;
+    const int grid = loss_grid(rows * (K / 8));
+    BD_LOSS_PARTIALS(part, stream, grid, "focal_loss");
     if (gamma == 2.f && !general)
-        hipLaunchKernelGGL(focal_g2_kernel, dim3(loss_grid(rows * (K / 8))), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_raw*)logits, labels, (long long)rows, K, alpha, norm, norm_is_float, grad_scale, loss_sum,
+        hipLaunchKernelGGL(focal_g2_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                           (const bf16_raw*)logits, labels, (long long)rows, K, alpha, norm, norm_is_float, grad_scale, part,
                            (bf16_raw*)dlogits);
     else
-        hipLaunchKernelGGL(focal_kernel, dim3(loss_grid(rows * (K / 8))), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(focal_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                            (const bf16_raw*)logits, labels, (long long)rows, K, alpha, gamma, norm, norm_is_float, grad_scale,
-                           loss_sum, (bf16_raw*)dlogits);
+                           part, (bf16_raw*)dlogits);
+    loss_finalize(part, grid, 1, loss_sum, stream);
     BD_CHECK_LAUNCH("bd_focal_loss_fwd_bwd");
     return BD_OK;
 }
@@ -479,9 +534,12 @@ extern "C" int bd_smooth_l1_fwd_bwd(const void* pred, const float* target, const
     BD_REQUIRE(pred && target && labels && norm && loss_sum && dpred, "smooth_l1: null pointer");
     BD_REQUIRE(A > 0 && ld >= 4 * A && ld % 4 == 0, "smooth_l1: ld=%d must be a multiple of 4 and >= 4*A", ld);
     if (pixels == 0) return BD_OK;
-    hipLaunchKernelGGL(smooth_l1_kernel, dim3(loss_grid(pixels * (ld / 4))), dim3(256), 0, (hipStream_t)stream,
+    const int grid = loss_grid(pixels * (ld / 4));
+    BD_LOSS_PARTIALS(part, stream, grid, "smooth_l1");
+    hipLaunchKernelGGL(smooth_l1_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_raw*)pred, target, labels, (long long)pixels, A, ld, beta, norm, norm_is_float, weight,
-                       loss_sum, (bf16_raw*)dpred);
+                       part, (bf16_raw*)dpred);
+    loss_finalize(part, grid, 1, loss_sum, stream);
     BD_CHECK_LAUNCH("bd_smooth_l1_fwd_bwd");
     return BD_OK;
 }
@@ -491,8 +549,11 @@ extern "C" int bd_giou_ltrb_fwd_bwd(const void* pred, const float* target, const
                                     bd_stream_t stream) {
     BD_REQUIRE(pred && target && labels && norm && loss_sum && dpred, "giou_ltrb: null pointer");
     if (rows == 0) return BD_OK;
-    hipLaunchKernelGGL(giou_ltrb_kernel, dim3(loss_grid(rows)), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)pred,
-                       target, weight, labels, (long long)rows, norm, loss_weight, loss_sum, (bf16_raw*)dpred);
+    const int grid = loss_grid(rows);
+    BD_LOSS_PARTIALS(part, stream, grid, "giou_ltrb");
+    hipLaunchKernelGGL(giou_ltrb_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)pred,
+                       target, weight, labels, (long long)rows, norm, loss_weight, part, (bf16_raw*)dpred);
+    loss_finalize(part, grid, 1, loss_sum, stream);
     BD_CHECK_LAUNCH("bd_giou_ltrb_fwd_bwd");
     return BD_OK;
 }
@@ -502,8 +563,11 @@ extern "C" int bd_bce_logits_fwd_bwd(const void* pred, int ld, int off, const fl
     BD_REQUIRE(pred && target && labels && norm && loss_sum && dpred, "bce_logits: null pointer");
     BD_REQUIRE(ld >= 1 && off >= 0 && off < ld, "bce_logits: bad ld/off");
     if (rows == 0) return BD_OK;
-    hipLaunchKernelGGL(bce_kernel, dim3(loss_grid(rows)), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)pred, ld, off, target,
-                       labels, (long long)rows, norm, loss_sum, (bf16_raw*)dpred);
+    const int grid = loss_grid(rows);
+    BD_LOSS_PARTIALS(part, stream, grid, "bce_logits");
+    hipLaunchKernelGGL(bce_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)pred, ld, off, target,
+                       labels, (long long)rows, norm, part, (bf16_raw*)dpred);
+    loss_finalize(part, grid, 1, loss_sum, stream);
     BD_CHECK_LAUNCH("bd_bce_logits_fwd_bwd");
     return BD_OK;
 }
@@ -514,8 +578,11 @@ extern "C" int bd_rpn_loss_fwd_bwd(const void* raw, int ldc, int A, int cls_off,
     BD_REQUIRE(raw && labels && targets && num_valid && loss2 && draw, "rpn_loss: null pointer");
     BD_REQUIRE(A > 0 && cls_off >= 0 && box_off >= 0 && cls_off + A <= ldc && box_off + 4 * A <= ldc, "rpn_loss: bad channel layout");
     if (rows == 0) return BD_OK;
-    hipLaunchKernelGGL(rpn_loss_kernel, dim3(loss_grid(rows * A)), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)raw, ldc, A,
-                       cls_off, box_off, labels, targets, (long long)rows, beta, num_valid, loss2, (bf16_raw*)draw);
+    const int grid = loss_grid(rows * A);
+    BD_LOSS_PARTIALS(part, stream, 2 * (size_t)grid, "rpn_loss");
+    hipLaunchKernelGGL(rpn_loss_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)raw, ldc, A,
+                       cls_off, box_off, labels, targets, (long long)rows, beta, num_valid, part, (bf16_raw*)draw);
+    loss_finalize(part, grid, 2, loss2, stream);
     BD_CHECK_LAUNCH("bd_rpn_loss_fwd_bwd");
     return BD_OK;
 }
@@ -525,8 +592,10 @@ extern "C" int bd_rcnn_loss_fwd_bwd(const void* raw, int ld, int K, int box_off,
     BD_REQUIRE(raw && labels && targets && num_samples && loss2 && draw, "rcnn_loss: null pointer");
     BD_REQUIRE(K > 0 && box_off >= K + 1 && box_off + 4 * K <= ld, "rcnn_loss: bad channel layout");
     if (R == 0) return BD_OK;
+    BD_LOSS_PARTIALS(part, stream, 2 * (size_t)R, "rcnn_loss");
     hipLaunchKernelGGL(rcnn_loss_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)raw, ld, K, box_off,
-                       labels, targets, R, beta, num_samples, loss2, (bf16_raw*)draw);
+                       labels, targets, R, beta, num_samples, part, (bf16_raw*)draw);
+    loss_finalize(part, R, 2, loss2, stream);
     BD_CHECK_LAUNCH("bd_rcnn_loss_fwd_bwd");
     return BD_OK;
 }

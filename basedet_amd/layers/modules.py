@@ -108,6 +108,7 @@ class _Head(_Trunk):
         N, _, h0, w0 = features[0].shape
         s0 = m.strides[0]
         pl = m._plan(N, h0 * s0, w0 * s0)
+        m._bind_plan(pl)
         assert len(features) == pl.pyr.nlev, "input features expected {}, got {}".format(pl.pyr.nlev, len(features))
         P = pl.P.view(N, pl.pyr.pix_per_img, -1)
         for i, f in enumerate(features):

@@ -58,7 +58,8 @@ class ConvLayer:
         # gradient skip (MODEL.SPARSE_BOX_BWD): the bf16 backward launches carry bd_conv_desc.gskip and compute only the patches a nonzero
         # gradient reaches (the same bits); forward launches keep the plain descriptor
         self.gskip = False
-        self._gskip_cache = {}
+        self._gskip_cache = {}          # id(plain descriptor) -> (gskip descriptor, plain descriptor)
+        self._gskip_ws = None
         # fp8 forward (BASELINE config 5, enable_fp8): e4m3 weights with one scale per output channel + the input cast to e4m3
         self.fp8 = False
         self.fp8_dgrad = False          # data gradient on the fp8 patch kernel too (e5m2 gradients under a static gradient scale)
@@ -183,9 +184,14 @@ class ConvLayer:
             return d
         h = self._gskip_cache.get(id(d))
         if h is None:
-            nb = ops.conv2d_dgrad_gskip_bytes(d)
-            scratch = torch.empty((max(nb, 4) + 3) // 4, dtype=torch.int32, device=self.device)
-            h = self._gskip_cache[id(d)] = (ops.gskip_desc(d, scratch), scratch)
+            # ONE grow-only scratch per layer, whatever the number of shapes: the layer's data gradient runs once per step, on the main
+            # stream, and the scan / compact launches rewrite what they read.  A larger shape replaces it: the cached descriptors hold
+            # the old pointer and are rebuilt
+            n = (max(ops.conv2d_dgrad_gskip_bytes(d), 4) + 3) // 4
+            if self._gskip_ws is None or self._gskip_ws.numel() < n:
+                self._gskip_ws = torch.empty(n, dtype=torch.int32, device=self.device)
+                self._gskip_cache.clear()
+            h = self._gskip_cache[id(d)] = (ops.gskip_desc(d, self._gskip_ws), d)
         return h[0]
 
     def forward(self, x, gin, gout, y, add=None, relu=False, bits=None, x8=None, y8=None, q_scale=1.0):

@@ -97,60 +97,61 @@ class FasterRCNN(FPNDetector):
         m = self.cfg.MODEL
         N = pl.N
         A = self.num_anchors
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
+        C = pl._carve
+        bf, f32, i32 = torch.bfloat16, torch.float32, torch.int32
         pyr = pl.pyr
         rc = m.RPN.CHANNELS
-        pl.rpn_t = torch.empty((pyr.pixels, rc), **bf)
-        pl.rpn_raw = torch.empty((pyr.pixels, self.rpn_ld), **bf)
-        pl.d_rpn_raw = torch.zeros((pyr.pixels, self.rpn_ld), **bf)        # padding channel stays zero
-        pl.g_rpn_t = torch.empty((pyr.pixels, rc), **bf)
+        pl.rpn_t = C.empty((pyr.pixels, rc), bf)
+        pl.rpn_raw = C.empty((pyr.pixels, self.rpn_ld), bf)
+        pl.d_rpn_raw = C.zeros((pyr.pixels, self.rpn_ld), bf)        # padding channel stays zero (re-cleared whenever the plan is bound)
+        pl.g_rpn_t = C.empty((pyr.pixels, rc), bf)
         tot = pyr.pix_per_img * A
         pl.A_total = tot
-        pl.anchors = torch.empty((tot, 4), **f32)
+        pl.anchors = torch.empty((tot, 4), dtype=f32, device=dev)         # (a per-shape constant, not in the arena)
         o = 0
         for (h, w), s, base in zip(pl.sizes, self.strides, self.base_anchors):
             n = h * w * A
             ops.anchors_generate(h, w, s, m.ANCHOR.OFFSET, base, pl.anchors[o:o + n])
             o += n
-        pl.rpn_labels = torch.empty((N, tot), **i32)
-        pl.rpn_match = torch.empty((N, tot), **i32)
-        pl.rpn_offsets = torch.empty((N, tot, 4), **f32)
-        pl.rpn_num_fg = torch.zeros((1,), **i32)
-        pl.rpn_num_valid = torch.zeros((1,), **i32)
-        pl.assign_ws = None                   # scratch of bd_rpn_assign_encode (N x Gmax floats): sized by the first batch
+        pl.rpn_labels = C.empty((N, tot), i32)
+        pl.rpn_match = C.empty((N, tot), i32)
+        pl.rpn_offsets = C.empty((N, tot, 4), f32)
+        pl.rpn_num_fg = C.zeros((1,), i32)
+        pl.rpn_num_valid = C.zeros((1,), i32)
+        # the RPN sampling keys (drawn into these every step; the RoI keys' width follows Gmax: a model-level buffer, _keys)
+        pl.key_rpn_pos = C.empty((N, tot), f32)
+        pl.key_rpn_neg = C.empty((N, tot), f32)
         lvl_pixels = [h * w for h, w in pl.sizes]
         post = self.post_k[True]
         assert self.post_k[False] == post, "train / test post-NMS top-k share the proposal slots"
-        pl.rois = torch.empty((N, post, 4), **f32)
-        pl.num_rois = torch.zeros((N,), **i32)
-        pl.prop_ws = torch.empty((max(ops.rpn_proposals_workspace_bytes(N, lvl_pixels, A, k, post) for k in self.pre_k.values()),),
-                                 dtype=torch.uint8, device=dev)
+        pl.rois = C.empty((N, post, 4), f32)
+        pl.num_rois = C.zeros((N,), i32)
+        pl.prop_ws = C.empty((max(ops.rpn_proposals_workspace_bytes(N, lvl_pixels, A, k, post) for k in self.pre_k.values()),), torch.uint8)
         S = m.RCNN.NUM_ROIS
         R = N * S
         pl.R = R
-        pl.s_rois = torch.empty((N, S, 4), **f32)
-        pl.s_labels = torch.empty((N, S), **i32)
-        pl.s_targets = torch.empty((N, S, 4), **f32)
-        pl.s_count = torch.zeros((N,), **i32)
-        pl.s_total = torch.zeros((1,), **i32)
+        pl.s_rois = C.empty((N, S, 4), f32)
+        pl.s_labels = C.empty((N, S), i32)
+        pl.s_targets = C.empty((N, S, 4), f32)
+        pl.s_count = C.zeros((N,), i32)
+        pl.s_total = C.zeros((1,), i32)
         ch = self.fpn_ch
         fin = ch * self.pool[0] * self.pool[1]
-        pl.pooled = torch.empty((R, fin), **bf)
-        pl.fc1_out = torch.empty((R, 1024), **bf)
-        pl.fc2_out = torch.empty((R, 1024), **bf)
-        pl.rcnn_raw = torch.empty((R, self.rcnn_ld), **bf)
-        pl.d_rcnn_raw = torch.empty((R, self.rcnn_ld), **bf)
-        pl.g_fc2 = torch.empty((R, 1024), **bf)
-        pl.g_fc1 = torch.empty((R, 1024), **bf)
-        pl.g_pooled = torch.empty((R, fin), **bf)
-        pl.g_feat32 = None                # (the fp32 scatter's staging pyramid, 1.5 GB at batch 16: allocated when that variant runs)
+        pl.pooled = C.empty((R, fin), bf)
+        pl.fc1_out = C.empty((R, 1024), bf)
+        pl.fc2_out = C.empty((R, 1024), bf)
+        pl.rcnn_raw = C.empty((R, self.rcnn_ld), bf)
+        pl.d_rcnn_raw = C.empty((R, self.rcnn_ld), bf)        # (bd_rcnn_loss_fwd_bwd writes the padding columns' zero gradient)
+        pl.g_fc2 = C.empty((R, 1024), bf)
+        pl.g_fc1 = C.empty((R, 1024), bf)
+        pl.g_pooled = C.empty((R, fin), bf)
         pl.roi_bwd_tiled = self.pool == (7, 7) and S <= 512 and self.fpn_ch % 2 == 0       # the tiled kernel's limits (rcnn_ops.hip)
-        pl.roi_bwd_ws = (torch.empty((ops.roi_align_bwd_bf16_workspace_bytes(pyr, S),), dtype=torch.uint8, device=dev)
-                         if pl.roi_bwd_tiled else None)
+        # the fp32 scatter's staging pyramid (1.5 GB at batch 16): in the arena when the plan routes RoIAlign's backward to the scatter;
+        # a model that forces the scatter on a tiled plan (deterministic_roi_bwd = False, a test switch) allocates it on first use
+        pl.g_feat32 = None if pl.roi_bwd_tiled else C.empty((pyr.pixels, self.fpn_ch), f32)
+        pl.roi_bwd_ws = C.empty((ops.roi_align_bwd_bf16_workspace_bytes(pyr, S),), torch.uint8) if pl.roi_bwd_tiled else None
         pl.g_fc = ops.single(1, R, 1)
-        pl.loss_buf = torch.zeros((4,), **f32)
+        pl.loss_buf = C.zeros((4,), f32)
 
     # ---- forward -----------------------------------------------------------------------------------------
     def head_forward(self, pl):
@@ -161,15 +162,16 @@ class FasterRCNN(FPNDetector):
         else:
             self.rpn_pred.forward(pl.rpn_t, pl.pyr, pl.pyr, pl.rpn_raw)
 
-    def _keys(self, inputs, name, shape):
+    def _keys(self, inputs, name, out):
+        """Fill `out` (a contiguous float32 buffer) with this step's keys: the injected ones, or a draw of the model's generator --
+        torch.rand(..., out=) on a contiguous buffer draws exactly what torch.rand(shape) would."""
         sk = inputs.get("sample_keys") if isinstance(inputs, dict) else None
         if sk is not None and name in sk:
             k = sk[name]
             k = torch.as_tensor(np.asarray(k), dtype=torch.float32) if not torch.is_tensor(k) else k
-            k = k.to(self.device, dtype=torch.float32).contiguous()
-            assert tuple(k.shape) == tuple(shape), f"sample_keys[{name}] has shape {tuple(k.shape)}, expected {tuple(shape)}"
-            return k
-        return torch.rand(shape, generator=self._gen, device=self.device, dtype=torch.float32)
+            assert tuple(k.shape) == tuple(out.shape), f"sample_keys[{name}] has shape {tuple(k.shape)}, expected {tuple(out.shape)}"
+            return out.copy_(k.to(self.device, dtype=torch.float32))
+        return torch.rand(tuple(out.shape), generator=self._gen, out=out)
 
     def _proposals(self, pl, img_info):
         m = self.cfg.MODEL
@@ -196,15 +198,17 @@ class FasterRCNN(FPNDetector):
         key_ld = pl.rois.shape[1] + Gmax
         # The four random-key tensors of a step (sampling.py:26 draws them where it needs them) are drawn HERE, on the main stream, in one
         # fixed order: which side stream consumes them -- and whether the RPN targets run early -- no longer changes what a seed produces.
-        # The plan keeps them until the next step's draw (the side streams that read them have joined by then).
-        keys = {name: self._keys(inputs, name, shape) for name, shape in
-                (("rpn_pos", (N, pl.A_total)), ("rpn_neg", (N, pl.A_total)), ("rcnn_fg", (N, key_ld)), ("rcnn_bg", (N, key_ld)))}
-        pl.sample_keys = keys
+        # They are drawn into arena / model buffers that the next step overwrites only after the side streams reading them have joined
+        # the main stream (within a step; across shapes, _bind_plan), so nothing has to keep them alive.
+        rk = self._scratch("rcnn_keys", 2 * N * key_ld * 4).view(torch.float32).view(2, N, key_ld)
+        keys = {}
+        for name, out in (("rpn_pos", pl.key_rpn_pos), ("rpn_neg", pl.key_rpn_neg), ("rcnn_fg", rk[0]), ("rcnn_bg", rk[1])):
+            keys[name] = self._keys(inputs, name, out)
 
         def rpn_targets():
             """RPN.get_ground_truth (rpn.py:215-240): anchors, ground truth and random keys in, labels / offsets out -- nothing of the network."""
             ops.rpn_assign_encode(pl.anchors, gt, num_gt, thr[0], thr[1], m.MATCHER.ALLOW_LOW_QUALITY, m.RPN_BOX_REG.MEAN,
-                                  m.RPN_BOX_REG.STD, pl.rpn_labels, pl.rpn_match, pl.rpn_offsets, pl.rpn_num_fg, pl.assign_ws)
+                                  m.RPN_BOX_REG.STD, pl.rpn_labels, pl.rpn_match, pl.rpn_offsets, pl.rpn_num_fg, assign_ws)
             ops.sample_labels(pl.rpn_labels, keys["rpn_pos"], keys["rpn_neg"], int(m.RPN.POSITIVE_ANCHOR_RATIO * nsa), nsa, pl.rpn_num_valid)
             if not (self.deterministic_roi_bwd and pl.roi_bwd_tiled):     # (the fp32 scatter only)
                 if pl.g_feat32 is None:
@@ -216,8 +220,7 @@ class FasterRCNN(FPNDetector):
         # 268 569 keys per image) and that clear run on the weight-gradient stream, which is idle during the forward pass, UNDER the
         # backbone -- as RetinaNet's assignment does (rounds 1-4 ran them between the forward and the RPN losses, on the main chain).
         early = self._wstream if (self.async_wgrad and self._wstream is not None and m.get("RPN_TARGETS_EARLY", True)) else None
-        if pl.assign_ws is None or pl.assign_ws.numel() < N * Gmax:
-            pl.assign_ws = torch.empty((N * Gmax,), dtype=torch.float32, device=self.device)
+        assign_ws = self._scratch("rpn_assign", N * Gmax * 4).view(torch.float32)     # (N x Gmax floats: grow-only per model)
         if early is not None:
             early.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(early):
@@ -314,9 +317,8 @@ class FasterRCNN(FPNDetector):
         pyr = pl.pyr
         if self.thin_rpn_bwd and self.rpn_pred.thin_backward_ok(pyr):
             # the prediction layer (256 -> 3 + 12 channels): data, weight and bias gradient in one pass over rpn_t (csrc/conv1x1_thin.hip)
-            if getattr(pl, "thin_ws", None) is None:
-                pl.thin_ws = torch.empty((ops.conv1x1_thin_bwd_workspace_bytes(),), dtype=torch.uint8, device=self.device)
-            self.rpn_pred.thin_backward(pl.rpn_t, pl.d_rpn_raw, pyr, pl.g_rpn_t, pl.thin_ws)
+            ws1 = self._scratch("rpn_thin", ops.conv1x1_thin_bwd_workspace_bytes())        # (a fixed size: one per model)
+            self.rpn_pred.thin_backward(pl.rpn_t, pl.d_rpn_raw, pyr, pl.g_rpn_t, ws1)
         else:
             self._wgrad(self.rpn_pred, pl.rpn_t, pl.d_rpn_raw, pyr, pyr, ws, cws)
             self.rpn_pred.dgrad(pl.d_rpn_raw, pyr, pyr, pl.g_rpn_t, mask=pl.rpn_t)
@@ -357,13 +359,13 @@ class FasterRCNN(FPNDetector):
         K = self.num_classes
         dev = self.device
         bf = dict(dtype=torch.bfloat16, device=dev)
-        if not hasattr(pl, "inf"):
+        if getattr(self, "_inf", None) is None:     # (R rows whatever the shape: one set per model, every plan's `inf` names it)
             fin = self.fpn_ch * self.pool[0] * self.pool[1]
-            pl.inf = dict(pooled=torch.empty((R, fin), **bf), fc1=torch.empty((R, 1024), **bf), fc2=torch.empty((R, 1024), **bf),
+            self._inf = dict(pooled=torch.empty((R, fin), **bf), fc1=torch.empty((R, 1024), **bf), fc2=torch.empty((R, 1024), **bf),
                           raw=torch.empty((R, self.rcnn_ld), **bf), g=ops.single(1, R, 1),
                           scores=torch.empty((R * K,), dtype=torch.float32, device=dev),
                           boxes=torch.empty((R * K, 4), dtype=torch.float32, device=dev))
-        b = pl.inf
+        b = pl.inf = self._inf
         ops.roi_align_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, pl.rois.view(-1, 4), None, R, self.pool, 2, b["pooled"])
         g = b["g"]
         self.fc1.forward(b["pooled"], g, g, b["fc1"], relu=True)

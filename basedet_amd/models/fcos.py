@@ -59,29 +59,29 @@ class FCOS(FPNDetector):
         dev = self.device
         ch = self.fpn_ch
         N = pl.N
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
+        C = pl._carve
+        bf, f32 = torch.bfloat16, torch.float32
 
         def act(c):
-            return torch.empty((pl.pyr.pixels, c), **bf)
+            return C.empty((pl.pyr.pixels, c), bf)
 
         nc = len(self.towers["cls_subnet"][0])
         L = pl.pyr.nlev
         pl.tw = {}
         for tower in self.towers:
             pl.tw[tower] = dict(y=[act(ch) for _ in range(nc)], z=[act(ch) for _ in range(nc)],
-                                stats=[torch.empty((N, L, 32, 2), **f32) for _ in range(nc)])
+                                stats=[C.empty((N, L, 32, 2), f32) for _ in range(nc)])
         pl.logits = act(self.num_classes)
-        pl.raw = act(8)
+        pl.raw = act(8)                                 # (channels 5..7: zero weight rows and bias -- written as 0 by every forward)
         pl.offsets = act(4)
-        pl.d_logits = torch.empty_like(pl.logits)
-        pl.d_off = torch.empty_like(pl.offsets)
-        pl.d_ctr = torch.empty((pl.pyr.pixels,), **bf)
-        pl.d_raw = torch.empty_like(pl.raw)
+        pl.d_logits = C.like(pl.logits)
+        pl.d_off = C.like(pl.offsets)
+        pl.d_ctr = C.empty((pl.pyr.pixels,), bf)
+        pl.d_raw = C.like(pl.raw)                       # (bd_fcos_offsets_bwd writes all 8 channels of every row)
         pl.g_z = act(ch)                                                  # dL/dz scratch (consumed at once by the GN bwd)
         pl.g_y = [[act(ch) for _ in range(nc)] for _ in range(2)]         # dL/dy per tower layer (read by async wgrads)
         P_total = pl.pyr.pix_per_img
-        pl.points = torch.empty((P_total, 2), **f32)
+        pl.points = torch.empty((P_total, 2), dtype=f32, device=dev)     # (a per-shape constant, not in the arena)
         o = 0
         for (h, w), s in zip(pl.sizes, self.strides):
             ops.points_generate(h, w, s, self.cfg.MODEL.ANCHOR.OFFSET, 1, pl.points[o:o + h * w])
@@ -89,17 +89,17 @@ class FCOS(FPNDetector):
         pl.lvl_start = [0]
         for (h, w) in pl.sizes:
             pl.lvl_start.append(pl.lvl_start[-1] + h * w)
-        pl.labels = torch.empty((N, P_total), dtype=torch.int32, device=dev)
-        pl.gt_offsets = torch.empty((N, P_total, 4), **f32)
-        pl.gt_ctr = torch.empty((N, P_total), **f32)
-        pl.stats = torch.zeros((2,), **f32)          # (num_fg, sum_ctr)
-        pl.loss_buf = torch.zeros((3,), **f32)
-        pl.gn_ws = torch.empty((ops.groupnorm_workspace_bytes(N, L, ch, pl.pyr.pix_per_img) // 4 + 16,), **f32)
-        pl.off_ws = torch.empty((ops.fcos_offsets_workspace_bytes() // 4,), **f32)
+        pl.labels = C.empty((N, P_total), torch.int32)
+        pl.gt_offsets = C.empty((N, P_total, 4), f32)
+        pl.gt_ctr = C.empty((N, P_total), f32)
+        pl.stats = C.zeros((2,), f32)          # (num_fg, sum_ctr)
+        pl.loss_buf = C.zeros((3,), f32)
+        pl.gn_ws = C.empty((ops.groupnorm_workspace_bytes(N, L, ch, pl.pyr.pix_per_img) // 4 + 16,), f32)
+        pl.off_ws = C.empty((ops.fcos_offsets_workspace_bytes() // 4,), f32)
         # MODEL.FUSE_GN_STATS (default on): GroupNorm's statistics from the tower convolutions' epilogues instead of a pass over their outputs
         tower_convs = self.towers["cls_subnet"][0] + self.towers["bbox_subnet"][0]
         fuse = bool(self.cfg.MODEL.get("FUSE_GN_STATS", True)) and dev.type == "cuda" and all(c.gnstats_ok() for c in tower_convs)
-        pl.gn_part = (torch.empty((ops.conv2d_fwd_gnstats_bytes(tower_convs[0].desc(pl.pyr, pl.pyr)) // 4,), **f32) if fuse else None)
+        pl.gn_part = (C.empty((ops.conv2d_fwd_gnstats_bytes(tower_convs[0].desc(pl.pyr, pl.pyr)) // 4,), f32) if fuse else None)
 
     # ---- forward -----------------------------------------------------------------------------------------
     def head_forward(self, pl):
@@ -225,11 +225,12 @@ class ATSS(FCOS):
 
     ASSIGN_ON_SIDE_STREAM = True
 
+    def _plan_head(self, pl):
+        super()._plan_head(pl)
+        pl.atss_ws = pl._carve.empty((ops.atss_assign_workspace_bytes(pl.N, pl.pyr.pix_per_img),), torch.uint8)
+
     def _assign(self, pl, gt, num_gt):
         m = self.cfg.MODEL
-        N, P_total = pl.labels.shape
-        if getattr(pl, "atss_ws", None) is None:
-            pl.atss_ws = torch.empty((ops.atss_assign_workspace_bytes(N, P_total),), dtype=torch.uint8, device=self.device)
         ops.atss_assign(pl.points, pl.lvl_start, self.strides, m.ANCHOR.TOPK, m.ANCHOR.SCALE, gt, num_gt, pl.labels, pl.gt_offsets,
                         pl.gt_ctr, pl.stats, pl.atss_ws)
 
@@ -250,17 +251,17 @@ class OTA(FCOS):
 
     def _plan_head(self, pl):
         super()._plan_head(pl)
-        pl.ota_ws = torch.empty((ops.ota_assign_workspace_bytes(pl.N, pl.points.shape[0]),), dtype=torch.uint8, device=self.device)
+        pl.ota_ws = pl._carve.empty((ops.ota_assign_workspace_bytes(pl.N, pl.points.shape[0]),), torch.uint8)
 
     def _assign(self, pl, gt, num_gt):
         m = self.cfg.MODEL
         if self.matching == "sinkhorn":              # SinkhornMatcher(eps=0.1, max_iter=50) (ota.py:43-44)
             need = ops.ota_sinkhorn_workspace_bytes(pl.N, pl.points.shape[0], gt.shape[1])
-            if pl.ota_ws.numel() < need:
-                pl.ota_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            # (sized by Gmax as well: the model's grow-only workspace when the plan's top-k one is too small)
+            ws = pl.ota_ws if pl.ota_ws.numel() >= need else self._scratch("ota_sinkhorn", need)
             ops.ota_assign_sinkhorn(pl.points, pl.lvl_start, self.strides, pl.logits, self.num_classes, pl.offsets, gt, num_gt,
                                     m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA, m.HEAD.get("COST_REG_WEIGHTS", 1.5), 2.5,
-                                    pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, pl.ota_ws)
+                                    pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, ws)
             return
         ops.ota_assign(pl.points, pl.lvl_start, self.strides, pl.logits, self.num_classes, pl.offsets, gt, num_gt,
                        m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA, m.HEAD.get("COST_REG_WEIGHTS", 1.5), 2.5,

@@ -27,7 +27,59 @@ def _round_up(v, m):
 
 
 class _Plan:
-    """Shape-dependent buffers (activations, gradients, anchors, workspaces) for one (N, Hp, Wp)."""
+    """Shape-dependent state for one (N, Hp, Wp).  Per-shape constants (geometry, level tables, anchors / points, routing decisions) are
+    the plan's own; every per-step buffer (activations, gradients, twins, targets, counters, workspaces) is a view into the model's plan
+    arena, laid out by a _Carver at fixed offsets from 0 -- the views of different shapes alias the same memory."""
+
+
+class _Carver:
+    """Byte layout of one plan's per-step buffers in the plan arena.  While _plan runs they are meta placeholders (nothing is allocated);
+    FPNDetector._place swaps them for arena views once the arena is large enough."""
+
+    ALIGN = 256
+    BIG_ALIGN = 2 << 20
+
+    def __init__(self):
+        self.nbytes = 0
+        self.slots = {}          # id(placeholder) -> (byte offset, placeholder)
+        self.zero = []           # (byte offset, bytes): buffers whose all-zero start state is re-established whenever the plan is bound
+
+    def empty(self, shape, dtype, zero=False):
+        t = torch.empty(shape, dtype=dtype, device="meta")
+        n = t.numel() * t.element_size()
+        # buffers of 1 MiB and more start on a 2 MiB boundary, as the caching allocator's large blocks mostly did (packed at 256 B the
+        # fixed-shape step measured ~0.9 % slower)
+        off = _round_up(self.nbytes, self.BIG_ALIGN if n >= (1 << 20) else self.ALIGN)
+        self.nbytes = off + _round_up(n, self.ALIGN)
+        self.slots[id(t)] = (off, t)
+        if zero and n:
+            self.zero.append((off, n))
+        return t
+
+    def zeros(self, shape, dtype):
+        return self.empty(shape, dtype, zero=True)
+
+    def like(self, t):
+        return self.empty(tuple(t.shape), t.dtype)
+
+
+def _map_tensors(v, fn):
+    """Replace every tensor t held by v (a plan: attributes, nested plans, lists, tuples, dicts) by fn(t).  (A plain recursive function:
+    a self-referencing closure would be a reference cycle that keeps fn -- and the arena it names -- alive until the next gc pass.)"""
+    if torch.is_tensor(v):
+        return fn(v)
+    if isinstance(v, _Plan):
+        d = v.__dict__
+        for k in list(d):
+            d[k] = _map_tensors(d[k], fn)
+    elif isinstance(v, list):
+        v[:] = [_map_tensors(x, fn) for x in v]
+    elif isinstance(v, tuple):
+        return tuple(_map_tensors(x, fn) for x in v)
+    elif isinstance(v, dict):
+        for k in list(v):
+            v[k] = _map_tensors(v[k], fn)
+    return v
 
 
 class VecParam:
@@ -86,6 +138,13 @@ class FPNDetector:
         self._build_layers(params)
         self._plans = {}
         self._cur = None
+        # ONE plan arena per model (uint8): every plan's per-step buffers are carved from offset 0, so device memory for them is what the
+        # largest shape seen needs, whatever the number of shapes (multi-scale training).  Only one step runs at a time; _bound is the plan
+        # whose state the arena holds now (_bind_plan re-establishes a plan's start state when another one used the memory in between).
+        self._arena_buf = None
+        self._bound = None
+        self.arena_grows = 0
+        self._scratch_bufs = {}            # model-level grow-only workspaces whose size follows the batch (Gmax), not the shape
         self.extra_meter = {}
         # weight-gradient kernels run on a side stream, concurrently with the dgrad chain they do not feed: tails and
         # barrier bubbles of one kernel are filled by the other (set False to serialise, e.g. for per-kernel timing)
@@ -494,19 +553,22 @@ class FPNDetector:
     # shape plan
     # ------------------------------------------------------------------------------------------------
     def _plan(self, N, Hp, Wp):
+        """The plan of one padded batch shape: built once (constants + carved layout) and kept; its per-step buffers are arena views.
+        Calling it for a cached shape returns the plan untouched -- the buffers of that shape's last step are still readable, as long as
+        no step at another shape ran in between."""
         key = (N, Hp, Wp)
         pl = self._plans.get(key)
         if pl is not None:
             return pl
-        dev = self.device
         pl = _Plan()
         pl.N, pl.Hp, pl.Wp = N, Hp, Wp
-        bf = dict(dtype=torch.bfloat16, device=dev)
+        C = pl._carve = _Carver()
+        bf = torch.bfloat16
 
         def act(g, c):
-            return torch.empty((g.pixels, c), **bf)
+            return C.empty((g.pixels, c), bf)
 
-        pl.x_halo = torch.empty((N, Hp + 6, Wp + 8, 4), **bf)
+        pl.x_halo = C.empty((N, Hp + 6, Wp + 8, 4), bf)      # (bd_pad_normalize writes every element, the zero halo included)
         g2 = ops.single(N, Hp // 2, Wp // 2)
         g4 = ops.single(N, (Hp // 2 - 1) // 2 + 1, (Wp // 2 - 1) // 2 + 1)
         pl.g_stem, pl.g_pool = g2, g4
@@ -537,7 +599,7 @@ class FPNDetector:
             b.mid8 = None
             if (blk["kind"] == "bottleneck" and blk["convs"][1].fp8
                     and ops.dense_1x1_bits_ok(blk["convs"][0].desc(gin, gin))):
-                b.mid8 = torch.empty((gin.pixels, blk["ch"]), dtype=torch.uint8, device=dev)
+                b.mid8 = C.empty((gin.pixels, blk["ch"]), torch.uint8)
             b.out_bits = None
             b.g_mid8 = None
             # one-byte twins for the fp8 1x1 launches: conv2's output (conv3 reads it), the block output (the next block's conv1 reads
@@ -545,7 +607,7 @@ class FPNDetector:
             b.mid8b = b.out8 = b.g_out8 = b.g_mid8a = None
             b.g_out8_ready = False
             if blk["kind"] == "bottleneck":
-                u8 = lambda geo, ch: torch.empty((geo.pixels, ch), dtype=torch.uint8, device=dev)
+                u8 = lambda geo, ch: C.empty((geo.pixels, ch), torch.uint8)
                 nxt = self.blocks[len(pl.blk) + 1] if len(pl.blk) + 1 < len(self.blocks) else None
                 if blk["convs"][2].fp8_1x1 and blk["convs"][1].fp8 and blk["convs"][1].stride == 1:
                     b.mid8b = u8(b.gout, blk["ch"])
@@ -558,16 +620,16 @@ class FPNDetector:
                     if blk["convs"][0].fp8_1x1_dgrad and blk["convs"][1].fp8_dgrad:
                         b.g_mid8a = u8(gin, blk["ch"])
             if blk["trainable"]:
-                b.g_mids = [torch.empty_like(t) for t in b.mids]
-                b.g_out = torch.empty_like(b.out)
+                b.g_mids = [C.like(t) for t in b.mids]
+                b.g_out = C.like(b.out)
                 if (blk["kind"] == "bottleneck" and blk["convs"][1].fp8_dgrad and self.fp8_grad_twins
                         and blk["convs"][2].dgrad_writes_twin(b.gout, b.gout)):
-                    b.g_mid8 = torch.empty((b.gout.pixels, blk["ch"]), dtype=torch.uint8, device=dev)
+                    b.g_mid8 = C.empty((b.gout.pixels, blk["ch"]), torch.uint8)
                 # the block output's ReLU gate, bit-packed by the conv3 launch that writes it (1 bit instead of a bf16 per element):
                 # what the NEXT block's conv1 / the FPN lateral read as their data-gradient mask (dense 1x1 launches: conv1x1.hip)
                 if (blk["kind"] == "bottleneck" and self.use_mask_bits
                         and ops.dense_1x1_bits_ok(blk["convs"][-1].desc(b.gout, b.gout))):
-                    b.out_bits = torch.empty((blk["cout"] // 32, b.gout.pixels), dtype=torch.int32, device=dev)
+                    b.out_bits = C.empty((blk["cout"] // 32, b.gout.pixels), torch.int32)
             pl.blk.append(b)
             gin = b.gout
         # feature taps (last block of layer 2..4 -> res3..res5)
@@ -590,12 +652,12 @@ class FPNDetector:
         # e4m3 twin of the pyramid: written by the fp8 launches that produce P (FPN output convolutions, P6, P7), read by the heads'
         # first convolutions instead of a cast pass.  Only when EVERY level is written by an fp8 convolution (LastLevelP6P7).
         writers = [self.output[s] for s in self.fpn_stages] + ([self.p6, self.p7] if self.TOP_BLOCK == "p6p7" else [])
-        pl.P8 = (torch.empty((pl.pyr.pixels, ch), dtype=torch.uint8, device=dev)
+        pl.P8 = (C.empty((pl.pyr.pixels, ch), torch.uint8)
                  if self.TOP_BLOCK == "p6p7" and all(c.fp8 for c in writers) else None)
         pl.lat = {s: act(pl.blk[pl.res[s]].gout, ch) for s in self.fpn_stages}
-        pl.g_lat = {s: torch.empty_like(pl.lat[s]) for s in self.fpn_stages}
+        pl.g_lat = {s: C.like(pl.lat[s]) for s in self.fpn_stages}
         g6 = pl.pyr.level(len(self.fpn_stages))
-        pl.p6_relu = torch.empty((N * h6 * w6, ch), **bf)
+        pl.p6_relu = C.empty((N * h6 * w6, ch), bf)
         pl.g_p6r = ops.single(N, h6, w6)
         self._plan_head(pl)
         # workspaces
@@ -618,10 +680,104 @@ class FPNDetector:
         if self.TOP_BLOCK == "p6p7":
             need = max(need, self.p6.wgrad_ws_bytes(g5, g6), self.p7.wgrad_ws_bytes(pl.g_p6r, pl.pyr.level(len(self.fpn_stages) + 1)))
         need = max(need, self._head_wgrad_ws_bytes(pl))
-        pl.wgrad_ws = torch.empty((need // 4 + 64,), dtype=torch.float32, device=dev)
-        pl.colsum_ws = torch.empty((ops.colsum_workspace_bytes(2048) // 4,), dtype=torch.float32, device=dev)
+        pl.wgrad_ws = C.empty((need // 4 + 64,), torch.float32)
+        pl.colsum_ws = C.empty((ops.colsum_workspace_bytes(2048) // 4,), torch.float32)
+        self._place(pl)
         self._plans[key] = pl
         return pl
+
+    # ------------------------------------------------------------------------------------------------
+    # plan arena
+    # ------------------------------------------------------------------------------------------------
+    def _place(self, pl):
+        """Swap the carved placeholders of a new plan for views into the arena (grown first if the plan needs more bytes)."""
+        c = pl._carve
+        self._grow_arena(c.nbytes)
+        buf = self._arena_buf
+
+        def place(t):
+            if not t.is_meta:
+                return t
+            off, ph = c.slots[id(t)]
+            assert ph is t, "a meta tensor that the carver did not lay out"
+            return buf[off: off + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
+
+        _map_tensors(pl, place)
+        c.slots = None
+
+    def _grow_arena(self, nbytes):
+        """Replace the arena by a larger one.  The old storage is freed only once no stream can still touch it (device synchronisation:
+        growth happens a few times per run at most); its contents move along, so the last step's buffers stay readable, and every cached
+        plan's views are re-based onto the new storage at the same offsets."""
+        have = 0 if self._arena_buf is None else self._arena_buf.numel()
+        if nbytes <= have:
+            return
+        nbytes = _round_up(nbytes, 2 << 20)
+        old = self._arena_buf
+        if old is not None and self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        new = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        if old is not None:
+            new[:have].copy_(old)
+            base = old.data_ptr()
+
+            def rebase(t):
+                if t.device != new.device or t.untyped_storage().data_ptr() != base:
+                    return t
+                off = t.data_ptr() - base
+                return new[off: off + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
+
+            for p in self._plans.values():
+                _map_tensors(p, rebase)
+        self._arena_buf = new
+        self.arena_grows += 1
+
+    @property
+    def arena_bytes(self):
+        """Bytes of the plan arena (what the largest plan seen so far needs, rounded up to 2 MiB)."""
+        return 0 if self._arena_buf is None else self._arena_buf.numel()
+
+    @staticmethod
+    def plan_bytes(pl):
+        """Bytes one plan's per-step buffers take in the arena."""
+        return pl._carve.nbytes
+
+    def reserve(self, N, H, W):
+        """Grow the plan arena to fit a batch of N images of (up to) H x W without running a step: a run pre-sizes for its largest batch.
+        Returns the plan of that padded shape."""
+        return self._plan(N, _round_up(H, 32), _round_up(W, 32))
+
+    def _join_side_streams(self):
+        """The current stream waits for the side streams that touch plan memory or model scratch (weight gradients, _tstream)."""
+        if self._wstream is not None and self.device.type == "cuda":
+            cur = torch.cuda.current_stream()
+            cur.wait_stream(self._wstream)
+            cur.wait_stream(self._tstream)
+
+    def _bind_plan(self, pl):
+        """Start of a step at plan pl.  When another plan used the arena since pl's last step, every buffer of pl's can hold that plan's
+        data: the main stream first waits for every stream that touched plan memory (the weight-gradient stream, _tstream; the
+        communicator only reads the parameter arena and the FCOS statistics, behind a wait of its own), then the buffers whose start
+        state is all-zero (counters, loss sums, d_rpn_raw's padding channel) are cleared -- as torch.zeros did once per plan."""
+        if self._bound is pl:
+            return
+        if self._bound is not None:
+            self._join_side_streams()
+        buf = self._arena_buf
+        for off, n in pl._carve.zero:
+            buf[off: off + n].zero_()
+        self._bound = pl
+
+    def _scratch(self, name, nbytes):
+        """Model-level grow-only uint8 workspace (its size follows the batch -- Gmax -- rather than the shape).  Before a smaller one is
+        freed the current stream waits for the side streams, so that no later allocation on it can overlap a reader still running."""
+        nbytes = max(int(nbytes), 1)
+        t = self._scratch_bufs.get(name)
+        if t is None or t.numel() < nbytes:
+            if t is not None:
+                self._join_side_streams()
+            t = self._scratch_bufs[name] = torch.empty((_round_up(nbytes, 256),), dtype=torch.uint8, device=self.device)
+        return t[:nbytes]
 
     def _head_wgrad_ws_bytes(self, pl):
         return max(c.wgrad_ws_bytes(pl.pyr, pl.pyr) for c in self._head_convs())
@@ -638,6 +794,7 @@ class FPNDetector:
         N, _, H, W = image.shape
         Hp, Wp = _round_up(H, 32), _round_up(W, 32)
         pl = self._plan(N, Hp, Wp)
+        self._bind_plan(pl)
         ops.pad_normalize(image, Hp, Wp, self.img_mean, self.img_std, pl.x_halo)
         out = {"plan": pl}
         if isinstance(inputs, dict) and "gt_boxes" in inputs:
@@ -666,9 +823,11 @@ class FPNDetector:
             st = self._stager = ops.HostStager(self.device, int(self.cfg.MODEL.get("H2D_THREADS", 0)))
         if not st.supports(arr):
             arr = np.ascontiguousarray(arr, dtype=np.float32)
-        dst = getattr(self, "_h2d_dst", None)
-        if dst is None or dst.shape != arr.shape:
-            dst = self._h2d_dst = torch.empty(arr.shape, dtype=torch.float32, device=self.device)
+        # one grow-only destination for every input shape (the copies and their reader, bd_pad_normalize, run on the current stream)
+        buf = getattr(self, "_h2d_buf", None)
+        if buf is None or buf.numel() < arr.size:
+            buf = self._h2d_buf = torch.empty((arr.size,), dtype=torch.float32, device=self.device)
+        dst = self._h2d_dst = buf[: arr.size].view(arr.shape)
         return st.submit(arr, dst, int(self.cfg.MODEL.get("H2D_CHUNK_ELEMS", 0)))
 
     def _block_forward(self, blk, b, x, x8=None):

@@ -76,29 +76,30 @@ class RetinaNet(FPNDetector):
         ch = self.fpn_ch
         N = pl.N
         sizes = pl.sizes
-        bf = dict(dtype=torch.bfloat16, device=dev)
+        C = pl._carve
+        bf = torch.bfloat16
 
         def act(g, c):
-            return torch.empty((g.pixels, c), **bf)
+            return C.empty((g.pixels, c), bf)
 
         nc = len(self.cls_tower)
         pl.cls_act = [act(pl.pyr, ch) for _ in range(nc)]
         pl.box_act = [act(pl.pyr, ch) for _ in range(nc)]
         A, K = self.num_anchors, self.num_classes
         pl.logits = act(pl.pyr, A * K)
-        pl.offsets = act(pl.pyr, self.box_ld)
-        pl.d_logits = torch.empty_like(pl.logits)
-        pl.d_offsets = torch.empty_like(pl.offsets)
+        pl.offsets = act(pl.pyr, self.box_ld)          # (channels 36..39: zero weight rows and bias -- written as 0 by every forward)
+        pl.d_logits = C.like(pl.logits)
+        pl.d_offsets = C.like(pl.offsets)              # (bd_smooth_l1_fwd_bwd writes the padding slots' zero gradient)
         pl.g_tower = [[act(pl.pyr, ch) for _ in range(nc)] for _ in range(2)]   # one gradient buffer per tower layer
         # fp8 forward: every tower activation gets an e4m3 twin, written by the launch that produces it (no cast passes in the head)
-        tw = lambda: torch.empty((pl.pyr.pixels, ch), dtype=torch.uint8, device=dev)      # noqa: E731
+        tw = lambda: C.empty((pl.pyr.pixels, ch), torch.uint8)      # noqa: E731
         pl.cls_act8 = [tw() if c.fp8 else None for c in self.cls_tower]
         pl.box_act8 = [tw() if c.fp8 else None for c in self.box_tower]
         # fp8 data gradients: e5m2 twins of the tower gradients and of dL/dP, written by the launch that produces them
         tg = self.fp8_grad_twins
         pl.g_tower8 = [[tw() if (c.fp8_dgrad and tg) else None for c in tower] for tower in (self.cls_tower, self.box_tower)]
         pl.g_P8 = tw() if (tg and all(t[0].fp8_dgrad for t in (self.cls_tower, self.box_tower))) else None
-        # anchors (regenerated per forward in the reference, retinanet.py:116; cached per shape here)
+        # anchors (regenerated per forward in the reference, retinanet.py:116; cached per shape here: a per-shape constant, not in the arena)
         tot = pl.pyr.pix_per_img * A
         pl.anchors = torch.empty((tot, 4), dtype=torch.float32, device=dev)
         o = 0
@@ -107,11 +108,11 @@ class RetinaNet(FPNDetector):
             ops.anchors_generate(h, w, s, self.cfg.MODEL.ANCHOR.OFFSET, base, pl.anchors[o:o + n])
             o += n
         pl.A_total = tot
-        pl.labels = torch.empty((N, tot), dtype=torch.int32, device=dev)
-        pl.match_idx = torch.empty((N, tot), dtype=torch.int32, device=dev)
-        pl.gt_offsets = torch.empty((N, tot, 4), dtype=torch.float32, device=dev)
-        pl.num_fg = torch.zeros((1,), dtype=torch.int32, device=dev)
-        pl.loss_buf = torch.zeros((2,), dtype=torch.float32, device=dev)
+        pl.labels = C.empty((N, tot), torch.int32)
+        pl.match_idx = C.empty((N, tot), torch.int32)
+        pl.gt_offsets = C.empty((N, tot, 4), torch.float32)
+        pl.num_fg = C.zeros((1,), torch.int32)
+        pl.loss_buf = C.zeros((2,), torch.float32)
 
     # ---- forward -----------------------------------------------------------------------------------------
     def head_forward(self, pl):
@@ -154,7 +155,7 @@ class RetinaNet(FPNDetector):
         gt = pre["gt_boxes"]
         num_gt = pre["img_info"][:, 4].to(torch.int32).contiguous()
         N, Gmax = gt.shape[0], gt.shape[1]
-        ws = pl.wgrad_ws[: N * Gmax]
+        ws = self._scratch("assign", N * Gmax * 4).view(torch.float32)     # (N x Gmax floats: grows with the batch's Gmax, not the shape)
         thr = m.MATCHER.THRESHOLDS
         # The target assignment depends on the anchors and the gt boxes only (retinanet.py:211-232), not on the network's output: its two
         # launches (~0.12 ms at 16 x 201 600 anchors) run on a side stream under the forward pass instead of between forward and losses.
