@@ -219,7 +219,7 @@ class FasterRCNN(FPNDetector):
         # Round 5: the RPN targets (0.7 ms of one-workgroup-per-image kernels at batch 16: gt_rowmax, assignment, the radix select over
         # 268 569 keys per image) and that clear run on the weight-gradient stream, which is idle during the forward pass, UNDER the
         # backbone -- as RetinaNet's assignment does (rounds 1-4 ran them between the forward and the RPN losses, on the main chain).
-        early = self._wstream if (self.async_wgrad and self._wstream is not None and m.get("RPN_TARGETS_EARLY", True)) else None
+        early = self.wgrads.side() if m.get("RPN_TARGETS_EARLY", True) else None
         assign_ws = self._scratch("rpn_assign", N * Gmax * 4).view(torch.float32)     # (N x Gmax floats: grow-only per model)
         if early is not None:
             early.wait_stream(torch.cuda.current_stream())
@@ -232,7 +232,7 @@ class FasterRCNN(FPNDetector):
         # backward's sum into dL/dP, under the whole proposal / box-head chain: 523-524 img/s against 545-547 on one box,
         # profiles/r05_frcnn_ab.txt -- the persistent one-workgroup-per-CU convolution kernels keep the box chain's many small grids
         # waiting for a CU, and the box chain is the critical path; that schedule also failed the bench-batch parity test once.)
-        side = self._tstream if (self.async_wgrad and self._tstream is not None) else None
+        side = self.wgrads.top()
 
         def sample():
             ops.rcnn_sample_targets(pl.rois, pl.num_rois, gt, num_gt, keys["rcnn_fg"], keys["rcnn_bg"], S, int(S * m.RCNN.FG_RATIO), m.RCNN.FG_THRESHOLD,

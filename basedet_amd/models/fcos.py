@@ -136,7 +136,7 @@ class FCOS(FPNDetector):
         # FCOS / ATSS targets depend on the points and the gt boxes only (fcos.py:222-293, atss.py:17-86): they can be assigned on a side
         # stream under the forward pass (as RetinaNet's).  Measured, same box: ATSS (two launches per (gt, image)) +0.5 %, FCOS (one cheap
         # launch: the two stream joins cost more than it) -0.3 % -- on for ATSS, off for FCOS.
-        side = self._tstream if (self.async_wgrad and self._tstream is not None and m.get("ASSIGN_ON_SIDE_STREAM", self.ASSIGN_ON_SIDE_STREAM)) else None
+        side = self.wgrads.top() if m.get("ASSIGN_ON_SIDE_STREAM", self.ASSIGN_ON_SIDE_STREAM) else None
         if side is not None:
             side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side) if side is not None else _nullcontext():

@@ -20,66 +20,9 @@ from .. import ops
 from ..ops import Geom
 from . import params as P
 from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena
-
-
-def _round_up(v, m):
-    return (v + m - 1) // m * m
-
-
-class _Plan:
-    """Shape-dependent state for one (N, Hp, Wp).  Per-shape constants (geometry, level tables, anchors / points, routing decisions) are
-    the plan's own; every per-step buffer (activations, gradients, twins, targets, counters, workspaces) is a view into the model's plan
-    arena, laid out by a _Carver at fixed offsets from 0 -- the views of different shapes alias the same memory."""
-
-
-class _Carver:
-    """Byte layout of one plan's per-step buffers in the plan arena.  While _plan runs they are meta placeholders (nothing is allocated);
-    FPNDetector._place swaps them for arena views once the arena is large enough."""
-
-    ALIGN = 256
-    BIG_ALIGN = 2 << 20
-
-    def __init__(self):
-        self.nbytes = 0
-        self.slots = {}          # id(placeholder) -> (byte offset, placeholder)
-        self.zero = []           # (byte offset, bytes): buffers whose all-zero start state is re-established whenever the plan is bound
-
-    def empty(self, shape, dtype, zero=False):
-        t = torch.empty(shape, dtype=dtype, device="meta")
-        n = t.numel() * t.element_size()
-        # buffers of 1 MiB and more start on a 2 MiB boundary, as the caching allocator's large blocks mostly did (packed at 256 B the
-        # fixed-shape step measured ~0.9 % slower)
-        off = _round_up(self.nbytes, self.BIG_ALIGN if n >= (1 << 20) else self.ALIGN)
-        self.nbytes = off + _round_up(n, self.ALIGN)
-        self.slots[id(t)] = (off, t)
-        if zero and n:
-            self.zero.append((off, n))
-        return t
-
-    def zeros(self, shape, dtype):
-        return self.empty(shape, dtype, zero=True)
-
-    def like(self, t):
-        return self.empty(tuple(t.shape), t.dtype)
-
-
-def _map_tensors(v, fn):
-    """Replace every tensor t held by v (a plan: attributes, nested plans, lists, tuples, dicts) by fn(t).  (A plain recursive function:
-    a self-referencing closure would be a reference cycle that keeps fn -- and the arena it names -- alive until the next gc pass.)"""
-    if torch.is_tensor(v):
-        return fn(v)
-    if isinstance(v, _Plan):
-        d = v.__dict__
-        for k in list(d):
-            d[k] = _map_tensors(d[k], fn)
-    elif isinstance(v, list):
-        v[:] = [_map_tensors(x, fn) for x in v]
-    elif isinstance(v, tuple):
-        return tuple(_map_tensors(x, fn) for x in v)
-    elif isinstance(v, dict):
-        for k in list(v):
-            v[k] = _map_tensors(v[k], fn)
-    return v
+from .fp8_scaling import Fp8GradScaler, initial_grad_scale
+from .plan_arena import PlanArena, _Carver, _Plan, _round_up
+from .wgrad_sched import WgradScheduler
 
 
 class VecParam:
@@ -135,36 +78,23 @@ class FPNDetector:
         self.img_mean, self.img_std = list(m.BACKBONE.IMG_MEAN), list(m.BACKBONE.IMG_STD)
         if params is None:
             params = self.init_params(cfg, seed)
+        self._pack_table = None            # bd_weight_pack_multi's table: built by the first repack_trainable, dropped by _bind_params
+        self._stager = self._h2d_buf = self._h2d_dst = None        # host-to-device staging, created by the first host batch
         self._build_layers(params)
         self._plans = {}
         self._cur = None
-        # ONE plan arena per model (uint8): every plan's per-step buffers are carved from offset 0, so device memory for them is what the
-        # largest shape seen needs, whatever the number of shapes (multi-scale training).  Only one step runs at a time; _bound is the plan
-        # whose state the arena holds now (_bind_plan re-establishes a plan's start state when another one used the memory in between).
-        self._arena_buf = None
-        self._bound = None
-        self.arena_grows = 0
-        self._scratch_bufs = {}            # model-level grow-only workspaces whose size follows the batch (Gmax), not the shape
+        self.wgrads = WgradScheduler(self.device, m.get("WGRAD_QUEUE", "layer"))
+        self.plan_arena = PlanArena(self.device, self.wgrads.join_side)
         self.extra_meter = {}
-        # weight-gradient kernels run on a side stream, concurrently with the dgrad chain they do not feed: tails and
-        # barrier bubbles of one kernel are filled by the other (set False to serialise, e.g. for per-kernel timing)
-        self.async_wgrad = True
-        # WGRAD_QUEUE: "layer" (default again since round 5) = one fixed-order reduce per layer right behind its partial-sum kernel: the slabs
-        # are still in the Infinity Cache when they are read back; "bucket" (round 4's default) = the reduces of a gradient bucket (head /
-        # fpn / layer4 / layer3 / layer2) in ONE launch (bd_wgrad_queue_*: 5 reduce launches per step instead of 60); an integer =
-        # additionally flush whenever that many bytes of partial sums are pending.  Same bits in every mode (tests/test_wgrad_queue_gpu.py).
-        # Measured, alternating on one box (profiles/r05_workloads.txt, r05_queue_ab.txt; round 4 had read the same sign and called it
-        # neutral): layer 635.8 / 637.0 / 636.3 img/s, bucket 632.0 / 630.9 / 635.1 -- and 647.4 / 643.7 against 643.2 / 639.5 on two other boxes.
-        self.wgrad_queue_mode = m.get("WGRAD_QUEUE", "layer")
-        self._wq = None
-        self._wq_need = {}                  # (layer name, full geometry) -> workspace bytes
-        # ONE partial-sum arena per model, as large as the largest flush interval (gradient bucket) seen so far: a flush's reduce and
-        # every later partial-sum kernel run on the same stream, so the slices are re-used from offset 0 after each flush
-        self._wq_arena = None
-        self._wq_off = self._wq_pending = self._wq_peak = 0
         self.use_mask_bits = True          # bit-packed ReLU gates for the wide 1x1 data gradients (False: bf16 activations as masks)
-        self._wstream = torch.cuda.Stream() if (torch.cuda.is_available() and self.device.type == "cuda") else None
-        self._tstream = torch.cuda.Stream() if self._wstream is not None else None      # P6/P7 top-block dgrads
+
+    # bench.py and the tests assign these between steps; the scheduler reads them at every call
+    async_wgrad = property(lambda self: self.wgrads.async_wgrad, lambda self, v: setattr(self.wgrads, "async_wgrad", v))
+    wgrad_queue_mode = property(lambda self: self.wgrads.queue_mode, lambda self, v: setattr(self.wgrads, "queue_mode", v))
+    _tstream = property(lambda self: self.wgrads.tstream)
+    fp8_scale_log = property(lambda self: self.fp8_scaler.scale_log)
+    fp8_group_scales = property(lambda self: self.fp8_scaler.group_scales)
+    fp8_last_fill = property(lambda self: self.fp8_scaler.last_fill)
 
     # ------------------------------------------------------------------------------------------------
     # construction
@@ -225,190 +155,60 @@ class FPNDetector:
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.reserve(self.arena)
         self.arena.allocate()
-        # BASELINE config 5: fp8-e4m3 weights (one scale per output channel) for the forward of the 3x3 convolutions -- where a
-        # quantised copy of the input is read nine times; the HBM-bound 1x1 layers and the whole backward pass stay bf16
         self.fuse_stem_pool = bool(m.get("FUSE_STEM_POOL", True))
         # frozen bottleneck blocks (layer1 under FREEZE_AT = 2) in one launch each: the two mid tensors and the residual re-read never
         # reach HBM (bd_bottleneck_fwd; False: the three / four bd_conv2d_fwd launches, kept as the parity reference)
         self.fuse_frozen_blocks = bool(m.get("FUSE_FROZEN_BLOCKS", True))
         self.sparse_shortcut_grad = bool(m.get("SPARSE_SHORTCUT_GRAD", True))   # False: the shortcut's data gradient as a full-resolution pass (A/B)
         self.weight_dtype = m.get("WEIGHT_DTYPE", "bf16")
-        # FP8_DGRAD (default True again since round 3): e5m2 gradients x e4m3 weights for the data gradients of the fp8 layers, +2.5-3.5 % on
-        # the step.  Round 2 had to make it opt-in: with ONE delayed scale for all layers R101 at the batch-32 learning rate left the
-        # finite range between steps 620 and 1 020 of the repeated-batch run.  Round 3: one scale per backward phase (FP8_SCALE_GROUPS)
-        # with two binades of headroom below e5m2's maximum and a four-probe history -- see _fp8_probe_end and DESIGN.md (a21).
-        fp8_dgrad_default = True
-        # Initial (pre-probe) scale of the e5m2 gradients.  Every loss is normalised by a count that grows with the batch (num_fg, sample
-        # counts), so the gradients shrink like 1 / batch: a fixed 4 096 put the head's gradients of a 32-image batch next to e5m2's
-        # subnormals for the first FP8_AMAX_DELAY steps (tests/test_bench_batch_gpu.py: cls_subnet weight gradient 51 % off the batch-2
-        # one).  4 096 was tuned on two images; the default follows the batch in powers of two until the first probe takes over.
-        fp8_scale0 = 4096.0 * 2.0 ** max(0, int(round(np.log2(max(1, int(m.get("BATCHSIZE", 2))) / 2.0))))
         self._q8 = {}
         # e5m2 twins of gradients written by the producing launch (False: every fp8 data gradient casts its input in a pass; a test knob)
         self.fp8_grad_twins = bool(m.get("FP8_GRAD_TWINS", True))
+        assert self.weight_dtype in ("bf16", "fp8_e4m3"), self.weight_dtype
         if self.weight_dtype == "fp8_e4m3":
-            side = {id(getattr(self, n)) for n in ("p6", "p7") if hasattr(self, n)}
-            for c in self.convs.values():
-                # the staggered fp8 patch kernel serves 3x3 / stride 1 with Cout > 128 (1.6x the bf16 kernel); the top block's stride-2
-                # convolutions go through the generic fp8 kernel (faster than their bf16 launches, and they complete the pyramid's e4m3
-                # twin); narrower or strided backbone layers are FASTER on their bf16 kernels and stay there
-                if (c.k == 3 and c.cin % 16 == 0 and not isinstance(c, FCLayer)
-                        and ((c.stride == 1 and c.cout > 128) or id(c) in side)):
-                    key = "side" if id(c) in side else "main"          # P6 / P7 run on a side stream: their own scratch
-                    c.enable_fp8(lambda n, key=key: self._q8_buf(key, n), m.get("FP8_ACT_SCALE", 1.0),
-                                 dgrad=bool(m.get("FP8_DGRAD", fp8_dgrad_default)), grad_scale=m.get("FP8_GRAD_SCALE", fp8_scale0),
-                                 # FP8_WGRAD: 0 = bf16 weight gradients, 1 = the one-byte kernel (bd_conv2d_wgrad_fp8) for the bias-free
-                                 # layers (backbone conv2), 2 (default since round 4) = also the towers.  Exact on representable inputs;
-                                 # 1.4x the bf16 ring kernel per head-tower launch.  Round 2 kept it opt-in (no gain in the step then,
-                                 # and a repeated-batch run under the static scale lost convergence); under per-group delayed scales and
-                                 # stochastic rounding: R101 batch 32 same box 487.6 / 487.6 img/s at 0, 494.5 / 496.4 at 2; ten of ten
-                                 # seeds through 1 500 repeated-batch steps (profiles/r04_fp8_stability_wgrad.txt; bf16 and the
-                                 # FP8_WGRAD = 0 form: nine of ten each); whole-model gradient cosine vs bf16 0.9814 (0.9818 at 0) at
-                                 # 2 x 800 x 1344 (tests/test_r101_gpu.py)
-                                 wgrad=(int(m.get("FP8_WGRAD", 2)) >= (2 if c.has_bias else 1)) and bool(m.get("FP8_DGRAD", fp8_dgrad_default)))
-            # the bottleneck 1x1s around an fp8 3x3 (res4 / res5 blocks after the first) on one-byte operands.  In isolation the reducing
-            # direction (conv1 forward, conv3's data gradient: the input is most of the bytes) is 1.5 - 1.6x faster than its bf16 launch
-            # and the expanding one about even; in the step the extra twins the neighbouring launches must write take most of it back:
-            # R101 batch 32, one box: 461.3 img/s without, 463.9 with both directions (the default), 458.5 with the reducing one only
-            if bool(m.get("FP8_1X1", True)):
-                for blk in self.blocks:
-                    if blk["kind"] == "bottleneck" and blk["convs"][1].fp8 and blk["convs"][1].stride == 1:
-                        for c in (blk["convs"][0], blk["convs"][2]):
-                            if c.cin % 32 == 0 and c.cout % 32 == 0:
-                                c.enable_fp8_1x1(m.get("FP8_ACT_SCALE", 1.0), dgrad=bool(m.get("FP8_DGRAD", fp8_dgrad_default)),
-                                                 grad_scale=m.get("FP8_GRAD_SCALE", fp8_scale0),
-                                                 expanding=bool(m.get("FP8_1X1_EXPANDING", True)))
-        else:
-            assert self.weight_dtype == "bf16", self.weight_dtype
-        # Delayed scaling of the e5m2 gradients (the reference's hook for this is the AMP GradScaler, solver/default_solver.py:66-76): one
-        # scale for all fp8 data gradients (twins pass from layer to layer, so the layers must agree on it), re-derived every
-        # FP8_AMAX_INTERVAL steps from max |g| over the gradients those launches consume -- measured by bd_absmax_bf16 on the probe step,
-        # copied to the host asynchronously and applied FP8_AMAX_DELAY steps later, after that step's data gradients and before its
-        # weight repack, so that quantisation and the folded 1 / scale of the packed weights always agree.  A static scale underflows
-        # once training has shrunk the gradients: 4 096 diverged after ~1 500 steps of the repeated-batch run, 65 536 did not.
-        self._fp8_grad_layers = [c for c in self.convs.values() if c.fp8_dgrad or c.fp8_1x1_dgrad or c.fp8_wgrad]
-        if self._fp8_grad_layers:
-            for c in self.convs.values():             # one scale everywhere at the start (a twin's producer reads it off the consumer's layer object)
-                c.grad_scale = float(m.get("FP8_GRAD_SCALE", fp8_scale0))
-        self.fp8_delayed_scaling = bool(m.get("FP8_DELAYED_SCALING", True)) and bool(self._fp8_grad_layers) and self.device.type == "cuda"
-        # Stochastic rounding of those gradients (bd_conv_desc.sr_seed): round-to-nearest e5m2 repeats the same error on the
-        # same value every step, which a repeated batch turns into a drift (the long repeated-batch runs)
-        self.fp8_stochastic_rounding = bool(m.get("FP8_STOCHASTIC_ROUNDING", True)) and bool(self._fp8_grad_layers) and self.device.type == "cuda"
-        self.fp8_amax_interval = int(m.get("FP8_AMAX_INTERVAL", 10))
-        self.fp8_amax_delay = int(m.get("FP8_AMAX_DELAY", 4))
-        self.fp8_amax_history = max(1, int(m.get("FP8_AMAX_HISTORY", 4)))         # probes whose maximum sets the scale
-        # max |g| * scale lands in (2^(t-1), 2^t]; e5m2 tops out at 1.75 * 2^15 and everything above is CLAMPED.  One global scale: t = 15 (R50:
-        # 12 and the static 4 096 diverged in the 2 020-step run, 13 - 15 did not; R101 at batch 32: 14 diverged before step 1 020): only
-        # the head sits at the top of the range, every other layer has binades of headroom.  Per-group scales put EVERY group at the top,
-        # and a group whose gradients grow between two probes then saturates: R101 batch 32 at t = 15 had layer3 at 92 672 = 1.6 x the
-        # maximum at step 100 and left the finite range before step 400, while t = 12 (0.3035 after 1 500 steps) and an eight-probe
-        # history at t = 15 (0.3306) both ran through (profiles/r03_fp8_scale_groups.txt).  Round 3 shipped t = 13 with a four-probe
-        # history, a combination that had NOT run through (seed 0 diverged on it, same file, section 2): the default is t = 12 with the
-        # four-probe history, the combination that did; the round-4 seed matrix is profiles/r04_fp8_stability.txt.
-        self.fp8_amax_target = float(m.get("FP8_AMAX_TARGET_LOG2", 15.0 if str(m.get("FP8_SCALE_GROUPS", "group")) == "global" else 12.0))
-        # Granularity of the delayed scale (round 3).  One scale for all layers had to span the 2^9.7 spread between max |g| at the head and
-        # at the backbone's conv1 layers (scripts/exp/fp8_amax_spread.py): with the head's maximum at 2^15 the backbone's gradients sat
-        # ten binades lower and their small values flushed to zero -- R101 at the batch-32 learning rate left the finite range.  "group"
-        # (default) keeps one scale per backward phase (head / fpn / layer4 / layer3 / layer2: the all-reduce buckets), "layer" one
-        # per layer, "global" the round-2 behaviour.  Every twin is written with its CONSUMER's scale (q_scale at each hand-off) and a
-        # layer's transposed fp8 weights fold in 1 / its own scale, so any partition is consistent.
-        self.fp8_scale_groups = str(m.get("FP8_SCALE_GROUPS", "group"))
-        assert self.fp8_scale_groups in ("global", "group", "layer"), self.fp8_scale_groups
-        self._fp8_t, self._amax_pending, self._amax_prev = 0, None, {}
-        self._fp8_staged = None                  # {conv: scale} waiting for the next weight repack (optimizer step)
-        self.fp8_scale_log = []
-        self.fp8_group_scales = {}
-        if self.fp8_delayed_scaling:
-            n = len(self._fp8_grad_layers)
-            self._amax_dev = torch.zeros(n, dtype=torch.float32, device=self.device)
-            self._amax_host = torch.zeros(n, dtype=torch.float32).pin_memory()
-            self._probe_ctl = [False]
-            for i, c in enumerate(self._fp8_grad_layers):
-                c.amax_slot, c.probe_ctl = self._amax_dev[i:i + 1], self._probe_ctl
+            self._enable_fp8_layers()
+        self.fp8_scaler = Fp8GradScaler(m, dev, self.convs)
         self._bind_params(params)
 
-    def _fp8_probe_begin(self):
-        if self.fp8_stochastic_rounding:          # this step's e5m2 quantisers: a new hash seed per step (reset at the end of backward)
-            ops.fp8_set_stochastic_rounding(((self._fp8_t + 1) * 2654435761 + 0x9E3779B9) | 1)
-        if not self.fp8_delayed_scaling:
-            self._fp8_t += 1
-            return False
-        t = self._fp8_t
-        self._fp8_t += 1
-        if self._amax_pending is None and t % self.fp8_amax_interval == 0:
-            self._amax_dev.zero_()
-            self._probe_ctl[0] = True
-            return True
-        return False
-
-    def _fp8_scale_key(self, c):
-        if self.fp8_scale_groups == "global":
-            return "all"
-        if self.fp8_scale_groups == "layer":
-            return "fpn_output" if "fpn_output" in c.name else c.name      # the output convolutions all read ONE twin of dL/dP
-        n = c.name
-        if n.startswith(("head.", "rpn.", "rcnn.")):
-            return "head"
-        if "fpn_" in n or "top_block" in n:
-            return "fpn"
-        return n.split(".")[2] if n.startswith("backbone.bottom_up.") else "head"
-
-    def _fp8_apply_staged(self):
-        """New gradient scales take effect HERE, together with the weight repack that folds 1 / scale into the transposed fp8 weights
-        (repack_trainable, i.e. the optimizer step): a second backward() without a step keeps quantisers and weights consistent."""
-        st, self._fp8_staged = self._fp8_staged, None
-        if st:
-            for c, sc in st.items():
-                c.grad_scale = sc
-
-    def _fp8_probe_end(self, probing):
-        if self.fp8_stochastic_rounding:
-            ops.fp8_set_stochastic_rounding(0)
-        if not self.fp8_delayed_scaling:
-            return
-        t = self._fp8_t - 1
-        if probing:
-            self._probe_ctl[0] = False
-            from .. import comm as _comm
-            cm = _comm.get_comm()
-            if cm is not None and cm.world > 1:       # every rank quantises with the same scales: max |g| over the ranks
-                cm.allreduce_async(self._amax_dev, [torch.cuda.current_stream()], "max")
-                cm.wait()
-            self._amax_host.copy_(self._amax_dev, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._amax_pending = (ev, t)
-        elif self._amax_pending is not None and t >= self._amax_pending[1] + self.fp8_amax_delay:
-            ev, t0 = self._amax_pending
-            ev.synchronize()                      # long done: the host runs a few steps ahead of the device, not FP8_AMAX_DELAY + the queue
-            self._amax_pending = None
-            am = self._amax_host.numpy().astype(np.float64)
-            keys = {}
-            for i, c in enumerate(self._fp8_grad_layers):
-                k = self._fp8_scale_key(c)
-                if np.isfinite(am[i]):
-                    keys[k] = max(keys.get(k, 0.0), float(am[i]))
-            scales = {}
-            # diagnostic: where the probe's largest value sat in e5m2's range under the scale it was quantised with (> 57 344: clamped)
-            cur = {self._fp8_scale_key(c): c.grad_scale for c in self._fp8_grad_layers}
-            self.fp8_last_fill = {k: a * cur[k] for k, a in keys.items()}
-            for k, amax in keys.items():
-                if amax > 0.0:
-                    hist = self._amax_prev.setdefault(k, [])          # probe history: a scale never chases a single small reading
-                    hist.append(amax)
-                    del hist[:-self.fp8_amax_history]
-                    eff = max(hist)
-                    scales[k] = float(2.0 ** min(max(np.floor(self.fp8_amax_target - np.log2(eff)), -16.0), 40.0))
-            if scales:
-                staged = {}
-                for c in self.convs.values():         # every layer of a group (a twin's producer reads the scale off its CONSUMER's layer object)
-                    k = self._fp8_scale_key(c)
-                    if k in scales:
-                        staged[c] = scales[k]
-                self._fp8_staged = staged
-                self.fp8_group_scales.update(scales)
-                top = max(keys.values())
-                self.fp8_scale_log.append((t0, t, top, min(scales.values())))
+    def _enable_fp8_layers(self):
+        """BASELINE config 5: fp8-e4m3 weights (one scale per output channel) for the forward of the 3x3 convolutions -- where a
+        quantised copy of the input is read nine times; the HBM-bound 1x1 layers and the whole backward pass stay bf16."""
+        m = self.cfg.MODEL
+        # FP8_DGRAD (default True again since round 3): e5m2 gradients x e4m3 weights for the data gradients of the fp8 layers, +2.5-3.5 % on
+        # the step.  Round 2 had to make it opt-in: with ONE delayed scale for all layers R101 at the batch-32 learning rate left the
+        # finite range between steps 620 and 1 020 of the repeated-batch run.  Round 3: one scale per backward phase (FP8_SCALE_GROUPS)
+        # with two binades of headroom below e5m2's maximum and a four-probe history -- see fp8_scaling.py and DESIGN.md (a21).
+        dgrad = bool(m.get("FP8_DGRAD", True))
+        scale0 = initial_grad_scale(m)
+        side = {id(getattr(self, n)) for n in ("p6", "p7") if hasattr(self, n)}
+        for c in self.convs.values():
+            # the staggered fp8 patch kernel serves 3x3 / stride 1 with Cout > 128 (1.6x the bf16 kernel); the top block's stride-2
+            # convolutions go through the generic fp8 kernel (faster than their bf16 launches, and they complete the pyramid's e4m3
+            # twin); narrower or strided backbone layers are FASTER on their bf16 kernels and stay there
+            if (c.k == 3 and c.cin % 16 == 0 and not isinstance(c, FCLayer)
+                    and ((c.stride == 1 and c.cout > 128) or id(c) in side)):
+                key = "side" if id(c) in side else "main"          # P6 / P7 run on a side stream: their own scratch
+                c.enable_fp8(lambda n, key=key: self._q8_buf(key, n), m.get("FP8_ACT_SCALE", 1.0), dgrad=dgrad, grad_scale=scale0,
+                             # FP8_WGRAD: 0 = bf16 weight gradients, 1 = the one-byte kernel (bd_conv2d_wgrad_fp8) for the bias-free
+                             # layers (backbone conv2), 2 (default since round 4) = also the towers.  Exact on representable inputs;
+                             # 1.4x the bf16 ring kernel per head-tower launch.  Round 2 kept it opt-in (no gain in the step then,
+                             # and a repeated-batch run under the static scale lost convergence); under per-group delayed scales and
+                             # stochastic rounding: R101 batch 32 same box 487.6 / 487.6 img/s at 0, 494.5 / 496.4 at 2; ten of ten
+                             # seeds through 1 500 repeated-batch steps (profiles/r04_fp8_stability_wgrad.txt; bf16 and the
+                             # FP8_WGRAD = 0 form: nine of ten each); whole-model gradient cosine vs bf16 0.9814 (0.9818 at 0) at
+                             # 2 x 800 x 1344 (tests/test_r101_gpu.py)
+                             wgrad=(int(m.get("FP8_WGRAD", 2)) >= (2 if c.has_bias else 1)) and dgrad)
+        # the bottleneck 1x1s around an fp8 3x3 (res4 / res5 blocks after the first) on one-byte operands.  In isolation the reducing
+        # direction (conv1 forward, conv3's data gradient: the input is most of the bytes) is 1.5 - 1.6x faster than its bf16 launch
+        # and the expanding one about even; in the step the extra twins the neighbouring launches must write take most of it back:
+        # R101 batch 32, one box: 461.3 img/s without, 463.9 with both directions (the default), 458.5 with the reducing one only
+        if bool(m.get("FP8_1X1", True)):
+            for blk in self.blocks:
+                if blk["kind"] == "bottleneck" and blk["convs"][1].fp8 and blk["convs"][1].stride == 1:
+                    for c in (blk["convs"][0], blk["convs"][2]):
+                        if c.cin % 32 == 0 and c.cout % 32 == 0:
+                            c.enable_fp8_1x1(m.get("FP8_ACT_SCALE", 1.0), dgrad=dgrad, grad_scale=scale0,
+                                             expanding=bool(m.get("FP8_1X1_EXPANDING", True)))
 
     def _bind_params(self, params):
         """(Re)load every parameter from a reference-layout dict (name -> numpy) and refresh the packed bf16 copies."""
@@ -448,8 +248,8 @@ class FPNDetector:
     def repack_trainable(self):
         """All trainable convs in ONE launch (bd_weight_pack_multi); the table holds raw pointers into the arena and the packed
         tensors, which never move after _build_layers."""
-        self._fp8_apply_staged()
-        if getattr(self, "_pack_table", None) is None:
+        self.fp8_scaler.apply_staged()
+        if self._pack_table is None:
             ent = [(c.w, c.row_scale, c.w_fwd, c.w_dgrad, c.cout, c.k * c.k, c.cin) for c in self.convs.values()
                    if c.trainable and not isinstance(c, DeconvLayer)]
             self._pack_table = ops.build_pack_table(ent, self.device)
@@ -682,60 +482,15 @@ class FPNDetector:
         need = max(need, self._head_wgrad_ws_bytes(pl))
         pl.wgrad_ws = C.empty((need // 4 + 64,), torch.float32)
         pl.colsum_ws = C.empty((ops.colsum_workspace_bytes(2048) // 4,), torch.float32)
-        self._place(pl)
+        self.plan_arena.place(pl)
         self._plans[key] = pl
         return pl
 
     # ------------------------------------------------------------------------------------------------
     # plan arena
     # ------------------------------------------------------------------------------------------------
-    def _place(self, pl):
-        """Swap the carved placeholders of a new plan for views into the arena (grown first if the plan needs more bytes)."""
-        c = pl._carve
-        self._grow_arena(c.nbytes)
-        buf = self._arena_buf
-
-        def place(t):
-            if not t.is_meta:
-                return t
-            off, ph = c.slots[id(t)]
-            assert ph is t, "a meta tensor that the carver did not lay out"
-            return buf[off: off + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
-
-        _map_tensors(pl, place)
-        c.slots = None
-
-    def _grow_arena(self, nbytes):
-        """Replace the arena by a larger one.  The old storage is freed only once no stream can still touch it (device synchronisation:
-        growth happens a few times per run at most); its contents move along, so the last step's buffers stay readable, and every cached
-        plan's views are re-based onto the new storage at the same offsets."""
-        have = 0 if self._arena_buf is None else self._arena_buf.numel()
-        if nbytes <= have:
-            return
-        nbytes = _round_up(nbytes, 2 << 20)
-        old = self._arena_buf
-        if old is not None and self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        new = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
-        if old is not None:
-            new[:have].copy_(old)
-            base = old.data_ptr()
-
-            def rebase(t):
-                if t.device != new.device or t.untyped_storage().data_ptr() != base:
-                    return t
-                off = t.data_ptr() - base
-                return new[off: off + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
-
-            for p in self._plans.values():
-                _map_tensors(p, rebase)
-        self._arena_buf = new
-        self.arena_grows += 1
-
-    @property
-    def arena_bytes(self):
-        """Bytes of the plan arena (what the largest plan seen so far needs, rounded up to 2 MiB)."""
-        return 0 if self._arena_buf is None else self._arena_buf.numel()
+    arena_bytes = property(lambda self: self.plan_arena.nbytes)
+    arena_grows = property(lambda self: self.plan_arena.grows)
 
     @staticmethod
     def plan_bytes(pl):
@@ -747,37 +502,11 @@ class FPNDetector:
         Returns the plan of that padded shape."""
         return self._plan(N, _round_up(H, 32), _round_up(W, 32))
 
-    def _join_side_streams(self):
-        """The current stream waits for the side streams that touch plan memory or model scratch (weight gradients, _tstream)."""
-        if self._wstream is not None and self.device.type == "cuda":
-            cur = torch.cuda.current_stream()
-            cur.wait_stream(self._wstream)
-            cur.wait_stream(self._tstream)
-
     def _bind_plan(self, pl):
-        """Start of a step at plan pl.  When another plan used the arena since pl's last step, every buffer of pl's can hold that plan's
-        data: the main stream first waits for every stream that touched plan memory (the weight-gradient stream, _tstream; the
-        communicator only reads the parameter arena and the FCOS statistics, behind a wait of its own), then the buffers whose start
-        state is all-zero (counters, loss sums, d_rpn_raw's padding channel) are cleared -- as torch.zeros did once per plan."""
-        if self._bound is pl:
-            return
-        if self._bound is not None:
-            self._join_side_streams()
-        buf = self._arena_buf
-        for off, n in pl._carve.zero:
-            buf[off: off + n].zero_()
-        self._bound = pl
+        self.plan_arena.bind(pl)
 
     def _scratch(self, name, nbytes):
-        """Model-level grow-only uint8 workspace (its size follows the batch -- Gmax -- rather than the shape).  Before a smaller one is
-        freed the current stream waits for the side streams, so that no later allocation on it can overlap a reader still running."""
-        nbytes = max(int(nbytes), 1)
-        t = self._scratch_bufs.get(name)
-        if t is None or t.numel() < nbytes:
-            if t is not None:
-                self._join_side_streams()
-            t = self._scratch_bufs[name] = torch.empty((_round_up(nbytes, 256),), dtype=torch.uint8, device=self.device)
-        return t[:nbytes]
+        return self.plan_arena.scratch(name, nbytes)
 
     def _head_wgrad_ws_bytes(self, pl):
         return max(c.wgrad_ws_bytes(pl.pyr, pl.pyr) for c in self._head_convs())
@@ -818,13 +547,13 @@ class FPNDetector:
         chunk into pinned memory and every chunk leaves with its own DMA as soon as it is converted (conversion under transfer).
         Round 2 converted the whole batch with one host copy first: 13-20 ms of the reference-protocol step."""
         arr = image.numpy() if torch.is_tensor(image) else np.asarray(image)
-        st = getattr(self, "_stager", None)
+        st = self._stager
         if st is None:
             st = self._stager = ops.HostStager(self.device, int(self.cfg.MODEL.get("H2D_THREADS", 0)))
         if not st.supports(arr):
             arr = np.ascontiguousarray(arr, dtype=np.float32)
         # one grow-only destination for every input shape (the copies and their reader, bd_pad_normalize, run on the current stream)
-        buf = getattr(self, "_h2d_buf", None)
+        buf = self._h2d_buf
         if buf is None or buf.numel() < arr.size:
             buf = self._h2d_buf = torch.empty((arr.size,), dtype=torch.float32, device=self.device)
         dst = self._h2d_dst = buf[: arr.size].view(arr.shape)
@@ -833,7 +562,7 @@ class FPNDetector:
     def _block_forward(self, blk, b, x, x8=None):
         """x8: the e4m3 twin of the block input when the previous block's conv3 wrote one (fp8 mode)."""
         convs = blk["convs"]
-        if getattr(b, "fused", False):
+        if b.fused:
             ds = blk["ds"]
             return ops.bottleneck_fwd(b.gin.N, b.gin.H[0], b.gin.W[0], blk["cin"], blk["ch"], blk["cout"], x, convs[0].w_fwd, convs[0].b,
                                       convs[1].w_fwd, convs[1].b, convs[2].w_fwd, convs[2].b, ds.w_fwd if ds is not None else None,
@@ -846,14 +575,14 @@ class FPNDetector:
         t, t8 = x, x8
         for ci, c in enumerate(convs[:-1]):
             y8 = None
-            if ci == 0 and getattr(b, "mid8", None) is not None:
+            if ci == 0 and b.mid8 is not None:
                 y8 = b.mid8
-            elif ci == 1 and getattr(b, "mid8b", None) is not None:
+            elif ci == 1 and b.mid8b is not None:
                 y8 = b.mid8b
             c.forward(t, geos[ci], geos[ci + 1], b.mids[ci], relu=True, x8=t8, y8=y8,
                       q_scale=convs[ci + 1].act_scale if y8 is not None else 1.0)
             t, t8 = b.mids[ci], y8
-        convs[-1].forward(t, geos[-2], geos[-1], b.out, add=idt, relu=True, bits=b.out_bits, x8=t8, y8=getattr(b, "out8", None))
+        convs[-1].forward(t, geos[-2], geos[-1], b.out, add=idt, relu=True, bits=b.out_bits, x8=t8, y8=b.out8)
         return b.out
 
     def network_forward(self, pl):
@@ -869,12 +598,12 @@ class FPNDetector:
         x8 = None
         for blk, b in zip(self.blocks, pl.blk):
             x = self._block_forward(blk, b, x, x8)
-            x8 = getattr(b, "out8", None)
+            x8 = b.out8
         # FPN (fpn_backbone.py:123-160): top-down from the coarsest level
         st = self.fpn_stages
         nl = len(st)
         b5 = pl.blk[pl.res[st[-1]]]
-        side = self._wstream if (self.TOP_BLOCK == "p6p7" and self.async_wgrad and self._wstream is not None) else None
+        side = self.wgrads.side() if self.TOP_BLOCK == "p6p7" else None
         if self.TOP_BLOCK == "p6p7":
             # LastLevelP6P7 (:198-204) only needs res5 and writes its own pyramid levels: its two small-grid convs (70 workgroups for
             # P6 at 800x1344) run on the side stream, concurrently with the lateral / output convs below
@@ -952,72 +681,20 @@ class FPNDetector:
     # backward (replaces GradManager.backward, solver/default_solver.py:118-124)
     # ------------------------------------------------------------------------------------------------
     def _wgrad(self, conv, x, g, gin, gout, ws, cws=None, x8=None, g8=None):
-        """conv.wgrad on the side stream: it only needs x and g as they are NOW (everything enqueued so far on the main
-        stream), and nothing on the main stream reads its outputs before `_join_wgrads`.  Callers must not overwrite g/x
-        later in the same backward pass (the heads keep one gradient buffer per layer for that reason)."""
-        q = None
-        if self.wgrad_queue_mode != "layer" and self.device.type == "cuda" and not (conv.fp8_wgrad and x8 is not None and g8 is not None):
-            # deferred reduce: this layer's partial sums get their own slice of the model's arena, untouched until the next flush (a
-            # gradient bucket's end, or the byte threshold).  A layer that does not fit (the first backward pass of a model, a larger
-            # input size, another set of queued layers) runs un-queued on the plan's shared workspace -- same bits -- and the arena is
-            # re-grown to the recorded peak at _join_wgrads
-            key = (conv.name, gin.N, tuple(gin.H), tuple(gin.W), tuple(gout.H), tuple(gout.W))
-            need = self._wq_need.get(key)
-            if need is None:
-                need = self._wq_need[key] = (conv.wgrad_ws_bytes(gin, gout) + 255) // 256 * 256
-            off = self._wq_off
-            self._wq_off = off + need
-            arena = self._wq_arena
-            if arena is not None and off + need <= arena.numel() * 4:
-                ws = arena[off // 4: (off + need) // 4]
-                self._wq_pending += need
-                if self._wq is None:
-                    self._wq = ops.WgradQueue()
-                q = self._wq
-        if not (self.async_wgrad and self._wstream is not None):
-            conv.wgrad(x, g, gin, gout, ws, cws, x8=x8, g8=g8, queue=q)
-        else:
-            self._wstream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._wstream):
-                conv.wgrad(x, g, gin, gout, ws, cws, x8=x8, g8=g8, queue=q)
-        if q is not None and isinstance(self.wgrad_queue_mode, int) and self._wq_pending >= self.wgrad_queue_mode:
-            self._flush_wgrads()
+        self.wgrads.run(conv, x, g, gin, gout, ws, cws, x8, g8)
 
     def _begin_wgrads(self):
-        """Start of a backward pass (also the head modules' own, layers/modules.py): the arena is free from offset 0 -- UNLESS partial sums
-        are already waiting for the head bucket's flush: Faster R-CNN runs its RPN head's backward inside get_losses, under the proposal
-        chain, and those slices must survive until then.  (Rounds 4's reset here let the box head's kernels overwrite them: the RPN
-        weight gradients of every queued step were wrong -- found by tests/test_wgrad_queue_gpu.py, the first test of the queued path.)"""
-        if self._wq is None or not self._wq.pending():
-            self._wq_off = self._wq_pending = 0
+        self.wgrads.begin()
 
     def _flush_wgrads(self):
-        """One launch reduces every weight gradient queued since the last flush (on the stream the partial sums were computed on); the
-        arena is free again from offset 0 for the kernels enqueued behind that reduce."""
-        self._wq_peak = max(self._wq_peak, self._wq_off)
-        self._wq_off = self._wq_pending = 0
-        q = self._wq
-        if q is None or not q.pending():
-            return
-        if self.async_wgrad and self._wstream is not None:
-            with torch.cuda.stream(self._wstream):
-                q.flush()
-        else:
-            q.flush()
+        self.wgrads.flush()
 
     def _join_wgrads(self):
-        self._flush_wgrads()
-        if self.async_wgrad and self._wstream is not None:
-            torch.cuda.current_stream().wait_stream(self._wstream)
-        have = 0 if self._wq_arena is None else self._wq_arena.numel() * 4
-        if self.wgrad_queue_mode != "layer" and self._wq_peak > have:
-            # (behind the join: the old arena's last readers have been ordered in front of the current stream, which owns both allocations)
-            self._wq_arena = None
-            self._wq_arena = torch.empty((self._wq_peak // 4 + 64,), dtype=torch.float32, device=self.device)
+        self.wgrads.join()
 
     def backward(self, on_bucket_ready=None):
         pl = self._cur
-        probing = self._fp8_probe_begin()
+        probing = self.fp8_scaler.begin_step()
         self._begin_wgrads()
         ws, cws = pl.wgrad_ws, pl.colsum_ws
         pyr = pl.pyr
@@ -1025,7 +702,8 @@ class FPNDetector:
         for b in pl.blk:
             b.g_out8_ready = False
         self.head_backward(pl, ws, cws)
-        side = (self._wstream,) if (self.async_wgrad and self._wstream is not None) else ()
+        wside = self.wgrads.side()
+        side = (wside,) if wside is not None else ()
         self._flush_wgrads()
         if on_bucket_ready:
             on_bucket_ready("head", side)
@@ -1039,7 +717,7 @@ class FPNDetector:
             # P7 = conv(relu(P6)): d P6 = dgrad(g_P7) * (P6 > 0) + g_P6(head), written in place into g_P's P6 level
             # The two dgrads are small grids that only touch the P6/P7 levels of g_P and res5's gradient, which the main stream
             # does not read before the top lateral dgrad below: they run on their own stream next to the P3.. output-conv dgrads.
-            top = self._tstream if self.async_wgrad else None
+            top = self.wgrads.top()
             self._wgrad(self.p7, pl.p6_relu, pl.g_P, pl.g_p6r, g7, ws, cws)
             if top is not None:
                 top.wait_stream(torch.cuda.current_stream())
@@ -1071,8 +749,8 @@ class FPNDetector:
             if not self.blocks[pl.res[s]]["trainable"]:
                 continue                                   # res2 of a FREEZE_AT=2 backbone: nothing below needs the gradient
             if is_top:
-                if not pool_top and self._tstream is not None and self.async_wgrad:
-                    torch.cuda.current_stream().wait_stream(self._tstream)
+                if not pool_top and top is not None:
+                    torch.cuda.current_stream().wait_stream(top)
                 self.lateral[s].dgrad(pl.g_lat[s], b.gout, b.gout, b.g_out, first=pool_top, mask=b.out, maskbits=b.out_bits)
             else:
                 self.lateral[s].dgrad(pl.g_lat[s], b.gout, b.gout, b.g_out, first=True)
@@ -1098,16 +776,16 @@ class FPNDetector:
             # main branch, last conv backwards
             g = G
             # fp8 mode: the e5m2 twin of the block's output gradient, written by the next block's conv1 data gradient (its last writer)
-            g8 = b.g_out8 if (getattr(b, "g_out8", None) is not None and b.g_out8_ready) else None
+            g8 = b.g_out8 if (b.g_out8 is not None and b.g_out8_ready) else None
             for ci in range(len(convs) - 1, 0, -1):
                 # conv2's weight gradient from the twins both neighbours wrote (conv1's forward output, conv3's data gradient)
-                wx8 = getattr(b, "mid8", None) if (ci == 1 and len(convs) == 3) else None
+                wx8 = b.mid8 if (ci == 1 and len(convs) == 3) else None
                 self._wgrad(convs[ci], b.mids[ci - 1], g, geos[ci], geos[ci + 1], ws, x8=wx8, g8=g8 if wx8 is not None else None)
                 # conv3's (dense 1x1) data gradient also writes the e5m2 twin that conv2's fp8 data gradient reads, conv2's the one
                 # conv1's reads
                 nxt = None
                 if len(convs) == 3:
-                    nxt = getattr(b, "g_mid8", None) if ci == 2 else getattr(b, "g_mid8a", None)
+                    nxt = b.g_mid8 if ci == 2 else b.g_mid8a
                 if nxt is not None and not convs[ci].dgrad_writes_twin(geos[ci], geos[ci + 1]):
                     nxt = None
                 wrote = convs[ci].dgrad(g, geos[ci], geos[ci + 1], b.g_mids[ci - 1], mask=b.mids[ci - 1], g8=g8, dx8=nxt,
@@ -1122,7 +800,7 @@ class FPNDetector:
                 # conv1's data gradient is the LAST writer of the previous block's output gradient: it also writes that gradient's e5m2
                 # twin (fp8 mode) for the previous block's conv3
                 pb = pl.blk[bi - 1]
-                gx8 = getattr(pb, "g_out8", None)
+                gx8 = pb.g_out8
                 # ... written with the scale of its consumer, the previous block's conv3 (another scale group at a layer boundary)
                 kw = dict(mask=xin, maskbits=xbits, g8=g8, dx8=gx8, q_scale=self.blocks[bi - 1]["convs"][-1].grad_scale)
                 if blk["ds"] is not None and gx8 is None and self.sparse_shortcut_grad:
@@ -1147,5 +825,5 @@ class FPNDetector:
                 if on_bucket_ready:
                     on_bucket_ready(f"layer{blk['layer']}", side)
         self._join_wgrads()
-        self._fp8_probe_end(probing)
+        self.fp8_scaler.end_step(probing)
 

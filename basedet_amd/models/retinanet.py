@@ -125,13 +125,12 @@ class RetinaNet(FPNDetector):
         # gradients on the main stream (bench.py's instrumented steps, --serial-wgrad) stay serial here too: clean per-kernel durations.
         side = None
         # (bf16 only: in fp8 mode the tower convolutions may share the main stream's cast scratch)
-        # The second stream is the model's EXISTING side stream (_tstream: the target assignment at the start of the forward pass, long done
+        # The second stream is the model's EXISTING side stream (the top-block stream: the target assignment at the start of the forward pass, long done
         # here; the top block's data gradients in the backward pass).  A stream of its own made five per process under torch.distributed (main,
         # weight gradients, side, communicator, this one) and the step lost 2.8 ms (577 against 643 img/s with one rank and a forced
         # all-reduce: profiles/r06_head_towers_ab.txt; cause not established -- GPU_MAX_HW_QUEUES=8 did not remove it).
-        if (bool(self.cfg.MODEL.get("HEAD_TOWERS_CONCURRENT", True)) and self.device.type == "cuda" and self.async_wgrad
-                and self._tstream is not None and self.weight_dtype != "fp8_e4m3"):
-            side = self._tstream
+        if bool(self.cfg.MODEL.get("HEAD_TOWERS_CONCURRENT", True)) and self.wgrads.top() is not None and self.weight_dtype != "fp8_e4m3":
+            side = self.wgrads.top()
             side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side) if side is not None else _nullcontext():
             t, t8 = pl.P, getattr(pl, "P8", None)
@@ -159,7 +158,7 @@ class RetinaNet(FPNDetector):
         thr = m.MATCHER.THRESHOLDS
         # The target assignment depends on the anchors and the gt boxes only (retinanet.py:211-232), not on the network's output: its two
         # launches (~0.12 ms at 16 x 201 600 anchors) run on a side stream under the forward pass instead of between forward and losses.
-        side = self._tstream if (self.async_wgrad and self._tstream is not None and m.get("ASSIGN_ON_SIDE_STREAM", True)) else None
+        side = self.wgrads.top() if m.get("ASSIGN_ON_SIDE_STREAM", True) else None
         if side is not None:
             side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side) if side is not None else _nullcontext():

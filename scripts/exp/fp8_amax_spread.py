@@ -14,8 +14,8 @@ m = RetinaNet(cfg, params=params)
 b = next(DummyLoader(B, (800, 1344), seed=0))
 batch = {"data": torch.from_numpy(b["data"].astype(np.float32)).cuda(), "gt_boxes": torch.from_numpy(b["gt_boxes"]).cuda(), "im_info": torch.from_numpy(b["im_info"]).cuda()}
 m(batch); m.backward(); torch.cuda.synchronize()
-am = m._amax_host.numpy().copy()
-rows = sorted(zip(am, [c.name for c in m._fp8_grad_layers]), reverse=True)
+am = m.fp8_scaler.amax_host.numpy().copy()
+rows = sorted(zip(am, [c.name for c in m.fp8_scaler.grad_layers]), reverse=True)
 for a, n in rows:
     print(f"{n:50s} {a:.3e}  2^{np.log2(a) if a > 0 else float('-inf'):.1f}")
 nz = am[am > 0]

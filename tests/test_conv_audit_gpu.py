@@ -523,7 +523,7 @@ def test_dispatched_kernels_and_launch_counts(audited_step):
     assert c["bottleneck_fwd"] == len(fused) and c["stem_pool_fwd"] == 1
     assert c["conv2d_fwd"] + c["conv2d_fwd_gnstats"] == len(convs) - in_fused
     assert c["conv2d_wgrad"] + c["conv2d_wgrad_bias"] == sum(1 for cv in convs if cv.trainable)
-    assert model._wq is None                             # WGRAD_QUEUE = "layer": no deferred reduce on this step
+    assert model.wgrads.queue is None                      # WGRAD_QUEUE = "layer": no deferred reduce on this step
     if name == "retinanet":
         assert c["upsample2x_add_fwd"] == 2 and c["upsample2x_add_bwd"] == 2
         audited = set(au.stats)

@@ -66,20 +66,20 @@ def test_queued_weight_gradients_equal_the_per_layer_ones_bit_for_bit(kind):
     for mode in ("bucket", 48 << 20):
         m = _build(kind, mode)
         first = _grads(m, b)                  # the sizing pass: un-queued
-        assert m._wq_arena is not None and m._wq_peak > 0
-        peak = m._wq_peak
+        assert m.wgrads.arena is not None and m.wgrads.peak > 0
+        peak = m.wgrads.peak
         second = _grads(m, b)                 # queued: every layer in the arena, one reduce per bucket (or per 48 MB)
-        assert m._wq is not None and m._wq.pending() == 0
+        assert m.wgrads.queue is not None and m.wgrads.queue.pending() == 0
         same(first, (mode, "first")); same(second, (mode, "second"))
         assert torch.equal(first, second)
         # the arena holds the LARGEST flush interval, not the sum over the pass
-        total = sum(m._wq_need.values())
+        total = sum(m.wgrads.need.values())
         assert peak < total, (peak, total)
         # a forced overflow (arena cut to a quarter): the layers that do not fit run un-queued -- same bits -- and the arena is re-grown
-        m._wq_arena = m._wq_arena[: m._wq_arena.numel() // 4].clone()
+        m.wgrads.arena = m.wgrads.arena[: m.wgrads.arena.numel() // 4].clone()
         third = _grads(m, b)
         same(third, (mode, "overflow"))
-        assert m._wq_arena.numel() * 4 >= peak
+        assert m.wgrads.arena.numel() * 4 >= peak
     # the gradient buckets are closed in backward order with the side stream's work flushed: what the all-reduce hook sees at
     # "bucket ready" time is final (a forced hook run: the hook copies each bucket as it is announced)
     m = _build(kind, "bucket")
