@@ -163,8 +163,10 @@ def test_fcos_bench_batch_equals_tiled_batch2():
 
 
 def test_faster_rcnn_bench_batch_equals_tiled_batch2():
-    """C4: the sampling keys are tiled with the images, so image k draws the samples of image k // (B/2).  RoIAlign's backward scatters with
-    float atomics (order differs run to run): gradients are compared within tolerance, not bitwise."""
+    """C4: the sampling keys are tiled with the images, so image k draws the samples of image k // (B/2).  RoIAlign's backward is the tiled
+    fixed-order sum (bd_roi_align_bwd_bf16: the default, bitwise reproducible; the fp32 scatter with float atomics is the fallback for other
+    pooler sizes), so a batch-16 step reproduces itself bit for bit -- tests/test_frcnn_audit_gpu.py asserts that.  Batch 16 against batch 2
+    differs in the ORDER of the fp32 sums over images and RoIs: gradients are compared within tolerance, not bitwise."""
     from basedet_amd.configs import FasterRCNNConfig
     from basedet_amd.models import FasterRCNN, params as P
     from basedet_amd.utils import DummyLoader
@@ -194,6 +196,6 @@ def test_faster_rcnn_bench_batch_equals_tiled_batch2():
     _check_tiled(small, big, B, outs)
     for k in l2:
         assert abs(lB[k] - l2[k]) <= 1e-3 * abs(l2[k]), (k, lB[k], l2[k])
-    # (the packed-bf16 RoIAlign backward keeps running bf16 sums whose roundings depend on the atomics' order: 6e-3 per level, see
-    # test_rcnn_ops_gpu.py; the default fp32 scatter is order-dependent at the 1e-6 level only)
+    # (the tiled RoIAlign backward adds its fp32 sums onto the RPN head's bf16 dL/dP and rounds once: the batch-16 and batch-2 sums differ
+    # in the bf16 roundings of dL/dP along the backbone)
     _check_grads(g2, gB, "Faster R-CNN R50 b16", bound=2e-3)

@@ -1,4 +1,6 @@
 """Helpers shared by the GPU parity tests (layout conversions, reference convs on CPU fp32)."""
+import math
+
 import numpy as np
 import torch
 import torch.nn.functional as TF
@@ -229,3 +231,272 @@ def bound_ratio(got, ref, S, rel, abs_s, exact=None):
     if exact is not None:
         r = torch.where(exact, torch.where(g == ref, torch.zeros_like(r), torch.full_like(r, float("inf"))), r)
     return torch.nan_to_num(r, nan=0.0, posinf=float("inf"))
+
+
+# ---- float64 references of the launches only the Faster R-CNN step makes ---------------------------------------------------------------
+# Same conventions as conv_ref_*: torch float64 on the operands' device, S = the same operation on |operands|.
+def thin_ref_fwd(x, w, bias, chunk=1 << 18):
+    """bd_conv1x1_thin_fwd: y = x bf16(w)^T + bias; x (M, Cin) bf16, w (Cout, Cin) the fp32 MASTER weight (the kernel rounds it to bf16
+    itself).  Returns (ref, S), float64 (M, Cout)."""
+    W = w.reshape(w.shape[0], -1).to(torch.bfloat16).double()
+    b = bias.double() if bias is not None else torch.zeros(W.shape[0], dtype=torch.float64, device=x.device)
+    M = x.shape[0]
+    ref = torch.empty((M, W.shape[0]), dtype=torch.float64, device=x.device)
+    S = torch.empty_like(ref)
+    for r0 in range(0, M, chunk):
+        xi = x[r0:r0 + chunk].double()
+        ref[r0:r0 + chunk] = xi @ W.t() + b
+        S[r0:r0 + chunk] = xi.abs() @ W.abs().t() + b.abs()
+    return ref, S
+
+
+def thin_ref_bwd(x, g, w, cout_real, chunk=1 << 18, dx=True):
+    """bd_conv1x1_thin_bwd: dx = (x != 0) * g bf16(w) (x is a ReLU output: the gate is closed exactly where x is zero, and dx is an
+    exact zero there), dW = g^T x, db = sum g; rows cout_real .. of dW / db are exact zeros.
+    Returns (dx, S_dx, exact_dx, dW, S_dW, db, S_db); the first three are None with dx=False."""
+    Cout = g.shape[1]
+    W = w.reshape(Cout, -1).to(torch.bfloat16).double()
+    M, Cin = x.shape
+    dev = x.device
+    rdx = sdx = ex = None
+    if dx:
+        rdx = torch.empty((M, Cin), dtype=torch.float64, device=dev)
+        sdx = torch.empty_like(rdx)
+        ex = torch.empty((M, Cin), dtype=torch.bool, device=dev)
+    dW = torch.zeros((Cout, Cin), dtype=torch.float64, device=dev)
+    sW = torch.zeros_like(dW)
+    db = torch.zeros((Cout,), dtype=torch.float64, device=dev)
+    sb = torch.zeros_like(db)
+    for r0 in range(0, M, chunk):
+        xi, gi = x[r0:r0 + chunk].double(), g[r0:r0 + chunk].double()
+        if dx:
+            open_ = xi != 0
+            rdx[r0:r0 + chunk] = (gi @ W) * open_
+            sdx[r0:r0 + chunk] = (gi.abs() @ W.abs()) * open_
+            ex[r0:r0 + chunk] = ~open_
+        dW += gi.t() @ xi
+        sW += gi.abs().t() @ xi.abs()
+        db += gi.sum(0)
+        sb += gi.abs().sum(0)
+    for t in (dW, sW, db, sb):
+        t[cout_real:] = 0
+    return rdx, sdx, ex, dW, sW, db, sb
+
+
+def roi_levels(rois, strides, dtype):
+    """assign_rois (roi_pool.py:12-25): floor(4 + log2(sqrt(area) / 224)) clamped to the levels of `strides`, evaluated in `dtype` from
+    the fp32 boxes; a NaN or -inf argument gives the lowest level.  Returns int64 level indices."""
+    lo, hi = int(math.log2(strides[0])), int(math.log2(strides[-1]))
+    b = rois.to(dtype)
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    v = 4.0 + torch.log(torch.sqrt(area) / 224.0) / 0.6931471805599453
+    lv = torch.full(v.shape, lo, dtype=torch.int64, device=rois.device)
+    ok = (v == v) & (v > lo)
+    fl = torch.floor(torch.where(ok, v, torch.zeros_like(v))).clamp(lo, hi).to(torch.int64)
+    return torch.where(ok, torch.where(v >= hi, torch.full_like(lv, hi), fl), lv) - lo
+
+
+def _roi_samples(rois, scale, H, W, PH, PW, SP):
+    """Sample points of RoIs (r, 4) on one level in float64 (the coordinates of roi_align_fwd_kernel, from the fp32 boxes):
+    returns (idx (r, PH*PW, SP*SP, 4) int64 pixel index y * W + x of the four corners, wgt same shape float64 (zero for a sample outside
+    the [-1, size] window), cell (r, PH*PW, SP*SP) int64 index of the top-left corner, frac (r, PH*PW, SP*SP, 2) the offsets (ly, lx) of the
+    sample inside its cell)."""
+    b = rois.double()
+    dev = rois.device
+    sw, sh = b[:, 0] * scale - 0.5, b[:, 1] * scale - 0.5
+    bw, bh = ((b[:, 2] * scale - 0.5) - sw) / PW, ((b[:, 3] * scale - 0.5) - sh) / PH
+    ar = lambda n: torch.arange(n, dtype=torch.float64, device=dev)
+    # (r, P, SP) sample coordinates along each axis
+    ys = sh.view(-1, 1, 1) + ar(PH).view(1, -1, 1) * bh.view(-1, 1, 1) + (ar(SP).view(1, 1, -1) + 0.5) * bh.view(-1, 1, 1) / SP
+    xs = sw.view(-1, 1, 1) + ar(PW).view(1, -1, 1) * bw.view(-1, 1, 1) + (ar(SP).view(1, 1, -1) + 0.5) * bw.view(-1, 1, 1) / SP
+
+    def lin(c, n):
+        ok = ~((c < -1.0) | (c > n))
+        c = c.clamp_min(0.0)
+        i0 = torch.floor(c).to(torch.int64)
+        top = i0 >= n - 1
+        i0 = torch.where(top, torch.full_like(i0, n - 1), i0)
+        i1 = torch.where(top, i0, i0 + 1)
+        l = torch.where(top, torch.zeros_like(c), c - i0.double())
+        return i0, i1, 1.0 - l, l, ok
+    y0, y1, hy, ly, oky = lin(ys, H)
+    x0, x1, hx, lx, okx = lin(xs, W)
+    r = rois.shape[0]
+    # broadcast to (r, PH, PW, SPy, SPx)
+    Y = lambda t: t.view(r, PH, 1, SP, 1)
+    X = lambda t: t.view(r, 1, PW, 1, SP)
+    ok = (Y(oky) & X(okx)).double()
+    idx = torch.stack([Y(y0) * W + X(x0), Y(y0) * W + X(x1), Y(y1) * W + X(x0), Y(y1) * W + X(x1)], -1)
+    wgt = torch.stack([Y(hy) * X(hx), Y(hy) * X(lx), Y(ly) * X(hx), Y(ly) * X(lx)], -1) * ok.unsqueeze(-1)
+    shape = (r, PH * PW, SP * SP)
+    frac = torch.stack([Y(ly).expand(r, PH, PW, SP, SP), X(lx).expand(r, PH, PW, SP, SP)], -1).reshape(shape + (2,))
+    return idx.reshape(shape + (4,)), wgt.reshape(shape + (4,)), idx[..., 0].reshape(shape), frac
+
+
+def _box4(a, H, W):
+    """(H*W, C) -> the sum of a over the 4 x 4 pixels (y-1 .. y+2, x-1 .. x+2) around every pixel (zero outside the map)."""
+    t = a.t().reshape(1, -1, H, W)
+    t = TF.pad(t, (1, 2, 1, 2))
+    return (TF.avg_pool2d(t, 4, stride=1) * 16.0)[0].reshape(-1, H * W).t()
+
+
+def roi_align_ref_fwd(feat, geom, nlev, strides, C, rois, labels, rois_per_img, pool, SP, levels, rois_chunk=128, edge_eps=None):
+    """bd_roi_align_fwd: out (R, PH*PW*C) = the mean over SP x SP bilinear samples per bin of the level `levels[r]` map of image
+    r // rois_per_img; slots with label < 0 give zeros (exact).  Returns (ref, S, F, exact): S weighs |feat| with the same weights; F is
+    the UNWEIGHTED mean over the samples of the sum of |feat| over each sample's four corners -- the scale an error of the bilinear
+    WEIGHTS (fp32 sample coordinates in the kernel) is measured against.  A sample whose offset in its cell is within edge_eps[level] of 0
+    or 1 (None: every sample) may land in the neighbouring cell when its coordinate is rounded: it counts the 4 x 4 pixels around its cell."""
+    PH, PW = pool
+    R = rois.shape[0]
+    dev = feat.device
+    nb = PH * PW
+    ref = torch.zeros((R, nb, C), dtype=torch.float64, device=dev)
+    S, F = torch.zeros_like(ref), torch.zeros_like(ref)
+    valid = torch.ones(R, dtype=torch.bool, device=dev) if labels is None else labels >= 0
+    img = torch.arange(R, device=dev) // rois_per_img
+    for n in range(geom.N):
+        for l in range(nlev):
+            sel = torch.nonzero((img == n) & (levels == l) & valid).view(-1)
+            if sel.numel() == 0:
+                continue
+            H, W = geom.H[l], geom.W[l]
+            f = feat[n * geom.pix_per_img + geom.off[l]: n * geom.pix_per_img + geom.off[l] + H * W].double()
+            fa = f.abs()
+            f4 = _box4(fa, H, W)
+            for c0 in range(0, sel.numel(), rois_chunk):
+                s = sel[c0:c0 + rois_chunk]
+                idx, wgt, cell, frac = _roi_samples(rois[s], 1.0 / strides[l], H, W, PH, PW, SP)
+                w = wgt.unsqueeze(-1)
+                ref[s] = (f[idx] * w).sum((2, 3)) / (SP * SP)
+                S[s] = (fa[idx] * w).sum((2, 3)) / (SP * SP)
+                wide = f4[cell]
+                if edge_eps is not None:
+                    near = ((frac < edge_eps[l]) | (frac > 1.0 - edge_eps[l])).any(-1)
+                    wide = torch.where(near.unsqueeze(-1), wide, fa[idx].sum(3))
+                F[s] = wide.sum(2) / (SP * SP)
+    exact = (~valid).view(R, 1, 1).expand(R, nb, C)
+    return ref.view(R, -1), S.view(R, -1), F.view(R, -1), exact.reshape(R, -1)
+
+
+def roi_align_ref_bwd(gout, geom, nlev, strides, C, rois, labels, rois_per_img, pool, SP, levels, rois_chunk=128):
+    """The adjoint of roi_align_ref_fwd: gout (R, PH*PW*C) -> (ref, S, G, cnt) over the whole pixel-major pyramid (N * ppi, C) float64
+    (levels no RoI is pooled from, and pixels no sample reaches, are zero): ref the gradient, S the same sum over |gout|, G the sum of
+    |gout| / SP^2 over every sample whose cell lies within the 4 x 4 pixels around the pixel (the scale of a weight error), cnt (N * ppi,)
+    the number of (sample, corner) terms the pixel's sum has."""
+    PH, PW = pool
+    R = rois.shape[0]
+    dev = gout.device
+    nb = PH * PW
+    shape = (geom.N * geom.pix_per_img, C)
+    ref = torch.zeros(shape, dtype=torch.float64, device=dev)
+    S, G = torch.zeros_like(ref), torch.zeros_like(ref)
+    cnt = torch.zeros(shape[0], dtype=torch.float64, device=dev)
+    valid = torch.ones(R, dtype=torch.bool, device=dev) if labels is None else labels >= 0
+    img = torch.arange(R, device=dev) // rois_per_img
+    gv = gout.view(R, nb, C)
+    for n in range(geom.N):
+        for l in range(nlev):
+            sel = torch.nonzero((img == n) & (levels == l) & valid).view(-1)
+            if sel.numel() == 0:
+                continue
+            H, W = geom.H[l], geom.W[l]
+            r0 = n * geom.pix_per_img + geom.off[l]
+            acc = torch.zeros((H * W, C), dtype=torch.float64, device=dev)
+            sa, ga = torch.zeros_like(acc), torch.zeros_like(acc)
+            ca = torch.zeros(H * W, dtype=torch.float64, device=dev)
+            for c0 in range(0, sel.numel(), rois_chunk):
+                s = sel[c0:c0 + rois_chunk]
+                idx, wgt, cell, frac = _roi_samples(rois[s], 1.0 / strides[l], H, W, PH, PW, SP)
+                g = gv[s].double() / (SP * SP)                                     # (r, nb, C)
+                contrib = g.view(-1, nb, 1, 1, C) * wgt.unsqueeze(-1)              # (r, nb, SP^2, 4, C)
+                acc.index_add_(0, idx.reshape(-1), contrib.reshape(-1, C))
+                sa.index_add_(0, idx.reshape(-1), contrib.abs().reshape(-1, C))
+                ca.index_add_(0, idx.reshape(-1), (wgt.reshape(-1) != 0).double())
+                ga.index_add_(0, cell.reshape(-1), g.abs().view(-1, nb, 1, C).expand(-1, nb, SP * SP, C).reshape(-1, C))
+            ref[r0:r0 + H * W], S[r0:r0 + H * W], cnt[r0:r0 + H * W] = acc, sa, ca
+            # a sample of cell (y0, x0) can reach pixels y0 - 1 .. y0 + 2: pixel p collects the cells p - 2 .. p + 1 (the mirrored window)
+            G[r0:r0 + H * W] = _box4(ga.flip(0), H, W).flip(0)
+    return ref, S, G, cnt
+
+
+def subsample2x_ref(src, gsrc, gdst):
+    """bd_subsample2x_fwd: level gdst = the even pixels of level gsrc; returns the (N, Hd*Wd, C) tensor the destination level must hold
+    (same dtype: a copy)."""
+    N, Hs, Ws = gsrc.N, gsrc.H[0], gsrc.W[0]
+    v = src.view(N, gsrc.pix_per_img, -1)[:, gsrc.off[0]:gsrc.off[0] + Hs * Ws].reshape(N, Hs, Ws, -1)
+    return v[:, ::2, ::2].reshape(N, gdst.H[0] * gdst.W[0], -1)
+
+
+def subsample2x_ref_bwd(g_before, gdst, gsrc):
+    """bd_subsample2x_bwd_add on a buffer that holds both levels: g[src level][2y, 2x] += g[dst level][y, x].  Returns (ref, S, touched)
+    for the rows of the source level, (N, Hs*Ws, C) float64 / bool (touched: the even grid; every other pixel keeps its bits)."""
+    N, Hs, Ws = gsrc.N, gsrc.H[0], gsrc.W[0]
+    Hd, Wd = gdst.H[0], gdst.W[0]
+    C = g_before.shape[1]
+    s = g_before.view(N, gsrc.pix_per_img, C)[:, gsrc.off[0]:gsrc.off[0] + Hs * Ws].reshape(N, Hs, Ws, C).double()
+    d = g_before.view(N, gdst.pix_per_img, C)[:, gdst.off[0]:gdst.off[0] + Hd * Wd].reshape(N, Hd, Wd, C).double()
+    ref, S = s.clone(), s.abs()
+    ref[:, ::2, ::2] += d
+    S[:, ::2, ::2] += d.abs()
+    touched = torch.zeros((N, Hs, Ws, 1), dtype=torch.bool, device=g_before.device)
+    touched[:, ::2, ::2] = True
+    return ref.view(N, Hs * Ws, C), S.view(N, Hs * Ws, C), touched.expand(N, Hs, Ws, C).reshape(N, Hs * Ws, C)
+
+
+def f32_to_bf16_ref(src, dst_before=None):
+    """bd_f32_to_bf16 (dst = bf16(src)) and bd_f32_to_bf16_add (dst = bf16(float(dst) + src)); returns (ref, S) float64."""
+    ref, S = src.double(), src.double().abs()
+    if dst_before is not None:
+        ref, S = ref + dst_before.double().view_as(ref), S + dst_before.double().abs().view_as(ref)
+    return ref, S
+
+
+def rcnn_loss_ref(raw, ld, K, box_off, labels, targets, beta, num_samples):
+    """bd_rcnn_loss_fwd_bwd (rcnn.py:65-83) from the bf16 prediction rows raw (R, ld): softmax cross-entropy over the K + 1 logits and
+    smooth-L1 (beta; plain L1 below 1e-5) on the four deltas of the ground-truth class of foreground rows, both divided by
+    max(num_samples, 1).  Returns a dict: draw / S_draw (R, ld) float64, exact (R, ld) bool (label -1 rows, the columns outside the logits
+    and the row's own deltas: exact zeros), amp (R, 1) = 2 max |logit| + 8 (the fp32 exp / log argument error in units of 2^-23),
+    cls / box the two losses, S_cls / S_box their scales."""
+    r = raw.double()
+    R = r.shape[0]
+    dev = raw.device
+    gs = 1.0 / max(float(num_samples), 1.0)
+    lab = labels.view(-1).to(torch.int64)
+    valid = lab >= 0
+    lc = lab.clamp_min(0)
+    logits = r[:, :K + 1]
+    lse = torch.logsumexp(logits, 1, keepdim=True)
+    p = torch.exp(logits - lse)
+    onehot = torch.zeros_like(p).scatter_(1, lc.view(-1, 1), 1.0)
+    draw = torch.zeros((R, ld), dtype=torch.float64, device=dev)
+    S = torch.zeros_like(draw)
+    exact = torch.ones((R, ld), dtype=torch.bool, device=dev)
+    draw[:, :K + 1] = (p - onehot) * gs
+    S[:, :K + 1] = (p + onehot) * gs
+    exact[:, :K + 1] = False
+    fg = lab > 0
+    cols = box_off + (lc - 1).clamp_min(0).view(-1, 1) * 4 + torch.arange(4, device=dev).view(1, 4)          # (R, 4)
+    x = torch.gather(r, 1, cols) - targets.double().view(R, 4)
+    xs = torch.gather(r, 1, cols).abs() + targets.double().view(R, 4).abs()
+    if beta < 1e-5:
+        gbox, sbox = torch.sign(x), torch.ones_like(x)
+        lbox, slbox = x.abs(), xs
+    else:
+        gbox = torch.where(x.abs() < beta, x / beta, torch.sign(x))
+        sbox = torch.where(x.abs() < beta, xs / beta, torch.ones_like(x))
+        lbox = torch.where(x.abs() < beta, 0.5 * x * x / beta, x.abs() - 0.5 * beta)
+        slbox = torch.where(x.abs() < beta, 0.5 * xs * xs / beta, xs + 0.5 * beta)
+    fgc = fg.view(-1, 1).expand(R, 4)
+    rows = torch.arange(R, device=dev).view(-1, 1).expand(R, 4)
+    draw[rows[fgc], cols[fgc]] = gbox[fgc] * gs
+    S[rows[fgc], cols[fgc]] = sbox[fgc] * gs
+    exact[rows[fgc], cols[fgc]] = False
+    dead = ~valid
+    draw[dead], S[dead], exact[dead] = 0.0, 0.0, True
+    xl = torch.gather(logits, 1, lc.view(-1, 1))
+    cls_rows = torch.where(valid.view(-1, 1), lse - xl, torch.zeros_like(lse))
+    s_rows = torch.where(valid.view(-1, 1), lse.abs() + xl.abs(), torch.zeros_like(lse))
+    fg4 = fgc.double()
+    return dict(draw=draw, S_draw=S, exact=exact, amp=2.0 * logits.abs().max(1, keepdim=True)[0] + 8.0,
+                cls=float(cls_rows.sum() * gs), S_cls=float(s_rows.sum() * gs),
+                box=float((lbox * fg4).sum() * gs), S_box=float((slbox * fg4).sum() * gs))
