@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
+ABI_VERSION = 101              # bd_version() of the library this binding's ConvDesc matches (101: the liveness-map fields)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -29,6 +30,9 @@ class ConvDesc(C.Structure):
         ("in_pix_per_img", C.c_int32), ("out_pix_per_img", C.c_int32),
         ("route", C.c_int32 * 4), ("sr_seed", C.c_uint32),        # per-call kernel routing / e5m2 rounding seed (0 = the library's choice)
         ("gskip", C.c_int32), ("gskip_ws", C.c_void_p), ("gskip_ws_bytes", C.c_size_t),   # gradient-skip hint + dgrad scratch (0 = dense)
+        # liveness maps of g (read) and dx (written), and the promise that dx holds +0 outside the dx map's last list (0 = none)
+        ("gskip_gmap", C.c_void_p), ("gskip_gmap_bytes", C.c_size_t), ("gskip_dxmap", C.c_void_p), ("gskip_dxmap_bytes", C.c_size_t),
+        ("gskip_dx_clean", C.c_int32),
     ]
 
 
@@ -50,6 +54,8 @@ SIGNATURES = {
     "bd_conv2d_fwd": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
     "bd_conv2d_dgrad": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
     "bd_conv2d_dgrad_gskip_bytes": (_Z, [_D]),
+    "bd_conv2d_gskip_map_bytes": (_Z, [_D, _I]),
+    "bd_gskip_map_scan": (_I, [_D, _I, _P, _P, _Z, _P]),
     "bd_conv2d_fwd_bits": (_I, [_D, _P, _P, _P, _P, _P, _P, _I, _P]),
     "bd_conv2d_fwd_ex": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "bd_conv2d_dgrad_ex": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
@@ -196,12 +202,21 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m basedet_amd.build` (hipcc, gfx950). "
             "There is no CPU fallback for the basedet_amd operator path.")
     lib = C.CDLL(LIB_PATH)
+    lib.bd_version.restype = C.c_int
+    check_version(int(lib.bd_version()))
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def check_version(have):
+    """A library built from another header lays bd_conv_desc out differently: refuse it instead of handing it a struct it misreads."""
+    if have != ABI_VERSION:
+        raise BasedetHipError(f"{LIB_PATH} reports bd_version() = {have}, this binding needs {ABI_VERSION}: rebuild it with "
+                              "`python -m basedet_amd.build`")
 
 
 def check(rc, what=""):

@@ -167,6 +167,10 @@ static inline int bd_tune_env(const char*, int dflt) { return dflt; }
 static inline const char* bd_tune_env_str(const char*) { return nullptr; }
 #endif
 
+// Liveness map of a gradient tensor (bd_conv_desc.gskip_gmap / gskip_dxmap; gskip.hip): int offsets of its parts, patch counts, size
+struct BdGskipMap { int p4, p8, m4, m8, live, list; size_t ints; };
+void bd_gskip_map_layout(const bd_conv_desc* d, int side, BdGskipMap* out);      // side 0: the map of g, 1: of dx
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

@@ -64,6 +64,14 @@ struct PParams {
     const int* sp_list;
     const int* sp_count;
     int sp_keep_dead;
+    // ... with liveness maps (bd_conv_desc.gskip_gmap / gskip_dxmap; the layout: gskip.hip): sp_hdr != NULL = the header of g's map -- sp_list is
+    // then list 0 of its two lists (sp_stride ints apart; header word 0 says which is current, words 2 / 3 hold the counts).  sp_ohdr != NULL =
+    // the header of dx's map (its finished-workgroup counter is cleared here, in front of gskip_fill_kernel), sp_olist its list 0; sp_clean:
+    // dx holds +0 outside that map's current list (the caller's promise), so only the patches of that list that are dead now are cleared
+    const int* sp_hdr;
+    int* sp_ohdr;
+    const int* sp_olist;
+    int sp_stride, sp_clean;
 };
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -149,15 +157,25 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
         if (p.sp_keep_dead) return;
         const int cpp = p.CO >> 3;
         const int items = PH * PW * cpp;
-        for (int k0 = 0; z0 + k0 * zn < p.total_patches; k0 += 512) {
+        int zt = p.total_patches;                              // candidates: every patch, or (sp_clean) the previous call's live list
+        const int* plist = nullptr;
+        if (p.sp_clean) {
+            const int oc = __builtin_amdgcn_readfirstlane(p.sp_ohdr[0]) & 1;
+            const int pc = __builtin_amdgcn_readfirstlane(p.sp_ohdr[2 + oc]);
+            zt = pc < 0 ? 0 : (pc < zt ? pc : zt);
+            plist = p.sp_olist + oc * p.sp_stride;
+        }
+        for (int k0 = 0; z0 + k0 * zn < zt; k0 += 512) {
             const int k = k0 + wave * 64 + lane;
-            const int q = z0 + k * zn;
-            const bool dead = q < p.total_patches && p.sp_live[q] == 0;
+            const int idx = z0 + k * zn;
+            int q = idx;
+            if (plist) q = idx < zt ? plist[idx] : -1;
+            const bool dead = idx < zt && q >= 0 && q < p.total_patches && p.sp_live[q] == 0;
             unsigned long long m = __ballot(dead);
             while (m) {
                 const int l = __builtin_ctzll(m);
                 m &= m - 1;
-                const int qq = z0 + (k0 + wave * 64 + l) * zn;
+                const int qq = __builtin_amdgcn_readfirstlane(__shfl(q, l, 64));
                 const int n = qq / p.patches_per_img, rem = qq - n * p.patches_per_img;
                 int sgi = 0;
 #pragma unroll
@@ -177,8 +195,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
     };
     int n_px = p.px_tiles, n_live = p.total_patches;          // pixel tiles / patches this launch computes
     int z_first = 0;                                           // SPARSE: the first workgroup without a tile (main_grid: none)
+    const int* sp_list = p.sp_list;
     if constexpr (SPARSE) {
-        n_live = __builtin_amdgcn_readfirstlane(*p.sp_count);
+        if (p.sp_ohdr && blockIdx.x == 0 && threadIdx.x == 0) p.sp_ohdr[1] = 0;
+        // (one load through a selected pointer: the two-armed form does not compile -- "illegal VGPR to SGPR copy")
+        const int cur = p.sp_hdr ? __builtin_amdgcn_readfirstlane(p.sp_hdr[0]) & 1 : 0;
+        const int* cntp = p.sp_hdr ? p.sp_hdr + 2 + cur : p.sp_count;
+        n_live = __builtin_amdgcn_readfirstlane(*cntp);
+        sp_list += cur * p.sp_stride;
+        n_live = __builtin_amdgcn_readfirstlane(n_live < 0 ? 0 : (n_live < p.total_patches ? n_live : p.total_patches));
         n_px = (n_live + NPATCH - 1) / NPATCH;
         z_first = n_px * p.n_tiles < p.main_grid ? n_px * p.n_tiles : p.main_grid;
         if (pt >= n_px) {                                      // no live tile for this workgroup: bid >= z_first
@@ -204,7 +229,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
         const int k = k0 + (lane >> 2);
         const int ptile = pt_first + k * pt_step;
         int pid = ptile * NPATCH + (lane & (NPATCH - 1));
-        if (SPARSE) pid = (ptile < n_px && pid < n_live) ? p.sp_list[pid] : p.total_patches;
+        if (SPARSE) pid = (ptile < n_px && pid < n_live) ? sp_list[pid] : p.total_patches;
         int vH = 0, vW = 0, vy = 0, vx = 0, vs = 0, vd = 0;
         if (ptile < n_px && pid < p.total_patches) {
             const int n = pp_div(pid, p.patches_per_img, p.inv_ppi);
@@ -728,6 +753,7 @@ BD_KNOB int g_pp_tail_split = 1;     // bd_conv_desc.route[1] bit 13 clears it
 BD_KNOB int g_pp_persistent = 1;     // bit 14 clears it: one workgroup per tile
 extern BD_KNOB int g_patch_pp;       // 0 = never, 1 = where the makespan estimate favours it, 2 = wherever the shape allows (default)
 int bd_gskip_patches(const bd_conv_desc* d, int ph, int pw);
+void bd_gskip_fill(const bd_conv_desc* d, int side, const void* t, const int* live_in, int* map, hipStream_t stream);
 void bd_gskip_scan(const bd_conv_desc* d, const void* g, int ph, int pw, int* mask, hipStream_t stream);
 void bd_gskip_compact(const bd_conv_desc* d, int ph, int pw, const int* mask, int* live, int* list, int* count, hipStream_t stream);
 
@@ -736,6 +762,28 @@ void bd_gskip_compact(const bd_conv_desc* d, int ph, int pw, const int* mask, in
 extern "C" size_t bd_conv2d_dgrad_gskip_bytes(const bd_conv_desc* d) {
     if (!d || d->nseg < 1 || d->nseg > BD_MAX_SEGS || !(d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1)) return 0;
     return ((size_t)3 * bd_gskip_patches(d, PH, PW) + 4) * sizeof(int);
+}
+
+// the epilogues the SPARSE instance serves: a data gradient whose dead output patches are +0 (overwrite, BD_EPI_MASK) or keep dx (in-place
+// accumulate without a gate)
+static bool pp_sparse_epilogue(int flags, const void* add, const void* dst) {
+    const bool in_place = (flags & BD_EPI_ADD_BEFORE) && add && add == dst;
+    return !(flags & BD_EPI_ADD_AFTER) && (!((flags & BD_EPI_ADD_BEFORE) && add) || (in_place && !(flags & BD_EPI_MASK)));
+}
+
+// conv2d_dgrad_impl's check of a call that carries liveness maps: the SPARSE instance must take it, or the maps would be neither read nor
+// written (same shape conditions as pp_launch below)
+bool bd_conv3x3_pp_maps_ok(const bd_conv_desc* d, int flags, const void* add, const void* dst) {
+    if (g_patch_pp < 2 || !(d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1)) return false;
+    if (d->Cout % 8 != 0 || d->Cin <= 128 || d->Cin % 8 != 0) return false;
+    if ((long long)d->N * d->out_pix_per_img * d->Cout * 2 >= 0x7fffffffll || (long long)d->N * d->in_pix_per_img >= 0x7fffffffll ||
+        (long long)d->Cin * 9 * d->Cout >= 0x7fffffffll) return false;
+    for (int s = 0; s < d->nseg; ++s)
+        if (d->Hi[s] != d->Ho[s] || d->Wi[s] != d->Wo[s]) return false;
+    if (bd_gskip_patches(d, PH, PW) >= (1 << 24)) return false;
+    const bool in_place = (flags & BD_EPI_ADD_BEFORE) && add && add == dst;
+    if (d->gskip_dxmap && in_place) return false;            // (dx outside the live list is the caller's data, not +0)
+    return pp_sparse_epilogue(flags, add, dst);
 }
 
 static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const void* w, const float* bias, const void* add,
@@ -778,8 +826,7 @@ static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const voi
     // Gradient skip (bd_conv_desc.gskip; conv2d_dgrad_impl has checked the scratch): a data gradient whose dead output patches are +0
     // (overwrite, BD_EPI_MASK) or keep dx (in-place accumulate without a gate).  Any other epilogue walks every patch.
     const bool in_place = (flags & BD_EPI_ADD_BEFORE) && add && add == dst;
-    const bool sparse = mode == 1 && d->gskip && !gn_part && !(flags & BD_EPI_ADD_AFTER) &&
-                        (!((flags & BD_EPI_ADD_BEFORE) && add) || (in_place && !(flags & BD_EPI_MASK)));
+    const bool sparse = mode == 1 && d->gskip && !gn_part && pp_sparse_epilogue(flags, add, dst);
     if (g_pp_tail_split && !sparse && !gn_part && p.n_tiles == 1 && px_tiles > num_cus) {          // (the tail body leaves no GroupNorm statistics)
         const int r = px_tiles % num_cus;
         if (r > 0 && r * (TILE_CO / TAIL_CO) <= num_cus) {
@@ -813,13 +860,30 @@ static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const voi
     if (sparse) {
         // three launches on the call's stream: scan g, compact the live output patches (one workgroup), then the tiles of the live patches and
         // the +0 stores of the dead ones (the grid is the dense plan's: workgroups past the live tiles only store zeros)
-        int* mk = (int*)d->gskip_ws;
+        // With the map of g (gskip_gmap) the first two are gone: its producer left the live list.  With a map of dx to write (gskip_dxmap)
+        // one launch over the computed patches follows (gskip_fill_kernel).
         const int tot = p.total_patches;
-        p.sp_live = mk + tot; p.sp_list = mk + 2 * tot; p.sp_count = mk + 3 * tot;
         p.sp_keep_dead = in_place ? 1 : 0;
-        bd_gskip_scan(d, src, PH, PW, mk, stream);
-        bd_gskip_compact(d, PH, PW, mk, mk + tot, mk + 2 * tot, mk + 3 * tot, stream);
+        p.sp_stride = tot;
+        if (d->gskip_gmap) {
+            BdGskipMap gm;
+            bd_gskip_map_layout(d, 0, &gm);
+            const int* m = (const int*)d->gskip_gmap;
+            p.sp_hdr = m; p.sp_live = m + gm.live; p.sp_list = m + gm.list;
+        } else {
+            int* mk = (int*)d->gskip_ws;
+            p.sp_live = mk + tot; p.sp_list = mk + 2 * tot; p.sp_count = mk + 3 * tot;
+            bd_gskip_scan(d, src, PH, PW, mk, stream);
+            bd_gskip_compact(d, PH, PW, mk, mk + tot, mk + 2 * tot, mk + 3 * tot, stream);
+        }
+        if (d->gskip_dxmap) {
+            BdGskipMap xm;
+            bd_gskip_map_layout(d, 1, &xm);
+            p.sp_ohdr = (int*)d->gskip_dxmap; p.sp_olist = p.sp_ohdr + xm.list;
+            p.sp_clean = d->gskip_dx_clean ? 1 : 0;
+        }
         hipLaunchKernelGGL((conv3x3_pp_kernel<1, false, true>), dim3(p.main_grid), dim3(512), LDS_BYTES, stream, p);
+        if (d->gskip_dxmap) bd_gskip_fill(d, 1, dst, p.sp_live, (int*)d->gskip_dxmap, stream);
     } else if (gn_part) {
         BD_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         hipLaunchKernelGGL((conv3x3_pp_kernel<0, true>), dim3(p.main_grid), dim3(512), LDS_BYTES, stream, p);

@@ -457,6 +457,7 @@ BD_KNOB int g_bk32_s2 = 1;
 
 int bd_conv3x3_patch_launch(const bd_conv_desc* d, int mode, const void* src, const void* w, const float* bias,
                             const void* add, const void* mask, void* dst, int flags, hipStream_t stream);
+bool bd_conv3x3_pp_maps_ok(const bd_conv_desc* d, int flags, const void* add, const void* dst);
 
 // debug/measurement knob: bit 0 clear forces the generic per-tap kernel for 3x3 stride-1 convolutions; bit 1: BK=32 tiles for 1x1
 extern BD_KNOB int g_patch_dma;
@@ -608,10 +609,20 @@ static int conv2d_dgrad_impl(const bd_conv_desc* d, const void* g, const void* w
                              const unsigned* maskbits, void* dx, void* dx8, float q_scale, int flags, bd_stream_t stream) {
     if (int e = check_desc(d)) return e;
     BD_REQUIRE(g && w_packed_t && dx, "conv2d_dgrad: null pointer");
-    if (d->gskip && is_3x3s1(d)) {
+    if (d->gskip && is_3x3s1(d) && !d->gskip_gmap) {
         const size_t need = bd_conv2d_dgrad_gskip_bytes(d);
         BD_REQUIRE(d->gskip_ws && d->gskip_ws_bytes >= need, "conv2d_dgrad: gskip scratch %zu < required %zu bytes (or NULL)",
                    (size_t)d->gskip_ws_bytes, need);
+    }
+    if (d->gskip_gmap || d->gskip_dxmap || d->gskip_dx_clean) {          // liveness maps: only a call the sparse patch kernel takes may carry them
+        BD_REQUIRE(d->gskip && is_3x3s1(d) && g_use_patch3x3 && !maskbits && !dx8 && bd_conv3x3_pp_maps_ok(d, flags, add, dx),
+                   "conv2d_dgrad: liveness maps need gskip on a 3x3 / stride 1 / pad 1 descriptor into more than 128 channels with an overwriting "
+                   "(or, without gskip_dxmap, in-place accumulating) epilogue on the default route");
+        BD_REQUIRE(!d->gskip_gmap || d->gskip_gmap_bytes >= bd_conv2d_gskip_map_bytes(d, 0), "conv2d_dgrad: gskip_gmap %zu < required %zu bytes",
+                   (size_t)d->gskip_gmap_bytes, bd_conv2d_gskip_map_bytes(d, 0));
+        BD_REQUIRE(!d->gskip_dxmap || d->gskip_dxmap_bytes >= bd_conv2d_gskip_map_bytes(d, 1), "conv2d_dgrad: gskip_dxmap %zu < required %zu bytes",
+                   (size_t)d->gskip_dxmap_bytes, bd_conv2d_gskip_map_bytes(d, 1));
+        BD_REQUIRE(!d->gskip_dx_clean || d->gskip_dxmap, "conv2d_dgrad: gskip_dx_clean needs gskip_dxmap (the list the promise refers to)");
     }
     if (d->stride == 1) flags &= ~BD_EPI_SPARSE;          // every pixel of a stride-1 data gradient is reached
     BD_REQUIRE(d->Cout % 8 == 0, "conv2d_dgrad: Cout=%d must be a multiple of 8 (pad the gradient)", d->Cout);

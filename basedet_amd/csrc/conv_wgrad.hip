@@ -552,8 +552,16 @@ static int wgrad_impl(const bd_conv_desc* d, const void* x, const void* g, const
         bd_note_kernel("conv_wgrad3x3_ring_kernel");
         int* gflags = nullptr;
         if (gskip_patches(d) > 0) {            // gradient skip: scan g in the ring's 8 x 8 patches, then walk only the flagged ones
-            gflags = (int*)((unsigned char*)ws + align256(wgrad_ws_base(d)));
-            bd_gskip_scan(d, g, 8, 8, gflags, (hipStream_t)stream);
+            if (d->gskip_gmap) {               // ... or take the flags g's producer left in its liveness map: no scan
+                BdGskipMap gm;
+                bd_gskip_map_layout(d, 0, &gm);
+                BD_REQUIRE(d->gskip_gmap_bytes >= gm.ints * sizeof(int) && gm.p8 == gskip_patches(d),
+                           "conv2d_wgrad: gskip_gmap %zu < required %zu bytes", (size_t)d->gskip_gmap_bytes, gm.ints * sizeof(int));
+                gflags = (int*)d->gskip_gmap + gm.m8;
+            } else {
+                gflags = (int*)((unsigned char*)ws + align256(wgrad_ws_base(d)));
+                bd_gskip_scan(d, g, 8, 8, gflags, (hipStream_t)stream);
+            }
         }
         bd_wgrad3x3r_launch(d, x, g, (float*)ws, dbias ? (float*)extra : nullptr, gflags, &splitsr, (hipStream_t)stream);
         BD_CHECK_LAUNCH("bd_conv2d_wgrad(3x3 ring)");

@@ -46,7 +46,8 @@ struct RParams {
     const bf16_raw* g;
     float* slab;             // [splits * tiles][8 waves][36][64 lanes] f32x4
     float* csum;             // optional [splits][Cout] partial column sums of g (bias gradient), written by the ci_tile 0 workgroups
-    const int* gflags;       // SPARSE instance: per 8 x 8 patch of g, nonzero iff it holds a nonzero bit (gskip.hip)
+    const int* gflags;       // SPARSE instance: per 8 x 8 patch of g, nonzero iff it holds a nonzero bit (gskip.hip): this call's own scan of g, or --
+                             // bd_conv_desc.gskip_gmap -- the 8 x 8 flags of the liveness map that g's producer left (conv_wgrad.hip picks)
     int Cin, Cout, N, nseg;
     int in_ppi, out_ppi;
     unsigned x_bytes, g_bytes;

@@ -60,6 +60,10 @@ class ConvLayer:
         self.gskip = False
         self._gskip_cache = {}          # id(plain descriptor) -> (gskip descriptor, plain descriptor)
         self._gskip_ws = None
+        # liveness maps of this step's launches (set_chain): the map of the gradient this layer reads, the map of the gradient its data
+        # gradient writes, and the promise about that buffer's bytes (bd_conv_desc.gskip_gmap / gskip_dxmap / gskip_dx_clean)
+        self._chain = (None, None, False)
+        self._chain_cache = {}
         # fp8 forward (BASELINE config 5, enable_fp8): e4m3 weights with one scale per output channel + the input cast to e4m3
         self.fp8 = False
         self.fp8_dgrad = False          # data gradient on the fp8 patch kernel too (e5m2 gradients under a static gradient scale)
@@ -192,7 +196,23 @@ class ConvLayer:
                 self._gskip_ws = torch.empty(n, dtype=torch.int32, device=self.device)
                 self._gskip_cache.clear()
             h = self._gskip_cache[id(d)] = (ops.gskip_desc(d, self._gskip_ws), d)
-        return h[0]
+        gmap, dxmap, clean = self._chain
+        if gmap is None and dxmap is None:
+            return h[0]
+        # (keyed by the maps' addresses: the plan arena re-bases them when it grows)
+        key = (id(d), self._gskip_ws.data_ptr(), gmap.data_ptr() if gmap is not None else 0, dxmap.data_ptr() if dxmap is not None else 0, clean)
+        c = self._chain_cache.get(key)
+        if c is None:
+            if len(self._chain_cache) > 64:
+                self._chain_cache.clear()
+            c = self._chain_cache[key] = (ops.gskip_desc(d, self._gskip_ws, gmap=gmap, dxmap=dxmap, dx_clean=clean), d)
+        return c[0]
+
+    def set_chain(self, gmap=None, dxmap=None, dx_clean=False):
+        """The liveness maps this layer's NEXT hinted backward launches carry (None: scan g / write no map, as without a chain): gmap = the
+        map of the gradient it reads, dxmap = the map its data gradient writes for the next layer down, dx_clean = the caller knows that
+        the data gradient's output buffer still holds the layout the previous step left (see bd_conv_desc.gskip_dx_clean)."""
+        self._chain = (gmap, dxmap, bool(dx_clean) and dxmap is not None) if self.gskip else (None, None, False)
 
     def forward(self, x, gin, gout, y, add=None, relu=False, bits=None, x8=None, y8=None, q_scale=1.0):
         """x8: the e4m3 twin of x when a producing fp8 launch wrote one (else x is cast by bd_quantize_fp8); y8: twin of y to write

@@ -75,6 +75,7 @@ class PlanArena:
         self.buf = None
         self.bound = None
         self.grows = 0
+        self.epoch = 0                    # counts the events after which a plan's buffers may hold other bytes than its own last step's
         self.plans = []                   # every placed plan: re-based when the arena grows
         self._scratch = {}                # model-level grow-only workspaces whose size follows the batch (Gmax), not the shape
 
@@ -126,6 +127,7 @@ class PlanArena:
                 _map_tensors(p, rebase)
         self.buf = new
         self.grows += 1
+        self.epoch += 1
 
     def bind(self, pl):
         """Start of a step at plan pl.  When another plan used the arena since pl's last step, every buffer of pl's can hold that plan's
@@ -140,6 +142,7 @@ class PlanArena:
         for off, n in pl._carve.zero:
             buf[off: off + n].zero_()
         self.bound = pl
+        self.epoch += 1
 
     def scratch(self, name, nbytes):
         """Model-level grow-only uint8 workspace (its size follows the batch -- Gmax -- rather than the shape).  Before a smaller one is

@@ -51,6 +51,10 @@ class RetinaNet(FPNDetector):
         if bool(m.get("SPARSE_BOX_BWD", True)) and m.get("WEIGHT_DTYPE", "bf16") == "bf16":
             for c in self.box_tower + [self.bbox_pred]:
                 c.gskip = True
+        # MODEL.SPARSE_BOX_CHAIN (default on): the liveness is handed down the box tower in maps carved beside the tower gradients (_plan_head)
+        # instead of being scanned out of every gradient again -- by its data gradient AND its weight gradient (bd_conv_desc.gskip_gmap /
+        # gskip_dxmap).  Off: every launch scans for itself, as before the maps existed.
+        self.sparse_chain = bool(m.get("SPARSE_BOX_CHAIN", True))
         # base anchors: python float64 -> float32 (layers/common/anchor_generator.py:95-109)
         scales = np.asarray(m.ANCHOR.SCALES, np.float32).tolist()
         ratios = np.asarray(m.ANCHOR.RATIOS, np.float32).tolist()
@@ -91,6 +95,15 @@ class RetinaNet(FPNDetector):
         pl.d_logits = C.like(pl.logits)
         pl.d_offsets = C.like(pl.offsets)              # (bd_smooth_l1_fwd_bwd writes the padding slots' zero gradient)
         pl.g_tower = [[act(pl.pyr, ch) for _ in range(nc)] for _ in range(2)]   # one gradient buffer per tower layer
+        # one liveness map per BOX tower gradient (int32; the layout is the library's).  A plan's buffers never overlap each other (_Carver
+        # hands out disjoint ranges), so within a plan only the tower's own data gradient writes g_tower[1][i]: the promise that it still holds
+        # last step's layout (gskip_dx_clean) can be given while the arena's epoch stands -- see head_backward
+        pl.g_map = None
+        if self.sparse_chain and all(c.gskip for c in self.box_tower + [self.bbox_pred]):
+            nb = ops.conv2d_gskip_map_bytes(self.box_tower[0].desc(pl.pyr, pl.pyr))
+            if nb:
+                pl.g_map = [C.empty(((nb + 3) // 4,), torch.int32) for _ in range(nc)]
+        pl.chain_epoch = None
         # fp8 forward: every tower activation gets an e4m3 twin, written by the launch that produces it (no cast passes in the head)
         tw = lambda: C.empty((pl.pyr.pixels, ch), torch.uint8)      # noqa: E731
         pl.cls_act8 = [tw() if c.fp8 else None for c in self.cls_tower]
@@ -186,6 +199,18 @@ class RetinaNet(FPNDetector):
                                                          (self.box_tower, pl.box_act, self.bbox_pred, pl.d_offsets))):
             gbuf, g8 = pl.g_tower[ti], pl.g_tower8[ti]
             n = len(tower)
+            # box tower: the liveness maps travel down the chain -- bbox_pred's data gradient scans d_offsets (40 channels) and leaves the map
+            # of gbuf[n - 1]; every layer below reads the map of its gradient (data and weight gradient: no scan) and leaves the next one.
+            # The promise that a gradient buffer still holds last step's layout stands only if that step ran this chain on this plan and
+            # nothing re-bound, grew or re-based the arena since (PlanArena.epoch); any other step withdraws it.
+            maps = pl.g_map if (ti == 1 and self.sparse_chain and all(c.gskip for c in tower + [pred])) else None
+            if ti == 1:
+                clean = maps is not None and pl.chain_epoch == self.plan_arena.epoch
+                pl.chain_epoch = self.plan_arena.epoch if maps is not None else None
+                if maps is not None:
+                    pred.set_chain(None, maps[n - 1], clean)
+                    for i in range(n):
+                        tower[i].set_chain(maps[i], maps[i - 1] if i > 0 else None, clean)
             gs = tower[n - 1].grad_scale
             self._wgrad(pred, acts[-1], dpred, pyr, pyr, ws, cws)
             tw = g8[n - 1] if pred.dgrad_writes_twin(pyr, pyr) else None       # None also when twins are off (g8 holds no buffers)
@@ -206,6 +231,8 @@ class RetinaNet(FPNDetector):
                     wrote_p = tower[i].dgrad(gbuf[i], pyr, pyr, pl.g_P, first=(ti == 0), g8=tw,
                                              dx8=pl.g_P8 if tower[i].dgrad_writes_twin(pyr, pyr) else None,
                                              q_scale=self.output[self.fpn_stages[0]].grad_scale)
+        for c in self.box_tower + [self.bbox_pred]:
+            c.set_chain()
         # the box tower's launch wrote the twin of the FINAL dL/dP (it accumulates onto the class tower's contribution)
         pl.g_P8_ready = pl.g_P8 is not None and bool(wrote_p)
 

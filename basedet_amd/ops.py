@@ -132,15 +132,36 @@ def conv2d_dgrad_gskip_bytes(d):
     return int(L().bd_conv2d_dgrad_gskip_bytes(C.byref(d)))
 
 
-def gskip_desc(d, scratch=None):
+def conv2d_gskip_map_bytes(d, of_dx=False):
+    """Bytes of the liveness map of d's gradient operand g (of_dx=False) or of its data gradient dx (bd_conv_desc.gskip_gmap / gskip_dxmap)."""
+    return int(L().bd_conv2d_gskip_map_bytes(C.byref(d), int(bool(of_dx))))
+
+
+def gskip_map_scan(d, t, gmap, of_dx=False):
+    """Fill the liveness map of tensor t (g or dx of d) by scanning all of it (bd_gskip_map_scan)."""
+    check(L().bd_gskip_map_scan(C.byref(d), int(bool(of_dx)), ptr(t), ptr(gmap), gmap.numel() * gmap.element_size(), stream_ptr()),
+          "bd_gskip_map_scan")
+    return gmap
+
+
+def gskip_desc(d, scratch=None, gmap=None, dxmap=None, dx_clean=False):
     """A copy of descriptor d with the gradient-skip hint set (include/basedet_hip.h, bd_conv_desc.gskip): its bf16 data and weight gradients
     scan g and compute only the patches a nonzero g reaches (same bits).  scratch: device tensor of conv2d_dgrad_gskip_bytes(d) bytes for
-    the data gradient (the weight gradient keeps its flags in ws, sized from this descriptor)."""
+    the data gradient (the weight gradient keeps its flags in ws, sized from this descriptor).  gmap: the liveness map of g, left by the
+    call that wrote g (no scan); dxmap: the map of dx for the data gradient to write; dx_clean: the promise that dx holds +0 outside
+    the list the previous call left in dxmap (int32 device tensors of conv2d_gskip_map_bytes)."""
     h = ConvDesc.from_buffer_copy(d)
     h.gskip = 1
     if scratch is not None:
         h.gskip_ws = scratch.data_ptr()
         h.gskip_ws_bytes = scratch.numel() * scratch.element_size()
+    if gmap is not None:
+        h.gskip_gmap = gmap.data_ptr()
+        h.gskip_gmap_bytes = gmap.numel() * gmap.element_size()
+    if dxmap is not None:
+        h.gskip_dxmap = dxmap.data_ptr()
+        h.gskip_dxmap_bytes = dxmap.numel() * dxmap.element_size()
+    h.gskip_dx_clean = int(bool(dx_clean))
     return h
 
 

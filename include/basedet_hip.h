@@ -85,10 +85,31 @@ typedef struct bd_conv_desc {
      *     g reaches are written as +0, or, accumulating in place (add == dx), keep what dx holds (as BD_EPI_SPARSE).
      *   bd_conv2d_wgrad / _bias / _queued (conv_wgrad3x3_ring.hip's kernel): the liveness flags live in ws, whose size
      *     bd_conv2d_wgrad(_bias)_workspace_bytes reports for the hinted descriptor; gskip_ws is not read.
-     * Other kernels (e.g. the 40-channel weight gradient) ignore the hint. */
+     * Other kernels (e.g. the 40-channel weight gradient) ignore the hint.
+     *
+     * Liveness maps (bd_version() >= 101): a chain of hinted data gradients hands the liveness down instead of scanning every tensor again.
+     * A map is a caller-owned device int buffer that BELONGS TO ONE GRADIENT TENSOR (bd_conv2d_gskip_map_bytes; it holds the per-patch
+     * flags of both consumers' tile geometries and a double-buffered live list); only this library reads or writes its contents.
+     *   gskip_gmap   (NULL: scan g yourself, as above) the map of g, complete on the call's stream: bd_conv2d_dgrad issues no scan and no
+     *                compaction and needs no gskip_ws; bd_conv2d_wgrad* issues no scan and reads the map's 8 x 8 flags.
+     *   gskip_dxmap  (NULL: none; bd_conv2d_dgrad only) the map of dx to WRITE: one small launch behind the compute launch tests the patches
+     *                this call computed and records them (every other patch holds +0); the map is complete on `stream` when the call
+     *                returns.  Overwriting epilogues only (no accumulate into dx).
+     *   gskip_dx_clean  a caller PROMISE, default 0: outside the live list that the previous call recorded in gskip_dxmap, dx already holds
+     *                +0 (same buffer, same descriptor geometry, nothing else wrote it since).  The call then clears only the patches that were
+     *                live then and are dead now instead of storing +0 into every dead patch.  dx is fully valid for a dense reader either way.
+     *                Requires gskip_dxmap.
+     * A call with a map that the descriptor / epilogue cannot honour returns BD_EINVAL (nothing is launched).
+     * DESCRIPTORS MUST BE ZERO-INITIALISED (memset / = {0}) before their fields are set: new optional fields are appended to this struct,
+     * and a zero word always selects the behaviour of the previous version. */
     int32_t gskip;
     void* gskip_ws;
     size_t gskip_ws_bytes;
+    void* gskip_gmap;
+    size_t gskip_gmap_bytes;
+    void* gskip_dxmap;
+    size_t gskip_dxmap_bytes;
+    int32_t gskip_dx_clean;
 } bd_conv_desc;
 
 const char* bd_last_error_string(void);
@@ -129,6 +150,13 @@ int bd_conv2d_dgrad(const bd_conv_desc* d, const void* g, const void* w_packed_t
                     const void* mask, void* dx, int flags, bd_stream_t stream);
 /* Scratch bytes bd_conv2d_dgrad needs at d->gskip_ws when d->gskip is set (0 for a descriptor the hint does not apply to). */
 size_t bd_conv2d_dgrad_gskip_bytes(const bd_conv_desc* d);
+/* Bytes of the liveness map (bd_conv_desc.gskip_gmap / gskip_dxmap) of this descriptor's g (of_dx == 0: the conv's output geometry) or dx
+ * (of_dx != 0: its input geometry); 0 for a descriptor that is not 3x3 / stride 1 / pad 1. */
+size_t bd_conv2d_gskip_map_bytes(const bd_conv_desc* d, int of_dx);
+/* Fills the map of a bf16 tensor nobody left a map for (t = g or dx of d, per of_dx) by scanning all of it: both tile geometries and the
+ * live list of the data gradient that reads it.  The start of a chain whose first gradient comes from a loss; the reference the
+ * producer-written maps are tested against. */
+int bd_gskip_map_scan(const bd_conv_desc* d, int of_dx, const void* t, void* map, size_t map_bytes, bd_stream_t stream);
 
 /* Bit-packed ReLU masks for the HBM-bound 1x1 layers.  A forward launch with BD_EPI_RELU may also write ybits: one bit per output
  * element (y > 0), uint32 [Cout/32][M] (M = N * pixels of the level; word (g, m) holds channels 32g .. 32g+31 of pixel m, bit b =
