@@ -150,9 +150,13 @@ SIGNATURES = {
     "bd_rpn_loss_fwd_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _L, _F, _P, _P, _P, _P]),
     "bd_rcnn_loss_fwd_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P]),
     "bd_det_scores": (_I, [_P, _P, _I, _I, _L, _I, _P, _P]),
+    "bd_det_select_workspace_bytes": (_Z, [_I, _I, _L, _I, _I]),
+    "bd_det_select": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
     "bd_rcnn_predict": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bd_det_candidates": (_I, [_I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "bd_det_finalize": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bd_det_candidates_batched": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P]),
+    "bd_det_finalize_batched": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "bd_sgd_momentum_step": (_I, [_P, _P, _P, _L, _F, _F, _F, _F, _P]),
     "bd_clip_grad_value": (_I, [_P, _L, _F, _F, _F, _P]),
     "bd_clip_grad_norm_workspace_bytes": (_Z, []),

@@ -37,6 +37,7 @@ SOURCES = {
     "boxops.hip": ["-ffp-contract=off"],
     "rcnn_ops.hip": ["-ffp-contract=off"],
     "postprocess.hip": ["-ffp-contract=off"],
+    "det_select.hip": ["-ffp-contract=off"],
     "freeanchor.hip": ["-ffp-contract=off"],
     "ota.hip": ["-ffp-contract=off"],
     "losses.hip": [],

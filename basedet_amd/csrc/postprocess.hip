@@ -50,16 +50,23 @@ __global__ __launch_bounds__(256) void rcnn_predict_kernel(const bf16_raw* __res
 struct CandLevels { int row_off[BD_MAX_SEGS]; int L; };
 
 // mode 0: BoxCoder.decode(anchor, offsets) (retinanet.py:195-196); mode 1: PointCoder.decode (fcos.py:206-207);
-// mode 2: boxes precomputed per item (RCNN: item = roi*K + class)
+// mode 2: boxes precomputed per item (RCNN: item = roi*K + class).  blockIdx.y = image: topk_* [B][L][k], outputs [B][L*k]; anchors / points are
+// shared by the images, offsets advance by off_stride elements and item_boxes by item_stride boxes per image.
 __global__ __launch_bounds__(256) void det_candidates_kernel(int mode, const int* __restrict__ topk_idx, const float* __restrict__ topk_score,
                                                              const int* __restrict__ topk_cnt, CandLevels lv, int k, int K,
                                                              const float* __restrict__ anchors, const bf16_raw* __restrict__ offsets,
-                                                             int off_ld, int A, Coder coder, const float* __restrict__ item_boxes,
+                                                             long long off_stride, int off_ld, int A, Coder coder,
+                                                             const float* __restrict__ item_boxes, long long item_stride,
                                                              float* __restrict__ boxes, float* __restrict__ scores,
                                                              int* __restrict__ labels) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= lv.L * k) return;
     const int l = c / k, rnk = c - l * k;
+    const long long n = blockIdx.y, C = (long long)lv.L * k;
+    topk_idx += n * C; topk_score += n * C; topk_cnt += n * lv.L;
+    boxes += n * C * 4; scores += n * C; labels += n * C;
+    if (offsets) offsets += n * off_stride;
+    if (item_boxes) item_boxes += n * item_stride * 4;
     f32x4_t b = {0.f, 0.f, 0.f, 0.f};
     float sc = -INFINITY;
     int lab = 0;
@@ -87,18 +94,24 @@ __global__ __launch_bounds__(256) void det_candidates_kernel(int mode, const int
     labels[c] = lab;
 }
 
-// post_processing.py:93-101: gather the NMS survivors, scale to the original image size, clip
+// post_processing.py:93-101: gather the NMS survivors, scale to the original image size, clip.  blockIdx.y = image: candidates [B][C],
+// keep [B][max_out], num_keep [B], im_info [B][info_ld], outputs [B][max_out]
 __global__ __launch_bounds__(256) void det_finalize_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                            const int* __restrict__ labels, const int* __restrict__ keep,
                                                            const int* __restrict__ num_keep, int max_out,
-                                                           const float* __restrict__ im_info, float* __restrict__ out_boxes,
-                                                           float* __restrict__ out_scores, int* __restrict__ out_labels) {
+                                                           const float* __restrict__ im_info, int C, int info_ld,
+                                                           float* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                                           int* __restrict__ out_labels) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= max_out) return;
+    const long long n = blockIdx.y;
+    boxes += n * C * 4; scores += n * C; labels += n * C;
+    keep += n * max_out; num_keep += n; im_info += n * info_ld;
+    out_boxes += n * max_out * 4; out_scores += n * max_out; out_labels += n * max_out;
     f32x4_t b = {0.f, 0.f, 0.f, 0.f};
     float s = 0.f;
     int l = -1;
-    if (j < num_keep[0]) {
+    if (j < num_keep[0]) {   // (this image's count)
         const int i = keep[j];
         b = *reinterpret_cast<const f32x4_t*>(boxes + i * 4ll);
         const float sh = im_info[2] / im_info[0], sw = im_info[3] / im_info[1];
@@ -150,9 +163,29 @@ extern "C" int bd_det_candidates(int mode, const int32_t* topk_idx, const float*
     lv.L = L;
     for (int l = 0; l < L; ++l) lv.row_off[l] = lvl_row_off_host[l];
     hipLaunchKernelGGL(det_candidates_kernel, dim3(cdiv(L * k, 256)), dim3(256), 0, (hipStream_t)stream, mode, topk_idx, topk_score,
-                       topk_cnt, lv, k, K, anchors, (const bf16_raw*)offsets, off_ld, A, make_coder(mean4_host, std4_host), item_boxes,
-                       boxes, scores, labels);
+                       topk_cnt, lv, k, K, anchors, (const bf16_raw*)offsets, 0ll, off_ld, A, make_coder(mean4_host, std4_host), item_boxes,
+                       0ll, boxes, scores, labels);
     BD_CHECK_LAUNCH("bd_det_candidates");
+    return BD_OK;
+}
+
+extern "C" int bd_det_candidates_batched(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int B, int L,
+                                         int k, const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets,
+                                         int64_t off_stride, int off_ld, int A, const float* mean4_host, const float* std4_host,
+                                         const float* item_boxes, int64_t item_stride, float* boxes, float* scores, int32_t* labels,
+                                         bd_stream_t stream) {
+    BD_REQUIRE(topk_idx && topk_score && topk_cnt && lvl_row_off_host && boxes && scores && labels, "det_candidates_batched: null pointer");
+    BD_REQUIRE(mode >= 0 && mode <= 2 && B > 0 && B <= 65535 && L > 0 && L <= BD_MAX_SEGS && k > 0 && K > 0 && A > 0,
+               "det_candidates_batched: bad sizes");
+    BD_REQUIRE(mode == 2 ? item_boxes != nullptr : (anchors && offsets), "det_candidates_batched: missing inputs for mode %d", mode);
+    BD_REQUIRE(off_stride >= 0 && item_stride >= 0, "det_candidates_batched: negative image stride");
+    CandLevels lv{};
+    lv.L = L;
+    for (int l = 0; l < L; ++l) lv.row_off[l] = lvl_row_off_host[l];
+    hipLaunchKernelGGL(det_candidates_kernel, dim3(cdiv(L * k, 256), B), dim3(256), 0, (hipStream_t)stream, mode, topk_idx, topk_score,
+                       topk_cnt, lv, k, K, anchors, (const bf16_raw*)offsets, (long long)off_stride, off_ld, A,
+                       make_coder(mean4_host, std4_host), item_boxes, (long long)item_stride, boxes, scores, labels);
+    BD_CHECK_LAUNCH("bd_det_candidates_batched");
     return BD_OK;
 }
 
@@ -162,7 +195,19 @@ extern "C" int bd_det_finalize(const float* boxes, const float* scores, const in
     BD_REQUIRE(boxes && scores && labels && keep && num_keep && im_info && out_boxes && out_scores && out_labels && max_out > 0,
                "det_finalize: bad arguments");
     hipLaunchKernelGGL(det_finalize_kernel, dim3(cdiv(max_out, 256)), dim3(256), 0, (hipStream_t)stream, boxes, scores, labels, keep,
-                       num_keep, max_out, im_info, out_boxes, out_scores, out_labels);
+                       num_keep, max_out, im_info, 0, 0, out_boxes, out_scores, out_labels);
     BD_CHECK_LAUNCH("bd_det_finalize");
+    return BD_OK;
+}
+
+extern "C" int bd_det_finalize_batched(const float* boxes, const float* scores, const int32_t* labels, const int32_t* keep,
+                                       const int32_t* num_keep, int B, int C, int max_out, const float* im_info, int info_ld,
+                                       float* out_boxes, float* out_scores, int32_t* out_labels, bd_stream_t stream) {
+    BD_REQUIRE(boxes && scores && labels && keep && num_keep && im_info && out_boxes && out_scores && out_labels,
+               "det_finalize_batched: null pointer");
+    BD_REQUIRE(B > 0 && B <= 65535 && C > 0 && max_out > 0 && info_ld >= 4, "det_finalize_batched: bad sizes");
+    hipLaunchKernelGGL(det_finalize_kernel, dim3(cdiv(max_out, 256), B), dim3(256), 0, (hipStream_t)stream, boxes, scores, labels, keep,
+                       num_keep, max_out, im_info, C, info_ld, out_boxes, out_scores, out_labels);
+    BD_CHECK_LAUNCH("bd_det_finalize_batched");
     return BD_OK;
 }

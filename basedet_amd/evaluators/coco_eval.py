@@ -19,6 +19,13 @@ AREA_RNG = {"all": (0.0, 1e10), "small": (0.0, 32.0 ** 2), "medium": (32.0 ** 2,
 MAX_DETS = (1, 10, 100)
 
 
+def _to_numpy(a):
+    """A host array of a torch tensor (any device) or of anything numpy takes."""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    return np.asarray(a)
+
+
 def _iou_xywh(dt, gt, crowd):
     """dt (D,4), gt (G,4) in xywh; crowd (G,) bool -> (D,G); a crowd column uses the detection's area as the union."""
     if len(dt) == 0 or len(gt) == 0:
@@ -143,7 +150,12 @@ class COCOEvaluator:
 
     def postprocess(self, model_outputs, image_id):
         """model_outputs: dict with boxes (D,4) xyxy in original-image pixels, box_scores (D,), box_labels (D,) 0-based
-        (what `model.inference` returns per image)."""
+        (what `model.inference` returns per image; device tensors are copied to the host).  A list of outputs (`inference_batch`)
+        with a list of image ids gives the list of records."""
+        if isinstance(model_outputs, (list, tuple)):
+            assert len(model_outputs) == len(image_id), "one image id per output"
+            return [self.postprocess(o, i) for o, i in zip(model_outputs, image_id)]
+        model_outputs = {k: _to_numpy(model_outputs[k]) for k in ("boxes", "box_scores", "box_labels")}
         boxes = np.asarray(model_outputs["boxes"], dtype=np.float64).reshape(-1, 4)
         if boxes.shape[0] == 0:
             return {"det_res": np.zeros((0, 6)), "image_id": int(image_id)}

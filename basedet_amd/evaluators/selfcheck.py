@@ -58,18 +58,13 @@ def batch_annotations(host_batch):
 
 
 def evaluate_batch(model, cfg, host_batch, dev_batch):
-    """Every image of the batch through model.inference and the evaluator; returns (stats dict, number of detections)."""
+    """The whole batch through one model.inference_batch call and the evaluator; returns (stats dict, number of detections)."""
     was_training = model.training
     model.eval()
     ev = COCOEvaluator(cfg)
-    results = []
     B = host_batch["im_info"].shape[0]
-    for i in range(B):
-        out = model.inference({"data": dev_batch["data"][i:i + 1], "im_info": dev_batch["im_info"][i:i + 1]})
-        n = len(out.box_scores) if hasattr(out, "box_scores") else 0
-        results.append(ev.postprocess({"boxes": out.boxes.cpu().numpy() if n else np.zeros((0, 4)),
-                                       "box_scores": out.box_scores.cpu().numpy() if n else np.zeros((0,)),
-                                       "box_labels": out.box_labels.cpu().numpy() if n else np.zeros((0,))}, image_id=i + 1))
+    outs = model.inference_batch({"data": dev_batch["data"], "im_info": dev_batch["im_info"]})
+    results = ev.postprocess(outs, image_id=[i + 1 for i in range(B)])
     stats = ev.evaluate(ev.format(results), batch_annotations(host_batch))
     if was_training:
         model.train()

@@ -342,35 +342,48 @@ class FasterRCNN(FPNDetector):
                     s_labels=pl.s_labels.cpu().numpy(), s_targets=pl.s_targets.cpu().numpy(), s_count=pl.s_count.cpu().numpy(),
                     rpn_labels=pl.rpn_labels.cpu().numpy())
 
-    def inference(self, inputs):
-        """FasterRCNN.inference (faster_rcnn.py:98-131): RPN proposals (test top-k) -> RoIAlign + box head on every proposal ->
-        softmax scores / per-class decode (rcnn.py:84-93) -> score threshold -> NMS by class -> rescale.
-        The reference thresholds all R*K scores without a cap; here the NMS input is the 2048 best of them."""
+    def _inference_buffers(self, NR):
+        """Box-head buffers of NR RoI rows: views into one grow-only set per model (every plan's `inf` names it), with the fc geometry
+        of that row count.  RoIAlign's forward, the fc layers and bd_rcnn_predict take any row count -- the 512-RoIs-per-image limit
+        noted in __init__ is the tiled BACKWARD's -- and the per-image top-k segment is R * K items whatever N."""
+        K = self.num_classes
+        st = getattr(self, "_inf", None)
+        if st is None or st["rows"] < NR:
+            dev = self.device
+            bf = dict(dtype=torch.bfloat16, device=dev)
+            fin = self.fpn_ch * self.pool[0] * self.pool[1]
+            st = self._inf = dict(rows=NR, geo={}, pooled=torch.empty((NR, fin), **bf), fc1=torch.empty((NR, 1024), **bf),
+                                  fc2=torch.empty((NR, 1024), **bf), raw=torch.empty((NR, self.rcnn_ld), **bf),
+                                  scores=torch.empty((NR * K,), dtype=torch.float32, device=dev),
+                                  boxes=torch.empty((NR * K, 4), dtype=torch.float32, device=dev))
+        if NR not in st["geo"]:
+            st["geo"][NR] = ops.single(1, NR, 1)
+        b = {n: st[n][:NR] for n in ("pooled", "fc1", "fc2", "raw")}
+        b["scores"], b["boxes"], b["g"] = st["scores"][: NR * K], st["boxes"][: NR * K], st["geo"][NR]
+        return b
+
+    def inference_batch(self, inputs):
+        """FasterRCNN.inference (faster_rcnn.py:98-131) for every image of the batch: RPN proposals (test top-k) -> RoIAlign + box head
+        on every proposal -> softmax scores / per-class decode (rcnn.py:84-93) -> score threshold -> NMS by class -> rescale.
+        The reference thresholds all R*K scores without a cap; here the NMS input is the 2048 best of them per image.
+        Returns a list of N Containers (FPNDetector.inference unwraps a single one)."""
         assert not self.training
         pre = self.pre_process(inputs)
         pl = pre["plan"]
-        assert pl.N == 1, "inference supports batch size 1"
         self._cur = pl
         self.network_forward(pl)
         m = self.cfg.MODEL
         info = pre["img_info"]
         self._proposals(pl, info)
-        R = pl.rois.shape[1]
+        N, R = pl.N, pl.rois.shape[1]
         K = self.num_classes
-        dev = self.device
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        if getattr(self, "_inf", None) is None:     # (R rows whatever the shape: one set per model, every plan's `inf` names it)
-            fin = self.fpn_ch * self.pool[0] * self.pool[1]
-            self._inf = dict(pooled=torch.empty((R, fin), **bf), fc1=torch.empty((R, 1024), **bf), fc2=torch.empty((R, 1024), **bf),
-                          raw=torch.empty((R, self.rcnn_ld), **bf), g=ops.single(1, R, 1),
-                          scores=torch.empty((R * K,), dtype=torch.float32, device=dev),
-                          boxes=torch.empty((R * K, 4), dtype=torch.float32, device=dev))
-        b = pl.inf = self._inf
-        ops.roi_align_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, pl.rois.view(-1, 4), None, R, self.pool, 2, b["pooled"])
+        b = pl.inf = self._inference_buffers(N * R)
+        rois = pl.rois.view(-1, 4)
+        ops.roi_align_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, rois, None, R, self.pool, 2, b["pooled"])
         g = b["g"]
         self.fc1.forward(b["pooled"], g, g, b["fc1"], relu=True)
         self.fc2.forward(b["fc1"], g, g, b["fc2"], relu=True)
         self.rcnn_pred.forward(b["fc2"], g, g, b["raw"])
-        ops.rcnn_predict(b["raw"], self.rcnn_ld, K, K + 1, pl.rois.view(-1, 4), pl.num_rois, R, m.RCNN_BOX_REG.MEAN, m.RCNN_BOX_REG.STD,
+        ops.rcnn_predict(b["raw"], self.rcnn_ld, K, K + 1, rois, pl.num_rois, R, m.RCNN_BOX_REG.MEAN, m.RCNN_BOX_REG.STD,
                          b["scores"], b["boxes"])
-        return self._detect(b["scores"], [R], K, 2, info, k=2048, item_boxes=b["boxes"])
+        return self._detect(N, [R], K, 2, info, k=2048, scores=b["scores"], item_boxes=b["boxes"])

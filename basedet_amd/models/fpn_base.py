@@ -644,38 +644,82 @@ class FPNDetector:
     # ------------------------------------------------------------------------------------------------
     # inference post-processing shared by the heads (layers/common/post_processing.py:50-103)
     # ------------------------------------------------------------------------------------------------
-    def _detect(self, scores, lvl_rows, K, mode, info, k=1000, anchors=None, offsets=None, off_ld=4, A=1, mean=(0, 0, 0, 0),
-                std=(1, 1, 1, 1), item_boxes=None):
-        """scores: fp32 [sum(lvl_rows) * K] on the device.  Per level: score > TEST.CLS_THRESHOLD -> top-k (descending) ->
-        label = idx % K, box of row idx // K; then batched NMS by label, keep MAX_BOXES_PER_IMAGE, rescale + clip.
-        Everything stays on the device; the only host read is the final detection count."""
+    def inference(self, inputs):
+        """One image: its detections as a Container (boxes, box_scores, box_labels), as the reference returns them; a batch of N > 1
+        images of one padded shape: the list of the N Containers in batch order (see inference_batch)."""
+        outs = self.inference_batch(inputs)
+        return outs[0] if len(outs) == 1 else outs
+
+    def _detect_scratch(self, N, Ln, k, select_dims=None):
+        """Device scratch of the post-processing chain for N images x Ln levels x top-k: built once per model and (N, Ln, k), reused by
+        every call.  select_dims = (rows, K): also bd_det_select's workspace (its size does not depend on them)."""
+        cache = self.__dict__.setdefault("_det_scratch", {})
+        sc = cache.get((N, Ln, k))
+        if sc is None:
+            dev = self.device
+            i32 = dict(dtype=torch.int32, device=dev)
+            f32 = dict(dtype=torch.float32, device=dev)
+            C = Ln * k
+            max_out = self.cfg.TEST.MAX_BOXES_PER_IMAGE
+            sc = cache[(N, Ln, k)] = dict(
+                tk_idx=torch.empty((N, Ln, k), **i32), tk_sc=torch.empty((N, Ln, k), **f32), tk_cnt=torch.empty((N, Ln), **i32),
+                boxes=torch.empty((N, C, 4), **f32), sc=torch.empty((N, C), **f32), labels=torch.empty((N, C), **i32),
+                keep=torch.empty((N, max_out), **i32), num=torch.zeros((N,), **i32),
+                nms_ws=torch.empty((ops.nms_batched_workspace_bytes(N, C),), dtype=torch.uint8, device=dev))
+        if select_dims is not None and "sel_ws" not in sc:
+            sc["sel_ws"] = torch.empty((ops.det_select_workspace_bytes(N, Ln, *select_dims, k),), dtype=torch.uint8, device=self.device)
+        return sc
+
+    def _detect(self, N, lvl_rows, K, mode, info, k=1000, logits=None, ctr=None, ctr_ld=1, ctr_off=0, scores=None, anchors=None,
+                offsets=None, off_ld=4, A=1, mean=(0, 0, 0, 0), std=(1, 1, 1, 1), item_boxes=None):
+        """Post-processing of N images in one launch chain.  Per image and level: score > TEST.CLS_THRESHOLD -> top-k (descending) ->
+        label = idx % K, box of row idx // K; then batched NMS by label, keep MAX_BOXES_PER_IMAGE, rescale + clip by the image's own
+        im_info row.  The candidates come from `logits` (bf16 [N][sum(lvl_rows)][K], one-stage heads: bd_det_select computes the scores
+        on the fly) or from `scores` (fp32 [N][sum(lvl_rows) * K], the RCNN head's softmax).  Everything stays on the device; the only
+        host read is the N detection counts.  Returns the list of N Containers."""
         from ..structures import Boxes, Container
         t = self.cfg.TEST
         dev = self.device
         Ln = len(lvl_rows)
+        rows = sum(lvl_rows)
         row_off = [0]
         for r in lvl_rows[:-1]:
             row_off.append(row_off[-1] + r)
-        i32 = dict(dtype=torch.int32, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        tk_idx = torch.empty((Ln, k), **i32); tk_sc = torch.empty((Ln, k), **f32); tk_cnt = torch.empty((Ln,), **i32)
-        ops.segment_topk(scores, 1, 0, 1, 1, 0, [r * K for r in row_off], [r * K for r in lvl_rows], k, tk_idx, tk_sc, tk_cnt,
-                         min_score=t.CLS_THRESHOLD)
-        C = Ln * k
-        boxes = torch.empty((C, 4), **f32); sc = torch.empty((1, C), **f32); labels = torch.empty((1, C), **i32)
-        ops.det_candidates(mode, tk_idx, tk_sc, tk_cnt, Ln, k, row_off, K, anchors, offsets, off_ld, A, mean, std, item_boxes,
-                           boxes, sc, labels)
+        s = self._detect_scratch(N, Ln, k, (rows, K) if logits is not None else None)
+        if logits is not None:
+            ops.det_select(logits, N, rows, K, row_off, lvl_rows, k, t.CLS_THRESHOLD, s["tk_idx"], s["tk_sc"], s["tk_cnt"], s["sel_ws"],
+                           ctr=ctr, ctr_ld=ctr_ld, ctr_off=ctr_off)
+        else:
+            ops.segment_topk(scores, N, rows * K, 1, 1, 0, [r * K for r in row_off], [r * K for r in lvl_rows], k, s["tk_idx"], s["tk_sc"],
+                             s["tk_cnt"], min_score=t.CLS_THRESHOLD)
+        # One image goes through the single-image entries of the C ABI: they launch the same two kernels with a one-image grid, and the
+        # launch audit of single-image inference (tests/test_frcnn_audit_gpu.py) names every entry that path may reach.
+        if N == 1:
+            ops.det_candidates(mode, s["tk_idx"], s["tk_sc"], s["tk_cnt"], Ln, k, row_off, K, anchors, offsets, off_ld, A, mean, std,
+                               item_boxes, s["boxes"], s["sc"], s["labels"])
+        else:
+            ops.det_candidates_batched(mode, s["tk_idx"], s["tk_sc"], s["tk_cnt"], N, Ln, k, row_off, K, anchors, offsets,
+                                       offsets.numel() // N if offsets is not None else 0, off_ld, A, mean, std, item_boxes, rows * K,
+                                       s["boxes"], s["sc"], s["labels"])
         max_out = t.MAX_BOXES_PER_IMAGE
-        keep = torch.empty((1, max_out), **i32); num = torch.zeros((1,), **i32)
-        ws = torch.empty((ops.nms_batched_workspace_bytes(1, C),), dtype=torch.uint8, device=dev)
-        ops.nms_batched(boxes, sc, labels, t.IOU_THRESHOLD, max_out, keep, num, ws)
-        ob = torch.empty((max_out, 4), **f32); osc = torch.empty((max_out,), **f32); ol = torch.empty((max_out,), **i32)
-        ops.det_finalize(boxes, sc, labels, keep, num, max_out, info[0].contiguous(), ob, osc, ol)
-        n = int(num.item())
-        if n == 0:
-            e = torch.zeros((0,))
-            return Container(boxes=e, box_scores=e, box_labels=e)
-        return Container(boxes=Boxes(ob[:n]), box_scores=osc[:n], box_labels=ol[:n])
+        s["num"].zero_()
+        ops.nms_batched(s["boxes"], s["sc"], s["labels"], t.IOU_THRESHOLD, max_out, s["keep"], s["num"], s["nms_ws"])
+        # (the results are the caller's: not part of the cached scratch)
+        ob = torch.empty((N, max_out, 4), dtype=torch.float32, device=dev)
+        osc = torch.empty((N, max_out), dtype=torch.float32, device=dev)
+        ol = torch.empty((N, max_out), dtype=torch.int32, device=dev)
+        if N == 1:
+            ops.det_finalize(s["boxes"], s["sc"], s["labels"], s["keep"], s["num"], max_out, info[0].contiguous(), ob, osc, ol)
+        else:
+            ops.det_finalize_batched(s["boxes"], s["sc"], s["labels"], s["keep"], s["num"], max_out, info, ob, osc, ol)
+        outs = []
+        for i, n in enumerate(s["num"].tolist()):
+            if n == 0:
+                e = torch.zeros((0,))
+                outs.append(Container(boxes=e, box_scores=e, box_labels=e))
+            else:
+                outs.append(Container(boxes=Boxes(ob[i, :n]), box_scores=osc[i, :n], box_labels=ol[i, :n]))
+        return outs
 
     # ------------------------------------------------------------------------------------------------
     # backward (replaces GradManager.backward, solver/default_solver.py:118-124)

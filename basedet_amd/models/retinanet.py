@@ -245,18 +245,16 @@ class RetinaNet(FPNDetector):
             out[f"offs_{i}"] = lvl(pl.offsets, i, self.num_anchors * 4)
 
     # ------------------------------------------------------------------------------------------------
-    # inference (retinanet.py:172-201) -- single image, like the reference
+    # inference (retinanet.py:172-201) -- the reference takes one image; here N images of one padded shape share every launch
     # ------------------------------------------------------------------------------------------------
-    def inference(self, inputs):
+    def inference_batch(self, inputs):
+        """The detections of every image of the batch: a list of N Containers (FPNDetector.inference unwraps a single one)."""
         assert not self.training
         pre = self.pre_process(inputs)
         pl = pre["plan"]
-        assert pl.N == 1, "inference supports batch size 1 (retinanet.py:174)"
         self.network_forward(pl)
         K, A = self.num_classes, self.num_anchors
         m = self.cfg.MODEL
-        rows = pl.pyr.pix_per_img * A                               # anchors
-        scores = torch.empty((rows * K,), dtype=torch.float32, device=self.device)
-        ops.det_scores(pl.logits, rows, K, scores)                  # F.sigmoid(F.flatten(logits)) (:184)
-        return self._detect(scores, [h * w * A for h, w in pl.sizes], K, 0, pre["img_info"], anchors=pl.anchors, offsets=pl.offsets,
-                            off_ld=self.box_ld, A=A, mean=m.BOX_REG.MEAN, std=m.BOX_REG.STD)
+        # F.sigmoid(F.flatten(logits)) (:184) happens inside the selection: no score tensor
+        return self._detect(pl.N, [h * w * A for h, w in pl.sizes], K, 0, pre["img_info"], logits=pl.logits, anchors=pl.anchors,
+                            offsets=pl.offsets, off_ld=self.box_ld, A=A, mean=m.BOX_REG.MEAN, std=m.BOX_REG.STD)

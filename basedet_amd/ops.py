@@ -665,6 +665,32 @@ def det_finalize(boxes, scores, labels, keep, num_keep, max_out, im_info, out_bo
                               ptr(out_scores), ptr(out_labels), stream_ptr()), "bd_det_finalize")
 
 
+def det_select_workspace_bytes(B, Ln, rows, K, k):
+    return int(L().bd_det_select_workspace_bytes(B, Ln, rows, K, k))
+
+
+def det_select(logits, B, rows, K, seg_start, seg_rows, k, min_score, out_idx, out_score, out_cnt, ws, ctr=None, ctr_ld=1, ctr_off=0):
+    """Scores + per-level top-k of B images straight from the bf16 logits [B][rows][K] (= det_scores -> segment_topk(min_score), bit for
+    bit); seg_start / seg_rows in rows."""
+    check(L().bd_det_select(ptr(logits), ptr(ctr), ctr_ld, ctr_off, B, rows, K, len(seg_start), i32arr(seg_start), i32arr(seg_rows), k,
+                            float(min_score), ptr(out_idx), ptr(out_score), ptr(out_cnt), ptr(ws), ws.numel() * ws.element_size(),
+                            stream_ptr()), "bd_det_select")
+
+
+def det_candidates_batched(mode, topk_idx, topk_score, topk_cnt, B, Ln, k, lvl_row_off, K, anchors, offsets, off_stride, off_ld, A, mean, std,
+                           item_boxes, item_stride, boxes, scores, labels):
+    check(L().bd_det_candidates_batched(mode, ptr(topk_idx), ptr(topk_score), ptr(topk_cnt), B, Ln, k, i32arr(lvl_row_off), K, ptr(anchors),
+                                        ptr(offsets), off_stride, off_ld, A, f32arr(mean), f32arr(std), ptr(item_boxes), item_stride,
+                                        ptr(boxes), ptr(scores), ptr(labels), stream_ptr()), "bd_det_candidates_batched")
+
+
+def det_finalize_batched(boxes, scores, labels, keep, num_keep, max_out, im_info, out_boxes, out_scores, out_labels):
+    B, Cn = scores.shape
+    check(L().bd_det_finalize_batched(ptr(boxes), ptr(scores), ptr(labels), ptr(keep), ptr(num_keep), B, Cn, max_out, ptr(im_info),
+                                      im_info.shape[1], ptr(out_boxes), ptr(out_scores), ptr(out_labels), stream_ptr()),
+          "bd_det_finalize_batched")
+
+
 # ---- losses -----------------------------------------------------------------------------------------------
 def focal_loss_fwd_bwd(logits, labels, rows, K, alpha, gamma, norm, grad_scale, loss_sum, dlogits, general=False):
     """general: the general-gamma kernel also for gamma == 2 (bd_focal_loss_fwd_bwd_general)"""

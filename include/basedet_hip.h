@@ -639,13 +639,29 @@ int bd_rcnn_loss_fwd_bwd(const void* raw, int ld, int K, int box_off, const int3
 /* ---------------------------------------------------------------------------------------------------------
  * Inference post-processing (retinanet.py:172-209, fcos.py:181-216, rcnn.py:84-93, post_processing.py:50-103):
  * bd_det_scores -> bd_segment_topk(min_score = TEST.CLS_THRESHOLD) -> bd_det_candidates -> bd_nms_batched ->
- * bd_det_finalize.  One image per call, like the reference.
+ * bd_det_finalize for one image, as the reference runs it; for a batch of B images of one padded shape
+ * bd_det_select (one-stage heads: scores and per-level top-k straight from the bf16 logits) or bd_rcnn_predict ->
+ * bd_segment_topk(B) (RCNN head), then bd_det_candidates_batched -> bd_nms_batched(B) -> bd_det_finalize_batched.
+ * The batched chain at B = 1 computes what the single-image chain computes, bit for bit.
  * ------------------------------------------------------------------------------------------------------- */
 
 /* scores[r*K + k] = sigmoid(logits[r*K + k]), or sqrt(sigmoid(logit) * sigmoid(ctr[r*ctr_ld + ctr_off])) when ctr != NULL
  * (fcos.py:194).  logits/ctr bf16, scores fp32. */
 int bd_det_scores(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
                   bd_stream_t stream);
+/* bd_det_scores + bd_segment_topk(min_score) in one entry for B images x L levels, without the fp32 score tensor
+ * (retinanet.py:183-192, fcos.py:194-204).  logits bf16 [B][rows][K]; ctr (optional) bf16 [B][rows][ctr_ld], centerness of a row at
+ * column ctr_off.  Level l is rows [seg_start[l], seg_start[l] + seg_rows[l]) of every image; its item i is logits[b][seg_start[l] +
+ * i / K][i % K], seg_rows[l] * K < 2^24.  score = sigmoid(logit), or sqrt(sigmoid(logit) * sigmoid(ctr)), computed as bd_det_scores
+ * does; the items with score > min_score compete and the best k (<= 2048) come out in bd_segment_topk's order (score descending,
+ * then item index ascending) and layout: out_idx / out_score [B][L][k] (idx -1 past the count), out_cnt [B][L] -- the same bits as
+ * the two calls it replaces, whatever the number of items above the threshold.
+ * Workspace: B * L * (32 + 8192 * 4 + 8192 * 8) bytes (+ padding to 256): per (image, level) a state record, one 8192-bin
+ * histogram and 8192 candidate keys -- independent of rows and K (96 KiB per level against rows * K * 4 bytes of scores). */
+size_t bd_det_select_workspace_bytes(int B, int L, int64_t rows, int K, int k);
+int bd_det_select(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
+                  const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
+                  float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream);
 /* RCNN test branch (rcnn.py:84-93): scores [R][K] = softmax(logits)[:, 1:] (-inf for empty RoI slots),
  * boxes [R][K][4] = BoxCoder.decode(roi, deltas of class k).  raw: bf16 [R][ld] as in bd_rcnn_loss_fwd_bwd. */
 int bd_rcnn_predict(const void* raw, int ld, int K, int box_off, const float* rois, const int32_t* num_rois,
@@ -659,11 +675,25 @@ int bd_det_candidates(int mode, const int32_t* topk_idx, const float* topk_score
                       const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets, int off_ld, int A,
                       const float* mean4_host, const float* std4_host, const float* item_boxes, float* boxes, float* scores,
                       int32_t* labels, bd_stream_t stream);
+/* bd_det_candidates for B images in one launch: topk_* [B][L][k] / [B][L] (bd_det_select, or bd_segment_topk with B images).
+ * anchors / points (modes 0, 1) are shared by the images; image b reads its offsets at offsets + b * off_stride (bf16 elements)
+ * and, in mode 2, its boxes at item_boxes + b * item_stride * 4 (item_stride counted in boxes).  Outputs [B][L*k], the layout
+ * bd_nms_batched takes. */
+int bd_det_candidates_batched(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int B, int L,
+                              int k, const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets,
+                              int64_t off_stride, int off_ld, int A, const float* mean4_host, const float* std4_host,
+                              const float* item_boxes, int64_t item_stride, float* boxes, float* scores, int32_t* labels,
+                              bd_stream_t stream);
 /* post_processing.py:93-101: out[j] = candidate keep[j] scaled by (im_info[2]/im_info[0], im_info[3]/im_info[1]) and
  * clipped to (im_info[2], im_info[3]); slots past num_keep[0]: zero box, label -1. */
 int bd_det_finalize(const float* boxes, const float* scores, const int32_t* labels, const int32_t* keep,
                     const int32_t* num_keep, int max_out, const float* im_info, float* out_boxes, float* out_scores,
                     int32_t* out_labels, bd_stream_t stream);
+/* bd_det_finalize for B images in one launch: candidates [B][C], keep [B][max_out] and num_keep [B] as bd_nms_batched wrote them
+ * (keep_ld = max_out), im_info [B][info_ld] -- every image is rescaled and clipped by its own row.  Outputs [B][max_out]. */
+int bd_det_finalize_batched(const float* boxes, const float* scores, const int32_t* labels, const int32_t* keep,
+                            const int32_t* num_keep, int B, int C, int max_out, const float* im_info, int info_ld,
+                            float* out_boxes, float* out_scores, int32_t* out_labels, bd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Optimizer (megengine.optimizer.SGD as configured at solver/default_solver.py:96-114).
