@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 101              # bd_version() of the library this binding's ConvDesc matches (101: the liveness-map fields)
+ABI_VERSION = 102              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -158,6 +158,9 @@ SIGNATURES = {
     "bd_det_candidates_batched": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P]),
     "bd_det_finalize_batched": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "bd_sgd_momentum_step": (_I, [_P, _P, _P, _L, _F, _F, _F, _F, _P]),
+    "bd_ema_update": (_I, [_P, _P, _L, _F, _F, _P]),
+    "bd_sgd_momentum_ema_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P]),
+    "bd_swap_f32": (_I, [_P, _P, _L, _P]),
     "bd_clip_grad_value": (_I, [_P, _L, _F, _F, _F, _P]),
     "bd_clip_grad_norm_workspace_bytes": (_Z, []),
     "bd_clip_grad_norm": (_I, [_P, _L, _F, _F, _F, _P, _P, _Z, _P]),

@@ -171,6 +171,12 @@ static inline const char* bd_tune_env_str(const char*) { return nullptr; }
 struct BdGskipMap { int p4, p8, m4, m8, live, list; size_t ints; };
 void bd_gskip_map_layout(const bd_conv_desc* d, int side, BdGskipMap* out);      // side 0: the map of g, 1: of dx
 
+// blocks of a grid-stride launch over n work items: enough to cover them once, capped (the loop takes the rest)
+static inline int grid_for(long long n, int block = 256, int cap = 4096) {
+    long long g = (n + block - 1) / block;
+    if (g < 1) g = 1;
+    return (int)(g < cap ? g : cap);
+}
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

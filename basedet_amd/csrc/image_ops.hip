@@ -34,7 +34,7 @@ extern "C" const char* bd_last_error_string(void) { return g_bd_error.c_str(); }
 static thread_local const char* g_bd_last_kernel = "";
 void bd_note_kernel(const char* name) { g_bd_last_kernel = name; }
 extern "C" const char* bd_conv_last_kernel(void) { return g_bd_last_kernel; }
-extern "C" int bd_version(void) { return 101; }
+extern "C" int bd_version(void) { return 102; }
 
 namespace {
 
@@ -387,12 +387,6 @@ __global__ void sgd_kernel(float* __restrict__ w, float* __restrict__ v, const f
             }
         }
     }
-}
-
-inline int grid_for(long long n, int block = 256, int cap = 4096) {
-    long long g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    return (int)(g < cap ? g : cap);
 }
 
 }  // namespace

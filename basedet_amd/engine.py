@@ -1,9 +1,11 @@
 """DetTrainer (basedet/engine/trainer.py:12-100): the loop that calls the hot path -- `solver.minimize(model, batch)` once per
-iteration (:98) with the LR schedule stepped before it (engine/hooks.py:218).  Everything else the reference hangs on its trainer
-(checkpoint / eval / tensorboard hooks, EMA, resume) is control plane and out of this build's scope."""
+iteration (:98) with the LR schedule stepped before it (engine/hooks.py:218), and the moving average of the weights (TRAINER.EMA,
+:63-72,99-100; layers/ema.py) stepped after it.  Everything else the reference hangs on its trainer (checkpoint / eval / tensorboard
+hooks, resume) is control plane and out of this build's scope."""
 import time
 
 from . import comm as _comm
+from .layers.ema import ModelEMA, calculate_momentum
 from .solver import WarmupMultiStepLR, clip_grad
 from .utils.registry import registers
 
@@ -35,6 +37,14 @@ class DetTrainer:
         gc = t.get("GRAD_CLIP", {})
         if gc.get("ENABLE", False):                                            # trainer.py:56-61
             self.solver.grad_clip_fn = clip_grad(self.model, gc["TYPE"], **dict(gc["ARGS"]))
+        ema_cfg = t.get("EMA", None)                                           # trainer.py:63-72
+        self.enable_ema = False if ema_cfg is None else bool(ema_cfg["ENABLE"])
+        if self.enable_ema:
+            momentum = ema_cfg["MOMENTUM"]
+            if momentum is None:
+                total_iter = self.progress.max_epoch * self.progress.max_iter
+                momentum = calculate_momentum(ema_cfg["ALPHA"], total_iter, ema_cfg["UPDATE_PERIOD"])
+            self.ema = ModelEMA(self.model, momentum, burnin_iter=ema_cfg["BURNIN_ITER"])
         self.meter = {}
         self.log_interval = cfg.GLOBAL.LOG_INTERVAL
         self._hooks = list(hooks or [])
@@ -50,7 +60,11 @@ class DetTrainer:
 
     def model_step(self, model_inputs):
         """trainer.py:88-100."""
-        return self.solver.minimize(self.model, model_inputs)
+        if not self.enable_ema:
+            return self.solver.minimize(self.model, model_inputs)
+        model_outputs = self.solver.minimize(self.model, model_inputs, ema=self.ema)
+        self.ema.step()
+        return model_outputs
 
     def train(self, max_iters=None, log=print):
         """BaseTrainer.train: epochs x iterations; `max_iters` bounds a smoke run."""

@@ -6,6 +6,7 @@ from .box_ops import (  # noqa: F401
 from .losses import (  # noqa: F401
     binary_cross_entropy, iou_loss, sigmoid_focal_loss, smooth_l1_loss, weighted_cross_entropy,
 )
+from .ema import ModelEMA, calculate_momentum  # noqa: F401
 from .roi_pool import assign_rois, roi_pool, sample_labels  # noqa: F401
 from .modules import FPN, PointHead, RetinaNetHead, build_backbone, resnet18, resnet34, resnet50, resnet101  # noqa: F401
 from ..structures import box_center, box_ioa, box_iou  # noqa: F401

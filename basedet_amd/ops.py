@@ -781,6 +781,34 @@ def sgd_momentum_step(w, v, g, lr, momentum, wd, grad_scale=1.0):
                                    float(grad_scale), stream_ptr()), "bd_sgd_momentum_step")
 
 
+def ema_coeffs(m):
+    """(m, 1 - m) as the reference hands them to its kernels (ema.py:80: `mge.tensor(m)`, `mge.tensor(1 - m)`): the difference is taken
+    in Python float64, the cast to fp32 happens at the C boundary."""
+    return float(m), float(1 - m)
+
+
+def _same_f32(*ts):
+    assert all(t.dtype == torch.float32 and t.numel() == ts[0].numel() for t in ts), "fp32 buffers of one length expected"
+
+
+def ema_update(e, w, m):
+    _same_f32(e, w)
+    mm, om = ema_coeffs(m)
+    check(L().bd_ema_update(ptr(e), ptr(w), e.numel(), mm, om, stream_ptr()), "bd_ema_update")
+
+
+def sgd_momentum_ema_step(w, v, g, e, lr, momentum, wd, grad_scale, m):
+    _same_f32(w, v, g, e)
+    mm, om = ema_coeffs(m)
+    check(L().bd_sgd_momentum_ema_step(ptr(w), ptr(v), ptr(g), ptr(e), w.numel(), float(lr), float(momentum), float(wd),
+                                       float(grad_scale), mm, om, stream_ptr()), "bd_sgd_momentum_ema_step")
+
+
+def swap_f32(a, b):
+    _same_f32(a, b)
+    check(L().bd_swap_f32(ptr(a), ptr(b), a.numel(), stream_ptr()), "bd_swap_f32")
+
+
 class WgradQueue:
     """bd_wgrad_queue_*: weight-gradient launches whose reduces are deferred to ONE launch per flush (the solver's gradient buckets).
     Every queued layer must keep its own workspace untouched until `flush`."""

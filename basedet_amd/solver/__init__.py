@@ -23,10 +23,17 @@ class SGD:
         self.model = model
         self.param_groups = [_ParamGroupView(lr=lr, weight_decay=weight_decay, momentum=momentum)]
 
-    def step(self, grad_scale=1.0):
+    def step(self, grad_scale=1.0, ema=None):
+        """`ema`: the trainer's ModelEMA (engine/trainer.py:98-100 steps it right after minimize).  Past its burn-in the average is
+        updated from the new weights inside this launch (bd_sgd_momentum_ema_step; `ema.step()` then only counts); up to and including
+        the burn-in iteration, and without `ema`, the launch is the plain one."""
         a = self.model.arena
         g = self.param_groups[0]
-        ops.sgd_momentum_step(a.w, a.v, a.g, g["lr"], g["momentum"], g["weight_decay"], grad_scale)
+        m = ema.fused_momentum() if ema is not None else None
+        if m is None:
+            ops.sgd_momentum_step(a.w, a.v, a.g, g["lr"], g["momentum"], g["weight_decay"], grad_scale)
+        else:
+            ops.sgd_momentum_ema_step(a.w, a.v, a.g, ema.e, g["lr"], g["momentum"], g["weight_decay"], grad_scale, m)
         self.model.repack_trainable()
         return self
 
@@ -148,19 +155,19 @@ class Solver:
         self.grad_scaler = grad_scaler
         self.grad_clip_fn = grad_clip_fn
 
-    def minimize(self, model, inputs):
-        """One training step (basecore Solver.minimize; called at engine/trainer.py:98).  `high_priority_main = True` runs the step's main
+    def minimize(self, model, inputs, ema=None):
+        """One training step (basecore Solver.minimize; called at engine/trainer.py:98); `ema`: see SGD.step.  `high_priority_main = True` runs the step's main
         chain (forward, losses, data gradients, SGD) on a HIGH-priority stream owned by the solver, ahead of the weight-gradient side
         stream at workgroup dispatch (the caller's stream waits for it at the end).  Round 2 measured +0.8 % for it; since layer1 runs as
         one persistent launch per block (round 3) the caller's default-priority stream is the faster one -- 9 of 9 alternations on two
         boxes, +0.5 % on average -- and is the default."""
         hp = self._main_stream(model)
         if hp is None:
-            return self._step(model, inputs)
+            return self._step(model, inputs, ema)
         cur = torch.cuda.current_stream()
         hp.wait_stream(cur)
         with torch.cuda.stream(hp):
-            losses = self._step(model, inputs)
+            losses = self._step(model, inputs, ema)
         cur.wait_stream(hp)
         return losses
 
@@ -172,7 +179,7 @@ class Solver:
             self._hp = torch.cuda.Stream(device=model.device, priority=-1)
         return self._hp
 
-    def _step(self, model, inputs):
+    def _step(self, model, inputs, ema=None):
         losses = model(inputs)
         model.backward(on_bucket_ready=self.buckets.on_ready)
         prof = getattr(self, "comm_profile", None)        # bench.py (N > 1): [(backward done on this stream, collectives done on the comm stream)]
@@ -192,7 +199,10 @@ class Solver:
                     model.arena.g.mul_(scale)
                 self.grad_clip_fn()
                 scale = 1.0
-        self.optimizer.step(grad_scale=scale)
+        if ema is None:
+            self.optimizer.step(grad_scale=scale)
+        else:
+            self.optimizer.step(grad_scale=scale, ema=ema)
         self.optimizer.clear_grad()
         return losses
 

@@ -24,6 +24,7 @@ def default_parser():
     p.add_argument("-f", "--file", type=str, required=True, help="training process description file (defines Cfg)")
     p.add_argument("-n", "--ngpus", type=int, default=1, help="number of GPUs (processes) on this node")
     p.add_argument("--iters", type=int, default=None, help="stop after this many iterations (smoke runs)")
+    p.add_argument("--ema", action="store_true", help="use model ema during training or not")
     p.add_argument("--synthetic", action="store_true",
                    help="train on the synthetic DummyLoader batches (utils/dummy.py) -- the ONLY data source of this build: dataset "
                         "readers are outside the hot-path scope, so without this flag (or DATA.BUILDER_NAME DummyLoader) the entry refuses to run")
@@ -41,14 +42,22 @@ def load_cfg(path):
     return mod.Cfg()
 
 
+def apply_flags(cfg, args):
+    """det_train.py:77-80: the switches that set a config key."""
+    if args.ema:
+        cfg.TRAINER.EMA.ENABLE = True
+    if args.synthetic:
+        cfg.DATA.BUILDER_NAME = "DummyLoader"
+    return cfg
+
+
 def worker(args):
     import torch
     from basedet_amd import comm
     cfg = load_cfg(args.file)
     if args.opts:
         cfg.merge(args.opts)                                            # det_train.py:71
-    if args.synthetic:
-        cfg.DATA.BUILDER_NAME = "DummyLoader"
+    apply_flags(cfg, args)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         comm.set_comm(comm.Comm.from_env())
     else:

@@ -713,6 +713,20 @@ int bd_clip_grad_value(float* g, int64_t n, float pre_scale, float lower, float 
 size_t bd_clip_grad_norm_workspace_bytes(void);
 int bd_clip_grad_norm(float* g, int64_t n, float pre_scale, float max_norm, float ord, float* norm_out, void* ws, size_t ws_bytes,
                       bd_stream_t stream);
+/* Moving average of the weights (TRAINER.EMA; bd_version() >= 102), over the flat fp32 arena like the launches above.  All three:
+ * n == 0 is a no-op; BD_EINVAL for a null pointer, a base pointer that is not 16-byte aligned, or overlapping buffers.
+ * ModelEMA.update (layers/common/ema.py:71-81, `v * m + (1 - m) * model_state` per tensor): e = e*m + one_minus_m*w with both products
+ * and the sum rounded to fp32 separately (no FMA), which is what the reference's three elementwise kernels compute.  one_minus_m is
+ * the caller's float32(1 - m) formed in double precision, as `mge.tensor(1 - m)` forms it.  m = 0 (the burn-in copy, ema.py:65-67)
+ * runs the same arithmetic. */
+int bd_ema_update(float* e, const float* w, int64_t n, float m, float one_minus_m, bd_stream_t stream);
+/* `solver.minimize` followed by `ema.step()` (engine/trainer.py:98-100) in one pass: bd_sgd_momentum_step's update -- w and v get the
+ * same bits -- then bd_ema_update's with the new w, 28 bytes per parameter instead of 20 + 12. */
+int bd_sgd_momentum_ema_step(float* w, float* v, const float* g, float* e, int64_t n, float lr, float momentum, float wd,
+                             float grad_scale, float m, float one_minus_m, bd_stream_t stream);
+/* a <-> b.  Evaluating the averaged model (engine/hooks.py:275-282 runs the evaluator on `ema.ema`, a second module): here the average
+ * trades places with the arena's weights for the length of the evaluation, so no third arena-sized buffer exists. */
+int bd_swap_f32(float* a, float* b, int64_t n, bd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * fp8 (OCP e4m3) forward convolutions on the block-scaled MFMA (BASELINE config 5, "fp8 weights").  The reference's
