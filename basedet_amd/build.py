@@ -36,6 +36,7 @@ SOURCES = {
     "fpn_deconv.hip": [],
     "stem.hip": [],
     "boxops.hip": ["-ffp-contract=off"],
+    "nms.hip": ["-ffp-contract=off"],
     "rcnn_ops.hip": ["-ffp-contract=off"],
     "postprocess.hip": ["-ffp-contract=off"],
     "det_select.hip": ["-ffp-contract=off"],

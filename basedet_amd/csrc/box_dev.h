@@ -1,5 +1,6 @@
-// Device helpers shared by the box-operator translation units (boxops.hip, rcnn_ops.hip).  Both are compiled with
-// -ffp-contract=off so that IoU / encode / decode values are bit-identical to the float32 numpy oracle.
+// Device helpers shared by the box-operator translation units (boxops.hip, nms.hip, rcnn_ops.hip and the other includers of
+// select_dev.h).  All are compiled with -ffp-contract=off so that IoU / encode / decode values are bit-identical to the float32 numpy
+// oracle.
 #pragma once
 #include "common.h"
 

@@ -377,94 +377,6 @@ __global__ __launch_bounds__(256) void atss_finalize_kernel(const float* __restr
     if ((threadIdx.x & 63) == 0 && fgf > 0.f) atomicAdd(stats, fgf);          // (the centre-ness sum: ctr_sum_kernel, fixed order)
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// batched NMS (layers/common/post_processing.py:17-47)
-// ------------------------------------------------------------------------------------------------------------
-constexpr int NMS_MAX = 16384;
-
-// one workgroup: max coordinate, class-offset boxes, bitonic sort of (score desc, index asc)
-__global__ __launch_bounds__(1024) void nms_prepare_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
-                                                           const int* __restrict__ idxs, int n, int npow2,
-                                                           float* __restrict__ sboxes, int* __restrict__ order) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
-    __shared__ float red[16];
-    const int tid = threadIdx.x;
-    float mx = -INFINITY;
-    for (int i = tid; i < n * 4; i += 1024) mx = fmaxf(mx, boxes[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = red[0];
-    for (int k = 1; k < 16; ++k) mx = fmaxf(mx, red[k]);
-    const float step = mx + 1.f;                                   // post_processing.py:44-45
-    for (int i = tid; i < npow2; i += 1024) {
-        unsigned long long key = ~0ull;
-        if (i < n) {
-            key = ((unsigned long long)float_desc_key(scores[i]) << 32) | (unsigned int)i;
-            const float off = idxs ? (float)idxs[i] * step : 0.f;
-            const Box b = ld_box(boxes + i * 4ll);
-            f32x4_t o = {b.x1 + off, b.y1 + off, b.x2 + off, b.y2 + off};
-            *reinterpret_cast<f32x4_t*>(sboxes + i * 4ll) = o;
-        }
-        keys[i] = key;
-    }
-    __syncthreads();
-    for (int k = 2; k <= npow2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < npow2; i += 1024) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], b = keys[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) { keys[i] = b; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < n; i += 1024) order[i] = (int)(keys[i] & 0xffffffffu);
-}
-
-// mask[i][w] bit b: sorted box (w*64+b) is suppressed by sorted box i  (iou > thr, j > i)
-__global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ sboxes, const int* __restrict__ order, int n,
-                                                      float thr, unsigned long long* __restrict__ mask, int words) {
-    const int i = blockIdx.x;          // sorted row
-    const int w = blockIdx.y;          // column word
-    const int j = w * 64 + threadIdx.x;
-    bool sup = false;
-    if (j < n && j > i) {
-        const Box a = ld_box(sboxes + order[i] * 4ll), b = ld_box(sboxes + order[j] * 4ll);
-        const float inter = box_inter(a, b);
-        const float uni = (box_area(a) + box_area(b)) - inter;
-        sup = (inter / uni) > thr;     // keep iff iou <= thr (py_cpu_nms, post_processing.py:130)
-    }
-    const unsigned long long bal = __ballot(sup);
-    if (threadIdx.x == 0) mask[(long long)i * words + w] = bal;
-}
-
-// one wave walks the sorted list; removed[] lives in LDS (words <= 256)
-__global__ __launch_bounds__(64) void nms_scan_kernel(const unsigned long long* __restrict__ mask, const int* __restrict__ order,
-                                                      int n, int words, int max_output, int* __restrict__ keep,
-                                                      int* __restrict__ num_keep) {
-    __shared__ unsigned long long removed[NMS_MAX / 64];
-    const int lane = threadIdx.x;
-    for (int w = lane; w < words; w += 64) removed[w] = 0ull;
-    __syncthreads();
-    int cnt = 0;
-    for (int i = 0; i < n; ++i) {
-        const unsigned long long r = removed[i >> 6];
-        if ((r >> (i & 63)) & 1ull) continue;   // wave-uniform
-        if (lane == 0) keep[cnt] = order[i];
-        ++cnt;
-        if (max_output > 0 && cnt >= max_output) break;
-        for (int w = lane; w < words; w += 64) removed[w] |= mask[(long long)i * words + w];
-        __syncthreads();
-    }
-    if (lane == 0) *num_keep = cnt;
-}
-
 }  // namespace
 
 extern "C" int bd_anchors_generate(int H, int W, int stride, float offset, const float* base, int A, float* out,
@@ -602,44 +514,5 @@ extern "C" int bd_atss_assign(const float* points, int P, const int32_t* lvl_sta
                        (const unsigned long long*)ws, labels, offsets, ctrness, stats);
     hipLaunchKernelGGL(ctr_sum_kernel, dim3(1), dim3(1024), 0, st, (const int*)labels, (const float*)ctrness, (long long)N * P, stats);
     BD_CHECK_LAUNCH("bd_atss_assign");
-    return BD_OK;
-}
-
-static inline int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-
-extern "C" size_t bd_nms_workspace_bytes(int n) {
-    if (n <= 0) return 16;
-    const size_t words = (size_t)cdiv(n, 64);
-    return (size_t)n * 16 + (size_t)n * 4 + (size_t)n * words * 8 + 64;
-}
-
-extern "C" int bd_batched_nms(const float* boxes, const float* scores, const int32_t* idxs, int n, float iou_thresh,
-                              int max_output, int32_t* keep, int32_t* num_keep, void* ws, size_t ws_bytes,
-                              bd_stream_t stream) {
-    BD_REQUIRE(num_keep, "batched_nms: null num_keep");
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) { (void)hipMemsetAsync(num_keep, 0, sizeof(int32_t), st); return BD_OK; }
-    BD_REQUIRE(boxes && scores && keep && ws, "batched_nms: null pointer");
-    BD_REQUIRE(n > 0 && n <= NMS_MAX, "batched_nms: n=%d out of range (1..%d)", n, NMS_MAX);
-    if (ws_bytes < bd_nms_workspace_bytes(n)) {
-        bd_set_error("batched_nms: workspace %zu < %zu bytes", ws_bytes, bd_nms_workspace_bytes(n));
-        return BD_EWORKSPACE;
-    }
-    const int words = cdiv(n, 64);
-    unsigned char* p = (unsigned char*)ws;
-    float* sboxes = (float*)p;                 p += (size_t)n * 16;
-    int* order = (int*)p;                      p += (((size_t)n * 4 + 15) / 16) * 16;
-    unsigned long long* mask = (unsigned long long*)p;
-    const int npow2 = next_pow2(n);
-    const size_t lds = (size_t)npow2 * 8;
-    BD_ONCE_PER_DEVICE(
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_prepare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  NMS_MAX * 8));
-    hipLaunchKernelGGL(nms_prepare_kernel, dim3(1), dim3(1024), lds, st, boxes, scores, idxs, n, npow2, sboxes, order);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(n, words), dim3(64), 0, st, (const float*)sboxes, (const int*)order, n,
-                       iou_thresh, mask, words);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)mask, (const int*)order, n, words,
-                       max_output, keep, num_keep);
-    BD_CHECK_LAUNCH("bd_batched_nms");
     return BD_OK;
 }

@@ -208,19 +208,7 @@ __global__ __launch_bounds__(1024) void det_select_sort_kernel(const SegState* _
     const unsigned long long* src = cand + sid * DS_SORT_N;
     for (int i = tid; i < P; i += 1024) keys[i] = i < n ? src[i] : 0ull;       // (a valid key is >= 2^24)
     __syncthreads();
-    for (int kk = 2; kk <= P; kk <<= 1) {                   // bitonic sort, descending
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += 1024) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], b = keys[ixj];
-                    const bool up = (i & kk) == 0;
-                    if ((a < b) == up) { keys[i] = b; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_1024<true>(keys, P);
     for (int i = tid; i < k; i += 1024) {
         int idx = -1;
         float sc = 0.f;

@@ -1,13 +1,14 @@
-// Faster R-CNN operators on the HIP path: RPN proposal selection (per-level top-k, decode, clip, size filter, NMS across
-// levels), random subsampling of labels, RoI sampling + target encoding, multi-level RoIAlign forward / backward and the
+// Faster R-CNN operators on the HIP path: RPN proposal selection (per-level top-k, decode, clip, size filter; its NMS across
+// levels is nms.hip's, called through nms.h), random subsampling of labels, RoI sampling + target encoding, multi-level RoIAlign forward / backward and the
 // FPNP6 sub-sampling.  Reference: models/det/rpn.py, layers/head/rcnn.py, layers/common/roi_pool.py,
 // layers/common/sampling.py, layers/backbone/fpn_backbone.py:172-183.
 //
-// Everything that decides an index (top-k membership, NMS survivors, fg/bg sampling) is integer / exact-fp32 work and is
+// Everything that decides an index (top-k membership, fg/bg sampling) is integer / exact-fp32 work and is
 // bit-exact against oracle/rcnn_ops.py; this translation unit is compiled with -ffp-contract=off like boxops.hip.
 // All kernels are HBM/LDS-latency bound selection passes: one workgroup per (image, level) or per image, wave ballots
 // and LDS histograms instead of global sorts.
 #pragma clang fp contract(off)
+#include "nms.h"
 #include "select_dev.h"
 
 namespace {
@@ -83,20 +84,7 @@ __global__ __launch_bounds__(1024) void segment_topk_kernel(const void* __restri
         }
     }
     __syncthreads();
-    // bitonic sort, descending
-    for (int kk = 2; kk <= TOPK_MAX; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < TOPK_MAX; i += 1024) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], b = keys[ixj];
-                    const bool up = (i & kk) == 0;
-                    if ((a < b) == up) { keys[i] = b; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_1024<true>(keys, TOPK_MAX);
     const long long ob = ((long long)n * segs.nseg + seg) * k;
     for (int i = tid; i < k; i += 1024) {
         int idx = -1;
@@ -115,8 +103,6 @@ __global__ __launch_bounds__(1024) void segment_topk_kernel(const void* __restri
 // ------------------------------------------------------------------------------------------------------------
 // RPN: decode + clip + size filter of the per-level top-k candidates (rpn.py:150-172)
 // ------------------------------------------------------------------------------------------------------------
-struct RpnLevels { int pix_off[BD_MAX_SEGS]; int cand_off[BD_MAX_SEGS + 1]; int L; };
-
 __global__ __launch_bounds__(256) void rpn_decode_kernel(const bf16_raw* __restrict__ raw, long long ppi, int ldc, int A, int doff,
                                                          const float* __restrict__ anchors, RpnLevels lv, int k,
                                                          const int* __restrict__ topk_idx, const float* __restrict__ topk_score,
@@ -151,363 +137,6 @@ __global__ __launch_bounds__(256) void rpn_decode_kernel(const bf16_raw* __restr
     *reinterpret_cast<f32x4_t*>(boxes + o * 4) = box;
     scores[o] = sc;
     levels[o] = l;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// batched NMS over B independent problems of capacity C (post_processing.py:17-47 per problem).
-// Items with score == -inf are absent.  Greedy order: score descending, then index ascending.
-// ------------------------------------------------------------------------------------------------------------
-constexpr int NMSB_MAX = 16384;
-
-__global__ __launch_bounds__(1024) void nmsb_prepare_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
-                                                            const int* __restrict__ idxs, int C, int npow2,
-                                                            float* __restrict__ sboxes, int* __restrict__ order,
-                                                            int* __restrict__ nvalid) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
-    __shared__ float red[16];
-    __shared__ int cnt_sh;
-    const int tid = threadIdx.x;
-    const long long b0 = (long long)blockIdx.x * C;
-    boxes += b0 * 4; scores += b0; sboxes += b0 * 4; order += b0;
-    if (idxs) idxs += b0;
-    if (tid == 0) cnt_sh = 0;
-    float mx = -INFINITY;
-    int nv = 0;
-    for (int i = tid; i < C; i += 1024) {
-        if (scores[i] > -INFINITY) {
-            const Box b = ld_box(boxes + i * 4ll);
-            mx = fmaxf(mx, fmaxf(fmaxf(b.x1, b.y1), fmaxf(b.x2, b.y2)));
-            ++nv;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    if (nv) atomicAdd(&cnt_sh, nv);
-    mx = red[0];
-    for (int q = 1; q < 16; ++q) mx = fmaxf(mx, red[q]);
-    const float step = mx + 1.f;                                   // post_processing.py:44-45
-    for (int i = tid; i < npow2; i += 1024) {
-        unsigned long long key = ~0ull;
-        if (i < C) {
-            key = ((unsigned long long)float_desc_key(scores[i]) << 32) | (unsigned int)i;
-            const float off = idxs ? (float)idxs[i] * step : 0.f;
-            const Box b = ld_box(boxes + i * 4ll);
-            f32x4_t o = {b.x1 + off, b.y1 + off, b.x2 + off, b.y2 + off};
-            *reinterpret_cast<f32x4_t*>(sboxes + i * 4ll) = o;
-        }
-        keys[i] = key;
-    }
-    __syncthreads();
-    for (int kk = 2; kk <= npow2; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < npow2; i += 1024) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], b = keys[ixj];
-                    const bool up = (i & kk) == 0;
-                    if ((a > b) == up) { keys[i] = b; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < C; i += 1024) order[i] = (int)(keys[i] & 0xffffffffu);
-    if (tid == 0) nvalid[blockIdx.x] = cnt_sh;
-}
-
-// 64 sorted rows x 64 sorted columns per wave; mask[i][w] bit b: sorted box (64w+b) is suppressed by sorted box i.
-// Only the upper triangle (w >= i/64) inside the valid range is written -- the scan never reads anything else.
-__global__ __launch_bounds__(64) void nmsb_mask_kernel(const float* __restrict__ sboxes, const int* __restrict__ order,
-                                                       const int* __restrict__ nvalid, int C, int words, float thr,
-                                                       unsigned long long* __restrict__ mask) {
-    __shared__ float rows[64 * 4];
-    const int rt = blockIdx.x, w = blockIdx.y, b = blockIdx.z;
-    const int nv = nvalid[b];
-    if (w < rt || rt * 64 >= nv || w * 64 >= nv) return;
-    const long long b0 = (long long)b * C;
-    sboxes += b0 * 4; order += b0; mask += b0 * words;
-    const int lane = threadIdx.x;
-    const int j = w * 64 + lane;
-    Box cb{0.f, 0.f, 0.f, 0.f};
-    if (j < nv) cb = ld_box(sboxes + order[j] * 4ll);
-    const int ri = rt * 64 + lane;
-    f32x4_t rb = {0.f, 0.f, 0.f, 0.f};
-    if (ri < nv) rb = *reinterpret_cast<const f32x4_t*>(sboxes + order[ri] * 4ll);
-    *reinterpret_cast<f32x4_t*>(rows + lane * 4) = rb;
-    __syncthreads();
-    const float ca = box_area(cb);
-    const int rmax = min(64, nv - rt * 64);
-    unsigned long long mine = 0ull;
-    for (int q = 0; q < rmax; ++q) {
-        const int i = rt * 64 + q;
-        const Box a = Box{rows[q * 4], rows[q * 4 + 1], rows[q * 4 + 2], rows[q * 4 + 3]};
-        bool sup = false;
-        if (j < nv && j > i) {
-            const float inter = box_inter(a, cb);
-            const float uni = (box_area(a) + ca) - inter;
-            sup = (inter / uni) > thr;     // keep iff iou <= thr (py_cpu_nms, post_processing.py:130)
-        }
-        const unsigned long long bal = __ballot(sup);
-        if (lane == q) mine = bal;
-    }
-    if (lane < rmax) mask[(long long)(rt * 64 + lane) * words + w] = mine;
-}
-
-// one wave per problem walks the sorted list 64 boxes at a time: the diagonal 64x64 block is resolved in registers,
-// then the rows of the survivors are OR-ed into the LDS `removed` bitmap with independent (pipelined) loads.
-__global__ __launch_bounds__(64) void nmsb_scan_kernel(const unsigned long long* __restrict__ mask, const int* __restrict__ order,
-                                                       const int* __restrict__ nvalid, int C, int words, int max_output,
-                                                       int keep_ld, int* __restrict__ keep, int* __restrict__ num_keep) {
-    __shared__ unsigned long long removed[NMSB_MAX / 64];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const long long b0 = (long long)b * C;
-    mask += b0 * words; order += b0; keep += (long long)b * keep_ld;
-    const int nv = nvalid[b];
-    const int nw = (nv + 63) >> 6;
-    for (int w = lane; w < nw; w += 64) removed[w] = 0ull;
-    __syncthreads();
-    int cnt = 0;
-    const int cap = max_output > 0 ? max_output : nv;
-    for (int c = 0; c < nw && cnt < cap; ++c) {
-        const int i0 = c * 64;
-        const int i = i0 + lane;
-        const unsigned long long diag = i < nv ? mask[(long long)i * words + c] : 0ull;
-        const int nin = min(64, nv - i0);
-        unsigned long long alive = ~removed[c];
-        if (nin < 64) alive &= (1ull << nin) - 1ull;
-        unsigned long long kept = 0ull;
-        const unsigned int dlo = (unsigned int)diag, dhi = (unsigned int)(diag >> 32);
-        for (int q = 0; q < nin; ++q) {
-            if ((alive >> q) & 1ull) {                                   // wave-uniform
-                kept |= 1ull << q;
-                const unsigned long long row = ((unsigned long long)(unsigned int)__shfl((int)dhi, q, 64) << 32) |
-                                               (unsigned int)__shfl((int)dlo, q, 64);
-                alive &= ~row;
-            }
-        }
-        // honour max_output: keep only the first (cap - cnt) survivors of this chunk
-        int nk = __popcll(kept);
-        if (cnt + nk > cap) {
-            int drop = cnt + nk - cap;
-            while (drop > 0) { kept &= ~(1ull << (63 - __builtin_clzll(kept))); --drop; }
-            nk = cap - cnt;
-        }
-        if ((kept >> lane) & 1ull) keep[cnt + __popcll(kept & ((1ull << lane) - 1ull))] = order[i];
-        cnt += nk;
-        if (cnt >= cap) break;
-        for (int w = c + 1 + lane; w < nw; w += 64) {
-            unsigned long long acc = 0ull;
-            unsigned long long kk = kept;
-            while (kk) {
-                const int q = __ffsll((long long)kk) - 1;
-                kk &= kk - 1ull;
-                acc |= mask[(long long)(i0 + q) * words + w];
-            }
-            removed[w] |= acc;
-        }
-        __syncthreads();
-    }
-    if (lane == 0) num_keep[b] = cnt;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// RPN proposals, round 5: the batched NMS level by level.  rpn.py:163-172 runs ONE batched_nms over an image's candidates with the
-// pyramid level as the class id: boxes of different levels are shifted apart before the greedy pass (post_processing.py:44-45), so that
-// pass decomposes into L independent ones -- 16 x 5 problems of <= 2 048 boxes instead of 16 of ~8 900 (a 157-chunk serial scan per
-// image: nmsb_scan 0.76 ms, nmsb_mask 0.47 ms, the 16 384-key sort 0.26 ms per step at batch 16) -- and the joint keep list (score
-// descending, candidate index ascending, first post_k) is the MERGE of the per-level lists.  The boxes keep the joint form's shift
-// (level x (max coordinate + 1), in fp32): the IoUs, and with them every keep decision, are the same bits.
-// ------------------------------------------------------------------------------------------------------------
-constexpr int NMSL_CAP = 2048;                  // candidates per (image, level): pre_k <= TOPK_MAX
-constexpr int NMSL_WORDS = NMSL_CAP / 64;
-
-// grid (L, N): sorts one level's candidates (score descending, index ascending), writes the shifted boxes of that level
-__global__ __launch_bounds__(1024) void nmsl_prepare_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, RpnLevels lv,
-                                                            int C, float* __restrict__ sboxes, int* __restrict__ order,
-                                                            int* __restrict__ nvalid) {
-    __shared__ unsigned long long keys[NMSL_CAP];
-    __shared__ float red[16];
-    __shared__ int cnt_sh;
-    const int tid = threadIdx.x, l = blockIdx.x, n = blockIdx.y;
-    const long long b0 = (long long)n * C;
-    boxes += b0 * 4; scores += b0; sboxes += b0 * 4; order += b0;
-    if (tid == 0) cnt_sh = 0;
-    // the shift step of the JOINT problem: largest coordinate over ALL of the image's candidates + 1
-    float mx = -INFINITY;
-    for (int i = tid; i < C; i += 1024) {
-        if (scores[i] > -INFINITY) {
-            const Box b = ld_box(boxes + i * 4ll);
-            mx = fmaxf(mx, fmaxf(fmaxf(b.x1, b.y1), fmaxf(b.x2, b.y2)));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = red[0];
-    for (int q = 1; q < 16; ++q) mx = fmaxf(mx, red[q]);
-    const float off = (float)l * (mx + 1.f);
-    const int c0 = lv.cand_off[l], cap = lv.cand_off[l + 1] - c0;
-    int nv = 0;
-    for (int i = tid; i < NMSL_CAP; i += 1024) {
-        unsigned long long key = ~0ull;
-        if (i < cap) {
-            const float sc = scores[c0 + i];
-            key = ((unsigned long long)float_desc_key(sc) << 32) | (unsigned int)(c0 + i);
-            nv += sc > -INFINITY;
-            const Box b = ld_box(boxes + (c0 + i) * 4ll);
-            f32x4_t o = {b.x1 + off, b.y1 + off, b.x2 + off, b.y2 + off};
-            *reinterpret_cast<f32x4_t*>(sboxes + (c0 + i) * 4ll) = o;
-        }
-        keys[i] = key;
-    }
-    if (nv) atomicAdd(&cnt_sh, nv);
-    __syncthreads();
-    for (int kk = 2; kk <= NMSL_CAP; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < NMSL_CAP; i += 1024) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], b = keys[ixj];
-                    const bool up = (i & kk) == 0;
-                    if ((a > b) == up) { keys[i] = b; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < cap; i += 1024) order[c0 + i] = (int)(keys[i] & 0xffffffffu);        // candidate index inside the image
-    if (tid == 0) nvalid[n * lv.L + l] = cnt_sh;
-}
-
-// grid (32 row tiles, 32 words, N * L), one wave: as nmsb_mask_kernel on one level's sorted list
-__global__ __launch_bounds__(64) void nmsl_mask_kernel(const float* __restrict__ sboxes, const int* __restrict__ order,
-                                                       const int* __restrict__ nvalid, RpnLevels lv, int C, float thr,
-                                                       unsigned long long* __restrict__ mask) {
-    __shared__ float rows[64 * 4];
-    const int rt = blockIdx.x, w = blockIdx.y, b = blockIdx.z;
-    const int nv = nvalid[b];
-    if (w < rt || rt * 64 >= nv || w * 64 >= nv) return;
-    const int n = b / lv.L, l = b - n * lv.L;
-    sboxes += (long long)n * C * 4; order += (long long)n * C + lv.cand_off[l]; mask += (long long)b * NMSL_CAP * NMSL_WORDS;
-    const int lane = threadIdx.x;
-    const int j = w * 64 + lane;
-    Box cb{0.f, 0.f, 0.f, 0.f};
-    if (j < nv) cb = ld_box(sboxes + order[j] * 4ll);
-    const int ri = rt * 64 + lane;
-    f32x4_t rb = {0.f, 0.f, 0.f, 0.f};
-    if (ri < nv) rb = *reinterpret_cast<const f32x4_t*>(sboxes + order[ri] * 4ll);
-    *reinterpret_cast<f32x4_t*>(rows + lane * 4) = rb;
-    __syncthreads();
-    const float ca = box_area(cb);
-    const int rmax = min(64, nv - rt * 64);
-    unsigned long long mine = 0ull;
-    for (int q = 0; q < rmax; ++q) {
-        const int i = rt * 64 + q;
-        const Box a = Box{rows[q * 4], rows[q * 4 + 1], rows[q * 4 + 2], rows[q * 4 + 3]};
-        bool sup = false;
-        if (j < nv && j > i) {
-            const float inter = box_inter(a, cb);
-            const float uni = (box_area(a) + ca) - inter;
-            sup = (inter / uni) > thr;     // keep iff iou <= thr (py_cpu_nms, post_processing.py:130)
-        }
-        const unsigned long long bal = __ballot(sup);
-        if (lane == q) mine = bal;
-    }
-    if (lane < rmax) mask[(long long)(rt * 64 + lane) * NMSL_WORDS + w] = mine;
-}
-
-// grid (N * L), one wave: as nmsb_scan_kernel; a level keeps at most post_k boxes (no more of them can reach the joint list's first post_k)
-__global__ __launch_bounds__(64) void nmsl_scan_kernel(const unsigned long long* __restrict__ mask, const int* __restrict__ order,
-                                                       const int* __restrict__ nvalid, RpnLevels lv, int C, int post_k,
-                                                       int* __restrict__ keep_l, int* __restrict__ num_l) {
-    __shared__ unsigned long long removed[NMSL_WORDS];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int n = b / lv.L, l = b - n * lv.L;
-    mask += (long long)b * NMSL_CAP * NMSL_WORDS; order += (long long)n * C + lv.cand_off[l]; keep_l += (long long)b * post_k;
-    const int nv = nvalid[b];
-    const int nw = (nv + 63) >> 6;
-    if (lane < NMSL_WORDS) removed[lane] = 0ull;
-    __syncthreads();
-    int cnt = 0;
-    const int cap = post_k;
-    for (int c = 0; c < nw && cnt < cap; ++c) {
-        const int i0 = c * 64;
-        const int i = i0 + lane;
-        const unsigned long long diag = i < nv ? mask[(long long)i * NMSL_WORDS + c] : 0ull;
-        const int nin = min(64, nv - i0);
-        unsigned long long alive = ~removed[c];
-        if (nin < 64) alive &= (1ull << nin) - 1ull;
-        unsigned long long kept = 0ull;
-        const unsigned int dlo = (unsigned int)diag, dhi = (unsigned int)(diag >> 32);
-        for (int q = 0; q < nin; ++q) {
-            if ((alive >> q) & 1ull) {                                   // wave-uniform
-                kept |= 1ull << q;
-                const unsigned long long row = ((unsigned long long)(unsigned int)__shfl((int)dhi, q, 64) << 32) |
-                                               (unsigned int)__shfl((int)dlo, q, 64);
-                alive &= ~row;
-            }
-        }
-        int nk = __popcll(kept);
-        if (cnt + nk > cap) {
-            int drop = cnt + nk - cap;
-            while (drop > 0) { kept &= ~(1ull << (63 - __builtin_clzll(kept))); --drop; }
-            nk = cap - cnt;
-        }
-        if ((kept >> lane) & 1ull) keep_l[cnt + __popcll(kept & ((1ull << lane) - 1ull))] = order[i];
-        cnt += nk;
-        if (cnt >= cap) break;
-        const int w = c + 1 + lane;
-        if (w < nw) {
-            unsigned long long acc = 0ull;
-            unsigned long long kk = kept;
-            while (kk) {
-                const int q = __ffsll((long long)kk) - 1;
-                kk &= kk - 1ull;
-                acc |= mask[(long long)(i0 + q) * NMSL_WORDS + w];
-            }
-            removed[w] |= acc;
-        }
-        __syncthreads();
-    }
-    if (lane == 0) num_l[b] = cnt;
-}
-
-// grid (N): joint rank of every kept box = its rank inside its level + the kept boxes of the other levels that precede it in
-// (score descending, candidate index ascending) order -- levels are laid out in candidate-index order, so a box of a LOWER level precedes
-// on a score tie, one of a higher level does not.  Binary searches over the per-level lists (sorted by construction).
-__global__ __launch_bounds__(1024) void nmsl_merge_kernel(const float* __restrict__ scores, const int* __restrict__ keep_l,
-                                                          const int* __restrict__ num_l, RpnLevels lv, int C, int post_k,
-                                                          int* __restrict__ keep, int* __restrict__ num_keep) {
-    const int n = blockIdx.x, tid = threadIdx.x;
-    scores += (long long)n * C; keep_l += (long long)n * lv.L * post_k; num_l += n * lv.L; keep += (long long)n * post_k;
-    int tot = 0;
-    for (int l = 0; l < lv.L; ++l) tot += num_l[l];
-    for (int l = 0; l < lv.L; ++l) {
-        const int nl = num_l[l];
-        for (int r = tid; r < nl; r += 1024) {
-            const int c = keep_l[l * post_k + r];
-            const unsigned int key = float_desc_key(scores[c]);
-            int rank = r;
-            for (int o = 0; o < lv.L; ++o) {
-                if (o == l) continue;
-                const int* lst = keep_l + o * post_k;
-                int lo = 0, hi = num_l[o];               // first index whose key is > key (o < l: ties precede) or >= key (o > l)
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    const unsigned int km = float_desc_key(scores[lst[mid]]);
-                    const bool before = o < l ? km <= key : km < key;
-                    if (before) lo = mid + 1; else hi = mid;
-                }
-                rank += lo;
-            }
-            if (rank < post_k) keep[rank] = c;
-        }
-    }
-    if (tid == 0) num_keep[n] = tot < post_k ? tot : post_k;
 }
 
 __global__ __launch_bounds__(256) void rpn_gather_kernel(const float* __restrict__ boxes, const int* __restrict__ keep,
@@ -1214,55 +843,7 @@ __global__ __launch_bounds__(256) void f32_to_bf16_add_kernel(const float* __res
     }
 }
 
-inline int next_pow2_i(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct NmsbLayout { size_t sboxes, order, nvalid, mask, total; int words; };
-inline NmsbLayout nmsb_layout(int B, int C) {
-    NmsbLayout l;
-    l.words = (C + 63) / 64;
-    size_t o = 0;
-    l.sboxes = o; o += align256((size_t)B * C * 16);
-    l.order = o; o += align256((size_t)B * C * 4);
-    l.nvalid = o; o += align256((size_t)B * 4);
-    l.mask = o; o += align256((size_t)B * C * l.words * 8);
-    l.total = o;
-    return l;
-}
-
-int nmsb_run(const float* boxes, const float* scores, const int32_t* idxs, int B, int C, float thr, int max_output, int keep_ld,
-             int32_t* keep, int32_t* num_keep, unsigned char* ws, hipStream_t st) {
-    const NmsbLayout l = nmsb_layout(B, C);
-    float* sboxes = (float*)(ws + l.sboxes);
-    int* order = (int*)(ws + l.order);
-    int* nvalid = (int*)(ws + l.nvalid);
-    unsigned long long* mask = (unsigned long long*)(ws + l.mask);
-    const int npow2 = next_pow2_i(C);
-    BD_ONCE_PER_DEVICE(
-        (void)hipFuncSetAttribute((const void*)nmsb_prepare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NMSB_MAX * 8));
-    hipLaunchKernelGGL(nmsb_prepare_kernel, dim3(B), dim3(1024), (size_t)npow2 * 8, st, boxes, scores, idxs, C, npow2, sboxes,
-                       order, nvalid);
-    const int tiles = (C + 63) / 64;
-    hipLaunchKernelGGL(nmsb_mask_kernel, dim3(tiles, l.words, B), dim3(64), 0, st, sboxes, order, nvalid, C, l.words, thr, mask);
-    hipLaunchKernelGGL(nmsb_scan_kernel, dim3(B), dim3(64), 0, st, mask, order, nvalid, C, l.words, max_output, keep_ld, keep,
-                       num_keep);
-    return BD_OK;
-}
-
-struct NmslLayout { size_t sboxes, order, nvalid, mask, keep_l, num_l, total; };
-inline NmslLayout nmsl_layout(int N, int L, int C, int post_k) {
-    NmslLayout l;
-    size_t o = 0;
-    l.sboxes = o; o += align256((size_t)N * C * 16);
-    l.order = o; o += align256((size_t)N * C * 4);
-    l.nvalid = o; o += align256((size_t)N * L * 4);
-    l.mask = o; o += align256((size_t)N * L * NMSL_CAP * NMSL_WORDS * 8);
-    l.keep_l = o; o += align256((size_t)N * L * post_k * 4);
-    l.num_l = o; o += align256((size_t)N * L * 4);
-    l.total = o;
-    return l;
-}
-
 
 struct RpnWs { size_t tk_idx, tk_score, tk_cnt, boxes, scores, levels, keep, nms, total; };
 inline RpnWs rpn_ws_layout(int N, int C, int L, int k, int post_k) {
@@ -1275,7 +856,7 @@ inline RpnWs rpn_ws_layout(int N, int C, int L, int k, int post_k) {
     w.scores = o; o += align256((size_t)N * C * 4);
     w.levels = o; o += align256((size_t)N * C * 4);
     w.keep = o; o += align256((size_t)N * post_k * 4);
-    const size_t joint = nmsb_layout(N, C).total, per_level = nmsl_layout(N, L, C, post_k).total;
+    const size_t joint = bd_nms_joint_ws_bytes(N, C), per_level = bd_nms_levels_ws_bytes(N, L, C, post_k);
     w.nms = o; o += joint > per_level ? joint : per_level;
     w.total = o;
     return w;
@@ -1313,26 +894,6 @@ extern "C" int bd_segment_topk(const void* scores, int is_bf16, int B, int64_t b
     return BD_OK;
 }
 
-extern "C" size_t bd_nms_batched_workspace_bytes(int B, int C) {
-    if (B <= 0 || C <= 0) return 256;
-    return nmsb_layout(B, C).total;
-}
-
-extern "C" int bd_nms_batched(const float* boxes, const float* scores, const int32_t* idxs, int B, int C, float iou_thresh,
-                              int max_output, int keep_ld, int32_t* keep, int32_t* num_keep, void* ws, size_t ws_bytes,
-                              bd_stream_t stream) {
-    BD_REQUIRE(boxes && scores && keep && num_keep && ws, "nms_batched: null pointer");
-    BD_REQUIRE(B > 0 && C > 0 && C <= NMSB_MAX, "nms_batched: C=%d out of range (1..%d)", C, NMSB_MAX);
-    BD_REQUIRE(keep_ld >= (max_output > 0 ? (max_output < C ? max_output : C) : C), "nms_batched: keep_ld too small");
-    if (ws_bytes < bd_nms_batched_workspace_bytes(B, C)) {
-        bd_set_error("nms_batched: workspace %zu < %zu bytes", ws_bytes, bd_nms_batched_workspace_bytes(B, C));
-        return BD_EWORKSPACE;
-    }
-    nmsb_run(boxes, scores, idxs, B, C, iou_thresh, max_output, keep_ld, keep, num_keep, (unsigned char*)ws, (hipStream_t)stream);
-    BD_CHECK_LAUNCH("bd_nms_batched");
-    return BD_OK;
-}
-
 extern "C" size_t bd_rpn_proposals_workspace_bytes(int N, int L, const int32_t* lvl_pixels_host, int A, int pre_k, int post_k) {
     if (N <= 0 || L <= 0 || L > BD_MAX_SEGS || !lvl_pixels_host) return 0;
     return rpn_ws_layout(N, rpn_capacity(L, lvl_pixels_host, A, pre_k), L, pre_k, post_k).total;
@@ -1347,7 +908,7 @@ static int rpn_proposals_impl(const void* raw, int ldc, int A, int cls_off, int 
     BD_REQUIRE(N > 0 && L > 0 && L <= BD_MAX_SEGS && A > 0 && pre_k > 0 && pre_k <= TOPK_MAX && post_k > 0, "rpn_proposals: bad sizes");
     BD_REQUIRE(cls_off >= 0 && box_off >= 0 && cls_off + A <= ldc && box_off + 4 * A <= ldc, "rpn_proposals: bad channel layout");
     const int C = rpn_capacity(L, lvl_pixels_host, A, pre_k);
-    BD_REQUIRE(C <= NMSB_MAX, "rpn_proposals: %d candidates per image exceed %d", C, NMSB_MAX);
+    BD_REQUIRE(C <= NMS_MAX, "rpn_proposals: %d candidates per image exceed %d", C, NMS_MAX);
     const RpnWs w = rpn_ws_layout(N, C, L, pre_k, post_k);
     if (ws_bytes < w.total) {
         bd_set_error("rpn_proposals: workspace %zu < %zu bytes", ws_bytes, w.total);
@@ -1381,22 +942,10 @@ static int rpn_proposals_impl(const void* raw, int ldc, int A, int cls_off, int 
     hipLaunchKernelGGL(rpn_decode_kernel, dim3(cdiv(C, 256), N), dim3(256), 0, st, (const bf16_raw*)raw, (long long)pix_per_img, ldc,
                        A, box_off, anchors, lv, pre_k, tk_idx, tk_score, tk_cnt, im_info, info_ld, make_coder(mean4_host, std4_host),
                        C, boxes, scores, levels);
-    if (nms_per_level) {
-        const NmslLayout nl = nmsl_layout(N, L, C, post_k);
-        unsigned char* nb = wb + w.nms;
-        float* sboxes = (float*)(nb + nl.sboxes);
-        int* order = (int*)(nb + nl.order);
-        int* nvalid = (int*)(nb + nl.nvalid);
-        unsigned long long* mask = (unsigned long long*)(nb + nl.mask);
-        int* keep_l = (int*)(nb + nl.keep_l);
-        int* num_l = (int*)(nb + nl.num_l);
-        hipLaunchKernelGGL(nmsl_prepare_kernel, dim3(L, N), dim3(1024), 0, st, boxes, scores, lv, C, sboxes, order, nvalid);
-        hipLaunchKernelGGL(nmsl_mask_kernel, dim3(NMSL_WORDS, NMSL_WORDS, N * L), dim3(64), 0, st, sboxes, order, nvalid, lv, C, nms_thresh, mask);
-        hipLaunchKernelGGL(nmsl_scan_kernel, dim3(N * L), dim3(64), 0, st, mask, order, nvalid, lv, C, post_k, keep_l, num_l);
-        hipLaunchKernelGGL(nmsl_merge_kernel, dim3(N), dim3(1024), 0, st, scores, keep_l, num_l, lv, C, post_k, keep, num_rois);
-    } else {
-        nmsb_run(boxes, scores, levels, N, C, nms_thresh, post_k, post_k, keep, num_rois, wb + w.nms, st);
-    }
+    if (nms_per_level)
+        bd_nms_levels_run(boxes, scores, lv, N, C, nms_thresh, post_k, keep, num_rois, wb + w.nms, st);
+    else
+        bd_nms_joint_run(boxes, scores, levels, N, C, nms_thresh, post_k, post_k, keep, num_rois, wb + w.nms, st);
     hipLaunchKernelGGL(rpn_gather_kernel, dim3(cdiv(post_k, 256), N), dim3(256), 0, st, boxes, keep, num_rois, C, post_k, rois);
     BD_CHECK_LAUNCH("bd_rpn_proposals");
     return BD_OK;

@@ -1,5 +1,6 @@
-// Block-wide selection helpers shared by the selection kernels (rcnn_ops.hip, freeanchor.hip): radix select of the k largest
-// 32-bit keys of a segment by one workgroup, and the ordered rank of a flag within a 1024-thread workgroup.
+// Block-wide selection helpers shared by the selection kernels (rcnn_ops.hip, nms.hip, det_select.hip, freeanchor.hip): radix select of
+// the k largest 32-bit keys of a segment by one workgroup, the ordered rank of a flag within a 1024-thread workgroup, and the LDS bitonic
+// sort of 64-bit keys by a 1024-thread workgroup.
 #pragma once
 #include "box_dev.h"
 
@@ -93,6 +94,26 @@ __device__ __forceinline__ int block_rank_1024(bool flag, int* wcnt, int& total)
     }
     total = tot;
     return before + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// Sorts keys[0 .. n) in LDS, n a power of two, by the 1024 threads of the workgroup: DESC largest first, otherwise smallest first.
+// The caller puts a barrier between its last write of `keys` and the call; the sort ends after its last barrier.
+template <bool DESC>
+__device__ __forceinline__ void bitonic_sort_1024(unsigned long long* keys, int n) {
+    const int tid = threadIdx.x;
+    for (int kk = 2; kk <= n; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n; i += 1024) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const unsigned long long a = keys[i], b = keys[ixj];
+                    const bool up = (i & kk) == 0;
+                    if ((DESC ? a < b : a > b) == up) { keys[i] = b; keys[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
 }
 
 }  // namespace

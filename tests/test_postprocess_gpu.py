@@ -1,5 +1,5 @@
 """The inference post-processing kernels one at a time (csrc/postprocess.hip det_scores / det_candidates / det_finalize /
-rcnn_predict, csrc/rcnn_ops.hip segment_topk / nms_batched) in the call forms and at the sizes of 800x1344 inference, against
+rcnn_predict, csrc/rcnn_ops.hip segment_topk, csrc/nms.hip nms_batched) in the call forms and at the sizes of 800x1344 inference, against
 float64 torch or the numpy oracle: oracle/rcnn_ops.py topk_desc (:44-53) and detect_postprocess (:294-318), oracle/box_ops.py
 box_decode (:203-215), point_decode (:225-230), batched_nms (:598-609), box_scale / box_clip (:142-162).
 

@@ -1,4 +1,4 @@
-"""GPU parity of the Faster R-CNN operators (csrc/rcnn_ops.hip, RPN / RCNN losses) against oracle/rcnn_ops.py.
+"""GPU parity of the Faster R-CNN operators (csrc/rcnn_ops.hip, csrc/nms.hip, RPN / RCNN losses) against oracle/rcnn_ops.py.
 Index-valued outputs (top-k order, NMS survivors, sampled labels / RoIs) are compared bit-exactly; RoIAlign within one
 bf16 ulp; the losses against a float64 restatement with the tolerance written at each assert."""
 import numpy as np
@@ -110,6 +110,68 @@ def test_nms_batched():
             assert np.array_equal(gk[b, : gn[b]], ref)
 
 
+def _nms_batched_one(ops, boxes, scores, idxs, thr, max_output):
+    """ops.nms_batched on one problem: its keep list"""
+    n = len(scores)
+    keep = torch.full((1, max_output or n), -1, dtype=torch.int32, device="cuda")
+    num = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    ws = torch.empty((ops.nms_batched_workspace_bytes(1, n),), dtype=torch.uint8, device="cuda")
+    ops.nms_batched(_dev(boxes[None]), _dev(scores[None]), _dev(idxs[None]), thr, max_output or 0, keep, num, ws)
+    return keep.cpu().numpy()[0, : int(num.item())]
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 129, 700])
+def test_nms_public_entries_agree(n):
+    """bd_batched_nms (one problem, every item present) and bd_nms_batched with B = 1 run the same kernels: on finite scores both return
+    the oracle's keep list.  The sizes are the chunk boundaries of the 64-wide tiles and the one-word case; scores rounded to 1/512 tie."""
+    ops = _ops()
+    rng = np.random.default_rng(100 + n)
+    boxes = _rand_boxes(rng, n, 1344, 800, 40, 200)
+    scores = (np.round(rng.uniform(0, 1, n) * 512) / 512).astype(np.float32)
+    idxs = rng.integers(0, 5, n).astype(np.int32)
+    h = n // 2                                # clustered, a cluster in one class: about half of the boxes is suppressed
+    boxes[h:2 * h] = boxes[:h] + rng.normal(0, 2, (h, 4)).astype(np.float32)
+    idxs[h:2 * h] = idxs[:h]
+    for max_output in (None, 1, 17):
+        ref = ob.batched_nms(boxes, scores, idxs, 0.7, max_output)
+        if max_output is None and n == 700:
+            assert 0.4 * n < len(ref) < 0.7 * n          # (the clusters do suppress)
+        one = ops.batched_nms(_dev(boxes), _dev(scores), _dev(idxs), 0.7, max_output).cpu().numpy()
+        many = _nms_batched_one(ops, boxes, scores, idxs, 0.7, max_output)
+        assert np.array_equal(one, many)
+        assert np.array_equal(one, ref)
+        assert np.array_equal(many, ref)
+
+
+def test_nms_absent_against_present():
+    """A score of -inf: bd_batched_nms treats the item as present (it sorts last, takes part in the shift step's maximum and is kept unless
+    suppressed, as the oracle's and the reference's batched_nms), bd_nms_batched as absent (out of the maximum, never kept).  Items 10..19
+    lie far from every other box and from each other; item 13 has the largest coordinate of the set."""
+    ops = _ops()
+    rng = np.random.default_rng(7)
+    n = 130
+    boxes = _rand_boxes(rng, n, 1344, 800, 40, 200)
+    scores = (np.round(rng.uniform(0, 1, n) * 512) / 512).astype(np.float32)
+    idxs = rng.integers(0, 5, n).astype(np.int32)
+    boxes[65:125] = boxes[:60] + rng.normal(0, 2, (60, 4)).astype(np.float32)
+    idxs[65:125] = idxs[:60]
+    for q, i in enumerate(range(10, 20)):
+        x = 3000.0 + 150.0 * q
+        boxes[i] = [x, x, x + 100.0, x + (2000.0 if i == 13 else 100.0)]
+    scores[10:20] = -np.inf
+    assert boxes.max() == boxes[13, 3] and boxes[13, 3] > boxes[np.isfinite(scores)].max()
+    for max_output in (None, 17):
+        ref = ob.batched_nms(boxes, scores, idxs, 0.7, max_output)
+        got = ops.batched_nms(_dev(boxes), _dev(scores), _dev(idxs), 0.7, max_output).cpu().numpy()
+        assert np.array_equal(got, ref)
+        if max_output is None:
+            assert np.array_equal(ref[-10:], np.arange(10, 20))          # present: kept, at the end, in index order
+        valid = np.nonzero(np.isfinite(scores))[0]
+        ref_v = valid[ob.batched_nms(boxes[valid], scores[valid], idxs[valid], 0.7, max_output)]
+        got_v = _nms_batched_one(ops, boxes, scores, idxs, 0.7, max_output)
+        assert np.array_equal(got_v, ref_v)
+
+
 def _pyramid_inputs(rng, N, sizes, A, ldc):
     ppi = sum(h * w for h, w in sizes)
     raw = np.zeros((N, ppi, ldc), np.float32)
@@ -126,12 +188,13 @@ def _anchors(sizes):
 
 
 @pytest.mark.parametrize("pre_k,post_k,per_level,ties", [(500, 300, 1, 0), (500, 300, 0, 0), (2000, 1000, 1, 0), (2000, 120, 1, 0),
-                                                         (2000, 1000, 1, 1), (700, 64, 1, 1)])
+                                                         (2000, 1000, 1, 1), (700, 64, 1, 1), (64, 40, 1, 0), (65, 40, 1, 1)])
 def test_rpn_proposals(pre_k, post_k, per_level, ties):
     """per_level = 1 (round 5, default): the batched NMS level by level + a merge into the joint order; 0: one problem per image (rounds
     1-4).  Both against the oracle's joint batched_nms; (2000, 1000): the configured sizes (every level of this pyramid below pre_k keeps
     all its anchors); (2000, 120): the per-level cap and the merge cut the lists; ties = 1: five images whose scores take 17 distinct
-    values only -- the merge's tie rule (lower level first, then candidate index) decides most of the joint order."""
+    values only -- the merge's tie rule (lower level first, then candidate index) decides most of the joint order.  pre_k = 64 / 65: levels
+    of exactly one 64-box word and of one word plus one box, beside the 45-anchor coarsest level below one word."""
     ops = _ops()
     rng = np.random.default_rng(2)
     N, A, ldc = (5 if ties else 2), 3, 16
