@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 102              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries)
+ABI_VERSION = 103              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -39,6 +39,12 @@ class ConvDesc(C.Structure):
 class PackDesc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("row_scale", C.c_void_p), ("w_fwd", C.c_void_p), ("w_dgrad", C.c_void_p),
                 ("Cout", C.c_int32), ("RS", C.c_int32), ("Cin", C.c_int32), ("block_start", C.c_int32)]
+
+
+class ImageDesc(C.Structure):
+    """bd_image_desc: one image of a packed raw batch (bd_resize_pad_normalize)."""
+    _fields_ = [("offset", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("dst_h", C.c_int32), ("dst_w", C.c_int32),
+                ("flip", C.c_int32), ("reserved_", C.c_int32 * 1)]
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -90,6 +96,7 @@ SIGNATURES = {
     "bd_h2d_submit": (_I, [_P, _P, _I, _L, _P, _L, _P]),
     "bd_h2d_destroy": (_I, [_P]),
     "bd_pad_normalize_nchw": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "bd_resize_pad_normalize": (_I, [_P, _L, C.POINTER(ImageDesc), _I, _I, _I, _P, _P, _P, _P]),
     "bd_maxpool3x3s2_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "bd_upsample2x_add_fwd": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _P]),
     "bd_upsample2x_add_bwd": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _P]),

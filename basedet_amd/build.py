@@ -11,9 +11,10 @@ LIB = os.path.join(OUT_DIR, os.environ.get("BD_LIB_NAME", "libbasedet_hip.so")) 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-# per-file extra flags: the box ops must not contract a*b+c into FMA (bit-exact parity with the numpy oracle)
+# per-file extra flags: the box ops and the image resize must not contract a*b+c into FMA (bit-exact parity with numpy)
 SOURCES = {
     "image_ops.hip": [],
+    "image_resize.hip": ["-ffp-contract=off"],
     "ema.hip": [],
     "h2d.hip": [],
     "conv_igemm.hip": [],

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..data.raw import RawImageBatch
 from ..ops import Geom
 from . import params as P
 from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena
@@ -80,6 +81,7 @@ class FPNDetector:
             params = self.init_params(cfg, seed)
         self._pack_table = None            # bd_weight_pack_multi's table: built by the first repack_trainable, dropped by _bind_params
         self._stager = self._h2d_buf = self._h2d_dst = None        # host-to-device staging, created by the first host batch
+        self._raw_buf = None                                       # device copy of a RawImageBatch's packed bytes (grow-only)
         self._build_layers(params)
         self._plans = {}
         self._cur = None
@@ -517,14 +519,22 @@ class FPNDetector:
     def pre_process(self, inputs):
         """RetinaNet.pre_process (retinanet.py:90-107): H2D copy + pad to x32 + normalise (fused kernel)."""
         image = inputs["data"] if isinstance(inputs, dict) else inputs
-        if not (torch.is_tensor(image) and image.is_cuda):
-            image = self._host_to_device(image)
-        image = image.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
-        N, _, H, W = image.shape
+        if isinstance(image, RawImageBatch):
+            # raw uint8 images of their own sizes (data/raw.py): resize, flip, pad and normalise happen in the one launch that fills x_halo
+            N, H, W = image.N, image.Hmax, image.Wmax
+            packed = self._raw_to_device(image)
+        else:
+            if not (torch.is_tensor(image) and image.is_cuda):
+                image = self._host_to_device(image)
+            image = image.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
+            N, _, H, W = image.shape
         Hp, Wp = _round_up(H, 32), _round_up(W, 32)
         pl = self._plan(N, Hp, Wp)
         self._bind_plan(pl)
-        ops.pad_normalize(image, Hp, Wp, self.img_mean, self.img_std, pl.x_halo)
+        if isinstance(image, RawImageBatch):
+            ops.resize_pad_normalize(packed, image.descs, Hp, Wp, self.img_mean, self.img_std, pl.x_halo)
+        else:
+            ops.pad_normalize(image, Hp, Wp, self.img_mean, self.img_std, pl.x_halo)
         out = {"plan": pl}
         if isinstance(inputs, dict) and "gt_boxes" in inputs:
             gt = torch.as_tensor(np.asarray(inputs["gt_boxes"]), dtype=torch.float32) if not torch.is_tensor(inputs["gt_boxes"]) else inputs["gt_boxes"]
@@ -558,6 +568,20 @@ class FPNDetector:
             buf = self._h2d_buf = torch.empty((arr.size,), dtype=torch.float32, device=self.device)
         dst = self._h2d_dst = buf[: arr.size].view(arr.shape)
         return st.submit(arr, dst, int(self.cfg.MODEL.get("H2D_CHUNK_ELEMS", 0)))
+
+    def _raw_to_device(self, batch):
+        """The packed bytes of a RawImageBatch -> one grow-only uint8 device buffer, in one asynchronous copy on the current stream (its
+        reader, bd_resize_pad_normalize, runs there too); the batch's collator learns when its buffer is free again."""
+        src = batch.packed
+        buf = self._raw_buf
+        if buf is None or buf.numel() < src.numel():
+            buf = self._raw_buf = torch.empty((src.numel(),), dtype=torch.uint8, device=self.device)
+        dst = buf[: src.numel()]
+        dst.copy_(src, non_blocking=True)
+        drained = torch.cuda.Event()
+        drained.record()
+        batch.copied(drained)
+        return dst
 
     def _block_forward(self, blk, b, x, x8=None):
         """x8: the e4m3 twin of the block input when the previous block's conv3 wrote one (fp8 mode)."""

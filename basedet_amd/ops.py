@@ -363,6 +363,17 @@ def pad_normalize_nchw(x, Hp, Wp, mean, std, out):
     return out
 
 
+def resize_pad_normalize(packed, descs, Hp, Wp, mean, std, out):
+    """bd_resize_pad_normalize: packed = uint8 device tensor holding the raw HWC images, descs = their _lib.ImageDesc records (host);
+    out = bf16 (N, Hp + 6, Wp + 8, 4), written whole."""
+    N = len(descs)
+    assert packed.dtype == torch.uint8 and out.dtype == torch.bfloat16 and out.numel() == N * (Hp + 6) * (Wp + 8) * 4
+    arr = descs if isinstance(descs, C.Array) else (_lib.ImageDesc * N)(*descs)
+    check(L().bd_resize_pad_normalize(ptr(packed), packed.numel(), arr, N, int(Hp), int(Wp), f32arr(mean), f32arr(std), ptr(out),
+                                      stream_ptr()), "bd_resize_pad_normalize")
+    return out
+
+
 def stem_pool_fwd(N, H, W, x_halo, w_stem, bias, y_pool):
     """stem_conv7x7_fwd + maxpool3x3s2_fwd in one launch (bit-identical; the half-resolution tensor is never written)."""
     check(L().bd_stem_pool_fwd(N, H, W, ptr(x_halo), ptr(w_stem), ptr(bias), ptr(y_pool), stream_ptr()), "bd_stem_pool_fwd")

@@ -304,6 +304,23 @@ int bd_h2d_destroy(bd_h2d_t h);
 int bd_pad_normalize_nchw(const float* in, int N, int H, int W, int Hp, int Wp, const float* mean3,
                           const float* std3, float* out, bd_stream_t stream);
 
+/* Raw-image input (bd_version() >= 103): N decoded uint8 images, each of its own size, packed into one device buffer -> the
+ * layout bd_pad_normalize writes (bf16 [N][Hp+6][Wp+8][4], zero halo, channel 3 = 0, every element written), in one pass: bilinear
+ * resize to (dst_h, dst_w) with the arithmetic of data/transforms.py's resize_bilinear (float64 source coordinates, fp32 blends without
+ * multiply-add contraction, rint to a byte), horizontal flip AFTER the resize when `flip` is set, zero-pad to (Hp, Wp), then
+ * (x - mean) / std -- bit for bit what the numpy transform, the pad collator, bd_h2d_submit and bd_pad_normalize produce together.
+ * Image i is C-contiguous [src_h][src_w][3] at byte `offset` of packed_dev, channels in the order of mean3 / std3.
+ * descs_host is a HOST array, read before the call returns (no lifetime beyond it): it travels to the kernel by value, 32 images per
+ * launch.  BD_EINVAL, with nothing launched, unless every dimension is > 0, offset + src_h * src_w * 3 <= packed_bytes,
+ * dst_h <= Hp, dst_w <= Wp and Hp, Wp are multiples of 32. */
+typedef struct bd_image_desc {
+    int64_t offset;
+    int32_t src_h, src_w, dst_h, dst_w, flip;
+    int32_t reserved_[1];                       /* 32 bytes */
+} bd_image_desc;
+int bd_resize_pad_normalize(const uint8_t* packed_dev, int64_t packed_bytes, const bd_image_desc* descs_host, int N, int Hp, int Wp,
+                            const float* mean3, const float* std3, void* x_halo, bd_stream_t stream);
+
 /* M.MaxPool2d(3, 2, 1) (models/cls/resnet.py:146) on NHWC bf16. */
 int bd_maxpool3x3s2_fwd(const void* x, int N, int H, int W, int C, void* y, bd_stream_t stream);
 
