@@ -9,12 +9,11 @@ slots (label -1 = empty slot, zero loss / zero gradient); nothing is synchronise
 Randomness: the reference subsamples anchors and RoIs with megengine.random.uniform keys (layers/common/sampling.py:26).
 Here the keys come from a seeded device generator, or from ``batch["sample_keys"]`` (tests feed the same keys to the oracle).
 """
-import math
-
 import numpy as np
 import torch
 
 from .. import ops
+from ..streams import fork, join
 from ..utils.registry import registers
 from . import params as P
 from .engine import FCLayer, FusedPredConv
@@ -57,21 +56,7 @@ class FasterRCNN(FPNDetector):
                                  cout_pad=self.rcnn_ld)
         for c in (self.fc1, self.fc2, self.rcnn_pred):
             self.convs[c.name] = c
-        scales = np.asarray(m.ANCHOR.SCALES, np.float32).tolist()
-        ratios = np.asarray(m.ANCHOR.RATIOS, np.float32).tolist()
-        if len(ratios) == 1:
-            ratios = ratios * len(self.strides)
-        if len(scales) == 1:
-            scales = scales * len(self.strides)
-        self.base_anchors = []
-        for sc_, ra_ in zip(scales, ratios):     # layers/common/anchor_generator.py:95-109
-            base = []
-            for s_ in sc_:
-                area = float(s_) ** 2.0
-                for r_ in ra_:
-                    w = math.sqrt(area / float(r_)); h = float(r_) * w
-                    base.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
-            self.base_anchors.append(torch.tensor(base, dtype=torch.float32, device=dev))
+        self._build_base_anchors()
         self.pre_k = {True: m.RPN.TRAIN_PREV_NMS_TOPK, False: m.RPN.TEST_PREV_NMS_TOPK}
         self.post_k = {True: m.RPN.TRAIN_POST_NMS_TOPK, False: m.RPN.TEST_POST_NMS_TOPK}
         # RoIAlign backward: the tiled fixed-order sum (bd_roi_align_bwd_bf16: per-tile RoI lists in slot order, sums in registers, written
@@ -93,7 +78,6 @@ class FasterRCNN(FPNDetector):
         return max(need, *(c.wgrad_ws_bytes(pl.g_fc, pl.g_fc) for c in (self.fc1, self.fc2, self.rcnn_pred)))
 
     def _plan_head(self, pl):
-        dev = self.device
         m = self.cfg.MODEL
         N = pl.N
         A = self.num_anchors
@@ -105,14 +89,8 @@ class FasterRCNN(FPNDetector):
         pl.rpn_raw = C.empty((pyr.pixels, self.rpn_ld), bf)
         pl.d_rpn_raw = C.zeros((pyr.pixels, self.rpn_ld), bf)        # padding channel stays zero (re-cleared whenever the plan is bound)
         pl.g_rpn_t = C.empty((pyr.pixels, rc), bf)
-        tot = pyr.pix_per_img * A
-        pl.A_total = tot
-        pl.anchors = torch.empty((tot, 4), dtype=f32, device=dev)         # (a per-shape constant, not in the arena)
-        o = 0
-        for (h, w), s, base in zip(pl.sizes, self.strides, self.base_anchors):
-            n = h * w * A
-            ops.anchors_generate(h, w, s, m.ANCHOR.OFFSET, base, pl.anchors[o:o + n])
-            o += n
+        self._plan_anchors(pl)
+        tot = pl.A_total
         pl.rpn_labels = C.empty((N, tot), i32)
         pl.rpn_match = C.empty((N, tot), i32)
         pl.rpn_offsets = C.empty((N, tot, 4), f32)
@@ -219,37 +197,32 @@ class FasterRCNN(FPNDetector):
         # Round 5: the RPN targets (0.7 ms of one-workgroup-per-image kernels at batch 16: gt_rowmax, assignment, the radix select over
         # 268 569 keys per image) and that clear run on the weight-gradient stream, which is idle during the forward pass, UNDER the
         # backbone -- as RetinaNet's assignment does (rounds 1-4 ran them between the forward and the RPN losses, on the main chain).
-        early = self.wgrads.side() if m.get("RPN_TARGETS_EARLY", True) else None
+        early = self.streams.wgrad() if m.get("RPN_TARGETS_EARLY", True) else None
         assign_ws = self._scratch("rpn_assign", N * Gmax * 4).view(torch.float32)     # (N x Gmax floats: grow-only per model)
         if early is not None:
-            early.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(early):
+            with fork(early):
                 rpn_targets()
         self.network_forward(pl)
         # ---- RPN: proposals (detached), targets, losses.  The proposal chain (decode, per-level top-k, NMS level by level + merge: small
-        # grids) runs on a side stream under the RPN losses and the RPN head's backward on the main one.
+        # grids) runs on the auxiliary stream under the RPN losses and the RPN head's backward on the main one.
         # (Round 5, measured and REMOVED: the other way round -- RPN losses + the RPN head's backward on the side stream until the RoIAlign
         # backward's sum into dL/dP, under the whole proposal / box-head chain: 523-524 img/s against 545-547 on one box,
         # profiles/r05_frcnn_ab.txt -- the persistent one-workgroup-per-CU convolution kernels keep the box chain's many small grids
         # waiting for a CU, and the box chain is the critical path; that schedule also failed the bench-batch parity test once.)
-        side = self.wgrads.top()
+        side = self.streams.aux()
 
         def sample():
             ops.rcnn_sample_targets(pl.rois, pl.num_rois, gt, num_gt, keys["rcnn_fg"], keys["rcnn_bg"], S, int(S * m.RCNN.FG_RATIO), m.RCNN.FG_THRESHOLD,
                                     m.RCNN.BG_THRESHOLD_HIGH, m.RCNN.BG_THRESHOLD_LOW, m.RCNN_BOX_REG.MEAN, m.RCNN_BOX_REG.STD,
                                     pl.s_rois, pl.s_labels, pl.s_targets, pl.s_count, pl.s_total)
 
-        sample_on_side = bool(m.get("RCNN_SAMPLE_ON_SIDE", True))
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._proposals(pl, info)
-                if sample_on_side:        # the RoI sampling (one workgroup per image, 0.23 ms) right behind the proposals, under the RPN head's backward
-                    sample()
-        else:
+        sample_on_side = side is not None and bool(m.get("RCNN_SAMPLE_ON_SIDE", True))
+        with fork(side):
             self._proposals(pl, info)
+            if sample_on_side:            # the RoI sampling (one workgroup per image, 0.23 ms) right behind the proposals, under the RPN head's backward
+                sample()
         if early is not None:
-            torch.cuda.current_stream().wait_stream(early)
+            join(early)
         else:
             rpn_targets()
         pl.loss_buf.zero_()
@@ -263,10 +236,9 @@ class FasterRCNN(FPNDetector):
             self._flush_wgrads()          # (partial sums left by a get_losses() that was never followed by backward(): reduce them now, free the arena)
             self._rpn_head_backward(pl, pl.wgrad_ws, pl.colsum_ws, first=True)
             pl.rpn_bwd_done = True
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
+        join(side)
         # ---- RCNN: sampling, RoIAlign, box head, losses
-        if side is None or not sample_on_side:
+        if not sample_on_side:
             sample()
         self._box_head(pl)
         ops.rcnn_loss_fwd_bwd(pl.rcnn_raw, self.rcnn_ld, self.num_classes, self.num_classes + 1, pl.s_labels, pl.s_targets, pl.R,

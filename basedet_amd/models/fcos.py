@@ -6,10 +6,10 @@ Data-parallel detail (fcos.py:143-144): ``num_fg`` and ``sum_ctr`` are all-reduc
 are normalised -- one 2-float RCCL all-reduce in the forward pass.
 """
 import torch
-from contextlib import nullcontext as _nullcontext
 
 from .. import comm as _comm
 from .. import ops
+from ..streams import fork, join
 from ..utils.registry import registers
 from . import params as P
 from .engine import FusedPredConv
@@ -136,14 +136,11 @@ class FCOS(FPNDetector):
         # FCOS / ATSS targets depend on the points and the gt boxes only (fcos.py:222-293, atss.py:17-86): they can be assigned on a side
         # stream under the forward pass (as RetinaNet's).  Measured, same box: ATSS (two launches per (gt, image)) +0.5 %, FCOS (one cheap
         # launch: the two stream joins cost more than it) -0.3 % -- on for ATSS, off for FCOS.
-        side = self.wgrads.top() if m.get("ASSIGN_ON_SIDE_STREAM", self.ASSIGN_ON_SIDE_STREAM) else None
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side) if side is not None else _nullcontext():
+        side = self.streams.aux() if m.get("ASSIGN_ON_SIDE_STREAM", self.ASSIGN_ON_SIDE_STREAM) else None
+        with fork(side):
             self._assign(pl, gt, num_gt)
         self.network_forward(pl)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
+        join(side)
         c = _comm.get_comm()
         if c is not None:                                              # a one-rank communicator (BD_FORCE_ALLREDUCE) goes through RCCL too: identity
             self._allreduce_stats(c, pl.stats)                         # all_reduce(mode="mean") of num_fg and sum_ctr (fcos.py:143-144)

@@ -11,7 +11,6 @@ by T > 0).  When T has several consumers, all but the last dgrad accumulate unma
 mask in its epilogue -- so ReLU backward, residual fan-in and FrozenBN never cost a separate pass over HBM.
 """
 import math
-from contextlib import nullcontext as _nullcontext
 
 import numpy as np
 import torch
@@ -19,6 +18,7 @@ import torch
 from .. import ops
 from ..data.raw import RawImageBatch
 from ..ops import Geom
+from ..streams import SideStreams, fork, join
 from . import params as P
 from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena
 from .fp8_scaling import Fp8GradScaler, initial_grad_scale
@@ -85,15 +85,16 @@ class FPNDetector:
         self._build_layers(params)
         self._plans = {}
         self._cur = None
-        self.wgrads = WgradScheduler(self.device, m.get("WGRAD_QUEUE", "layer"))
-        self.plan_arena = PlanArena(self.device, self.wgrads.join_side)
+        self.streams = SideStreams(self.device)
+        self.wgrads = WgradScheduler(self.device, m.get("WGRAD_QUEUE", "layer"), self.streams)
+        self.plan_arena = PlanArena(self.device, self.streams.join_all)
         self.extra_meter = {}
         self.use_mask_bits = True          # bit-packed ReLU gates for the wide 1x1 data gradients (False: bf16 activations as masks)
 
-    # bench.py and the tests assign these between steps; the scheduler reads them at every call
-    async_wgrad = property(lambda self: self.wgrads.async_wgrad, lambda self, v: setattr(self.wgrads, "async_wgrad", v))
+    # bench.py and the tests assign these between steps; the streams and the scheduler read them at every call
+    async_wgrad = property(lambda self: self.streams.enabled, lambda self, v: setattr(self.streams, "enabled", v))
     wgrad_queue_mode = property(lambda self: self.wgrads.queue_mode, lambda self, v: setattr(self.wgrads, "queue_mode", v))
-    _tstream = property(lambda self: self.wgrads.tstream)
+    _tstream = property(lambda self: self.streams.aux_stream)
     fp8_scale_log = property(lambda self: self.fp8_scaler.scale_log)
     fp8_group_scales = property(lambda self: self.fp8_scaler.group_scales)
     fp8_last_fill = property(lambda self: self.fp8_scaler.last_fill)
@@ -171,6 +172,37 @@ class FPNDetector:
             self._enable_fp8_layers()
         self.fp8_scaler = Fp8GradScaler(m, dev, self.convs)
         self._bind_params(params)
+
+    def _build_base_anchors(self):
+        """The anchor heads' base anchors, one (A, 4) tensor per level: python float64 -> float32 (layers/common/anchor_generator.py:95-109)."""
+        m = self.cfg.MODEL
+        scales = np.asarray(m.ANCHOR.SCALES, np.float32).tolist()
+        ratios = np.asarray(m.ANCHOR.RATIOS, np.float32).tolist()
+        if len(ratios) == 1:
+            ratios = ratios * len(self.strides)
+        if len(scales) == 1:
+            scales = scales * len(self.strides)
+        self.base_anchors = []
+        for sc_, ra_ in zip(scales, ratios):
+            base = []
+            for s_ in sc_:
+                area = float(s_) ** 2.0
+                for r_ in ra_:
+                    w = math.sqrt(area / float(r_)); h = float(r_) * w
+                    base.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
+            self.base_anchors.append(torch.tensor(base, dtype=torch.float32, device=self.device))
+
+    def _plan_anchors(self, pl):
+        """pl.anchors, pl.A_total: every level's anchors in one (sum HWA, 4) tensor (regenerated per forward in the reference,
+        retinanet.py:116; cached per shape here: a per-shape constant, not in the arena)."""
+        A = self.num_anchors
+        pl.A_total = pl.pyr.pix_per_img * A
+        pl.anchors = torch.empty((pl.A_total, 4), dtype=torch.float32, device=self.device)
+        o = 0
+        for (h, w), s, base in zip(pl.sizes, self.strides, self.base_anchors):
+            n = h * w * A
+            ops.anchors_generate(h, w, s, self.cfg.MODEL.ANCHOR.OFFSET, base, pl.anchors[o:o + n])
+            o += n
 
     def _enable_fp8_layers(self):
         """BASELINE config 5: fp8-e4m3 weights (one scale per output channel) for the forward of the 3x3 convolutions -- where a
@@ -627,14 +659,12 @@ class FPNDetector:
         st = self.fpn_stages
         nl = len(st)
         b5 = pl.blk[pl.res[st[-1]]]
-        side = self.wgrads.side() if self.TOP_BLOCK == "p6p7" else None
         if self.TOP_BLOCK == "p6p7":
             # LastLevelP6P7 (:198-204) only needs res5 and writes its own pyramid levels: its two small-grid convs (70 workgroups for
-            # P6 at 800x1344) run on the side stream, concurrently with the lateral / output convs below
+            # P6 at 800x1344) run on the weight-gradient stream (idle in the forward pass), concurrently with the lateral / output convs below
             g6, g7 = pl.pyr.level(nl), pl.pyr.level(nl + 1)
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side) if side is not None else _nullcontext():
+            side = self.streams.wgrad()
+            with fork(side):
                 self.p6.forward(b5.out, b5.gout, g6, pl.P, y8=pl.P8)
                 self._relu_level(pl.P, g6, pl.p6_relu)
                 self.p7.forward(pl.p6_relu, pl.g_p6r, g7, pl.P, y8=pl.P8)
@@ -650,8 +680,7 @@ class FPNDetector:
             self.output[s].forward(pl.lat[s], b.gout, pl.pyr.level(li), pl.P, y8=pl.P8)
             prev, prev_geo = pl.lat[s], b.gout
         if self.TOP_BLOCK == "p6p7":
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
+            join(side)
         else:
             ops.subsample2x_fwd(pl.P, pl.pyr.level(nl - 1), pl.P, pl.pyr.level(nl), self.fpn_ch)   # FPNP6 (:172-183)
         self.head_forward(pl)
@@ -770,7 +799,7 @@ class FPNDetector:
         for b in pl.blk:
             b.g_out8_ready = False
         self.head_backward(pl, ws, cws)
-        wside = self.wgrads.side()
+        wside = self.streams.wgrad()
         side = (wside,) if wside is not None else ()
         self._flush_wgrads()
         if on_bucket_ready:
@@ -784,12 +813,10 @@ class FPNDetector:
             g6, g7 = pyr.level(nl), pyr.level(nl + 1)
             # P7 = conv(relu(P6)): d P6 = dgrad(g_P7) * (P6 > 0) + g_P6(head), written in place into g_P's P6 level
             # The two dgrads are small grids that only touch the P6/P7 levels of g_P and res5's gradient, which the main stream
-            # does not read before the top lateral dgrad below: they run on their own stream next to the P3.. output-conv dgrads.
-            top = self.wgrads.top()
+            # does not read before the top lateral dgrad below: they run on the auxiliary stream next to the P3.. output-conv dgrads.
+            top = self.streams.aux()
             self._wgrad(self.p7, pl.p6_relu, pl.g_P, pl.g_p6r, g7, ws, cws)
-            if top is not None:
-                top.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(top) if top is not None else _nullcontext():
+            with fork(top):
                 self.p7.dgrad(pl.g_P, g6, g7, pl.g_P, mask=pl.P, add_after=pl.g_P)
                 self._wgrad(self.p6, b5.out, pl.g_P, b5.gout, g6, ws, cws)
                 self.p6.dgrad(pl.g_P, b5.gout, g6, b5.g_out, first=True)
@@ -817,8 +844,8 @@ class FPNDetector:
             if not self.blocks[pl.res[s]]["trainable"]:
                 continue                                   # res2 of a FREEZE_AT=2 backbone: nothing below needs the gradient
             if is_top:
-                if not pool_top and top is not None:
-                    torch.cuda.current_stream().wait_stream(top)
+                if not pool_top:
+                    join(top)
                 self.lateral[s].dgrad(pl.g_lat[s], b.gout, b.gout, b.g_out, first=pool_top, mask=b.out, maskbits=b.out_bits)
             else:
                 self.lateral[s].dgrad(pl.g_lat[s], b.gout, b.gout, b.g_out, first=True)

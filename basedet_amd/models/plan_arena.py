@@ -131,7 +131,7 @@ class PlanArena:
 
     def bind(self, pl):
         """Start of a step at plan pl.  When another plan used the arena since pl's last step, every buffer of pl's can hold that plan's
-        data: the main stream first waits for every stream that touched plan memory (the weight-gradient stream, the top-block stream;
+        data: the main stream first waits for every stream that touched plan memory (the weight-gradient stream, the auxiliary stream;
         the communicator only reads the parameter arena and the FCOS statistics, behind a wait of its own), then the buffers whose start
         state is all-zero (counters, loss sums, d_rpn_raw's padding channel) are cleared -- as torch.zeros did once per plan."""
         if self.bound is pl:

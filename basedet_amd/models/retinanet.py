@@ -5,13 +5,10 @@ Same protocol as the reference's BaseNet (models/base_net.py:50-71): ``model(bat
 ``{"total_loss", "cls_loss", "reg_loss"}``; the batch dict is the collator contract
 (data/collators/pad_collator.py:38-49): ``data`` (N,3,H,W), ``gt_boxes`` (N,G,5), ``im_info`` (N,5).
 """
-import math
-
-import numpy as np
 import torch
-from contextlib import nullcontext as _nullcontext
 
 from .. import ops
+from ..streams import fork, join
 from ..utils.registry import registers
 from . import params as P
 from .fpn_base import FPNDetector, _round_up
@@ -35,7 +32,6 @@ class RetinaNet(FPNDetector):
         """RetinaNetHead (layers/head/retina_head.py:9-70): two 4-conv towers + cls_score / bbox_pred, weights shared
         over the five levels."""
         m = self.cfg.MODEL
-        dev = self.device
         ch = self.fpn_ch
         self.num_anchors = len(m.ANCHOR.SCALES[0]) * len(m.ANCHOR.RATIOS[0])
         nc = m.HEAD.NUM_CONVS
@@ -55,31 +51,14 @@ class RetinaNet(FPNDetector):
         # instead of being scanned out of every gradient again -- by its data gradient AND its weight gradient (bd_conv_desc.gskip_gmap /
         # gskip_dxmap).  Off: every launch scans for itself, as before the maps existed.
         self.sparse_chain = bool(m.get("SPARSE_BOX_CHAIN", True))
-        # base anchors: python float64 -> float32 (layers/common/anchor_generator.py:95-109)
-        scales = np.asarray(m.ANCHOR.SCALES, np.float32).tolist()
-        ratios = np.asarray(m.ANCHOR.RATIOS, np.float32).tolist()
-        if len(ratios) == 1:
-            ratios = ratios * len(self.strides)
-        if len(scales) == 1:
-            scales = scales * len(self.strides)
-        self.base_anchors = []
-        for sc_, ra_ in zip(scales, ratios):
-            base = []
-            for s_ in sc_:
-                area = float(s_) ** 2.0
-                for r_ in ra_:
-                    w = math.sqrt(area / float(r_)); h = float(r_) * w
-                    base.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
-            self.base_anchors.append(torch.tensor(base, dtype=torch.float32, device=dev))
+        self._build_base_anchors()
 
     def _head_convs(self):
         return self.cls_tower + self.box_tower + [self.cls_score, self.bbox_pred]
 
     def _plan_head(self, pl):
-        dev = self.device
         ch = self.fpn_ch
         N = pl.N
-        sizes = pl.sizes
         C = pl._carve
         bf = torch.bfloat16
 
@@ -112,15 +91,8 @@ class RetinaNet(FPNDetector):
         tg = self.fp8_grad_twins
         pl.g_tower8 = [[tw() if (c.fp8_dgrad and tg) else None for c in tower] for tower in (self.cls_tower, self.box_tower)]
         pl.g_P8 = tw() if (tg and all(t[0].fp8_dgrad for t in (self.cls_tower, self.box_tower))) else None
-        # anchors (regenerated per forward in the reference, retinanet.py:116; cached per shape here: a per-shape constant, not in the arena)
-        tot = pl.pyr.pix_per_img * A
-        pl.anchors = torch.empty((tot, 4), dtype=torch.float32, device=dev)
-        o = 0
-        for (h, w), s, base in zip(sizes, self.strides, self.base_anchors):
-            n = h * w * A
-            ops.anchors_generate(h, w, s, self.cfg.MODEL.ANCHOR.OFFSET, base, pl.anchors[o:o + n])
-            o += n
-        pl.A_total = tot
+        self._plan_anchors(pl)
+        tot = pl.A_total
         pl.labels = C.empty((N, tot), torch.int32)
         pl.match_idx = C.empty((N, tot), torch.int32)
         pl.gt_offsets = C.empty((N, tot, 4), torch.float32)
@@ -136,16 +108,12 @@ class RetinaNet(FPNDetector):
         # the 0.907 factor of profiles/r06_pp_power.txt), +0.4-0.5 % per step on three boxes (profiles/r06_head_towers_ab.txt).  The same on the
         # BACKWARD pass, where the weight-gradient stream already runs beside the chain, costs 1.2 %: not done.  Steps that keep the weight
         # gradients on the main stream (bench.py's instrumented steps, --serial-wgrad) stay serial here too: clean per-kernel durations.
-        side = None
         # (bf16 only: in fp8 mode the tower convolutions may share the main stream's cast scratch)
-        # The second stream is the model's EXISTING side stream (the top-block stream: the target assignment at the start of the forward pass, long done
-        # here; the top block's data gradients in the backward pass).  A stream of its own made five per process under torch.distributed (main,
-        # weight gradients, side, communicator, this one) and the step lost 2.8 ms (577 against 643 img/s with one rank and a forced
-        # all-reduce: profiles/r06_head_towers_ab.txt; cause not established -- GPU_MAX_HW_QUEUES=8 did not remove it).
-        if bool(self.cfg.MODEL.get("HEAD_TOWERS_CONCURRENT", True)) and self.wgrads.top() is not None and self.weight_dtype != "fp8_e4m3":
-            side = self.wgrads.top()
-            side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side) if side is not None else _nullcontext():
+        # The second stream is the model's auxiliary stream (the target assignment at the start of the forward pass is long done here), not one
+        # of its own: see SideStreams.
+        concurrent = bool(self.cfg.MODEL.get("HEAD_TOWERS_CONCURRENT", True)) and self.weight_dtype != "fp8_e4m3"
+        side = self.streams.aux() if concurrent else None
+        with fork(side):
             t, t8 = pl.P, getattr(pl, "P8", None)
             for c, a, a8 in zip(self.box_tower, pl.box_act, pl.box_act8):
                 c.forward(t, pl.pyr, pl.pyr, a, relu=True, x8=t8, y8=a8); t, t8 = a, a8
@@ -154,8 +122,7 @@ class RetinaNet(FPNDetector):
         for c, a, a8 in zip(self.cls_tower, pl.cls_act, pl.cls_act8):
             c.forward(t, pl.pyr, pl.pyr, a, relu=True, x8=t8, y8=a8); t, t8 = a, a8
         self.cls_score.forward(t, pl.pyr, pl.pyr, pl.logits, x8=t8)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
+        join(side)
 
     def get_losses(self, inputs):
         """RetinaNet.get_losses (retinanet.py:120-170)."""
@@ -170,16 +137,13 @@ class RetinaNet(FPNDetector):
         ws = self._scratch("assign", N * Gmax * 4).view(torch.float32)     # (N x Gmax floats: grows with the batch's Gmax, not the shape)
         thr = m.MATCHER.THRESHOLDS
         # The target assignment depends on the anchors and the gt boxes only (retinanet.py:211-232), not on the network's output: its two
-        # launches (~0.12 ms at 16 x 201 600 anchors) run on a side stream under the forward pass instead of between forward and losses.
-        side = self.wgrads.top() if m.get("ASSIGN_ON_SIDE_STREAM", True) else None
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side) if side is not None else _nullcontext():
+        # launches (~0.12 ms at 16 x 201 600 anchors) run on the auxiliary stream under the forward pass instead of between forward and losses.
+        side = self.streams.aux() if m.get("ASSIGN_ON_SIDE_STREAM", True) else None
+        with fork(side):
             ops.retina_assign_encode(pl.anchors, gt, num_gt, thr[0], thr[1], m.MATCHER.ALLOW_LOW_QUALITY, m.BOX_REG.MEAN,
                                      m.BOX_REG.STD, pl.labels, pl.match_idx, pl.gt_offsets, pl.num_fg, ws)
         self.network_forward(pl)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
+        join(side)
         pl.loss_buf.zero_()
         rows = N * pl.A_total
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA,

@@ -1,16 +1,17 @@
-"""Where and when the weight-gradient kernels of a backward pass run: the two side streams of a model, and the deferred-reduce queue
-with its partial-sum arena."""
+"""When the weight-gradient kernels of a backward pass run: their forks onto the model's weight-gradient stream (streams.py), and the
+deferred-reduce queue with its partial-sum arena."""
 import torch
 
 from .. import ops
+from ..streams import fork, join
 
 
 class WgradScheduler:
-    def __init__(self, device, queue_mode):
+    def __init__(self, device, queue_mode, streams):
         self.device = torch.device(device)
-        # weight-gradient kernels run on a side stream, concurrently with the dgrad chain they do not feed: tails and
-        # barrier bubbles of one kernel are filled by the other (set False to serialise, e.g. for per-kernel timing)
-        self.async_wgrad = True
+        # weight-gradient kernels run on a side stream (streams.wgrad()), concurrently with the dgrad chain they do not feed: tails and
+        # barrier bubbles of one kernel are filled by the other (streams.enabled = False serialises, e.g. for per-kernel timing)
+        self.streams = streams
         # WGRAD_QUEUE: "layer" (default again since round 5) = one fixed-order reduce per layer right behind its partial-sum kernel: the slabs
         # are still in the Infinity Cache when they are read back; "bucket" (round 4's default) = the reduces of a gradient bucket (head /
         # fpn / layer4 / layer3 / layer2) in ONE launch (bd_wgrad_queue_*: 5 reduce launches per step instead of 60); an integer =
@@ -24,23 +25,6 @@ class WgradScheduler:
         # every later partial-sum kernel run on the same stream, so the slices are re-used from offset 0 after each flush
         self.arena = None
         self.off = self.pending = self.peak = 0
-        self.wstream = torch.cuda.Stream() if (torch.cuda.is_available() and self.device.type == "cuda") else None
-        self.tstream = torch.cuda.Stream() if self.wstream is not None else None      # P6/P7 top-block dgrads
-
-    def side(self):
-        """The weight-gradient stream, or None when the weight gradients run on the main stream (async_wgrad off, no GPU)."""
-        return self.wstream if self.async_wgrad else None
-
-    def top(self):
-        """The top-block stream, or None under the same conditions."""
-        return self.tstream if self.async_wgrad else None
-
-    def join_side(self):
-        """The current stream waits for the side streams that touch plan memory or model scratch (weight gradients, top block)."""
-        if self.wstream is not None:
-            cur = torch.cuda.current_stream()
-            cur.wait_stream(self.wstream)
-            cur.wait_stream(self.tstream)
 
     def run(self, conv, x, g, gin, gout, ws, cws=None, x8=None, g8=None):
         """conv.wgrad on the side stream: it only needs x and g as they are NOW (everything enqueued so far on the main
@@ -65,13 +49,8 @@ class WgradScheduler:
                 if self.queue is None:
                     self.queue = ops.WgradQueue()
                 q = self.queue
-        side = self.side()
-        if side is None:
+        with fork(self.streams.wgrad()):
             conv.wgrad(x, g, gin, gout, ws, cws, x8=x8, g8=g8, queue=q)
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                conv.wgrad(x, g, gin, gout, ws, cws, x8=x8, g8=g8, queue=q)
         if q is not None and isinstance(self.queue_mode, int) and self.pending >= self.queue_mode:
             self.flush()
 
@@ -91,18 +70,12 @@ class WgradScheduler:
         q = self.queue
         if q is None or not q.pending():
             return
-        side = self.side()
-        if side is not None:
-            with torch.cuda.stream(side):
-                q.flush()
-        else:
+        with fork(self.streams.wgrad(), wait=False):         # (behind the partial sums already there: no main -> side dependency per flush)
             q.flush()
 
     def join(self):
         self.flush()
-        side = self.side()
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
+        join(self.streams.wgrad())
         have = 0 if self.arena is None else self.arena.numel() * 4
         if self.queue_mode != "layer" and self.peak > have:
             # (behind the join: the old arena's last readers have been ordered in front of the current stream, which owns both allocations)

@@ -1,12 +1,17 @@
 """The three state machines FPNDetector delegates to, on CPU tensors and without the native library: the plan arena's byte layout and
 view re-basing (models/plan_arena.py), the host arithmetic of the delayed e5m2 gradient scales (models/fp8_scaling.py) and the
-weight-gradient scheduler's bookkeeping (models/wgrad_sched.py).  Every expected value is written out by hand from the rules."""
+weight-gradient scheduler's bookkeeping (models/wgrad_sched.py) -- and what its stream helpers (streams.py) do when there is no stream.
+Every expected value is written out by hand from the rules."""
+import threading
+
 import numpy as np
+import pytest
 import torch
 
 from basedet_amd.models.fp8_scaling import Fp8GradScaler, initial_grad_scale
 from basedet_amd.models.plan_arena import PlanArena, _Carver, _Plan
 from basedet_amd.models.wgrad_sched import WgradScheduler
+from basedet_amd.streams import SideStreams, fork, join
 
 MiB = 1 << 20
 
@@ -222,8 +227,9 @@ class _Conv:
 def test_wgrad_scheduler_layer_mode_hands_out_the_shared_workspace():
     """Only the "layer" mode is checked here: the queued modes need ops.WgradQueue, i.e. the native library and a GPU
     (tests/test_wgrad_queue_gpu.py)."""
-    s = WgradScheduler("cpu", "layer")
-    assert s.async_wgrad and s.side() is None and s.top() is None                # no GPU: no side streams, whatever async_wgrad says
+    st = SideStreams("cpu")
+    s = WgradScheduler("cpu", "layer", st)
+    assert st.enabled and st.wgrad() is None and st.aux() is None                # no GPU: no side streams, whatever the flag says
     conv = _Conv()
     x, g, gin, gout, ws, cws, x8 = (object() for _ in range(7))
     s.begin()
@@ -232,10 +238,28 @@ def test_wgrad_scheduler_layer_mode_hands_out_the_shared_workspace():
     s.flush()
     s.run(conv, g, x, gout, gin, ws, cws)
     s.join()
-    s.join_side()
+    st.join_all()
     assert conv.calls == [((x, g, gin, gout, ws, cws), dict(x8=None, g8=None, queue=None)),
                           ((x, g, gin, gout, ws, None), dict(x8=x8, g8=None, queue=None)),
                           ((g, x, gout, gin, ws, cws), dict(x8=None, g8=None, queue=None))]
     assert s.queue is None and s.arena is None and s.need == {} and (s.off, s.pending, s.peak) == (0, 0, 0)
-    s.async_wgrad = False
-    assert s.side() is None and s.top() is None
+    st.enabled = False
+    assert st.wgrad() is None and st.aux() is None
+
+
+def test_fork_and_join_without_a_stream_run_inline():
+    ran = []
+    with fork(None):
+        ran.append(threading.get_ident())
+    with fork(None, wait=False):
+        ran.append(threading.get_ident())
+    assert ran == [threading.get_ident()] * 2                  # each body once, on the calling thread
+    with pytest.raises(KeyError, match="from the body"):
+        with fork(None):
+            raise KeyError("from the body")
+    assert join(None) is None
+    st = SideStreams("cpu")
+    for flag in (True, False):
+        st.enabled = flag
+        assert st.wgrad() is None and st.aux() is None and st.wgrad_stream is None and st.aux_stream is None
+        st.join_all()
