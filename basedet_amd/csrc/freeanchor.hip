@@ -11,8 +11,9 @@
 //                    anchor and class (:72-73, an indexed assignment; order unpinned) -- kept in LDS as (gt index, value) under
 //                    a 64-bit atomicMax, then the negative loss q^gamma * -log(1 - q), q = sigmoid(x)(1 - box_prob) (:38-39,
 //                    :128-130) and its gradient for all logits;
-//   fa_apply_kernel  one workgroup per image: adds the bag gradients to d_logits / d_offsets gt after gt (fixed order:
-//                    two bags may share an anchor), and block 0 reduces the losses in a fixed order.
+//   fa_apply_kernel  one workgroup per image: sums the bag gradients that meet on one anchor (d_offsets) or one (anchor, class)
+//                    (d_logits, on top of the negative-loss gradient) in fp32, gt after gt (fixed order), and rounds each sum to
+//                    bf16 once; block 0 reduces the losses in a fixed order.
 // safelog = log(max(x, FLT_MIN)) (layers/common/function.py:35-44).  Compiled with -ffp-contract=off (IoU / encode / decode as in
 // the oracle).
 #pragma clang fp contract(off)
@@ -243,6 +244,34 @@ __global__ __launch_bounds__(1024) void fa_gt_kernel(const bf16_raw* __restrict_
     }
 }
 
+// negative loss q^gamma * -log(1 - q), q = sigmoid(x) (1 - box_prob), of one logit; g = scale * its derivative
+__device__ __forceinline__ float fa_neg_elem(float x, float bpv, float gamma, float scale, float& g) {
+    if (gamma == 2.f) {
+        // round 5: the default focal exponent on the raw transcendental instructions (v_exp_f32 / v_log_f32 / v_rcp_f32, 1 ulp), as
+        // focal_g2_kernel (losses.hip): expf / logf / the two divisions compile to ~80 vector instructions per logit, this to ~25
+        const float e = __builtin_amdgcn_exp2f(-x * 1.4426950408889634f);
+        const float s = __builtin_amdgcn_rcpf(1.f + e);
+        const float keep = 1.f - bpv;
+        const float q = s * keep;
+        const float om = 1.f - q;
+        const float nl = -0.6931471805599453f * __builtin_amdgcn_logf(fmaxf(om, FLT_MIN));
+        const float qg = q * q;
+        const float dq = 2.f * q * nl + (om > FLT_MIN ? qg * __builtin_amdgcn_rcpf(om) : 0.f);
+        g = scale * dq * s * (1.f - s) * keep;
+        return qg * nl;
+    }
+    const float s = sigmoidf_(x);
+    const float keep = 1.f - bpv;
+    const float q = s * keep;
+    const float om = 1.f - q;
+    const float nl = -safelogf_(om);
+    const float qg = gamma == 2.f ? q * q : (q > 0.f ? expf(gamma * logf(q)) : 0.f);
+    const float qg1 = gamma == 2.f ? q : (q > 0.f ? expf((gamma - 1.f) * logf(q)) : 0.f);
+    const float dq = gamma * qg1 * nl + (om > FLT_MIN ? qg / om : 0.f);
+    g = scale * dq * s * (1.f - s) * keep;
+    return qg * nl;
+}
+
 __global__ __launch_bounds__(256) void fa_neg_kernel(const bf16_raw* __restrict__ logits, const bf16_raw* __restrict__ offsets,
                                                      int box_ld, int apix, const float* __restrict__ anchors, int A, int K,
                                                      const float* __restrict__ gt, const int* __restrict__ num_gt, int N, int Gmax,
@@ -280,32 +309,7 @@ __global__ __launch_bounds__(256) void fa_neg_kernel(const bf16_raw* __restrict_
     float acc = 0.f;
     const int nel = (A - a0 < FA_NEG_ANCH ? A - a0 : FA_NEG_ANCH) * K;
     const long long e0 = ((long long)n * A + a0) * K;
-    auto elem = [&](float x, float bpv, float& g) -> float {
-        if (gamma == 2.f) {
-            // round 5: the default focal exponent on the raw transcendental instructions (v_exp_f32 / v_log_f32 / v_rcp_f32, 1 ulp), as
-            // focal_g2_kernel (losses.hip): expf / logf / the two divisions compile to ~80 vector instructions per logit, this to ~25
-            const float e = __builtin_amdgcn_exp2f(-x * 1.4426950408889634f);
-            const float s = __builtin_amdgcn_rcpf(1.f + e);
-            const float keep = 1.f - bpv;
-            const float q = s * keep;
-            const float om = 1.f - q;
-            const float nl = -0.6931471805599453f * __builtin_amdgcn_logf(fmaxf(om, FLT_MIN));
-            const float qg = q * q;
-            const float dq = 2.f * q * nl + (om > FLT_MIN ? qg * __builtin_amdgcn_rcpf(om) : 0.f);
-            g = scale * dq * s * (1.f - s) * keep;
-            return qg * nl;
-        }
-        const float s = sigmoidf_(x);
-        const float keep = 1.f - bpv;
-        const float q = s * keep;
-        const float om = 1.f - q;
-        const float nl = -safelogf_(om);
-        const float qg = gamma == 2.f ? q * q : (q > 0.f ? expf(gamma * logf(q)) : 0.f);
-        const float qg1 = gamma == 2.f ? q : (q > 0.f ? expf((gamma - 1.f) * logf(q)) : 0.f);
-        const float dq = gamma * qg1 * nl + (om > FLT_MIN ? qg / om : 0.f);
-        g = scale * dq * s * (1.f - s) * keep;
-        return qg * nl;
-    };
+    auto elem = [&](float x, float bpv, float& g) -> float { return fa_neg_elem(x, bpv, gamma, scale, g); };
     if (K % 8 == 0) {           // 16-byte logit / gradient accesses (e0 is a multiple of 8)
         for (int i = tid; i < nel / 8; i += 256) {
             const u32x4_t v = *reinterpret_cast<const u32x4_t*>(logits + e0 + 8ll * i);
@@ -332,43 +336,103 @@ __global__ __launch_bounds__(256) void fa_neg_kernel(const bf16_raw* __restrict_
     if (tid == 0) neg_part[(long long)n * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
 }
 
-__global__ __launch_bounds__(256) void fa_apply_kernel(const int* __restrict__ num_gt, int N, int Gmax, int A, int K, int apix,
-                                                       int box_ld, int bucket, const float* __restrict__ gt,
-                                                       const int* __restrict__ bag_idx, const float* __restrict__ bag_grad,
-                                                       const float* __restrict__ pos_loss, const float* __restrict__ neg_part,
-                                                       int neg_blocks, bf16_raw* __restrict__ d_logits,
-                                                       bf16_raw* __restrict__ d_offsets, float* __restrict__ loss_out) {
+// position of anchor a in one bag's index list bi[0 .. bucket) (ascending, padded with -1 behind the members), or -1
+__device__ __forceinline__ int fa_bag_find(const int* bi, int bucket, int a) {
+    int lo = 0, hi = bucket;          // lo -> the first entry that is a pad or >= a
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int v = bi[mid];
+        if (v >= 0 && v < a) lo = mid + 1; else hi = mid;
+    }
+    return lo < bucket && bi[lo] == a ? lo : -1;
+}
+
+// Bags share anchors, and an anchor's logit at the gt's class also carries the negative-loss gradient.  Adding one bag after the other
+// into the bf16 outputs rounded once per bag (and the negative part once before): up to 10 x 2^-8 of the result where the parts
+// cancel.  Here the thread of the FIRST bag entry on an anchor (d_offsets) or on an (anchor, class) (d_logits) looks the anchor up in
+// the later bags, sums in fp32 in gt order -- for d_logits starting from the negative-loss gradient, recomputed in fp32 exactly as
+// fa_neg_kernel does -- and stores the rounded sum: one writer per element, one rounding, a fixed order.
+__global__ __launch_bounds__(1024) void fa_apply_kernel(const int* __restrict__ num_gt, int N, int Gmax, int A, int K, int apix,
+                                                        int box_ld, int bucket, const float* __restrict__ gt,
+                                                        const int* __restrict__ bag_idx, const float* __restrict__ bag_grad,
+                                                        const float* __restrict__ pos_loss, const float* __restrict__ neg_part,
+                                                        int neg_blocks, const bf16_raw* __restrict__ logits,
+                                                        const bf16_raw* __restrict__ offsets, const float* __restrict__ anchors,
+                                                        Coder coder, float iou_thresh, float alpha, float gamma,
+                                                        const float* __restrict__ thresh2, int stage, bf16_raw* __restrict__ d_logits,
+                                                        bf16_raw* __restrict__ d_offsets, float* __restrict__ loss_out) {
+    extern __shared__ int s_bi[];            // the image's bag index lists, when they fit (stage)
     __shared__ float red[4];
     const int tid = threadIdx.x, n = blockIdx.x;
     const int G = num_gt[n];
-    for (int g = 0; g < G; ++g) {
-        const int slot = n * Gmax + g;
-        const int cls = (int)gt[(long long)slot * 5 + 4] - 1;
-        if (tid < bucket) {
-            const int a = bag_idx[(long long)slot * bucket + tid];
-            if (a >= 0) {
-                const float* gq = bag_grad + ((long long)slot * bucket + tid) * 5;
-                bf16_raw* dl = d_logits + ((long long)n * A + a) * K + cls;
-                *dl = f2bf(bf2f(*dl) + gq[0]);
-                bf16_raw* dp = d_offsets + ((long long)n * (A / apix) + a / apix) * box_ld + (a % apix) * 4;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) dp[k] = f2bf(bf2f(dp[k]) + gq[1 + k]);
-            }
-        }
+    const int* bi = bag_idx + (long long)n * Gmax * bucket;
+    if (stage) {
+        for (int i = tid; i < G * bucket; i += 1024) s_bi[i] = bi[i];
         __syncthreads();
+        bi = s_bi;
     }
-    if (n == 0) {           // fixed-order loss reductions
+    const float* gtn = gt + (long long)n * Gmax * 5;
+    const float* bgn = bag_grad + (long long)n * Gmax * bucket * 5;
+    const float scale = (1.f - alpha) / fmaxf(1.f, (float)total_fg(num_gt, N) * (float)bucket);
+    for (int e = tid; e < G * bucket; e += 1024) {
+        const int a = bi[e];
+        if (a < 0) continue;
+        const int g = e / bucket;
+        const int cls = (int)gtn[g * 5 + 4] - 1;
+        bool first_a = true, first_ac = true;
+        for (int h = 0; h < g; ++h)
+            if (fa_bag_find(bi + h * bucket, bucket, a) >= 0) {
+                first_a = false;
+                if ((int)gtn[h * 5 + 4] - 1 == cls) first_ac = false;
+            }
+        if (!first_a && !first_ac) continue;
+        float sl = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        if (first_ac) {         // the negative-loss gradient of (a, cls): box probability as fa_neg_kernel, the last gt of the class with a non-zero one
+            const Box ab = ld_box(anchors + 4ll * a);
+            const f32x4_t pb = decode_dev(ab, ld_offsets(offsets, (long long)n * (A / apix), a, apix, box_ld), coder);
+            const Box p{pb[0], pb[1], pb[2], pb[3]};
+            const float parea = box_area(p);
+            float bpv = 0.f;
+            for (int h = 0; h < G; ++h) {
+                const float* gp = gtn + h * 5;
+                if ((int)gp[4] - 1 != cls) continue;
+                const Box gb = ld_gt(gp);
+                const float ov = box_iou_dev(gb, box_area(gb), p, parea);
+                const float t2 = thresh2[n * Gmax + h];
+                const float prob = fminf(fmaxf((ov - iou_thresh) / (t2 - iou_thresh), 0.f), 1.f);
+                if (prob != 0.f) bpv = prob;
+            }
+            (void)fa_neg_elem(bf2f(logits[((long long)n * A + a) * K + cls]), bpv, gamma, scale, sl);
+        }
+        for (int h = g; h < G; ++h) {            // gt order; h == g is this entry itself
+            const int j = h == g ? e - g * bucket : fa_bag_find(bi + h * bucket, bucket, a);
+            if (j < 0) continue;
+            const float* gq = bgn + ((long long)h * bucket + j) * 5;
+            if (first_ac && (int)gtn[h * 5 + 4] - 1 == cls) sl += gq[0];
+            if (first_a) { s0 += gq[1]; s1 += gq[2]; s2 += gq[3]; s3 += gq[4]; }
+        }
+        if (first_ac) d_logits[((long long)n * A + a) * K + cls] = f2bf(sl);
+        if (first_a) {
+            bf16_raw* dp = d_offsets + ((long long)n * (A / apix) + a / apix) * box_ld + (a % apix) * 4;
+            dp[0] = f2bf(s0); dp[1] = f2bf(s1); dp[2] = f2bf(s2); dp[3] = f2bf(s3);
+        }
+    }
+    if (n == 0) {           // fixed-order loss reductions (by the first 256 threads)
         float s = 0.f;
-        for (int i = tid; i < N * Gmax; i += 256) s += pos_loss[i];
-        s = wave_sum(s);
-        if ((tid & 63) == 0) red[tid >> 6] = s;
+        if (tid < 256) {
+            for (int i = tid; i < N * Gmax; i += 256) s += pos_loss[i];
+            s = wave_sum(s);
+            if ((tid & 63) == 0) red[tid >> 6] = s;
+        }
         __syncthreads();
         if (tid == 0) loss_out[0] = (red[0] + red[1]) + (red[2] + red[3]);
         __syncthreads();
         s = 0.f;
-        for (int i = tid; i < N * neg_blocks; i += 256) s += neg_part[i];
-        s = wave_sum(s);
-        if ((tid & 63) == 0) red[tid >> 6] = s;
+        if (tid < 256) {
+            for (int i = tid; i < N * neg_blocks; i += 256) s += neg_part[i];
+            s = wave_sum(s);
+            if ((tid & 63) == 0) red[tid >> 6] = s;
+        }
         __syncthreads();
         if (tid == 0) loss_out[1] = (red[0] + red[1]) + (red[2] + red[3]);
     }
@@ -414,8 +478,11 @@ extern "C" int bd_freeanchor_loss_fwd_bwd(const void* logits, const void* offset
     hipLaunchKernelGGL(fa_neg_kernel, dim3(neg_blocks, N), dim3(256), (size_t)FA_NEG_ANCH * K * 8, st, (const bf16_raw*)logits,
                        (const bf16_raw*)offsets, box_ld, anchors_per_pix, anchors, A, K, gt, num_gt, N, Gmax, coder, iou_thresh,
                        bucket, alpha, gamma, thresh2, neg_part, (bf16_raw*)d_logits);
-    hipLaunchKernelGGL(fa_apply_kernel, dim3(N), dim3(256), 0, st, num_gt, N, Gmax, A, K, anchors_per_pix, box_ld, bucket, gt, bag_idx,
-                       bag_grad, pos_loss, neg_part, neg_blocks, (bf16_raw*)d_logits, (bf16_raw*)d_offsets, loss_out);
+    const size_t lists = sizeof(int) * (size_t)Gmax * bucket;          // the bag index lists of one image: through LDS up to 48 KB
+    const int stage = lists <= 48 * 1024;
+    hipLaunchKernelGGL(fa_apply_kernel, dim3(N), dim3(1024), stage ? lists : 0, st, num_gt, N, Gmax, A, K, anchors_per_pix, box_ld, bucket,
+                       gt, bag_idx, bag_grad, pos_loss, neg_part, neg_blocks, (const bf16_raw*)logits, (const bf16_raw*)offsets, anchors,
+                       coder, iou_thresh, alpha, gamma, (const float*)thresh2, stage, (bf16_raw*)d_logits, (bf16_raw*)d_offsets, loss_out);
     BD_CHECK_LAUNCH("bd_freeanchor_loss_fwd_bwd");
     return BD_OK;
 }

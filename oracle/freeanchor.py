@@ -20,11 +20,19 @@ def safelog(x):
 
 
 def bag_losses(logits, offsets, anchors, gt_boxes, num_gt, *, mean=(0, 0, 0, 0), std=(0.1, 0.1, 0.2, 0.2), iou_thresh=0.6,
-               bucket=50, beta=0.0, reg_weight=0.75, alpha=0.25, gamma=2.0):
+               bucket=50, beta=0.0, reg_weight=0.75, alpha=0.25, gamma=2.0, dtype=torch.float32, aux=None):
     """logits (N, A, K), offsets (N, A, 4): torch fp32 (requires_grad for gradients); anchors (A, 4), gt_boxes (N, G, 5),
-    num_gt (N,) numpy.  Returns (pos_loss, neg_loss) as torch scalars (already weighted by alpha / 1 - alpha)."""
+    num_gt (N,) numpy.  Returns (pos_loss, neg_loss) as torch scalars (already weighted by alpha / 1 - alpha).
+
+    dtype=torch.float64 (pass float64 leaves to get float64 gradients): the differentiable part -- sigmoid, smooth-L1, exp, the bag
+    weights, the logs and the sums -- runs in float64, while every SELECTION (decode, IoUs, t1 / t2, the clipped box probability, the
+    top-k order, the encode targets) stays on the fp32 numpy values, so that the oracle picks the anchors the kernels pick.
+    aux: a list that receives one dict per image with the selection intermediates (ov (G, A) IoU of gt and decoded prediction, t2 (G, 1),
+    gp (G, A) clipped box probability per gt, mq (G, A) IoU of gt and anchor, order (G, k) bag members best first, labels (G,)); an
+    image without boxes gives an empty dict."""
     N, A, K = logits.shape
     anchors = np.asarray(anchors, np.float32)
+    logits, offsets = logits.to(dtype), offsets.to(dtype)
     scores = torch.sigmoid(logits)
     box_probs = []
     pos_losses = []
@@ -34,16 +42,17 @@ def bag_losses(logits, offsets, anchors, gt_boxes, num_gt, *, mean=(0, 0, 0, 0),
         info = np.asarray(gt_boxes[n][:G], np.float32)
         labels = info[:, 4].astype(np.int32) - 1
         gt = info[:, :4]
-        prob = torch.zeros((A, K), dtype=torch.float32)
+        prob = torch.zeros((A, K), dtype=dtype)
+        rec = {}
         if G > 0:
-            pred_box = box_ops.box_decode(anchors, offsets[n].detach().numpy(), mean, std)
+            pred_box = box_ops.box_decode(anchors, offsets[n].detach().float().numpy(), mean, std)
             ov = box_ops.box_iou(gt, pred_box)                                              # (G, A)
             t1 = np.float32(iou_thresh)
             t2 = np.clip(ov.max(axis=1, keepdims=True), np.float32(t1 + np.float32(eps)), np.float32(1.0)).astype(np.float32)
             gp = np.clip((ov - t1) / (t2 - t1), 0, 1.0).astype(np.float32)
             for g in range(G):                                                             # later gts overwrite earlier ones
                 nz = np.nonzero(gp[g])[0]
-                prob[torch.from_numpy(nz), int(labels[g])] = torch.from_numpy(gp[g][nz])
+                prob[torch.from_numpy(nz), int(labels[g])] = torch.from_numpy(gp[g][nz]).to(dtype)
             # bags
             mq = box_ops.box_iou(gt, anchors)
             k = min(bucket, A)
@@ -52,7 +61,7 @@ def bag_losses(logits, offsets, anchors, gt_boxes, num_gt, *, mean=(0, 0, 0, 0),
             lab = torch.from_numpy(np.repeat(labels.astype(np.int64), k))
             matched_score = scores[n][idx, lab].reshape(G, k)
             tgt = box_ops.box_encode(anchors[order.reshape(-1)], np.repeat(gt, k, axis=0), mean, std)
-            d = offsets[n][idx] - torch.from_numpy(tgt.astype(np.float32))
+            d = offsets[n][idx] - torch.from_numpy(tgt.astype(np.float32)).to(dtype)
             if beta < 1e-5:
                 sl1 = d.abs()
             else:
@@ -62,7 +71,10 @@ def bag_losses(logits, offsets, anchors, gt_boxes, num_gt, *, mean=(0, 0, 0, 0),
             w = 1.0 / (1.0 - p)
             w = w / w.sum(dim=1, keepdim=True)
             pos_losses.append(-safelog((w * p).sum(dim=1)))
+            rec = dict(ov=ov, t2=t2, gp=gp, mq=mq, order=order, labels=labels)
         box_probs.append(prob)
+        if aux is not None:
+            aux.append(rec)
     num_fg = float(np.asarray(num_gt, np.float64).sum())
     pos = (torch.cat(pos_losses).sum() if pos_losses else scores.sum() * 0) / max(1.0, num_fg)
     bp = torch.stack(box_probs, 0)
