@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 103              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input)
+ABI_VERSION = 104              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -112,16 +112,20 @@ SIGNATURES = {
     "bd_fcos_assign": (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bd_ota_assign_workspace_bytes": (_Z, [_I, _I]),
     "bd_ota_assign": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "bd_ota_assign_ld": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_ota_sinkhorn_workspace_bytes": (_Z, [_I, _I, _I]),
     "bd_ota_assign_sinkhorn": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "bd_ota_assign_sinkhorn_ld": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_freeanchor_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "bd_freeanchor_loss_fwd_bwd": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _F, _I, _F, _F, _F, _F, _P, _P, _P, _P, _Z, _P]),
+    "bd_freeanchor_loss_fwd_bwd_ld": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _F, _I, _F, _F, _F, _F, _P, _P, _P, _P, _Z, _P]),
     "bd_atss_assign_workspace_bytes": (_Z, [_I, _I]),
     "bd_atss_assign": (_I, [_P, _I, _P, _P, _I, _I, _F, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_nms_workspace_bytes": (_Z, [_I]),
     "bd_batched_nms": (_I, [_P, _P, _P, _I, _F, _I, _P, _P, _P, _Z, _P]),
     "bd_focal_loss_fwd_bwd": (_I, [_P, _P, _L, _I, _F, _F, _P, _I, _F, _P, _P, _P]),
     "bd_focal_loss_fwd_bwd_general": (_I, [_P, _P, _L, _I, _F, _F, _P, _I, _F, _P, _P, _P]),
+    "bd_focal_loss_fwd_bwd_ld": (_I, [_P, _P, _L, _I, _I, _F, _F, _P, _I, _F, _P, _P, _I, _P]),
     "bd_smooth_l1_fwd_bwd": (_I, [_P, _P, _P, _L, _I, _I, _F, _P, _I, _F, _P, _P, _P]),
     "bd_giou_ltrb_fwd_bwd": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _P, _P]),
     "bd_bce_logits_fwd_bwd": (_I, [_P, _I, _I, _P, _P, _L, _P, _P, _P, _P]),
@@ -157,8 +161,10 @@ SIGNATURES = {
     "bd_rpn_loss_fwd_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _L, _F, _P, _P, _P, _P]),
     "bd_rcnn_loss_fwd_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P]),
     "bd_det_scores": (_I, [_P, _P, _I, _I, _L, _I, _P, _P]),
+    "bd_det_scores_ld": (_I, [_P, _I, _P, _I, _I, _L, _I, _P, _P]),
     "bd_det_select_workspace_bytes": (_Z, [_I, _I, _L, _I, _I]),
     "bd_det_select": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
+    "bd_det_select_ld": (_I, [_P, _I, _P, _I, _I, _I, _L, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
     "bd_rcnn_predict": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bd_det_candidates": (_I, [_I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "bd_det_finalize": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),

@@ -456,7 +456,7 @@ extern "C" int bd_conv2d_wgrad_bias(const bd_conv_desc* d, const void* x, const 
                                     float* dbias, int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream) {
     BD_ROUTE(d);
     BD_REQUIRE(dbias, "conv2d_wgrad_bias: null bias gradient");
-    BD_REQUIRE(d && d->Cout <= 2048, "conv2d_wgrad_bias: Cout must be <= 2048");
+    BD_REQUIRE(d != nullptr, "conv2d_wgrad_bias: null descriptor");
     const size_t need = bd_conv2d_wgrad_bias_workspace_bytes(d);
     if (ws_bytes < need) {
         bd_set_error("conv2d_wgrad_bias: workspace %zu < required %zu bytes", ws_bytes, need);
@@ -487,7 +487,7 @@ extern "C" int bd_conv2d_wgrad_queued(bd_wgrad_queue_t q, const bd_conv_desc* d,
     BD_ROUTE(d);
     BD_REQUIRE(q != nullptr, "bd_conv2d_wgrad_queued: null queue");
     if (dbias) {
-        BD_REQUIRE(d && d->Cout <= 2048, "conv2d_wgrad_queued: Cout must be <= 2048");
+        BD_REQUIRE(d != nullptr, "conv2d_wgrad_queued: null descriptor");
         const size_t need = bd_conv2d_wgrad_bias_workspace_bytes(d);
         if (ws_bytes < need) {
             bd_set_error("conv2d_wgrad_queued: workspace %zu < required %zu bytes", ws_bytes, need);

@@ -54,10 +54,13 @@ inline SelWs sel_layout(void* ws, int B, int L) {
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 // f(i, ck) for every item i in [i0, i1) of the segment whose score passes the threshold.  lg / ctr: this image's logits / centerness rows;
-// item i is element item0 + i of the image's [rows][K] logits.  i0 is a multiple of 8: 16-byte loads wherever the segment starts on one.
+// item i is element item0 + i of the image's [rows][ld] logits.  i0 is a multiple of 8: 16-byte loads wherever the segment starts on one.
+// ld > K (ld = round_up(K, 8): a vector never leaves its row): the slots >= K of a row are padding -- a pad logit of 0 would score 0.5 --
+// and are skipped; the index handed to f and kept in ck is the compact one, (row in the segment) * K + class, which grows with i: the
+// order of the keys, ties included, is that of the compact [rows][K] tensor.
 template <class F>
 __device__ __forceinline__ void for_each_valid(const bf16_raw* __restrict__ lg, const bf16_raw* __restrict__ ctr, int ctr_ld, int ctr_off,
-                                               int K, long long item0, int i0, int i1, float min_score, unsigned int key_lo,
+                                               int K, int ld, long long item0, int i0, int i1, float min_score, unsigned int key_lo,
                                                unsigned int kk_max, F f) {
     const bool vec = (reinterpret_cast<unsigned long long>(lg + item0) & 15ull) == 0ull;
     for (int i = i0 + (int)threadIdx.x * 8; i < i1; i += 256 * 8) {
@@ -72,20 +75,21 @@ __device__ __forceinline__ void for_each_valid(const bf16_raw* __restrict__ lg, 
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = j < n ? p[j] : (bf16_raw)0;
         }
-        long long row = (item0 + i) / K;
-        int c = (int)(item0 + i - row * K);
+        long long row = (item0 + i) / ld;
+        int c = (int)(item0 + i - row * ld);
+        const int ci = ld == K ? i : i - (i / ld) * (ld - K);       // compact index of slot j = 0 (the segment starts on a row)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            if (j < n) {
+            if (j < n && c < K) {
                 float s = sigmoid_f(bf2f(v[j]));
                 if (ctr) s = sqrtf(s * sigmoid_f(bf2f(ctr[row * ctr_ld + ctr_off])));
                 if (s > min_score) {
                     unsigned int kk = f32_asc_key(s) - key_lo;          // >= 1: the key is strictly increasing in the score
                     kk = kk < kk_max ? kk : kk_max;                      // (a sigmoid score is <= 1: never taken, keeps ck below 2^T)
-                    f(i + j, ((unsigned long long)kk << DS_IDX_BITS) | (unsigned long long)((1u << DS_IDX_BITS) - 1u - (unsigned int)(i + j)));
+                    f(ci + j, ((unsigned long long)kk << DS_IDX_BITS) | (unsigned long long)((1u << DS_IDX_BITS) - 1u - (unsigned int)(ci + j)));
                 }
             }
-            if (++c == K) { c = 0; ++row; }
+            if (++c == ld) { c = 0; ++row; }
         }
     }
 }
@@ -93,7 +97,7 @@ __device__ __forceinline__ void for_each_valid(const bf16_raw* __restrict__ lg, 
 // COMPACT = false: histogram of digit `pass` over the keys that share the segment's prefix.  COMPACT = true: keys >= collect_min -> slots.
 template <bool COMPACT>
 __global__ __launch_bounds__(256) void det_select_pass_kernel(const bf16_raw* __restrict__ logits, const bf16_raw* __restrict__ ctr,
-                                                              int ctr_ld, int ctr_off, long long rows, int K, SelSegs segs,
+                                                              int ctr_ld, int ctr_off, long long rows, int K, int ld, SelSegs segs,
                                                               float min_score, unsigned int key_lo, unsigned int kk_max, int T, int pass,
                                                               SegState* __restrict__ st, unsigned int* __restrict__ hist,
                                                               unsigned long long* __restrict__ cand) {
@@ -105,12 +109,12 @@ __global__ __launch_bounds__(256) void det_select_pass_kernel(const bf16_raw* __
     SegState* s = st + sid;
     const int i0 = ((int)blockIdx.x - segs.chunk0[seg]) * DS_CHUNK;
     const int i1 = i0 + DS_CHUNK < segs.count[seg] ? i0 + DS_CHUNK : segs.count[seg];
-    const bf16_raw* lg = logits + (long long)b * rows * K;
+    const bf16_raw* lg = logits + (long long)b * rows * ld;
     const bf16_raw* ct = ctr ? ctr + (long long)b * rows * ctr_ld : nullptr;
     if (COMPACT) {
         const unsigned long long lo = s->collect_min;
         unsigned long long* out = cand + sid * DS_SORT_N;
-        for_each_valid(lg, ct, ctr_ld, ctr_off, K, segs.item0[seg], i0, i1, min_score, key_lo, kk_max, [&](int, unsigned long long ck) {
+        for_each_valid(lg, ct, ctr_ld, ctr_off, K, ld, segs.item0[seg], i0, i1, min_score, key_lo, kk_max, [&](int, unsigned long long ck) {
             if (ck >= lo) {
                 const int slot = atomicAdd(&s->n_slots, 1);
                 if (slot < DS_SORT_N) out[slot] = ck;       // (the scan bounds the count below SORT_N)
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(256) void det_select_pass_kernel(const bf16_raw* __
         const unsigned long long prefix = s->prefix;
         for (int q = threadIdx.x; q < DS_NBINS; q += 256) h[q] = 0u;
         __syncthreads();
-        for_each_valid(lg, ct, ctr_ld, ctr_off, K, segs.item0[seg], i0, i1, min_score, key_lo, kk_max, [&](int, unsigned long long ck) {
+        for_each_valid(lg, ct, ctr_ld, ctr_off, K, ld, segs.item0[seg], i0, i1, min_score, key_lo, kk_max, [&](int, unsigned long long ck) {
             if ((ck >> hi) == prefix) atomicAdd(&h[(unsigned int)(ck >> shift) & ((1u << w) - 1u)], 1u);
         });
         __syncthreads();
@@ -237,11 +241,14 @@ extern "C" size_t bd_det_select_workspace_bytes(int B, int L, int64_t rows, int 
     return sel_layout(nullptr, B, L).total;
 }
 
-extern "C" int bd_det_select(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
-                             const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
-                             float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream) {
+// logits [B][rows][ld], ld = K or round_up(K, 8) (the slots >= K of a row are padding and never selected); the indices are the compact
+// row * K + class of bd_det_select whatever ld is.  SelSegs.item0 / count / chunk0 walk the PADDED items (rows * ld < 2^31).
+extern "C" int bd_det_select_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
+                                const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
+                                float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream) {
     BD_REQUIRE(logits && seg_start_host && seg_rows_host && out_idx && out_score && out_cnt && ws, "det_select: null pointer");
-    BD_REQUIRE(B > 0 && L > 0 && L <= BD_MAX_SEGS && K > 0 && rows >= 0 && rows * K < (1ll << 31), "det_select: bad sizes");
+    BD_REQUIRE(K > 0 && (ld == K || (ld % 8 == 0 && ld > K && ld - K < 8)), "det_select: ld=%d must be K=%d or K rounded up to a multiple of 8", ld, K);
+    BD_REQUIRE(B > 0 && L > 0 && L <= BD_MAX_SEGS && rows >= 0 && rows * ld < (1ll << 31), "det_select: bad sizes");
     BD_REQUIRE(k > 0 && k <= DS_K_MAX, "det_select: k=%d out of range (1..%d)", k, DS_K_MAX);
     BD_REQUIRE(!ctr || (ctr_ld > 0 && ctr_off >= 0 && ctr_off < ctr_ld), "det_select: bad centerness layout");
     BD_REQUIRE(min_score == min_score, "det_select: min_score is NaN");
@@ -250,9 +257,10 @@ extern "C" int bd_det_select(const void* logits, const void* ctr, int ctr_ld, in
     for (int s = 0; s < L; ++s) {
         BD_REQUIRE(seg_start_host[s] >= 0 && seg_rows_host[s] >= 0 && (long long)seg_start_host[s] + seg_rows_host[s] <= rows,
                    "det_select: segment %d leaves the %lld rows", s, (long long)rows);
-        const long long c = (long long)seg_rows_host[s] * K;
-        BD_REQUIRE(c < (1ll << DS_IDX_BITS), "det_select: segment of %lld items is too long", c);
-        segs.item0[s] = (int)((long long)seg_start_host[s] * K);
+        BD_REQUIRE((long long)seg_rows_host[s] * K < (1ll << DS_IDX_BITS), "det_select: segment of %lld items is too long",
+                   (long long)seg_rows_host[s] * K);
+        const long long c = (long long)seg_rows_host[s] * ld;
+        segs.item0[s] = (int)((long long)seg_start_host[s] * ld);
         segs.count[s] = (int)c;
         segs.chunk0[s + 1] = segs.chunk0[s] + (int)cdiv64(c, DS_CHUNK);
     }
@@ -276,14 +284,21 @@ extern "C" int bd_det_select(const void* logits, const void* ctr, int ctr_ld, in
     const bf16_raw* ct = (const bf16_raw*)ctr;
     for (int p = 0; p < npass; ++p) {
         if (nchunk > 0)
-            hipLaunchKernelGGL(det_select_pass_kernel<false>, dim3(nchunk, B), dim3(256), 0, st, lg, ct, ctr_ld, ctr_off, (long long)rows, K,
+            hipLaunchKernelGGL(det_select_pass_kernel<false>, dim3(nchunk, B), dim3(256), 0, st, lg, ct, ctr_ld, ctr_off, (long long)rows, K, ld,
                                segs, min_score, key_lo, kk_max, T, p, w.st, w.hist, w.cand);
         hipLaunchKernelGGL(det_select_scan_kernel, dim3(B * L), dim3(1024), 0, st, w.st, w.hist, k, T, p);
     }
     if (nchunk > 0)
-        hipLaunchKernelGGL(det_select_pass_kernel<true>, dim3(nchunk, B), dim3(256), 0, st, lg, ct, ctr_ld, ctr_off, (long long)rows, K, segs,
+        hipLaunchKernelGGL(det_select_pass_kernel<true>, dim3(nchunk, B), dim3(256), 0, st, lg, ct, ctr_ld, ctr_off, (long long)rows, K, ld, segs,
                            min_score, key_lo, kk_max, T, 0, w.st, w.hist, w.cand);
     hipLaunchKernelGGL(det_select_sort_kernel, dim3(B * L), dim3(1024), 0, st, w.st, w.cand, k, key_lo, out_idx, out_score, out_cnt);
     BD_CHECK_LAUNCH("bd_det_select");
     return BD_OK;
+}
+
+extern "C" int bd_det_select(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
+                             const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
+                             float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream) {
+    return bd_det_select_ld(logits, K, ctr, ctr_ld, ctr_off, B, rows, K, L, seg_start_host, seg_rows_host, k, min_score, out_idx, out_score,
+                            out_cnt, ws, ws_bytes, stream);
 }

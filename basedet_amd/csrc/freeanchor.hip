@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void fa_maxiou_kernel(const bf16_raw* __restri
 }
 
 __global__ __launch_bounds__(1024) void fa_gt_kernel(const bf16_raw* __restrict__ logits, const bf16_raw* __restrict__ offsets,
-                                                     int box_ld, int apix, const float* __restrict__ anchors, int A, int K,
+                                                     int box_ld, int apix, const float* __restrict__ anchors, int A, int K, int ld,
                                                      const float* __restrict__ gt, const int* __restrict__ num_gt, int N, int Gmax,
                                                      Coder coder, float iou_thresh, int bucket, float beta, float reg_weight,
                                                      float alpha, const unsigned int* __restrict__ maxiou, float* __restrict__ thresh2,
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(1024) void fa_gt_kernel(const bf16_raw* __restrict_
     int a = 0;
     if (tid < m) {
         a = s_idx[tid];
-        score = sigmoidf_(bf2f(logits[((long long)n * A + a) * K + cls]));
+        score = sigmoidf_(bf2f(logits[((long long)n * A + a) * ld + cls]));
         const Box ab = ld_box(anchors + 4ll * a);
         const f32x4_t tgt = encode_dev(ab, gb, coder);
         const f32x4_t pr = ld_offsets(offsets, pix0, a, apix, box_ld);
@@ -273,7 +273,7 @@ __device__ __forceinline__ float fa_neg_elem(float x, float bpv, float gamma, fl
 }
 
 __global__ __launch_bounds__(256) void fa_neg_kernel(const bf16_raw* __restrict__ logits, const bf16_raw* __restrict__ offsets,
-                                                     int box_ld, int apix, const float* __restrict__ anchors, int A, int K,
+                                                     int box_ld, int apix, const float* __restrict__ anchors, int A, int K, int ld,
                                                      const float* __restrict__ gt, const int* __restrict__ num_gt, int N, int Gmax,
                                                      Coder coder, float iou_thresh, int bucket, float alpha, float gamma,
                                                      const float* __restrict__ thresh2, float* __restrict__ neg_part,
@@ -307,24 +307,37 @@ __global__ __launch_bounds__(256) void fa_neg_kernel(const bf16_raw* __restrict_
     const float nf = fmaxf(1.f, (float)total_fg(num_gt, N) * (float)bucket);
     const float scale = (1.f - alpha) / nf;
     float acc = 0.f;
-    const int nel = (A - a0 < FA_NEG_ANCH ? A - a0 : FA_NEG_ANCH) * K;
-    const long long e0 = ((long long)n * A + a0) * K;
+    const int nanch = A - a0 < FA_NEG_ANCH ? A - a0 : FA_NEG_ANCH;
+    const long long e0 = ((long long)n * A + a0) * ld;
     auto elem = [&](float x, float bpv, float& g) -> float { return fa_neg_elem(x, bpv, gamma, scale, g); };
-    if (K % 8 == 0) {           // 16-byte logit / gradient accesses (e0 is a multiple of 8)
-        for (int i = tid; i < nel / 8; i += 256) {
+    if (ld % 8 == 0) {          // 16-byte logit / gradient accesses (e0 is a multiple of 8); ld > K: the row's last vector ends in padding
+        const int kv = ld / 8;
+        for (int i = tid; i < nanch * kv; i += 256) {
+            const int la = i / kv, c0 = (i - la * kv) * 8;
+            const unsigned long long* bpr = bp + la * K + c0;
             const u32x4_t v = *reinterpret_cast<const u32x4_t*>(logits + e0 + 8ll * i);
             u32x4_t o;
+            if (c0 + 8 <= K) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float g0, g1;
-                acc += elem(bf_lo(v[j]), __uint_as_float((unsigned int)(bp[8 * i + 2 * j] & 0xffffffffull)), g0);
-                acc += elem(bf_hi(v[j]), __uint_as_float((unsigned int)(bp[8 * i + 2 * j + 1] & 0xffffffffull)), g1);
-                o[j] = pack_bf2(g0, g1);
+                for (int j = 0; j < 4; ++j) {
+                    float g0, g1;
+                    acc += elem(bf_lo(v[j]), __uint_as_float((unsigned int)(bpr[2 * j] & 0xffffffffull)), g0);
+                    acc += elem(bf_hi(v[j]), __uint_as_float((unsigned int)(bpr[2 * j + 1] & 0xffffffffull)), g1);
+                    o[j] = pack_bf2(g0, g1);
+                }
+            } else {            // pad slots: no loss, gradient +0
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float g0 = 0.f, g1 = 0.f;
+                    if (c0 + 2 * j < K) acc += elem(bf_lo(v[j]), __uint_as_float((unsigned int)(bpr[2 * j] & 0xffffffffull)), g0);
+                    if (c0 + 2 * j + 1 < K) acc += elem(bf_hi(v[j]), __uint_as_float((unsigned int)(bpr[2 * j + 1] & 0xffffffffull)), g1);
+                    o[j] = pack_bf2(g0, g1);
+                }
             }
             *reinterpret_cast<u32x4_t*>(d_logits + e0 + 8ll * i) = o;
         }
-    } else {
-        for (int i = tid; i < nel; i += 256) {
+    } else {                    // compact rows of any K (ld == K)
+        for (int i = tid; i < nanch * K; i += 256) {
             float g;
             acc += elem(bf2f(logits[e0 + i]), __uint_as_float((unsigned int)(bp[i] & 0xffffffffull)), g);
             d_logits[e0 + i] = f2bf(g);
@@ -352,7 +365,7 @@ __device__ __forceinline__ int fa_bag_find(const int* bi, int bucket, int a) {
 // cancel.  Here the thread of the FIRST bag entry on an anchor (d_offsets) or on an (anchor, class) (d_logits) looks the anchor up in
 // the later bags, sums in fp32 in gt order -- for d_logits starting from the negative-loss gradient, recomputed in fp32 exactly as
 // fa_neg_kernel does -- and stores the rounded sum: one writer per element, one rounding, a fixed order.
-__global__ __launch_bounds__(1024) void fa_apply_kernel(const int* __restrict__ num_gt, int N, int Gmax, int A, int K, int apix,
+__global__ __launch_bounds__(1024) void fa_apply_kernel(const int* __restrict__ num_gt, int N, int Gmax, int A, int K, int ld, int apix,
                                                         int box_ld, int bucket, const float* __restrict__ gt,
                                                         const int* __restrict__ bag_idx, const float* __restrict__ bag_grad,
                                                         const float* __restrict__ pos_loss, const float* __restrict__ neg_part,
@@ -402,7 +415,7 @@ __global__ __launch_bounds__(1024) void fa_apply_kernel(const int* __restrict__ 
                 const float prob = fminf(fmaxf((ov - iou_thresh) / (t2 - iou_thresh), 0.f), 1.f);
                 if (prob != 0.f) bpv = prob;
             }
-            (void)fa_neg_elem(bf2f(logits[((long long)n * A + a) * K + cls]), bpv, gamma, scale, sl);
+            (void)fa_neg_elem(bf2f(logits[((long long)n * A + a) * ld + cls]), bpv, gamma, scale, sl);
         }
         for (int h = g; h < G; ++h) {            // gt order; h == g is this entry itself
             const int j = h == g ? e - g * bucket : fa_bag_find(bi + h * bucket, bucket, a);
@@ -411,7 +424,7 @@ __global__ __launch_bounds__(1024) void fa_apply_kernel(const int* __restrict__ 
             if (first_ac && (int)gtn[h * 5 + 4] - 1 == cls) sl += gq[0];
             if (first_a) { s0 += gq[1]; s1 += gq[2]; s2 += gq[3]; s3 += gq[4]; }
         }
-        if (first_ac) d_logits[((long long)n * A + a) * K + cls] = f2bf(sl);
+        if (first_ac) d_logits[((long long)n * A + a) * ld + cls] = f2bf(sl);
         if (first_a) {
             bf16_raw* dp = d_offsets + ((long long)n * (A / apix) + a / apix) * box_ld + (a % apix) * 4;
             dp[0] = f2bf(s0); dp[1] = f2bf(s1); dp[2] = f2bf(s2); dp[3] = f2bf(s3);
@@ -445,13 +458,16 @@ extern "C" size_t bd_freeanchor_workspace_bytes(int N, int Gmax, int bucket, int
     return fa_layout(N, Gmax, bucket, A).total;
 }
 
-extern "C" int bd_freeanchor_loss_fwd_bwd(const void* logits, const void* offsets, int box_ld, int anchors_per_pix,
+// cls_ld: slots between the class rows of two anchors -- K (compact, any K) or K rounded up to a multiple of 8 (pad slots: no loss, +0 gradient)
+extern "C" int bd_freeanchor_loss_fwd_bwd_ld(const void* logits, int cls_ld, const void* offsets, int box_ld, int anchors_per_pix,
                                           const float* anchors, int A, int K, const float* gt, const int32_t* num_gt, int N,
                                           int Gmax, const float* mean4, const float* std4, float iou_thresh, int bucket,
                                           float beta, float reg_weight, float alpha, float gamma, float* loss_out,
                                           void* d_logits, void* d_offsets, void* ws, size_t ws_bytes, bd_stream_t stream) {
     BD_REQUIRE(logits && offsets && anchors && gt && num_gt && loss_out && d_logits && d_offsets && ws, "freeanchor: null pointer");
     BD_REQUIRE(N > 0 && Gmax > 0 && A > 0 && K > 0, "freeanchor: empty problem (N=%d Gmax=%d A=%d K=%d)", N, Gmax, A, K);
+    const int ld = cls_ld;
+    BD_REQUIRE(ld == K || (ld % 8 == 0 && ld > K && ld - K < 8), "freeanchor: cls_ld=%d must be K=%d or K rounded up to a multiple of 8", ld, K);
     BD_REQUIRE(bucket > 0 && bucket <= FA_MAX_BUCKET, "freeanchor: bucket=%d must be in 1..%d", bucket, FA_MAX_BUCKET);
     BD_REQUIRE(anchors_per_pix > 0 && A % anchors_per_pix == 0 && box_ld >= 4 * anchors_per_pix && box_ld % 4 == 0,
                "freeanchor: A=%d / anchors_per_pix=%d / box_ld=%d inconsistent", A, anchors_per_pix, box_ld);
@@ -473,16 +489,26 @@ extern "C" int bd_freeanchor_loss_fwd_bwd(const void* logits, const void* offset
     hipLaunchKernelGGL(fa_maxiou_kernel, dim3(cdiv(A, 256), N), dim3(256), 0, st, (const bf16_raw*)offsets, box_ld, anchors_per_pix, anchors, A,
                        gt, num_gt, Gmax, coder, maxiou);
     hipLaunchKernelGGL(fa_gt_kernel, dim3(Gmax, N), dim3(1024), 0, st, (const bf16_raw*)logits, (const bf16_raw*)offsets, box_ld,
-                       anchors_per_pix, anchors, A, K, gt, num_gt, N, Gmax, coder, iou_thresh, bucket, beta, reg_weight, alpha,
+                       anchors_per_pix, anchors, A, K, ld, gt, num_gt, N, Gmax, coder, iou_thresh, bucket, beta, reg_weight, alpha,
                        (const unsigned int*)maxiou, thresh2, bag_idx, bag_grad, pos_loss);
     hipLaunchKernelGGL(fa_neg_kernel, dim3(neg_blocks, N), dim3(256), (size_t)FA_NEG_ANCH * K * 8, st, (const bf16_raw*)logits,
-                       (const bf16_raw*)offsets, box_ld, anchors_per_pix, anchors, A, K, gt, num_gt, N, Gmax, coder, iou_thresh,
+                       (const bf16_raw*)offsets, box_ld, anchors_per_pix, anchors, A, K, ld, gt, num_gt, N, Gmax, coder, iou_thresh,
                        bucket, alpha, gamma, thresh2, neg_part, (bf16_raw*)d_logits);
     const size_t lists = sizeof(int) * (size_t)Gmax * bucket;          // the bag index lists of one image: through LDS up to 48 KB
     const int stage = lists <= 48 * 1024;
-    hipLaunchKernelGGL(fa_apply_kernel, dim3(N), dim3(1024), stage ? lists : 0, st, num_gt, N, Gmax, A, K, anchors_per_pix, box_ld, bucket,
+    hipLaunchKernelGGL(fa_apply_kernel, dim3(N), dim3(1024), stage ? lists : 0, st, num_gt, N, Gmax, A, K, ld, anchors_per_pix, box_ld, bucket,
                        gt, bag_idx, bag_grad, pos_loss, neg_part, neg_blocks, (const bf16_raw*)logits, (const bf16_raw*)offsets, anchors,
                        coder, iou_thresh, alpha, gamma, (const float*)thresh2, stage, (bf16_raw*)d_logits, (bf16_raw*)d_offsets, loss_out);
     BD_CHECK_LAUNCH("bd_freeanchor_loss_fwd_bwd");
     return BD_OK;
+}
+
+extern "C" int bd_freeanchor_loss_fwd_bwd(const void* logits, const void* offsets, int box_ld, int anchors_per_pix,
+                                          const float* anchors, int A, int K, const float* gt, const int32_t* num_gt, int N,
+                                          int Gmax, const float* mean4, const float* std4, float iou_thresh, int bucket,
+                                          float beta, float reg_weight, float alpha, float gamma, float* loss_out,
+                                          void* d_logits, void* d_offsets, void* ws, size_t ws_bytes, bd_stream_t stream) {
+    return bd_freeanchor_loss_fwd_bwd_ld(logits, K, offsets, box_ld, anchors_per_pix, anchors, A, K, gt, num_gt, N, Gmax, mean4, std4,
+                                         iou_thresh, bucket, beta, reg_weight, alpha, gamma, loss_out, d_logits, d_offsets, ws, ws_bytes,
+                                         stream);
 }

@@ -34,7 +34,7 @@ extern "C" const char* bd_last_error_string(void) { return g_bd_error.c_str(); }
 static thread_local const char* g_bd_last_kernel = "";
 void bd_note_kernel(const char* name) { g_bd_last_kernel = name; }
 extern "C" const char* bd_conv_last_kernel(void) { return g_bd_last_kernel; }
-extern "C" int bd_version(void) { return 103; }
+extern "C" int bd_version(void) { return 104; }
 
 namespace {
 
@@ -317,8 +317,11 @@ __global__ __launch_bounds__(256) void weight_pack_multi_kernel(const bd_pack_de
 // column sums (bias gradients), atomics-free and reproducible:
 // stage 1: block b sums rows b, b+nblocks*rif, ... into partial[b][C] (16-byte loads, LDS reduce over row lanes);
 // stage 2 sums the partials in block order.
+// One launch pair covers C <= COLSUM_CHUNK columns (one thread per 8 columns of a row); a wider tensor is summed chunk by chunk: g points at
+// the chunk's first column, ldg is the full row length.  A column's summation order does not depend on the chunking.
 constexpr int COLSUM_BLOCKS = 1024;
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_raw* __restrict__ g, long long rows, int C,
+constexpr int COLSUM_CHUNK = 2048;
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_raw* __restrict__ g, long long rows, int C, long long ldg,
                                                              long long cnt, long long ppi, long long off,
                                                              float* __restrict__ partial) {
     __shared__ float red[256 * 8];
@@ -330,7 +333,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_raw* __r
         for (long long r = (long long)blockIdx.x * rif + ty; r < rows; r += (long long)gridDim.x * rif) {
             const long long img = r / cnt;
             const long long row = img * ppi + off + (r - img * cnt);
-            const u32x4_t v = *reinterpret_cast<const u32x4_t*>(g + row * C + tx * 8);
+            const u32x4_t v = *reinterpret_cast<const u32x4_t*>(g + row * ldg + tx * 8);
 #pragma unroll
             for (int k = 0; k < 4; ++k) { acc[2 * k] += bf_lo(v[k]); acc[2 * k + 1] += bf_hi(v[k]); }
         }
@@ -493,15 +496,20 @@ extern "C" int bd_colsum_bf16(const void* g, int N, int64_t pix_per_img, int64_t
                               int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream) {
     BD_REQUIRE(g && out && ws && N >= 0 && cnt >= 0, "colsum: null pointer");
     const long long rows = (long long)N * cnt;
-    BD_REQUIRE(C > 0 && C % 8 == 0 && C <= 2048, "colsum: C=%d must be a multiple of 8 and <= 2048", C);
+    BD_REQUIRE(C > 0 && C % 8 == 0, "colsum: C=%d must be a multiple of 8", C);
     if (ws_bytes < bd_colsum_workspace_bytes(C)) {
         bd_set_error("colsum: workspace %zu < required %zu bytes", ws_bytes, bd_colsum_workspace_bytes(C));
         return BD_EWORKSPACE;
     }
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(COLSUM_BLOCKS), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)g,
-                       rows, C, (long long)(cnt > 0 ? cnt : 1), (long long)pix_per_img, (long long)off, (float*)ws);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(C, 8)), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
-                       COLSUM_BLOCKS, C, out, accumulate);
+    // chunk c0 keeps its partials at ws + COLSUM_BLOCKS * c0 floats ([block][chunk width]): the chunks' launches never share scratch
+    for (int c0 = 0; c0 < C; c0 += COLSUM_CHUNK) {
+        const int cc = C - c0 < COLSUM_CHUNK ? C - c0 : COLSUM_CHUNK;
+        float* part = (float*)ws + (size_t)COLSUM_BLOCKS * c0;
+        hipLaunchKernelGGL(colsum_partial_kernel, dim3(COLSUM_BLOCKS), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)g + c0,
+                           rows, cc, (long long)C, (long long)(cnt > 0 ? cnt : 1), (long long)pix_per_img, (long long)off, part);
+        hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(cc, 8)), dim3(256), 0, (hipStream_t)stream, (const float*)part,
+                           COLSUM_BLOCKS, cc, out + c0, accumulate);
+    }
     BD_CHECK_LAUNCH("bd_colsum_bf16");
     return BD_OK;
 }

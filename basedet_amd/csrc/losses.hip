@@ -86,15 +86,27 @@ __device__ __forceinline__ void focal_g2_neg2(float x0, float x1, float a, f32x2
     grad = aq2 * ((ce + ce) * (1.f - q) + q);
 }
 
+// zero the gradient slots >= nreal (0 <= nreal < 8) of a packed row tail: the padding behind the K classes of a row of ld = round_up(K, 8)
+__device__ __forceinline__ u32x4_t clear_pad_slots(u32x4_t o, int nreal) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (2 * k >= nreal) o[k] = 0u;
+        else if (2 * k + 1 >= nreal) o[k] &= 0xffffu;
+    }
+    return o;
+}
+
 // The 8 logits of a vector are treated as negatives; the (at most one) positive among them is recomputed in a rare branch.
+// Rows are ld = round_up(K, 8) slots apart: the last vector of a row holds K - (ld - 8) classes, its other slots are padding
+// (no loss, gradient +0).  ld == K: no vector has a tail.
 __global__ __launch_bounds__(256) void focal_g2_kernel(const bf16_raw* __restrict__ logits, const int* __restrict__ labels,
-                                                       long long rows, int K, float alpha, const void* norm, int norm_is_float,
+                                                       long long rows, int K, int ld, float alpha, const void* norm, int norm_is_float,
                                                        float grad_scale, float* __restrict__ partial, bf16_raw* __restrict__ dlogits) {
     __shared__ float red[4];
     const float inv_norm = 1.f / load_norm(norm, norm_is_float);
     const float gs = grad_scale * inv_norm;
     const float a_neg = alpha >= 0.f ? 1.f - alpha : 1.f, a_pos = alpha >= 0.f ? alpha : 1.f;
-    const int kv = K / 8;
+    const int kv = ld / 8;
     const long long nvec = rows * kv;
     float acc = 0.f;
     const long long stride = (long long)gridDim.x * 256;
@@ -125,12 +137,24 @@ __global__ __launch_bounds__(256) void focal_g2_kernel(const bf16_raw* __restric
             if (lab[u] >= 0) {
                 float g[8];
                 f32x2_l lsum = {0.f, 0.f};
+                const int nreal = K - c0[u];                    // classes in this vector: >= 8 but in a padded row's tail
+                if (nreal >= 8) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    f32x2_l l2, g2;
-                    focal_g2_neg2(bf_lo(v[u][k]), bf_hi(v[u][k]), a_neg, l2, g2);
-                    g[2 * k] = g2[0]; g[2 * k + 1] = g2[1];
-                    lsum += l2;
+                    for (int k = 0; k < 4; ++k) {
+                        f32x2_l l2, g2;
+                        focal_g2_neg2(bf_lo(v[u][k]), bf_hi(v[u][k]), a_neg, l2, g2);
+                        g[2 * k] = g2[0]; g[2 * k + 1] = g2[1];
+                        lsum += l2;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        f32x2_l l2, g2;
+                        focal_g2_neg2(bf_lo(v[u][k]), bf_hi(v[u][k]), a_neg, l2, g2);
+                        g[2 * k] = g2[0]; g[2 * k + 1] = g2[1];
+                        lsum[0] += 2 * k < nreal ? l2[0] : 0.f;
+                        lsum[1] += 2 * k + 1 < nreal ? l2[1] : 0.f;
+                    }
                 }
                 acc += lsum[0] + lsum[1];
                 const int pos = lab[u] - 1 - c0[u];
@@ -147,6 +171,7 @@ __global__ __launch_bounds__(256) void focal_g2_kernel(const bf16_raw* __restric
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) o[k] = pack_bf2(g[2 * k] * gs, g[2 * k + 1] * gs);
+                if (nreal < 8) o = clear_pad_slots(o, nreal);
             }
             *reinterpret_cast<u32x4_t*>(dlogits + (i + u * stride) * 8) = o;
         }
@@ -156,13 +181,13 @@ __global__ __launch_bounds__(256) void focal_g2_kernel(const bf16_raw* __restric
 }
 
 __global__ __launch_bounds__(256) void focal_kernel(const bf16_raw* __restrict__ logits, const int* __restrict__ labels,
-                                                    long long rows, int K, float alpha, float gamma, const void* norm,
+                                                    long long rows, int K, int ld, float alpha, float gamma, const void* norm,
                                                     int norm_is_float, float grad_scale, float* __restrict__ partial,
                                                     bf16_raw* __restrict__ dlogits) {
     __shared__ float red[4];
     const float inv_norm = 1.f / load_norm(norm, norm_is_float);
     const float gs = grad_scale * inv_norm;
-    const int kv = K / 8;
+    const int kv = ld / 8;
     const long long nvec = rows * kv;
     float acc = 0.f;
     // (row, chunk) of vector i advance by a fixed (quotient, remainder) per grid stride: one 64-bit division per thread instead of
@@ -181,13 +206,26 @@ __global__ __launch_bounds__(256) void focal_kernel(const bf16_raw* __restrict__
         u32x4_t o = {0u, 0u, 0u, 0u};
         if (lab >= 0) {
             const u32x4_t v = *reinterpret_cast<const u32x4_t*>(logits + i * 8);
+            const int nreal = K - c0;                           // < 8 only in the tail vector of a padded row (see focal_g2_kernel)
+            if (nreal >= 8) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float l0, g0, l1, g1;
-                focal_elem(bf_lo(v[k]), lab - 1 == c0 + 2 * k, alpha, gamma, l0, g0);
-                focal_elem(bf_hi(v[k]), lab - 1 == c0 + 2 * k + 1, alpha, gamma, l1, g1);
-                acc += l0 + l1;
-                o[k] = pack_bf2(g0 * gs, g1 * gs);
+                for (int k = 0; k < 4; ++k) {
+                    float l0, g0, l1, g1;
+                    focal_elem(bf_lo(v[k]), lab - 1 == c0 + 2 * k, alpha, gamma, l0, g0);
+                    focal_elem(bf_hi(v[k]), lab - 1 == c0 + 2 * k + 1, alpha, gamma, l1, g1);
+                    acc += l0 + l1;
+                    o[k] = pack_bf2(g0 * gs, g1 * gs);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float l0, g0, l1, g1;
+                    focal_elem(bf_lo(v[k]), lab - 1 == c0 + 2 * k, alpha, gamma, l0, g0);
+                    focal_elem(bf_hi(v[k]), lab - 1 == c0 + 2 * k + 1, alpha, gamma, l1, g1);
+                    acc += (2 * k < nreal ? l0 : 0.f) + (2 * k + 1 < nreal ? l1 : 0.f);
+                    o[k] = pack_bf2(g0 * gs, g1 * gs);
+                }
+                o = clear_pad_slots(o, nreal);
             }
         }
         *reinterpret_cast<u32x4_t*>(dlogits + i * 8) = o;
@@ -495,20 +533,20 @@ static void loss_finalize(const float* partial, int n, int slots, float* loss, b
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, n, slots, loss);
 }
 
-static int focal_launch(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha, float gamma, const void* norm,
+static int focal_launch(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma, const void* norm,
                         int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, bool general, bd_stream_t stream) {
     BD_REQUIRE(logits && labels && norm && loss_sum && dlogits, "focal_loss: null pointer");
-    BD_REQUIRE(K > 0 && K % 8 == 0, "focal_loss: K=%d must be a multiple of 8", K);
+    BD_REQUIRE(K > 0 && ld % 8 == 0 && ld >= K && ld - K < 8, "focal_loss: the row stride ld=%d must be K=%d rounded up to a multiple of 8", ld, K);
     if (rows == 0) return BD_OK;
-    const int grid = loss_grid(rows * (K / 8));
+    const int grid = loss_grid(rows * (ld / 8));
     BD_LOSS_PARTIALS(part, stream, grid, "focal_loss");
     if (gamma == 2.f && !general)
         hipLaunchKernelGGL(focal_g2_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_raw*)logits, labels, (long long)rows, K, alpha, norm, norm_is_float, grad_scale, part,
+                           (const bf16_raw*)logits, labels, (long long)rows, K, ld, alpha, norm, norm_is_float, grad_scale, part,
                            (bf16_raw*)dlogits);
     else
         hipLaunchKernelGGL(focal_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_raw*)logits, labels, (long long)rows, K, alpha, gamma, norm, norm_is_float, grad_scale,
+                           (const bf16_raw*)logits, labels, (long long)rows, K, ld, alpha, gamma, norm, norm_is_float, grad_scale,
                            part, (bf16_raw*)dlogits);
     loss_finalize(part, grid, 1, loss_sum, stream);
     BD_CHECK_LAUNCH("bd_focal_loss_fwd_bwd");
@@ -518,14 +556,24 @@ static int focal_launch(const void* logits, const int32_t* labels, int64_t rows,
 extern "C" int bd_focal_loss_fwd_bwd(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha, float gamma,
                                      const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits,
                                      bd_stream_t stream) {
-    return focal_launch(logits, labels, rows, K, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, false, stream);
+    BD_REQUIRE(K > 0 && K % 8 == 0, "focal_loss: K=%d must be a multiple of 8 (bd_focal_loss_fwd_bwd_ld takes any K)", K);
+    return focal_launch(logits, labels, rows, K, K, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, false, stream);
+}
+
+// any class count: rows of ld = round_up(K, 8) slots, the first K the classes, the rest padding (no loss, gradient +0).  general != 0:
+// the general-gamma kernel whatever gamma is.  ld == K is bd_focal_loss_fwd_bwd / _general, bit for bit.
+extern "C" int bd_focal_loss_fwd_bwd_ld(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma,
+                                        const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, int general,
+                                        bd_stream_t stream) {
+    return focal_launch(logits, labels, rows, K, ld, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, general != 0, stream);
 }
 
 // the general-gamma kernel whatever gamma is (the gamma == 2 instance of bd_focal_loss_fwd_bwd is checked against it)
 extern "C" int bd_focal_loss_fwd_bwd_general(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha, float gamma,
                                              const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits,
                                              bd_stream_t stream) {
-    return focal_launch(logits, labels, rows, K, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, true, stream);
+    BD_REQUIRE(K > 0 && K % 8 == 0, "focal_loss: K=%d must be a multiple of 8 (bd_focal_loss_fwd_bwd_ld takes any K)", K);
+    return focal_launch(logits, labels, rows, K, K, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, true, stream);
 }
 
 extern "C" int bd_smooth_l1_fwd_bwd(const void* pred, const float* target, const int32_t* labels, int64_t pixels, int A,

@@ -46,7 +46,7 @@ __device__ __forceinline__ float ltrb_iou_dev(const f32x4_t p, const f32x4_t t, 
 
 struct OtaIn {
     const float* points; const bf16_raw* logits; const bf16_raw* offsets; const float* sbg;
-    int P, K; float alpha, gamma, reg_w;
+    int P, ld; float alpha, gamma, reg_w;        // ld: slots between the class rows of two points (K, or K rounded up to a multiple of 8)
 };
 
 __device__ __forceinline__ f32x4_t ld_pred(const bf16_raw* offsets, long long row) {
@@ -66,24 +66,34 @@ __device__ __forceinline__ void ota_pair(const OtaIn& in, long long row, int p, 
     const bool in_ctr = fminf(fminf(px - c1x, py - c1y), fminf(c2x - px, c2y - py)) > 0.f;     // ota.py:98-113
     iou = ltrb_iou_dev(ld_pred(in.offsets, row), delta, FLT_EPSILON);
     const float loss_delta = -logf(fmaxf(iou, FLT_EPSILON));                                    // iou_loss(loss_type="iou") (:97-98)
-    const float xc = bf2f(in.logits[row * in.K + cls]);
+    const float xc = bf2f(in.logits[row * in.ld + cls]);
     const float cls_cost = (in.sbg[row] - focal_value(xc, false, in.alpha, in.gamma)) + focal_value(xc, true, in.alpha, in.gamma);
     cost = (cls_cost + in.reg_w * loss_delta) + ((in_box && in_ctr) ? 0.f : 1e6f);            // ota.py:151
     if (inside) *inside = in_box && in_ctr;
 }
 
-__global__ __launch_bounds__(256) void ota_prep_kernel(const bf16_raw* __restrict__ logits, long long rows, int K, float alpha,
+// (rows of ld = round_up(K, 8) slots: the slots >= K of the last vector are padding and add nothing to the background sum)
+__global__ __launch_bounds__(256) void ota_prep_kernel(const bf16_raw* __restrict__ logits, long long rows, int K, int ld, float alpha,
                                                        float gamma, float* __restrict__ sbg, int* __restrict__ cnt,
                                                        int* __restrict__ gsel) {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
     float s = 0.f;
-    for (int k = 0; k < K; k += 8) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(logits + r * K + k);
+    int k = 0;
+    for (; k + 8 <= K; k += 8) {
+        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(logits + r * ld + k);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             s += focal_value(bf_lo(v[j]), false, alpha, gamma);
             s += focal_value(bf_hi(v[j]), false, alpha, gamma);
+        }
+    }
+    if (k < K) {
+        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(logits + r * ld + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (k + 2 * j < K) s += focal_value(bf_lo(v[j]), false, alpha, gamma);
+            if (k + 2 * j + 1 < K) s += focal_value(bf_hi(v[j]), false, alpha, gamma);
         }
     }
     sbg[r] = s; cnt[r] = 0; gsel[r] = 0;
@@ -356,14 +366,15 @@ extern "C" size_t bd_ota_sinkhorn_workspace_bytes(int N, int P, int Gmax) {
     return (size_t)N * P * 8 + (size_t)N * (Gmax + 1) * P * 4 + (size_t)N * (Gmax + 1) * 4 + 1024;
 }
 
-extern "C" int bd_ota_assign_sinkhorn(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L,
-                                      const void* logits, int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N,
+extern "C" int bd_ota_assign_sinkhorn_ld(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L,
+                                      const void* logits, int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N,
                                       int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps,
                                       int iters, int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
                                       bd_stream_t stream) {
     BD_REQUIRE(points && lvl_start && strides && logits && pred_ltrb && gt_boxes && num_gt && labels && targets && gt_ious && stats && ws,
                "ota_assign_sinkhorn: null pointer");
-    BD_REQUIRE(L >= 1 && L <= BD_MAX_SEGS && P > 0 && N > 0 && Gmax > 0 && K > 0 && K % 8 == 0, "ota_assign_sinkhorn: bad sizes");
+    BD_REQUIRE(L >= 1 && L <= BD_MAX_SEGS && P > 0 && N > 0 && Gmax > 0 && K > 0, "ota_assign_sinkhorn: bad sizes");
+    BD_REQUIRE(ld % 8 == 0 && ld >= K && ld - K < 8, "ota_assign_sinkhorn: ld=%d must be K=%d rounded up to a multiple of 8", ld, K);
     BD_REQUIRE(Gmax + 1 <= SK_MAX_ROWS, "ota_assign_sinkhorn: %d gt slots exceed %d", Gmax, SK_MAX_ROWS - 1);
     BD_REQUIRE(topq >= 1 && topq <= OTA_MAX_K && eps > 0.f && iters >= 1, "ota_assign_sinkhorn: bad matcher parameters");
     if (ws_bytes < bd_ota_sinkhorn_workspace_bytes(N, P, Gmax)) {
@@ -380,11 +391,11 @@ extern "C" int bd_ota_assign_sinkhorn(const float* points, int P, const int32_t*
     float* vbuf = (float*)(wb + rows * 4);
     float* cost = (float*)(wb + rows * 8);
     float* mu = (float*)(wb + rows * 8 + (size_t)N * (Gmax + 1) * P * 4);
-    OtaIn in{points, (const bf16_raw*)logits, (const bf16_raw*)pred_ltrb, sbg, P, K, alpha, gamma, reg_weight};
+    OtaIn in{points, (const bf16_raw*)logits, (const bf16_raw*)pred_ltrb, sbg, P, ld, alpha, gamma, reg_weight};
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(stats, 0, 2 * sizeof(float), st);
     // the prep kernel also zeroes two int vectors of `rows` entries: point them at the v buffer and the first cost row
-    hipLaunchKernelGGL(ota_prep_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, (const bf16_raw*)logits, rows, K, alpha, gamma,
+    hipLaunchKernelGGL(ota_prep_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, (const bf16_raw*)logits, rows, K, ld, alpha, gamma,
                        sbg, (int*)vbuf, (int*)vbuf);
     hipLaunchKernelGGL(ota_sk_rows_kernel, dim3(Gmax, N), dim3(1024), 0, st, in, lv, gt_boxes, num_gt, Gmax, topq, cost, mu);
     hipLaunchKernelGGL(ota_sinkhorn_kernel, dim3(N), dim3(1024), 0, st, in, lv, gt_boxes, num_gt, Gmax, eps, iters, cost, mu, vbuf, labels,
@@ -398,13 +409,14 @@ extern "C" size_t bd_ota_assign_workspace_bytes(int N, int P) {
     return (size_t)N * P * 12 + 256;
 }
 
-extern "C" int bd_ota_assign(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L, const void* logits,
-                             int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
+extern "C" int bd_ota_assign_ld(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L, const void* logits,
+                             int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
                              float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
                              float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream) {
     BD_REQUIRE(points && lvl_start && strides && logits && pred_ltrb && gt_boxes && num_gt && labels && targets && gt_ious && stats && ws,
                "ota_assign: null pointer");
-    BD_REQUIRE(L >= 1 && L <= BD_MAX_SEGS && P > 0 && N > 0 && Gmax > 0 && K > 0 && K % 8 == 0, "ota_assign: bad sizes");
+    BD_REQUIRE(L >= 1 && L <= BD_MAX_SEGS && P > 0 && N > 0 && Gmax > 0 && K > 0, "ota_assign: bad sizes");
+    BD_REQUIRE(ld % 8 == 0 && ld >= K && ld - K < 8, "ota_assign: ld=%d must be K=%d rounded up to a multiple of 8", ld, K);
     BD_REQUIRE(candidate_k >= 1 && candidate_k <= OTA_MAX_K, "ota_assign: candidate_k=%d must be in 1..%d", candidate_k, OTA_MAX_K);
     if (ws_bytes < bd_ota_assign_workspace_bytes(N, P)) {
         bd_set_error("ota_assign: workspace %zu < %zu bytes", ws_bytes, bd_ota_assign_workspace_bytes(N, P));
@@ -418,14 +430,34 @@ extern "C" int bd_ota_assign(const float* points, int P, const int32_t* lvl_star
     float* sbg = (float*)ws;
     int* cnt = (int*)((unsigned char*)ws + rows * 4);
     int* gsel = (int*)((unsigned char*)ws + rows * 8);
-    OtaIn in{points, (const bf16_raw*)logits, (const bf16_raw*)pred_ltrb, sbg, P, K, alpha, gamma, reg_weight};
+    OtaIn in{points, (const bf16_raw*)logits, (const bf16_raw*)pred_ltrb, sbg, P, ld, alpha, gamma, reg_weight};
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(stats, 0, 2 * sizeof(float), st);
-    hipLaunchKernelGGL(ota_prep_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, (const bf16_raw*)logits, rows, K, alpha, gamma,
+    hipLaunchKernelGGL(ota_prep_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, (const bf16_raw*)logits, rows, K, ld, alpha, gamma,
                        sbg, cnt, gsel);
     hipLaunchKernelGGL(ota_gt_kernel, dim3(Gmax, N), dim3(1024), 0, st, in, lv, gt_boxes, num_gt, Gmax, candidate_k, cnt, gsel);
     hipLaunchKernelGGL(ota_resolve_kernel, dim3(cdiv(P, 256), N), dim3(256), 0, st, in, lv, gt_boxes, num_gt, Gmax, cnt, gsel, labels,
                        targets, gt_ious, stats);
     BD_CHECK_LAUNCH("bd_ota_assign");
     return BD_OK;
+}
+
+// the entry points without a row stride: compact [N * P][K] logits, K a multiple of 8
+extern "C" int bd_ota_assign_sinkhorn(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L,
+                                      const void* logits, int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N,
+                                      int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps,
+                                      int iters, int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
+                                      bd_stream_t stream) {
+    BD_REQUIRE(K > 0 && K % 8 == 0, "ota_assign_sinkhorn: K=%d must be a multiple of 8 (bd_ota_assign_sinkhorn_ld takes any K)", K);
+    return bd_ota_assign_sinkhorn_ld(points, P, lvl_start, strides, L, logits, K, K, pred_ltrb, gt_boxes, num_gt, N, Gmax, alpha, gamma,
+                                     reg_weight, center_radius, topq, eps, iters, labels, targets, gt_ious, stats, ws, ws_bytes, stream);
+}
+
+extern "C" int bd_ota_assign(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L, const void* logits,
+                             int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
+                             float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
+                             float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream) {
+    BD_REQUIRE(K > 0 && K % 8 == 0, "ota_assign: K=%d must be a multiple of 8 (bd_ota_assign_ld takes any K)", K);
+    return bd_ota_assign_ld(points, P, lvl_start, strides, L, logits, K, K, pred_ltrb, gt_boxes, num_gt, N, Gmax, alpha, gamma, reg_weight,
+                            center_radius, candidate_k, labels, targets, gt_ious, stats, ws, ws_bytes, stream);
 }

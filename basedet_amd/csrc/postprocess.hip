@@ -9,13 +9,16 @@ namespace {
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
-// scores[r*K + k] = sigmoid(logit)  or  sqrt(sigmoid(logit) * sigmoid(ctr[r]))   (fcos.py:194)
-__global__ __launch_bounds__(256) void det_scores_kernel(const bf16_raw* __restrict__ logits, const bf16_raw* __restrict__ ctr,
+// scores[r*K + k] = sigmoid(logit)  or  sqrt(sigmoid(logit) * sigmoid(ctr[r]))   (fcos.py:194); logits [rows][ld], ld >= K: the slots
+// behind a row's K classes are padding and get no score (the output is the compact [rows][K]; ld != K pays a 64-bit division per element
+// for the row, which this single-image reference chain can afford: the batched path is bd_det_select_ld)
+__global__ __launch_bounds__(256) void det_scores_kernel(const bf16_raw* __restrict__ logits, int ld, const bf16_raw* __restrict__ ctr,
                                                          int ctr_ld, int ctr_off, long long rows, int K, float* __restrict__ scores) {
     const long long total = rows * K;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        float s = sigmoid_f(bf2f(logits[i]));
-        if (ctr) s = sqrtf(s * sigmoid_f(bf2f(ctr[(i / K) * ctr_ld + ctr_off])));
+        const long long r = (ctr || ld != K) ? i / K : 0;
+        float s = sigmoid_f(bf2f(logits[ld == K ? i : r * ld + (i - r * K)]));
+        if (ctr) s = sqrtf(s * sigmoid_f(bf2f(ctr[r * ctr_ld + ctr_off])));
         scores[i] = s;
     }
 }
@@ -128,16 +131,22 @@ __global__ __launch_bounds__(256) void det_finalize_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" int bd_det_scores(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
-                             bd_stream_t stream) {
+extern "C" int bd_det_scores_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
+                                bd_stream_t stream) {
     BD_REQUIRE(logits && scores && K > 0 && rows >= 0, "det_scores: bad arguments");
+    BD_REQUIRE(ld == K || (ld % 8 == 0 && ld > K && ld - K < 8), "det_scores: ld=%d must be K=%d or K rounded up to a multiple of 8", ld, K);
     if (rows == 0) return BD_OK;
     long long g = cdiv64(rows * K, 256);
     if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(det_scores_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)logits,
+    hipLaunchKernelGGL(det_scores_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)logits, ld,
                        (const bf16_raw*)ctr, ctr_ld, ctr_off, (long long)rows, K, scores);
     BD_CHECK_LAUNCH("bd_det_scores");
     return BD_OK;
+}
+
+extern "C" int bd_det_scores(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
+                             bd_stream_t stream) {
+    return bd_det_scores_ld(logits, K, ctr, ctr_ld, ctr_off, rows, K, scores, stream);
 }
 
 extern "C" int bd_rcnn_predict(const void* raw, int ld, int K, int box_off, const float* rois, const int32_t* num_rois,

@@ -128,6 +128,23 @@ def _store(dst, geom, grads, C):
         v[:, geom.off[i]: geom.off[i] + g.shape[2] * g.shape[3], :C] = g.permute(0, 2, 3, 1).reshape(N, -1, C).to(dst.dtype)
 
 
+def _real_classes(conv, t):
+    """NCHW logits with the class predictor's A * cls_ld channels -> the reference's A * K (PaddedClsConv; the identity for K % 8 == 0)."""
+    if conv.cls_ld == conv.K:
+        return t
+    return conv.real_logits(t.permute(0, 2, 3, 1)).permute(0, 3, 1, 2).contiguous()
+
+
+def _pad_classes(conv, g):
+    """The inverse for a gradient: NCHW (N, A * K, H, W) -> (N, A * cls_ld, H, W) with zero pad slots."""
+    if conv.cls_ld == conv.K:
+        return g
+    N, _, H, W = g.shape
+    out = g.new_zeros((N, conv.A, conv.cls_ld, H, W))
+    out[:, :, : conv.K] = g.reshape(N, conv.A, conv.K, H, W)
+    return out.reshape(N, conv.A * conv.cls_ld, H, W)
+
+
 class _HeadBackward:
     def _finish(self, pl):
         m = self.model
@@ -152,7 +169,7 @@ class RetinaNetHead(_Head, _HeadBackward):
         m.head_forward(pl)
         n = pl.pyr.nlev
         self._pl = pl
-        return ([_level(pl.logits, pl.pyr, i) for i in range(n)],
+        return ([_real_classes(m.cls_score, _level(pl.logits, pl.pyr, i)) for i in range(n)],
                 [_level(pl.offsets, pl.pyr, i, m.num_anchors * 4) for i in range(n)])
 
     def backward(self, d_logits, d_offsets):
@@ -160,7 +177,8 @@ class RetinaNetHead(_Head, _HeadBackward):
         pl, m = self._pl, self.model
         m._cur = pl
         m._begin_wgrads()
-        _store(pl.d_logits, pl.pyr, d_logits, m.num_anchors * m.num_classes)
+        assert all(g.shape[1] == m.num_anchors * m.num_classes for g in d_logits), "gradient shapes must match the forward outputs"
+        _store(pl.d_logits, pl.pyr, [_pad_classes(m.cls_score, g) for g in d_logits], m.num_anchors * m.cls_ld)
         _store(pl.d_offsets, pl.pyr, d_offsets, m.num_anchors * 4)
         m.head_backward(pl, pl.wgrad_ws, pl.colsum_ws)
         return self._finish(pl)
@@ -179,7 +197,7 @@ class PointHead(_Head, _HeadBackward):
         pl = self._load(features)
         self.model.head_forward(pl)
         n = pl.pyr.nlev
-        logits = [_level(pl.logits, pl.pyr, i) for i in range(n)]
+        logits = [_level(pl.logits, pl.pyr, i, self.model.num_classes) for i in range(n)]
         offsets = [_level(pl.offsets, pl.pyr, i, 4) for i in range(n)]
         ctr = [_level(pl.raw, pl.pyr, i)[:, 4:5].contiguous() for i in range(n)]
         self._pl = pl

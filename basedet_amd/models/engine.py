@@ -346,6 +346,71 @@ class FusedPredConv(ConvLayer):
             o += c
 
 
+def cls_ld(K):
+    """Slots one anchor's class logits occupy: K rounded up to a multiple of 8 (16-byte rows of bf16)."""
+    return (int(K) + 7) // 8 * 8
+
+
+def pad_class_rows(a, A, K):
+    """Reference rows (A*K, ...) (row a*K + k, retina_head.py:66 / point_head.py:88) -> A groups of cls_ld(K) rows, the pad rows zero."""
+    ld = cls_ld(K)
+    a = np.asarray(a)
+    assert a.shape[0] == A * K, (a.shape, A, K)
+    if ld == K:
+        return a
+    out = np.zeros((A, ld) + a.shape[1:], a.dtype)
+    out[:, :K] = a.reshape((A, K) + a.shape[1:])
+    return out.reshape((A * ld,) + a.shape[1:])
+
+
+def unpad_class_rows(a, A, K):
+    """The inverse gather, (A*cls_ld(K), ...) -> (A*K, ...); numpy arrays and torch tensors alike."""
+    ld = cls_ld(K)
+    assert a.shape[0] == A * ld, (a.shape, A, K)
+    if ld == K:
+        return a
+    return a.reshape((A, ld) + tuple(a.shape[1:]))[:, :K].reshape((A * K,) + tuple(a.shape[1:]))
+
+
+class PaddedClsConv(ConvLayer):
+    """The class predictor of a one-stage head (head.cls_score) at any class count: the reference's A*K output channels (anchor-major)
+    are kept as A groups of cls_ld = round_up(K, 8) rows, so that every anchor's K logits start on a 16-byte boundary of the
+    [pixels][A * cls_ld] bf16 output.  bind scatters the reference's (A*K, Cin, k, k) weight and (A*K,) bias into the groups; export and
+    export_grad gather back: checkpoints, state_dict, reference_grads and the EMA keep the reference's names and shapes.  K % 8 == 0: the
+    mapping is the identity and this is a plain ConvLayer.
+
+    INVARIANT: the pad rows of the weight, the bias, their gradients and the momentum are exactly zero for a whole run.  bind zeroes
+    them; every loss writes a zero gradient into the pad slots of d_logits (bd_focal_loss_fwd_bwd_ld, bd_freeanchor_loss_fwd_bwd_ld), so
+    the weight and bias gradients of the pad rows are sums of zeros; SGD with momentum and weight decay, gradient clipping, the EMA and
+    the gradient all-reduce map zero to zero.  tests/test_class_count_gpu.py::test_pad_rows_stay_zero holds this."""
+
+    def __init__(self, name, cin, A, K, k, stride, pad, device):
+        self.A, self.K, self.cls_ld = int(A), int(K), cls_ld(K)
+        super().__init__(name, cin, self.A * self.K, k, stride, pad, device, has_bias=True, trainable=True, cout_pad=self.A * self.cls_ld)
+
+    def bind(self, arena, params):
+        w = pad_class_rows(np.asarray(params[self.name + ".weight"], np.float32), self.A, self.K)
+        b = pad_class_rows(np.asarray(params[self.name + ".bias"], np.float32), self.A, self.K)
+        self.w = arena.view("w", self._wi); self.gw = arena.view("g", self._wi)
+        self.w.copy_(torch.from_numpy(w).permute(0, 2, 3, 1).contiguous())             # OIHW -> OHWI
+        self.b = arena.view("w", self._bi); self.gb = arena.view("g", self._bi)
+        self.b.copy_(torch.from_numpy(b))
+
+    def export(self, out):
+        out[self.name + ".weight"] = unpad_class_rows(self.w, self.A, self.K).permute(0, 3, 1, 2).contiguous().cpu().numpy()
+        out[self.name + ".bias"] = unpad_class_rows(self.b, self.A, self.K).cpu().numpy().copy()
+
+    def export_grad(self, out):
+        out[self.name + ".weight"] = unpad_class_rows(self.gw, self.A, self.K).permute(0, 3, 1, 2).contiguous().cpu()
+        out[self.name + ".bias"] = unpad_class_rows(self.gb, self.A, self.K).cpu().clone()
+
+    def real_logits(self, t):
+        """[..., A * cls_ld] predictions or gradients -> the real class slots, [..., A * K]."""
+        if self.cls_ld == self.K:
+            return t
+        return t.reshape(tuple(t.shape[:-1]) + (self.A, self.cls_ld))[..., : self.K].reshape(tuple(t.shape[:-1]) + (self.A * self.K,))
+
+
 class FCLayer(ConvLayer):
     """megengine.module.Linear (or several that read the same input, fused along the output dimension) as a 1x1 convolution
     whose "pixels" are the rows.  The reference flattens RoI features as (c, h, w) (layers/head/rcnn.py:59); the HIP

@@ -12,7 +12,7 @@ from .. import ops
 from ..streams import fork, join
 from ..utils.registry import registers
 from . import params as P
-from .engine import FusedPredConv
+from .engine import FusedPredConv, PaddedClsConv
 from .fpn_base import FPNDetector, VecParam
 
 GN_EPS = 1e-5   # megengine.module.normalization.GroupNorm default
@@ -45,7 +45,9 @@ class FCOS(FPNDetector):
                 self.vparams[b.name] = b
                 gammas.append(g); betas.append(b)
             self.towers[tower] = (convs, gammas, betas)
-        self.cls_score = add("head.cls_score", ch, self.num_classes, 3, 1, 1, bias=True)
+        # cls_ld = round_up(K, 8) channels (the identity for K % 8 == 0): any class count
+        self.cls_score = self.convs["head.cls_score"] = PaddedClsConv("head.cls_score", ch, 1, self.num_classes, 3, 1, 1, self.device)
+        self.cls_ld = self.cls_score.cls_ld
         # bbox_pred (4) and ctrness (1) read the same tower output: one conv with 5 (padded to 8) output channels
         self.pred = FusedPredConv("head.bbox_ctr", [("head.bbox_pred", 4), ("head.ctrness", 1)], ch, 3, 1, 1, self.device, cout_pad=8)
         self.convs[self.pred.name] = self.pred
@@ -71,7 +73,7 @@ class FCOS(FPNDetector):
         for tower in self.towers:
             pl.tw[tower] = dict(y=[act(ch) for _ in range(nc)], z=[act(ch) for _ in range(nc)],
                                 stats=[C.empty((N, L, 32, 2), f32) for _ in range(nc)])
-        pl.logits = act(self.num_classes)
+        pl.logits = act(self.cls_ld)                    # (pad slots K..cls_ld-1: zero weight rows and bias -> logit 0; zero gradient)
         pl.raw = act(8)                                 # (channels 5..7: zero weight rows and bias -- written as 0 by every forward)
         pl.offsets = act(4)
         pl.d_logits = C.like(pl.logits)
@@ -148,12 +150,16 @@ class FCOS(FPNDetector):
         rows = pl.N * pl.pyr.pix_per_img
         assert m.LOSSES.IOU_LOSS_TYPE == "giou", "HIP FCOS path implements the giou ltrb loss"
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA,
-                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits)
+                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self._ld())
         ops.giou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, pl.gt_ctr, pl.labels, rows, pl.stats[1:2], m.LOSSES.REG_LOSS_WEIGHT,
                               pl.loss_buf[1:2], pl.d_off)
         ops.bce_logits_fwd_bwd(pl.raw, pl.gt_ctr, pl.labels, rows, pl.stats[0:1], pl.loss_buf[2:3], pl.d_ctr, ld=8, off=4)
         cls_loss, reg_loss, ctr_loss = pl.loss_buf[0], pl.loss_buf[1], pl.loss_buf[2]
         return {"total_loss": cls_loss + reg_loss + ctr_loss, "cls_loss": cls_loss, "reg_loss": reg_loss, "ctr_loss": ctr_loss}
+
+    def _ld(self):
+        """The class stride for the ops that take one: None (the compact entry points) when K is a multiple of 8."""
+        return self.cls_ld if self.cls_ld != self.num_classes else None
 
     @staticmethod
     def _allreduce_stats(c, stats):
@@ -198,7 +204,7 @@ class FCOS(FPNDetector):
                 for k in range(len(self.towers[tower][0])):
                     out[f"{tag}y{k}_{i}"] = lvl(pl.tw[tower]["y"][k], i)
                     out[f"{tag}{k}_{i}"] = lvl(pl.tw[tower]["z"][k], i)
-            out[f"logits_{i}"] = lvl(pl.logits, i)
+            out[f"logits_{i}"] = lvl(pl.logits, i, self.num_classes)
             out[f"raw_{i}"] = lvl(pl.raw, i, 5)
 
     def inference_batch(self, inputs):
@@ -210,7 +216,7 @@ class FCOS(FPNDetector):
         self.network_forward(pl)
         K = self.num_classes
         return self._detect(pl.N, [h * w for h, w in pl.sizes], K, 1, pre["img_info"], logits=pl.logits, ctr=pl.raw, ctr_ld=8, ctr_off=4,
-                            anchors=pl.points, offsets=pl.offsets, off_ld=4, A=1)
+                            anchors=pl.points, offsets=pl.offsets, off_ld=4, A=1, cls_ld=self.cls_ld)
 
 
 @registers.models.register()
@@ -255,11 +261,11 @@ class OTA(FCOS):
             ws = pl.ota_ws if pl.ota_ws.numel() >= need else self._scratch("ota_sinkhorn", need)
             ops.ota_assign_sinkhorn(pl.points, pl.lvl_start, self.strides, pl.logits, self.num_classes, pl.offsets, gt, num_gt,
                                     m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA, m.HEAD.get("COST_REG_WEIGHTS", 1.5), 2.5,
-                                    pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, ws)
+                                    pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, ws, ld=self._ld())
             return
         ops.ota_assign(pl.points, pl.lvl_start, self.strides, pl.logits, self.num_classes, pl.offsets, gt, num_gt,
                        m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA, m.HEAD.get("COST_REG_WEIGHTS", 1.5), 2.5,
-                       m.HEAD.get("CANDIDATE_K", 10), pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, pl.ota_ws)
+                       m.HEAD.get("CANDIDATE_K", 10), pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, pl.ota_ws, ld=self._ld())
 
     def get_losses(self, inputs):
         """OTA.get_losses (ota.py:62-74) + emd_losses (:183-233); pl.gt_ctr holds the IoU targets, pl.stats = (num_fg, 2 num_fg)."""
@@ -279,7 +285,7 @@ class OTA(FCOS):
         rows = pl.N * pl.pyr.pix_per_img
         assert m.LOSSES.IOU_LOSS_TYPE == "giou", "HIP OTA path implements the giou ltrb loss"
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA,
-                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits)
+                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self._ld())
         ops.giou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, None, pl.labels, rows, pl.stats[0:1], 2.0, pl.loss_buf[1:2], pl.d_off)
         ops.bce_logits_fwd_bwd(pl.raw, pl.gt_ctr, pl.labels, rows, pl.stats[1:2], pl.loss_buf[2:3], pl.d_ctr, ld=8, off=4)
         loss_cls, loss_box, loss_iou = pl.loss_buf[0], pl.loss_buf[1], pl.loss_buf[2]

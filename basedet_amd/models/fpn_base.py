@@ -515,7 +515,8 @@ class FPNDetector:
             need = max(need, self.p6.wgrad_ws_bytes(g5, g6), self.p7.wgrad_ws_bytes(pl.g_p6r, pl.pyr.level(len(self.fpn_stages) + 1)))
         need = max(need, self._head_wgrad_ws_bytes(pl))
         pl.wgrad_ws = C.empty((need // 4 + 64,), torch.float32)
-        pl.colsum_ws = C.empty((ops.colsum_workspace_bytes(2048) // 4,), torch.float32)
+        cmax = max([2048] + [c.cout for c in self.convs.values() if c.trainable and c.has_bias])      # (a class predictor may be wider)
+        pl.colsum_ws = C.empty((ops.colsum_workspace_bytes(cmax) // 4,), torch.float32)
         self.plan_arena.place(pl)
         self._plans[key] = pl
         return pl
@@ -724,11 +725,11 @@ class FPNDetector:
         return sc
 
     def _detect(self, N, lvl_rows, K, mode, info, k=1000, logits=None, ctr=None, ctr_ld=1, ctr_off=0, scores=None, anchors=None,
-                offsets=None, off_ld=4, A=1, mean=(0, 0, 0, 0), std=(1, 1, 1, 1), item_boxes=None):
+                offsets=None, off_ld=4, A=1, mean=(0, 0, 0, 0), std=(1, 1, 1, 1), item_boxes=None, cls_ld=None):
         """Post-processing of N images in one launch chain.  Per image and level: score > TEST.CLS_THRESHOLD -> top-k (descending) ->
         label = idx % K, box of row idx // K; then batched NMS by label, keep MAX_BOXES_PER_IMAGE, rescale + clip by the image's own
-        im_info row.  The candidates come from `logits` (bf16 [N][sum(lvl_rows)][K], one-stage heads: bd_det_select computes the scores
-        on the fly) or from `scores` (fp32 [N][sum(lvl_rows) * K], the RCNN head's softmax).  Everything stays on the device; the only
+        im_info row.  The candidates come from `logits` (bf16 [N][sum(lvl_rows)][cls_ld or K], one-stage heads: bd_det_select computes the
+        scores on the fly and skips a row's pad slots) or from `scores` (fp32 [N][sum(lvl_rows) * K], the RCNN head's softmax).  Everything stays on the device; the only
         host read is the N detection counts.  Returns the list of N Containers."""
         from ..structures import Boxes, Container
         t = self.cfg.TEST
@@ -741,7 +742,7 @@ class FPNDetector:
         s = self._detect_scratch(N, Ln, k, (rows, K) if logits is not None else None)
         if logits is not None:
             ops.det_select(logits, N, rows, K, row_off, lvl_rows, k, t.CLS_THRESHOLD, s["tk_idx"], s["tk_sc"], s["tk_cnt"], s["sel_ws"],
-                           ctr=ctr, ctr_ld=ctr_ld, ctr_off=ctr_off)
+                           ctr=ctr, ctr_ld=ctr_ld, ctr_off=ctr_off, ld=cls_ld if cls_ld not in (None, K) else None)
         else:
             ops.segment_topk(scores, N, rows * K, 1, 1, 0, [r * K for r in row_off], [r * K for r in lvl_rows], k, s["tk_idx"], s["tk_sc"],
                              s["tk_cnt"], min_score=t.CLS_THRESHOLD)

@@ -11,6 +11,7 @@ from .. import ops
 from ..streams import fork, join
 from ..utils.registry import registers
 from . import params as P
+from .engine import PaddedClsConv
 from .fpn_base import FPNDetector, _round_up
 
 
@@ -38,7 +39,9 @@ class RetinaNet(FPNDetector):
         self.cls_tower = [add(f"head.cls_subnet.{2 * i}", ch, ch, 3, 1, 1, bias=True) for i in range(nc)]
         self.box_tower = [add(f"head.bbox_subnet.{2 * i}", ch, ch, 3, 1, 1, bias=True) for i in range(nc)]
         A, K = self.num_anchors, self.num_classes
-        self.cls_score = add("head.cls_score", ch, A * K, 3, 1, 1, bias=True)
+        # A groups of cls_ld = round_up(K, 8) channels (the identity for K % 8 == 0): any class count, 16-byte anchor rows
+        self.cls_score = self.convs["head.cls_score"] = PaddedClsConv("head.cls_score", ch, A, K, 3, 1, 1, self.device)
+        self.cls_ld = self.cls_score.cls_ld
         self.box_ld = _round_up(A * 4, 8)                                          # 36 -> 40 channels (8-aligned rows)
         self.bbox_pred = add("head.bbox_pred", ch, A * 4, 3, 1, 1, bias=True, cout_pad=self.box_ld)
         # MODEL.SPARSE_BOX_BWD (default on, bf16 only): the box branch's gradient is nonzero only around the foreground anchors (the
@@ -69,9 +72,9 @@ class RetinaNet(FPNDetector):
         pl.cls_act = [act(pl.pyr, ch) for _ in range(nc)]
         pl.box_act = [act(pl.pyr, ch) for _ in range(nc)]
         A, K = self.num_anchors, self.num_classes
-        pl.logits = act(pl.pyr, A * K)
+        pl.logits = act(pl.pyr, A * self.cls_ld)       # (pad slots K..cls_ld-1 of every anchor: zero weight rows and bias -> logit 0)
         pl.offsets = act(pl.pyr, self.box_ld)          # (channels 36..39: zero weight rows and bias -- written as 0 by every forward)
-        pl.d_logits = C.like(pl.logits)
+        pl.d_logits = C.like(pl.logits)                # (the losses write the pad slots' zero gradient)
         pl.d_offsets = C.like(pl.offsets)              # (bd_smooth_l1_fwd_bwd writes the padding slots' zero gradient)
         pl.g_tower = [[act(pl.pyr, ch) for _ in range(nc)] for _ in range(2)]   # one gradient buffer per tower layer
         # one liveness map per BOX tower gradient (int32; the layout is the library's).  A plan's buffers never overlap each other (_Carver
@@ -147,7 +150,8 @@ class RetinaNet(FPNDetector):
         pl.loss_buf.zero_()
         rows = N * pl.A_total
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA,
-                               m.LOSSES.FOCAL_LOSS_GAMMA, pl.num_fg, 1.0, pl.loss_buf[0:1], pl.d_logits)
+                               m.LOSSES.FOCAL_LOSS_GAMMA, pl.num_fg, 1.0, pl.loss_buf[0:1], pl.d_logits,
+                               ld=self.cls_ld if self.cls_ld != self.num_classes else None)
         ops.smooth_l1_fwd_bwd(pl.offsets, pl.gt_offsets, pl.labels, pl.pyr.pixels, self.num_anchors, self.box_ld,
                               m.LOSSES.SMOOTH_L1_BETA, pl.num_fg, m.LOSSES.REG_LOSS_WEIGHT, pl.loss_buf[1:2], pl.d_offsets)
         cls_loss, reg_loss = pl.loss_buf[0], pl.loss_buf[1]
@@ -205,7 +209,8 @@ class RetinaNet(FPNDetector):
             for k in range(len(self.cls_tower)):
                 out[f"cls{k}_{i}"] = lvl(pl.cls_act[k], i)
                 out[f"box{k}_{i}"] = lvl(pl.box_act[k], i)
-            out[f"logits_{i}"] = lvl(pl.logits, i)
+            lg = lvl(pl.logits, i)
+            out[f"logits_{i}"] = self.cls_score.real_logits(lg.permute(0, 2, 3, 1)).permute(0, 3, 1, 2).contiguous()
             out[f"offs_{i}"] = lvl(pl.offsets, i, self.num_anchors * 4)
 
     # ------------------------------------------------------------------------------------------------
@@ -221,4 +226,4 @@ class RetinaNet(FPNDetector):
         m = self.cfg.MODEL
         # F.sigmoid(F.flatten(logits)) (:184) happens inside the selection: no score tensor
         return self._detect(pl.N, [h * w * A for h, w in pl.sizes], K, 0, pre["img_info"], logits=pl.logits, anchors=pl.anchors,
-                            offsets=pl.offsets, off_ld=self.box_ld, A=A, mean=m.BOX_REG.MEAN, std=m.BOX_REG.STD)
+                            offsets=pl.offsets, off_ld=self.box_ld, A=A, mean=m.BOX_REG.MEAN, std=m.BOX_REG.STD, cls_ld=self.cls_ld)

@@ -474,10 +474,16 @@ def ota_assign_workspace_bytes(N, P):
 
 
 def ota_assign(points, lvl_start, strides, logits, K, pred_ltrb, gt_boxes, num_gt, alpha, gamma, reg_weight, center_radius,
-               candidate_k, labels, targets, gt_ious, stats, ws):
-    """OTA.get_ground_truth, top-k matcher (models/det/ota.py:76-181)."""
+               candidate_k, labels, targets, gt_ious, stats, ws, ld=None):
+    """OTA.get_ground_truth, top-k matcher (models/det/ota.py:76-181).  ld: slots per row of `logits` (round_up(K, 8)) when they are padded."""
     P = points.shape[0]
     N, Gmax = gt_boxes.shape[0], gt_boxes.shape[1]
+    if ld is not None:
+        check(L().bd_ota_assign_ld(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), int(ld), ptr(pred_ltrb),
+                                   ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight), float(center_radius),
+                                   int(candidate_k), ptr(labels), ptr(targets), ptr(gt_ious), ptr(stats), ptr(ws),
+                                   ws.numel() * ws.element_size(), stream_ptr()), "bd_ota_assign_ld")
+        return
     check(L().bd_ota_assign(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), ptr(pred_ltrb),
                             ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight), float(center_radius),
                             int(candidate_k), ptr(labels), ptr(targets), ptr(gt_ious), ptr(stats), ptr(ws),
@@ -489,10 +495,16 @@ def ota_sinkhorn_workspace_bytes(N, P, Gmax):
 
 
 def ota_assign_sinkhorn(points, lvl_start, strides, logits, K, pred_ltrb, gt_boxes, num_gt, alpha, gamma, reg_weight, center_radius,
-                        labels, targets, gt_ious, stats, ws, topq=20, eps=0.1, iters=50):
-    """OTA.get_ground_truth with the SinkhornMatcher (models/det/ota.py:153-157, layers/common/matcher.py:106-121)."""
+                        labels, targets, gt_ious, stats, ws, topq=20, eps=0.1, iters=50, ld=None):
+    """OTA.get_ground_truth with the SinkhornMatcher (models/det/ota.py:153-157, layers/common/matcher.py:106-121).  ld: as ota_assign."""
     P = points.shape[0]
     N, Gmax = gt_boxes.shape[0], gt_boxes.shape[1]
+    if ld is not None:
+        check(L().bd_ota_assign_sinkhorn_ld(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), int(ld),
+                                            ptr(pred_ltrb), ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight),
+                                            float(center_radius), int(topq), float(eps), int(iters), ptr(labels), ptr(targets), ptr(gt_ious),
+                                            ptr(stats), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "bd_ota_assign_sinkhorn_ld")
+        return
     check(L().bd_ota_assign_sinkhorn(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), ptr(pred_ltrb),
                                      ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight),
                                      float(center_radius), int(topq), float(eps), int(iters), ptr(labels), ptr(targets), ptr(gt_ious),
@@ -504,10 +516,18 @@ def freeanchor_workspace_bytes(N, Gmax, bucket, A):
 
 
 def freeanchor_loss_fwd_bwd(logits, offsets, box_ld, anchors_per_pix, anchors, K, gt_boxes, num_gt, mean, std, iou_thresh, bucket,
-                            beta, reg_weight, alpha, gamma, loss_out, d_logits, d_offsets, ws):
-    """FreeAnchor bag losses + gradients (models/det/free_anchor.py:38-142); loss_out: fp32[2] = (pos_loss, neg_loss)."""
+                            beta, reg_weight, alpha, gamma, loss_out, d_logits, d_offsets, ws, cls_ld=None):
+    """FreeAnchor bag losses + gradients (models/det/free_anchor.py:38-142); loss_out: fp32[2] = (pos_loss, neg_loss).
+    cls_ld: slots per anchor row of logits / d_logits (round_up(K, 8)) when they are padded."""
     A = anchors.shape[0]
     N, Gmax = gt_boxes.shape[0], gt_boxes.shape[1]
+    if cls_ld is not None:
+        check(L().bd_freeanchor_loss_fwd_bwd_ld(ptr(logits), int(cls_ld), ptr(offsets), int(box_ld), int(anchors_per_pix), ptr(anchors), A,
+                                                int(K), ptr(gt_boxes), ptr(num_gt), N, Gmax, f32arr(mean), f32arr(std), float(iou_thresh),
+                                                int(bucket), float(beta), float(reg_weight), float(alpha), float(gamma), ptr(loss_out),
+                                                ptr(d_logits), ptr(d_offsets), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+              "bd_freeanchor_loss_fwd_bwd_ld")
+        return
     check(L().bd_freeanchor_loss_fwd_bwd(ptr(logits), ptr(offsets), int(box_ld), int(anchors_per_pix), ptr(anchors), A, int(K),
                                          ptr(gt_boxes), ptr(num_gt), N, Gmax, f32arr(mean), f32arr(std), float(iou_thresh),
                                          int(bucket), float(beta), float(reg_weight), float(alpha), float(gamma), ptr(loss_out),
@@ -654,7 +674,11 @@ def rcnn_loss_fwd_bwd(raw, ld, K, box_off, labels, targets, R, beta, num_samples
 
 
 # ---- inference post-processing ----------------------------------------------------------------------------
-def det_scores(logits, rows, K, scores, ctr=None, ctr_ld=1, ctr_off=0):
+def det_scores(logits, rows, K, scores, ctr=None, ctr_ld=1, ctr_off=0, ld=None):
+    """ld: slots per row of `logits` when they are padded behind the K classes (scores stays [rows][K])."""
+    if ld is not None:
+        check(L().bd_det_scores_ld(ptr(logits), int(ld), ptr(ctr), ctr_ld, ctr_off, rows, K, ptr(scores), stream_ptr()), "bd_det_scores_ld")
+        return
     check(L().bd_det_scores(ptr(logits), ptr(ctr), ctr_ld, ctr_off, rows, K, ptr(scores), stream_ptr()), "bd_det_scores")
 
 
@@ -680,9 +704,15 @@ def det_select_workspace_bytes(B, Ln, rows, K, k):
     return int(L().bd_det_select_workspace_bytes(B, Ln, rows, K, k))
 
 
-def det_select(logits, B, rows, K, seg_start, seg_rows, k, min_score, out_idx, out_score, out_cnt, ws, ctr=None, ctr_ld=1, ctr_off=0):
+def det_select(logits, B, rows, K, seg_start, seg_rows, k, min_score, out_idx, out_score, out_cnt, ws, ctr=None, ctr_ld=1, ctr_off=0,
+               ld=None):
     """Scores + per-level top-k of B images straight from the bf16 logits [B][rows][K] (= det_scores -> segment_topk(min_score), bit for
-    bit); seg_start / seg_rows in rows."""
+    bit); seg_start / seg_rows in rows.  ld: slots per row of `logits` (round_up(K, 8)) when they are padded: same indices, scores, counts."""
+    if ld is not None:
+        check(L().bd_det_select_ld(ptr(logits), int(ld), ptr(ctr), ctr_ld, ctr_off, B, rows, K, len(seg_start), i32arr(seg_start),
+                                   i32arr(seg_rows), k, float(min_score), ptr(out_idx), ptr(out_score), ptr(out_cnt), ptr(ws),
+                                   ws.numel() * ws.element_size(), stream_ptr()), "bd_det_select_ld")
+        return
     check(L().bd_det_select(ptr(logits), ptr(ctr), ctr_ld, ctr_off, B, rows, K, len(seg_start), i32arr(seg_start), i32arr(seg_rows), k,
                             float(min_score), ptr(out_idx), ptr(out_score), ptr(out_cnt), ptr(ws), ws.numel() * ws.element_size(),
                             stream_ptr()), "bd_det_select")
@@ -703,8 +733,14 @@ def det_finalize_batched(boxes, scores, labels, keep, num_keep, max_out, im_info
 
 
 # ---- losses -----------------------------------------------------------------------------------------------
-def focal_loss_fwd_bwd(logits, labels, rows, K, alpha, gamma, norm, grad_scale, loss_sum, dlogits, general=False):
-    """general: the general-gamma kernel also for gamma == 2 (bd_focal_loss_fwd_bwd_general)"""
+def focal_loss_fwd_bwd(logits, labels, rows, K, alpha, gamma, norm, grad_scale, loss_sum, dlogits, general=False, ld=None):
+    """general: the general-gamma kernel also for gamma == 2 (bd_focal_loss_fwd_bwd_general)
+    ld: slots per row of logits / dlogits (round_up(K, 8)) for a K that is no multiple of 8 (bd_focal_loss_fwd_bwd_ld)"""
+    if ld is not None:
+        check(L().bd_focal_loss_fwd_bwd_ld(ptr(logits), ptr(labels), rows, K, int(ld), float(alpha), float(gamma), ptr(norm),
+                                           int(norm.dtype == torch.float32), float(grad_scale), ptr(loss_sum), ptr(dlogits), int(bool(general)),
+                                           stream_ptr()), "bd_focal_loss_fwd_bwd_ld")
+        return
     fn = L().bd_focal_loss_fwd_bwd_general if general else L().bd_focal_loss_fwd_bwd
     check(fn(ptr(logits), ptr(labels), rows, K, float(alpha), float(gamma), ptr(norm),
              int(norm.dtype == torch.float32), float(grad_scale), ptr(loss_sum), ptr(dlogits), stream_ptr()), "bd_focal_loss_fwd_bwd")

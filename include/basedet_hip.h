@@ -259,7 +259,9 @@ int bd_weight_pack_multi(const bd_pack_desc* descs_dev, int n, int total_blocks,
 
 /* bias gradient: column sums over the pixel rows {n*pix_per_img + off + i : n < N, i < cnt} of a bf16
  * [.][C] activation gradient (one pyramid level, or the whole tensor with N=1, off=0) into fp32 out[C];
- * accumulate != 0 adds.  C % 8 == 0, C <= 2048; two-stage fixed-order reduction through ws (reproducible). */
+ * accumulate != 0 adds.  C % 8 == 0; two-stage fixed-order reduction through ws (reproducible).  More than 2048 columns
+ * (bd_version() >= 104; a class predictor of A * cls_ld channels, retina_head.py:66) are summed in chunks of 2048: a column's
+ * summation order does not depend on C. */
 size_t bd_colsum_workspace_bytes(int C);
 int bd_colsum_bf16(const void* g, int N, int64_t pix_per_img, int64_t off, int64_t cnt, int C, float* out,
                    int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream);
@@ -422,6 +424,12 @@ int bd_ota_assign(const float* points, int P, const int32_t* lvl_start_host, con
                   int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
                   float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
                   float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream);
+/* Any class count (bd_version() >= 104; ota.py:76-181 with DATA.NUM_CLASSES of the config): logits bf16 [N*P][ld], ld = K rounded up to a
+ * multiple of 8, the first K slots of a row the classes, the rest padding that no cost reads.  ld == K is bd_ota_assign. */
+int bd_ota_assign_ld(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L, const void* logits,
+                     int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
+                     float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
+                     float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream);
 
 /* The same assignment with the Sinkhorn matcher (cfg MATCHING = "sinkhorn"; layers/common/matcher.py:106-121,
  * layers/blocks/sinkhorn_distance.py:22-50): supplies mu_g = max(1, int(sum of the `topq` = 20 largest in-box IoUs)), background
@@ -434,6 +442,12 @@ int bd_ota_assign_sinkhorn(const float* points, int P, const int32_t* lvl_start_
                            int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps, int iters,
                            int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
                            bd_stream_t stream);
+/* ... on logits bf16 [N*P][ld] as bd_ota_assign_ld (ota.py:76-181, matcher.py:106-121). */
+int bd_ota_assign_sinkhorn_ld(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L,
+                              const void* logits, int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt,
+                              int N, int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps,
+                              int iters, int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
+                              bd_stream_t stream);
 
 /* FreeAnchor.get_losses after the network forward (models/det/free_anchor.py:38-142): positive bag loss over the `bucket`
  * anchors of largest IoU per gt (ties at the boundary: lowest anchor index) and negative loss over every (anchor, class) with the
@@ -448,6 +462,13 @@ int bd_freeanchor_loss_fwd_bwd(const void* logits, const void* offsets, int box_
                                const float* std4, float iou_thresh, int bucket, float beta, float reg_weight, float alpha,
                                float gamma, float* loss_out, void* d_logits, void* d_offsets, void* ws, size_t ws_bytes,
                                bd_stream_t stream);
+/* The same (free_anchor.py:38-142) on logits / d_logits bf16 [N*A][cls_ld] (bd_version() >= 104): cls_ld = K (bd_freeanchor_loss_fwd_bwd)
+ * or K rounded up to a multiple of 8 -- the slots >= K of an anchor's row are padding: no loss, d_logits written as +0. */
+int bd_freeanchor_loss_fwd_bwd_ld(const void* logits, int cls_ld, const void* offsets, int box_ld, int anchors_per_pix,
+                                  const float* anchors, int A, int K, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax,
+                                  const float* mean4, const float* std4, float iou_thresh, int bucket, float beta, float reg_weight,
+                                  float alpha, float gamma, float* loss_out, void* d_logits, void* d_offsets, void* ws, size_t ws_bytes,
+                                  bd_stream_t stream);
 
 /* layers/common/post_processing.py:17-47 batched_nms (class-offset trick + greedy NMS, suppress iff IoU > thr).
  * boxes [n][4], scores [n], idxs [n] (may be NULL = plain NMS).  keep: int32[n] (descending score order),
@@ -473,6 +494,13 @@ int bd_focal_loss_fwd_bwd(const void* logits, const int32_t* labels, int64_t row
 int bd_focal_loss_fwd_bwd_general(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha,
                                   float gamma, const void* norm, int norm_is_float, float grad_scale,
                                   float* loss_sum, void* dlogits, bd_stream_t stream);
+/* Any class count (bd_version() >= 104; sigmoid_focal_loss.py:9-36 at retinanet.py:148-156 / fcos.py:146-151 with the config's
+ * DATA.NUM_CLASSES): logits / dlogits bf16 [rows][ld], ld = K rounded up to a multiple of 8.  The first K slots of a row are the classes;
+ * the others are padding: they add no loss and their gradient is written as +0.  general != 0 selects the general-gamma kernel as
+ * bd_focal_loss_fwd_bwd_general does.  ld == K gives the bits of the two entries above. */
+int bd_focal_loss_fwd_bwd_ld(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma,
+                             const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, int general,
+                             bd_stream_t stream);
 
 /* smooth_l1_loss (layers/losses/smooth_l1_loss.py:7-34) over rows with label > 0 (retinanet.py:158-162).
  * Row r = pixel*A + a; pred/dpred are bf16 with `ld` channels per pixel (ld >= 4*A, ld % 4 == 0), element
@@ -666,6 +694,10 @@ int bd_rcnn_loss_fwd_bwd(const void* raw, int ld, int K, int box_off, const int3
  * (fcos.py:194).  logits/ctr bf16, scores fp32. */
 int bd_det_scores(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
                   bd_stream_t stream);
+/* The same (retinanet.py:184, fcos.py:194) from logits bf16 [rows][ld], ld = K or K rounded up to a multiple of 8 (bd_version() >= 104): the slots >= K of a row are padding
+ * and get no score; scores stays the compact fp32 [rows][K]. */
+int bd_det_scores_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
+                     bd_stream_t stream);
 /* bd_det_scores + bd_segment_topk(min_score) in one entry for B images x L levels, without the fp32 score tensor
  * (retinanet.py:183-192, fcos.py:194-204).  logits bf16 [B][rows][K]; ctr (optional) bf16 [B][rows][ctr_ld], centerness of a row at
  * column ctr_off.  Level l is rows [seg_start[l], seg_start[l] + seg_rows[l]) of every image; its item i is logits[b][seg_start[l] +
@@ -679,6 +711,13 @@ size_t bd_det_select_workspace_bytes(int B, int L, int64_t rows, int K, int k);
 int bd_det_select(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
                   const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
                   float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream);
+/* The same (retinanet.py:183-192, fcos.py:194-204) from logits bf16 [B][rows][ld], ld = K or K rounded up to a multiple of 8
+ * (bd_version() >= 104).  The slots >= K of a row are padding (a pad logit of 0 would score 0.5) and never compete; out_idx keeps the
+ * compact numbering (row - seg_start[l]) * K + class, so the results are those of bd_det_select on the compacted [B][rows][K] copy, bit for
+ * bit, and bd_det_candidates* read them unchanged.  rows * ld < 2^31. */
+int bd_det_select_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
+                     const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
+                     float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream);
 /* RCNN test branch (rcnn.py:84-93): scores [R][K] = softmax(logits)[:, 1:] (-inf for empty RoI slots),
  * boxes [R][K][4] = BoxCoder.decode(roi, deltas of class k).  raw: bf16 [R][ld] as in bd_rcnn_loss_fwd_bwd. */
 int bd_rcnn_predict(const void* raw, int ld, int K, int box_off, const float* rois, const int32_t* num_rois,
