@@ -341,10 +341,15 @@ def sinkhorn_match(cost, ious, eps=0.1, max_iter=50, topq=20):
 
 
 def ota_ground_truth(points_list, strides, logits, pred_ltrb, batched_gt_boxes, num_valid, alpha=0.25, gamma=2.0,
-                     reg_weight=1.5, center_radius=2.5, candidate_k=10, matching="topk"):
+                     reg_weight=1.5, center_radius=2.5, candidate_k=10, matching="topk", class_cost="literal"):
     """logits (N, P, K), pred_ltrb (N, P, 4) float32 (detached predictions).  Returns labels (N, P) int32 (class, 0 = bg), ltrb
     targets (N, P, 4), IoU targets (N, P), and the cost / IoU matrices per image (for tie analysis in the tests).
-    Unpinned orders fixed here: F.topk ties -> lowest point index, F.argmin ties -> lowest gt index."""
+    Unpinned orders fixed here: F.topk ties -> lowest point index, F.argmin ties -> lowest gt index.
+    class_cost: "literal" sums the focal loss over the K one-hot columns (ota.py:130-135); "reassociated" evaluates the same sum as
+    (S_bg - f(x_c, 0)) + f(x_c, 1) in float32, S_bg = the background sum accumulated in column order (the association of
+    basedet_amd/csrc/ota.hip): the two differ by fp32 rounding only, which is what the tests measure their tie excuses against."""
+    if class_cost not in ("literal", "reassociated"):
+        raise ValueError(f"class_cost={class_cost!r}: literal or reassociated")
     all_pts = np.concatenate(points_list, axis=0).astype(F32)
     P = all_pts.shape[0]
     eps = np.finfo(np.float32).eps
@@ -370,13 +375,20 @@ def ota_ground_truth(points_list, strides, logits, pred_ltrb, batched_gt_boxes, 
         K = x.shape[1]
         onehot = np.zeros((G, K), F32)
         onehot[np.arange(G), gtl[:, 4].astype(np.int32) - 1] = 1
-        loss_cls = np.stack([sigmoid_focal_loss(x, np.broadcast_to(onehot[g][None], x.shape), alpha, gamma).sum(axis=-1)
-                             for g in range(G)]).astype(F32)                          # (G, P)
+        if class_cost == "literal":
+            loss_cls = np.stack([sigmoid_focal_loss(x, np.broadcast_to(onehot[g][None], x.shape), alpha, gamma).sum(axis=-1)
+                                 for g in range(G)]).astype(F32)                      # (G, P)
+        else:
+            f0 = sigmoid_focal_loss(x, np.zeros_like(x), alpha, gamma).astype(F32)
+            f1 = sigmoid_focal_loss(x, np.ones_like(x), alpha, gamma).astype(F32)
+            s_bg = np.cumsum(f0, axis=1, dtype=F32)[:, -1]                             # sequential fp32 sum over the columns
+            c = gtl[:, 4].astype(np.int32) - 1
+            loss_cls = ((s_bg[None, :] - f0[:, c].T).astype(F32) + f1[:, c].T).astype(F32)
         ious = ltrb_iou(np.broadcast_to(np.asarray(pred_ltrb[n], F32)[None], deltas.shape), deltas, "iou", eps).astype(F32)
         loss_delta = (-np.log(np.maximum(ious, eps))).astype(F32)
         cost = (loss_cls + F32(reg_weight) * loss_delta + F32(1e6) * (~in_boxes).astype(F32)).astype(F32)
         if matching == "sinkhorn":                                                       # ota.py:153-157
-            loss_cls_bg = sigmoid_focal_loss(x, np.zeros_like(x), alpha, gamma).sum(axis=-1).astype(F32)
+            loss_cls_bg = sigmoid_focal_loss(x, np.zeros_like(x), alpha, gamma).sum(axis=-1).astype(F32) if class_cost == "literal" else s_bg
             cost_bg = np.concatenate([cost, loss_cls_bg[None]], 0)
             ious_m = (ious * in_boxes.astype(F32)).astype(F32)
             mg, pi = sinkhorn_match(cost_bg, ious_m)

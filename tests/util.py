@@ -500,3 +500,159 @@ def rcnn_loss_ref(raw, ld, K, box_off, labels, targets, beta, num_samples):
     return dict(draw=draw, S_draw=S, exact=exact, amp=2.0 * logits.abs().max(1, keepdim=True)[0] + 8.0,
                 cls=float(cls_rows.sum() * gs), S_cls=float(s_rows.sum() * gs),
                 box=float((lbox * fg4).sum() * gs), S_box=float((slbox * fg4).sum() * gs))
+
+
+# ---- OTA assignment on edge-case gts (tests/test_ota_edges_gpu.py, tests/test_ota_edges_cpu.py) ----------------------------------------
+# The pyramid of a 320 x 448 image: P = 2987 points = three 1024-point passes of the selection loops, the last one ragged (939).
+OTA_EDGE_IMAGE = (320, 448)
+OTA_EDGE_SIZES = ((40, 56), (20, 28), (10, 14), (5, 7), (3, 4))
+OTA_EDGE_STRIDES = (8, 16, 32, 64, 128)
+OTA_ARGS = (0.25, 2.0, 1.5, 2.5, 10)              # alpha, gamma, reg_weight, center_radius, candidate_k (OTAConfig)
+# name -> (seed, gt counts per image, Gmax, K): the arguments of ota_edge_problem
+OTA_EDGE_CASES = {
+    "g100_0_37_1": (41, (100, 0, 37, 1), 100, 80),
+    "g1_1": (12, (1, 1), 1, 80),
+    "k13_ld16": (41, (100, 0, 37, 1), 100, 13),
+}
+
+
+def ota_edge_problem(seed, counts, Gmax, K, kinds=("zero_area", "outside", "dup")):
+    """One OTA assignment problem on the 320 x 448 pyramid.  Gts as tests/test_assign_edges_gpu.py::edge_gts draws them (quarter-pixel
+    coordinates, centres anywhere in the image, sides of 4 .. 200 px: the small ones hold fewer points than their dynamic k, so the
+    +1e6 "outside" branch of the cost decides their selection); images with >= 8 gts get, from the end of their valid rows, a zero-area
+    box, a box wholly outside the image and an exact copy of gt 0 with another class; rows >= num_gt hold NaN / 1e30.
+    The copy's class logit is a copy of gt 0's at every point: the two cost rows are then the same numbers, every point they select is
+    a conflict whose argmin is an exact tie, and "lowest gt index wins" decides the label.
+    Images with a zero-area gt also hold a few "tie points" whose cost against that gt is one and the same smallest number (below).
+    Predictions as tests/test_ota_gpu.py::_problem: ltrb towards a random gt plus noise.  Logits and predictions are bf16 values.
+    Returns a dict: pts (per level), allp (P, 2), lvl_start, strides, gt (N, Gmax, 5), num (N,), logits (N, P, K), pred (N, P, 4),
+    planted {(image, kind): gt row}, tie_points {image: point indices}."""
+    from oracle import box_ops
+    rng = np.random.default_rng(seed)
+    H, W = OTA_EDGE_IMAGE
+    pts = box_ops.point_anchors(list(OTA_EDGE_SIZES), list(OTA_EDGE_STRIDES), 0.5, 1)
+    allp = np.concatenate(pts, 0).astype(np.float32)
+    P, N = allp.shape[0], len(counts)
+    gt = np.zeros((N, Gmax, 5), np.float32)
+    planted = {}
+    for n, G in enumerate(counts):
+        cx, cy = rng.uniform(0, W, G), rng.uniform(0, H, G)
+        w, h = 4 * 50 ** rng.random(G), 4 * 50 ** rng.random(G)              # 4 .. 200 px, as many below 28 px as above
+        b = np.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2], 1).astype(np.float32)
+        gt[n, :G, :4] = np.round(b * 4) / 4
+        gt[n, :G, 4] = rng.integers(1, K + 1, G)
+        if G >= 8:
+            s = G - 1
+            for k in kinds:
+                if k == "zero_area":
+                    gt[n, s, :4] = [150.0, 100.0, 150.0, 160.0]                  # x1 == x2
+                    gt[n, s, 4] = ((int(gt[n, 0, 4]) + 1) % K) + 1               # a class of its own among the planted rows
+                elif k == "outside":
+                    gt[n, s, :4] = [W + 50.0, H + 20.0, W + 300.0, H + 200.0]
+                elif k == "dup":
+                    gt[n, s] = gt[n, 0]
+                    gt[n, s, 4] = (int(gt[n, 0, 4]) % K) + 1
+                planted[(n, k)] = s
+                s -= 1
+        if G < Gmax:
+            gt[n, G:] = np.where(rng.random((Gmax - G, 5)) < 0.5, np.nan, 1e30).astype(np.float32)
+    num = np.asarray(counts, np.int32)
+    pred = np.zeros((N, P, 4), np.float32)
+    for n in range(N):
+        if num[n] == 0:
+            pred[n] = rng.uniform(0, 60, (P, 4))
+            continue
+        b = gt[n, rng.integers(0, num[n], P), :4]
+        d = np.stack([allp[:, 0] - b[:, 0], allp[:, 1] - b[:, 1], b[:, 2] - allp[:, 0], b[:, 3] - allp[:, 1]], 1)
+        pred[n] = np.maximum(d * rng.uniform(0.7, 1.3, (P, 4)) + rng.normal(0, 2.0, (P, 4)), 0)
+    logits = rng.normal(-2.5, 1.2, (N, P, K)).astype(np.float32)
+    for (n, k), s in planted.items():
+        if k == "dup":
+            logits[n, :, int(gt[n, s, 4]) - 1] = logits[n, :, int(gt[n, 0, 4]) - 1]
+    tie_points = {}
+    for (n, k), s in planted.items():
+        if k == "zero_area":
+            # the points the zero-area gt must choose among: a confident logit of its class, nothing else, and an empty predicted box
+            # (IoU 0).  Their cost against that gt is one number, the smallest of its row; dyn_k is 1: the lowest index wins.
+            # Image 0 has them in all three 1024-point passes, the other images only in the second and third.
+            idx = [1024 * q + 37 + 301 * j for q in ((0, 1, 2) if n == 0 else (1, 2)) for j in range(2)]
+            c = int(gt[n, s, 4]) - 1
+            logits[n, :, c] = np.minimum(logits[n, :, c], -2.0)      # every other point: a class cost >= 0.4, several fp32 steps at 1e6 away
+            logits[n, idx, :] = -6.0
+            logits[n, idx, c] = 4.0
+            pred[n, idx] = 0.0
+            tie_points[n] = idx
+    lvl_start = np.cumsum([0] + [h * w for h, w in OTA_EDGE_SIZES]).tolist()
+    return dict(pts=pts, allp=allp, lvl_start=lvl_start, strides=list(OTA_EDGE_STRIDES), gt=gt, num=num, planted=planted, tie_points=tie_points,
+                logits=bf16_round(torch.from_numpy(logits)).numpy(), pred=bf16_round(torch.from_numpy(pred)).numpy())
+
+
+def ota_cost_tol(c):
+    """How far two evaluations of one OTA cost may lie apart: 1e-4 |c| below the outside penalty (the re-associated class cost plus the
+    exp / log intrinsics), 0.125 = two fp32 spacings at 1e6 above it (the pre-penalty costs differ by far less than one spacing, so the
+    two sums land on the same or on neighbouring grid points)."""
+    c = abs(float(c))
+    return 1e-4 * c if c < 1e5 else 0.125
+
+
+def ota_topk_selection(cost, ious, candidate_k=10):
+    """OTATopkMatcher before its conflict step, from the oracle's cost / IoU matrices (G, P): (dyn_k (G,), the fp32 sums of the
+    candidate_k largest IoUs (G,), the match matrix (G, P) bool, the costs of every row sorted ascending)."""
+    G, P = cost.shape
+    topk = -np.sort(-ious, axis=1, kind="stable")[:, :min(candidate_k, P)]
+    sums = np.zeros(G, np.float32)
+    for v in topk.T:
+        sums = (sums + v).astype(np.float32)
+    dyn = np.maximum(1, sums.astype(np.int64))
+    mm = np.zeros((G, P), bool)
+    for g in range(G):
+        mm[g, np.argsort(cost[g], kind="stable")[: dyn[g]]] = True
+    return dyn, sums, mm, np.sort(cost, axis=1)
+
+
+def ota_topk_excuse(p, lab_o, lab_x, tgt_x, allp, gtl, cost, sel):
+    """Why point p of one image may carry another label (lab_x, with ltrb target tgt_x) than the oracle's lab_o: "a", "b", "c" or None.
+    cost (G, P) is the oracle's, sel = ota_topk_selection of it, gtl (G, 5) the valid gt rows.
+      a  selection tie: a gt that selects p on one side only has cost(g, p) within ota_cost_tol of its dyn_k-th or (dyn_k + 1)-th
+         smallest cost.  The gts in question: the oracle's selectors of p that the other side did not assign p to, and the gt the other
+         side assigned p to (the one of class lab_x whose encoding of p is tgt_x, bit for bit) if the oracle did not select p for it;
+      b  conflict tie: the two smallest costs of p's column are within ota_cost_tol of each other;
+      c  dynamic-k tie: for one of the gts of (a) the sum of the 10 largest IoUs is within 1e-5 of an integer (the two sides' IoUs
+         agree to 2e-6, ten of them are summed)."""
+    from oracle import box_ops
+    dyn, sums, mm, srt = sel
+    G, P = cost.shape
+    theirs = []
+    if lab_x > 0:
+        enc = box_ops.point_encode(allp[p][None, :], gtl[:, :4]).astype(np.float32)
+        theirs = [g for g in range(G) if int(gtl[g, 4]) == lab_x and np.array_equal(enc[g], tgt_x)]
+    one_sided = [g for g in theirs if not mm[g, p]] + [g for g in np.nonzero(mm[:, p])[0] if g not in theirs]
+    for g in one_sided:
+        c = cost[g, p]
+        kth = [srt[g, dyn[g] - 1]] + ([srt[g, dyn[g]]] if dyn[g] < P else [])
+        if min(abs(float(c) - float(t)) for t in kth) <= ota_cost_tol(c):
+            return "a"
+    if G >= 2:
+        two = np.sort(cost[:, p])[:2]
+        if float(two[1]) - float(two[0]) <= ota_cost_tol(two[0]):
+            return "b"
+    for g in one_sided:
+        if abs(float(sums[g]) - round(float(sums[g]))) <= 1e-5:
+            return "c"
+    return None
+
+
+def ota_topk_compare(prob, ref, lab_x, tgt_x):
+    """The label maps of ref = ota_ground_truth(...) (top-k) and of another evaluation of the same problem: (number of foreground
+    points of the oracle, the cap on differing points, [(image, point, excuse)] of every differing point)."""
+    lab_o, _, _, aux = ref
+    nfg = int((lab_o > 0).sum())
+    out = []
+    sels = {}
+    for n, p in np.argwhere(lab_x != lab_o):
+        G = int(prob["num"][n])
+        if n not in sels:
+            sels[n] = ota_topk_selection(aux[n][0], aux[n][1], OTA_ARGS[4])
+        out.append((int(n), int(p), ota_topk_excuse(p, int(lab_o[n, p]), int(lab_x[n, p]), tgt_x[n, p], prob["allp"], prob["gt"][n, :G],
+                                                    aux[n][0], sels[n])))
+    return nfg, max(1, int(0.005 * nfg)), out
