@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 104              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries)
+ABI_VERSION = 105              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -127,6 +127,8 @@ SIGNATURES = {
     "bd_focal_loss_fwd_bwd_general": (_I, [_P, _P, _L, _I, _F, _F, _P, _I, _F, _P, _P, _P]),
     "bd_focal_loss_fwd_bwd_ld": (_I, [_P, _P, _L, _I, _I, _F, _F, _P, _I, _F, _P, _P, _I, _P]),
     "bd_smooth_l1_fwd_bwd": (_I, [_P, _P, _P, _L, _I, _I, _F, _P, _I, _F, _P, _P, _P]),
+    "bd_loss_grid_cap": (_I, []),
+    "bd_iou_ltrb_fwd_bwd": (_I, [_P, _P, _P, _P, _L, _I, _P, _F, _P, _P, _P]),
     "bd_giou_ltrb_fwd_bwd": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _P, _P]),
     "bd_bce_logits_fwd_bwd": (_I, [_P, _I, _I, _P, _P, _L, _P, _P, _P, _P]),
     "bd_groupnorm_workspace_bytes": (_Z, [_I, _I, _I, _L]),

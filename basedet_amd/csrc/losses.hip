@@ -274,11 +274,27 @@ __global__ __launch_bounds__(256) void smooth_l1_kernel(const bf16_raw* __restri
     if (threadIdx.x == 0) partial[blockIdx.x] = s * gs;
 }
 
-// iou_loss(box_mode="ltrb", loss_type="giou") (layers/losses/iou_loss.py:9-56, 59-105), weighted by centerness
-__global__ __launch_bounds__(256) void giou_ltrb_kernel(const bf16_raw* __restrict__ pred, const float* __restrict__ target,
-                                                        const float* __restrict__ wgt, const int* __restrict__ labels,
-                                                        long long rows, const float* __restrict__ norm, float loss_weight,
-                                                        float* __restrict__ partial, bf16_raw* __restrict__ dpred) {
+// iou_loss(box_mode="ltrb", loss_type=...) (layers/losses/iou_loss.py:9-56, 59-105), weighted by centerness.  LT: the loss type codes of
+// bd_iou_loss_ltrb -- 0 "iou" -log(max(iou, eps)), 1 "linear_iou" 1 - iou, 2 "giou" 1 - giou, 3 "square_iou" 1 - iou^2.  Only LT == 2
+// computes the hull; its arithmetic is that of the giou-only kernel this one generalises (same operations in the same order).
+constexpr int IOU_LT_IOU = 0, IOU_LT_LINEAR = 1, IOU_LT_GIOU = 2, IOU_LT_SQUARE = 3;
+
+// The hull of pred and target (p, t: l, t, r, b), which only "giou" has: width, height, area, the area clipped at eps, and giou itself.
+template <bool GIOU> struct LtrbHull {
+    __device__ LtrbHull(const float*, const f32x4_t&, float, float, float) {}
+};
+template <> struct LtrbHull<true> {
+    float gw, gh, ac, acc_, giou;
+    __device__ LtrbHull(const float* p, const f32x4_t& t, float au, float iou, float eps)
+        : gw(fmaxf(p[2], t[2]) + fmaxf(p[0], t[0])), gh(fmaxf(p[3], t[3]) + fmaxf(p[1], t[1])), ac(gw * gh), acc_(fmaxf(ac, eps)),
+          giou(iou - (ac - au) / acc_) {}
+};
+
+template <int LT>
+__global__ __launch_bounds__(256) void iou_ltrb_kernel(const bf16_raw* __restrict__ pred, const float* __restrict__ target,
+                                                       const float* __restrict__ wgt, const int* __restrict__ labels,
+                                                       long long rows, const float* __restrict__ norm, float loss_weight,
+                                                       float* __restrict__ partial, bf16_raw* __restrict__ dpred) {
     __shared__ float red[4];
     const float eps = 1e-8f;
     const float gs = loss_weight / fmaxf(*norm, 1.f);
@@ -302,14 +318,17 @@ __global__ __launch_bounds__(256) void giou_ltrb_kernel(const bf16_raw* __restri
             const float au = a1 + a2 - ai;
             const float auc = fmaxf(au, eps);
             const float iou = ai / auc;
-            // hull
-            const float gw = fmaxf(p[2], t[2]) + fmaxf(p[0], t[0]);
-            const float gh = fmaxf(p[3], t[3]) + fmaxf(p[1], t[1]);
-            const float ac = gw * gh;
-            const float acc_ = fmaxf(ac, eps);
-            const float giou = iou - (ac - au) / acc_;
+            const LtrbHull<LT == IOU_LT_GIOU> h(p, t, au, iou, eps);
             const float w = wgt ? wgt[i] : 1.f;
-            acc += (1.f - giou) * w;
+            if constexpr (LT == IOU_LT_GIOU) {
+                acc += (1.f - h.giou) * w;
+            } else if constexpr (LT == IOU_LT_LINEAR) {
+                acc += (1.f - iou) * w;
+            } else if constexpr (LT == IOU_LT_SQUARE) {
+                acc += (1.f - iou * iou) * w;
+            } else {
+                acc += -logf(fmaxf(iou, eps)) * w;
+            }
             // gradients w.r.t. p[k]; index k: 0 l, 1 t, 2 r, 3 b   (l,r are "x" sides, t,b are "y" sides)
             float g[4];
 #pragma unroll
@@ -321,11 +340,19 @@ __global__ __launch_bounds__(256) void giou_ltrb_kernel(const bf16_raw* __restri
                 const float dau = da1 - dai;
                 const float dauc = au > eps ? dau : 0.f;
                 const float diou = (dai * auc - ai * dauc) / (auc * auc);
-                const float dmax = p[k] > t[k] ? 1.f : 0.f;                 // d max(p,t)/dp
-                const float dac = isx ? dmax * gh : dmax * gw;
-                const float dacc = ac > eps ? dac : 0.f;
-                const float dterm = ((dac - dau) * acc_ - (ac - au) * dacc) / (acc_ * acc_);
-                g[k] = -(diou - dterm) * w * gs;
+                if constexpr (LT == IOU_LT_GIOU) {
+                    const float dmax = p[k] > t[k] ? 1.f : 0.f;             // d max(p,t)/dp
+                    const float dac = isx ? dmax * h.gh : dmax * h.gw;
+                    const float dacc = h.ac > eps ? dac : 0.f;
+                    const float dterm = ((dac - dau) * h.acc_ - (h.ac - au) * dacc) / (h.acc_ * h.acc_);
+                    g[k] = -(diou - dterm) * w * gs;
+                } else if constexpr (LT == IOU_LT_LINEAR) {
+                    g[k] = -diou * w * gs;
+                } else if constexpr (LT == IOU_LT_SQUARE) {
+                    g[k] = -2.f * iou * diou * w * gs;
+                } else {
+                    g[k] = iou > eps ? -diou / iou * w * gs : 0.f;          // (max(iou, eps) has slope 0 at and below eps)
+                }
             }
             o[0] = pack_bf2(g[0], g[1]);
             o[1] = pack_bf2(g[2], g[3]);
@@ -491,10 +518,12 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
     }
 }
 
+constexpr int LOSS_GRID_CAP = 4096;     // blocks of 256 threads; the kernels stride over what is left
+
 inline int loss_grid(long long n) {
     long long g = (n + 255) / 256;
     if (g < 1) g = 1;
-    return (int)(g < 4096 ? g : 4096);
+    return (int)(g < LOSS_GRID_CAP ? g : LOSS_GRID_CAP);
 }
 
 }  // namespace
@@ -592,18 +621,30 @@ extern "C" int bd_smooth_l1_fwd_bwd(const void* pred, const float* target, const
     return BD_OK;
 }
 
+extern "C" int bd_loss_grid_cap(void) { return LOSS_GRID_CAP; }
+
+extern "C" int bd_iou_ltrb_fwd_bwd(const void* pred, const float* target, const float* weight, const int32_t* labels,
+                                   int64_t rows, int loss_type, const float* norm, float loss_weight, float* loss_sum, void* dpred,
+                                   bd_stream_t stream) {
+    BD_REQUIRE(pred && target && labels && norm && loss_sum && dpred, "iou_ltrb: null pointer");
+    BD_REQUIRE(loss_type >= 0 && loss_type <= 3, "iou_ltrb: loss_type %d (0 iou, 1 linear_iou, 2 giou, 3 square_iou)", loss_type);
+    if (rows == 0) return BD_OK;
+    const int grid = loss_grid(rows);
+    BD_LOSS_PARTIALS(part, stream, grid, "iou_ltrb");
+    auto kernel = loss_type == IOU_LT_GIOU ? iou_ltrb_kernel<IOU_LT_GIOU> : loss_type == IOU_LT_LINEAR ? iou_ltrb_kernel<IOU_LT_LINEAR>
+                : loss_type == IOU_LT_SQUARE ? iou_ltrb_kernel<IOU_LT_SQUARE> : iou_ltrb_kernel<IOU_LT_IOU>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)pred,
+                       target, weight, labels, (long long)rows, norm, loss_weight, part, (bf16_raw*)dpred);
+    loss_finalize(part, grid, 1, loss_sum, stream);
+    BD_CHECK_LAUNCH("bd_iou_ltrb_fwd_bwd");
+    return BD_OK;
+}
+
+// loss_type "giou" of bd_iou_ltrb_fwd_bwd
 extern "C" int bd_giou_ltrb_fwd_bwd(const void* pred, const float* target, const float* weight, const int32_t* labels,
                                     int64_t rows, const float* norm, float loss_weight, float* loss_sum, void* dpred,
                                     bd_stream_t stream) {
-    BD_REQUIRE(pred && target && labels && norm && loss_sum && dpred, "giou_ltrb: null pointer");
-    if (rows == 0) return BD_OK;
-    const int grid = loss_grid(rows);
-    BD_LOSS_PARTIALS(part, stream, grid, "giou_ltrb");
-    hipLaunchKernelGGL(giou_ltrb_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)pred,
-                       target, weight, labels, (long long)rows, norm, loss_weight, part, (bf16_raw*)dpred);
-    loss_finalize(part, grid, 1, loss_sum, stream);
-    BD_CHECK_LAUNCH("bd_giou_ltrb_fwd_bwd");
-    return BD_OK;
+    return bd_iou_ltrb_fwd_bwd(pred, target, weight, labels, rows, IOU_LT_GIOU, norm, loss_weight, loss_sum, dpred, stream);
 }
 
 extern "C" int bd_bce_logits_fwd_bwd(const void* pred, int ld, int off, const float* target, const int32_t* labels, int64_t rows,

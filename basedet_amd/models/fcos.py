@@ -1,5 +1,5 @@
 """FCOS (basedet/models/det/fcos.py) on the HIP path: PointHead (GroupNorm towers, per-level scales, centre-ness) +
-point target assignment + focal / GIoU / BCE losses on the shared ResNet-FPN trunk.
+point target assignment + focal / IoU (MODEL.LOSSES.IOU_LOSS_TYPE) / BCE losses on the shared ResNet-FPN trunk.
 
 ``model(batch)`` returns ``{"total_loss", "cls_loss", "reg_loss", "ctr_loss"}`` (fcos.py:173-178).
 Data-parallel detail (fcos.py:143-144): ``num_fg`` and ``sum_ctr`` are all-reduced (mean) across ranks before the losses
@@ -26,11 +26,19 @@ class FCOS(FPNDetector):
     def init_params(cfg, seed=0):
         return P.init_fcos_params(cfg, seed)
 
+    @classmethod
+    def check_config(cls, cfg):
+        super().check_config(cfg)
+        t = cfg.MODEL.LOSSES.IOU_LOSS_TYPE
+        if not isinstance(t, str) or t not in ops.IOU_LOSS_TYPES:                  # iou_loss's own set (layers/losses/iou_loss.py:78)
+            raise ValueError(f"MODEL.LOSSES.IOU_LOSS_TYPE = {t!r} is not supported: use one of {', '.join(map(repr, ops.IOU_LOSS_TYPES))}")
+
     # ---- construction ------------------------------------------------------------------------------------
     def _build_head(self, add, params):
         """PointHead (layers/head/point_head.py:40-105)."""
         m = self.cfg.MODEL
         ch = self.fpn_ch
+        self.iou_loss_type = ops.IOU_LOSS_TYPES[m.LOSSES.IOU_LOSS_TYPE]           # the regression loss of get_losses (FCOS, ATSS and OTA)
         assert m.ANCHOR.NUM_ANCHORS == 1, "the HIP PointHead path supports one anchor point per location"
         assert ch == 256, "GroupNorm kernel: 32 groups x 8 channels"
         nc = m.HEAD.NUM_CONVS
@@ -148,11 +156,10 @@ class FCOS(FPNDetector):
             self._allreduce_stats(c, pl.stats)                         # all_reduce(mode="mean") of num_fg and sum_ctr (fcos.py:143-144)
         pl.loss_buf.zero_()
         rows = pl.N * pl.pyr.pix_per_img
-        assert m.LOSSES.IOU_LOSS_TYPE == "giou", "HIP FCOS path implements the giou ltrb loss"
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA,
                                pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self._ld())
-        ops.giou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, pl.gt_ctr, pl.labels, rows, pl.stats[1:2], m.LOSSES.REG_LOSS_WEIGHT,
-                              pl.loss_buf[1:2], pl.d_off)
+        ops.iou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, pl.gt_ctr, pl.labels, rows, self.iou_loss_type, pl.stats[1:2],
+                             m.LOSSES.REG_LOSS_WEIGHT, pl.loss_buf[1:2], pl.d_off)
         ops.bce_logits_fwd_bwd(pl.raw, pl.gt_ctr, pl.labels, rows, pl.stats[0:1], pl.loss_buf[2:3], pl.d_ctr, ld=8, off=4)
         cls_loss, reg_loss, ctr_loss = pl.loss_buf[0], pl.loss_buf[1], pl.loss_buf[2]
         return {"total_loss": cls_loss + reg_loss + ctr_loss, "cls_loss": cls_loss, "reg_loss": reg_loss, "ctr_loss": ctr_loss}
@@ -283,10 +290,10 @@ class OTA(FCOS):
             self._allreduce_stats(c, pl.stats)                         # all_reduce(num_foreground, mode="mean") (ota.py:200)
         pl.loss_buf.zero_()
         rows = pl.N * pl.pyr.pix_per_img
-        assert m.LOSSES.IOU_LOSS_TYPE == "giou", "HIP OTA path implements the giou ltrb loss"
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA,
                                pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self._ld())
-        ops.giou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, None, pl.labels, rows, pl.stats[0:1], 2.0, pl.loss_buf[1:2], pl.d_off)
+        ops.iou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, None, pl.labels, rows, self.iou_loss_type, pl.stats[0:1], 2.0, pl.loss_buf[1:2],
+                             pl.d_off)
         ops.bce_logits_fwd_bwd(pl.raw, pl.gt_ctr, pl.labels, rows, pl.stats[1:2], pl.loss_buf[2:3], pl.d_ctr, ld=8, off=4)
         loss_cls, loss_box, loss_iou = pl.loss_buf[0], pl.loss_buf[1], pl.loss_buf[2]
         return {"total_loss": loss_cls + loss_box + loss_iou, "loss_cls": loss_cls, "loss_offsets": loss_box, "loss_ious": loss_iou}

@@ -752,6 +752,20 @@ def smooth_l1_fwd_bwd(pred, target, labels, pixels, A, ld, beta, norm, weight, l
           "bd_smooth_l1_fwd_bwd")
 
 
+def loss_grid_cap():
+    """Blocks of 256 threads the loss launches run at most; past 256 x this many rows a thread walks more than one."""
+    return int(L().bd_loss_grid_cap())
+
+
+IOU_LOSS_TYPES = {"iou": 0, "linear_iou": 1, "giou": 2, "square_iou": 3}     # iou_loss's loss_type (layers/losses/iou_loss.py:78)
+
+
+def iou_ltrb_fwd_bwd(pred, target, weight, labels, rows, loss_type, norm, loss_weight, loss_sum, dpred):
+    """loss_type: a code of IOU_LOSS_TYPES."""
+    check(L().bd_iou_ltrb_fwd_bwd(ptr(pred), ptr(target), ptr(weight), ptr(labels), rows, int(loss_type), ptr(norm), float(loss_weight),
+                                  ptr(loss_sum), ptr(dpred), stream_ptr()), "bd_iou_ltrb_fwd_bwd")
+
+
 def giou_ltrb_fwd_bwd(pred, target, weight, labels, rows, norm, loss_weight, loss_sum, dpred):
     check(L().bd_giou_ltrb_fwd_bwd(ptr(pred), ptr(target), ptr(weight), ptr(labels), rows, ptr(norm), float(loss_weight),
                                    ptr(loss_sum), ptr(dpred), stream_ptr()), "bd_giou_ltrb_fwd_bwd")

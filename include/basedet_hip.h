@@ -502,6 +502,10 @@ int bd_focal_loss_fwd_bwd_ld(const void* logits, const int32_t* labels, int64_t 
                              const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, int general,
                              bd_stream_t stream);
 
+/* (bd_version() >= 105) The focal, smooth-L1, IoU and BCE launches of this section run at most this many blocks of 256 threads; past
+ * 256 x that many work items (rows for the IoU and BCE losses) a thread strides over more than one. */
+int bd_loss_grid_cap(void);
+
 /* smooth_l1_loss (layers/losses/smooth_l1_loss.py:7-34) over rows with label > 0 (retinanet.py:158-162).
  * Row r = pixel*A + a; pred/dpred are bf16 with `ld` channels per pixel (ld >= 4*A, ld % 4 == 0), element
  * (r, k) at pixel*ld + a*4 + k; pad channels of dpred are written as zero.  target fp32 [rows][4]. */
@@ -509,8 +513,14 @@ int bd_smooth_l1_fwd_bwd(const void* pred, const float* target, const int32_t* l
                          int ld, float beta, const void* norm, int norm_is_float, float weight, float* loss_sum,
                          void* dpred, bd_stream_t stream);
 
-/* iou_loss(box_mode="ltrb", loss_type="giou") * ctrness weight (layers/losses/iou_loss.py:9-105,
- * models/det/fcos.py:157-164); norm = max(1, sum_ctr). */
+/* (bd_version() >= 105) iou_loss(box_mode="ltrb", loss_type=MODEL.LOSSES.IOU_LOSS_TYPE) * weight (layers/losses/iou_loss.py:9-105, models/det/fcos.py:157-164,
+ * models/det/ota.py:211-216) on the rows with labels > 0: loss_sum[0] = loss_weight / max(1, *norm) * sum(loss * weight), dpred its bf16
+ * gradient (zero rows for labels <= 0).  pred [rows][4] bf16 l, t, r, b; weight NULL = 1.  loss_type as bd_iou_loss_ltrb, eps = 1e-8:
+ * 0 "iou" (-log max(iou, eps); zero gradient where iou <= eps), 1 "linear_iou" (1 - iou), 2 "giou" (1 - giou), 3 "square_iou" (1 - iou^2);
+ * any other code: BD_EINVAL, nothing launched. */
+int bd_iou_ltrb_fwd_bwd(const void* pred, const float* target, const float* weight, const int32_t* labels, int64_t rows, int loss_type,
+                        const float* norm, float loss_weight, float* loss_sum, void* dpred, bd_stream_t stream);
+/* bd_iou_ltrb_fwd_bwd with loss_type 2 ("giou"); norm = max(1, sum_ctr) in FCOS. */
 int bd_giou_ltrb_fwd_bwd(const void* pred, const float* target, const float* weight, const int32_t* labels,
                          int64_t rows, const float* norm, float loss_weight, float* loss_sum, void* dpred,
                          bd_stream_t stream);
