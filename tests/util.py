@@ -656,3 +656,183 @@ def ota_topk_compare(prob, ref, lab_x, tgt_x):
         out.append((int(n), int(p), ota_topk_excuse(p, int(lab_o[n, p]), int(lab_x[n, p]), tgt_x[n, p], prob["allp"], prob["gt"][n, :G],
                                                     aux[n][0], sels[n])))
     return nfg, max(1, int(0.005 * nfg)), out
+
+
+# ---- guard bands (tests/test_guard_cpu.py, tests/test_guard_gpu.py) --------------------------------------------------------------------
+# A kernel test that allocates its operands at exactly their logical size cannot see a load or store that runs past them: the caching
+# allocator rounds every block up, and the stray access lands in padding nobody inspects.  guarded() puts a tensor between two guards
+# of a known bit pattern inside ONE allocation the test owns; gapped_geom() does the same between the levels and images of a pixel-major
+# pyramid.  Everything is compared as integer bit patterns (NaN != NaN).
+GUARD_MIN_ROWS = 512
+GUARD_MIN_BYTES = 4096
+GUARD_ALIGN = 256                        # the interior keeps the alignment the 16-byte vector / buffer loads of the library assume
+FILLS = ("zero", "nan", "max")           # what an INPUT's guards and gaps hold; outputs hold "sentinel"
+_INT_OF_SIZE = {1: torch.uint8, 2: torch.int16, 4: torch.int32}
+# (even element, odd element) bit patterns.  nan: the quiet NaN of the format (e4m3 bytes: 0x7f).  max: the largest finite value, sign
+# alternating (fmaxf drops a NaN: a max-pool that reads out of range passes a NaN-only test).  sentinel: a NaN with a payload no kernel
+# produces by accident (one-byte tensors: 0xff, NaN in e4m3 and e5m2, which the saturating quantisers never write).
+_PATTERNS = {
+    (torch.bfloat16, "nan"): (0x7FC0, 0x7FC0), (torch.bfloat16, "max"): (0x7F7F, 0xFF7F), (torch.bfloat16, "sentinel"): (0x7FA5, 0x7FA5),
+    (torch.float32, "nan"): (0x7FC00000, 0x7FC00000), (torch.float32, "max"): (0x7F7FFFFF, 0xFF7FFFFF),
+    (torch.float32, "sentinel"): (0x7FA5A5A5, 0x7FA5A5A5),
+    (torch.uint8, "nan"): (0x7F, 0x7F), (torch.uint8, "max"): (0x7E, 0xFE), (torch.uint8, "sentinel"): (0xFF, 0xFF),
+    # one-byte tensors that hold e5m2 (guarded(..., fmt="e5m2")): 0x7e is a NaN there, the largest finite value is 0x7b
+    ("e5m2", "nan"): (0x7F, 0x7F), ("e5m2", "max"): (0x7B, 0xFB), ("e5m2", "sentinel"): (0xFF, 0xFF),
+}
+
+
+def _signed(v, bits):
+    return v - (1 << bits) if bits > 8 and v >= 1 << (bits - 1) else v
+
+
+def fill_pattern(dtype, fill, n, device="cpu", fmt=None):
+    """n elements of the fill's bit pattern, as the integer dtype of the same width.  fmt: the number format a one-byte tensor holds
+    ("e5m2"; default e4m3)."""
+    it = _INT_OF_SIZE[torch.empty(0, dtype=dtype).element_size()]
+    if fill == "zero":
+        return torch.zeros(n, dtype=it, device=device)
+    bits = 8 * torch.empty(0, dtype=dtype).element_size()
+    even, odd = (_signed(v, bits) for v in _PATTERNS[(fmt or dtype, fill)])
+    out = torch.full((n,), even, dtype=it, device=device)
+    out[1::2] = odd
+    return out
+
+
+def guard_rows_for(row_bytes, guard_rows=None):
+    """Rows of one guard: at least GUARD_MIN_ROWS (or guard_rows) and GUARD_MIN_BYTES, rounded up to a multiple of GUARD_ALIGN bytes."""
+    g = max(guard_rows or GUARD_MIN_ROWS, -(-GUARD_MIN_BYTES // row_bytes))
+    step = GUARD_ALIGN // math.gcd(row_bytes, GUARD_ALIGN)
+    return -(-g // step) * step
+
+
+def bits_of(t):
+    """The integer view of a tensor's bit patterns."""
+    return t.view(_INT_OF_SIZE[t.element_size()])
+
+
+def count_sentinel(t):
+    """Elements of t that still hold the output sentinel."""
+    return int((bits_of(t) == int(fill_pattern(t.dtype, "sentinel", 1)[0])).sum())
+
+
+class GuardError(AssertionError):
+    pass
+
+
+class Guarded:
+    """One allocation [front guard | interior | back guard]; .t is the interior: (rows, cols), or (rows,) for cols=None.  Gap rows of a
+    gapped geometry (set_gaps) are part of the interior and are checked like the guards."""
+    PLACES = ("front guard", "back guard", "level gap", "image gap")
+
+    def __init__(self, rows, cols, dtype, device, guard_rows, fill, name, fmt=None):
+        self.name, self.dtype, self.fill, self.fmt = name, dtype, fill, fmt
+        self.rows, self.cols = rows, (1 if cols is None else cols)
+        es = torch.empty(0, dtype=dtype).element_size()
+        self.g = guard_rows_for(self.cols * es, guard_rows)
+        slack = GUARD_ALIGN // es
+        n = (2 * self.g + rows) * self.cols
+        self.store = torch.empty(n + slack, dtype=dtype, device=device)
+        lead = (-self.store.data_ptr() % GUARD_ALIGN) // es             # host allocations are not 256-byte aligned by themselves
+        self.whole = self.store[lead:lead + n]
+        bits_of(self.whole).copy_(fill_pattern(dtype, fill, n, device, fmt))
+        self._rows2d = self.whole.view(2 * self.g + rows, self.cols)
+        inner = self._rows2d[self.g:self.g + rows]
+        self.t = inner.view(rows) if cols is None else inner
+        self.kind = None
+        self._snap = None
+
+    def _row_pattern(self, first_elem):
+        """(1, cols) bit pattern of a row whose first element has flat index `first_elem` in the allocation (the sign alternates per element)."""
+        p = fill_pattern(self.dtype, self.fill, self.cols + 1, self.whole.device, self.fmt)
+        return p[first_elem % 2:first_elem % 2 + self.cols].view(1, -1)
+
+    def set(self, data):
+        """Copy data into the interior (before set_gaps: the gaps are filled afterwards)."""
+        self.t.copy_(data.to(self.t.device).view_as(self.t))
+        return self
+
+    def set_gaps(self, kind):
+        """kind (rows,) int8: 0 = a row some level owns, 1 = a row between two levels, 2 = a row behind an image's last level.  The gap rows
+        get the fill and are checked from now on."""
+        assert kind.numel() == self.rows
+        self.kind = kind.to(self.whole.device)
+        rows = torch.nonzero(self.kind > 0).view(-1)
+        body = bits_of(self._rows2d[self.g:self.g + self.rows])
+        if self.cols % 2 == 0 or self.fill != "max":
+            body[rows] = self._row_pattern(0).expand(rows.numel(), -1)
+        else:
+            par = ((rows + self.g) * self.cols) % 2
+            p = fill_pattern(self.dtype, self.fill, self.cols + 1, self.whole.device, self.fmt)
+            body[rows] = torch.where(par.view(-1, 1) == 0, p[:self.cols].view(1, -1), p[1:].view(1, -1))
+        return self
+
+    def _regions(self):
+        """[(place, first row in the allocation, rows tensor or None for a contiguous block, row count)]"""
+        out = [("front guard", 0, None, self.g), ("back guard", self.g + self.rows, None, self.g)]
+        if self.kind is not None:
+            for place, k in (("level gap", 1), ("image gap", 2)):
+                rows = torch.nonzero(self.kind == k).view(-1)
+                if rows.numel():
+                    out.append((place, self.g, rows, rows.numel()))
+        return out
+
+    def check(self, ignore=()):
+        """Raise GuardError unless both guards and every gap row hold the fill, bit for bit.  ignore: places to leave out (only the helper's
+        own test uses it, to show that each place is looked at)."""
+        whole = bits_of(self._rows2d)
+        for place, r0, rows, cnt in self._regions():
+            if place in ignore:
+                continue
+            got = whole[r0:r0 + cnt] if rows is None else whole[r0 + rows]
+            idx = torch.arange(r0, r0 + cnt, device=whole.device) if rows is None else r0 + rows
+            if self.cols % 2 == 0 or self.fill != "max":
+                want = self._row_pattern(0)
+            else:
+                p = fill_pattern(self.dtype, self.fill, self.cols + 1, whole.device, self.fmt)
+                want = torch.where(((idx * self.cols) % 2).view(-1, 1) == 0, p[:self.cols].view(1, -1), p[1:].view(1, -1))
+            bad = got != want
+            nbad = int(bad.sum())
+            if nbad:
+                first = int(torch.nonzero(bad.any(1)).view(-1)[0])
+                row = int(idx[first]) - (0 if place == "front guard" else self.g + self.rows if place == "back guard" else self.g)
+                col = int(torch.nonzero(bad[first]).view(-1)[0])
+                raise GuardError(f"{self.name}: {place} changed: {nbad} element(s), first at row {row} (column {col}) of the "
+                                 f"{'guard' if 'guard' in place else 'interior'}; fill {self.fill!r}")
+
+    def snapshot(self):
+        """Remember every bit of the allocation (inputs: guards, gaps and data must come back unchanged)."""
+        self._snap = bits_of(self.whole).clone()
+        return self
+
+    def assert_unchanged(self):
+        self.check()
+        same = bits_of(self.whole) == self._snap
+        if not bool(same.all()):
+            bad = torch.nonzero(~same.view(-1)).view(-1)
+            raise GuardError(f"{self.name}: input changed: {bad.numel()} element(s), first at interior row "
+                             f"{int(bad[0]) // self.cols - self.g} (column {int(bad[0]) % self.cols})")
+
+
+def guarded(rows, cols, dtype, device, guard_rows=None, fill="sentinel", name="tensor", fmt=None):
+    """(interior view, handle): a contiguous (rows, cols) tensor -- (rows,) elements with cols=None -- inside one larger allocation whose
+    guards in front and behind are each >= 512 rows and >= 4 KiB, a multiple of 256 bytes, and hold `fill` (the interior too, until it is
+    written).  handle.check() compares the guards with the fill as integers.  fmt="e5m2": a one-byte tensor of e5m2 numbers (its +-max differs)."""
+    h = Guarded(rows, cols, dtype, device, guard_rows, fill, name, fmt)
+    return h.t, h
+
+
+def gapped_geom(N, levels, gap=GUARD_MIN_ROWS):
+    """An ops.Geom of `levels` [(H, W)] per image in which `gap` rows that no level owns follow every level: off[i] leaves them between
+    levels, pix_per_img behind the last level of every image.  Returns (geom, kind): kind (N * pix_per_img,) int8 on the CPU, 0 = owned,
+    1 = gap between two levels, 2 = gap behind an image's last level (Guarded.set_gaps)."""
+    from basedet_amd import ops
+    off, o = [], 0
+    for h, w in levels:
+        off.append(o)
+        o += h * w + gap
+    geom = ops.Geom(N, [h for h, _ in levels], [w for _, w in levels], off, o)
+    kind = torch.ones(N, o, dtype=torch.int8)
+    for i, (h, w) in enumerate(levels):
+        kind[:, off[i]:off[i] + h * w] = 0
+    kind[:, off[-1] + levels[-1][0] * levels[-1][1]:] = 2
+    return geom, kind.view(-1)
