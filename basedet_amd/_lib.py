@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 105              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap)
+ABI_VERSION = 106              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -176,6 +176,11 @@ SIGNATURES = {
     "bd_ema_update": (_I, [_P, _P, _L, _F, _F, _P]),
     "bd_sgd_momentum_ema_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P]),
     "bd_swap_f32": (_I, [_P, _P, _L, _P]),
+    # (w, m, v, g[, e], n, lr, beta1, 1 - beta1, beta2, 1 - beta2, bc1, bc2, eps, wd, grad_scale, decoupled[, ema_m, 1 - ema_m], stream)
+    "bd_adam_step": (_I, [_P, _P, _P, _P, _L] + [_F] * 10 + [_I, _P]),
+    "bd_adam_ema_step": (_I, [_P, _P, _P, _P, _P, _L] + [_F] * 10 + [_I, _F, _F, _P]),
+    "bd_sgd_nesterov_step": (_I, [_P, _P, _P, _L, _F, _F, _F, _F, _P]),
+    "bd_sgd_nesterov_ema_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P]),
     "bd_clip_grad_value": (_I, [_P, _L, _F, _F, _F, _P]),
     "bd_clip_grad_norm_workspace_bytes": (_Z, []),
     "bd_clip_grad_norm": (_I, [_P, _L, _F, _F, _F, _P, _P, _Z, _P]),

@@ -16,6 +16,9 @@ SOURCES = {
     "image_ops.hip": [],
     "image_resize.hip": ["-ffp-contract=off"],
     "ema.hip": [],
+    # one fp32 rounding per operation (tests/test_optim_gpu.py compares bits with numpy): no FMA contraction, IEEE division and square
+    # root (hipcc's default, stated because the tests depend on it)
+    "optim.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "h2d.hip": [],
     "conv_igemm.hip": [],
     "conv3x3.hip": [],

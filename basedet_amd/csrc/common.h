@@ -102,6 +102,17 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- moving average of a weight (ema.hip, and the optimizer launches of ema.hip / optim.hip that fold it in) -----------------------------
+// ema.py:80: v * m + (1 - m) * model_state -- each product rounded to fp32, then the sum; never an FMA (the compiler contracts a * b + c by
+// default, and __fmul_rn / __fadd_rn are plain operators here, so the function switches contraction off).  (1 - m) arrives as an
+// argument: the reference forms it in Python float64 before the cast.  m = 0 takes the same three operations.
+__device__ __forceinline__ float ema_elem(float e, float w, float m, float one_minus_m) {
+#pragma clang fp contract(off)
+    const float a = e * m;
+    const float b = one_minus_m * w;
+    return a + b;
+}
+
 // ---- in-kernel clock probe (bd_probe_kernel_clock) -----------------------------------------------------------------------------------
 // The chip lowers its clock under MFMA-dense load (MI355X_MICROARCH.md, DVFS give-back), so a TFLOP/s figure is (in-cycle efficiency) x
 // (held clock).  The two dominant MFMA-bound kernels carry this probe in the SHIPPED build: lane 0 of workgroup 0 reads the shader-cycle

@@ -5,16 +5,7 @@
 
 namespace {
 
-// ema.py:80: v * m + (1 - m) * model_state -- each product rounded to fp32, then the sum; never an FMA (the compiler contracts a * b + c by
-// default, and __fmul_rn / __fadd_rn are plain operators here, so the block switches contraction off).  (1 - m) arrives as an
-// argument: the reference forms it in Python float64 before the cast.  m = 0 takes the same three operations.
-__device__ __forceinline__ float ema_elem(float e, float w, float m, float one_minus_m) {
-#pragma clang fp contract(off)
-    const float a = e * m;
-    const float b = one_minus_m * w;
-    return a + b;
-}
-
+// ema_elem (common.h): ema.py:80, both products and the sum rounded to fp32, never an FMA
 __global__ void ema_kernel(float* __restrict__ e, const float* __restrict__ w, long long n, float m, float one_minus_m) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i * 4 < n; i += (long long)gridDim.x * blockDim.x) {
         const long long o = i * 4;

@@ -870,6 +870,45 @@ def swap_f32(a, b):
     check(L().bd_swap_f32(ptr(a), ptr(b), a.numel(), stream_ptr()), "bd_swap_f32")
 
 
+def adam_coeffs(betas, step):
+    """(beta1, 1 - beta1, beta2, 1 - beta2, 1 - beta1**step, 1 - beta2**step): the differences and the bias corrections of step `step`
+    (counted from 1) are taken in Python float64, the cast to fp32 happens at the C boundary -- the way `ema_coeffs` hands 1 - m over."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    return b1, 1 - b1, b2, 1 - b2, 1 - b1 ** step, 1 - b2 ** step
+
+
+def adam_step(w, m, v, g, lr, betas, eps, wd, step, grad_scale=1.0, decoupled=False):
+    """megengine.optimizer.Adam (`decoupled` False: wd * w joins the gradient) / AdamW (True: it joins the update) over fp32 buffers of one
+    length in one launch (bd_adam_step); `m`, `v`: the first and second moments, `step`: this update's number, from 1."""
+    _same_f32(w, m, v, g)
+    check(L().bd_adam_step(ptr(w), ptr(m), ptr(v), ptr(g), w.numel(), float(lr), *adam_coeffs(betas, step), float(eps), float(wd),
+                           float(grad_scale), int(bool(decoupled)), stream_ptr()), "bd_adam_step")
+
+
+def adam_ema_step(w, m, v, g, e, lr, betas, eps, wd, step, grad_scale, decoupled, ema_m):
+    """`adam_step`, then `ema_update(e, w, ema_m)` with the new weights, in the same launch (bd_adam_ema_step)."""
+    _same_f32(w, m, v, g, e)
+    mm, om = ema_coeffs(ema_m)
+    check(L().bd_adam_ema_step(ptr(w), ptr(m), ptr(v), ptr(g), ptr(e), w.numel(), float(lr), *adam_coeffs(betas, step), float(eps),
+                               float(wd), float(grad_scale), int(bool(decoupled)), mm, om, stream_ptr()), "bd_adam_ema_step")
+
+
+def sgd_nesterov_step(w, v, g, lr, momentum, wd, grad_scale=1.0):
+    """megengine.optimizer.SGD(nesterov=True): g' = g*grad_scale + wd*w; v = momentum*v + g'; w -= lr*(g' + momentum*v)
+    (bd_sgd_nesterov_step)."""
+    _same_f32(w, v, g)
+    check(L().bd_sgd_nesterov_step(ptr(w), ptr(v), ptr(g), w.numel(), float(lr), float(momentum), float(wd), float(grad_scale),
+                                   stream_ptr()), "bd_sgd_nesterov_step")
+
+
+def sgd_nesterov_ema_step(w, v, g, e, lr, momentum, wd, grad_scale, m):
+    """`sgd_nesterov_step`, then `ema_update(e, w, m)` with the new weights, in the same launch (bd_sgd_nesterov_ema_step)."""
+    _same_f32(w, v, g, e)
+    mm, om = ema_coeffs(m)
+    check(L().bd_sgd_nesterov_ema_step(ptr(w), ptr(v), ptr(g), ptr(e), w.numel(), float(lr), float(momentum), float(wd),
+                                       float(grad_scale), mm, om, stream_ptr()), "bd_sgd_nesterov_ema_step")
+
+
 class WgradQueue:
     """bd_wgrad_queue_*: weight-gradient launches whose reduces are deferred to ONE launch per flush (the solver's gradient buckets).
     Every queued layer must keep its own workspace untouched until `flush`."""

@@ -1,6 +1,6 @@
 """DetSolver (basedet/solver/default_solver.py:79-124) + the basecore `Solver.minimize` step it returns.
 
-lr = BASIC_LR * BATCHSIZE * world_size for MEAN reduction (:99-106); SGD(momentum, weight_decay) over the
+lr = BASIC_LR * BATCHSIZE * world_size for MEAN reduction (:99-106); SOLVER.OPTIMIZER_NAME (SGD, Adam or AdamW, :47-55) over the
 trainable parameter arena in ONE fused launch; gradients are all-reduced (mean) over RCCL in arena buckets that
 follow the backward order (head -> FPN -> layer4 -> ... -> layer2) on the communicator's stream, overlapped with backward.
 The collectives are the bd_comm_* entry points of the C ABI (basedet_amd/comm.py); no c10d process group is involved.
@@ -17,29 +17,154 @@ class _ParamGroupView(dict):
     pass
 
 
-class SGD:
-    """megengine.optimizer.SGD semantics: g' = g + wd*w; v = momentum*v + g'; w -= lr*v (fused HIP kernel)."""
+def _moments_out(model, buf):
+    """An arena-shaped buffer as {reference parameter name: numpy array in the reference's shape}: `buf` trades places with the arena's
+    weights and the model's own export gathers it (layouts, fused predictors, PaddedClsConv's pad rows dropped) -- the way
+    ModelEMA.state_dict reads its average."""
+    w = model.arena.w
+    ops.swap_f32(buf, w)
+    try:
+        states = model.state_dict()
+    finally:
+        ops.swap_f32(buf, w)
+    return {k: states[k] for k in model.state_dict_trainable_names()}
 
-    def __init__(self, model, lr, weight_decay, momentum=0.9):
+
+def _moments_in(model, buf, values):
+    """The inverse of `_moments_out`, through the model's own binding code (pad rows come back as zeros); the live weights are untouched."""
+    own = model.state_dict()
+    trainable = set(model.state_dict_trainable_names())
+    missing = sorted(trainable - set(values))
+    if missing:
+        raise ValueError(f"optimizer state lacks {len(missing)} trainable parameter(s), e.g. {missing[0]!r}")
+    merged = {k: (values[k] if k in trainable else v) for k, v in own.items()}
+    w = model.arena.w
+    try:
+        ops.swap_f32(buf, w)
+        try:
+            model._bind_params(merged)
+        finally:
+            ops.swap_f32(buf, w)
+    finally:
+        model.repack_weights()
+
+
+class SGD:
+    """megengine.optimizer.SGD semantics: g' = g + wd*w; v = momentum*v + g'; w -= lr*v, or with `nesterov` w -= lr*(g' + momentum*v)
+    (fused HIP kernels)."""
+
+    def __init__(self, model, lr, weight_decay, momentum=0.9, nesterov=False):
+        if nesterov and momentum <= 0:                   # megengine/optimizer/sgd.py raises the same
+            raise ValueError("SGD: nesterov=True requires a momentum > 0")
         self.model = model
+        self.nesterov = bool(nesterov)
+        self.step_count = 0
         self.param_groups = [_ParamGroupView(lr=lr, weight_decay=weight_decay, momentum=momentum)]
 
     def step(self, grad_scale=1.0, ema=None):
         """`ema`: the trainer's ModelEMA (engine/trainer.py:98-100 steps it right after minimize).  Past its burn-in the average is
         updated from the new weights inside this launch (bd_sgd_momentum_ema_step; `ema.step()` then only counts); up to and including
-        the burn-in iteration, and without `ema`, the launch is the plain one."""
+        the burn-in iteration, and without `ema`, the launch is the plain one.  With `nesterov` the two launches are
+        bd_sgd_nesterov_step / bd_sgd_nesterov_ema_step."""
         a = self.model.arena
         g = self.param_groups[0]
         m = ema.fused_momentum() if ema is not None else None
+        plain, fused = (ops.sgd_nesterov_step, ops.sgd_nesterov_ema_step) if self.nesterov else \
+            (ops.sgd_momentum_step, ops.sgd_momentum_ema_step)
         if m is None:
-            ops.sgd_momentum_step(a.w, a.v, a.g, g["lr"], g["momentum"], g["weight_decay"], grad_scale)
+            plain(a.w, a.v, a.g, g["lr"], g["momentum"], g["weight_decay"], grad_scale)
         else:
-            ops.sgd_momentum_ema_step(a.w, a.v, a.g, ema.e, g["lr"], g["momentum"], g["weight_decay"], grad_scale, m)
+            fused(a.w, a.v, a.g, ema.e, g["lr"], g["momentum"], g["weight_decay"], grad_scale, m)
+        self.step_count += 1
         self.model.repack_trainable()
         return self
 
     def clear_grad(self):
         return self   # every gradient slot is overwritten by the next backward (no accumulation across steps)
+
+    def state_dict(self):
+        """For TRAINER.RESUME: {"step", "momentum_buffer": {parameter name: array in the reference's shape}}."""
+        return {"step": self.step_count, "momentum_buffer": _moments_out(self.model, self.model.arena.v)}
+
+    def load_state_dict(self, states):
+        self.step_count = int(states["step"])
+        _moments_in(self.model, self.model.arena.v, states["momentum_buffer"])
+
+
+class Adam:
+    """megengine.optimizer.Adam semantics in one fused HIP launch (bd_adam_step): g' = g + wd*w; m = b1*m + (1 - b1)*g';
+    v = b2*v + (1 - b2)*g'^2; w -= lr * (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps), t = the step number from 1.
+
+    The first moment lives in `arena.v` (the buffer SGD keeps its velocity in); the second moment is this object's own buffer.  The
+    step count stays on the host: the bias corrections travel to the kernel as arguments."""
+
+    decoupled = False
+
+    def __init__(self, model, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8):
+        if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+            raise ValueError(f"{type(self).__name__}: betas must be two values in [0, 1), got {betas!r}")
+        betas = (float(betas[0]), float(betas[1]))
+        if eps < 0:
+            raise ValueError(f"{type(self).__name__}: eps must not be negative, got {eps!r}")
+        self.model = model
+        self.step_count = 0
+        self.param_groups = [_ParamGroupView(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)]
+        a = model.arena
+        self.exp_avg_sq = torch.zeros(a.total, dtype=torch.float32, device=a.w.device)
+
+    def step(self, grad_scale=1.0, ema=None):
+        """`ema`: as SGD.step -- past the burn-in the average is updated inside this launch (bd_adam_ema_step)."""
+        a = self.model.arena
+        g = self.param_groups[0]
+        m = ema.fused_momentum() if ema is not None else None
+        t = self.step_count + 1
+        if m is None:
+            ops.adam_step(a.w, a.v, self.exp_avg_sq, a.g, g["lr"], g["betas"], g["eps"], g["weight_decay"], t, grad_scale,
+                          self.decoupled)
+        else:
+            ops.adam_ema_step(a.w, a.v, self.exp_avg_sq, a.g, ema.e, g["lr"], g["betas"], g["eps"], g["weight_decay"], t, grad_scale,
+                              self.decoupled, m)
+        self.step_count = t
+        self.model.repack_trainable()
+        return self
+
+    def clear_grad(self):
+        return self   # as SGD.clear_grad
+
+    def state_dict(self):
+        """For TRAINER.RESUME: {"step", "exp_avg", "exp_avg_sq"}, the moments as {parameter name: array in the reference's shape}."""
+        return {"step": self.step_count, "exp_avg": _moments_out(self.model, self.model.arena.v),
+                "exp_avg_sq": _moments_out(self.model, self.exp_avg_sq)}
+
+    def load_state_dict(self, states):
+        self.step_count = int(states["step"])
+        _moments_in(self.model, self.model.arena.v, states["exp_avg"])
+        _moments_in(self.model, self.exp_avg_sq, states["exp_avg_sq"])
+
+
+class AdamW(Adam):
+    """megengine.optimizer.AdamW: Adam with the decay decoupled from the gradient -- w -= lr * (m^ / (sqrt(v^) + eps) + wd*w)."""
+
+    decoupled = True
+
+
+# SOLVER.OPTIMIZER_NAME -> (class, the EXTRA_OPT_ARGS it takes): megengine.optimizer's names
+OPTIMIZERS = {"SGD": (SGD, ("momentum", "nesterov")), "Adam": (Adam, ("betas", "eps")), "AdamW": (AdamW, ("betas", "eps"))}
+
+
+def build_optimizer(name, model, lr, weight_decay, extra):
+    """`getattr(megengine.optimizer, name)(params, lr=, weight_decay=, **extra)` (solver/default_solver.py:47-55) over the three
+    optimizers this build has; anything else raises instead of training with another rule."""
+    if name not in OPTIMIZERS:
+        raise ValueError(f"SOLVER.OPTIMIZER_NAME = {name!r} is not supported: one of {sorted(OPTIMIZERS)} is implemented")
+    cls, takes = OPTIMIZERS[name]
+    unknown = sorted(set(extra) - set(takes))
+    if unknown:
+        raise ValueError(f"SOLVER.EXTRA_OPT_ARGS {unknown} not supported by OPTIMIZER_NAME = {name!r}: it takes {list(takes)}")
+    if cls is SGD:
+        extra = dict(extra)
+        extra.setdefault("momentum", 0.0)               # megengine.optimizer.SGD's default
+    return cls(model, lr=lr, weight_decay=weight_decay, **extra)
 
 
 class GradBuckets:
@@ -255,7 +380,7 @@ class DetSolver:
         else:
             wd = wd * world
         extra = dict(solver_cfg.get("EXTRA_OPT_ARGS", {}))
-        opt = SGD(model, lr=lr, weight_decay=wd, momentum=extra.get("momentum", 0.0))
+        opt = build_optimizer(solver_cfg.get("OPTIMIZER_NAME", "SGD"), model, lr, wd, extra)
         amp = cfg.get("TRAINER", {}).get("AMP", {}) if hasattr(cfg, "get") else {}
         scaler = None
         if amp.get("ENABLE", False):                      # default_solver.py:66-76

@@ -794,6 +794,34 @@ int bd_sgd_momentum_ema_step(float* w, float* v, const float* g, float* e, int64
  * trades places with the arena's weights for the length of the evaluation, so no third arena-sized buffer exists. */
 int bd_swap_f32(float* a, float* b, int64_t n, bd_stream_t stream);
 
+/* SOLVER.OPTIMIZER_NAME = "Adam" / "AdamW" and SGD with EXTRA_OPT_ARGS nesterov=True (bd_version() >= 106; solver/default_solver.py:47-55,
+ * 107-115 builds getattr(megengine.optimizer, OPTIMIZER_NAME)), over the flat fp32 arena like bd_sgd_momentum_step, each with a twin that
+ * folds bd_ema_update in (the *_ema_step entries give w and the moments the bits of the plain ones).  Every operation below is one fp32
+ * rounding -- no FMA, IEEE division and square root -- in exactly this order:
+ *   gg = g * grad_scale;              decoupled == 0 (Adam): gg = gg + wd * w
+ *   m  = beta1 * m + one_minus_beta1 * gg
+ *   v  = beta2 * v + one_minus_beta2 * (gg * gg)
+ *   d  = (m / bc1) / (sqrtf(v / bc2) + eps);       decoupled != 0 (AdamW): d = d + wd * w
+ *   w  = w - lr * d                   [e = e * ema_m + one_minus_ema_m * w]
+ * one_minus_beta*, bc1 = 1 - beta1^step and bc2 = 1 - beta2^step (step counted from 1) are formed by the caller in double precision: the
+ * device keeps no step counter.  m (first moment) and v (second moment) start as zeros.
+ * All four entries: n == 0 is a no-op; BD_EINVAL, with nothing launched, for n < 0, a null pointer, a base pointer that is not 16-byte
+ * aligned, e overlapping any other buffer, m, v and w overlapping one another, and (Adam) bc1 <= 0, bc2 <= 0, eps < 0 or a beta outside
+ * [0, 1). */
+int bd_adam_step(float* w, float* m, float* v, const float* g, int64_t n, float lr, float beta1, float one_minus_beta1, float beta2,
+                 float one_minus_beta2, float bc1, float bc2, float eps, float wd, float grad_scale, int decoupled, bd_stream_t stream);
+/* bd_adam_step, then bd_ema_update with the new w, in one pass: 36 bytes per parameter instead of 28 + 12. */
+int bd_adam_ema_step(float* w, float* m, float* v, const float* g, float* e, int64_t n, float lr, float beta1, float one_minus_beta1,
+                     float beta2, float one_minus_beta2, float bc1, float bc2, float eps, float wd, float grad_scale, int decoupled,
+                     float ema_m, float one_minus_ema_m, bd_stream_t stream);
+/* megengine.optimizer.SGD(nesterov=True) (the reference's YOLOX solver): gg = g*grad_scale + wd*w ; v = momentum*v + gg ;
+ * w -= lr*(gg + momentum*v) -- bd_sgd_momentum_step's velocity, the weight one look-ahead further.  One fp32 rounding per operation. */
+int bd_sgd_nesterov_step(float* w, float* v, const float* g, int64_t n, float lr, float momentum, float wd, float grad_scale,
+                         bd_stream_t stream);
+/* bd_sgd_nesterov_step, then bd_ema_update with the new w, in one pass (28 bytes per parameter). */
+int bd_sgd_nesterov_ema_step(float* w, float* v, const float* g, float* e, int64_t n, float lr, float momentum, float wd,
+                             float grad_scale, float ema_m, float one_minus_ema_m, bd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * fp8 (OCP e4m3) forward convolutions on the block-scaled MFMA (BASELINE config 5, "fp8 weights").  The reference's
  * mixed-precision hook is fp16 autocast + GradScaler (solver/default_solver.py:66-76, tools/det_train.py:77-78); there is
