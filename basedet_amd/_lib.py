@@ -156,6 +156,9 @@ SIGNATURES = {
     "bd_roi_align_bwd": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "bd_roi_align_bwd_bf16_workspace_bytes": (_Z, [_I, _I, _P, _P, _I]),
     "bd_roi_align_bwd_bf16": (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
+    "bd_roi_pool_fwd": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "bd_roi_pool_bwd_bf16_workspace_bytes": (_Z, [_I, _I, _P, _P, _I]),
+    "bd_roi_pool_bwd_bf16": (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
     "bd_subsample2x_fwd": (_I, [_P, _L, _L, _I, _I, _P, _L, _L, _I, _I, _P]),
     "bd_subsample2x_bwd_add": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _P]),
     "bd_f32_to_bf16": (_I, [_P, _P, _L, _P]),

@@ -1,5 +1,5 @@
 // Faster R-CNN operators on the HIP path: RPN proposal selection (per-level top-k, decode, clip, size filter; its NMS across
-// levels is nms.hip's, called through nms.h), random subsampling of labels, RoI sampling + target encoding, multi-level RoIAlign forward / backward and the
+// levels is nms.hip's, called through nms.h), random subsampling of labels, RoI sampling + target encoding, multi-level RoIAlign and RoI max pooling forward / backward and the
 // FPNP6 sub-sampling.  Reference: models/det/rpn.py, layers/head/rcnn.py, layers/common/roi_pool.py,
 // layers/common/sampling.py, layers/backbone/fpn_backbone.py:172-183.
 //
@@ -583,35 +583,41 @@ __device__ __forceinline__ void tile_decode(const PyrTiles& pt, int t, int& la, 
 }
 
 // count (fill == 0) or write (fill == 1) the RoI list of every tile, slots ascending: one WAVE per tile walks its image's footprints 64 at a
-// time (ballot + prefix count: the order within the list is the slot order, whatever the hardware does); blockIdx.y = image
+// time (ballot + prefix count: the order within the list is the slot order, whatever the hardware does); blockIdx.y = image.  The footprints
+// pass through LDS ROI_LIST_MAX at a time (one pass for the training default of <= 512 slots; RoI max pooling takes any slot count < 65536)
 __global__ __launch_bounds__(1024) void roi_tile_list_kernel(const int4* __restrict__ foot, int S, PyrTiles pt, int fill, int* __restrict__ tile_cnt,
                                                              const int* __restrict__ tile_off, unsigned short* __restrict__ entries, int cap) {
     __shared__ int4 s_f[ROI_LIST_MAX];
     const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tpi = pt.tile_start[pt.L];
-    for (int i = tid; i < S; i += 1024) s_f[i] = foot[(long long)n * S + i];
-    __syncthreads();
     const int t = blockIdx.x * 16 + wave;
-    if (t >= tpi) return;
-    int la, ty, tx;
-    tile_decode(pt, t, la, ty, tx);
-    const int base = fill ? tile_off[n * tpi + t] : 0;
+    const bool live = t < tpi;                  // (a wave past the last tile still takes part in the barriers)
+    int la = 0, ty = 0, tx = 0;
+    if (live) tile_decode(pt, t, la, ty, tx);
+    const int base = (fill && live) ? tile_off[n * tpi + t] : 0;
     int cnt = 0;
-    for (int i0 = 0; i0 < S; i0 += 64) {
-        const int i = i0 + lane;
-        bool hit = false;
-        if (i < S) {
-            const int4 f = s_f[i];
-            hit = f.x == la && tx >= (f.y & 0xffff) && tx <= (f.y >> 16) && ty >= (f.z & 0xffff) && ty <= (f.z >> 16);
+    for (int s0 = 0; s0 < S; s0 += ROI_LIST_MAX) {
+        const int sn = min(S - s0, ROI_LIST_MAX);
+        if (s0 > 0) __syncthreads();
+        for (int i = tid; i < sn; i += 1024) s_f[i] = foot[(long long)n * S + s0 + i];
+        __syncthreads();
+        if (!live) continue;
+        for (int i0 = 0; i0 < sn; i0 += 64) {
+            const int i = i0 + lane;
+            bool hit = false;
+            if (i < sn) {
+                const int4 f = s_f[i];
+                hit = f.x == la && tx >= (f.y & 0xffff) && tx <= (f.y >> 16) && ty >= (f.z & 0xffff) && ty <= (f.z >> 16);
+            }
+            const unsigned long long bal = __ballot(hit);
+            if (fill && hit) {
+                const int o = base + cnt + __popcll(bal & ((1ull << lane) - 1ull));
+                if (o < cap) entries[o] = (unsigned short)(s0 + i);
+            }
+            cnt += __popcll(bal);
         }
-        const unsigned long long bal = __ballot(hit);
-        if (fill && hit) {
-            const int o = base + cnt + __popcll(bal & ((1ull << lane) - 1ull));
-            if (o < cap) entries[o] = (unsigned short)i;
-        }
-        cnt += __popcll(bal);
     }
-    if (!fill && lane == 0) tile_cnt[n * tpi + t] = cnt;
+    if (!fill && live && lane == 0) tile_cnt[n * tpi + t] = cnt;
 }
 
 // exclusive scan of the tile counts in two small launches: every workgroup scans its own 1024 counts (coalesced) and leaves their total;
@@ -644,6 +650,12 @@ __global__ __launch_bounds__(1024) void roi_tile_scan_add_kernel(int* __restrict
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) tile_off[ntiles] = before + chunk_tot[blockIdx.x];
 }
 
+// neighbouring tiles share RoIs: every XCD (blocks go round-robin over the eight) takes a contiguous range of them
+__device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 __global__ __launch_bounds__(64, 2) void roi_align_bwd_tile_kernel(const bf16_raw* __restrict__ gout, long long ppi, int C, RoiLevels lv, PyrTiles pt,
                                                                    const float* __restrict__ rois, int S, int SP, const int* __restrict__ tile_off,
                                                                    const unsigned short* __restrict__ entries, int cap,
@@ -653,11 +665,7 @@ __global__ __launch_bounds__(64, 2) void roi_align_bwd_tile_kernel(const bf16_ra
     __shared__ int s_slot[2][64];
     const int lane = threadIdx.x;
     const int slices = (C + 127) / 128;
-    int bid = blockIdx.x;
-    {   // neighbouring tiles share RoIs: every XCD (blocks go round-robin over the eight) takes a contiguous range of them
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int slice = bid % slices;
     const int tb = bid / slices;                   // n * tiles_per_img + t
     const int tpi = pt.tile_start[pt.L];
@@ -781,6 +789,197 @@ __global__ __launch_bounds__(64, 2) void roi_align_bwd_tile_kernel(const bf16_ra
                     unsigned int* o = gp_out + (long long)((ty0 + y) * W + tx0 + x) * rowp;
                     *o = (unsigned int)f2bf(acc[y][x][0]) | ((unsigned int)f2bf(acc[y][x][1]) << 16);
                 }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// multi-level RoI max pooling (roi_pool.py:64-65: F.nn.roi_pooling(mode="max"), the Caffe ROIPooling rule) on the pixel-major bf16 pyramid.
+// The rule is roi_pool_max_kernel's (layer_ops.hip), on the level roi_level() assigns: corners roundf(coord / stride), rw = max(x2 - x1 + 1, 1),
+// bin rows floorf(ph * rh/PH) + y1 .. ceilf((ph + 1) * rh/PH) + y1 clamped to [0, H] (columns likewise), an empty bin gives 0, otherwise the
+// maximum from -inf.  Ties go to the FIRST pixel in row-major order (y outer, x inner, strict >): forward and backward walk the window
+// through pool_scan*() below, so they agree bit for bit.  The backward keeps no argmax: it finds it again in the still-live pyramid.
+// ------------------------------------------------------------------------------------------------------------
+struct PoolRoi { int x1, y1; float bw, bh; };
+
+// rounded corners beyond +-2^20 level pixels are held there: the integer window arithmetic cannot overflow (no map is that large)
+__device__ __forceinline__ int pool_round(float v) { return (int)fminf(fmaxf(roundf(v), -1048576.f), 1048576.f); }
+
+__device__ __forceinline__ PoolRoi pool_roi_setup(const Box& b, float sc, int PH, int PW, int& rw, int& rh) {
+    PoolRoi p;
+    p.x1 = pool_round(b.x1 * sc); p.y1 = pool_round(b.y1 * sc);
+    const int x2 = pool_round(b.x2 * sc), y2 = pool_round(b.y2 * sc);
+    rw = max(x2 - p.x1 + 1, 1); rh = max(y2 - p.y1 + 1, 1);
+    p.bw = (float)rw / (float)PW; p.bh = (float)rh / (float)PH;
+    return p;
+}
+
+// window [s, e) of bin p along one axis (start = the RoI's first row / column, b = bin size, n = the map's extent)
+__device__ __forceinline__ void pool_window(int p, int start, float b, int n, int& s, int& e) {
+    s = min(max((int)floorf((float)p * b) + start, 0), n);
+    e = min(max((int)ceilf((float)(p + 1) * b) + start, 0), n);
+}
+
+__global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const bf16_raw* __restrict__ feat, long long ppi, int C, RoiLevels lv,
+                                                           const float* __restrict__ rois, const int* __restrict__ labels,
+                                                           int rois_per_img, int PH, int PW, bf16_raw* __restrict__ out) {
+    const int r = blockIdx.x;
+    const int n = r / rois_per_img;
+    const int tid = threadIdx.x;
+    const int nb = PH * PW;
+    bf16_raw* op = out + (long long)r * nb * C;
+    if (labels && labels[r] < 0) {
+        for (int e = tid * 8; e < nb * C; e += 256 * 8) *reinterpret_cast<u32x4_t*>(op + e) = (u32x4_t){0u, 0u, 0u, 0u};
+        return;
+    }
+    const Box b = ld_box(rois + r * 4ll);
+    const int l = roi_level(b, lv);
+    const int H = lv.H[l], W = lv.W[l];
+    int rw, rh;
+    const PoolRoi pr = pool_roi_setup(b, lv.scale[l], PH, PW, rw, rh);
+    const bf16_raw* fp = feat + ((long long)n * ppi + lv.pix_off[l]) * C;
+    const int cgs = C / 8;
+    for (int w = tid; w < nb * cgs; w += 256) {         // lanes along channels: a window row is one contiguous 16-byte-per-lane read
+        const int bin = w / cgs, cg = w - bin * cgs;
+        const int ph = bin / PW, pw = bin - ph * PW;
+        int hs, he, ws, we;
+        pool_window(ph, pr.y1, pr.bh, H, hs, he);
+        pool_window(pw, pr.x1, pr.bw, W, ws, we);
+        u32x4_t o = (u32x4_t){0u, 0u, 0u, 0u};
+        if (he > hs && we > ws) {
+            float best[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) best[q] = -INFINITY;
+            for (int y = hs; y < he; ++y) {
+                const bf16_raw* row = fp + ((long long)y * W + ws) * C + cg * 8;
+                for (int x = ws; x < we; ++x, row += C) {
+                    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(row);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float a = bf_lo(v[q]), c = bf_hi(v[q]);
+                        if (a > best[2 * q]) best[2 * q] = a;
+                        if (c > best[2 * q + 1]) best[2 * q + 1] = c;
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = (__float_as_uint(best[2 * q]) >> 16) | (__float_as_uint(best[2 * q + 1]) & 0xffff0000u);    // (bf16 values: exact)
+        }
+        *reinterpret_cast<u32x4_t*>(op + (long long)bin * C + cg * 8) = o;
+    }
+}
+
+// the pixel extent of every RoI slot on its level, as the tile range the shared list kernels take (roi_foot_kernel's format); conservative by
+// one pixel on the far side (PW * (rw / PW) may round above rw); an empty slot or a RoI wholly outside its level is on no list
+__global__ __launch_bounds__(256) void roi_pool_foot_kernel(const float* __restrict__ rois, const int* __restrict__ labels, int total, RoiLevels lv,
+                                                            PyrTiles pt, int PH, int PW, int4* __restrict__ foot) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= total) return;
+    int4 f = make_int4(-1, 0, 0, 0);
+    if (!(labels && labels[r] < 0)) {
+        const Box b = ld_box(rois + r * 4ll);
+        const int l = roi_level(b, lv);
+        int rw, rh;
+        const PoolRoi pr = pool_roi_setup(b, lv.scale[l], PH, PW, rw, rh);
+        const int W = pt.W[l], H = pt.H[l];
+        const int xs = min(max(pr.x1, 0), W), xe = min(max(pr.x1 + rw + 1, 0), W);
+        const int ys = min(max(pr.y1, 0), H), ye = min(max(pr.y1 + rh + 1, 0), H);
+        if (xe > xs && ye > ys) f = make_int4(l, (xs / RT) | (((xe - 1) / RT) << 16), (ys / RT) | (((ye - 1) / RT) << 16), 0);
+    }
+    foot[r] = f;
+}
+
+// Adjoint of roi_pool_fwd_kernel, one wave per (8x8 tile, 128-channel slice), two channels per lane.  The wave walks the tile's RoI list in slot
+// order and, per RoI, the bins whose window meets the tile in bin order; it scans the WHOLE window of such a bin in the pyramid (the argmax may
+// lie in a neighbouring tile: then that tile's wave takes the gradient) and adds the bin's gradient to the argmax pixel's fp32 sum.  The sums
+// sit in LDS (the target pixel differs from lane to lane: registers cannot be indexed by it), each lane in its own column: no races, no
+// bank conflicts, a fixed order.  One rounding at the end, on top of what gfeat holds when `accumulate`; only touched pixels are rewritten then.
+__global__ __launch_bounds__(64) void roi_pool_bwd_tile_kernel(const bf16_raw* __restrict__ feat, const bf16_raw* __restrict__ gout, long long ppi, int C,
+                                                               RoiLevels lv, PyrTiles pt, const float* __restrict__ rois, int S, int PH, int PW,
+                                                               const int* __restrict__ tile_off, const unsigned short* __restrict__ entries, int cap,
+                                                               bf16_raw* __restrict__ gfeat, int accumulate) {
+    __shared__ float s_lo[RT * RT][64];            // fp32 sums of the even / odd channel of every lane, pixel-major
+    __shared__ float s_hi[RT * RT][64];
+    const int lane = threadIdx.x;
+    const int slices = (C + 127) / 128;
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
+    const int slice = bid % slices;
+    const int tb = bid / slices;                   // n * tiles_per_img + t
+    const int tpi = pt.tile_start[pt.L];
+    const int n = tb / tpi;
+    int la, tyi, txi;
+    tile_decode(pt, tb - n * tpi, la, tyi, txi);
+    const int ty0 = tyi * RT, tx0 = txi * RT;
+    const int H = pt.H[la], W = pt.W[la];
+    const int beg = min(tile_off[tb], cap), cnt = min(tile_off[tb + 1], cap) - beg;
+    const int c0 = slice * 128 + lane * 2;
+    const bool cok = c0 < C;                        // (C is even)
+    const int rowp = C / 2;                         // pixel pitch in 32-bit words
+    unsigned int* gp_out = reinterpret_cast<unsigned int*>(gfeat + ((long long)n * ppi + pt.pix_off[la]) * C + (cok ? c0 : 0));
+    if (cnt == 0) {
+        if (!accumulate && cok)
+            for (int y = 0; y < RT && ty0 + y < H; ++y)
+                for (int x = 0; x < RT && tx0 + x < W; ++x) gp_out[((long long)(ty0 + y) * W + tx0 + x) * rowp] = 0u;
+        return;
+    }
+    if (!cok) return;                               // (no barrier below: a lane past the last channel has nothing to do)
+    for (int p = 0; p < RT * RT; ++p) { s_lo[p][lane] = 0.f; s_hi[p][lane] = 0.f; }
+    unsigned long long hit_lo = 0ull, hit_hi = 0ull;        // which of the tile's pixels this lane's two channels have received a gradient on
+    const float sc = lv.scale[la];                  // (tiles with a list are on a RoI level)
+    const unsigned int* fp = reinterpret_cast<const unsigned int*>(feat + ((long long)n * ppi + pt.pix_off[la]) * C + c0);
+    const unsigned int* gbase = reinterpret_cast<const unsigned int*>(gout + (long long)n * S * ((long long)PH * PW) * C + c0);
+    for (int q = 0; q < cnt; ++q) {
+        const int slot = entries[beg + q];
+        const Box b = ld_box(rois + ((long long)n * S + slot) * 4);
+        int rw, rh;
+        const PoolRoi pr = pool_roi_setup(b, sc, PH, PW, rw, rh);
+        const unsigned int* go = gbase + (long long)slot * ((long long)PH * PW) * rowp;
+        for (int ph = 0; ph < PH; ++ph) {
+            int hs, he;
+            pool_window(ph, pr.y1, pr.bh, H, hs, he);
+            if (he <= hs || he <= ty0 || hs >= ty0 + RT) continue;
+            for (int pw = 0; pw < PW; ++pw) {
+                int ws, we;
+                pool_window(pw, pr.x1, pr.bw, W, ws, we);
+                if (we <= ws || we <= tx0 || ws >= tx0 + RT) continue;
+                const unsigned int gpk = go[(long long)(ph * PW + pw) * rowp];
+                float b0 = -INFINITY, b1 = -INFINITY;
+                int a0 = -1, a1 = -1;               // argmax pixel y * W + x of the level, -1 = none (a window of -inf / NaN: the gradient is dropped)
+                for (int y = hs; y < he; ++y) {
+                    const unsigned int* row = fp + ((long long)y * W + ws) * rowp;
+                    for (int x = ws; x < we; ++x, row += rowp) {
+                        const unsigned int v = *row;
+                        const float v0 = bf_lo(v), v1 = bf_hi(v);
+                        const int code = y * W + x;
+                        if (v0 > b0) { b0 = v0; a0 = code; }
+                        if (v1 > b1) { b1 = v1; a1 = code; }
+                    }
+                }
+                if (a0 >= 0) {
+                    const int y = a0 / W - ty0, x = a0 % W - tx0;
+                    if ((unsigned)y < (unsigned)RT && (unsigned)x < (unsigned)RT) { s_lo[y * RT + x][lane] += bf_lo(gpk); hit_lo |= 1ull << (y * RT + x); }
+                }
+                if (a1 >= 0) {
+                    const int y = a1 / W - ty0, x = a1 % W - tx0;
+                    if ((unsigned)y < (unsigned)RT && (unsigned)x < (unsigned)RT) { s_hi[y * RT + x][lane] += bf_hi(gpk); hit_hi |= 1ull << (y * RT + x); }
+                }
+            }
+        }
+    }
+    for (int p = 0; p < RT * RT; ++p) {
+        const int y = ty0 + p / RT, x = tx0 + p % RT;
+        if (y >= H || x >= W) continue;
+        unsigned int* o = gp_out + ((long long)y * W + x) * rowp;
+        float v0 = s_lo[p][lane], v1 = s_hi[p][lane];
+        if (accumulate) {
+            const bool t0 = (hit_lo >> p) & 1ull, t1 = (hit_hi >> p) & 1ull;
+            if (!t0 && !t1) continue;               // untouched: left alone, bit for bit
+            const unsigned int old = *o;
+            const unsigned int lo = t0 ? (unsigned int)f2bf(v0 + bf_lo(old)) : (old & 0xffffu);
+            const unsigned int hi = t1 ? ((unsigned int)f2bf(v1 + bf_hi(old)) << 16) : (old & 0xffff0000u);
+            *o = lo | hi;
+        } else {
+            *o = pack_bf2(v0, v1);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1106,13 +1305,62 @@ static int roi_tiles_max_level(int L_all, const int32_t* H, const int32_t* W) {
     return m;
 }
 
-// workspace: tile counts | tile offsets (+1) | footprints (int4 per RoI slot) | tile lists (u16 slots) | totals of the 1024-tile scan chunks
-extern "C" size_t bd_roi_align_bwd_bf16_workspace_bytes(int N, int L_all, const int32_t* lvl_h_host, const int32_t* lvl_w_host,
-                                                        int rois_per_img) {
+// workspace of the per-tile RoI lists: tile counts | tile offsets (+1) | footprints (int4 per RoI slot) | tile lists (u16 slots) | totals of the 1024-tile scan chunks
+static size_t roi_tile_ws_bytes(int N, int L_all, const int32_t* lvl_h_host, const int32_t* lvl_w_host, int rois_per_img) {
     if (N <= 0 || L_all <= 0 || L_all > BD_MAX_SEGS || rois_per_img <= 0 || !lvl_h_host || !lvl_w_host) return 256;
     const size_t ntiles = (size_t)N * roi_tiles_per_img(L_all, lvl_h_host, lvl_w_host);
     return 2 * align256((ntiles + 1) * 4) + align256((size_t)N * rois_per_img * 16) + align256((size_t)N * rois_per_img * roi_tiles_max_level(L_all, lvl_h_host, lvl_w_host) * 2) +
            align256((ntiles / 1024 + 1) * 4) + 256;
+}
+
+// The tile geometry of a pyramid and the carving of the workspace; lists(): count, scan, fill in slot order from the footprints a kernel of the
+// caller has left in `foot` (shared by the RoIAlign and the RoI max pooling backward).
+struct RoiTilePlan {
+    PyrTiles pt;
+    int ts, ntiles, total, cap;
+    int *tile_cnt, *tile_off, *chunk_tot;
+    int4* foot;
+    unsigned short* entries;
+    int init(const char* who, int N, int L_all, const int32_t* pix_off, const int32_t* H, const int32_t* W, int rois_per_img, void* ws) {
+        pt = PyrTiles{};
+        pt.L = L_all;
+        ts = 0;
+        for (int l = 0; l < L_all; ++l) {
+            pt.pix_off[l] = pix_off[l]; pt.H[l] = H[l]; pt.W[l] = W[l];
+            pt.tiles_x[l] = cdiv(W[l], RT);
+            // (tile coordinates are packed two to a SIGNED int and unpacked with an arithmetic shift: 15 bits each)
+            BD_REQUIRE(pt.tiles_x[l] < 32768 && cdiv(H[l], RT) < 32768, "%s: level too large", who);
+            pt.tile_start[l] = ts;
+            ts += pt.tiles_x[l] * cdiv(H[l], RT);
+        }
+        pt.tile_start[L_all] = ts;
+        ntiles = N * ts;
+        total = N * rois_per_img;
+        unsigned char* wb = (unsigned char*)ws;
+        tile_cnt = (int*)wb;
+        tile_off = (int*)(wb + align256(((size_t)ntiles + 1) * 4));
+        foot = (int4*)(wb + 2 * align256(((size_t)ntiles + 1) * 4));
+        entries = (unsigned short*)((unsigned char*)foot + align256((size_t)total * 16));
+        const long long cap_ll = (long long)total * roi_tiles_max_level(L_all, H, W);
+        BD_REQUIRE(cap_ll < 0x7fffffffll, "%s: tile lists too large", who);
+        cap = (int)cap_ll;
+        chunk_tot = (int*)((unsigned char*)entries + align256((size_t)cap * 2));      // (behind the lists)
+        return BD_OK;
+    }
+    void lists(int N, int rois_per_img, hipStream_t st) const {
+        hipLaunchKernelGGL(roi_tile_list_kernel, dim3(cdiv(ts, 16), N), dim3(1024), 0, st, (const int4*)foot, rois_per_img, pt, 0, tile_cnt,
+                           (const int*)tile_off, entries, cap);
+        const int chunks = cdiv(ntiles, 1024);
+        hipLaunchKernelGGL(roi_tile_scan_local_kernel, dim3(chunks), dim3(1024), 0, st, (const int*)tile_cnt, tile_off, ntiles, chunk_tot);
+        hipLaunchKernelGGL(roi_tile_scan_add_kernel, dim3(chunks), dim3(1024), 0, st, tile_off, ntiles, (const int*)chunk_tot);
+        hipLaunchKernelGGL(roi_tile_list_kernel, dim3(cdiv(ts, 16), N), dim3(1024), 0, st, (const int4*)foot, rois_per_img, pt, 1, tile_cnt,
+                           (const int*)tile_off, entries, cap);
+    }
+};
+
+extern "C" size_t bd_roi_align_bwd_bf16_workspace_bytes(int N, int L_all, const int32_t* lvl_h_host, const int32_t* lvl_w_host,
+                                                        int rois_per_img) {
+    return roi_tile_ws_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img);
 }
 
 extern "C" int bd_roi_align_bwd_bf16(const void* gout, int64_t pix_per_img, int C, int L, int L_all, const int32_t* lvl_pix_off_host,
@@ -1124,48 +1372,66 @@ extern "C" int bd_roi_align_bwd_bf16(const void* gout, int64_t pix_per_img, int 
                "roi_align_bwd_bf16: bad sizes");
     BD_REQUIRE(PH == 7 && PW == 7, "roi_align_bwd_bf16: the pooled size is 7 x 7 (got %d x %d)", PH, PW);
     BD_REQUIRE(rois_per_img <= ROI_LIST_MAX, "roi_align_bwd_bf16: %d RoIs per image exceed %d", rois_per_img, ROI_LIST_MAX);
-    if (ws_bytes < bd_roi_align_bwd_bf16_workspace_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img)) {
-        bd_set_error("roi_align_bwd_bf16: workspace %zu < %zu bytes", ws_bytes,
-                     bd_roi_align_bwd_bf16_workspace_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img));
+    if (ws_bytes < roi_tile_ws_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img)) {
+        bd_set_error("roi_align_bwd_bf16: workspace %zu < %zu bytes", ws_bytes, roi_tile_ws_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img));
         return BD_EWORKSPACE;
     }
     RoiLevels lv{};
     BD_REQUIRE(fill_roi_levels(lv, L, lvl_pix_off_host, lvl_h_host, lvl_w_host, strides_host) == 0, "roi_align_bwd_bf16: strides must be powers of two");
-    PyrTiles pt{};
-    pt.L = L_all;
-    int ts = 0;
-    for (int l = 0; l < L_all; ++l) {
-        pt.pix_off[l] = lvl_pix_off_host[l]; pt.H[l] = lvl_h_host[l]; pt.W[l] = lvl_w_host[l];
-        pt.tiles_x[l] = cdiv(lvl_w_host[l], RT);
-        // (tile coordinates are packed two to a SIGNED int and unpacked with an arithmetic shift: 15 bits each)
-        BD_REQUIRE(pt.tiles_x[l] < 32768 && cdiv(lvl_h_host[l], RT) < 32768, "roi_align_bwd_bf16: level too large");
-        pt.tile_start[l] = ts;
-        ts += pt.tiles_x[l] * cdiv(lvl_h_host[l], RT);
-    }
-    pt.tile_start[L_all] = ts;
-    const int ntiles = N * ts;
-    const int total = N * rois_per_img;
-    unsigned char* wb = (unsigned char*)ws;
-    int* tile_cnt = (int*)wb;
-    int* tile_off = (int*)(wb + align256(((size_t)ntiles + 1) * 4));
-    int4* foot = (int4*)(wb + 2 * align256(((size_t)ntiles + 1) * 4));
-    unsigned short* entries = (unsigned short*)((unsigned char*)foot + align256((size_t)total * 16));
-    const long long cap_ll = (long long)total * roi_tiles_max_level(L_all, lvl_h_host, lvl_w_host);
-    BD_REQUIRE(cap_ll < 0x7fffffffll, "roi_align_bwd_bf16: tile lists too large");
-    const int cap = (int)cap_ll;
+    RoiTilePlan tp;
+    if (int e = tp.init("roi_align_bwd_bf16", N, L_all, lvl_pix_off_host, lvl_h_host, lvl_w_host, rois_per_img, ws)) return e;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(roi_foot_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, rois, labels, total, lv, pt, foot);
-    hipLaunchKernelGGL(roi_tile_list_kernel, dim3(cdiv(ts, 16), N), dim3(1024), 0, st, (const int4*)foot, rois_per_img, pt, 0, tile_cnt,
-                       (const int*)tile_off, entries, cap);
-    const int chunks = cdiv(ntiles, 1024);
-    int* chunk_tot = (int*)((unsigned char*)entries + align256((size_t)cap * 2));      // (behind the lists)
-    hipLaunchKernelGGL(roi_tile_scan_local_kernel, dim3(chunks), dim3(1024), 0, st, (const int*)tile_cnt, tile_off, ntiles, chunk_tot);
-    hipLaunchKernelGGL(roi_tile_scan_add_kernel, dim3(chunks), dim3(1024), 0, st, tile_off, ntiles, (const int*)chunk_tot);
-    hipLaunchKernelGGL(roi_tile_list_kernel, dim3(cdiv(ts, 16), N), dim3(1024), 0, st, (const int4*)foot, rois_per_img, pt, 1, tile_cnt,
-                       (const int*)tile_off, entries, cap);
-    hipLaunchKernelGGL(roi_align_bwd_tile_kernel, dim3(ntiles * cdiv(C, 128)), dim3(64), 0, st, (const bf16_raw*)gout, (long long)pix_per_img,
-                       C, lv, pt, rois, rois_per_img, sample_points, (const int*)tile_off, (const unsigned short*)entries, cap,
+    hipLaunchKernelGGL(roi_foot_kernel, dim3(cdiv(tp.total, 256)), dim3(256), 0, st, rois, labels, tp.total, lv, tp.pt, tp.foot);
+    tp.lists(N, rois_per_img, st);
+    hipLaunchKernelGGL(roi_align_bwd_tile_kernel, dim3(tp.ntiles * cdiv(C, 128)), dim3(64), 0, st, (const bf16_raw*)gout, (long long)pix_per_img,
+                       C, lv, tp.pt, rois, rois_per_img, sample_points, (const int*)tp.tile_off, (const unsigned short*)tp.entries, tp.cap,
                        (bf16_raw*)gfeat, accumulate);
     BD_CHECK_LAUNCH("bd_roi_align_bwd_bf16");
+    return BD_OK;
+}
+
+extern "C" int bd_roi_pool_fwd(const void* feat, int64_t pix_per_img, int C, int L, const int32_t* lvl_pix_off_host,
+                               const int32_t* lvl_h_host, const int32_t* lvl_w_host, const int32_t* strides_host,
+                               const float* rois, const int32_t* labels, int R, int rois_per_img, int PH, int PW, void* out,
+                               bd_stream_t stream) {
+    BD_REQUIRE(feat && lvl_pix_off_host && lvl_h_host && lvl_w_host && strides_host && rois && out, "roi_pool_fwd: null pointer");
+    BD_REQUIRE(L > 0 && L <= BD_MAX_SEGS && C > 0 && C % 8 == 0 && PH > 0 && PW > 0 && rois_per_img > 0 && R >= 0, "roi_pool_fwd: bad sizes");
+    if (R == 0) return BD_OK;
+    RoiLevels lv{};
+    BD_REQUIRE(fill_roi_levels(lv, L, lvl_pix_off_host, lvl_h_host, lvl_w_host, strides_host) == 0, "roi_pool_fwd: strides must be powers of two");
+    hipLaunchKernelGGL(roi_pool_fwd_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)feat, (long long)pix_per_img,
+                       C, lv, rois, labels, rois_per_img, PH, PW, (bf16_raw*)out);
+    BD_CHECK_LAUNCH("bd_roi_pool_fwd");
+    return BD_OK;
+}
+
+extern "C" size_t bd_roi_pool_bwd_bf16_workspace_bytes(int N, int L_all, const int32_t* lvl_h_host, const int32_t* lvl_w_host,
+                                                       int rois_per_img) {
+    return roi_tile_ws_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img);
+}
+
+extern "C" int bd_roi_pool_bwd_bf16(const void* feat, const void* gout, int64_t pix_per_img, int C, int L, int L_all,
+                                    const int32_t* lvl_pix_off_host, const int32_t* lvl_h_host, const int32_t* lvl_w_host,
+                                    const int32_t* strides_host, const float* rois, const int32_t* labels, int N, int rois_per_img,
+                                    int PH, int PW, void* gfeat, int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream) {
+    BD_REQUIRE(feat && gout && lvl_pix_off_host && lvl_h_host && lvl_w_host && strides_host && rois && gfeat && ws, "roi_pool_bwd_bf16: null pointer");
+    BD_REQUIRE(L > 0 && L <= L_all && L_all <= BD_MAX_SEGS && C > 0 && C % 2 == 0 && PH > 0 && PW > 0 && rois_per_img > 0 && N > 0,
+               "roi_pool_bwd_bf16: bad sizes");
+    BD_REQUIRE(rois_per_img < 65536, "roi_pool_bwd_bf16: %d RoIs per image exceed 65535 (the tile lists hold 16-bit slots)", rois_per_img);
+    if (ws_bytes < roi_tile_ws_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img)) {
+        bd_set_error("roi_pool_bwd_bf16: workspace %zu < %zu bytes", ws_bytes, roi_tile_ws_bytes(N, L_all, lvl_h_host, lvl_w_host, rois_per_img));
+        return BD_EWORKSPACE;
+    }
+    RoiLevels lv{};
+    BD_REQUIRE(fill_roi_levels(lv, L, lvl_pix_off_host, lvl_h_host, lvl_w_host, strides_host) == 0, "roi_pool_bwd_bf16: strides must be powers of two");
+    RoiTilePlan tp;
+    if (int e = tp.init("roi_pool_bwd_bf16", N, L_all, lvl_pix_off_host, lvl_h_host, lvl_w_host, rois_per_img, ws)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(roi_pool_foot_kernel, dim3(cdiv(tp.total, 256)), dim3(256), 0, st, rois, labels, tp.total, lv, tp.pt, PH, PW, tp.foot);
+    tp.lists(N, rois_per_img, st);
+    hipLaunchKernelGGL(roi_pool_bwd_tile_kernel, dim3(tp.ntiles * cdiv(C, 128)), dim3(64), 0, st, (const bf16_raw*)feat, (const bf16_raw*)gout,
+                       (long long)pix_per_img, C, lv, tp.pt, rois, rois_per_img, PH, PW, (const int*)tp.tile_off,
+                       (const unsigned short*)tp.entries, tp.cap, (bf16_raw*)gfeat, accumulate);
+    BD_CHECK_LAUNCH("bd_roi_pool_bwd_bf16");
     return BD_OK;
 }

@@ -20,6 +20,16 @@ from .engine import FCLayer, FusedPredConv
 from .fpn_base import FPNDetector, _round_up
 
 
+ROI_POOLER_METHODS = ("roi_align", "roi_pool")        # layers/common/roi_pool.py:64-65
+
+
+def check_roi_pooler_method(method):
+    """The pooling rule of the box head (rcnn.py:21,56 hands it to roi_pool()); a value the reference does not have raises when the model is built."""
+    if method not in ROI_POOLER_METHODS:
+        raise ValueError(f"MODEL.ROI_POOLER.METHOD = {method!r} is not supported: use 'roi_align' or 'roi_pool'")
+    return method
+
+
 @registers.models.register()
 class FasterRCNN(FPNDetector):
     TOP_BLOCK = "pool"
@@ -44,7 +54,7 @@ class FasterRCNN(FPNDetector):
         self.convs[self.rpn_pred.name] = self.rpn_pred
         # RCNN (layers/head/rcnn.py:32-38)
         self.pool = tuple(m.ROI_POOLER.SIZE)
-        assert m.ROI_POOLER.METHOD == "roi_align", "the HIP path implements roi_align"
+        self.roi_method = check_roi_pooler_method(m.ROI_POOLER.METHOD)
         self.rcnn_levels = len(m.RCNN.IN_FEATURES)
         assert list(m.RCNN.STRIDES) == self.strides[: self.rcnn_levels]
         K = self.num_classes
@@ -123,11 +133,17 @@ class FasterRCNN(FPNDetector):
         pl.g_fc2 = C.empty((R, 1024), bf)
         pl.g_fc1 = C.empty((R, 1024), bf)
         pl.g_pooled = C.empty((R, fin), bf)
-        pl.roi_bwd_tiled = self.pool == (7, 7) and S <= 512 and self.fpn_ch % 2 == 0       # the tiled kernel's limits (rcnn_ops.hip)
-        # the fp32 scatter's staging pyramid (1.5 GB at batch 16): in the arena when the plan routes RoIAlign's backward to the scatter;
-        # a model that forces the scatter on a tiled plan (deterministic_roi_bwd = False, a test switch) allocates it on first use
-        pl.g_feat32 = None if pl.roi_bwd_tiled else C.empty((pyr.pixels, self.fpn_ch), f32)
-        pl.roi_bwd_ws = C.empty((ops.roi_align_bwd_bf16_workspace_bytes(pyr, S),), torch.uint8) if pl.roi_bwd_tiled else None
+        if self.roi_method == "roi_pool":
+            # RoI max pooling: its backward (bd_roi_pool_bwd_bf16) is tiled and reproducible at any pooled size / NUM_ROIS, finds the argmax
+            # again in pl.P (no argmax buffer: zero bytes beside the tile lists) and needs no fp32 staging pyramid
+            pl.roi_bwd_tiled, pl.g_feat32 = True, None
+            pl.roi_bwd_ws = C.empty((ops.roi_pool_bwd_bf16_workspace_bytes(pyr, S),), torch.uint8)
+        else:
+            pl.roi_bwd_tiled = self.pool == (7, 7) and S <= 512 and self.fpn_ch % 2 == 0       # the tiled kernel's limits (rcnn_ops.hip)
+            # the fp32 scatter's staging pyramid (1.5 GB at batch 16): in the arena when the plan routes RoIAlign's backward to the scatter;
+            # a model that forces the scatter on a tiled plan (deterministic_roi_bwd = False, a test switch) allocates it on first use
+            pl.g_feat32 = None if pl.roi_bwd_tiled else C.empty((pyr.pixels, self.fpn_ch), f32)
+            pl.roi_bwd_ws = C.empty((ops.roi_align_bwd_bf16_workspace_bytes(pyr, S),), torch.uint8) if pl.roi_bwd_tiled else None
         pl.g_fc = ops.single(1, R, 1)
         pl.loss_buf = C.zeros((4,), f32)
 
@@ -188,7 +204,7 @@ class FasterRCNN(FPNDetector):
             ops.rpn_assign_encode(pl.anchors, gt, num_gt, thr[0], thr[1], m.MATCHER.ALLOW_LOW_QUALITY, m.RPN_BOX_REG.MEAN,
                                   m.RPN_BOX_REG.STD, pl.rpn_labels, pl.rpn_match, pl.rpn_offsets, pl.rpn_num_fg, assign_ws)
             ops.sample_labels(pl.rpn_labels, keys["rpn_pos"], keys["rpn_neg"], int(m.RPN.POSITIVE_ANCHOR_RATIO * nsa), nsa, pl.rpn_num_valid)
-            if not (self.deterministic_roi_bwd and pl.roi_bwd_tiled):     # (the fp32 scatter only)
+            if self.roi_method == "roi_align" and not (self.deterministic_roi_bwd and pl.roi_bwd_tiled):     # (the fp32 scatter only)
                 if pl.g_feat32 is None:
                     pl.g_feat32 = torch.empty((pl.pyr.pixels, self.fpn_ch), dtype=torch.float32, device=self.device)
                 pl.g_feat32.zero_()           # the fp32 pyramid RoIAlign's backward scatters into (1.5 GB at batch 16): cleared here, not in backward
@@ -250,8 +266,12 @@ class FasterRCNN(FPNDetector):
     def _box_head(self, pl):
         """roi_pool + fc1/fc2 + predictors (rcnn.py:55-63) on the sampled RoI slots."""
         S = pl.s_rois.shape[1]
-        ops.roi_align_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, pl.s_rois.view(-1, 4), pl.s_labels.view(-1), S,
-                          self.pool, 2, pl.pooled)
+        if self.roi_method == "roi_pool":
+            ops.roi_pool_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, pl.s_rois.view(-1, 4), pl.s_labels.view(-1), S,
+                             self.pool, pl.pooled)
+        else:
+            ops.roi_align_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, pl.s_rois.view(-1, 4), pl.s_labels.view(-1), S,
+                              self.pool, 2, pl.pooled)
         g = pl.g_fc
         self.fc1.forward(pl.pooled, g, g, pl.fc1_out, relu=True)
         self.fc2.forward(pl.fc1_out, g, g, pl.fc2_out, relu=True)
@@ -269,7 +289,10 @@ class FasterRCNN(FPNDetector):
         self._wgrad(self.fc1, pl.pooled, pl.g_fc1, g, g, ws, cws)
         self.fc1.dgrad(pl.g_fc1, g, g, pl.g_pooled)
         # first contribution to dL/dP: every pyramid level is written (zeros where no RoI sample lands, all of P6)
-        if self.deterministic_roi_bwd and pl.roi_bwd_tiled:    # per-tile sums in registers, fixed order, written once (added to the RPN head's dL/dP when that ran first)
+        if self.roi_method == "roi_pool":       # the gradient of every bin to its argmax pixel of pl.P, fixed order, on top of the RPN head's dL/dP
+            ops.roi_pool_bwd_bf16(pl.P, pl.g_pooled, pyr, self.rcnn_levels, self.strides, self.fpn_ch, pl.s_rois.view(-1, 4),
+                                  pl.s_labels.view(-1), S, self.pool, pl.g_P, pl.roi_bwd_ws, accumulate=pl.rpn_bwd_done)
+        elif self.deterministic_roi_bwd and pl.roi_bwd_tiled:    # per-tile sums in registers, fixed order, written once (added to the RPN head's dL/dP when that ran first)
             ops.roi_align_bwd_bf16(pl.g_pooled, pyr, self.rcnn_levels, self.strides, self.fpn_ch, pl.s_rois.view(-1, 4),
                                    pl.s_labels.view(-1), S, self.pool, 2, pl.g_P, pl.roi_bwd_ws, accumulate=pl.rpn_bwd_done)
         else:
@@ -351,7 +374,10 @@ class FasterRCNN(FPNDetector):
         K = self.num_classes
         b = pl.inf = self._inference_buffers(N * R)
         rois = pl.rois.view(-1, 4)
-        ops.roi_align_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, rois, None, R, self.pool, 2, b["pooled"])
+        if self.roi_method == "roi_pool":
+            ops.roi_pool_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, rois, None, R, self.pool, b["pooled"])
+        else:
+            ops.roi_align_fwd(pl.P, pl.pyr, self.rcnn_levels, self.strides, self.fpn_ch, rois, None, R, self.pool, 2, b["pooled"])
         g = b["g"]
         self.fc1.forward(b["pooled"], g, g, b["fc1"], relu=True)
         self.fc2.forward(b["fc1"], g, g, b["fc2"], relu=True)

@@ -645,6 +645,26 @@ def roi_align_bwd_bf16(gout, geom: Geom, nlev, strides, Cn, rois, labels, rois_p
           "bd_roi_align_bwd_bf16")
 
 
+def roi_pool_fwd(feat, geom: Geom, nlev, strides, Cn, rois, labels, rois_per_img, pool, out):
+    """RoI max pooling (ROI_POOLER.METHOD = "roi_pool") of the first nlev levels of a pixel-major bf16 pyramid into out [R][PH*PW][C]."""
+    R = rois.shape[0]
+    check(L().bd_roi_pool_fwd(ptr(feat), geom.pix_per_img, Cn, nlev, i32arr(geom.off[:nlev]), i32arr(geom.H[:nlev]),
+                              i32arr(geom.W[:nlev]), i32arr(strides[:nlev]), ptr(rois), ptr(labels), R, rois_per_img, pool[0],
+                              pool[1], ptr(out), stream_ptr()), "bd_roi_pool_fwd")
+
+
+def roi_pool_bwd_bf16_workspace_bytes(geom: Geom, rois_per_img):
+    return int(L().bd_roi_pool_bwd_bf16_workspace_bytes(geom.N, geom.nlev, i32arr(geom.H), i32arr(geom.W), rois_per_img))
+
+
+def roi_pool_bwd_bf16(feat, gout, geom: Geom, nlev, strides, Cn, rois, labels, rois_per_img, pool, gfeat, ws, accumulate=False):
+    """Adjoint of roi_pool_fwd: `feat` is the pyramid the forward read (the argmax is found in it again), gfeat the bf16 gradient pyramid."""
+    check(L().bd_roi_pool_bwd_bf16(ptr(feat), ptr(gout), geom.pix_per_img, Cn, nlev, geom.nlev, i32arr(geom.off), i32arr(geom.H),
+                                   i32arr(geom.W), i32arr(strides[:nlev]), ptr(rois), ptr(labels), geom.N, rois_per_img, pool[0], pool[1],
+                                   ptr(gfeat), int(bool(accumulate)), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+          "bd_roi_pool_bwd_bf16")
+
+
 def subsample2x_fwd(src, gsrc: Geom, dst, gdst: Geom, Cn):
     check(L().bd_subsample2x_fwd(ptr(src), gsrc.pix_per_img, gsrc.off[0], gsrc.H[0], gsrc.W[0], ptr(dst), gdst.pix_per_img,
                                  gdst.off[0], Cn, gsrc.N, stream_ptr()), "bd_subsample2x_fwd")

@@ -671,6 +671,34 @@ int bd_roi_align_bwd_bf16(const void* gout, int64_t pix_per_img, int C, int L, i
                           const float* rois, const int32_t* labels, int N, int rois_per_img, int PH, int PW,
                           int sample_points, void* gfeat, int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream);
 
+/* roi_pool(..., "roi_pool") = F.nn.roi_pooling(mode="max") (roi_pool.py:64-65), the Caffe ROIPooling rule, on the level that the rule of
+ * bd_roi_align_fwd / bd_assign_roi_levels assigns; arguments as bd_roi_align_fwd (pixel-major bf16 pyramid, RoI r belongs to image
+ * r / rois_per_img, labels (optional) < 0 marks an empty slot whose output row is zeroed).  On a level of H x W pixels and stride s:
+ * x1 = roundf(rois[r][0] / s) (y1, x2, y2 likewise; held within +-2^20), rw = max(x2 - x1 + 1, 1), rh likewise; bin (ph, pw) covers rows
+ * floorf(ph * rh/PH) + y1 .. ceilf((ph + 1) * rh/PH) + y1 (exclusive) clamped to [0, H] and the columns likewise; an empty bin gives 0,
+ * any other the maximum of its window starting from -inf (an all-negative window gives its negative maximum).  A maximum of bf16 values:
+ * no rounding.  out: bf16 [R][PH*PW][C] (bin-major, channel-minor).  C % 8 == 0; any PH, PW, rois_per_img. */
+int bd_roi_pool_fwd(const void* feat, int64_t pix_per_img, int C, int L, const int32_t* lvl_pix_off_host,
+                    const int32_t* lvl_h_host, const int32_t* lvl_w_host, const int32_t* strides_host,
+                    const float* rois, const int32_t* labels, int R, int rois_per_img, int PH, int PW, void* out,
+                    bd_stream_t stream);
+
+/* Adjoint of bd_roi_pool_fwd, bitwise reproducible: every (RoI, bin, channel) gradient of gout (bf16 [N * rois_per_img][PH*PW][C]) goes to
+ * the bin's argmax pixel -- the FIRST maximum of the window in row-major order (y outer, x inner, strict >), found again in `feat`, which
+ * must still hold the pyramid the forward read; a window that selects nothing (all -inf / NaN) drops its gradient.  Contributions that
+ * meet on a pixel are summed in fp32 in a fixed order (RoI slots ascending, bins ascending within a slot: per-tile RoI lists as in
+ * bd_roi_align_bwd_bf16, no atomics) and rounded to bf16 once.  gfeat: the bf16 gradient of ALL L_all levels of the pixel-major buffer.
+ * accumulate == 0: every pixel of every level is written (zeros where nothing lands); != 0: the sums are added to what gfeat holds (one
+ * rounding of the total) and pixels / channels that no bin selects keep their bits.  lvl_* arrays have L_all entries, strides the first
+ * L.  C even; any PH, PW; rois_per_img < 65536.  ws: bd_roi_pool_bwd_bf16_workspace_bytes bytes, 256-byte aligned (the tile lists;
+ * no argmax is stored). */
+size_t bd_roi_pool_bwd_bf16_workspace_bytes(int N, int L_all, const int32_t* lvl_h_host, const int32_t* lvl_w_host,
+                                            int rois_per_img);
+int bd_roi_pool_bwd_bf16(const void* feat, const void* gout, int64_t pix_per_img, int C, int L, int L_all,
+                         const int32_t* lvl_pix_off_host, const int32_t* lvl_h_host, const int32_t* lvl_w_host,
+                         const int32_t* strides_host, const float* rois, const int32_t* labels, int N, int rois_per_img,
+                         int PH, int PW, void* gfeat, int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream);
+
 /* FPNP6 (fpn_backbone.py:172-183): dst[n,y,x,:] = src[n,2y,2x,:]; backward adds gdst into gsrc at the even pixels. */
 int bd_subsample2x_fwd(const void* src, int64_t src_pix_per_img, int64_t src_off, int Hs, int Ws, void* dst,
                        int64_t dst_pix_per_img, int64_t dst_off, int C, int N, bd_stream_t stream);
