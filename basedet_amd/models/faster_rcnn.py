@@ -39,6 +39,19 @@ class FasterRCNN(FPNDetector):
     def init_params(cfg, seed=0):
         return P.init_faster_rcnn_params(cfg, seed)
 
+    @classmethod
+    def check_config(cls, cfg):
+        super().check_config(cfg)
+        cls.check_anchor_config(cfg)
+        m = cfg.MODEL
+        check_roi_pooler_method(m.ROI_POOLER.METHOD)
+        if list(m.RCNN.STRIDES) != list(m.FPN.STRIDES)[: len(m.RCNN.IN_FEATURES)] or list(m.RCNN.IN_FEATURES) != list(m.FPN.OUT_FEATURES)[: len(m.RCNN.IN_FEATURES)]:
+            raise ValueError(f"MODEL.RCNN.IN_FEATURES = {list(m.RCNN.IN_FEATURES)!r} / STRIDES = {list(m.RCNN.STRIDES)!r} is not supported: "
+                             "the box head pools from the finest FPN levels, in order")
+        if m.RPN.TRAIN_POST_NMS_TOPK != m.RPN.TEST_POST_NMS_TOPK:
+            raise ValueError(f"MODEL.RPN.TEST_POST_NMS_TOPK = {m.RPN.TEST_POST_NMS_TOPK!r} is not supported: it has to equal TRAIN_POST_NMS_TOPK "
+                             f"({m.RPN.TRAIN_POST_NMS_TOPK!r}); training and inference share the proposal slots")
+
     # ---- construction ------------------------------------------------------------------------------------
     def _build_head(self, add, params):
         m = self.cfg.MODEL

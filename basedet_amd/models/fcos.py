@@ -21,6 +21,7 @@ GN_EPS = 1e-5   # megengine.module.normalization.GroupNorm default
 @registers.models.register()
 class FCOS(FPNDetector):
     ASSIGN_ON_SIDE_STREAM = False      # target assignment on a side stream under the forward pass (get_losses); ATSS: True
+    READS_SIZES_OF_INTEREST = True     # MODEL.HEAD.OBJECT_SIZES_OF_INTEREST (fcos.py:246); ATSS and OTA assign without it
 
     @staticmethod
     def init_params(cfg, seed=0):
@@ -32,6 +33,14 @@ class FCOS(FPNDetector):
         t = cfg.MODEL.LOSSES.IOU_LOSS_TYPE
         if not isinstance(t, str) or t not in ops.IOU_LOSS_TYPES:                  # iou_loss's own set (layers/losses/iou_loss.py:78)
             raise ValueError(f"MODEL.LOSSES.IOU_LOSS_TYPE = {t!r} is not supported: use one of {', '.join(map(repr, ops.IOU_LOSS_TYPES))}")
+        if cfg.MODEL.ANCHOR.NUM_ANCHORS != 1:
+            raise ValueError(f"MODEL.ANCHOR.NUM_ANCHORS = {cfg.MODEL.ANCHOR.NUM_ANCHORS!r} is not supported: only one anchor point per location is implemented")
+        if cfg.MODEL.FPN.OUT_CHANNELS != 256:
+            raise ValueError(f"MODEL.FPN.OUT_CHANNELS = {cfg.MODEL.FPN.OUT_CHANNELS!r} is not supported: the GroupNorm towers are built for 256 channels")
+        if cls.READS_SIZES_OF_INTEREST:
+            soi = [list(s) for s in cfg.MODEL.HEAD.OBJECT_SIZES_OF_INTEREST]
+            if len(soi) != len(cfg.MODEL.FPN.STRIDES) or any(len(s) != 2 for s in soi):
+                raise ValueError(f"MODEL.HEAD.OBJECT_SIZES_OF_INTEREST = {soi!r} is not supported: one [low, high] pair per FPN level is needed")
 
     # ---- construction ------------------------------------------------------------------------------------
     def _build_head(self, add, params):
@@ -231,6 +240,15 @@ class ATSS(FCOS):
     """ATSS (basedet/models/det/atss.py): the FCOS network and losses with the adaptive training-sample selection."""
 
     ASSIGN_ON_SIDE_STREAM = True
+    READS_SIZES_OF_INTEREST = False
+    MAX_TOPK = 16       # bd_atss_assign keeps at most 16 candidates per (gt, level) in LDS
+
+    @classmethod
+    def check_config(cls, cfg):
+        super().check_config(cfg)
+        k = cfg.MODEL.ANCHOR.TOPK
+        if not (isinstance(k, int) and 1 <= k <= cls.MAX_TOPK):
+            raise ValueError(f"MODEL.ANCHOR.TOPK = {k!r} is not supported: an integer from 1 to {cls.MAX_TOPK} is implemented")
 
     def _plan_head(self, pl):
         super()._plan_head(pl)
@@ -247,6 +265,8 @@ class OTA(FCOS):
     """OTA (basedet/models/det/ota.py): the FCOS network -- OTAPointHead with NORM_REG_TARGETS is PointHead's forward, its
     centre-ness branch read as the IoU prediction (point_head.py:154-212) -- with the prediction-aware dynamic top-k assignment
     (bd_ota_assign) and emd_losses' weighting (:183-233): focal / num_fg, 2 x GIoU / num_fg, 0.5 x BCE(iou) / num_fg."""
+
+    READS_SIZES_OF_INTEREST = False
 
     def __init__(self, cfg, *a, **k):
         self.matching = cfg.MODEL.get("MATCHING", "topk")

@@ -66,6 +66,25 @@ class FPNDetector:
             if up not in ("resize", "deconv"):
                 raise ValueError(f"MODEL.FPN.UPSAMPLE = {up!r} is not supported: use 'resize' or 'deconv'")
 
+    @staticmethod
+    def check_anchor_config(cfg, matcher=True):
+        """The anchor heads (RetinaNet family, the RPN): what the assignment kernels and the head's channel count hard-wire."""
+        m = cfg.MODEL
+        if matcher:
+            labels = list(m.MATCHER.LABELS)
+            if labels != [0, -1, 1]:
+                raise ValueError(f"MODEL.MATCHER.LABELS = {labels!r} is not supported: only [0, -1, 1] (background, ignore, foreground) is implemented")
+            thr = list(m.MATCHER.THRESHOLDS)
+            if len(thr) != 2 or not thr[0] <= thr[1]:
+                raise ValueError(f"MODEL.MATCHER.THRESHOLDS = {thr!r} is not supported: two ascending thresholds [low, high] are implemented")
+        scales, ratios = [list(s) for s in m.ANCHOR.SCALES], [list(r) for r in m.ANCHOR.RATIOS]
+        nlev = len(m.FPN.STRIDES)
+        if len(scales) not in (1, nlev) or len({len(s) for s in scales}) != 1:
+            raise ValueError(f"MODEL.ANCHOR.SCALES = {scales!r} is not supported: one list, or one per level, all of the same length "
+                             "(the head predicts the same number of anchors on every level)")
+        if len(ratios) != 1:
+            raise ValueError(f"MODEL.ANCHOR.RATIOS = {ratios!r} is not supported: only one ratio list shared by every level is implemented")
+
     def __init__(self, cfg, params=None, device="cuda", seed=0):
         self.check_config(cfg)
         self.cfg = cfg

@@ -10,6 +10,7 @@ from .retinanet import RetinaNet
 
 @registers.models.register()
 class FreeAnchor(RetinaNet):
+    READS_MATCHER = False
     MAX_CLASSES = 128       # bd_freeanchor_loss_fwd_bwd: the negative loss keeps 64 anchors x K box probabilities (8 bytes each) in 64 KB of LDS
 
     @classmethod

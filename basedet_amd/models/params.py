@@ -235,4 +235,7 @@ def oracle_arch(cfg):
                 strides=list(m.FPN.STRIDES), anchor_scales=[list(s) for s in m.ANCHOR.SCALES],
                 anchor_ratios=[list(r) for r in m.ANCHOR.RATIOS], anchor_offset=m.ANCHOR.OFFSET,
                 focal_alpha=m.LOSSES.FOCAL_LOSS_ALPHA, focal_gamma=m.LOSSES.FOCAL_LOSS_GAMMA,
-                smooth_l1_beta=m.LOSSES.SMOOTH_L1_BETA, reg_loss_weight=m.LOSSES.REG_LOSS_WEIGHT)
+                smooth_l1_beta=m.LOSSES.SMOOTH_L1_BETA, reg_loss_weight=m.LOSSES.REG_LOSS_WEIGHT,
+                # the Matcher and the BoxCoder (retinanet.py:32) of get_ground_truth (:224) and inference (:195)
+                matcher=(list(m.MATCHER.THRESHOLDS), list(m.MATCHER.LABELS), m.MATCHER.ALLOW_LOW_QUALITY),
+                box_reg=(list(m.BOX_REG.MEAN), list(m.BOX_REG.STD)))

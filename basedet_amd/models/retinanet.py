@@ -17,6 +17,8 @@ from .fpn_base import FPNDetector, _round_up
 
 @registers.models.register()
 class RetinaNet(FPNDetector):
+    READS_MATCHER = True        # MODEL.MATCHER.* (retinanet.py:33-37, :219); FreeAnchor's bag losses never call the matcher
+
     @staticmethod
     def init_params(cfg, seed=0):
         return P.init_retinanet_params(cfg, seed)
@@ -24,6 +26,7 @@ class RetinaNet(FPNDetector):
     @classmethod
     def check_config(cls, cfg):
         super().check_config(cfg)
+        cls.check_anchor_config(cfg, matcher=cls.READS_MATCHER)
         if not cfg.MODEL.HEAD.get("WITH_NORM", True):
             # retina_head.py:54-61: WITH_NORM = False drops the towers' ReLUs, which this head does not implement
             raise ValueError("MODEL.HEAD.WITH_NORM = False is not supported for the RetinaNet family: only True (the default) is implemented")

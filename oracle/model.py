@@ -207,7 +207,9 @@ class Oracle:
         logits, offsets, sizes, _ = self.retinanet_forward(image)
         anchors = np.concatenate(box_ops.default_anchors(sizes, a["strides"], a["anchor_scales"], a["anchor_ratios"], a["anchor_offset"]), 0)
         num_valid = np.asarray(batch["im_info"])[:, 4].astype(np.int32)
-        labels, gt_off, _ = box_ops.retinanet_ground_truth(anchors, batch["gt_boxes"], num_valid)
+        thr, labs, lq = a.get("matcher", ((0.4, 0.5), (0, -1, 1), True))
+        mean, std = a.get("box_reg", ((0, 0, 0, 0), (1, 1, 1, 1)))
+        labels, gt_off, _ = box_ops.retinanet_ground_truth(anchors, batch["gt_boxes"], num_valid, thr, labs, lq, mean, std)
         K = a["num_classes"]
         logits = logits.reshape(-1, K)
         offsets = offsets.reshape(-1, 4)
@@ -236,6 +238,11 @@ class Oracle:
         total = cls_loss + reg_loss
         return {"total_loss": total, "cls_loss": cls_loss, "reg_loss": reg_loss}, {
             "labels": labels, "gt_offsets": gt_off, "anchors": anchors, "logits": logits, "offsets": offsets, "num_fg": num_fg}
+
+    def retinanet_decode(self, anchors, offsets):
+        """RetinaNet.inference's box_coder.decode (retinanet.py:195): the BoxCoder(MODEL.BOX_REG) of :32 that get_ground_truth encodes with (:224)."""
+        mean, std = self.arch.get("box_reg", ((0, 0, 0, 0), (1, 1, 1, 1)))
+        return box_ops.box_decode(anchors, offsets, mean, std)
 
     # ---- FreeAnchor.get_losses (models/det/free_anchor.py:20-142): RetinaNet's network, bag losses ------------
     def freeanchor_losses(self, batch):

@@ -12,6 +12,8 @@ import torch
 
 from oracle import box_ops as ob
 from oracle import rcnn_ops as orc
+from tests.config_key_cases import SOI_EMPTY, SOI_OVERLAP
+from tests.config_key_cases import BOX_CODER_0 as CODER_0, BOX_CODER_A as CODER_A, BOX_CODER_B as CODER_B
 
 pytestmark = pytest.mark.gpu
 
@@ -84,10 +86,11 @@ def test_retina_assign_edge_cases(counts, Gmax):
     offs = torch.empty((N, A, 4), dtype=torch.float32, device="cuda")
     nfg = torch.zeros((1,), dtype=torch.int32, device="cuda")
     ws = torch.empty((N * Gmax,), dtype=torch.float32, device="cuda")
-    for thr, lq in (((0.4, 0.5), True), ((0.4, 0.5), False), ((0.3, 0.7), True)):
+    for thr, lq, (mean, std) in (((0.4, 0.5), True, CODER_0), ((0.4, 0.5), False, CODER_0), ((0.3, 0.7), True, CODER_0),
+                                 ((0.4, 0.5), False, CODER_A), ((0.3, 0.7), True, CODER_B), ((0.3, 0.6), False, CODER_A)):
         nfg.zero_()
-        ops.retina_assign_encode(_dev(anchors), _dev(gt), _dev(ng), thr[0], thr[1], lq, (0, 0, 0, 0), (1, 1, 1, 1), labels, midx, offs, nfg, ws)
-        rl, ro, ri = ob.retinanet_ground_truth(anchors, gt, ng, thresholds=thr, allow_low_quality=lq)
+        ops.retina_assign_encode(_dev(anchors), _dev(gt), _dev(ng), thr[0], thr[1], lq, mean, std, labels, midx, offs, nfg, ws)
+        rl, ro, ri = ob.retinanet_ground_truth(anchors, gt, ng, thresholds=thr, allow_low_quality=lq, mean=mean, std=std)
         gl = labels.cpu().numpy()
         assert np.array_equal(gl, rl), (thr, lq, int((gl != rl).sum()))
         assert np.array_equal(midx.cpu().numpy(), ri)
@@ -119,10 +122,11 @@ def test_fcos_and_atss_assign_edge_cases(counts, Gmax):
     offs = torch.empty((N, P, 4), dtype=torch.float32, device="cuda")
     ctr = torch.empty((N, P), dtype=torch.float32, device="cuda")
     stats = torch.zeros((2,), dtype=torch.float32, device="cuda")
-    for radius in (1.5, 0.0):
+    # the configured table at radius 1.5, 0 (inside the box) and 0.5; then overlapping ranges and a level with an empty range
+    for radius, table in ((1.5, soi), (0.0, soi), (0.5, soi), (1.5, SOI_OVERLAP), (0.0, SOI_EMPTY)):
         stats.zero_()
-        ops.fcos_assign(_dev(allp), start, soi, STRIDES, radius, _dev(gt), _dev(ng), labels, offs, ctr, stats)
-        rl, ro, rc = ob.fcos_ground_truth(pts, STRIDES, gt, ng, soi, radius)
+        ops.fcos_assign(_dev(allp), start, table, STRIDES, radius, _dev(gt), _dev(ng), labels, offs, ctr, stats)
+        rl, ro, rc = ob.fcos_ground_truth(pts, STRIDES, gt, ng, table, radius)
         assert np.array_equal(labels.cpu().numpy(), rl), radius
         assert np.array_equal(offs.cpu().numpy(), ro)
         fg = rl > 0
@@ -131,14 +135,15 @@ def test_fcos_and_atss_assign_edge_cases(counts, Gmax):
         assert st[0] == fg.sum() and np.isclose(st[1], rc[fg].sum(), rtol=1e-5)
     # ATSS on the same gts (models/det/atss.py:17-86)
     ws = torch.empty((ops.atss_assign_workspace_bytes(N, P),), dtype=torch.uint8, device="cuda")
-    stats.zero_()
-    ops.atss_assign(_dev(allp), start, STRIDES, 9, 8, _dev(gt), _dev(ng), labels, offs, ctr, stats, ws)
-    rl, ro, rc = ob.atss_ground_truth(pts, STRIDES, gt, ng, 8, 9)
-    assert np.array_equal(labels.cpu().numpy(), rl)
-    assert np.array_equal(offs.cpu().numpy(), ro)
-    fg = rl > 0
-    assert np.array_equal(ctr.cpu().numpy()[fg], rc[fg])
-    assert stats.cpu().numpy()[0] == fg.sum()
+    for topk, scale in ((9, 8), (13, 4), (1, 8)):            # (every level of this pyramid holds more than 13 points: 7 x 11 at the top)
+        stats.zero_()
+        ops.atss_assign(_dev(allp), start, STRIDES, topk, scale, _dev(gt), _dev(ng), labels, offs, ctr, stats, ws)
+        rl, ro, rc = ob.atss_ground_truth(pts, STRIDES, gt, ng, scale, topk)
+        assert np.array_equal(labels.cpu().numpy(), rl), (topk, scale)
+        assert np.array_equal(offs.cpu().numpy(), ro)
+        fg = rl > 0
+        assert np.array_equal(ctr.cpu().numpy()[fg], rc[fg])
+        assert stats.cpu().numpy()[0] == fg.sum()
 
 
 @pytest.mark.parametrize("counts,Gmax", [([1, 1], 1), ([37, 0, 9], 40), ([100, 100, 64], 100)])
@@ -161,14 +166,17 @@ def test_rpn_assign_and_sampling_edge_cases(counts, Gmax):
     nfg = torch.zeros((1,), dtype=torch.int32, device="cuda")
     nvalid = torch.zeros((1,), dtype=torch.int32, device="cuda")
     ws = torch.empty((N * Gmax,), dtype=torch.float32, device="cuda")
-    ops.rpn_assign_encode(_dev(anchors), _dev(gt), _dev(ng), 0.3, 0.7, True, [0, 0, 0, 0], [1, 1, 1, 1], labels, match, offs, nfg, ws)
-    ops.sample_labels(labels, _dev(kp), _dev(kn), 128, 256, nvalid)
-    ref_l, ref_o = orc.rpn_ground_truth(anchors, gt, ng, kp, kn, (0.3, 0.7), (0, -1, 1), True, 256, 128)
-    gl = labels.cpu().numpy()
-    assert np.array_equal(gl, ref_l), int((gl != ref_l).sum())
-    assert int(nvalid.item()) == int((ref_l >= 0).sum())
-    fg = (ref_l > 0) & np.isfinite(ref_o).all(axis=-1)
-    np.testing.assert_allclose(offs.cpu().numpy()[fg], ref_o[fg], rtol=2e-6, atol=2e-6)
+    # positive ratio 0.5 (the default), 0.25 and 1.0 of 256 samples; the identity coder and the two others
+    for num_pos, (mean, std) in ((128, CODER_0), (64, CODER_A), (256, CODER_B)):
+        nfg.zero_(); nvalid.zero_()
+        ops.rpn_assign_encode(_dev(anchors), _dev(gt), _dev(ng), 0.3, 0.7, True, list(mean), list(std), labels, match, offs, nfg, ws)
+        ops.sample_labels(labels, _dev(kp), _dev(kn), num_pos, 256, nvalid)
+        ref_l, ref_o = orc.rpn_ground_truth(anchors, gt, ng, kp, kn, (0.3, 0.7), (0, -1, 1), True, 256, num_pos, mean, std)
+        gl = labels.cpu().numpy()
+        assert np.array_equal(gl, ref_l), (num_pos, int((gl != ref_l).sum()))
+        assert int(nvalid.item()) == int((ref_l >= 0).sum())
+        fg = (ref_l > 0) & np.isfinite(ref_o).all(axis=-1)
+        np.testing.assert_allclose(offs.cpu().numpy()[fg], ref_o[fg], rtol=2e-6, atol=2e-6)
 
 
 @pytest.mark.parametrize("counts,Gmax", [([1, 1], 1), ([37, 0, 9], 40), ([100, 100, 64], 100)])
@@ -206,15 +214,20 @@ def test_rcnn_sample_targets_edge_cases(counts, Gmax):
     o_cnt = torch.empty((N,), dtype=torch.int32, device="cuda")
     tot = torch.zeros((1,), dtype=torch.int32, device="cuda")
     gt_clean = np.where(np.isfinite(gt), gt, 0).astype(np.float32)               # the oracle gets the sliced rows; the kernel the garbage too
-    ops.rcnn_sample_targets(_dev(rois), _dev(num_rois), _dev(gt), _dev(ng), _dev(kf), _dev(kb), S, nfgmax, 0.5, 0.5, 0.0,
-                            [0, 0, 0, 0], std, o_rois, o_lab, o_tgt, o_cnt, tot)
-    for n in range(N):
-        rr, rl, rt = orc.rcnn_ground_truth(rois[n, : num_rois[n]], gt_clean[n, : ng[n]], kf[n], kb[n], S, 0.5, 0.5, 0.5, 0.0, (0, 0, 0, 0), std)
-        m = len(rl)
-        assert int(o_cnt[n].item()) == m
-        gl = o_lab[n].cpu().numpy()
-        assert np.array_equal(gl[:m], rl), (n, int((gl[:m] != rl).sum()))
-        assert np.all(gl[m:] == -1)
-        assert np.array_equal(o_rois[n].cpu().numpy()[:m], rr)
-        fin = np.isfinite(rt).all(axis=-1) & (rl > 0)
-        np.testing.assert_allclose(o_tgt[n].cpu().numpy()[:m][fin], rt[fin], rtol=2e-5, atol=2e-5)
+    # the configured bands and coder; then a gap between the bands and a floor under the background band (0.6 / 0.4 / 0.1) with no
+    # foreground quota at all and with the whole sample as quota, under the two other coders
+    for nfgmax, (fg_t, bg_hi, bg_lo), (mean, std) in ((nfgmax, (0.5, 0.5, 0.0), ((0, 0, 0, 0), std)), (0, (0.6, 0.4, 0.1), CODER_A),
+                                                      (S, (0.6, 0.4, 0.1), CODER_B)):
+        tot.zero_()
+        ops.rcnn_sample_targets(_dev(rois), _dev(num_rois), _dev(gt), _dev(ng), _dev(kf), _dev(kb), S, nfgmax, fg_t, bg_hi, bg_lo,
+                                list(mean), list(std), o_rois, o_lab, o_tgt, o_cnt, tot)
+        for n in range(N):
+            rr, rl, rt = orc.rcnn_ground_truth(rois[n, : num_rois[n]], gt_clean[n, : ng[n]], kf[n], kb[n], S, nfgmax / S, fg_t, bg_hi, bg_lo, mean, std)
+            m = len(rl)
+            assert int(o_cnt[n].item()) == m
+            gl = o_lab[n].cpu().numpy()
+            assert np.array_equal(gl[:m], rl), (n, nfgmax, int((gl[:m] != rl).sum()))
+            assert np.all(gl[m:] == -1)
+            assert np.array_equal(o_rois[n].cpu().numpy()[:m], rr)
+            fin = np.isfinite(rt).all(axis=-1) & (rl > 0)
+            np.testing.assert_allclose(o_tgt[n].cpu().numpy()[:m][fin], rt[fin], rtol=2e-5, atol=2e-5)

@@ -102,20 +102,20 @@ def _compare_oracle(out, sc_l, bx_l, K, cfg, k, tol, im_info):
 _RUNS = {}
 
 
-def _retinanet_params(seed=5):
+def _retinanet_params(seed=5, overrides=None):
     from tests.test_model_gpu import _setup
-    cfg, params, _ = _setup("resnet18", N, SIZE, seed=seed)
+    cfg, params, _ = _setup("resnet18", N, SIZE, seed=seed, overrides=overrides)
     params["head.cls_score.weight"] = params["head.cls_score.weight"] * 8
     params["head.bbox_pred.weight"] = params["head.bbox_pred.weight"] * 8
     return cfg, params
 
 
-def _run_retinanet():
-    if "retinanet" in _RUNS:
-        return _RUNS["retinanet"]
+def _run_retinanet(name="retinanet", overrides=None):
+    if name in _RUNS:
+        return _RUNS[name]
     from basedet_amd import ops
     from basedet_amd.models import RetinaNet
-    cfg, params = _retinanet_params()
+    cfg, params = _retinanet_params(overrides=overrides)
     batch = {"data": _data(5), "im_info": IM_INFO}
     thr = cfg.TEST.CLS_THRESHOLD
     model = RetinaNet(cfg, params=params).eval()
@@ -144,8 +144,8 @@ def _run_retinanet():
         boxes = ops.box_decode(pl.anchors, deltas, m.MEAN, m.STD).cpu().numpy()
         np.testing.assert_allclose(boxes, ob.box_decode(pl.anchors.cpu().numpy(), deltas.cpu().numpy(), m.MEAN, m.STD), rtol=1e-5, atol=1e-3)
         per.append(dict(ref=ref, sc_l=_level_split(scores.cpu().numpy(), [r * K for r in lvl_rows]), bx_l=_level_split(boxes, lvl_rows)))
-    _RUNS["retinanet"] = (cfg, K, outs, per, 1000, (1e-5, 1e-3))
-    return _RUNS["retinanet"]
+    _RUNS[name] = (cfg, K, outs, per, 1000, (1e-5, 1e-3))
+    return _RUNS[name]
 
 
 def _fcos_params():
@@ -271,6 +271,18 @@ def test_batched_inference_matches_oracle_per_image(name):
     for i in range(N):
         n = _compare_oracle(outs[i], per[i]["sc_l"], per[i]["bx_l"], K, cfg, k, tol, IM_INFO[i, :4])
         assert n > 10
+
+
+@pytest.mark.parametrize("coder", ["A", "B"])
+def test_batched_retinanet_decodes_with_box_reg(coder):
+    """MODEL.BOX_REG with a non-zero mean (A) and with four different stds (B) through bd_det_candidates_batched: three images, bit-identical
+    to the single-image operators under the same coder and, per image, the oracle's detections (box_decode with that mean and std)."""
+    from tests import config_key_cases as C
+    cfg, K, outs, per, k, tol = _run_retinanet("retinanet_coder_" + coder, dict(MODEL=dict(BOX_REG=dict(A=C.CODER_A, B=C.CODER_B)[coder])))
+    assert list(cfg.MODEL.BOX_REG.STD) == list(dict(A=C.BOX_CODER_A, B=C.BOX_CODER_B)[coder][1])
+    for i in range(N):
+        _assert_same_bits(outs[i], per[i]["ref"], f"coder {coder} image {i}")
+        assert _compare_oracle(outs[i], per[i]["sc_l"], per[i]["bx_l"], K, cfg, k, tol, IM_INFO[i, :4]) > 10
 
 
 def test_an_image_without_detections_between_two_with():

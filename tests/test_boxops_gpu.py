@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import box_ops as ob
+from tests.config_key_cases import BOX_CODER_0 as CODER_0, BOX_CODER_A as CODER_A, BOX_CODER_B as CODER_B
 
 pytestmark = pytest.mark.gpu
 
@@ -89,14 +90,14 @@ def test_box_coder():
     anc = np.concatenate([xy, xy + wh], 1)
     xy = rng.uniform(0, 500, (5000, 2)).astype(np.float32); wh = rng.uniform(4, 200, (5000, 2)).astype(np.float32)
     gt = np.concatenate([xy, xy + wh], 1)
-    mean, std = (0.0, 0.0, 0.0, 0.0), (0.1, 0.1, 0.2, 0.2)
-    enc = ops.box_encode(_dev(anc), _dev(gt), mean, std).cpu().numpy()
-    ref = ob.box_encode(anc, gt, mean, std)
-    assert np.array_equal(enc[:, :2], ref[:, :2])                        # no transcendental: bit-exact
-    assert np.allclose(enc[:, 2:], ref[:, 2:], rtol=2e-6, atol=2e-6)      # logf: ulp-level tolerance
-    dec = ops.box_decode(_dev(anc), _dev(ref), mean, std).cpu().numpy()
-    assert np.allclose(dec, ob.box_decode(anc, ref, mean, std), rtol=1e-5, atol=1e-3)
-    assert np.allclose(dec, gt, rtol=1e-4, atol=1e-2)                     # encode -> decode round trip
+    for mean, std in (((0.0, 0.0, 0.0, 0.0), (0.1, 0.1, 0.2, 0.2)), CODER_0, CODER_A, CODER_B):
+        enc = ops.box_encode(_dev(anc), _dev(gt), mean, std).cpu().numpy()
+        ref = ob.box_encode(anc, gt, mean, std)
+        assert np.array_equal(enc[:, :2], ref[:, :2]), (mean, std)           # no transcendental: bit-exact
+        assert np.allclose(enc[:, 2:], ref[:, 2:], rtol=2e-6, atol=2e-6)      # logf: ulp-level tolerance
+        dec = ops.box_decode(_dev(anc), _dev(ref), mean, std).cpu().numpy()
+        assert np.allclose(dec, ob.box_decode(anc, ref, mean, std), rtol=1e-5, atol=1e-3)
+        assert np.allclose(dec, gt, rtol=1e-4, atol=1e-2), (mean, std)        # encode -> decode round trip
 
 
 @pytest.mark.parametrize("size", [(800, 1344), (512, 512)])
@@ -301,13 +302,18 @@ def test_atss_assign_bit_exact():
     ctr = torch.empty((N, P), dtype=torch.float32, device="cuda")
     stats = torch.zeros((2,), dtype=torch.float32, device="cuda")
     ws = torch.empty((ops.atss_assign_workspace_bytes(N, P),), dtype=torch.uint8, device="cuda")
-    ops.atss_assign(_dev(allp), lvl_start, strides, 9, 8, _dev(gt), _dev(num), labels, offs, ctr, stats, ws)
-    rl, ro, rc = ob.atss_ground_truth(pts, strides, gt, num, 8, 9)
-    assert np.array_equal(labels.cpu().numpy(), rl)
-    assert np.array_equal(offs.cpu().numpy(), ro)
-    got_c = ctr.cpu().numpy()
-    fg = rl > 0
-    assert fg.sum() > 20 and np.array_equal(got_c[fg], rc[fg])
-    assert np.array_equal(np.nan_to_num(got_c), np.nan_to_num(rc))
-    st = stats.cpu().numpy()
-    assert st[0] == fg.sum() and abs(st[1] - rc[fg].sum()) <= 1e-4 * rc[fg].sum()
+    # ANCHOR.TOPK x ANCHOR.SCALE; the coarsest level holds 2 x 3 = 6 points: topk = 9 and 13 take all of them there (atss.py:44
+    # F.topk(k = min(topk, points)), as the oracle), topk = 13 also exceeds nothing else (4 x 5 = 20)
+    assert sizes[-1][0] * sizes[-1][1] < 9
+    for topk, scale in ((9, 8), (1, 8), (13, 8), (9, 4), (1, 4), (13, 4)):
+        stats.zero_()
+        ops.atss_assign(_dev(allp), lvl_start, strides, topk, scale, _dev(gt), _dev(num), labels, offs, ctr, stats, ws)
+        rl, ro, rc = ob.atss_ground_truth(pts, strides, gt, num, scale, topk)
+        assert np.array_equal(labels.cpu().numpy(), rl), (topk, scale)
+        assert np.array_equal(offs.cpu().numpy(), ro)
+        got_c = ctr.cpu().numpy()
+        fg = rl > 0
+        assert fg.sum() > (20 if topk > 1 else 5) and np.array_equal(got_c[fg], rc[fg])
+        assert np.array_equal(np.nan_to_num(got_c), np.nan_to_num(rc))
+        st = stats.cpu().numpy()
+        assert st[0] == fg.sum() and abs(st[1] - rc[fg].sum()) <= 1e-4 * rc[fg].sum()

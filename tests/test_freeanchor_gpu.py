@@ -8,7 +8,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _problem(seed, N=2, K=16, sizes=((16, 20), (8, 10), (4, 5)), strides=(8, 16, 32), gmax=6, dup_class=False):
+CODER = ((0, 0, 0, 0), (0.1, 0.1, 0.2, 0.2))        # FreeAnchorConfig's BOX_REG
+
+
+def _problem(seed, N=2, K=16, sizes=((16, 20), (8, 10), (4, 5)), strides=(8, 16, 32), gmax=6, dup_class=False, coder=CODER):
     from oracle import box_ops
     rng = np.random.default_rng(seed)
     scales = [[s * 4, s * 4 * 2 ** (1 / 3), s * 4 * 2 ** (2 / 3)] for s in strides]
@@ -33,16 +36,29 @@ def _problem(seed, N=2, K=16, sizes=((16, 20), (8, 10), (4, 5)), strides=(8, 16,
     for n in range(N):
         best = box_ops.box_iou(gt[n, :max(1, num[n]), :4], anchors).argmax(0)
         tgt = box_ops.box_encode(anchors, gt[n, best, :4], (0, 0, 0, 0), (0.1, 0.1, 0.2, 0.2))
-        offsets[n] = np.clip(tgt, -8, 8) * rng.uniform(0.6, 1.0, (A, 1)).astype(np.float32) + rng.normal(0, 0.3, (A, 4)).astype(np.float32)
+        pred = np.clip(tgt, -8, 8) * rng.uniform(0.6, 1.0, (A, 1)).astype(np.float32) + rng.normal(0, 0.3, (A, 4)).astype(np.float32)
+        # the same predicted boxes under another coder: offsets' = (offsets * std + mean - mean') / std' (the identity for the default)
+        (m0, s0), (m1, s1) = CODER, coder
+        offsets[n] = ((pred * np.asarray(s0, np.float32) + np.asarray(m0, np.float32) - np.asarray(m1, np.float32)) / np.asarray(s1, np.float32)
+                      if coder != CODER else pred)
     logits = rng.normal(-2.0, 1.5, (N, A, K)).astype(np.float32)
     return anchors, gt, num, logits, offsets
 
 
 @pytest.mark.parametrize("seed,dup,beta", [(0, False, 0.0), (1, True, 0.0), (2, False, 0.11)])
 def test_freeanchor_losses_and_gradients(seed, dup, beta):
+    """The configured coder, then MODEL.BOX_REG with a non-zero mean and with four different stds (the kernel decodes the predictions and
+    encodes the bag targets with it): the same predicted boxes, so the same bags, expressed under each coder."""
+    from tests.config_key_cases import BOX_CODER_A, BOX_CODER_B
+    for coder in (CODER, BOX_CODER_A, BOX_CODER_B):
+        _check_losses_and_gradients(seed, dup, beta, coder)
+
+
+def _check_losses_and_gradients(seed, dup, beta, coder):
     from basedet_amd import ops
     from oracle import freeanchor
-    anchors, gt, num, logits, offsets = _problem(seed, dup_class=dup)
+    mean, std = coder
+    anchors, gt, num, logits, offsets = _problem(seed, dup_class=dup, coder=coder)
     N, A, K = logits.shape
     apix, ld = 9, 40
     bucket = 50 if seed != 2 else 20
@@ -51,7 +67,7 @@ def test_freeanchor_losses_and_gradients(seed, dup, beta):
     # ---- oracle on the bf16-rounded operands
     lt = lg.float().clone().requires_grad_(True)
     ot = of.float().clone().requires_grad_(True)
-    pos, neg = freeanchor.bag_losses(lt, ot, anchors, gt, num, std=(0.1, 0.1, 0.2, 0.2), iou_thresh=0.6, bucket=bucket, beta=beta,
+    pos, neg = freeanchor.bag_losses(lt, ot, anchors, gt, num, mean=mean, std=std, iou_thresh=0.6, bucket=bucket, beta=beta,
                                      reg_weight=0.75, alpha=0.25, gamma=2.0)
     (pos + neg).backward()
     # ---- HIP
@@ -64,7 +80,7 @@ def test_freeanchor_losses_and_gradients(seed, dup, beta):
     loss = torch.zeros(2, dtype=torch.float32, device=dev)
     ws = torch.empty(ops.freeanchor_workspace_bytes(N, gt.shape[1], bucket, A), dtype=torch.uint8, device=dev)
     ops.freeanchor_loss_fwd_bwd(lg_dev, off_dev, ld, apix, torch.from_numpy(anchors).to(dev), K, torch.from_numpy(gt).to(dev),
-                                torch.from_numpy(num).to(dev), (0, 0, 0, 0), (0.1, 0.1, 0.2, 0.2), 0.6, bucket, beta, 0.75, 0.25, 2.0,
+                                torch.from_numpy(num).to(dev), mean, std, 0.6, bucket, beta, 0.75, 0.25, 2.0,
                                 loss, d_lg, d_of, ws)
     torch.cuda.synchronize()
     got = loss.cpu().numpy()

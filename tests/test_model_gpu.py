@@ -11,12 +11,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _setup(backbone, N, size, seed=0):
+def _setup(backbone, N, size, seed=0, overrides=None):
     from basedet_amd.configs import RetinaNetConfig, retinanet_r18_config
     from basedet_amd.models import params as P
     from basedet_amd.utils import DummyLoader
     cfg = retinanet_r18_config() if backbone == "resnet18" else RetinaNetConfig()
     cfg.MODEL.BATCHSIZE = N
+    if overrides:
+        cfg.merge(overrides)
     params = P.init_retinanet_params(cfg, seed)
     rng = np.random.default_rng(seed + 1)
     for k in list(params):                       # non-trivial FrozenBN statistics
@@ -47,10 +49,16 @@ def _grad_of(model, name, like, cache={}):
 # plumbing configuration, which bench.py's cpu_baseline leg times on the oracle): the HIP step against the oracle on C1's workload
 @pytest.mark.parametrize("backbone,N,size", [("resnet18", 2, (128, 160)), ("resnet50", 3, (96, 128)), ("resnet18", 2, (512, 512))])
 def test_training_step_matches_oracle(backbone, N, size):
+    check_retinanet_step(*_setup(backbone, N, size))
+
+
+def check_retinanet_step(cfg, params, batch):
+    """One RetinaNet training step against the oracle: the assertions of test_training_step_matches_oracle, for any config (also
+    imported by test_config_keys_gpu.py)."""
     from basedet_amd.models import RetinaNet, params as P
     from basedet_amd.solver import DetSolver
     from oracle.model import Oracle
-    cfg, params, batch = _setup(backbone, N, size)
+    N = cfg.MODEL.BATCHSIZE
     model = RetinaNet(cfg, params=params)
     names = P.trainable_names(params, cfg.MODEL.BACKBONE.FREEZE_AT)
     assert sorted(names) == sorted(model.state_dict_trainable_names())
@@ -137,9 +145,15 @@ def _level_split(t, sizes, per_pixel):
 def test_retinanet_inference_matches_oracle():
     """retinanet.py:172-209 on the HIP kernels (scores, per-level top-k, decode, NMS, rescale) against the numpy restatement
     evaluated on the same bf16 logits / offsets."""
-    from basedet_amd.models import RetinaNet
-    from oracle import box_ops as ob, rcnn_ops as orc
-    cfg, params, batch = _setup("resnet18", 1, (128, 160), seed=5)
+    check_retinanet_inference()
+
+
+def check_retinanet_inference(overrides=None):
+    """The assertions of test_retinanet_inference_matches_oracle under a config override (also imported by test_config_keys_gpu.py)."""
+    from basedet_amd.models import RetinaNet, params as P
+    from oracle import rcnn_ops as orc
+    from oracle.model import Oracle
+    cfg, params, batch = _setup("resnet18", 1, (128, 160), seed=5, overrides=overrides)
     params["head.cls_score.bias"] = np.full_like(params["head.cls_score.bias"], -2.5)      # scores around the 0.05 threshold
     params["head.cls_score.weight"] = params["head.cls_score.weight"] * 8
     params["head.bbox_pred.weight"] = params["head.bbox_pred.weight"] * 8
@@ -151,7 +165,7 @@ def test_retinanet_inference_matches_oracle():
     K, A = model.num_classes, model.num_anchors
     logits = pl.logits.float().cpu().numpy().reshape(-1)
     offs = pl.offsets.float().cpu().numpy()[:, : A * 4].reshape(-1, 4)
-    boxes_all = ob.box_decode(pl.anchors.cpu().numpy(), offs)
+    boxes_all = Oracle(params, P.oracle_arch(cfg)).retinanet_decode(pl.anchors.cpu().numpy(), offs)      # MODEL.BOX_REG (identity by default)
     sc_l = _level_split(orc.sigmoid(logits), pl.sizes, A * K)
     bx_l = _level_split(boxes_all, pl.sizes, A)
     rb, rs, rl = orc.detect_postprocess(sc_l, bx_l, K, batch["im_info"][0], cfg.TEST.CLS_THRESHOLD, cfg.TEST.IOU_THRESHOLD,
@@ -196,9 +210,14 @@ def test_fcos_inference_matches_oracle():
 def test_faster_rcnn_inference_matches_oracle():
     """faster_rcnn.py:98-131: proposals (test top-k) -> box head on every proposal -> softmax / per-class decode -> threshold
     -> NMS; the oracle restates the post-processing on the box-head outputs of the HIP run."""
+    check_faster_rcnn_inference()
+
+
+def check_faster_rcnn_inference(overrides=None):
+    """The assertions of test_faster_rcnn_inference_matches_oracle under a config override (also imported by test_config_keys_gpu.py)."""
     from basedet_amd.models import FasterRCNN
     from oracle import box_ops as ob, rcnn_ops as orc
-    cfg, params, batch = _frcnn_setup(1, (128, 160), seed=2)
+    cfg, params, batch = _frcnn_setup(1, (128, 160), seed=2, overrides=overrides)
     params["rcnn.pred_cls.weight"] = params["rcnn.pred_cls.weight"] * 5      # confident but unsaturated softmax scores
     model = FasterRCNN(cfg, params=params).eval()
     out = model({"data": batch["data"], "im_info": batch["im_info"]})
@@ -226,13 +245,19 @@ def test_faster_rcnn_inference_matches_oracle():
 def test_fcos_training_step_matches_oracle():
     """FCOS (models/det/fcos.py): GroupNorm towers, per-level scales, centre-ness; point target assignment bit-exact,
     losses within bf16 tolerance, gradients tight against the oracle evaluated on the same stored activations."""
+    check_fcos_step(*fcos_setup())
+
+
+def fcos_setup(overrides=None):
+    """The FCOS fixture of test_fcos_training_step_matches_oracle; `overrides` is merged into the config before the parameters are drawn."""
     from basedet_amd.configs import FCOSConfig
-    from basedet_amd.models import FCOS, params as P
+    from basedet_amd.models import params as P
     from basedet_amd.utils import DummyLoader
-    from oracle.model import Oracle
     N, size = 2, (128, 160)
     cfg = FCOSConfig()
     cfg.MODEL.BATCHSIZE = N
+    if overrides:
+        cfg.merge(overrides)
     params = P.init_fcos_params(cfg, seed=0, residual_gamma=0.25)
     rng = np.random.default_rng(7)
     for k in list(params):
@@ -244,6 +269,13 @@ def test_fcos_training_step_matches_oracle():
             params[k] = np.full_like(params[k], 0.5)                                     # keep relu(bbox_pred * scale) alive
     batch = next(DummyLoader(N, size, seed=0))
     batch["data"] = (batch["data"] * 255).astype(np.float32)
+    return cfg, params, batch
+
+
+def check_fcos_step(cfg, params, batch):
+    """The assertions of test_fcos_training_step_matches_oracle, for any FCOS config (also imported by test_config_keys_gpu.py)."""
+    from basedet_amd.models import FCOS, params as P
+    from oracle.model import Oracle
     model = FCOS(cfg, params=params)
     names = P.trainable_names(params, cfg.MODEL.BACKBONE.FREEZE_AT)
     assert sorted(names) == sorted(model.state_dict_trainable_names())
@@ -271,7 +303,7 @@ def test_fcos_training_step_matches_oracle():
         assert rel < 2e-2, (n, rel)
 
 
-def _frcnn_setup(N, size, seed=0, pool=(7, 7)):
+def _frcnn_setup(N, size, seed=0, pool=(7, 7), overrides=None):
     from basedet_amd.configs import FasterRCNNConfig
     from basedet_amd.models import params as P
     from basedet_amd.utils import DummyLoader
@@ -281,6 +313,8 @@ def _frcnn_setup(N, size, seed=0, pool=(7, 7)):
                               RPN=dict(TRAIN_PREV_NMS_TOPK=300, TRAIN_POST_NMS_TOPK=120, TEST_PREV_NMS_TOPK=300, TEST_POST_NMS_TOPK=120,
                                        NUM_SAMPLE_ANCHORS=64),
                               RCNN=dict(NUM_ROIS=48), ROI_POOLER=dict(SIZE=tuple(pool)))))
+    if overrides:
+        cfg.merge(overrides)
     params = P.init_faster_rcnn_params(cfg, seed, residual_gamma=0.25)
     rng = np.random.default_rng(seed + 11)
     # larger head weights than the N(0, 0.01) init so that scores / deltas are not all ~0 (non-trivial top-k, NMS, sampling)
@@ -299,10 +333,16 @@ def test_faster_rcnn_training_step_matches_oracle(pool):
     proposal / sample selection sees identical scores); parameter gradients rel-L2 <= 2e-2 per parameter.
     ROI_POOLER.SIZE other than the configured 7 x 7 (the reference's roi_pool takes any, roi_pool.py:35-78): RoIAlign's backward then
     leaves the tiled 7 x 7 kernel for the general fp32 scatter -- chosen per plan, no flag."""
+    check_faster_rcnn_step(*_frcnn_setup(2, (128, 160), pool=pool))
+
+
+def check_faster_rcnn_step(cfg, params, batch):
+    """The assertions of test_faster_rcnn_training_step_matches_oracle, for any Faster R-CNN config at 2 x 128 x 160 (also imported by
+    test_config_keys_gpu.py)."""
     from basedet_amd.models import FasterRCNN, params as P
     from oracle.model import Oracle
     N, size = 2, (128, 160)
-    cfg, params, batch = _frcnn_setup(N, size, pool=pool)
+    pool = tuple(cfg.MODEL.ROI_POOLER.SIZE)
     model = FasterRCNN(cfg, params=params)
     assert model.deterministic_roi_bwd is True
     names = P.trainable_names(params, cfg.MODEL.BACKBONE.FREEZE_AT)
@@ -466,17 +506,30 @@ def test_inference_without_detections_returns_empty():
 def test_atss_training_step_matches_oracle():
     """ATSS (models/det/atss.py) = the FCOS network with the adaptive sample selection: assignment bit-exact, losses within bf16
     tolerance, gradients tight against the oracle evaluated on the same stored activations."""
+    check_atss_step(*atss_setup())
+
+
+def atss_setup(overrides=None):
+    """The ATSS fixture of test_atss_training_step_matches_oracle; `overrides` is merged into the config before the parameters are drawn."""
     from basedet_amd.configs import ATSSConfig
-    from basedet_amd.models import ATSS, params as P
+    from basedet_amd.models import params as P
     from basedet_amd.utils import DummyLoader
-    from oracle.model import Oracle
     N, size = 2, (128, 160)
     cfg = ATSSConfig()
     cfg.MODEL.BATCHSIZE = N
+    if overrides:
+        cfg.merge(overrides)
     params = P.init_fcos_params(cfg, seed=0, residual_gamma=0.25)
     params["head.bbox_pred.bias"] = np.full_like(params["head.bbox_pred.bias"], 0.5)
     batch = next(DummyLoader(N, size, seed=0))
     batch["data"] = (batch["data"] * 255).astype(np.float32)
+    return cfg, params, batch
+
+
+def check_atss_step(cfg, params, batch):
+    """The assertions of test_atss_training_step_matches_oracle, for any ATSS config (also imported by test_config_keys_gpu.py)."""
+    from basedet_amd.models import ATSS, params as P
+    from oracle.model import Oracle
     model = ATSS(cfg, params=params)
     names = P.trainable_names(params, cfg.MODEL.BACKBONE.FREEZE_AT)
     orc = Oracle(params, P.oracle_arch(cfg), trainable=names)

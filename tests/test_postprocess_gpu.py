@@ -19,7 +19,10 @@ SIZES = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]        # 800x1344, s
 STRIDES = [8, 16, 32, 64, 128]
 SCALES = [[x, x * 2 ** (1.0 / 3), x * 2 ** (2.0 / 3)] for x in [32, 64, 128, 256, 512]]
 RATIOS = [[0.5, 1, 2]]
+from tests.config_key_cases import BOX_CODER_A, BOX_CODER_B  # noqa: E402
+
 MEAN, STD = (0.0, 0.0, 0.0, 0.0), (0.1, 0.1, 0.2, 0.2)
+CODERS = ((MEAN, STD), BOX_CODER_A, BOX_CODER_B)      # further coders for the kernels that decode
 
 
 def _ops():
@@ -184,20 +187,22 @@ def test_det_candidates(mode):
     boxes = torch.full((L * k, 4), 7.0, device="cuda")
     scores = torch.full((1, L * k), 7.0, device="cuda")
     labels = torch.full((1, L * k), 7, dtype=torch.int32, device="cuda")
-    ops.det_candidates(mode, _dev(tk_idx), _dev(tk_sc), _dev(tk_cnt), L, k, row_off, K,
-                       _dev(anchors) if anchors is not None else None, offsets.cuda() if offsets_np is not None else None, off_ld, A,
-                       MEAN, STD, _dev(item_boxes) if item_boxes is not None else None, boxes, scores, labels)
+    for mean, std in (CODERS if mode == 0 else CODERS[:1]):          # mode 0 is the one that decodes with a box coder (MODEL.BOX_REG)
+        boxes.fill_(7.0); scores.fill_(7.0); labels.fill_(7)
+        ops.det_candidates(mode, _dev(tk_idx), _dev(tk_sc), _dev(tk_cnt), L, k, row_off, K,
+                           _dev(anchors) if anchors is not None else None, offsets.cuda() if offsets_np is not None else None, off_ld, A,
+                           mean, std, _dev(item_boxes) if item_boxes is not None else None, boxes, scores, labels)
 
-    def ref_box(l, idx):
-        row = row_off[l] + idx // K
-        if mode == 2:
-            return item_boxes[row * K + idx % K]
-        d = offsets_np[row // A][np.arange(len(row))[:, None], (row % A)[:, None] * 4 + np.arange(4)[None]]
-        if mode == 0:
-            return ob.box_decode(anchors[row], d, MEAN, STD)
-        return ob.point_decode(anchors[row], d)
+        def ref_box(l, idx):
+            row = row_off[l] + idx // K
+            if mode == 2:
+                return item_boxes[row * K + idx % K]
+            d = offsets_np[row // A][np.arange(len(row))[:, None], (row % A)[:, None] * 4 + np.arange(4)[None]]
+            if mode == 0:
+                return ob.box_decode(anchors[row], d, mean, std)
+            return ob.point_decode(anchors[row], d)
 
-    _check_candidates(boxes, scores, labels, tk_idx, tk_sc, tk_cnt, K, ref_box, exact=mode != 0)
+        _check_candidates(boxes, scores, labels, tk_idx, tk_sc, tk_cnt, K, ref_box, exact=mode != 0)
 
 
 # ---- nms_batched ----------------------------------------------------------------------------------------------------
@@ -311,6 +316,11 @@ def test_rcnn_predict(K):
     num_rois = np.array([per_img, 120, 0], np.int32)
     scores = torch.full((R * K,), float("nan"), device="cuda")
     boxes = torch.full((R * K, 4), float("nan"), device="cuda")
+    deltas = raw.float().numpy()[:, K + 1: K + 1 + 4 * K].reshape(R * K, 4)
+    for mean, std in CODERS[1:]:                     # MODEL.RCNN_BOX_REG other than the configured one (checked last, with the scores)
+        ops.rcnn_predict(raw.cuda(), ld, K, K + 1, _dev(rois), _dev(num_rois), per_img, mean, std, scores, boxes)
+        np.testing.assert_allclose(boxes.cpu().numpy(), ob.box_decode(np.repeat(rois, K, 0), deltas, mean, std), rtol=1e-5, atol=1e-3)
+        scores.fill_(float("nan")); boxes.fill_(float("nan"))
     ops.rcnn_predict(raw.cuda(), ld, K, K + 1, _dev(rois), _dev(num_rois), per_img, MEAN, STD, scores, boxes)
     r = raw.double()
     p64 = torch.softmax(r[:, : K + 1], 1)[:, 1:].reshape(-1)

@@ -7,6 +7,7 @@ import torch
 
 from oracle import box_ops as ob
 from oracle import rcnn_ops as orc
+from tests.config_key_cases import BOX_CODER_0 as CODER_0, BOX_CODER_A as CODER_A, BOX_CODER_B as CODER_B
 
 pytestmark = pytest.mark.gpu
 
@@ -207,32 +208,36 @@ def test_rpn_proposals(pre_k, post_k, per_level, ties):
     anchors = _anchors(sizes)
     anc_all = np.concatenate(anchors, 0)
     im_info = np.array([[H, W, H, W, 3], [180, 300, 180, 300, 2]] + [[H, W, H, W, 1]] * (N - 2), np.float32)
-    thr = 0.7
     geom = _geom(N, sizes)
     rois = torch.empty((N, post_k, 4), dtype=torch.float32, device="cuda")
     num = torch.empty((N,), dtype=torch.int32, device="cuda")
     ws = torch.empty((ops.rpn_proposals_workspace_bytes(N, [h * w for h, w in sizes], A, pre_k, post_k),), dtype=torch.uint8, device="cuda")
-    ops.rpn_proposals(raw_dev, ldc, A, 0, A, geom, _dev(anc_all), _dev(im_info), [0, 0, 0, 0], [1, 1, 1, 1], pre_k, thr, post_k, rois, num, ws,
-                      joint_nms=not per_level)
-    gr, gn = rois.cpu().numpy(), num.cpu().numpy()
-    if per_level:            # ... and the joint form gives the same proposals bit for bit
-        rois0, num0 = torch.empty_like(rois), torch.empty_like(num)
-        ops.rpn_proposals(raw_dev, ldc, A, 0, A, geom, _dev(anc_all), _dev(im_info), [0, 0, 0, 0], [1, 1, 1, 1], pre_k, thr, post_k, rois0, num0, ws,
-                          joint_nms=True)
-        assert torch.equal(num, num0) and torch.equal(rois, rois0)
-    for n in range(N):
-        sc, of = [], []
-        o = 0
-        for (h, w) in sizes:
-            blk = raw[n, o:o + h * w]
-            sc.append(blk[:, :A].reshape(-1))
-            of.append(blk[:, A:5 * A].reshape(-1, 4))
-            o += h * w
-        ref_rois, _, _ = orc.rpn_proposals(sc, of, anchors, im_info[n, :2], pre_k, post_k, thr)
-        assert gn[n] == len(ref_rois)
-        # decode uses expf on the device and np.exp in the oracle: boxes within a few ulp, selection identical
-        np.testing.assert_allclose(gr[n, : gn[n]], ref_rois, rtol=1e-5, atol=1e-3)
-        assert np.all(gr[n, gn[n]:] == 0)
+    # RPN.NMS_THRESHOLD 0.7 (the default) with the identity coder; on the smaller problems also 0.5 and 0.9 under the two other coders
+    # (RPN_BOX_REG: std < 1 shrinks the decoded shifts, std 2 on dw doubles them)
+    combos = [(0.7, CODER_0)] + ([(0.5, CODER_A), (0.9, CODER_B)] if pre_k <= 700 else [])
+    for thr, (mean, std) in combos:
+        mean, std = list(mean), list(std)
+        ops.rpn_proposals(raw_dev, ldc, A, 0, A, geom, _dev(anc_all), _dev(im_info), mean, std, pre_k, thr, post_k, rois, num, ws,
+                          joint_nms=not per_level)
+        gr, gn = rois.cpu().numpy(), num.cpu().numpy()
+        if per_level:            # ... and the joint form gives the same proposals bit for bit
+            rois0, num0 = torch.empty_like(rois), torch.empty_like(num)
+            ops.rpn_proposals(raw_dev, ldc, A, 0, A, geom, _dev(anc_all), _dev(im_info), mean, std, pre_k, thr, post_k, rois0, num0, ws,
+                              joint_nms=True)
+            assert torch.equal(num, num0) and torch.equal(rois, rois0)
+        for n in range(N):
+            sc, of = [], []
+            o = 0
+            for (h, w) in sizes:
+                blk = raw[n, o:o + h * w]
+                sc.append(blk[:, :A].reshape(-1))
+                of.append(blk[:, A:5 * A].reshape(-1, 4))
+                o += h * w
+            ref_rois, _, _ = orc.rpn_proposals(sc, of, anchors, im_info[n, :2], pre_k, post_k, thr, mean, std)
+            assert gn[n] == len(ref_rois), (thr, n)
+            # decode uses expf on the device and np.exp in the oracle: boxes within a few ulp, selection identical
+            np.testing.assert_allclose(gr[n, : gn[n]], ref_rois, rtol=1e-5, atol=1e-3)
+            assert np.all(gr[n, gn[n]:] == 0)
 
 
 def test_rpn_targets_and_sampling():
@@ -253,10 +258,11 @@ def test_rpn_targets_and_sampling():
     nfg = torch.zeros((1,), dtype=torch.int32, device="cuda")
     nvalid = torch.zeros((1,), dtype=torch.int32, device="cuda")
     ws = torch.empty((N * Gmax,), dtype=torch.float32, device="cuda")
-    for num_total, num_pos in ((256, 128), (64, 8)):
-        ops.rpn_assign_encode(_dev(anchors), _dev(gt), _dev(num_gt), 0.3, 0.7, True, [0, 0, 0, 0], [1, 1, 1, 1], labels, match, offs, nfg, ws)
+    # (256, 64) and (64, 64): RPN.POSITIVE_ANCHOR_RATIO 0.25 and 1.0, under the non-identity coders (RPN_BOX_REG)
+    for num_total, num_pos, (mean, std) in ((256, 128, CODER_0), (64, 8, CODER_0), (256, 64, CODER_A), (64, 64, CODER_B)):
+        ops.rpn_assign_encode(_dev(anchors), _dev(gt), _dev(num_gt), 0.3, 0.7, True, list(mean), list(std), labels, match, offs, nfg, ws)
         ops.sample_labels(labels, _dev(kp), _dev(kn), num_pos, num_total, nvalid)
-        ref_l, ref_o = orc.rpn_ground_truth(anchors, gt, num_gt, kp, kn, (0.3, 0.7), (0, -1, 1), True, num_total, num_pos)
+        ref_l, ref_o = orc.rpn_ground_truth(anchors, gt, num_gt, kp, kn, (0.3, 0.7), (0, -1, 1), True, num_total, num_pos, mean, std)
         gl = labels.cpu().numpy()
         assert np.array_equal(gl, ref_l)
         assert int(nvalid.item()) == int((ref_l >= 0).sum())
@@ -331,19 +337,24 @@ def test_rcnn_sample_targets():
     kb = rng.random((N, key_ld), dtype=np.float32)
     kb = (np.round(kb * 256) / 256).astype(np.float32)             # force key ties
     std = [0.1, 0.1, 0.2, 0.2]
-    for num_samples, fg_ratio in ((512, 0.5), (64, 0.25)):
+    # RCNN.FG_THRESHOLD / BG_THRESHOLD_HIGH / BG_THRESHOLD_LOW 0.6 / 0.4 / 0.1: a gap between the bands and a floor under the background
+    # band; FG_RATIO 0 and 1 (num_fg_max = 0 and = num_samples); RCNN_BOX_REG with a non-zero mean and with four different stds
+    for num_samples, fg_ratio, (fg_t, bg_hi, bg_lo), (mean, std) in ((512, 0.5, (0.5, 0.5, 0.0), ((0, 0, 0, 0), std)),
+                                                                      (64, 0.25, (0.5, 0.5, 0.0), ((0, 0, 0, 0), std)),
+                                                                      (64, 0.0, (0.6, 0.4, 0.1), CODER_A), (64, 1.0, (0.6, 0.4, 0.1), CODER_B),
+                                                                      (512, 0.5, (0.6, 0.4, 0.1), CODER_A)):
         nfg = int(num_samples * fg_ratio)
         o_rois = torch.empty((N, num_samples, 4), dtype=torch.float32, device="cuda")
         o_lab = torch.empty((N, num_samples), dtype=torch.int32, device="cuda")
         o_tgt = torch.empty((N, num_samples, 4), dtype=torch.float32, device="cuda")
         o_cnt = torch.empty((N,), dtype=torch.int32, device="cuda")
         tot = torch.zeros((1,), dtype=torch.int32, device="cuda")
-        ops.rcnn_sample_targets(_dev(rois), _dev(num_rois), _dev(gt), _dev(num_gt), _dev(kf), _dev(kb), num_samples, nfg, 0.5, 0.5, 0.0,
-                                [0, 0, 0, 0], std, o_rois, o_lab, o_tgt, o_cnt, tot)
+        ops.rcnn_sample_targets(_dev(rois), _dev(num_rois), _dev(gt), _dev(num_gt), _dev(kf), _dev(kb), num_samples, nfg, fg_t, bg_hi, bg_lo,
+                                list(mean), list(std), o_rois, o_lab, o_tgt, o_cnt, tot)
         total = 0
         for n in range(N):
             rr, rl, rt = orc.rcnn_ground_truth(rois[n, : num_rois[n]], gt[n, : num_gt[n]], kf[n], kb[n], num_samples, fg_ratio,
-                                               0.5, 0.5, 0.0, (0, 0, 0, 0), std)
+                                               fg_t, bg_hi, bg_lo, mean, std)
             m = len(rl)
             total += m
             assert int(o_cnt[n].item()) == m
