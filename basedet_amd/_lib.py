@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 106              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip)
+ABI_VERSION = 107              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -33,6 +33,8 @@ class ConvDesc(C.Structure):
         # liveness maps of g (read) and dx (written), and the promise that dx holds +0 outside the dx map's last list (0 = none)
         ("gskip_gmap", C.c_void_p), ("gskip_gmap_bytes", C.c_size_t), ("gskip_dxmap", C.c_void_p), ("gskip_dxmap_bytes", C.c_size_t),
         ("gskip_dx_clean", C.c_int32),
+        # forward liveness map of the output (bd_fwd_live_maps) and the promise that y holds +0 outside the previous call's list (0 = dense)
+        ("fwd_map", C.c_void_p), ("fwd_map_bytes", C.c_size_t), ("fwd_clean", C.c_int32),
     ]
 
 
@@ -62,6 +64,8 @@ SIGNATURES = {
     "bd_conv2d_dgrad_gskip_bytes": (_Z, [_D]),
     "bd_conv2d_gskip_map_bytes": (_Z, [_D, _I]),
     "bd_gskip_map_scan": (_I, [_D, _I, _P, _P, _Z, _P]),
+    "bd_fwd_live_map_bytes": (_Z, [_D]),
+    "bd_fwd_live_maps": (_I, [_D, _P, _I, _I, C.POINTER(C.c_void_p), _Z, _I, _P]),
     "bd_conv2d_fwd_bits": (_I, [_D, _P, _P, _P, _P, _P, _P, _I, _P]),
     "bd_conv2d_fwd_ex": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "bd_conv2d_dgrad_ex": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),

@@ -181,6 +181,9 @@ static inline const char* bd_tune_env_str(const char*) { return nullptr; }
 // Liveness map of a gradient tensor (bd_conv_desc.gskip_gmap / gskip_dxmap; gskip.hip): int offsets of its parts, patch counts, size
 struct BdGskipMap { int p4, p8, m4, m8, live, list; size_t ints; };
 void bd_gskip_map_layout(const bd_conv_desc* d, int side, BdGskipMap* out);      // side 0: the map of g, 1: of dx
+// Forward liveness map of one tower activation (bd_conv_desc.fwd_map; gskip.hip): int offsets of its parts, patch count, size
+struct BdFwdMap { int p4, live, list; size_t ints; };
+void bd_fwd_map_layout(const bd_conv_desc* d, BdFwdMap* out);
 
 // blocks of a grid-stride launch over n work items: enough to cover them once, capped (the loop takes the rest)
 static inline int grid_for(long long n, int block = 256, int cap = 4096) {

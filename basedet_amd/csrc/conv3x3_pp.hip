@@ -72,6 +72,9 @@ struct PParams {
     int* sp_ohdr;
     const int* sp_olist;
     int sp_stride, sp_clean;
+    // FORWARD sparse instance (bd_conv_desc.fwd_map): ONE map serves both roles -- sp_ohdr == sp_hdr, and sp_oflip = 1 makes the list that is NOT
+    // current (the previous call's) the candidates of the sp_clean clearing
+    int sp_oflip;
 };
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
         int zt = p.total_patches;                              // candidates: every patch, or (sp_clean) the previous call's live list
         const int* plist = nullptr;
         if (p.sp_clean) {
-            const int oc = __builtin_amdgcn_readfirstlane(p.sp_ohdr[0]) & 1;
+            const int oc = (__builtin_amdgcn_readfirstlane(p.sp_ohdr[0]) & 1) ^ p.sp_oflip;
             const int pc = __builtin_amdgcn_readfirstlane(p.sp_ohdr[2 + oc]);
             zt = pc < 0 ? 0 : (pc < zt ? pc : zt);
             plist = p.sp_olist + oc * p.sp_stride;
@@ -197,7 +200,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
     int z_first = 0;                                           // SPARSE: the first workgroup without a tile (main_grid: none)
     const int* sp_list = p.sp_list;
     if constexpr (SPARSE) {
-        if (p.sp_ohdr && blockIdx.x == 0 && threadIdx.x == 0) p.sp_ohdr[1] = 0;
+        if (p.sp_ohdr && !p.sp_oflip && blockIdx.x == 0 && threadIdx.x == 0) p.sp_ohdr[1] = 0;
         // (one load through a selected pointer: the two-armed form does not compile -- "illegal VGPR to SGPR copy")
         const int cur = p.sp_hdr ? __builtin_amdgcn_readfirstlane(p.sp_hdr[0]) & 1 : 0;
         const int* cntp = p.sp_hdr ? p.sp_hdr + 2 + cur : p.sp_count;
@@ -786,6 +789,19 @@ bool bd_conv3x3_pp_maps_ok(const bd_conv_desc* d, int flags, const void* add, co
     return pp_sparse_epilogue(flags, add, dst);
 }
 
+// conv2d_fwd_impl's check of a call that carries a forward liveness map: the SPARSE forward instance must take it, or the map would not be
+// read (same shape conditions as pp_launch below)
+bool bd_conv3x3_pp_fwd_map_ok(const bd_conv_desc* d, int flags, const void* add) {
+    if (g_patch_pp < 2 || !(d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1)) return false;
+    if (d->Cin % 8 != 0 || d->Cout <= 128 || d->Cout % 8 != 0) return false;
+    if ((long long)d->N * d->in_pix_per_img * d->Cin * 2 >= 0x7fffffffll || (long long)d->N * d->out_pix_per_img >= 0x7fffffffll ||
+        (long long)d->Cin * 9 * d->Cout >= 0x7fffffffll) return false;
+    for (int s = 0; s < d->nseg; ++s)
+        if (d->Hi[s] != d->Ho[s] || d->Wi[s] != d->Wo[s]) return false;
+    if (bd_gskip_patches(d, PH, PW) >= (1 << 24) || bd_gskip_patches(d, PH, PW) < 1) return false;
+    return !add && !(flags & (BD_EPI_ADD_BEFORE | BD_EPI_ADD_AFTER | BD_EPI_MASK));
+}
+
 static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const void* w, const float* bias, const void* add,
                      const void* mask, void* dst, int flags, float* gn_part, hipStream_t stream) {
     PParams p{};
@@ -827,7 +843,9 @@ static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const voi
     // (overwrite, BD_EPI_MASK) or keep dx (in-place accumulate without a gate).  Any other epilogue walks every patch.
     const bool in_place = (flags & BD_EPI_ADD_BEFORE) && add && add == dst;
     const bool sparse = mode == 1 && d->gskip && !gn_part && pp_sparse_epilogue(flags, add, dst);
-    if (g_pp_tail_split && !sparse && !gn_part && p.n_tiles == 1 && px_tiles > num_cus) {          // (the tail body leaves no GroupNorm statistics)
+    // Forward skip (bd_conv_desc.fwd_map; conv2d_fwd_impl has checked the call): the tiles are cut from the map's current list
+    const bool fsparse = mode == 0 && d->fwd_map && !gn_part;
+    if (g_pp_tail_split && !sparse && !fsparse && !gn_part && p.n_tiles == 1 && px_tiles > num_cus) {          // (the tail body leaves no GroupNorm statistics)
         const int r = px_tiles % num_cus;
         if (r > 0 && r * (TILE_CO / TAIL_CO) <= num_cus) {
             px_tiles -= r;
@@ -855,6 +873,8 @@ static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const voi
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   LDS_BYTES));
     bd_note_kernel("conv3x3_pp_kernel");
     if (sparse) {
@@ -884,6 +904,17 @@ static int pp_launch(const bd_conv_desc* d, int mode, const void* src, const voi
         }
         hipLaunchKernelGGL((conv3x3_pp_kernel<1, false, true>), dim3(p.main_grid), dim3(512), LDS_BYTES, stream, p);
         if (d->gskip_dxmap) bd_gskip_fill(d, 1, dst, p.sp_live, (int*)d->gskip_dxmap, stream);
+    } else if (fsparse) {
+        // one launch: the dense plan's grid, the live tiles first, then the +0 stores (every dead patch, or with fwd_clean the dead patches of
+        // the previous list).  No dense fallback: a full list is the dense walk, minus the tail split.  The bias + ReLU epilogue and the per-tile arithmetic are the dense instance's: the same bits in the live patches
+        const int tot = p.total_patches;
+        BdFwdMap fm;
+        bd_fwd_map_layout(d, &fm);
+        int* m = (int*)d->fwd_map;
+        p.sp_hdr = m; p.sp_live = m + fm.live; p.sp_list = m + fm.list; p.sp_stride = tot;
+        p.sp_ohdr = m; p.sp_olist = m + fm.list; p.sp_oflip = 1;
+        p.sp_clean = d->fwd_clean ? 1 : 0;
+        hipLaunchKernelGGL((conv3x3_pp_kernel<0, false, true>), dim3(p.main_grid), dim3(512), LDS_BYTES, stream, p);
     } else if (gn_part) {
         BD_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pp_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         hipLaunchKernelGGL((conv3x3_pp_kernel<0, true>), dim3(p.main_grid), dim3(512), LDS_BYTES, stream, p);

@@ -458,6 +458,7 @@ BD_KNOB int g_bk32_s2 = 1;
 int bd_conv3x3_patch_launch(const bd_conv_desc* d, int mode, const void* src, const void* w, const float* bias,
                             const void* add, const void* mask, void* dst, int flags, hipStream_t stream);
 bool bd_conv3x3_pp_maps_ok(const bd_conv_desc* d, int flags, const void* add, const void* dst);
+bool bd_conv3x3_pp_fwd_map_ok(const bd_conv_desc* d, int flags, const void* add);
 
 // debug/measurement knob: bit 0 clear forces the generic per-tap kernel for 3x3 stride-1 convolutions; bit 1: BK=32 tiles for 1x1
 extern BD_KNOB int g_patch_dma;
@@ -534,6 +535,13 @@ static int conv2d_fwd_impl(const bd_conv_desc* d, const void* x, const void* w_p
     BD_REQUIRE(d->Cin % 8 == 0, "conv2d_fwd: Cin=%d must be a multiple of 8", d->Cin);
     BD_REQUIRE(d->Cout % 8 == 0, "conv2d_fwd: Cout=%d must be a multiple of 8", d->Cout);
     BD_REQUIRE(!(flags & BD_EPI_MASK), "conv2d_fwd: BD_EPI_MASK is a dgrad-only flag");
+    if (d->fwd_map || d->fwd_clean) {          // forward liveness map: only a call the sparse patch kernel takes may carry it
+        BD_REQUIRE(d->fwd_map && is_3x3s1(d) && g_use_patch3x3 && !ybits && !y8 && bd_conv3x3_pp_fwd_map_ok(d, flags, add),
+                   "conv2d_fwd: fwd_map needs a 3x3 / stride 1 / pad 1 descriptor into more than 128 channels without residual operand on the "
+                   "default route (fwd_clean needs fwd_map)");
+        BD_REQUIRE(d->fwd_map_bytes >= bd_fwd_live_map_bytes(d), "conv2d_fwd: fwd_map %zu < required %zu bytes", (size_t)d->fwd_map_bytes,
+                   bd_fwd_live_map_bytes(d));
+    }
     if (is_dense_1x1(d) &&
         bd_conv1x1_dense_launch(x, w_packed, bias, add, nullptr, nullptr, y, ybits, y8, q_scale, 0, (long long)d->N * d->out_pix_per_img,
                                 d->Cin, d->Cout, flags, (hipStream_t)stream) == 0) {

@@ -262,6 +262,114 @@ __global__ __launch_bounds__(1024) void gskip_fill_kernel(const GmParams p, cons
     if (tid == 0) { p.map[0] = nxt; p.map[1] = 0; }
 }
 
+// ---- forward liveness (bd_conv_desc.fwd_map; the sparse FORWARD instance of conv3x3_pp.hip) ----
+// A tower of n 3x3 layers whose last output is read only at the foreground pixels F of each image and level (a pixel with an anchor whose
+// label is > 0) needs the output of the layer k steps above that one only inside F dilated k times (each 3x3 layer reaches one pixel further;
+// the dilation stops at the borders of the image and level).  bd_fwd_live_maps builds, from the labels alone, one map per depth k = 1 .. depths:
+//   hdr[8]      [0] = which of the two lists is current (bit 0), [2], [3] = the lists' counts; [1] of the depth-1 map = finished-workgroup counter
+//   live[P4]    0 / 1 per 4 x 16 patch: the patch holds a pixel of F dilated k times
+//   list[2][P4] the live patches, ascending: the current list and the previous call's
+// fwd_live_kernel: one workgroup per (image, level) keeps the level's pixel bitmap (one byte per pixel, two buffers) in LDS, dilates it
+// pixel by pixel and writes the level's patch flags of every depth; the last workgroup to finish (device-scope counter, nobody waits)
+// compacts every depth's flags into the list that is not current and flips.
+enum { FL_HDR = 8, FL_MAX_DEPTH = 8 };
+
+struct FlSeg { int H, W, off, s4, pw; };
+
+struct FlParams {
+    const int* labels;
+    int* map[FL_MAX_DEPTH];
+    int A, ppi, nseg, depths, pi4, tot4;
+    FlSeg seg[BD_MAX_SEGS];
+};
+
+__global__ __launch_bounds__(1024) void fwd_live_kernel(const FlParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char fl_bm[];      // [2][H * W]
+    __shared__ int slast;
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x;
+    const int n = blockIdx.x / p.nseg, s = blockIdx.x - n * p.nseg;
+    const int H = p.seg[s].H, W = p.seg[s].W, HW = H * W, pwn = p.seg[s].pw;
+    const int npatch = ((H + 3) >> 2) * pwn;
+    unsigned char* cur = fl_bm;
+    unsigned char* nxt = fl_bm + HW;
+    for (int i = tid; i < HW; i += 1024) cur[i] = 0;
+    __syncthreads();
+    const int* lab = p.labels + ((long long)n * p.ppi + p.seg[s].off) * p.A;
+    for (int i = tid; i < HW * p.A; i += 1024)
+        if (lab[i] > 0) cur[i / p.A] = 1;                    // (several anchors of a pixel may store the same 1)
+    __syncthreads();
+    for (int k = 0; k < p.depths; ++k) {
+        for (int i = tid; i < HW; i += 1024) {
+            const int y = i / W, x = i - y * W;
+            const int y0 = y > 0 ? y - 1 : 0, y1 = y + 1 < H ? y + 1 : H - 1, x0 = x > 0 ? x - 1 : 0, x1 = x + 1 < W ? x + 1 : W - 1;
+            int v = 0;
+            for (int yy = y0; yy <= y1; ++yy)
+                for (int xx = x0; xx <= x1; ++xx) v |= cur[yy * W + xx];
+            nxt[i] = (unsigned char)v;
+        }
+        __syncthreads();
+        int* live = p.map[k] + FL_HDR + n * p.pi4 + p.seg[s].s4;
+        for (int q = tid; q < npatch; q += 1024) {
+            const int by = q / pwn, bx = q - by * pwn;
+            const int ye = by * 4 + 4 < H ? by * 4 + 4 : H, xe = bx * 16 + 16 < W ? bx * 16 + 16 : W;
+            int v = 0;
+            for (int y = by * 4; y < ye; ++y)
+                for (int x = bx * 16; x < xe; ++x) v |= nxt[y * W + x];
+            live[q] = v;
+        }
+        unsigned char* t = cur; cur = nxt; nxt = t;
+        __syncthreads();
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");       // every thread's flags are visible device-wide before the workgroup counts as finished
+    __syncthreads();
+    if (tid == 0) slast = atomicAdd(p.map[0] + 1, 1) == (int)gridDim.x - 1;
+    __syncthreads();
+    if (!slast) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    // compaction, one depth after the other: each thread takes KP consecutive patches (ascending order: prefix sums over lanes, then waves)
+    constexpr int KP = 8;
+    const int wv = tid >> 6, ln = tid & 63;
+    for (int k = 0; k < p.depths; ++k) {
+        int* hdr = p.map[k];
+        const int* live = hdr + FL_HDR;
+        const int to = (hdr[0] & 1) ^ 1;
+        int* list = hdr + FL_HDR + p.tot4 * (1 + to);
+        int base = 0;
+        for (int c0 = 0; c0 < p.tot4; c0 += 1024 * KP) {
+            int lv[KP];
+            int cnt = 0;
+#pragma unroll
+            for (int j = 0; j < KP; ++j) {
+                const int q = c0 + tid * KP + j;
+                lv[j] = q < p.tot4 ? (__hip_atomic_load(live + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) : 0;
+                cnt += lv[j];
+            }
+            int inc = cnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int y = __shfl_up(inc, o, 64);
+                if (ln >= o) inc += y;
+            }
+            if (ln == 63) wsum[wv] = inc;
+            __syncthreads();
+            int off = base + inc - cnt, tot = 0;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) {
+                off += w < wv ? wsum[w] : 0;
+                tot += wsum[w];
+            }
+#pragma unroll
+            for (int j = 0; j < KP; ++j)
+                if (lv[j]) list[off++] = c0 + tid * KP + j;
+            base += tot;
+            __syncthreads();
+        }
+        if (tid == 0) { hdr[2 + to] = base; hdr[0] = to; }
+    }
+    if (tid == 0) p.map[0][1] = 0;
+}
+
 // side 0: the geometry of g (the conv's output levels), side 1: of dx (its input levels)
 GsParams gs_params(const bd_conv_desc* d, int ph, int pw, int side = 0) {
     GsParams p{};
@@ -350,5 +458,55 @@ extern "C" int bd_gskip_map_scan(const bd_conv_desc* d, int of_dx, const void* t
     }
     hipLaunchKernelGGL(gskip_compact_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, p4, mp + m.live, mp + m.list, mp + 2);
     BD_CHECK_LAUNCH("bd_gskip_map_scan");
+    return BD_OK;
+}
+
+// ---- forward liveness: layout and launch (see fwd_live_kernel) ----
+void bd_fwd_map_layout(const bd_conv_desc* d, BdFwdMap* out) {
+    const int p4 = gs_params(d, 4, 16, 0).total;
+    out->p4 = p4; out->live = FL_HDR; out->list = FL_HDR + p4;
+    out->ints = (size_t)FL_HDR + (size_t)3 * p4;
+}
+
+extern "C" size_t bd_fwd_live_map_bytes(const bd_conv_desc* d) {
+    if (!d || d->nseg < 1 || d->nseg > BD_MAX_SEGS || !(d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1)) return 0;
+    BdFwdMap m;
+    bd_fwd_map_layout(d, &m);
+    return m.ints * sizeof(int);
+}
+
+extern "C" int bd_fwd_live_maps(const bd_conv_desc* d, const int32_t* labels, int A, int depths, void* const* maps, size_t map_bytes,
+                                int reset, bd_stream_t stream) {
+    BD_REQUIRE(d && labels && maps, "fwd_live_maps: null pointer");
+    const size_t need = bd_fwd_live_map_bytes(d);
+    BD_REQUIRE(need > 0, "fwd_live_maps: forward liveness maps belong to 3x3 / stride 1 / pad 1 descriptors");
+    BD_REQUIRE(A >= 1 && depths >= 1 && depths <= FL_MAX_DEPTH, "fwd_live_maps: A=%d depths=%d (1 .. %d)", A, depths, (int)FL_MAX_DEPTH);
+    BD_REQUIRE(map_bytes >= need, "fwd_live_maps: map %zu < required %zu bytes", map_bytes, need);
+    const GsParams g4 = gs_params(d, 4, 16, 0);
+    FlParams p{};
+    p.labels = labels; p.A = A; p.ppi = g4.ppi; p.nseg = g4.nseg; p.depths = depths; p.pi4 = g4.patches_per_img; p.tot4 = g4.total;
+    size_t lds = 0;
+    for (int s = 0; s < g4.nseg; ++s) {
+        BD_REQUIRE(d->Hi[s] == d->Ho[s] && d->Wi[s] == d->Wo[s], "fwd_live_maps: level %d changes size", s);
+        p.seg[s] = FlSeg{g4.seg[s].H, g4.seg[s].W, g4.seg[s].off, g4.seg[s].patch_start, g4.seg[s].pw};
+        const size_t b = (size_t)2 * g4.seg[s].H * g4.seg[s].W;
+        BD_REQUIRE((long long)g4.seg[s].H * g4.seg[s].W * A < 0x7fffffffll, "fwd_live_maps: level %d too large", s);
+        lds = b > lds ? b : lds;
+    }
+    BD_REQUIRE(lds <= 160 * 1024 - 256, "fwd_live_maps: a level of %zu pixels does not fit the LDS bitmap", lds / 2);
+    for (int k = 0; k < depths; ++k) {
+        BD_REQUIRE(maps[k], "fwd_live_maps: null map %d", k);
+        p.map[k] = (int*)maps[k];
+        // reset: the maps hold no usable state (new or re-bound memory) -- list 0 current and both lists empty before the launch
+        if (reset && hipMemsetAsync(maps[k], 0, FL_HDR * sizeof(int), (hipStream_t)stream) != hipSuccess) {
+            bd_set_error("fwd_live_maps: memset failed");
+            return BD_ELAUNCH;
+        }
+    }
+    if (d->N < 1 || g4.total < 1) return BD_OK;
+    BD_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_live_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 160 * 1024 - 256));
+    hipLaunchKernelGGL(fwd_live_kernel, dim3(d->N * g4.nseg), dim3(1024), lds, (hipStream_t)stream, p);
+    BD_CHECK_LAUNCH("bd_fwd_live_maps");
     return BD_OK;
 }

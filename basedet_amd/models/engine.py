@@ -64,6 +64,8 @@ class ConvLayer:
         # gradient writes, and the promise about that buffer's bytes (bd_conv_desc.gskip_gmap / gskip_dxmap / gskip_dx_clean)
         self._chain = (None, None, False)
         self._chain_cache = {}
+        # forward skip (MODEL.SPARSE_BOX_FWD): descriptors that carry a forward liveness map (bd_conv_desc.fwd_map / fwd_clean)
+        self._fwd_map_cache = {}
         # fp8 forward (BASELINE config 5, enable_fp8): e4m3 weights with one scale per output channel + the input cast to e4m3
         self.fp8 = False
         self.fp8_dgrad = False          # data gradient on the fp8 patch kernel too (e5m2 gradients under a static gradient scale)
@@ -214,10 +216,25 @@ class ConvLayer:
         the data gradient's output buffer still holds the layout the previous step left (see bd_conv_desc.gskip_dx_clean)."""
         self._chain = (gmap, dxmap, bool(dx_clean) and dxmap is not None) if self.gskip else (None, None, False)
 
-    def forward(self, x, gin, gout, y, add=None, relu=False, bits=None, x8=None, y8=None, q_scale=1.0):
+    def fwd_map_desc(self, gin: Geom, gout: Geom, fmap, clean):
+        """desc() with the forward liveness map of the output and the promise about the output buffer's bytes (ops.fwd_map_desc)."""
+        d = self.desc(gin, gout)
+        key = (id(d), fmap.data_ptr(), bool(clean))          # (keyed by the map's address: the plan arena re-bases it when it grows)
+        c = self._fwd_map_cache.get(key)
+        if c is None:
+            if len(self._fwd_map_cache) > 64:
+                self._fwd_map_cache.clear()
+            c = self._fwd_map_cache[key] = (ops.fwd_map_desc(d, fmap, clean), d)
+        return c[0]
+
+    def forward(self, x, gin, gout, y, add=None, relu=False, bits=None, x8=None, y8=None, q_scale=1.0, fwd_map=None, fwd_clean=False):
         """x8: the e4m3 twin of x when a producing fp8 launch wrote one (else x is cast by bd_quantize_fp8); y8: twin of y to write
-        for a following fp8 convolution.  Both are ignored on the bf16 path."""
+        for a following fp8 convolution.  Both are ignored on the bf16 path.  fwd_map: the forward liveness map of y (bf16 path only): only
+        the patches on its list are computed, the rest of y is +0 (fwd_clean: see bd_conv_desc.fwd_clean)."""
         flags = (ops.EPI_RELU if relu else 0) | (ops.EPI_ADD_BEFORE if add is not None else 0)
+        if fwd_map is not None:
+            assert not self.fp8 and not self.fp8_1x1 and bits is None and y8 is None
+            return ops.conv2d_fwd(self.fwd_map_desc(gin, gout, fwd_map, fwd_clean), x, self.w_fwd, self.b, y, add=add, flags=flags)
         if self.fp8_1x1 and x8 is not None and ops.conv1x1_fp8_ok(self.desc(gin, gout), 0):
             return ops.conv1x1_fp8(self.desc(gin, gout), 0, x8, self.w_q8, self.w_scale8, self.b, y, add=add, bits=bits, y8=y8,
                                    q_scale=q_scale, flags=flags)

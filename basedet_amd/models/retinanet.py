@@ -57,6 +57,14 @@ class RetinaNet(FPNDetector):
         # instead of being scanned out of every gradient again -- by its data gradient AND its weight gradient (bd_conv_desc.gskip_gmap /
         # gskip_dxmap).  Off: every launch scans for itself, as before the maps existed.
         self.sparse_chain = bool(m.get("SPARSE_BOX_CHAIN", True))
+        # MODEL.SPARSE_BOX_FWD (default on): the box tower's FORWARD convolutions compute only what the step reads.  The regression loss reads
+        # bbox_pred's output at the foreground anchors alone, so the tower activation k layers below it is needed only within k pixels of
+        # a foreground pixel -- by bbox_pred, by the ReLU gates and by the weight gradients of the sparse backward chain, whose gradients
+        # vanish outside the same neighbourhoods.  bd_fwd_live_maps builds those sets from the labels under the backbone's forward pass;
+        # the rest of every activation holds +0 (the same bits in losses, gradients and dL/dP).  Exactly this class (FreeAnchor's bag
+        # loss reads every anchor's offsets), with the sparse backward, bf16, training mode; bbox_pred itself stays dense.
+        self.sparse_box_fwd = (bool(m.get("SPARSE_BOX_FWD", True)) and type(self) is RetinaNet and nc >= 1 and nc <= 8
+                               and all(c.gskip for c in self.box_tower + [self.bbox_pred]))
         self._build_base_anchors()
 
     def _head_convs(self):
@@ -89,6 +97,17 @@ class RetinaNet(FPNDetector):
             if nb:
                 pl.g_map = [C.empty(((nb + 3) // 4,), torch.int32) for _ in range(nc)]
         pl.chain_epoch = None
+        # one forward liveness map per BOX tower activation (int32; the layout is the library's): box_act[i] is needed within nc - i pixels of
+        # the foreground.  fwd_epoch: the arena epoch at which the last forward on this plan left box_act in a map's layout (None: it did
+        # not) -- the promise of bd_conv_desc.fwd_clean stands under the same rule as the backward chain's
+        pl.f_map = None
+        if self.sparse_box_fwd:
+            nb = ops.fwd_live_map_bytes(self.box_tower[0].desc(pl.pyr, pl.pyr))
+            if nb:
+                pl.f_map = [C.empty(((nb + 3) // 4,), torch.int32) for _ in range(nc)]
+        pl.fwd_epoch = None
+        pl.fwd_skip = None          # (clean,) between get_losses' map launch and the head_forward that consumes it
+        pl.fwd_skipped = False      # the last head_forward on this plan skipped: box_act / offsets are not the dense tensors
         # fp8 forward: every tower activation gets an e4m3 twin, written by the launch that produces it (no cast passes in the head)
         tw = lambda: C.empty((pl.pyr.pixels, ch), torch.uint8)      # noqa: E731
         pl.cls_act8 = [tw() if c.fp8 else None for c in self.cls_tower]
@@ -119,10 +138,22 @@ class RetinaNet(FPNDetector):
         # of its own: see SideStreams.
         concurrent = bool(self.cfg.MODEL.get("HEAD_TOWERS_CONCURRENT", True)) and self.weight_dtype != "fp8_e4m3"
         side = self.streams.aux() if concurrent else None
+        # MODEL.SPARSE_BOX_FWD: get_losses left this step's liveness maps on the auxiliary stream; a box tower that runs on the main stream
+        # instead waits for them here
+        skip, pl.fwd_skip = pl.fwd_skip, None
+        if skip is not None and side is None:
+            join(self.streams.aux_stream)
+        if skip is None:
+            pl.fwd_epoch = None          # a dense forward: box_act is in no map's layout any more
+        pl.fwd_skipped = skip is not None
         with fork(side):
             t, t8 = pl.P, getattr(pl, "P8", None)
-            for c, a, a8 in zip(self.box_tower, pl.box_act, pl.box_act8):
-                c.forward(t, pl.pyr, pl.pyr, a, relu=True, x8=t8, y8=a8); t, t8 = a, a8
+            for i, (c, a, a8) in enumerate(zip(self.box_tower, pl.box_act, pl.box_act8)):
+                if skip is not None:
+                    c.forward(t, pl.pyr, pl.pyr, a, relu=True, fwd_map=pl.f_map[i], fwd_clean=skip[0])
+                else:
+                    c.forward(t, pl.pyr, pl.pyr, a, relu=True, x8=t8, y8=a8)
+                t, t8 = a, a8
             self.bbox_pred.forward(t, pl.pyr, pl.pyr, pl.offsets, x8=t8)
         t, t8 = pl.P, getattr(pl, "P8", None)
         for c, a, a8 in zip(self.cls_tower, pl.cls_act, pl.cls_act8):
@@ -148,6 +179,16 @@ class RetinaNet(FPNDetector):
         with fork(side):
             ops.retina_assign_encode(pl.anchors, gt, num_gt, thr[0], thr[1], m.MATCHER.ALLOW_LOW_QUALITY, m.BOX_REG.MEAN,
                                      m.BOX_REG.STD, pl.labels, pl.match_idx, pl.gt_offsets, pl.num_fg, ws)
+            if pl.f_map is not None and self.streams.aux() is not None:
+                # the box tower's forward liveness, right behind the assignment that wrote the labels: maps[k - 1] belongs to the activation
+                # k layers below bbox_pred.  The promise that box_act still holds the previous step's layout: as head_backward's.
+                # Only with the side streams on: a serial step (async_wgrad off: bench.py's instrumented steps, the per-element launch
+                # audits) keeps every launch dense -- whole output tensors and clean per-kernel durations, and no map launch in the
+                # main stream's way
+                clean = pl.fwd_epoch == self.plan_arena.epoch
+                pl.fwd_epoch = self.plan_arena.epoch
+                ops.fwd_live_maps(self.box_tower[0].desc(pl.pyr, pl.pyr), pl.labels, self.num_anchors, pl.f_map[::-1], reset=not clean)
+                pl.fwd_skip = (clean,)
         self.network_forward(pl)
         join(side)
         pl.loss_buf.zero_()
@@ -208,6 +249,16 @@ class RetinaNet(FPNDetector):
         pl.g_P8_ready = pl.g_P8 is not None and bool(wrote_p)
 
     def _debug_head(self, pl, out, lvl):
+        """The head's stored activations.  When the last forward skipped (MODEL.SPARSE_BOX_FWD), box_act and offsets hold +0 outside the
+        foreground's reach: the box tower and bbox_pred are first run again densely from pl.P into the same buffers -- WITH THE CURRENT
+        WEIGHTS (call this before an optimizer step to see the forward's own values) -- and the promise about box_act is withdrawn."""
+        if getattr(pl, "fwd_skipped", False):
+            t = pl.P
+            for c, a in zip(self.box_tower, pl.box_act):
+                c.forward(t, pl.pyr, pl.pyr, a, relu=True); t = a
+            self.bbox_pred.forward(t, pl.pyr, pl.pyr, pl.offsets)
+            pl.fwd_skipped = False
+            pl.fwd_epoch = None
         for i in range(pl.pyr.nlev):
             for k in range(len(self.cls_tower)):
                 out[f"cls{k}_{i}"] = lvl(pl.cls_act[k], i)

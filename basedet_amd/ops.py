@@ -165,6 +165,34 @@ def gskip_desc(d, scratch=None, gmap=None, dxmap=None, dx_clean=False):
     return h
 
 
+def fwd_live_map_bytes(d):
+    """Bytes of one forward liveness map (bd_conv_desc.fwd_map) of d's output geometry; 0 for a descriptor that is not 3x3 / stride 1 / pad 1."""
+    return int(L().bd_fwd_live_map_bytes(C.byref(d)))
+
+
+def fwd_live_maps(d, labels, A, maps, reset=False):
+    """The forward liveness maps of a tower below a predictor that is read only at foreground anchors (bd_fwd_live_maps): maps[k - 1] (int32
+    device tensors of fwd_live_map_bytes(d)) gets the 4 x 16 patches within k pixels of a pixel with a label > 0.  labels: int32 (N, pixels
+    per image * A), pyramid order.  reset: the maps hold no state of an earlier call."""
+    if labels.dtype != torch.int32 or labels.numel() != d.N * d.out_pix_per_img * A:
+        raise _lib.BasedetHipError(f"fwd_live_maps: labels must be int32 with N * pixels * A = {d.N * d.out_pix_per_img * A} entries")
+    nb = min(m.numel() * m.element_size() for m in maps)
+    arr = (C.c_void_p * len(maps))(*[ptr(m).value for m in maps])
+    check(L().bd_fwd_live_maps(C.byref(d), ptr(labels), int(A), len(maps), arr, nb, int(bool(reset)), stream_ptr()), "bd_fwd_live_maps")
+    return maps
+
+
+def fwd_map_desc(d, fmap, clean=False):
+    """A copy of descriptor d whose forward launch follows the liveness map fmap of its output (bd_conv_desc.fwd_map): the patches on the
+    map's current list get the dense launch's bits, every other patch +0.  clean: the promise that the output still holds +0 outside
+    the list of the previous call with this map (bd_conv_desc.fwd_clean)."""
+    h = ConvDesc.from_buffer_copy(d)
+    h.fwd_map = fmap.data_ptr()
+    h.fwd_map_bytes = fmap.numel() * fmap.element_size()
+    h.fwd_clean = int(bool(clean))
+    return h
+
+
 def quantize_fp8(x, scale, q):
     """q (uint8, same element count) = e4m3(clamp(x * scale)) of a bf16 tensor."""
     check(L().bd_quantize_fp8(ptr(x), x.numel(), float(scale), ptr(q), stream_ptr()), "bd_quantize_fp8")

@@ -110,6 +110,19 @@ typedef struct bd_conv_desc {
     void* gskip_dxmap;
     size_t gskip_dxmap_bytes;
     int32_t gskip_dx_clean;
+    /* Forward skip (bd_version() >= 107; 0 / NULL = off: every pixel is computed).  fwd_map = a forward liveness map that bd_fwd_live_maps
+     * completed on the call's stream (caller-owned device ints, bd_fwd_live_map_bytes; it BELONGS TO THE OUTPUT TENSOR y): bd_conv2d_fwd of a
+     * 3x3 / stride-1 / pad-1 descriptor into more than 128 channels, without residual operand, computes only the 4 x 16 patches of y on the
+     * map's current list -- the same bits there as the dense launch -- and leaves +0 in every other patch (a list of any length is followed:
+     * nothing is decided on the host).
+     *   fwd_clean    a caller PROMISE, default 0: outside the list the previous call with this map computed, y already holds +0 (same
+     *                buffer, same geometry, nothing else wrote it since, and the map was not reset in between).  The call then clears only
+     *                the patches that were computed then and are dead now instead of storing +0 into every dead patch.
+     * A call with a map that the descriptor / epilogue cannot honour returns BD_EINVAL (nothing is launched).  Data gradients, weight
+     * gradients and the fp8 entry points ignore these fields. */
+    void* fwd_map;
+    size_t fwd_map_bytes;
+    int32_t fwd_clean;
 } bd_conv_desc;
 
 const char* bd_last_error_string(void);
@@ -157,6 +170,18 @@ size_t bd_conv2d_gskip_map_bytes(const bd_conv_desc* d, int of_dx);
  * live list of the data gradient that reads it.  The start of a chain whose first gradient comes from a loss; the reference the
  * producer-written maps are tested against. */
 int bd_gskip_map_scan(const bd_conv_desc* d, int of_dx, const void* t, void* map, size_t map_bytes, bd_stream_t stream);
+/* Forward liveness (bd_version() >= 107).  Bytes of one forward liveness map (bd_conv_desc.fwd_map) of this descriptor's output geometry; 0 for
+ * a descriptor that is not 3x3 / stride 1 / pad 1. */
+size_t bd_fwd_live_map_bytes(const bd_conv_desc* d);
+/* The forward liveness maps of a tower of `depths` (1 .. 8) 3x3 layers below a predictor that is read only at foreground anchors, from the
+ * target assignment alone: labels int32 [N][pixels per image * A] in pyramid order (A anchors per pixel; foreground = label > 0).  maps is a
+ * HOST array of `depths` device pointers, map_bytes the size of each: maps[k - 1] gets the 4 x 16 patches that hold a foreground pixel dilated
+ * k times inside its image and level (what the output of the layer k below the predictor's is needed on), as flags and as an ascending list
+ * written into the map's non-current list, which then becomes current.  reset != 0: the maps hold no state of an earlier call (new memory,
+ * or memory something else wrote): their headers are cleared first -- the next bd_conv2d_fwd with such a map must not carry fwd_clean.
+ * One launch, no host synchronisation. */
+int bd_fwd_live_maps(const bd_conv_desc* d, const int32_t* labels, int A, int depths, void* const* maps, size_t map_bytes, int reset,
+                     bd_stream_t stream);
 
 /* Bit-packed ReLU masks for the HBM-bound 1x1 layers.  A forward launch with BD_EPI_RELU may also write ybits: one bit per output
  * element (y > 0), uint32 [Cout/32][M] (M = N * pixels of the level; word (g, m) holds channels 32g .. 32g+31 of pixel m, bit b =
