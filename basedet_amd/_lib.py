@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 107              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps)
+ABI_VERSION = 108              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -87,6 +87,9 @@ SIGNATURES = {
     "bd_stem_conv7x7_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
     "bd_stem_pool_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
     "bd_stem_weight_pack": (_I, [_P, _P, _P, _P]),
+    "bd_maxpool3x3s2_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "bd_stem_conv7x7_wgrad_workspace_bytes": (_Z, [_I, _I, _I]),
+    "bd_stem_conv7x7_wgrad": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "bd_weight_pack": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "bd_weight_pack_blocks": (_I, [_I, _I, _I]),
     "bd_weight_pack_multi": (_I, [_P, _I, _I, _P]),

@@ -39,6 +39,7 @@ SOURCES = {
     "conv_wgrad1x1_ring.hip": [],
     "fpn_deconv.hip": [],
     "stem.hip": [],
+    "stem_bwd.hip": [],
     "boxops.hip": ["-ffp-contract=off"],
     "nms.hip": ["-ffp-contract=off"],
     "rcnn_ops.hip": ["-ffp-contract=off"],

@@ -363,6 +363,34 @@ class FusedPredConv(ConvLayer):
             o += c
 
 
+class TrainableStem:
+    """backbone.bottom_up.conv1 under MODEL.BACKBONE.FREEZE_AT = 0: the 7x7 stem's fp32 master and gradient in the parameter arena, OHWI
+    [64][7][7][3] like every ConvLayer master (what bd_stem_weight_pack reads and bd_stem_conv7x7_wgrad writes); state_dict, checkpoints and
+    reference_grads see the reference's OIHW (64, 3, 7, 7).  The object WgradScheduler.run takes: the weight gradient runs on the side stream."""
+
+    name = "backbone.bottom_up.conv1"
+    fp8_wgrad = False
+
+    def reserve(self, arena):
+        self._wi = arena.reserve(self.name + ".weight", (64, 7, 7, 3))
+
+    def bind(self, arena, w_ohwi, row_scale):
+        self.w = arena.view("w", self._wi); self.gw = arena.view("g", self._wi)
+        self.w.copy_(w_ohwi)
+        self.row_scale = row_scale
+        return self.w
+
+    def export_grad(self, out):
+        out[self.name + ".weight"] = self.gw.permute(0, 3, 1, 2).contiguous().cpu()
+
+    def wgrad(self, x, g, gin, gout, ws, colsum_ws=None, x8=None, g8=None, queue=None):
+        """x: x_halo of the padded batch (gin: its N x Hp x Wp geometry), g: dL/d(pre-activation) of the stem output."""
+        ops.stem_conv7x7_wgrad(gin.N, gin.H[0], gin.W[0], x, g, self.gw, ws, row_scale=self.row_scale)
+
+    def wgrad_ws_bytes(self, gin, gout):
+        return ops.stem_conv7x7_wgrad_workspace_bytes(gin.N, gin.H[0], gin.W[0])
+
+
 def cls_ld(K):
     """Slots one anchor's class logits occupy: K rounded up to a multiple of 8 (16-byte rows of bf16)."""
     return (int(K) + 7) // 8 * 8

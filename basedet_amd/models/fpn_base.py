@@ -20,7 +20,7 @@ from ..data.raw import RawImageBatch
 from ..ops import Geom
 from ..streams import SideStreams, fork, join
 from . import params as P
-from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena
+from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena, TrainableStem
 from .fp8_scaling import Fp8GradScaler, initial_grad_scale
 from .plan_arena import PlanArena, _Carver, _Plan, _round_up
 from .wgrad_sched import WgradScheduler
@@ -58,6 +58,10 @@ class FPNDetector:
         norm = m.BACKBONE.get("NORM", "FrozenBN")
         if norm != "FrozenBN":
             raise ValueError(f"MODEL.BACKBONE.NORM = {norm!r} is not supported: only 'FrozenBN' is implemented")
+        fa = m.BACKBONE.FREEZE_AT
+        if not isinstance(fa, int) or isinstance(fa, bool) or fa < 0:
+            raise ValueError(f"MODEL.BACKBONE.FREEZE_AT = {fa!r} is not supported: an integer >= 0 (0 trains the stem, 1 freezes it, "
+                             ">= 2 freezes layer1 too)")
         fnorm = m.FPN.get("NORM", None)
         if fnorm is not None:
             raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} is not supported: only None (no FPN norm) is implemented")
@@ -134,8 +138,11 @@ class FPNDetector:
             self.convs[name] = c
             return c
 
-        # stem (frozen when FREEZE_AT >= 1; the dedicated 7x7 kernel is forward-only)
-        assert self.freeze_at >= 1, "the 7x7 stem kernel is forward-only: FREEZE_AT must be >= 1 (reference default 2)"
+        # stem: frozen when FREEZE_AT >= 1 (solver/default_solver.py:83-94); at 0 its master weight and gradient live in the arena
+        # (first: the arena follows the forward order) and the backward pass ends with the kernels of csrc/stem_bwd.hip
+        self.stem = TrainableStem() if self.freeze_at < 1 else None
+        if self.stem is not None:
+            self.stem.reserve(self.arena)
         self.stem_packed = torch.empty((64, 7, 8, 4), dtype=torch.bfloat16, device=dev)
 
         for blk in self.blocks:
@@ -177,7 +184,8 @@ class FPNDetector:
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.reserve(self.arena)
         self.arena.allocate()
-        self.fuse_stem_pool = bool(m.get("FUSE_STEM_POOL", True))
+        # (a trainable stem needs its half-resolution output in the backward pass: FREEZE_AT = 0 always runs the two launches)
+        self.fuse_stem_pool = bool(m.get("FUSE_STEM_POOL", True)) and self.stem is None
         # frozen bottleneck blocks (layer1 under FREEZE_AT = 2) in one launch each: the two mid tensors and the residual re-read never
         # reach HBM (bd_bottleneck_fwd; False: the three / four bd_conv2d_fwd launches, kept as the parity reference)
         self.fuse_frozen_blocks = bool(m.get("FUSE_FROZEN_BLOCKS", True))
@@ -273,7 +281,9 @@ class FPNDetector:
         sc = g / np.sqrt(var + 1e-5)
         self.stem_scale = torch.from_numpy(sc.astype(np.float32)).to(dev)
         self.stem_shift = torch.from_numpy((b - mu * sc).astype(np.float32)).to(dev)
-        self._pack_table = None                 # row_scale tensors are re-created by bind()
+        if self.stem is not None:
+            self.stem_w = self.stem.bind(self.arena, self.stem_w, self.stem_scale)
+        self._pack_table = None                # row_scale tensors are re-created by bind()
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.bind(self.arena, params)
         self._bn_params = {k: np.asarray(v, np.float32).copy() for k, v in params.items() if (".bn" in k or "downsample.1" in k)}
@@ -307,7 +317,9 @@ class FPNDetector:
                    if c.trainable and not isinstance(c, DeconvLayer)]
             self._pack_table = ops.build_pack_table(ent, self.device)
         ops.weight_pack_multi(self._pack_table)
-        for c in self.upsample.values():         # phase-major operands of their own (bd_fpn_deconv_pack)
+        if self.stem is not None:                # the 7 x 8 x 4 layout of the stem kernels (bd_stem_weight_pack)
+            ops.stem_weight_pack(self.stem_w, self.stem_scale, self.stem_packed)
+        for c in self.upsample.values():        # phase-major operands of their own (bd_fpn_deconv_pack)
             c.pack()
         for c in self.convs.values():
             if (c.fp8 or c.fp8_1x1 or c.fp8_1x1_dgrad) and c.trainable:
@@ -355,7 +367,8 @@ class FPNDetector:
             v = v.reshape(N, g.H[i], g.W[i], -1).permute(0, 3, 1, 2).contiguous()
             return v if c is None else v[:, :c].contiguous()
 
-        out["pool"] = nchw(pl.pool_out, pl.g_pool)
+        if self.stem is None:       # (a trainable stem: the oracle must differentiate through its own stem and max-pool, not a constant)
+            out["pool"] = nchw(pl.pool_out, pl.g_pool)
         for blk, b in zip(self.blocks, pl.blk):
             pre = blk["prefix"]
             for i, (t, g) in enumerate(zip(b.mids, b.mid_geo)):
@@ -374,6 +387,8 @@ class FPNDetector:
         """Gradients of the last backward() keyed by the reference's parameter names, in the reference's layouts
         (conv weights OIHW, padding rows dropped) -- what megengine's GradManager would hand to the optimizer."""
         out = {}
+        if self.stem is not None:
+            self.stem.export_grad(out)
         for c in self.convs.values():
             if not c.trainable:
                 continue
@@ -387,7 +402,7 @@ class FPNDetector:
         return list(self.reference_grads_names())
 
     def reference_grads_names(self):
-        names = []
+        names = [self.stem.name + ".weight"] if self.stem is not None else []
         for c in self.convs.values():
             if not c.trainable:
                 continue
@@ -427,6 +442,9 @@ class FPNDetector:
         pl.g_stem, pl.g_pool = g2, g4
         # the fused stem + max-pool launch never materialises the half-resolution stem output (MODEL.FUSE_STEM_POOL False: two launches)
         pl.stem_out, pl.pool_out = (None if self.fuse_stem_pool else act(g2, 64)), act(g4, 64)
+        if self.stem is not None:   # FREEZE_AT = 0: dL/d(pool_out) from layer1's first block, dL/d(pre-activation) of stem_out
+            pl.grad_pool, pl.grad_stem = C.like(pl.pool_out), C.like(pl.stem_out)
+            pl.g_image = ops.single(N, Hp, Wp)
         # backbone
         pl.blk = []
         gin = g4
@@ -514,7 +532,7 @@ class FPNDetector:
         pl.g_p6r = ops.single(N, h6, w6)
         self._plan_head(pl)
         # workspaces
-        need = 0
+        need = self.stem.wgrad_ws_bytes(pl.g_image, pl.g_stem) if self.stem is not None else 0
         for blk, b in zip(self.blocks, pl.blk):
             if not blk["trainable"]:
                 continue
@@ -663,7 +681,10 @@ class FPNDetector:
 
     def network_forward(self, pl):
         """RetinaNet.network_forward (retinanet.py:109-118): backbone + FPN + head; logits/offsets come out already
-        in the (N, sum HWA, K) layout of permute_to_N_Any_K + concat (function.py:26-32, retinanet.py:127-132)."""
+        in the (N, sum HWA, K) layout of permute_to_N_Any_K + concat (function.py:26-32, retinanet.py:127-132).
+
+        The stem runs as one launch (bd_stem_pool_fwd, MODEL.FUSE_STEM_POOL) while it is frozen.  Under MODEL.BACKBONE.FREEZE_AT = 0 the
+        key is ignored: the backward pass reads the half-resolution stem output, so the two-launch form always runs."""
         N = pl.N
         if self.fuse_stem_pool:
             ops.stem_pool_fwd(N, pl.Hp, pl.Wp, pl.x_halo, self.stem_packed, self.stem_shift, pl.pool_out)
@@ -935,10 +956,25 @@ class FPNDetector:
                         # identity skip: gx = (dgrad + G) * mask
                         wrote = convs[0].dgrad(g, geos[0], geos[1], gx, add_before=G, **kw)
                 pb.g_out8_ready = gx8 is not None and bool(wrote)     # what the launch actually did (a bf16 fallback drops the twin)
+            elif bi == 0 and self.stem is not None:
+                # dL/d(pool_out): the same residual fan-in, without a gate -- pool_out is a max-pool output, the stem's ReLU gate is
+                # applied by bd_maxpool3x3s2_bwd below
+                if blk["ds"] is not None:
+                    blk["ds"].dgrad(G, b.gin, b.gout, pl.grad_pool, first=True)
+                    convs[0].dgrad(g, geos[0], geos[1], pl.grad_pool, first=False)
+                else:                    # BasicBlock, identity shortcut
+                    convs[0].dgrad(g, geos[0], geos[1], pl.grad_pool, add_before=G)
             if bi == 0 or self.blocks[bi - 1]["layer"] != blk["layer"]:
                 self._flush_wgrads()
                 if on_bucket_ready:
                     on_bucket_ready(f"layer{blk['layer']}", side)
+        if self.stem is not None:       # FREEZE_AT = 0 (csrc/stem_bwd.hip): through the max-pool and the stem's ReLU, then conv1's weight gradient
+            gs = pl.g_stem
+            ops.maxpool3x3s2_bwd(pl.grad_pool, pl.stem_out, pl.pool_out, pl.N, gs.H[0], gs.W[0], 64, pl.grad_stem)
+            self._wgrad(self.stem, pl.x_halo, pl.grad_stem, pl.g_image, gs, ws)
+            self._flush_wgrads()
+            if on_bucket_ready:
+                on_bucket_ready("conv1", side)
         self._join_wgrads()
         self.fp8_scaler.end_step(probing)
 

@@ -334,6 +334,23 @@ def stem_weight_pack(w, row_scale, w_stem):
     check(L().bd_stem_weight_pack(ptr(w), ptr(row_scale), ptr(w_stem), stream_ptr()), "bd_stem_weight_pack")
 
 
+def maxpool3x3s2_bwd(g_pool, stem_out, pool_out, N, Hs, Ws, Cn, g_stem):
+    """Adjoint of maxpool3x3s2_fwd, gated by stem_out > 0 (first-maximum rule, no atomics): g_stem = dL/d(pre-activation) of stem_out."""
+    check(L().bd_maxpool3x3s2_bwd(ptr(g_pool), ptr(stem_out), ptr(pool_out), N, Hs, Ws, Cn, ptr(g_stem), stream_ptr()), "bd_maxpool3x3s2_bwd")
+    return g_stem
+
+
+def stem_conv7x7_wgrad_workspace_bytes(N, H, W):
+    return int(L().bd_stem_conv7x7_wgrad_workspace_bytes(N, H, W))
+
+
+def stem_conv7x7_wgrad(N, H, W, x_halo, g_stem, dw, ws, row_scale=None, accumulate=False):
+    """Weight gradient of stem_conv7x7_fwd; dw fp32 [64][7][7][3] (OHWI, what stem_weight_pack reads)."""
+    check(L().bd_stem_conv7x7_wgrad(N, H, W, ptr(x_halo), ptr(g_stem), ptr(row_scale), ptr(dw), int(accumulate), ptr(ws),
+                                    ws.numel() * ws.element_size(), stream_ptr()), "bd_stem_conv7x7_wgrad")
+    return dw
+
+
 def weight_pack(w, row_scale, w_fwd, w_dgrad, Cout, RS, Cin):
     check(L().bd_weight_pack(ptr(w), ptr(row_scale), ptr(w_fwd), ptr(w_dgrad), Cout, RS, Cin, stream_ptr()), "bd_weight_pack")
 

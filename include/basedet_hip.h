@@ -264,6 +264,21 @@ int bd_stem_pool_fwd(int N, int H, int W, const void* x_halo, const void* w_stem
 int bd_stem_weight_pack(const float* w /*[64][7][7][3] fp32*/, const float* row_scale, void* w_stem,
                         bd_stream_t stream);
 
+/* Backward of the stem for MODEL.BACKBONE.FREEZE_AT = 0 (bd_version() >= 108; stem_bwd.hip).
+ * bd_maxpool3x3s2_bwd: adjoint of bd_maxpool3x3s2_fwd with the ReLU gate of the tensor that was pooled folded in.  g_pool, pool_out: bf16
+ * NHWC [N][(Hs-1)/2+1][(Ws-1)/2+1][C]; stem_out (post-ReLU), g_stem: bf16 NHWC [N][Hs][Ws][C], C % 8 == 0.  A pixel takes a window's
+ * gradient iff it is the window's FIRST maximum in row-major order (padding never wins); the taken gradients are summed in fp32 in
+ * row-major window order, gated by stem_out > 0 and rounded once.  No atomics: the same bits on every run. */
+int bd_maxpool3x3s2_bwd(const void* g_pool, const void* stem_out, const void* pool_out, int N, int Hs, int Ws, int C, void* g_stem,
+                        bd_stream_t stream);
+/* Weight gradient of bd_stem_conv7x7_fwd: dw fp32 [64][7][7][3] (the layout bd_stem_weight_pack reads) = (accumulate ? dw : 0) +
+ * row_scale[o] * sum_{n,y,x} g_stem[n][y][x][o] * x_halo[n][2y+ky][2x+1+kx][c]; g_stem bf16 NHWC [N][H/2][W/2][64], x_halo as the
+ * forward reads it; row_scale (the folded FrozenBN scale) may be NULL.  bf16 MFMA, fp32 accumulation; K is split over workgroups and the
+ * partial sums (ws, caller-owned, bd_stem_conv7x7_wgrad_workspace_bytes) are combined in a fixed order: the same bits on every run. */
+size_t bd_stem_conv7x7_wgrad_workspace_bytes(int N, int H, int W);
+int bd_stem_conv7x7_wgrad(int N, int H, int W, const void* x_halo, const void* g_stem, const float* row_scale, float* dw, int accumulate,
+                          void* ws, size_t ws_bytes, bd_stream_t stream);
+
 /* fp32 master [Cout][R*S][Cin] (* row_scale[Cout] if non-NULL) -> bf16 fwd layout [Cout][RS][Cin] and
  * bf16 dgrad layout [Cin][RS][Cout] (either output may be NULL). */
 int bd_weight_pack(const float* w, const float* row_scale, void* w_fwd, void* w_dgrad, int Cout, int RS,
