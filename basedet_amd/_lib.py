@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 108              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip)
+ABI_VERSION = 109              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -144,6 +144,11 @@ SIGNATURES = {
     "bd_conv2d_fwd_gnstats": (_I, [_D, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_groupnorm_fwd_parts": (_I, [_D, _P, _P, _P, _P, _F, _I, _P, _P, _P]),
     "bd_groupnorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _L, _I, _I, _P, _P, _P, _I, _P, _Z, _P]),
+    "bd_bn_workspace_bytes": (_Z, [_L, _I]),
+    "bd_bn_stats_fwd": (_I, [_P, _I, _L, _L, _L, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "bd_bn_apply_fwd": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _I, _L, _I, _P]),
+    "bd_bn_bwd_reduce": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _I, _L, _I, _P, _P, _P, _Z, _P]),
+    "bd_bn_bwd_apply": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _I, _P]),
     "bd_fcos_offsets_fwd": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _L, _P, _P]),
     "bd_fcos_offsets_workspace_bytes": (_Z, []),
     "bd_fcos_offsets_bwd": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _Z, _P]),

@@ -49,6 +49,8 @@ SOURCES = {
     "ota.hip": ["-ffp-contract=off"],
     "losses.hip": [],
     "norm.hip": [],
+    # IEEE division and square root for the statistics (inv_std of a constant channel is 1 / sqrt(eps) to the last bit)
+    "batchnorm.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"],
     "comm.hip": [],
     "layer_ops.hip": ["-ffp-contract=off"],
     "probe.hip": [],

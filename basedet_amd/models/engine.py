@@ -45,8 +45,9 @@ class ConvLayer:
     bf16 packed copies for the forward ([Cout][RS][Cin], BN scale folded in) and dgrad ([Cin][RS][Cout]) kernels."""
 
     def __init__(self, name, cin, cout, k, stride, pad, device, bn_prefix=None, has_bias=False, trainable=True,
-                 cout_pad=None):
+                 cout_pad=None, norm=None):
         self.name, self.cin, self.cout_real, self.k, self.stride, self.pad = name, cin, cout, k, stride, pad
+        self.norm = norm                      # BatchNormState of a normalised FPN convolution (MODEL.FPN.NORM): its slots follow the weight's
         self.cout = cout_pad or cout          # padded channel count seen by the kernels (bbox_pred: 36 -> 40)
         self.bn_prefix, self.has_bias, self.trainable = bn_prefix, has_bias, trainable
         self.device = device
@@ -106,6 +107,8 @@ class ConvLayer:
                 self.b.copy_(b)
             else:
                 self.b = b.to(self.device)
+        if self.norm is not None:
+            self.norm.bind(arena, params)
 
     def reserve(self, arena):
         if not self.trainable:
@@ -113,17 +116,23 @@ class ConvLayer:
         self._wi = arena.reserve(self.name + ".weight", (self.cout, self.k, self.k, self.cin))
         if self.has_bias:
             self._bi = arena.reserve(self.name + ".bias", (self.cout,))
+        if self.norm is not None:
+            self.norm.reserve(arena)
 
     def export(self, out):
         """Back to the reference layout (OIHW numpy)."""
         out[self.name + ".weight"] = self.w[: self.cout_real].permute(0, 3, 1, 2).contiguous().cpu().numpy()
         if self.has_bias and not self.bn_prefix:
             out[self.name + ".bias"] = self.b[: self.cout_real].cpu().numpy().copy()
+        if self.norm is not None:
+            self.norm.export(out)
 
     def export_grad(self, out):
         out[self.name + ".weight"] = self.gw[: self.cout_real].permute(0, 3, 1, 2).contiguous().cpu()
         if self.gb is not None:
             out[self.name + ".bias"] = self.gb[: self.cout_real].cpu().clone()
+        if self.norm is not None:
+            self.norm.export_grad(out)
 
     def enable_fp8(self, q8_scratch, act_scale=1.0, dgrad=False, grad_scale=4096.0, wgrad=False):
         """Forward through bd_conv2d_fwd_fp8 (csrc/conv3x3_pp8.hip / conv_fp8.hip); with dgrad=True the data gradient through
@@ -332,6 +341,50 @@ class ConvLayer:
         d = self.bwd_desc(gin, gout)
         n = ops.conv2d_wgrad_bias_workspace_bytes(d) if self.gb is not None else ops.conv2d_wgrad_workspace_bytes(d)
         return max(n, ops.conv2d_wgrad_fp8_workspace_bytes(d)) if self.fp8_wgrad else n
+
+
+class BatchNormState:
+    """The norm record of one normalised FPN convolution (MODEL.FPN.NORM = "BN" / "SyncBN"; layers.get_norm at fpn_backbone.py:49-76):
+    gamma / beta are trainable fp32 vectors in the parameter arena, right behind the convolution's weight (`<conv>.norm.weight` / `.bias`);
+    the running statistics are buffers (`.running_mean` / `.running_var`); mean / inv_std / sums are the batch statistics of the last
+    training forward (sums = [M, sum y, sum y^2]; the backward pass reads the count M).  The buffers are rows of model-level tensors, so
+    that every norm's vectors of one kind are contiguous (one broadcast)."""
+
+    EPS, MOMENTUM = 1e-5, 0.1      # MegEngine's BatchNorm2d defaults (momentum 0.9 in its convention = 0.1 in torch's); documented choice
+
+    def __init__(self, name, C, running, stats, sums):
+        self.name, self.C = name, C
+        self.running_mean, self.running_var = running[0], running[1]
+        self.mean, self.inv_std = stats[0], stats[1]
+        self.sums = sums
+        self.gamma = self.beta = self.g_gamma = self.g_beta = None
+        self.fold_scale = torch.empty(C, dtype=torch.float32, device=running.device)      # eval(): the affine the convolution's epilogue applies
+        self.fold_shift = torch.empty(C, dtype=torch.float32, device=running.device)
+
+    def reserve(self, arena):
+        self._gi = arena.reserve(self.name + ".weight", (self.C,))
+        self._bi = arena.reserve(self.name + ".bias", (self.C,))
+
+    def bind(self, arena, params):
+        self.gamma, self.g_gamma = arena.view("w", self._gi), arena.view("g", self._gi)
+        self.beta, self.g_beta = arena.view("w", self._bi), arena.view("g", self._bi)
+        for t, k in ((self.gamma, "weight"), (self.beta, "bias"), (self.running_mean, "running_mean"), (self.running_var, "running_var")):
+            t.copy_(torch.from_numpy(np.asarray(params[f"{self.name}.{k}"], np.float32).reshape(-1)))
+
+    def export(self, out):
+        for t, k in ((self.gamma, "weight"), (self.beta, "bias"), (self.running_mean, "running_mean"), (self.running_var, "running_var")):
+            out[f"{self.name}.{k}"] = t.cpu().numpy().copy()
+
+    def export_grad(self, out):
+        out[self.name + ".weight"] = self.g_gamma.detach().cpu().clone()
+        out[self.name + ".bias"] = self.g_beta.detach().cpu().clone()
+
+    def fold(self):
+        """fold_scale / fold_shift from the running statistics, on the host like FrozenBN's (ConvLayer.bind): evaluation only."""
+        g, b = self.gamma.cpu().numpy(), self.beta.cpu().numpy()
+        scale = g / np.sqrt(self.running_var.cpu().numpy() + np.float32(self.EPS))
+        self.fold_scale.copy_(torch.from_numpy(scale.astype(np.float32)))
+        self.fold_shift.copy_(torch.from_numpy((b - self.running_mean.cpu().numpy() * scale).astype(np.float32)))
 
 
 class FusedPredConv(ConvLayer):

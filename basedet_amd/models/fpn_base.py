@@ -20,7 +20,8 @@ from ..data.raw import RawImageBatch
 from ..ops import Geom
 from ..streams import SideStreams, fork, join
 from . import params as P
-from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena, TrainableStem
+from .. import comm as _comm
+from .engine import BatchNormState, ConvLayer, DeconvLayer, FCLayer, ParamArena, TrainableStem
 from .fp8_scaling import Fp8GradScaler, initial_grad_scale
 from .plan_arena import PlanArena, _Carver, _Plan, _round_up
 from .wgrad_sched import WgradScheduler
@@ -63,8 +64,15 @@ class FPNDetector:
             raise ValueError(f"MODEL.BACKBONE.FREEZE_AT = {fa!r} is not supported: an integer >= 0 (0 trains the stem, 1 freezes it, "
                              ">= 2 freezes layer1 too)")
         fnorm = m.FPN.get("NORM", None)
-        if fnorm is not None:
-            raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} is not supported: only None (no FPN norm) is implemented")
+        if fnorm not in (None, "BN", "SyncBN"):
+            raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} is not supported: None (no FPN norm), 'BN' and 'SyncBN' are implemented")
+        if fnorm == "SyncBN" and _comm.world_size() > 1:
+            raise ValueError(f"MODEL.FPN.NORM = 'SyncBN' at world size {_comm.world_size()} is not supported: the exchange of the batch "
+                             "statistics between the ranks is not built; 'SyncBN' runs at world size 1 (as 'BN'), 'BN' at any world size "
+                             "(statistics of the rank's own batch)")
+        if fnorm is not None and m.get("WEIGHT_DTYPE", "bf16") != "bf16":
+            raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} with MODEL.WEIGHT_DTYPE = {m.WEIGHT_DTYPE!r} is not supported: the fp8 twins of the "
+                             "normalised FPN tensors are not built; use 'bf16'")
         if cls.READS_FPN_UPSAMPLE:
             up = m.FPN.get("UPSAMPLE", "resize")
             if up not in ("resize", "deconv"):
@@ -133,8 +141,8 @@ class FPNDetector:
         self.blocks = P.resnet_conv_table(m.BACKBONE.NAME)
         self.convs = {}
 
-        def add(name, cin, cout, k, stride, pad, bn=None, bias=False, trainable=True, cout_pad=None):
-            c = ConvLayer(name, cin, cout, k, stride, pad, dev, bn_prefix=bn, has_bias=bias, trainable=trainable, cout_pad=cout_pad)
+        def add(name, cin, cout, k, stride, pad, bn=None, bias=False, trainable=True, cout_pad=None, norm=None):
+            c = ConvLayer(name, cin, cout, k, stride, pad, dev, bn_prefix=bn, has_bias=bias, trainable=trainable, cout_pad=cout_pad, norm=norm)
             self.convs[name] = c
             return c
 
@@ -166,9 +174,24 @@ class FPNDetector:
         self.fpn_stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES]          # [3, 4, 5]
         ch = self.fpn_ch
         self.lateral, self.output = {}, {}
+        # MODEL.FPN.NORM = "BN" / "SyncBN" (fpn_backbone.py:49-76): biasless lateral / output convolutions, each followed by a BatchNorm2d.
+        # Norm i of fpn_norms is lateral i (i < number of stages) or output i - stages: the model-level buffers keep every kind contiguous
+        self.fpn_norm = m.FPN.get("NORM", None)
+        self.fpn_norms = []
+        nrm = {}
+        if self.fpn_norm is not None:
+            nn_ = 2 * len(self.fpn_stages)
+            f32 = dict(dtype=torch.float32, device=dev)
+            self.bn_running, self.bn_stats = torch.zeros((nn_, 2, ch), **f32), torch.zeros((nn_, 2, ch), **f32)
+            self.bn_sums = torch.zeros((nn_, 3, ch), **f32)
+            for kind in ("lateral", "output"):
+                for s in self.fpn_stages:
+                    i = len(self.fpn_norms)
+                    nrm[kind, s] = BatchNormState(f"backbone.fpn_{kind}{s}.norm", ch, self.bn_running[i], self.bn_stats[i], self.bn_sums[i])
+                    self.fpn_norms.append(nrm[kind, s])
         for s, ci in zip(self.fpn_stages, m.BACKBONE.OUT_FEATURE_CHANNELS):
-            self.lateral[s] = add(f"backbone.fpn_lateral{s}", ci, ch, 1, 1, 0, bias=True)
-            self.output[s] = add(f"backbone.fpn_output{s}", ch, ch, 3, 1, 1, bias=True)
+            self.lateral[s] = add(f"backbone.fpn_lateral{s}", ci, ch, 1, 1, 0, bias=self.fpn_norm is None, norm=nrm.get(("lateral", s)))
+            self.output[s] = add(f"backbone.fpn_output{s}", ch, ch, 3, 1, 1, bias=self.fpn_norm is None, norm=nrm.get(("output", s)))
         # MODEL.FPN.UPSAMPLE = "deconv": a learned 2x upsampling per merge, named after the coarse stage it reads (fpn_backbone.py:92-103)
         self.fpn_deconv = self.READS_FPN_UPSAMPLE and m.FPN.get("UPSAMPLE", "resize") == "deconv"
         self.upsample = {}
@@ -286,6 +309,7 @@ class FPNDetector:
         self._pack_table = None                # row_scale tensors are re-created by bind()
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.bind(self.arena, params)
+        self._fold_fpn_norms()
         self._bn_params = {k: np.asarray(v, np.float32).copy() for k, v in params.items() if (".bn" in k or "downsample.1" in k)}
         self.repack_weights()
 
@@ -324,11 +348,35 @@ class FPNDetector:
         for c in self.convs.values():
             if (c.fp8 or c.fp8_1x1 or c.fp8_1x1_dgrad) and c.trainable:
                 c.pack_fp8()
+        if self.fpn_norms and not self.training:       # evaluating (ModelEMA.applied() swaps the weights in): the folded affine follows gamma / beta
+            self._fold_fpn_norms()
+
+    def _fold_fpn_norms(self):
+        """Training: the normalised convolutions run bare (no bias, no scale; the batch-norm kernels follow).  Evaluation: the running
+        statistics and gamma / beta become the per-channel affine of the convolution's own launch, as FrozenBN's (scale folded into the
+        packed weight, shift = its bias) -- inference launches no batch-norm kernel."""
+        if not self.fpn_norms:
+            return
+        for c in list(self.lateral.values()) + list(self.output.values()):
+            if self.training:
+                c.row_scale = c.b = None
+            else:
+                c.norm.fold()
+                c.row_scale, c.b = c.norm.fold_scale, c.norm.fold_shift
+            c.pack()
+        self._pack_table = None                # (it holds the row_scale pointers)
 
     # reference module protocol ------------------------------------------------------------------------
     def train(self, mode=True):
+        switch = bool(mode) != bool(self.training)
         self.training = mode
+        if switch:
+            self._fold_fpn_norms()
         return self
+
+    def load_state_dict(self, states, strict=True):
+        """Parameters and buffers (the FPN norm's running statistics among them) from a state_dict() of the same architecture."""
+        return self.load_weights(states, strict=strict)
 
     def eval(self):
         return self.train(False)
@@ -411,6 +459,8 @@ class FPNDetector:
                 names.append(n + ".weight")
                 if c.has_bias and not c.bn_prefix:
                     names.append(n + ".bias")
+            if c.norm is not None:
+                names += [c.norm.name + ".weight", c.norm.name + ".bias"]
         names += [v.name for v in self.vparams.values()]
         return names
 
@@ -527,6 +577,13 @@ class FPNDetector:
                  if self.TOP_BLOCK == "p6p7" and all(c.fp8 for c in writers) else None)
         pl.lat = {s: act(pl.blk[pl.res[s]].gout, ch) for s in self.fpn_stages}
         pl.g_lat = {s: C.like(pl.lat[s]) for s in self.fpn_stages}
+        if self.fpn_norms:
+            # the pre-norm output of every normalised convolution, kept for the backward pass, and the gradient with respect to it (a
+            # buffer of its own: the top-down path still reads g_lat, the side stream's weight gradients read it late)
+            pl.bn_y = {(k, s): C.like(pl.lat[s]) for k in ("lateral", "output") for s in self.fpn_stages}
+            pl.bn_gy = {(k, s): C.like(pl.lat[s]) for k in ("lateral", "output") for s in self.fpn_stages}
+            rows = max(pl.blk[pl.res[s]].gout.pixels for s in self.fpn_stages)
+            pl.bn_ws = C.empty((ops.bn_workspace_bytes(rows, ch) // 4 + 64,), torch.float32)
         g6 = pl.pyr.level(len(self.fpn_stages))
         pl.p6_relu = C.empty((N * h6 * w6, ch), bf)
         pl.g_p6r = ops.single(N, h6, w6)
@@ -709,8 +766,12 @@ class FPNDetector:
                 self.p6.forward(b5.out, b5.gout, g6, pl.P, y8=pl.P8)
                 self._relu_level(pl.P, g6, pl.p6_relu)
                 self.p7.forward(pl.p6_relu, pl.g_p6r, g7, pl.P, y8=pl.P8)
+        levels = range(nl - 1, -1, -1)
+        if self.fpn_norms and self.training:       # batch statistics: the norm kernels between the launches (evaluation: folded, the loop below)
+            self._fpn_forward_norm(pl)
+            levels = ()
         prev, prev_geo = None, None
-        for li in range(nl - 1, -1, -1):
+        for li in levels:
             s = st[li]
             b = pl.blk[pl.res[s]]
             self.lateral[s].forward(b.out, b.gout, b.gout, pl.lat[s])
@@ -725,6 +786,51 @@ class FPNDetector:
         else:
             ops.subsample2x_fwd(pl.P, pl.pyr.level(nl - 1), pl.P, pl.pyr.level(nl), self.fpn_ch)   # FPNP6 (:172-183)
         self.head_forward(pl)
+
+    def _fpn_forward_norm(self, pl):
+        """The FPN's lateral / output convolutions with MODEL.FPN.NORM in training mode: lat_s = BN(conv(res_s)) + top-down,
+        P_s = BN(conv(lat_s)), batch statistics over all N H W pixels of the level.  The laterals do not depend on each other, nor do the
+        output convolutions once every lat_s exists."""
+        st, ch = self.fpn_stages, self.fpn_ch
+        B = BatchNormState
+        geo = {s: pl.blk[pl.res[s]].gout for s in st}
+        for s in st:
+            b = pl.blk[pl.res[s]]
+            self.lateral[s].forward(b.out, b.gout, b.gout, pl.bn_y["lateral", s])
+        for s in st:
+            n = self.lateral[s].norm
+            ops.bn_stats_fwd(pl.bn_y["lateral", s], geo[s], ch, B.EPS, B.MOMENTUM, n.mean, n.inv_std, n.sums, n.running_mean, n.running_var,
+                             pl.bn_ws)
+        prev = None
+        for s in reversed(st):
+            n = self.lateral[s].norm
+            ops.bn_apply_fwd(pl.bn_y["lateral", s], geo[s], n.mean, n.inv_std, n.gamma, n.beta, pl.lat[s], geo[s], ch)
+            if prev is not None and self.fpn_deconv:
+                self.upsample[prev].forward(pl.lat[prev], geo[prev], pl.lat[s], add=pl.lat[s])
+            elif prev is not None:
+                ops.upsample2x_add_fwd(pl.lat[prev], geo[prev], pl.lat[s], geo[s], ch)
+            prev = s
+        for s in st:
+            self.output[s].forward(pl.lat[s], geo[s], geo[s], pl.bn_y["output", s])
+        for s in st:
+            n = self.output[s].norm
+            ops.bn_stats_fwd(pl.bn_y["output", s], geo[s], ch, B.EPS, B.MOMENTUM, n.mean, n.inv_std, n.sums, n.running_mean, n.running_var,
+                             pl.bn_ws)
+        for li, s in enumerate(st):
+            n = self.output[s].norm
+            ops.bn_apply_fwd(pl.bn_y["output", s], geo[s], n.mean, n.inv_std, n.gamma, n.beta, pl.P, pl.pyr.level(li), ch)
+
+    def _bn_backward(self, kind, gs, ggeos, pl):
+        """Through the norms of one group (every lateral, or every output convolution): dgamma / dbeta into the gradient arena, g_y into
+        pl.bn_gy."""
+        st, ch = self.fpn_stages, self.fpn_ch
+        convs = self.lateral if kind == "lateral" else self.output
+        geo = {s: pl.blk[pl.res[s]].gout for s in st}
+        for s, g, gg in zip(st, gs, ggeos):
+            n = convs[s].norm
+            ops.bn_bwd_reduce(g, gg, pl.bn_y[kind, s], geo[s], n.mean, n.inv_std, ch, n.g_gamma, n.g_beta, pl.bn_ws)
+            ops.bn_bwd_apply(g, gg, pl.bn_y[kind, s], geo[s], n.mean, n.inv_std, n.gamma, n.g_gamma, n.g_beta, n.sums[0], pl.bn_gy[kind, s],
+                             geo[s], ch)
 
     def _relu_level(self, src, geo, dst):
         """dst (dense, per level) = relu(one pyramid level of src); the level is contiguous per image."""
@@ -863,12 +969,34 @@ class FPNDetector:
                 self.p6.dgrad(pl.g_P, b5.gout, g6, b5.g_out, first=True)
         else:
             ops.subsample2x_bwd_add(pl.g_P, pyr.level(nl), pl.g_P, pyr.level(nl - 1), self.fpn_ch)      # P6 = P5[::2, ::2]
+        def lateral_backward(li, g):
+            """Weight and data gradient of lateral li from g = dL/d(its convolution's output): g_lat, or what the norm's backward made of it."""
+            s = st[li]
+            b = pl.blk[pl.res[s]]
+            self._wgrad(self.lateral[s], b.out, g, b.gout, b.gout, ws, cws)
+            # res_s gradient: first contribution for res3/res4, second (after P6) and final for res5 -> mask there
+            if not self.blocks[pl.res[s]]["trainable"]:
+                return                                     # res2 of a FREEZE_AT=2 backbone: nothing below needs the gradient
+            if li == nl - 1:
+                if not pool_top:
+                    join(top)
+                self.lateral[s].dgrad(g, b.gout, b.gout, b.g_out, first=pool_top, mask=b.out, maskbits=b.out_bits)
+            else:
+                self.lateral[s].dgrad(g, b.gout, b.gout, b.g_out, first=True)
+
+        normed = bool(self.fpn_norms)
+        if normed:       # dL/d(conv output) of every output convolution first: nothing below reads the P3.. levels of g_P again
+            self._bn_backward("output", [pl.g_P] * nl, [pyr.level(li) for li in range(nl)], pl)
         for li in range(nl):
             s = st[li]
             b = pl.blk[pl.res[s]]
             lvl = pyr.level(li)
-            self._wgrad(self.output[s], pl.lat[s], pl.g_P, b.gout, lvl, ws, cws)
-            self.output[s].dgrad(pl.g_P, b.gout, lvl, pl.g_lat[s], first=True, g8=pl.g_P8 if pl.g_P8_ready else None)
+            if normed:
+                self._wgrad(self.output[s], pl.lat[s], pl.bn_gy["output", s], b.gout, b.gout, ws, cws)
+                self.output[s].dgrad(pl.bn_gy["output", s], b.gout, b.gout, pl.g_lat[s], first=True)
+            else:
+                self._wgrad(self.output[s], pl.lat[s], pl.g_P, b.gout, lvl, ws, cws)
+                self.output[s].dgrad(pl.g_P, b.gout, lvl, pl.g_lat[s], first=True, g8=pl.g_P8 if pl.g_P8_ready else None)
             if li > 0:   # gradient arriving through the top-down path from the finer level
                 sf = st[li - 1]
                 if self.fpn_deconv:
@@ -879,17 +1007,14 @@ class FPNDetector:
                     up.dgrad(pl.g_lat[sf], b.gout, pl.g_lat[s], add=pl.g_lat[s])
                 else:
                     ops.upsample2x_add_bwd(pl.g_lat[sf], pl.blk[pl.res[sf]].gout, pl.g_lat[s], b.gout, self.fpn_ch, accumulate=True)
-            self._wgrad(self.lateral[s], b.out, pl.g_lat[s], b.gout, b.gout, ws, cws)
-            # res_s gradient: first contribution for res3/res4, second (after P6) and final for res5 -> mask there
-            is_top = li == nl - 1
-            if not self.blocks[pl.res[s]]["trainable"]:
-                continue                                   # res2 of a FREEZE_AT=2 backbone: nothing below needs the gradient
-            if is_top:
-                if not pool_top:
-                    join(top)
-                self.lateral[s].dgrad(pl.g_lat[s], b.gout, b.gout, b.g_out, first=pool_top, mask=b.out, maskbits=b.out_bits)
-            else:
-                self.lateral[s].dgrad(pl.g_lat[s], b.gout, b.gout, b.g_out, first=True)
+            if not normed:
+                lateral_backward(li, pl.g_lat[s])
+        if normed:
+            # every g_lat is complete (the un-normalised gradient the top-down path read): through the laterals' norms, then their
+            # convolutions on the gradient with respect to the convolution's output
+            self._bn_backward("lateral", [pl.g_lat[s] for s in st], [pl.blk[pl.res[s]].gout for s in st], pl)
+            for li in range(nl):
+                lateral_backward(li, pl.bn_gy["lateral", st[li]])
         self._flush_wgrads()
         if on_bucket_ready:
             on_bucket_ready("fpn", side)

@@ -73,17 +73,33 @@ def init_resnet(p, rng, name, residual_gamma=None):
             _bn(p, f"{pre}.downsample.1", blk["cout"])
 
 
-def init_fpn(p, rng, in_channels, stages, out_ch, top_in, top_convs=True):
+def init_fpn(p, rng, in_channels, stages, out_ch, top_in, top_convs=True, norm=None):
+    """norm (MODEL.FPN.NORM): the lateral / output convolutions lose their bias (fpn_backbone.py:49-76; the zeros are not drawn, so every
+    other entry keeps its bits); init_fpn_norm adds the norm's entries."""
     for s, ci in zip(stages, in_channels):
         p[f"backbone.fpn_lateral{s}.weight"] = _msra_normal(rng, (out_ch, ci, 1, 1), "fan_in")
-        p[f"backbone.fpn_lateral{s}.bias"] = np.zeros(out_ch, np.float32)
         p[f"backbone.fpn_output{s}.weight"] = _msra_normal(rng, (out_ch, out_ch, 3, 3), "fan_in")
-        p[f"backbone.fpn_output{s}.bias"] = np.zeros(out_ch, np.float32)
+        if norm is None:
+            p[f"backbone.fpn_lateral{s}.bias"] = np.zeros(out_ch, np.float32)
+            p[f"backbone.fpn_output{s}.bias"] = np.zeros(out_ch, np.float32)
     if not top_convs:      # FPNP6 (fpn_backbone.py:172-183) has no parameters
         return
     for nm, ci in (("p6", top_in), ("p7", out_ch)):
         p[f"backbone.top_block.{nm}.weight"] = (rng.standard_normal((out_ch, ci, 3, 3)) * math.sqrt(1.0 / (ci * 9))).astype(np.float32)
         p[f"backbone.top_block.{nm}.bias"] = np.zeros(out_ch, np.float32)
+
+
+def fpn_norm(cfg):
+    """MODEL.FPN.NORM: None, "BN" or "SyncBN" (FPNDetector.check_config refuses the rest)."""
+    return cfg.MODEL.FPN.get("NORM", None)
+
+
+def init_fpn_norm(p, stages, out_ch):
+    """layers.get_norm(norm, out_channels) behind every lateral and output convolution (fpn_backbone.py:49-76): gamma = 1, beta = 0,
+    running_mean = 0, running_var = 1.  Added after every other parameter, like init_fpn_upsample; top_block has no norm (:186-204)."""
+    for kind in ("lateral", "output"):
+        for s in stages:
+            _bn(p, f"backbone.fpn_{kind}{s}.norm", out_ch)
 
 
 def fpn_upsample_deconv(cfg):
@@ -117,11 +133,13 @@ def init_retinanet_params(cfg, seed=0, residual_gamma=None):
     p = {}
     init_resnet(p, rng, m.BACKBONE.NAME, residual_gamma)
     stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES]
-    init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, m.FPN.OUT_CHANNELS, m.FPN.TOP_BLOCK_IN_CHANNELS)
+    init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, m.FPN.OUT_CHANNELS, m.FPN.TOP_BLOCK_IN_CHANNELS, norm=fpn_norm(cfg))
     na = len(m.ANCHOR.SCALES[0]) * len(m.ANCHOR.RATIOS[0])
     init_retina_head(p, rng, m.FPN.OUT_CHANNELS, na, cfg.DATA.NUM_CLASSES, m.HEAD.NUM_CONVS, m.HEAD.CLS_PRIOR_PROB)
     if fpn_upsample_deconv(cfg):
         init_fpn_upsample(p, rng, stages, m.FPN.OUT_CHANNELS)
+    if fpn_norm(cfg) is not None:
+        init_fpn_norm(p, stages, m.FPN.OUT_CHANNELS)
     return p
 
 
@@ -149,11 +167,13 @@ def init_fcos_params(cfg, seed=0, residual_gamma=None):
     p = {}
     init_resnet(p, rng, m.BACKBONE.NAME, residual_gamma)
     stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES]
-    init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, m.FPN.OUT_CHANNELS, m.FPN.TOP_BLOCK_IN_CHANNELS)
+    init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, m.FPN.OUT_CHANNELS, m.FPN.TOP_BLOCK_IN_CHANNELS, norm=fpn_norm(cfg))
     init_point_head(p, rng, m.FPN.OUT_CHANNELS, m.ANCHOR.NUM_ANCHORS, cfg.DATA.NUM_CLASSES, m.HEAD.NUM_CONVS,
                     m.HEAD.CLS_PRIOR_PROB, len(m.FPN.STRIDES))
     if fpn_upsample_deconv(cfg):
         init_fpn_upsample(p, rng, stages, m.FPN.OUT_CHANNELS)
+    if fpn_norm(cfg) is not None:
+        init_fpn_norm(p, stages, m.FPN.OUT_CHANNELS)
     return p
 
 
@@ -166,7 +186,7 @@ def init_faster_rcnn_params(cfg, seed=0, residual_gamma=None):
     init_resnet(p, rng, m.BACKBONE.NAME, residual_gamma)
     stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES]
     ch = m.FPN.OUT_CHANNELS
-    init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, ch, m.FPN.TOP_BLOCK_IN_CHANNELS, top_convs=False)
+    init_fpn(p, rng, m.BACKBONE.OUT_FEATURE_CHANNELS, stages, ch, m.FPN.TOP_BLOCK_IN_CHANNELS, top_convs=False, norm=fpn_norm(cfg))
     na = len(m.ANCHOR.SCALES[0]) * len(m.ANCHOR.RATIOS[0])
     rc = m.RPN.CHANNELS
     p["rpn.rpn_conv.weight"] = (rng.standard_normal((rc, ch, 3, 3)) * 0.01).astype(np.float32)
@@ -185,6 +205,8 @@ def init_faster_rcnn_params(cfg, seed=0, residual_gamma=None):
     p["rcnn.pred_cls.bias"] = np.zeros(K + 1, np.float32)
     p["rcnn.pred_delta.weight"] = (rng.standard_normal((K * 4, 1024)) * 0.001).astype(np.float32)
     p["rcnn.pred_delta.bias"] = np.zeros(K * 4, np.float32)
+    if fpn_norm(cfg) is not None:
+        init_fpn_norm(p, stages, ch)
     return p
 
 
@@ -205,8 +227,9 @@ def trainable_names(params, freeze_at=2):
 
 def oracle_arch(cfg):
     m = cfg.MODEL
+    nrm = dict(fpn_norm=fpn_norm(cfg)) if fpn_norm(cfg) is not None else {}
     if m.NAME == "FasterRCNN":
-        return dict(backbone=m.BACKBONE.NAME, fpn_in=list(m.BACKBONE.OUT_FEATURES), top_block="pool",
+        return dict(nrm, backbone=m.BACKBONE.NAME, fpn_in=list(m.BACKBONE.OUT_FEATURES), top_block="pool",
                     num_classes=cfg.DATA.NUM_CLASSES, img_mean=list(m.BACKBONE.IMG_MEAN), img_std=list(m.BACKBONE.IMG_STD),
                     strides=list(m.FPN.STRIDES), anchor_scales=[list(s) for s in m.ANCHOR.SCALES],
                     anchor_ratios=[list(r) for r in m.ANCHOR.RATIOS], anchor_offset=m.ANCHOR.OFFSET,
@@ -215,7 +238,7 @@ def oracle_arch(cfg):
                     rcnn_box_reg=(list(m.RCNN_BOX_REG.MEAN), list(m.RCNN_BOX_REG.STD)),
                     matcher=(list(m.MATCHER.THRESHOLDS), list(m.MATCHER.LABELS), m.MATCHER.ALLOW_LOW_QUALITY),
                     rpn_beta=m.LOSSES.RPN_SMOOTH_L1_BETA, rcnn_beta=m.LOSSES.RCNN_SMOOTH_L1_BETA)
-    up = dict(upsample="deconv") if fpn_upsample_deconv(cfg) else {}
+    up = dict(nrm, **(dict(upsample="deconv") if fpn_upsample_deconv(cfg) else {}))
     if m.NAME in ("FCOS", "ATSS", "OTA"):
         extra = dict(atss=dict(scale=m.ANCHOR.SCALE, topk=m.ANCHOR.TOPK), sizes_of_interest=None, center_sampling_radius=None) \
             if m.NAME == "ATSS" else dict(sizes_of_interest=[list(s) for s in m.HEAD.OBJECT_SIZES_OF_INTEREST],

@@ -884,6 +884,40 @@ def groupnorm_bwd(dz, y, gamma, beta, stats, geom: Geom, Cn, relu, dy, dgamma, d
     return dy
 
 
+# ---- BatchNorm of one pyramid level (csrc/batchnorm.hip) ------------------------------------------------------------------
+def _lvl(geom: Geom):
+    assert geom.nlev == 1
+    return geom.pix_per_img, geom.off[0]
+
+
+def bn_workspace_bytes(rows, Cn):
+    return int(L().bd_bn_workspace_bytes(int(rows), Cn))
+
+
+def bn_stats_fwd(y, geom: Geom, Cn, eps, momentum, mean, inv_std, sums, running_mean, running_var, ws):
+    """Batch statistics of one level of y: mean, inv_std, sums = [M, sum y, sum y^2] (3, C), and the running statistics updated in place
+    (None: left alone)."""
+    check(L().bd_bn_stats_fwd(ptr(y), geom.N, *_lvl(geom), geom.H[0] * geom.W[0], Cn, eps, momentum, ptr(mean), ptr(inv_std), ptr(sums),
+                              ptr(running_mean), ptr(running_var), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "bd_bn_stats_fwd")
+
+
+def bn_apply_fwd(y, gy: Geom, mean, inv_std, gamma, beta, z, gz: Geom, Cn):
+    check(L().bd_bn_apply_fwd(ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), ptr(z), *_lvl(gz), gy.N,
+                              gy.H[0] * gy.W[0], Cn, stream_ptr()), "bd_bn_apply_fwd")
+    return z
+
+
+def bn_bwd_reduce(g, gg: Geom, y, gy: Geom, mean, inv_std, Cn, dgamma, dbeta, ws):
+    check(L().bd_bn_bwd_reduce(ptr(g), *_lvl(gg), ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), gy.N, gy.H[0] * gy.W[0], Cn, ptr(dgamma),
+                               ptr(dbeta), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "bd_bn_bwd_reduce")
+
+
+def bn_bwd_apply(g, gg: Geom, y, gy: Geom, mean, inv_std, gamma, dgamma, dbeta, count, out, go: Geom, Cn):
+    check(L().bd_bn_bwd_apply(ptr(g), *_lvl(gg), ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(dgamma), ptr(dbeta), ptr(count),
+                              ptr(out), *_lvl(go), gy.N, gy.H[0] * gy.W[0], Cn, stream_ptr()), "bd_bn_bwd_apply")
+    return out
+
+
 def fcos_offsets_fwd(raw, ld, scales, geom: Geom, strides, out):
     off, cnt = _lvl_arrays(geom)
     check(L().bd_fcos_offsets_fwd(ptr(raw), ld, ptr(scales), geom.N, geom.nlev, off, cnt, i32arr(strides), geom.pix_per_img, ptr(out),

@@ -394,4 +394,6 @@ def broadcast_parameters(model, src=0):
     c = _comm.get_comm()
     if c is not None and c.world > 1:
         c.bcast(model.arena.w, root=src)
+        if getattr(model, "fpn_norms", None):      # buffers: the FPN norm's running statistics
+            c.bcast(model.bn_running, root=src)
         model.repack_trainable()

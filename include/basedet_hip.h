@@ -601,6 +601,36 @@ int bd_groupnorm_bwd(const void* dz, const void* y, const float* gamma, const fl
                      const int32_t* lvl_off_host, const int32_t* lvl_cnt_host, int64_t pix_per_img, int C, int relu,
                      void* dy, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream);
 
+/* BatchNorm2d in training mode for the FPN's lateral / output convolutions (MODEL.FPN.NORM = "BN" / "SyncBN", fpn_backbone.py:49-76;
+ * bd_version() >= 109; batchnorm.hip).  Every entry serves ONE pyramid level of a pixel-major bf16 tensor that may hold several: row r
+ * (r < N * n, n = H * W) of the level is pixel row (r / n) * pix_per_img + off + r % n of its buffer, C channels each, C % 8 == 0,
+ * off + n <= pix_per_img; each tensor of a call has its own (pix_per_img, off).  Statistics and parameters are fp32 [C].  The reductions
+ * are two-stage over fixed 128-row slots, combined in a fixed order, without floating-point atomics: the same bits on every run.
+ * ws: bd_bn_workspace_bytes(N * n, C), shared by bd_bn_stats_fwd and bd_bn_bwd_reduce.
+ *
+ * bd_bn_stats_fwd: per-channel batch mean and BIASED variance of y over the N * n rows (N * n < 2^24).  Slots are reduced to (count, mean,
+ * M2) from sums shifted by a sample and combined with Chan's update -- never a raw sum of squares.  Writes mean, inv_std =
+ * 1 / sqrt(var + eps), sums = fp32 [3][C] = (M, sum y, sum y^2) and, where the pointers are not NULL,
+ * running = (1 - momentum) * running + momentum * batch with the unbiased variance M2 / max(M - 1, 1) (MegEngine's BatchNorm2d,
+ * momentum = 0.1 in torch's convention).  mean / inv_std or sums may be NULL (not both). */
+size_t bd_bn_workspace_bytes(int64_t rows, int C);
+int bd_bn_stats_fwd(const void* y, int N, int64_t pix_per_img, int64_t off, int64_t n, int C, float eps, float momentum, float* mean,
+                    float* inv_std, float* sums, float* running_mean, float* running_var, void* ws, size_t ws_bytes, bd_stream_t stream);
+/* z = gamma * (y - mean) * inv_std + beta, evaluated in fp64 on the fp32 statistics and rounded once to bf16; z must not be y (the
+ * backward pass reads y).  The FPN's top-down term is added by the launch that follows (bd_upsample2x_add_fwd / bd_fpn_deconv_fwd). */
+int bd_bn_apply_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
+                    const float* beta, void* z, int64_t z_pix_per_img, int64_t z_off, int N, int64_t n, int C,
+                    bd_stream_t stream);
+/* dbeta[c] = sum g, dgamma[c] = sum g * xhat with xhat = (y - mean) * inv_std recomputed from the saved pre-norm y; both overwritten. */
+int bd_bn_bwd_reduce(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
+                     const float* mean, const float* inv_std, int N, int64_t n, int C, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                     bd_stream_t stream);
+/* gy = gamma * inv_std * (g - dbeta / M - xhat * dgamma / M), M = count[c] (the first vector of sums);
+ * fp64 arithmetic, one rounding to bf16.  gy must not be g: the top-down path still reads g. */
+int bd_bn_bwd_apply(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
+                    const float* mean, const float* inv_std, const float* gamma, const float* dgamma, const float* dbeta, const float* count,
+                    void* gy, int64_t gy_pix_per_img, int64_t gy_off, int N, int64_t n, int C, bd_stream_t stream);
+
 /* offsets = relu(bbox_pred * scale_l) * stride_l (point_head.py:143).  raw: bf16 [pixels][ld = 8] (channels 0-3 =
  * bbox_pred, 4 = ctrness logit, 5-7 = 0), scales: device fp32 [L]; out: bf16 [pixels][4]. */
 int bd_fcos_offsets_fwd(const void* raw, int ld, const float* scales, int N, int L, const int32_t* lvl_off_host,
