@@ -1,4 +1,5 @@
-// BatchNorm2d in training mode for the FPN's lateral / output convolutions (MODEL.FPN.NORM = "BN" / "SyncBN"; fpn_backbone.py:49-76):
+// BatchNorm2d in training mode for the FPN's lateral / output convolutions (MODEL.FPN.NORM = "BN" / "SyncBN"; fpn_backbone.py:49-76) and for
+// the backbone's (MODEL.BACKBONE.NORM; its epilogue, norm + shortcut + ReLU in one pass, is bd_bn_apply_act_fwd):
 // NHWC bf16 activations, fp32 statistics.  One call serves ONE pyramid level of a pixel-major tensor that may hold several: row r of the
 // level (r < N * n) is pixel row (r / n) * pix_per_img + off + r % n of the buffer, C channels each, C % 8 == 0.
 //   fwd: stats (read y) -> apply (read y, write z)              bwd: reduce (read g, y) -> apply (read g, y, write g_y)
@@ -151,6 +152,41 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const bf16_raw* __res
     }
 }
 
+// z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]): the epilogue of a backbone convolution under MODEL.BACKBONE.NORM = "BN" /
+// "SyncBN" (conv -> BN -> ReLU, and conv -> BN -> + identity -> ReLU in a block's last stage; models/cls/resnet.py:42-52, 94-113) in ONE
+// pass: read y and the residual, write z.  Layout and arithmetic are bn_apply_fwd_kernel's (fp64 on the fp32 statistics, per-channel terms
+// once per thread); the residual joins in fp64 BEFORE the single rounding, so a shortcut that cancels gamma * xhat + beta keeps the bits
+// of the small difference.
+template <bool RES, bool RELU>
+__global__ __launch_bounds__(256) void bn_apply_act_fwd_kernel(const bf16_raw* __restrict__ y, BnGeo gy, const float* __restrict__ mean,
+                                                               const float* __restrict__ inv_std, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, const bf16_raw* __restrict__ res, BnGeo gr,
+                                                               bf16_raw* __restrict__ z, BnGeo gz, long long n, long long M, int C) {
+    const int cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
+    const int c0 = (blockIdx.y * 32 + cl) * 8;
+    if (c0 >= C) return;
+    double A[8];
+    float mu[8], bt[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { A[k] = (double)gamma[c0 + k] * (double)inv_std[c0 + k]; mu[k] = mean[c0 + k]; bt[k] = beta[c0 + k]; }
+    for (long long r = (long long)blockIdx.x * BN_PXL + pl; r < M; r += (long long)gridDim.x * BN_PXL) {
+        float v[8], a[8], o[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(y + bn_row_addr(r, n, gy) * C + c0), v);
+        if (RES) unpack8(*reinterpret_cast<const u32x4_t*>(res + bn_row_addr(r, n, gr) * C + c0), a);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            double t = ((double)v[k] - (double)mu[k]) * A[k] + (double)bt[k];
+            if (RES) t += (double)a[k];
+            const float f = (float)t;
+            o[k] = RELU ? (f > 0.f ? f : 0.f) : f;
+        }
+        u32x4_t w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = pack_bf2(o[2 * k], o[2 * k + 1]);
+        *reinterpret_cast<u32x4_t*>(z + bn_row_addr(r, n, gz) * C + c0) = w;
+    }
+}
+
 // stage 1 of the backward sums: part[(slot * C + c) * 2] = (sum g * xhat, sum g) over the slot's rows
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const bf16_raw* __restrict__ g, BnGeo gg, const bf16_raw* __restrict__ y, BnGeo gy,
                                                              const float* __restrict__ mean, const float* __restrict__ inv_std, long long n,
@@ -285,6 +321,26 @@ extern "C" int bd_bn_apply_fwd(const void* y, int64_t y_pix_per_img, int64_t y_o
                        BnGeo{y_pix_per_img, y_off}, mean, inv_std, gamma, beta, (bf16_raw*)z, BnGeo{z_pix_per_img, z_off},
                        (long long)n, M, C);
     BD_CHECK_LAUNCH("bd_bn_apply_fwd");
+    return BD_OK;
+}
+
+extern "C" int bd_bn_apply_act_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std,
+                                   const float* gamma, const float* beta, const void* residual, int64_t r_pix_per_img, int64_t r_off, void* z,
+                                   int64_t z_pix_per_img, int64_t z_off, int N, int64_t n, int C, int relu, bd_stream_t stream) {
+    BD_REQUIRE(y && mean && inv_std && gamma && beta && z, "bn_apply_act_fwd: null pointer");
+    BD_REQUIRE(N >= 1 && C >= 8 && C % 8 == 0 && bn_geo_ok(y_pix_per_img, y_off, n) && bn_geo_ok(z_pix_per_img, z_off, n)
+               && (!residual || bn_geo_ok(r_pix_per_img, r_off, n)), "bn_apply_act_fwd: bad shape (N=%d C=%d)", N, C);
+    BD_REQUIRE(z != y && z != residual, "bn_apply_act_fwd: the backward pass reads the pre-norm tensor and the shortcut: z needs a buffer of its own");
+    const long long M = (long long)N * n;
+    const BnGeo gy{y_pix_per_img, y_off}, gr{r_pix_per_img, r_off}, gz{z_pix_per_img, z_off};
+    hipStream_t st = (hipStream_t)stream;
+#define BD_BN_ACT(RES, RELU)                                                                                                             \
+    hipLaunchKernelGGL((bn_apply_act_fwd_kernel<RES, RELU>), bn_apply_grid(M, C), dim3(256), 0, st, (const bf16_raw*)y, gy, mean, inv_std, \
+                       gamma, beta, (const bf16_raw*)residual, gr, (bf16_raw*)z, gz, (long long)n, M, C)
+    if (residual) { if (relu) BD_BN_ACT(true, true); else BD_BN_ACT(true, false); }
+    else { if (relu) BD_BN_ACT(false, true); else BD_BN_ACT(false, false); }
+#undef BD_BN_ACT
+    BD_CHECK_LAUNCH("bd_bn_apply_act_fwd");
     return BD_OK;
 }
 

@@ -13,6 +13,8 @@ namespace {
 
 constexpr int W_PITCH = 480;  // bytes per weight row in LDS: 448 data + 32 pad (conflict-free b128 reads)
 
+// RAW (MODEL.BACKBONE.NORM = "BN" / "SyncBN" in training): the bare convolution, no shift and no ReLU -- the batch-norm kernels follow
+template <bool RAW>
 __global__ __launch_bounds__(256) void stem_conv_kernel(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ w,
                                                         const float* __restrict__ bias, bf16_raw* __restrict__ y,
                                                         int N, int H, int W) {
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const bf16_raw* __restri
     const int pix = lane & 15, q = lane >> 4;
     float bias_r[16];                              // this lane's 16 channels: 8q..8q+7 and 32+8q..32+8q+7
 #pragma unroll
-    for (int k = 0; k < 16; ++k) bias_r[k] = bias[32 * (k >> 3) + 8 * q + (k & 7)];
+    for (int k = 0; k < 16; ++k) bias_r[k] = RAW ? 0.f : bias[32 * (k >> 3) + 8 * q + (k & 7)];
 
     for (int grp = blockIdx.x * 4 + wave; grp < ngroups; grp += gridDim.x * 4) {
         const int mbase = grp * 64;
@@ -80,6 +82,9 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const bf16_raw* __restri
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int e0 = 2 * k, e1 = 2 * k + 1;       // element e of the 8: tile 2*half + (e>>2), register e&3
+                    if (RAW)
+                        o[k] = pack_bf2(acc[2 * half + (e0 >> 2)][j][e0 & 3], acc[2 * half + (e1 >> 2)][j][e1 & 3]);
+                    else
                     o[k] = pack_bf2(fmaxf(acc[2 * half + (e0 >> 2)][j][e0 & 3] + bias_r[8 * half + e0], 0.f),
                                     fmaxf(acc[2 * half + (e1 >> 2)][j][e1 & 3] + bias_r[8 * half + e1], 0.f));
                 }
@@ -252,9 +257,22 @@ extern "C" int bd_stem_conv7x7_fwd(int N, int H, int W, const void* x_halo, cons
     BD_REQUIRE(M < 0x7fffffffll, "stem_conv7x7_fwd: too many output pixels");
     long long groups = (M + 255) / 256;
     const int grid = (int)(groups < 2048 ? groups : 2048);
-    hipLaunchKernelGGL(stem_conv_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)x_halo,
+    hipLaunchKernelGGL(stem_conv_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)x_halo,
                        (const bf16_raw*)w_stem, bias, (bf16_raw*)y, N, H, W);
     BD_CHECK_LAUNCH("bd_stem_conv7x7_fwd");
+    return BD_OK;
+}
+
+extern "C" int bd_stem_conv7x7_raw_fwd(int N, int H, int W, const void* x_halo, const void* w_stem, void* y, bd_stream_t stream) {
+    BD_REQUIRE(x_halo && w_stem && y, "stem_conv7x7_raw_fwd: null pointer");
+    BD_REQUIRE(N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "stem_conv7x7_raw_fwd: H=%d W=%d must be even", H, W);
+    const long long M = (long long)N * (H / 2) * (W / 2);
+    BD_REQUIRE(M < 0x7fffffffll, "stem_conv7x7_raw_fwd: too many output pixels");
+    long long groups = (M + 255) / 256;
+    const int grid = (int)(groups < 2048 ? groups : 2048);
+    hipLaunchKernelGGL(stem_conv_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)x_halo,
+                       (const bf16_raw*)w_stem, (const float*)nullptr, (bf16_raw*)y, N, H, W);
+    BD_CHECK_LAUNCH("bd_stem_conv7x7_raw_fwd");
     return BD_OK;
 }
 

@@ -47,7 +47,9 @@ class ConvLayer:
     def __init__(self, name, cin, cout, k, stride, pad, device, bn_prefix=None, has_bias=False, trainable=True,
                  cout_pad=None, norm=None):
         self.name, self.cin, self.cout_real, self.k, self.stride, self.pad = name, cin, cout, k, stride, pad
-        self.norm = norm                      # BatchNormState of a normalised FPN convolution (MODEL.FPN.NORM): its slots follow the weight's
+        # BatchNormState of a normalised convolution (MODEL.FPN.NORM; MODEL.BACKBONE.NORM = "BN" / "SyncBN": named by the reference's
+        # bnK / downsample.1 prefix, bn_prefix then None): its slots follow the weight's
+        self.norm = norm
         self.cout = cout_pad or cout          # padded channel count seen by the kernels (bbox_pred: 36 -> 40)
         self.bn_prefix, self.has_bias, self.trainable = bn_prefix, has_bias, trainable
         self.device = device
@@ -344,8 +346,9 @@ class ConvLayer:
 
 
 class BatchNormState:
-    """The norm record of one normalised FPN convolution (MODEL.FPN.NORM = "BN" / "SyncBN"; layers.get_norm at fpn_backbone.py:49-76):
-    gamma / beta are trainable fp32 vectors in the parameter arena, right behind the convolution's weight (`<conv>.norm.weight` / `.bias`);
+    """The norm record of one normalised convolution (MODEL.FPN.NORM = "BN" / "SyncBN", layers.get_norm at fpn_backbone.py:49-76, named
+    `<conv>.norm`; MODEL.BACKBONE.NORM, layers/backbone/build.py:27-30, named `...bnK` / `...downsample.1` like the FrozenBN it replaces):
+    gamma / beta are trainable fp32 vectors in the parameter arena, right behind the convolution's weight (`<name>.weight` / `.bias`);
     the running statistics are buffers (`.running_mean` / `.running_var`); mean / inv_std / sums are the batch statistics of the last
     training forward (sums = [M, sum y, sum y^2]; the backward pass reads the count M).  The buffers are rows of model-level tensors, so
     that every norm's vectors of one kind are contiguous (one broadcast)."""
@@ -423,9 +426,12 @@ class TrainableStem:
 
     name = "backbone.bottom_up.conv1"
     fp8_wgrad = False
+    norm = None          # BatchNormState "backbone.bottom_up.bn1" under MODEL.BACKBONE.NORM = "BN" / "SyncBN": right behind the weight
 
     def reserve(self, arena):
         self._wi = arena.reserve(self.name + ".weight", (64, 7, 7, 3))
+        if self.norm is not None:
+            self.norm.reserve(arena)
 
     def bind(self, arena, w_ohwi, row_scale):
         self.w = arena.view("w", self._wi); self.gw = arena.view("g", self._wi)
@@ -435,6 +441,8 @@ class TrainableStem:
 
     def export_grad(self, out):
         out[self.name + ".weight"] = self.gw.permute(0, 3, 1, 2).contiguous().cpu()
+        if self.norm is not None:
+            self.norm.export_grad(out)
 
     def wgrad(self, x, g, gin, gout, ws, colsum_ws=None, x8=None, g8=None, queue=None):
         """x: x_halo of the padded batch (gin: its N x Hp x Wp geometry), g: dL/d(pre-activation) of the stem output."""

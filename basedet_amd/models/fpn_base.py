@@ -57,12 +57,25 @@ class FPNDetector:
         """Refuse the config variants this build does not implement (ValueError naming the key), instead of training another network."""
         m = cfg.MODEL
         norm = m.BACKBONE.get("NORM", "FrozenBN")
-        if norm != "FrozenBN":
-            raise ValueError(f"MODEL.BACKBONE.NORM = {norm!r} is not supported: only 'FrozenBN' is implemented")
+        if not isinstance(norm, str) or norm not in ("FrozenBN", "BN", "SyncBN"):
+            raise ValueError(f"MODEL.BACKBONE.NORM = {norm!r} is not supported: 'FrozenBN', 'BN' and 'SyncBN' are implemented")
         fa = m.BACKBONE.FREEZE_AT
         if not isinstance(fa, int) or isinstance(fa, bool) or fa < 0:
             raise ValueError(f"MODEL.BACKBONE.FREEZE_AT = {fa!r} is not supported: an integer >= 0 (0 trains the stem, 1 freezes it, "
                              ">= 2 freezes layer1 too)")
+        if norm != "FrozenBN":
+            if fa >= 1:
+                raise ValueError(f"MODEL.BACKBONE.NORM = {norm!r} with MODEL.BACKBONE.FREEZE_AT = {fa} is not supported: the reference's parameter "
+                                 "filter freezes conv1 / layer1 by name but not their norms, so gamma / beta below the frozen convolutions "
+                                 "would train through a data gradient without weight gradients -- that backward pass is not built; a live "
+                                 "backbone norm runs at FREEZE_AT = 0")
+            if norm == "SyncBN" and _comm.world_size() > 1:
+                raise ValueError(f"MODEL.BACKBONE.NORM = 'SyncBN' at world size {_comm.world_size()} is not supported: the exchange of the batch "
+                                 "statistics between the ranks is not built; 'SyncBN' runs at world size 1 (as 'BN'), 'BN' at any world size "
+                                 "(statistics of the rank's own batch)")
+            if m.get("WEIGHT_DTYPE", "bf16") != "bf16":
+                raise ValueError(f"MODEL.BACKBONE.NORM = {norm!r} with MODEL.WEIGHT_DTYPE = {m.WEIGHT_DTYPE!r} is not supported: the fp8 twins "
+                                 "of the normalised backbone tensors are not built; use 'bf16'")
         fnorm = m.FPN.get("NORM", None)
         if fnorm not in (None, "BN", "SyncBN"):
             raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} is not supported: None (no FPN norm), 'BN' and 'SyncBN' are implemented")
@@ -149,7 +162,33 @@ class FPNDetector:
         # stem: frozen when FREEZE_AT >= 1 (solver/default_solver.py:83-94); at 0 its master weight and gradient live in the arena
         # (first: the arena follows the forward order) and the backward pass ends with the kernels of csrc/stem_bwd.hip
         self.stem = TrainableStem() if self.freeze_at < 1 else None
+        # MODEL.BACKBONE.NORM = "BN" / "SyncBN" (layers/backbone/build.py:27-30; FREEZE_AT = 0 only, check_config): every bnK / downsample.1
+        # and the stem's bn1 is a live BatchNorm2d under the FrozenBN's name.  Their buffers are slices of three flat model-level tensors
+        # (one broadcast): per norm (2, C) running statistics, (2, C) batch statistics and (3, C) sums, in forward order
+        self.backbone_norm = P.backbone_norm(self.cfg)
+        self.backbone_norms = []
+        if self.backbone_norm is not None:
+            chans = [64] + [c for blk in self.blocks for c in
+                            ([blk["ch"], blk["ch"], blk["cout"]] if blk["kind"] == "bottleneck" else [blk["ch"], blk["cout"]])
+                            + ([blk["cout"]] if blk["has_ds"] else [])]
+            f32 = dict(dtype=torch.float32, device=dev)
+            tot = sum(chans)
+            self.bbn_running, self.bbn_stats, self.bbn_sums = torch.zeros(2 * tot, **f32), torch.zeros(2 * tot, **f32), torch.zeros(3 * tot, **f32)
+            self._bbn_off = 0
+
+        def bb_norm(prefix, c):
+            """(bn_prefix, norm) of one backbone convolution: the FrozenBN fold by name, or a live norm record."""
+            if self.backbone_norm is None:
+                return dict(bn=prefix)
+            o = self._bbn_off
+            self._bbn_off += c
+            n = BatchNormState(prefix, c, self.bbn_running[2 * o: 2 * (o + c)].view(2, c), self.bbn_stats[2 * o: 2 * (o + c)].view(2, c),
+                               self.bbn_sums[3 * o: 3 * (o + c)].view(3, c))
+            self.backbone_norms.append(n)
+            return dict(norm=n)
+
         if self.stem is not None:
+            self.stem.norm = bb_norm(bu + ".bn1", 64).get("norm")
             self.stem.reserve(self.arena)
         self.stem_packed = torch.empty((64, 7, 8, 4), dtype=torch.bfloat16, device=dev)
 
@@ -159,17 +198,17 @@ class FPNDetector:
             blk["trainable"] = tr
             if blk["kind"] == "bottleneck":
                 blk["convs"] = [
-                    add(pre + ".conv1", blk["cin"], blk["ch"], 1, 1, 0, bn=pre + ".bn1", trainable=tr),
-                    add(pre + ".conv2", blk["ch"], blk["ch"], 3, blk["stride"], 1, bn=pre + ".bn2", trainable=tr),
-                    add(pre + ".conv3", blk["ch"], blk["cout"], 1, 1, 0, bn=pre + ".bn3", trainable=tr),
+                    add(pre + ".conv1", blk["cin"], blk["ch"], 1, 1, 0, trainable=tr, **bb_norm(pre + ".bn1", blk["ch"])),
+                    add(pre + ".conv2", blk["ch"], blk["ch"], 3, blk["stride"], 1, trainable=tr, **bb_norm(pre + ".bn2", blk["ch"])),
+                    add(pre + ".conv3", blk["ch"], blk["cout"], 1, 1, 0, trainable=tr, **bb_norm(pre + ".bn3", blk["cout"])),
                 ]
             else:
                 blk["convs"] = [
-                    add(pre + ".conv1", blk["cin"], blk["ch"], 3, blk["stride"], 1, bn=pre + ".bn1", trainable=tr),
-                    add(pre + ".conv2", blk["ch"], blk["cout"], 3, 1, 1, bn=pre + ".bn2", trainable=tr),
+                    add(pre + ".conv1", blk["cin"], blk["ch"], 3, blk["stride"], 1, trainable=tr, **bb_norm(pre + ".bn1", blk["ch"])),
+                    add(pre + ".conv2", blk["ch"], blk["cout"], 3, 1, 1, trainable=tr, **bb_norm(pre + ".bn2", blk["cout"])),
                 ]
-            blk["ds"] = add(pre + ".downsample.0", blk["cin"], blk["cout"], 1, blk["stride"], 0, bn=pre + ".downsample.1",
-                            trainable=tr) if blk["has_ds"] else None
+            blk["ds"] = add(pre + ".downsample.0", blk["cin"], blk["cout"], 1, blk["stride"], 0, trainable=tr,
+                            **bb_norm(pre + ".downsample.1", blk["cout"])) if blk["has_ds"] else None
 
         self.fpn_stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES]          # [3, 4, 5]
         ch = self.fpn_ch
@@ -306,11 +345,15 @@ class FPNDetector:
         self.stem_shift = torch.from_numpy((b - mu * sc).astype(np.float32)).to(dev)
         if self.stem is not None:
             self.stem_w = self.stem.bind(self.arena, self.stem_w, self.stem_scale)
+            if self.stem.norm is not None:
+                self.stem.norm.bind(self.arena, params)
         self._pack_table = None                # row_scale tensors are re-created by bind()
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.bind(self.arena, params)
-        self._fold_fpn_norms()
-        self._bn_params = {k: np.asarray(v, np.float32).copy() for k, v in params.items() if (".bn" in k or "downsample.1" in k)}
+        self._fold_norms(pack=False)           # (repack_weights below packs everything)
+        # FrozenBN vectors are constants state_dict() hands back; live backbone norms export their own (moving) values
+        self._bn_params = {k: np.asarray(v, np.float32).copy() for k, v in params.items()
+                           if (".bn" in k or "downsample.1" in k) and self.backbone_norm is None}
         self.repack_weights()
 
     def _q8_buf(self, key, nbytes):
@@ -348,22 +391,36 @@ class FPNDetector:
         for c in self.convs.values():
             if (c.fp8 or c.fp8_1x1 or c.fp8_1x1_dgrad) and c.trainable:
                 c.pack_fp8()
-        if self.fpn_norms and not self.training:       # evaluating (ModelEMA.applied() swaps the weights in): the folded affine follows gamma / beta
-            self._fold_fpn_norms()
+        if (self.fpn_norms or self.backbone_norms) and not self.training:       # evaluating (ModelEMA.applied() swaps the weights in): the folded affine follows gamma / beta
+            self._fold_norms()
 
-    def _fold_fpn_norms(self):
+    def _fold_norms(self, pack=True):
         """Training: the normalised convolutions run bare (no bias, no scale; the batch-norm kernels follow).  Evaluation: the running
         statistics and gamma / beta become the per-channel affine of the convolution's own launch, as FrozenBN's (scale folded into the
-        packed weight, shift = its bias) -- inference launches no batch-norm kernel."""
-        if not self.fpn_norms:
+        packed weight, shift = its bias) -- inference launches no batch-norm kernel.  FPN norms and backbone norms alike; the stem's fold
+        is stem_scale / stem_shift."""
+        if not self.fpn_norms and not self.backbone_norms:
             return
-        for c in list(self.lateral.values()) + list(self.output.values()):
+        for c in self.convs.values():
+            if c.norm is None:
+                continue
             if self.training:
                 c.row_scale = c.b = None
             else:
                 c.norm.fold()
                 c.row_scale, c.b = c.norm.fold_scale, c.norm.fold_shift
-            c.pack()
+            if pack:
+                c.pack()
+        if self.backbone_norms:
+            n = self.stem.norm
+            if self.training:
+                self.stem_scale = None             # (bd_stem_conv7x7_raw_fwd reads no shift)
+            else:
+                n.fold()
+                self.stem_scale, self.stem_shift = n.fold_scale, n.fold_shift
+            self.stem.row_scale = self.stem_scale
+            if pack:
+                ops.stem_weight_pack(self.stem_w, self.stem_scale, self.stem_packed)
         self._pack_table = None                # (it holds the row_scale pointers)
 
     # reference module protocol ------------------------------------------------------------------------
@@ -371,7 +428,7 @@ class FPNDetector:
         switch = bool(mode) != bool(self.training)
         self.training = mode
         if switch:
-            self._fold_fpn_norms()
+            self._fold_norms()
         return self
 
     def load_state_dict(self, states, strict=True):
@@ -395,6 +452,8 @@ class FPNDetector:
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.export(out)
         out["backbone.bottom_up.conv1.weight"] = self.stem_w.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+        if self.backbone_norms:
+            self.stem.norm.export(out)
         out.update({k: v.copy() for k, v in self._bn_params.items()})
         return out
 
@@ -417,6 +476,14 @@ class FPNDetector:
 
         if self.stem is None:       # (a trainable stem: the oracle must differentiate through its own stem and max-pool, not a constant)
             out["pool"] = nchw(pl.pool_out, pl.g_pool)
+        elif self.backbone_norms:   # under a live norm the stem's stored ReLU output: the oracle's norm and max-pool see the same gates
+            out["stem_out"] = nchw(pl.stem_out, pl.g_stem)
+            # (of the last backward(): dL/dz of every backbone norm, the bf16 terms its sums read)
+            out["g_stem_out"] = nchw(pl.grad_stem, pl.g_stem)
+            for blk, b in zip(self.blocks, pl.blk):
+                for i, (t, g) in enumerate(zip(b.g_mids, b.mid_geo)):
+                    out[f"g_{blk['prefix']}.a{i}"] = nchw(t, g)
+                out[f"g_{blk['prefix']}.out"] = nchw(b.g_out, b.gout)
         for blk, b in zip(self.blocks, pl.blk):
             pre = blk["prefix"]
             for i, (t, g) in enumerate(zip(b.mids, b.mid_geo)):
@@ -451,6 +518,8 @@ class FPNDetector:
 
     def reference_grads_names(self):
         names = [self.stem.name + ".weight"] if self.stem is not None else []
+        if self.backbone_norms:
+            names += [self.stem.norm.name + ".weight", self.stem.norm.name + ".bias"]
         for c in self.convs.values():
             if not c.trainable:
                 continue
@@ -495,6 +564,12 @@ class FPNDetector:
         if self.stem is not None:   # FREEZE_AT = 0: dL/d(pool_out) from layer1's first block, dL/d(pre-activation) of stem_out
             pl.grad_pool, pl.grad_stem = C.like(pl.pool_out), C.like(pl.stem_out)
             pl.g_image = ops.single(N, Hp, Wp)
+        bn_rows = []                            # (rows, C) of every normalised tensor: the reduction workspace fits the largest
+        if self.backbone_norms:
+            # the pre-norm output of every backbone convolution, kept for the backward pass, and the gradient with respect to it: buffers
+            # of their own, never reused within a step (the side stream's weight gradients read g_y late)
+            pl.stem_y, pl.stem_gy = C.like(pl.stem_out), C.like(pl.stem_out)
+            bn_rows.append((g2.pixels, 64))
         # backbone
         pl.blk = []
         gin = g4
@@ -551,6 +626,11 @@ class FPNDetector:
                 if (blk["kind"] == "bottleneck" and self.use_mask_bits
                         and ops.dense_1x1_bits_ok(blk["convs"][-1].desc(b.gout, b.gout))):
                     b.out_bits = C.empty((blk["cout"] // 32, b.gout.pixels), torch.int32)
+            if self.backbone_norms:
+                outs = b.mids + [b.out]
+                b.ys, b.gys = [C.like(t) for t in outs], [C.like(t) for t in outs]
+                b.y_ds, b.gy_ds = (C.like(b.idt), C.like(b.idt)) if b.idt is not None else (None, None)
+                bn_rows += [(t.shape[0], t.shape[1]) for t in outs]
             pl.blk.append(b)
             gin = b.gout
         # feature taps (last block of layer 2..4 -> res3..res5)
@@ -582,8 +662,9 @@ class FPNDetector:
             # buffer of its own: the top-down path still reads g_lat, the side stream's weight gradients read it late)
             pl.bn_y = {(k, s): C.like(pl.lat[s]) for k in ("lateral", "output") for s in self.fpn_stages}
             pl.bn_gy = {(k, s): C.like(pl.lat[s]) for k in ("lateral", "output") for s in self.fpn_stages}
-            rows = max(pl.blk[pl.res[s]].gout.pixels for s in self.fpn_stages)
-            pl.bn_ws = C.empty((ops.bn_workspace_bytes(rows, ch) // 4 + 64,), torch.float32)
+            bn_rows.append((max(pl.blk[pl.res[s]].gout.pixels for s in self.fpn_stages), ch))
+        if bn_rows:
+            pl.bn_ws = C.empty((max(ops.bn_workspace_bytes(r, c) for r, c in bn_rows) // 4 + 64,), torch.float32)
         g6 = pl.pyr.level(len(self.fpn_stages))
         pl.p6_relu = C.empty((N * h6 * w6, ch), bf)
         pl.g_p6r = ops.single(N, h6, w6)
@@ -736,6 +817,31 @@ class FPNDetector:
         convs[-1].forward(t, geos[-2], geos[-1], b.out, add=idt, relu=True, bits=b.out_bits, x8=t8, y8=b.out8)
         return b.out
 
+    def _norm_forward(self, n, y, geo, z, pl, residual=None, relu=True):
+        """Batch statistics of the pre-norm y (running statistics updated), then the one-pass epilogue z = [relu](BN(y) [+ residual])."""
+        B = BatchNormState
+        ops.bn_stats_fwd(y, geo, n.C, B.EPS, B.MOMENTUM, n.mean, n.inv_std, n.sums, n.running_mean, n.running_var, pl.bn_ws)
+        ops.bn_apply_act_fwd(y, geo, n.mean, n.inv_std, n.gamma, n.beta, z, geo, n.C, residual=residual, gr=geo, relu=relu)
+
+    def _block_forward_norm(self, blk, b, x, pl):
+        """_block_forward under a live backbone norm: every convolution runs bare into its pre-norm tensor; conv -> BN -> ReLU, the last
+        stage conv -> BN -> + identity -> ReLU (models/cls/resnet.py:42-52, 94-113), the shortcut convolution conv -> BN."""
+        convs = blk["convs"]
+        idt = x
+        if blk["ds"] is not None:
+            blk["ds"].forward(x, b.gin, b.gout, b.y_ds)
+            self._norm_forward(blk["ds"].norm, b.y_ds, b.gout, b.idt, pl, relu=False)
+            idt = b.idt
+        geos = [b.gin] + b.mid_geo + [b.gout]
+        t = x
+        for ci, c in enumerate(convs):
+            last = ci + 1 == len(convs)
+            c.forward(t, geos[ci], geos[ci + 1], b.ys[ci])
+            z = b.out if last else b.mids[ci]
+            self._norm_forward(c.norm, b.ys[ci], geos[ci + 1], z, pl, residual=idt if last else None)
+            t = z
+        return b.out
+
     def network_forward(self, pl):
         """RetinaNet.network_forward (retinanet.py:109-118): backbone + FPN + head; logits/offsets come out already
         in the (N, sum HWA, K) layout of permute_to_N_Any_K + concat (function.py:26-32, retinanet.py:127-132).
@@ -743,7 +849,13 @@ class FPNDetector:
         The stem runs as one launch (bd_stem_pool_fwd, MODEL.FUSE_STEM_POOL) while it is frozen.  Under MODEL.BACKBONE.FREEZE_AT = 0 the
         key is ignored: the backward pass reads the half-resolution stem output, so the two-launch form always runs."""
         N = pl.N
-        if self.fuse_stem_pool:
+        live = bool(self.backbone_norms) and self.training      # batch statistics in the backbone (evaluation: folded, the FrozenBN launches)
+        if live:
+            n = self.stem.norm
+            ops.stem_conv7x7_raw_fwd(N, pl.Hp, pl.Wp, pl.x_halo, self.stem_packed, pl.stem_y)
+            self._norm_forward(n, pl.stem_y, pl.g_stem, pl.stem_out, pl)
+            ops.maxpool3x3s2_fwd(pl.stem_out, N, pl.g_stem.H[0], pl.g_stem.W[0], 64, pl.pool_out)
+        elif self.fuse_stem_pool:
             ops.stem_pool_fwd(N, pl.Hp, pl.Wp, pl.x_halo, self.stem_packed, self.stem_shift, pl.pool_out)
         else:
             ops.stem_conv7x7_fwd(N, pl.Hp, pl.Wp, pl.x_halo, self.stem_packed, self.stem_shift, pl.stem_out)
@@ -751,7 +863,7 @@ class FPNDetector:
         x = pl.pool_out
         x8 = None
         for blk, b in zip(self.blocks, pl.blk):
-            x = self._block_forward(blk, b, x, x8)
+            x = self._block_forward_norm(blk, b, x, pl) if live else self._block_forward(blk, b, x, x8)
             x8 = b.out8
         # FPN (fpn_backbone.py:123-160): top-down from the coarsest level
         st = self.fpn_stages
@@ -936,6 +1048,51 @@ class FPNDetector:
     def _join_wgrads(self):
         self.wgrads.join()
 
+    def _norm_backward(self, n, g, y, geo, gy, pl):
+        """g = dL/dz of norm n (the masked gradient of a post-ReLU tensor IS that) -> dgamma / dbeta into the gradient arena and
+        gy = dL/dy, the gradient the convolution's weight and data gradient read."""
+        ops.bn_bwd_reduce(g, geo, y, geo, n.mean, n.inv_std, n.C, n.g_gamma, n.g_beta, pl.bn_ws)
+        return ops.bn_bwd_apply(g, geo, y, geo, n.mean, n.inv_std, n.gamma, n.g_gamma, n.g_beta, n.sums[0], gy, geo, n.C)
+
+    def _block_backward_norm(self, bi, pl, ws):
+        """One block of the backbone loop of backward() under a live backbone norm: the same gradient convention and residual fan-out,
+        with every convolution's weight and data gradient reading its norm's g_y.  The block-output gradient G feeds bn3's (bn2's)
+        backward and the shortcut: the identity add, or downsample.1's backward and the shortcut convolution.  The shortcut's data
+        gradient runs as a full-resolution pass (the sparse in-place route of the FrozenBN loop is not taken; the sums are the same)."""
+        blk, b = self.blocks[bi], pl.blk[bi]
+        convs, ds = blk["convs"], blk["ds"]
+        geos = [b.gin] + b.mid_geo + [b.gout]
+        xin = pl.blk[bi - 1].out if bi > 0 else pl.pool_out
+        G = b.g_out
+        g_ds = None
+        if ds is not None:
+            g_ds = self._norm_backward(ds.norm, G, b.y_ds, b.gout, b.gy_ds, pl)
+            self._wgrad(ds, xin, g_ds, b.gin, b.gout, ws)
+        g = G
+        for ci in range(len(convs) - 1, 0, -1):
+            gy = self._norm_backward(convs[ci].norm, g, b.ys[ci], geos[ci + 1], b.gys[ci], pl)
+            self._wgrad(convs[ci], b.mids[ci - 1], gy, geos[ci], geos[ci + 1], ws)
+            convs[ci].dgrad(gy, geos[ci], geos[ci + 1], b.g_mids[ci - 1], mask=b.mids[ci - 1])
+            g = b.g_mids[ci - 1]
+        gy = self._norm_backward(convs[0].norm, g, b.ys[0], geos[1], b.gys[0], pl)
+        self._wgrad(convs[0], xin, gy, geos[0], geos[1], ws)
+        if bi > 0:
+            gx = pl.blk[bi - 1].g_out
+            tapped = any(pl.res[s] == bi - 1 for s in self.fpn_stages)      # the FPN lateral of res3 / res4 wrote gx first
+            if ds is not None:
+                ds.dgrad(g_ds, b.gin, b.gout, gx, first=not tapped)
+                convs[0].dgrad(gy, geos[0], geos[1], gx, first=False, mask=xin)
+            elif tapped:
+                ops.add_bf16(gx, G, gx)
+                convs[0].dgrad(gy, geos[0], geos[1], gx, first=False, mask=xin)
+            else:
+                convs[0].dgrad(gy, geos[0], geos[1], gx, add_before=G, mask=xin)      # identity skip: gx = (dgrad + G) * mask
+        elif ds is not None:        # dL/d(pool_out): no gate (bd_maxpool3x3s2_bwd applies the stem's)
+            ds.dgrad(g_ds, b.gin, b.gout, pl.grad_pool, first=True)
+            convs[0].dgrad(gy, geos[0], geos[1], pl.grad_pool, first=False)
+        else:
+            convs[0].dgrad(gy, geos[0], geos[1], pl.grad_pool, add_before=G)
+
     def backward(self, on_bucket_ready=None):
         pl = self._cur
         probing = self.fp8_scaler.begin_step()
@@ -980,7 +1137,9 @@ class FPNDetector:
             if li == nl - 1:
                 if not pool_top:
                     join(top)
-                self.lateral[s].dgrad(g, b.gout, b.gout, b.g_out, first=pool_top, mask=b.out, maskbits=b.out_bits)
+                # (under a live backbone norm the gate bits are not written: bd_bn_apply_act_fwd produces the block output)
+                self.lateral[s].dgrad(g, b.gout, b.gout, b.g_out, first=pool_top, mask=b.out,
+                                      maskbits=None if self.backbone_norms else b.out_bits)
             else:
                 self.lateral[s].dgrad(g, b.gout, b.gout, b.g_out, first=True)
 
@@ -1025,6 +1184,13 @@ class FPNDetector:
             blk, b = self.blocks[bi], pl.blk[bi]
             if not blk["trainable"]:
                 break
+            if self.backbone_norms:
+                self._block_backward_norm(bi, pl, ws)
+                if bi == 0 or self.blocks[bi - 1]["layer"] != blk["layer"]:
+                    self._flush_wgrads()
+                    if on_bucket_ready:
+                        on_bucket_ready(f"layer{blk['layer']}", side)
+                continue
             convs = blk["convs"]
             geos = [b.gin] + b.mid_geo + [b.gout]
             xin = pl.blk[bi - 1].out if bi > 0 else pl.pool_out
@@ -1096,7 +1262,10 @@ class FPNDetector:
         if self.stem is not None:       # FREEZE_AT = 0 (csrc/stem_bwd.hip): through the max-pool and the stem's ReLU, then conv1's weight gradient
             gs = pl.g_stem
             ops.maxpool3x3s2_bwd(pl.grad_pool, pl.stem_out, pl.pool_out, pl.N, gs.H[0], gs.W[0], 64, pl.grad_stem)
-            self._wgrad(self.stem, pl.x_halo, pl.grad_stem, pl.g_image, gs, ws)
+            g_stem = pl.grad_stem
+            if self.backbone_norms:     # grad_stem is dL/dz of bn1 (gated by stem_out > 0): through the norm, no folded row scale
+                g_stem = self._norm_backward(self.stem.norm, pl.grad_stem, pl.stem_y, gs, pl.stem_gy, pl)
+            self._wgrad(self.stem, pl.x_halo, g_stem, pl.g_image, gs, ws)
             self._flush_wgrads()
             if on_bucket_ready:
                 on_bucket_ready("conv1", side)

@@ -210,12 +210,21 @@ def init_faster_rcnn_params(cfg, seed=0, residual_gamma=None):
     return p
 
 
-def trainable_names(params, freeze_at=2):
+def backbone_norm(cfg):
+    """MODEL.BACKBONE.NORM when it is a live batch norm ("BN" / "SyncBN"), else None ("FrozenBN"; FPNDetector.check_config refuses the rest)."""
+    n = cfg.MODEL.BACKBONE.get("NORM", "FrozenBN")
+    return n if n in ("BN", "SyncBN") else None
+
+
+def trainable_names(params, freeze_at=2, backbone_norm=None):
     """DetSolver.params (solver/default_solver.py:83-94): drop bottom_up.conv1 / layer1 by name; FrozenBN
-    statistics and affine terms never receive gradients (configs/extra_cfg.py:55)."""
+    statistics and affine terms never receive gradients (configs/extra_cfg.py:55).  backbone_norm ("BN" / "SyncBN", FREEZE_AT = 0 only):
+    the backbone norms' gamma / beta train, their running statistics stay buffers."""
     out = []
     for k in params:
-        if ".bn" in k or "downsample.1" in k or "running_" in k:
+        if "running_" in k:
+            continue
+        if (".bn" in k or "downsample.1" in k) and backbone_norm is None:
             continue
         if "bottom_up.conv1" in k and freeze_at >= 1:
             continue

@@ -330,6 +330,12 @@ def stem_conv7x7_fwd(N, H, W, x_halo, w_stem, bias, y):
     return y
 
 
+def stem_conv7x7_raw_fwd(N, H, W, x_halo, w_stem, y):
+    """The bare 7x7 convolution (no shift, no ReLU): the stem under a live backbone norm; w_stem packed without a row scale."""
+    check(L().bd_stem_conv7x7_raw_fwd(N, H, W, ptr(x_halo), ptr(w_stem), ptr(y), stream_ptr()), "bd_stem_conv7x7_raw_fwd")
+    return y
+
+
 def stem_weight_pack(w, row_scale, w_stem):
     check(L().bd_stem_weight_pack(ptr(w), ptr(row_scale), ptr(w_stem), stream_ptr()), "bd_stem_weight_pack")
 
@@ -904,6 +910,14 @@ def bn_stats_fwd(y, geom: Geom, Cn, eps, momentum, mean, inv_std, sums, running_
 def bn_apply_fwd(y, gy: Geom, mean, inv_std, gamma, beta, z, gz: Geom, Cn):
     check(L().bd_bn_apply_fwd(ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), ptr(z), *_lvl(gz), gy.N,
                               gy.H[0] * gy.W[0], Cn, stream_ptr()), "bd_bn_apply_fwd")
+    return z
+
+
+def bn_apply_act_fwd(y, gy: Geom, mean, inv_std, gamma, beta, z, gz: Geom, Cn, residual=None, gr: Geom = None, relu=True):
+    """z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]) in one pass (the backbone's epilogue under MODEL.BACKBONE.NORM)."""
+    rl = _lvl(gr if gr is not None else gz) if residual is not None else (0, 0)
+    check(L().bd_bn_apply_act_fwd(ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), ptr(residual), *rl, ptr(z), *_lvl(gz),
+                                  gy.N, gy.H[0] * gy.W[0], Cn, int(bool(relu)), stream_ptr()), "bd_bn_apply_act_fwd")
     return z
 
 

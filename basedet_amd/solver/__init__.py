@@ -197,6 +197,8 @@ class GradBuckets:
                 k = "fpn"
             else:
                 k = name.split(".")[2]     # backbone.bottom_up.layerX...
+                if k == "bn1":             # the stem's live norm (MODEL.BACKBONE.NORM): finished with conv1's weight gradient
+                    k = "conv1"
             lo, hi = groups.get(k, (off, off))
             groups[k] = (min(lo, off), max(hi, (off + n + 63) // 64 * 64))
         return groups
@@ -396,4 +398,6 @@ def broadcast_parameters(model, src=0):
         c.bcast(model.arena.w, root=src)
         if getattr(model, "fpn_norms", None):      # buffers: the FPN norm's running statistics
             c.bcast(model.bn_running, root=src)
+        if getattr(model, "backbone_norms", None):      # and the backbone norm's
+            c.bcast(model.bbn_running, root=src)
         model.repack_trainable()

@@ -256,6 +256,9 @@ int bd_wgrad_queue_flush(bd_wgrad_queue_t q, bd_stream_t stream);
  * w_stem: bf16 [64][7][8][4] as written by bd_stem_weight_pack; y: bf16 NHWC [N][H/2][W/2][64]. */
 int bd_stem_conv7x7_fwd(int N, int H, int W, const void* x_halo, const void* w_stem, const float* bias,
                         void* y, bd_stream_t stream);
+/* The bare stem convolution (bd_version() >= 110): no shift, no ReLU; w_stem packed without a row scale.  The training forward under
+ * MODEL.BACKBONE.NORM = "BN" / "SyncBN": bd_bn_stats_fwd and bd_bn_apply_act_fwd (ReLU) follow, then bd_maxpool3x3s2_fwd. */
+int bd_stem_conv7x7_raw_fwd(int N, int H, int W, const void* x_halo, const void* w_stem, void* y, bd_stream_t stream);
 /* The same stem followed by M.MaxPool2d(3, 2, 1) (models/cls/resnet.py:146,238-241) in one pass: y_pool = bf16 NHWC
  * [N][(H/2-1)/2+1][(W/2-1)/2+1][64], bit-identical to bd_stem_conv7x7_fwd + bd_maxpool3x3s2_fwd; the half-resolution
  * stem output is never written (the stem is frozen: solver/default_solver.py:83-94, so nothing else reads it). */
@@ -602,7 +605,7 @@ int bd_groupnorm_bwd(const void* dz, const void* y, const float* gamma, const fl
                      void* dy, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes, bd_stream_t stream);
 
 /* BatchNorm2d in training mode for the FPN's lateral / output convolutions (MODEL.FPN.NORM = "BN" / "SyncBN", fpn_backbone.py:49-76;
- * bd_version() >= 109; batchnorm.hip).  Every entry serves ONE pyramid level of a pixel-major bf16 tensor that may hold several: row r
+ * bd_version() >= 109; batchnorm.hip) and the backbone's (MODEL.BACKBONE.NORM, layers/backbone/build.py:27-30: dense tensors, one level).  Every entry serves ONE pyramid level of a pixel-major bf16 tensor that may hold several: row r
  * (r < N * n, n = H * W) of the level is pixel row (r / n) * pix_per_img + off + r % n of its buffer, C channels each, C % 8 == 0,
  * off + n <= pix_per_img; each tensor of a call has its own (pix_per_img, off).  Statistics and parameters are fp32 [C].  The reductions
  * are two-stage over fixed 128-row slots, combined in a fixed order, without floating-point atomics: the same bits on every run.
@@ -621,6 +624,13 @@ int bd_bn_stats_fwd(const void* y, int N, int64_t pix_per_img, int64_t off, int6
 int bd_bn_apply_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
                     const float* beta, void* z, int64_t z_pix_per_img, int64_t z_off, int N, int64_t n, int C,
                     bd_stream_t stream);
+/* The backbone's epilogue under MODEL.BACKBONE.NORM = "BN" / "SyncBN" (bd_version() >= 110; models/cls/resnet.py:42-52, 94-113, 238-240):
+ * z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]) in one pass over y (and the residual, NULL = none; bf16, its own
+ * (pix_per_img, off)).  Evaluated as bd_bn_apply_fwd: fp64 on the fp32 statistics, the residual added in fp64, ONE rounding to bf16, then
+ * the ReLU (relu != 0).  z must be neither y nor the residual: the backward pass reads both. */
+int bd_bn_apply_act_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
+                        const float* beta, const void* residual, int64_t r_pix_per_img, int64_t r_off, void* z, int64_t z_pix_per_img,
+                        int64_t z_off, int N, int64_t n, int C, int relu, bd_stream_t stream);
 /* dbeta[c] = sum g, dgamma[c] = sum g * xhat with xhat = (y - mean) * inv_std recomputed from the saved pre-norm y; both overwritten. */
 int bd_bn_bwd_reduce(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
                      const float* mean, const float* inv_std, int N, int64_t n, int C, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
