@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 110              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd)
+ABI_VERSION = 111              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd; 111: bd_bn_apply_fwd removed, bd_bn_apply_act_fwd serves its callers)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -147,7 +147,6 @@ SIGNATURES = {
     "bd_groupnorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _L, _I, _I, _P, _P, _P, _I, _P, _Z, _P]),
     "bd_bn_workspace_bytes": (_Z, [_L, _I]),
     "bd_bn_stats_fwd": (_I, [_P, _I, _L, _L, _L, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "bd_bn_apply_fwd": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _I, _L, _I, _P]),
     "bd_bn_apply_act_fwd": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _I, _L, _I, _I, _P]),
     "bd_bn_bwd_reduce": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _I, _L, _I, _P, _P, _P, _Z, _P]),
     "bd_bn_bwd_apply": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _I, _P]),

@@ -125,38 +125,14 @@ __global__ __launch_bounds__(8 * BN_FL) void bn_stats_final_kernel(const float* 
     if (sl == 0 && c < C) bn_write_stats(c, C, (float)M, red[0][cl][1], red[0][cl][2], eps, momentum, mean, inv_std, sums, running_mean, running_var);
 }
 
-// z = gamma * (y - mean) * inv_std + beta.  block = 32 chunk lanes x 8 row lanes (blockIdx.y: the 256-channel tile), rows grid-strided: a
-// thread keeps ONE chunk of 8 channels, so everything that depends only on the channel is formed once per thread.  The arithmetic is fp64
-// on the fp32 statistics: the pass is HBM-bound (three fp64 operations per element), and where gamma * xhat cancels against beta -- or
-// y against a mean of 100 std -- an fp32 evaluation is off by more than the bf16 ulp of the small result.  One rounding to fp32, one to bf16.
-__global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const bf16_raw* __restrict__ y, BnGeo gy, const float* __restrict__ mean,
-                                                           const float* __restrict__ inv_std, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, bf16_raw* __restrict__ z, BnGeo gz,
-                                                           long long n, long long M, int C) {
-    const int cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
-    const int c0 = (blockIdx.y * 32 + cl) * 8;
-    if (c0 >= C) return;
-    double A[8];
-    float mu[8], bt[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { A[k] = (double)gamma[c0 + k] * (double)inv_std[c0 + k]; mu[k] = mean[c0 + k]; bt[k] = beta[c0 + k]; }
-    for (long long r = (long long)blockIdx.x * BN_PXL + pl; r < M; r += (long long)gridDim.x * BN_PXL) {
-        float v[8], o[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(y + bn_row_addr(r, n, gy) * C + c0), v);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (float)(((double)v[k] - (double)mu[k]) * A[k] + (double)bt[k]);
-        u32x4_t w;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = pack_bf2(o[2 * k], o[2 * k + 1]);
-        *reinterpret_cast<u32x4_t*>(z + bn_row_addr(r, n, gz) * C + c0) = w;
-    }
-}
-
-// z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]): the epilogue of a backbone convolution under MODEL.BACKBONE.NORM = "BN" /
-// "SyncBN" (conv -> BN -> ReLU, and conv -> BN -> + identity -> ReLU in a block's last stage; models/cls/resnet.py:42-52, 94-113) in ONE
-// pass: read y and the residual, write z.  Layout and arithmetic are bn_apply_fwd_kernel's (fp64 on the fp32 statistics, per-channel terms
-// once per thread); the residual joins in fp64 BEFORE the single rounding, so a shortcut that cancels gamma * xhat + beta keeps the bits
-// of the small difference.
+// z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]): the epilogue of every normalised convolution in ONE pass (read y and the
+// residual, write z).  The FPN's norms (MODEL.FPN.NORM) take neither residual nor ReLU; the backbone's (MODEL.BACKBONE.NORM) are conv -> BN
+// -> ReLU, and conv -> BN -> + identity -> ReLU in a block's last stage (models/cls/resnet.py:42-52, 94-113).
+// block = 32 chunk lanes x 8 row lanes (blockIdx.y: the 256-channel tile), rows grid-strided: a thread keeps ONE chunk of 8 channels, so
+// everything that depends only on the channel is formed once per thread.  The arithmetic is fp64 on the fp32 statistics: the pass is
+// HBM-bound (three fp64 operations per element), and where gamma * xhat cancels against beta -- or y against a mean of 100 std -- an fp32
+// evaluation is off by more than the bf16 ulp of the small result.  One rounding to fp32, one to bf16; the residual joins in fp64 BEFORE
+// that single rounding, so a shortcut that cancels gamma * xhat + beta keeps the bits of the small difference.
 template <bool RES, bool RELU>
 __global__ __launch_bounds__(256) void bn_apply_act_fwd_kernel(const bf16_raw* __restrict__ y, BnGeo gy, const float* __restrict__ mean,
                                                                const float* __restrict__ inv_std, const float* __restrict__ gamma,
@@ -247,7 +223,7 @@ __global__ __launch_bounds__(8 * BN_FL) void bn_bwd_final_kernel(const float* __
 }
 
 // g_y = gamma * inv_std * (g - dbeta / M - xhat * dgamma / M), M = count[c] (the first vector of sums).  Layout and fp64 as in
-// bn_apply_fwd_kernel (the three terms cancel wherever the gradient is mostly its own mean); the divisions are per thread, not per element:
+// bn_apply_act_fwd_kernel (the three terms cancel wherever the gradient is mostly its own mean); the divisions are per thread, not per element:
 // g_y = A * (g - B - (y - mean) * E) with A = gamma * inv_std, B = dbeta / M, E = inv_std * dgamma / M
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_raw* __restrict__ g, BnGeo gg, const bf16_raw* __restrict__ y, BnGeo gy,
                                                            const float* __restrict__ mean, const float* __restrict__ inv_std,
@@ -306,21 +282,6 @@ extern "C" int bd_bn_stats_fwd(const void* y, int N, int64_t pix_per_img, int64_
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3(cdiv(C, 8)), dim3(8 * BN_FL), 0, st, (const float*)ws, S, M, C, eps, momentum, mean, inv_std,
                        sums, running_mean, running_var);
     BD_CHECK_LAUNCH("bd_bn_stats_fwd");
-    return BD_OK;
-}
-
-extern "C" int bd_bn_apply_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
-                               const float* beta, void* z, int64_t z_pix_per_img, int64_t z_off, int N, int64_t n, int C,
-                               bd_stream_t stream) {
-    BD_REQUIRE(y && mean && inv_std && gamma && beta && z, "bn_apply_fwd: null pointer");
-    BD_REQUIRE(N >= 1 && C >= 8 && C % 8 == 0 && bn_geo_ok(y_pix_per_img, y_off, n) && bn_geo_ok(z_pix_per_img, z_off, n),
-               "bn_apply_fwd: bad shape (N=%d C=%d)", N, C);
-    const long long M = (long long)N * n;
-    BD_REQUIRE(z != y, "bn_apply_fwd: the backward pass reads the pre-norm tensor: z needs a buffer of its own");
-    hipLaunchKernelGGL(bn_apply_fwd_kernel, bn_apply_grid(M, C), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)y,
-                       BnGeo{y_pix_per_img, y_off}, mean, inv_std, gamma, beta, (bf16_raw*)z, BnGeo{z_pix_per_img, z_off},
-                       (long long)n, M, C);
-    BD_CHECK_LAUNCH("bd_bn_apply_fwd");
     return BD_OK;
 }
 

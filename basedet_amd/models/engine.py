@@ -345,51 +345,6 @@ class ConvLayer:
         return max(n, ops.conv2d_wgrad_fp8_workspace_bytes(d)) if self.fp8_wgrad else n
 
 
-class BatchNormState:
-    """The norm record of one normalised convolution (MODEL.FPN.NORM = "BN" / "SyncBN", layers.get_norm at fpn_backbone.py:49-76, named
-    `<conv>.norm`; MODEL.BACKBONE.NORM, layers/backbone/build.py:27-30, named `...bnK` / `...downsample.1` like the FrozenBN it replaces):
-    gamma / beta are trainable fp32 vectors in the parameter arena, right behind the convolution's weight (`<name>.weight` / `.bias`);
-    the running statistics are buffers (`.running_mean` / `.running_var`); mean / inv_std / sums are the batch statistics of the last
-    training forward (sums = [M, sum y, sum y^2]; the backward pass reads the count M).  The buffers are rows of model-level tensors, so
-    that every norm's vectors of one kind are contiguous (one broadcast)."""
-
-    EPS, MOMENTUM = 1e-5, 0.1      # MegEngine's BatchNorm2d defaults (momentum 0.9 in its convention = 0.1 in torch's); documented choice
-
-    def __init__(self, name, C, running, stats, sums):
-        self.name, self.C = name, C
-        self.running_mean, self.running_var = running[0], running[1]
-        self.mean, self.inv_std = stats[0], stats[1]
-        self.sums = sums
-        self.gamma = self.beta = self.g_gamma = self.g_beta = None
-        self.fold_scale = torch.empty(C, dtype=torch.float32, device=running.device)      # eval(): the affine the convolution's epilogue applies
-        self.fold_shift = torch.empty(C, dtype=torch.float32, device=running.device)
-
-    def reserve(self, arena):
-        self._gi = arena.reserve(self.name + ".weight", (self.C,))
-        self._bi = arena.reserve(self.name + ".bias", (self.C,))
-
-    def bind(self, arena, params):
-        self.gamma, self.g_gamma = arena.view("w", self._gi), arena.view("g", self._gi)
-        self.beta, self.g_beta = arena.view("w", self._bi), arena.view("g", self._bi)
-        for t, k in ((self.gamma, "weight"), (self.beta, "bias"), (self.running_mean, "running_mean"), (self.running_var, "running_var")):
-            t.copy_(torch.from_numpy(np.asarray(params[f"{self.name}.{k}"], np.float32).reshape(-1)))
-
-    def export(self, out):
-        for t, k in ((self.gamma, "weight"), (self.beta, "bias"), (self.running_mean, "running_mean"), (self.running_var, "running_var")):
-            out[f"{self.name}.{k}"] = t.cpu().numpy().copy()
-
-    def export_grad(self, out):
-        out[self.name + ".weight"] = self.g_gamma.detach().cpu().clone()
-        out[self.name + ".bias"] = self.g_beta.detach().cpu().clone()
-
-    def fold(self):
-        """fold_scale / fold_shift from the running statistics, on the host like FrozenBN's (ConvLayer.bind): evaluation only."""
-        g, b = self.gamma.cpu().numpy(), self.beta.cpu().numpy()
-        scale = g / np.sqrt(self.running_var.cpu().numpy() + np.float32(self.EPS))
-        self.fold_scale.copy_(torch.from_numpy(scale.astype(np.float32)))
-        self.fold_shift.copy_(torch.from_numpy((b - self.running_mean.cpu().numpy() * scale).astype(np.float32)))
-
-
 class FusedPredConv(ConvLayer):
     """Several reference convs that read the same input, fused along Cout into one launch (FCOS bbox_pred [4] + ctrness [1]
     -> 5 rows, padded to 8).  Parameters are bound from / exported to the reference's separate tensors."""
@@ -443,6 +398,10 @@ class TrainableStem:
         out[self.name + ".weight"] = self.gw.permute(0, 3, 1, 2).contiguous().cpu()
         if self.norm is not None:
             self.norm.export_grad(out)
+
+    def forward(self, x, gin, gout, y):
+        """The bare convolution under a live norm (no shift, no ReLU; `packed`: the model's stem_packed, then without a row scale)."""
+        ops.stem_conv7x7_raw_fwd(gin.N, gin.H[0], gin.W[0], x, self.packed, y)
 
     def wgrad(self, x, g, gin, gout, ws, colsum_ws=None, x8=None, g8=None, queue=None):
         """x: x_halo of the padded batch (gin: its N x Hp x Wp geometry), g: dL/d(pre-activation) of the stem output."""

@@ -21,8 +21,9 @@ from ..ops import Geom
 from ..streams import SideStreams, fork, join
 from . import params as P
 from .. import comm as _comm
-from .engine import BatchNormState, ConvLayer, DeconvLayer, FCLayer, ParamArena, TrainableStem
+from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena, TrainableStem
 from .fp8_scaling import Fp8GradScaler, initial_grad_scale
+from .live_norm import BatchNormState, LiveNorms
 from .plan_arena import PlanArena, _Carver, _Plan, _round_up
 from .wgrad_sched import WgradScheduler
 
@@ -69,27 +70,28 @@ class FPNDetector:
                                  "filter freezes conv1 / layer1 by name but not their norms, so gamma / beta below the frozen convolutions "
                                  "would train through a data gradient without weight gradients -- that backward pass is not built; a live "
                                  "backbone norm runs at FREEZE_AT = 0")
-            if norm == "SyncBN" and _comm.world_size() > 1:
-                raise ValueError(f"MODEL.BACKBONE.NORM = 'SyncBN' at world size {_comm.world_size()} is not supported: the exchange of the batch "
-                                 "statistics between the ranks is not built; 'SyncBN' runs at world size 1 (as 'BN'), 'BN' at any world size "
-                                 "(statistics of the rank's own batch)")
-            if m.get("WEIGHT_DTYPE", "bf16") != "bf16":
-                raise ValueError(f"MODEL.BACKBONE.NORM = {norm!r} with MODEL.WEIGHT_DTYPE = {m.WEIGHT_DTYPE!r} is not supported: the fp8 twins "
-                                 "of the normalised backbone tensors are not built; use 'bf16'")
+            cls._check_live_norm("MODEL.BACKBONE.NORM", norm, m)
         fnorm = m.FPN.get("NORM", None)
         if fnorm not in (None, "BN", "SyncBN"):
             raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} is not supported: None (no FPN norm), 'BN' and 'SyncBN' are implemented")
-        if fnorm == "SyncBN" and _comm.world_size() > 1:
-            raise ValueError(f"MODEL.FPN.NORM = 'SyncBN' at world size {_comm.world_size()} is not supported: the exchange of the batch "
-                             "statistics between the ranks is not built; 'SyncBN' runs at world size 1 (as 'BN'), 'BN' at any world size "
-                             "(statistics of the rank's own batch)")
-        if fnorm is not None and m.get("WEIGHT_DTYPE", "bf16") != "bf16":
-            raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} with MODEL.WEIGHT_DTYPE = {m.WEIGHT_DTYPE!r} is not supported: the fp8 twins of the "
-                             "normalised FPN tensors are not built; use 'bf16'")
+        if fnorm is not None:
+            cls._check_live_norm("MODEL.FPN.NORM", fnorm, m)
         if cls.READS_FPN_UPSAMPLE:
             up = m.FPN.get("UPSAMPLE", "resize")
             if up not in ("resize", "deconv"):
                 raise ValueError(f"MODEL.FPN.UPSAMPLE = {up!r} is not supported: use 'resize' or 'deconv'")
+
+    @staticmethod
+    def _check_live_norm(key, norm, m):
+        """What a live norm ("BN" / "SyncBN") does not run with, under either key (MODEL.BACKBONE.NORM, MODEL.FPN.NORM)."""
+        if norm == "SyncBN" and _comm.world_size() > 1:
+            raise ValueError(f"{key} = 'SyncBN' at world size {_comm.world_size()} is not supported: the exchange of the batch "
+                             "statistics between the ranks is not built; 'SyncBN' runs at world size 1 (as 'BN'), 'BN' at any world size "
+                             "(statistics of the rank's own batch)")
+        if m.get("WEIGHT_DTYPE", "bf16") != "bf16":
+            what = "backbone" if "BACKBONE" in key else "FPN"
+            raise ValueError(f"{key} = {norm!r} with MODEL.WEIGHT_DTYPE = {m.WEIGHT_DTYPE!r} is not supported: the fp8 twins of the "
+                             f"normalised {what} tensors are not built; use 'bf16'")
 
     @staticmethod
     def check_anchor_config(cfg, matcher=True):
@@ -163,34 +165,20 @@ class FPNDetector:
         # (first: the arena follows the forward order) and the backward pass ends with the kernels of csrc/stem_bwd.hip
         self.stem = TrainableStem() if self.freeze_at < 1 else None
         # MODEL.BACKBONE.NORM = "BN" / "SyncBN" (layers/backbone/build.py:27-30; FREEZE_AT = 0 only, check_config): every bnK / downsample.1
-        # and the stem's bn1 is a live BatchNorm2d under the FrozenBN's name.  Their buffers are slices of three flat model-level tensors
-        # (one broadcast): per norm (2, C) running statistics, (2, C) batch statistics and (3, C) sums, in forward order
+        # and the stem's bn1 is a live BatchNorm2d under the FrozenBN's name.  self.norms owns every live norm of the model, the FPN's
+        # below too, and their buffers (live_norm.py): in forward order, allocated once every layer is known
         self.backbone_norm = P.backbone_norm(self.cfg)
-        self.backbone_norms = []
-        if self.backbone_norm is not None:
-            chans = [64] + [c for blk in self.blocks for c in
-                            ([blk["ch"], blk["ch"], blk["cout"]] if blk["kind"] == "bottleneck" else [blk["ch"], blk["cout"]])
-                            + ([blk["cout"]] if blk["has_ds"] else [])]
-            f32 = dict(dtype=torch.float32, device=dev)
-            tot = sum(chans)
-            self.bbn_running, self.bbn_stats, self.bbn_sums = torch.zeros(2 * tot, **f32), torch.zeros(2 * tot, **f32), torch.zeros(3 * tot, **f32)
-            self._bbn_off = 0
+        self.norms = LiveNorms(dev)
 
         def bb_norm(prefix, c):
             """(bn_prefix, norm) of one backbone convolution: the FrozenBN fold by name, or a live norm record."""
-            if self.backbone_norm is None:
-                return dict(bn=prefix)
-            o = self._bbn_off
-            self._bbn_off += c
-            n = BatchNormState(prefix, c, self.bbn_running[2 * o: 2 * (o + c)].view(2, c), self.bbn_stats[2 * o: 2 * (o + c)].view(2, c),
-                               self.bbn_sums[3 * o: 3 * (o + c)].view(3, c))
-            self.backbone_norms.append(n)
-            return dict(norm=n)
+            return dict(bn=prefix) if self.backbone_norm is None else dict(norm=self.norms.add(prefix, c))
 
+        self.stem_packed = torch.empty((64, 7, 8, 4), dtype=torch.bfloat16, device=dev)
         if self.stem is not None:
             self.stem.norm = bb_norm(bu + ".bn1", 64).get("norm")
+            self.stem.packed = self.stem_packed
             self.stem.reserve(self.arena)
-        self.stem_packed = torch.empty((64, 7, 8, 4), dtype=torch.bfloat16, device=dev)
 
         for blk in self.blocks:
             pre = blk["prefix"]
@@ -213,21 +201,11 @@ class FPNDetector:
         self.fpn_stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES]          # [3, 4, 5]
         ch = self.fpn_ch
         self.lateral, self.output = {}, {}
-        # MODEL.FPN.NORM = "BN" / "SyncBN" (fpn_backbone.py:49-76): biasless lateral / output convolutions, each followed by a BatchNorm2d.
-        # Norm i of fpn_norms is lateral i (i < number of stages) or output i - stages: the model-level buffers keep every kind contiguous
+        # MODEL.FPN.NORM = "BN" / "SyncBN" (fpn_backbone.py:49-76): biasless lateral / output convolutions, each followed by a BatchNorm2d
+        # (in self.norms: every lateral's, then every output convolution's)
         self.fpn_norm = m.FPN.get("NORM", None)
-        self.fpn_norms = []
-        nrm = {}
-        if self.fpn_norm is not None:
-            nn_ = 2 * len(self.fpn_stages)
-            f32 = dict(dtype=torch.float32, device=dev)
-            self.bn_running, self.bn_stats = torch.zeros((nn_, 2, ch), **f32), torch.zeros((nn_, 2, ch), **f32)
-            self.bn_sums = torch.zeros((nn_, 3, ch), **f32)
-            for kind in ("lateral", "output"):
-                for s in self.fpn_stages:
-                    i = len(self.fpn_norms)
-                    nrm[kind, s] = BatchNormState(f"backbone.fpn_{kind}{s}.norm", ch, self.bn_running[i], self.bn_stats[i], self.bn_sums[i])
-                    self.fpn_norms.append(nrm[kind, s])
+        nrm = {(kind, s): self.norms.add(f"backbone.fpn_{kind}{s}.norm", ch) for kind in ("lateral", "output")
+               for s in (self.fpn_stages if self.fpn_norm is not None else ())}
         for s, ci in zip(self.fpn_stages, m.BACKBONE.OUT_FEATURE_CHANNELS):
             self.lateral[s] = add(f"backbone.fpn_lateral{s}", ci, ch, 1, 1, 0, bias=self.fpn_norm is None, norm=nrm.get(("lateral", s)))
             self.output[s] = add(f"backbone.fpn_output{s}", ch, ch, 3, 1, 1, bias=self.fpn_norm is None, norm=nrm.get(("output", s)))
@@ -246,6 +224,7 @@ class FPNDetector:
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.reserve(self.arena)
         self.arena.allocate()
+        self.norms.allocate()
         # (a trainable stem needs its half-resolution output in the backward pass: FREEZE_AT = 0 always runs the two launches)
         self.fuse_stem_pool = bool(m.get("FUSE_STEM_POOL", True)) and self.stem is None
         # frozen bottleneck blocks (layer1 under FREEZE_AT = 2) in one launch each: the two mid tensors and the residual re-read never
@@ -391,7 +370,7 @@ class FPNDetector:
         for c in self.convs.values():
             if (c.fp8 or c.fp8_1x1 or c.fp8_1x1_dgrad) and c.trainable:
                 c.pack_fp8()
-        if (self.fpn_norms or self.backbone_norms) and not self.training:       # evaluating (ModelEMA.applied() swaps the weights in): the folded affine follows gamma / beta
+        if self.norms and not self.training:       # evaluating (ModelEMA.applied() swaps the weights in): the folded affine follows gamma / beta
             self._fold_norms()
 
     def _fold_norms(self, pack=True):
@@ -399,7 +378,7 @@ class FPNDetector:
         statistics and gamma / beta become the per-channel affine of the convolution's own launch, as FrozenBN's (scale folded into the
         packed weight, shift = its bias) -- inference launches no batch-norm kernel.  FPN norms and backbone norms alike; the stem's fold
         is stem_scale / stem_shift."""
-        if not self.fpn_norms and not self.backbone_norms:
+        if not self.norms:
             return
         for c in self.convs.values():
             if c.norm is None:
@@ -411,8 +390,8 @@ class FPNDetector:
                 c.row_scale, c.b = c.norm.fold_scale, c.norm.fold_shift
             if pack:
                 c.pack()
-        if self.backbone_norms:
-            n = self.stem.norm
+        n = getattr(self.stem, "norm", None)
+        if n is not None:
             if self.training:
                 self.stem_scale = None             # (bd_stem_conv7x7_raw_fwd reads no shift)
             else:
@@ -452,7 +431,7 @@ class FPNDetector:
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.export(out)
         out["backbone.bottom_up.conv1.weight"] = self.stem_w.permute(0, 3, 1, 2).contiguous().cpu().numpy()
-        if self.backbone_norms:
+        if getattr(self.stem, "norm", None) is not None:
             self.stem.norm.export(out)
         out.update({k: v.copy() for k, v in self._bn_params.items()})
         return out
@@ -476,7 +455,7 @@ class FPNDetector:
 
         if self.stem is None:       # (a trainable stem: the oracle must differentiate through its own stem and max-pool, not a constant)
             out["pool"] = nchw(pl.pool_out, pl.g_pool)
-        elif self.backbone_norms:   # under a live norm the stem's stored ReLU output: the oracle's norm and max-pool see the same gates
+        elif self.stem.norm is not None:   # under a live norm the stem's stored ReLU output: the oracle's norm and max-pool see the same gates
             out["stem_out"] = nchw(pl.stem_out, pl.g_stem)
             # (of the last backward(): dL/dz of every backbone norm, the bf16 terms its sums read)
             out["g_stem_out"] = nchw(pl.grad_stem, pl.g_stem)
@@ -518,7 +497,7 @@ class FPNDetector:
 
     def reference_grads_names(self):
         names = [self.stem.name + ".weight"] if self.stem is not None else []
-        if self.backbone_norms:
+        if getattr(self.stem, "norm", None) is not None:
             names += [self.stem.norm.name + ".weight", self.stem.norm.name + ".bias"]
         for c in self.convs.values():
             if not c.trainable:
@@ -564,12 +543,8 @@ class FPNDetector:
         if self.stem is not None:   # FREEZE_AT = 0: dL/d(pool_out) from layer1's first block, dL/d(pre-activation) of stem_out
             pl.grad_pool, pl.grad_stem = C.like(pl.pool_out), C.like(pl.stem_out)
             pl.g_image = ops.single(N, Hp, Wp)
-        bn_rows = []                            # (rows, C) of every normalised tensor: the reduction workspace fits the largest
-        if self.backbone_norms:
-            # the pre-norm output of every backbone convolution, kept for the backward pass, and the gradient with respect to it: buffers
-            # of their own, never reused within a step (the side stream's weight gradients read g_y late)
-            pl.stem_y, pl.stem_gy = C.like(pl.stem_out), C.like(pl.stem_out)
-            bn_rows.append((g2.pixels, 64))
+        # (live norm, dense geometry of its convolution's output), in forward order
+        normed = [(self.stem.norm, g2)] if getattr(self.stem, "norm", None) is not None else []
         # backbone
         pl.blk = []
         gin = g4
@@ -626,11 +601,8 @@ class FPNDetector:
                 if (blk["kind"] == "bottleneck" and self.use_mask_bits
                         and ops.dense_1x1_bits_ok(blk["convs"][-1].desc(b.gout, b.gout))):
                     b.out_bits = C.empty((blk["cout"] // 32, b.gout.pixels), torch.int32)
-            if self.backbone_norms:
-                outs = b.mids + [b.out]
-                b.ys, b.gys = [C.like(t) for t in outs], [C.like(t) for t in outs]
-                b.y_ds, b.gy_ds = (C.like(b.idt), C.like(b.idt)) if b.idt is not None else (None, None)
-                bn_rows += [(t.shape[0], t.shape[1]) for t in outs]
+            normed += [(c.norm, g) for c, g in zip(blk["convs"] + [blk["ds"]], b.mid_geo + [b.gout, b.gout])
+                       if c is not None and c.norm is not None]
             pl.blk.append(b)
             gin = b.gout
         # feature taps (last block of layer 2..4 -> res3..res5)
@@ -657,14 +629,15 @@ class FPNDetector:
                  if self.TOP_BLOCK == "p6p7" and all(c.fp8 for c in writers) else None)
         pl.lat = {s: act(pl.blk[pl.res[s]].gout, ch) for s in self.fpn_stages}
         pl.g_lat = {s: C.like(pl.lat[s]) for s in self.fpn_stages}
-        if self.fpn_norms:
-            # the pre-norm output of every normalised convolution, kept for the backward pass, and the gradient with respect to it (a
-            # buffer of its own: the top-down path still reads g_lat, the side stream's weight gradients read it late)
-            pl.bn_y = {(k, s): C.like(pl.lat[s]) for k in ("lateral", "output") for s in self.fpn_stages}
-            pl.bn_gy = {(k, s): C.like(pl.lat[s]) for k in ("lateral", "output") for s in self.fpn_stages}
-            bn_rows.append((max(pl.blk[pl.res[s]].gout.pixels for s in self.fpn_stages), ch))
-        if bn_rows:
-            pl.bn_ws = C.empty((max(ops.bn_workspace_bytes(r, c) for r, c in bn_rows) // 4 + 64,), torch.float32)
+        normed += [(c[s].norm, pl.blk[pl.res[s]].gout) for c in (self.lateral, self.output) for s in self.fpn_stages if c[s].norm is not None]
+        # the pre-norm output of every normalised convolution, kept for the backward pass, and the gradient with respect to it: buffers of
+        # their own, never reused within a step (the FPN's top-down path still reads g_lat, the side stream's weight gradients read g_y
+        # late); the reduction workspace fits the largest
+        pl.norm_y, pl.norm_gy, pl.norm_geo = {}, {}, {}
+        for n, g in normed:
+            pl.norm_y[n.name], pl.norm_gy[n.name], pl.norm_geo[n.name] = act(g, n.C), act(g, n.C), g
+        if normed:
+            pl.bn_ws = C.empty((max(ops.bn_workspace_bytes(g.pixels, n.C) for n, g in normed) // 4 + 64,), torch.float32)
         g6 = pl.pyr.level(len(self.fpn_stages))
         pl.p6_relu = C.empty((N * h6 * w6, ch), bf)
         pl.g_p6r = ops.single(N, h6, w6)
@@ -817,28 +790,30 @@ class FPNDetector:
         convs[-1].forward(t, geos[-2], geos[-1], b.out, add=idt, relu=True, bits=b.out_bits, x8=t8, y8=b.out8)
         return b.out
 
-    def _norm_forward(self, n, y, geo, z, pl, residual=None, relu=True):
-        """Batch statistics of the pre-norm y (running statistics updated), then the one-pass epilogue z = [relu](BN(y) [+ residual])."""
-        B = BatchNormState
-        ops.bn_stats_fwd(y, geo, n.C, B.EPS, B.MOMENTUM, n.mean, n.inv_std, n.sums, n.running_mean, n.running_var, pl.bn_ws)
-        ops.bn_apply_act_fwd(y, geo, n.mean, n.inv_std, n.gamma, n.beta, z, geo, n.C, residual=residual, gr=geo, relu=relu)
+    def _conv_norm_forward(self, conv, x, gin, gout, z, gz, pl, residual=None, relu=False):
+        """A convolution under a live norm, in training mode: the bare convolution into its pre-norm tensor pl.norm_y (kept for the backward
+        pass), the batch statistics of that (running statistics updated), then the one-pass epilogue z = [relu](BN(y) [+ residual]).
+        gz: z's geometry -- gout's dense one, or a level of the pyramid."""
+        n, B = conv.norm, BatchNormState
+        y = pl.norm_y[n.name]
+        conv.forward(x, gin, gout, y)
+        ops.bn_stats_fwd(y, gout, n.C, B.EPS, B.MOMENTUM, n.mean, n.inv_std, n.sums, n.running_mean, n.running_var, pl.bn_ws)
+        ops.bn_apply_act_fwd(y, gout, n.mean, n.inv_std, n.gamma, n.beta, z, gz, n.C, residual=residual, gr=gout, relu=relu)
 
     def _block_forward_norm(self, blk, b, x, pl):
-        """_block_forward under a live backbone norm: every convolution runs bare into its pre-norm tensor; conv -> BN -> ReLU, the last
-        stage conv -> BN -> + identity -> ReLU (models/cls/resnet.py:42-52, 94-113), the shortcut convolution conv -> BN."""
+        """_block_forward under a live backbone norm: conv -> BN -> ReLU, the last stage conv -> BN -> + identity -> ReLU
+        (models/cls/resnet.py:42-52, 94-113), the shortcut convolution conv -> BN."""
         convs = blk["convs"]
         idt = x
         if blk["ds"] is not None:
-            blk["ds"].forward(x, b.gin, b.gout, b.y_ds)
-            self._norm_forward(blk["ds"].norm, b.y_ds, b.gout, b.idt, pl, relu=False)
+            self._conv_norm_forward(blk["ds"], x, b.gin, b.gout, b.idt, b.gout, pl)
             idt = b.idt
         geos = [b.gin] + b.mid_geo + [b.gout]
         t = x
         for ci, c in enumerate(convs):
             last = ci + 1 == len(convs)
-            c.forward(t, geos[ci], geos[ci + 1], b.ys[ci])
             z = b.out if last else b.mids[ci]
-            self._norm_forward(c.norm, b.ys[ci], geos[ci + 1], z, pl, residual=idt if last else None)
+            self._conv_norm_forward(c, t, geos[ci], geos[ci + 1], z, geos[ci + 1], pl, residual=idt if last else None, relu=True)
             t = z
         return b.out
 
@@ -849,11 +824,9 @@ class FPNDetector:
         The stem runs as one launch (bd_stem_pool_fwd, MODEL.FUSE_STEM_POOL) while it is frozen.  Under MODEL.BACKBONE.FREEZE_AT = 0 the
         key is ignored: the backward pass reads the half-resolution stem output, so the two-launch form always runs."""
         N = pl.N
-        live = bool(self.backbone_norms) and self.training      # batch statistics in the backbone (evaluation: folded, the FrozenBN launches)
+        live = self.backbone_norm is not None and self.training      # batch statistics in the backbone (evaluation: folded, the FrozenBN launches)
         if live:
-            n = self.stem.norm
-            ops.stem_conv7x7_raw_fwd(N, pl.Hp, pl.Wp, pl.x_halo, self.stem_packed, pl.stem_y)
-            self._norm_forward(n, pl.stem_y, pl.g_stem, pl.stem_out, pl)
+            self._conv_norm_forward(self.stem, pl.x_halo, pl.g_image, pl.g_stem, pl.stem_out, pl.g_stem, pl, relu=True)
             ops.maxpool3x3s2_fwd(pl.stem_out, N, pl.g_stem.H[0], pl.g_stem.W[0], 64, pl.pool_out)
         elif self.fuse_stem_pool:
             ops.stem_pool_fwd(N, pl.Hp, pl.Wp, pl.x_halo, self.stem_packed, self.stem_shift, pl.pool_out)
@@ -878,71 +851,30 @@ class FPNDetector:
                 self.p6.forward(b5.out, b5.gout, g6, pl.P, y8=pl.P8)
                 self._relu_level(pl.P, g6, pl.p6_relu)
                 self.p7.forward(pl.p6_relu, pl.g_p6r, g7, pl.P, y8=pl.P8)
-        levels = range(nl - 1, -1, -1)
-        if self.fpn_norms and self.training:       # batch statistics: the norm kernels between the launches (evaluation: folded, the loop below)
-            self._fpn_forward_norm(pl)
-            levels = ()
+        def conv(c, x, g, z, gz, **kw):
+            """One lateral / output convolution, x at the level's dense geometry g -> z at gz.  Under MODEL.FPN.NORM in training mode
+            z = BN(conv(x)) with batch statistics over all N H W pixels of the level (evaluation: folded into the convolution's launch)."""
+            if c.norm is not None and self.training:
+                self._conv_norm_forward(c, x, g, g, z, gz, pl)
+            else:
+                c.forward(x, g, gz, z, **kw)
+
         prev, prev_geo = None, None
-        for li in levels:
+        for li in range(nl - 1, -1, -1):
             s = st[li]
             b = pl.blk[pl.res[s]]
-            self.lateral[s].forward(b.out, b.gout, b.gout, pl.lat[s])
+            conv(self.lateral[s], b.out, b.gout, pl.lat[s], b.gout)
             if prev is not None and self.fpn_deconv:     # lat_s = lateral + deconv(lat_{s+1}), one rounding, in place
                 self.upsample[st[li + 1]].forward(prev, prev_geo, pl.lat[s], add=pl.lat[s])
             elif prev is not None:
                 ops.upsample2x_add_fwd(prev, prev_geo, pl.lat[s], b.gout, self.fpn_ch)
-            self.output[s].forward(pl.lat[s], b.gout, pl.pyr.level(li), pl.P, y8=pl.P8)
+            conv(self.output[s], pl.lat[s], b.gout, pl.P, pl.pyr.level(li), y8=pl.P8)
             prev, prev_geo = pl.lat[s], b.gout
         if self.TOP_BLOCK == "p6p7":
             join(side)
         else:
             ops.subsample2x_fwd(pl.P, pl.pyr.level(nl - 1), pl.P, pl.pyr.level(nl), self.fpn_ch)   # FPNP6 (:172-183)
         self.head_forward(pl)
-
-    def _fpn_forward_norm(self, pl):
-        """The FPN's lateral / output convolutions with MODEL.FPN.NORM in training mode: lat_s = BN(conv(res_s)) + top-down,
-        P_s = BN(conv(lat_s)), batch statistics over all N H W pixels of the level.  The laterals do not depend on each other, nor do the
-        output convolutions once every lat_s exists."""
-        st, ch = self.fpn_stages, self.fpn_ch
-        B = BatchNormState
-        geo = {s: pl.blk[pl.res[s]].gout for s in st}
-        for s in st:
-            b = pl.blk[pl.res[s]]
-            self.lateral[s].forward(b.out, b.gout, b.gout, pl.bn_y["lateral", s])
-        for s in st:
-            n = self.lateral[s].norm
-            ops.bn_stats_fwd(pl.bn_y["lateral", s], geo[s], ch, B.EPS, B.MOMENTUM, n.mean, n.inv_std, n.sums, n.running_mean, n.running_var,
-                             pl.bn_ws)
-        prev = None
-        for s in reversed(st):
-            n = self.lateral[s].norm
-            ops.bn_apply_fwd(pl.bn_y["lateral", s], geo[s], n.mean, n.inv_std, n.gamma, n.beta, pl.lat[s], geo[s], ch)
-            if prev is not None and self.fpn_deconv:
-                self.upsample[prev].forward(pl.lat[prev], geo[prev], pl.lat[s], add=pl.lat[s])
-            elif prev is not None:
-                ops.upsample2x_add_fwd(pl.lat[prev], geo[prev], pl.lat[s], geo[s], ch)
-            prev = s
-        for s in st:
-            self.output[s].forward(pl.lat[s], geo[s], geo[s], pl.bn_y["output", s])
-        for s in st:
-            n = self.output[s].norm
-            ops.bn_stats_fwd(pl.bn_y["output", s], geo[s], ch, B.EPS, B.MOMENTUM, n.mean, n.inv_std, n.sums, n.running_mean, n.running_var,
-                             pl.bn_ws)
-        for li, s in enumerate(st):
-            n = self.output[s].norm
-            ops.bn_apply_fwd(pl.bn_y["output", s], geo[s], n.mean, n.inv_std, n.gamma, n.beta, pl.P, pl.pyr.level(li), ch)
-
-    def _bn_backward(self, kind, gs, ggeos, pl):
-        """Through the norms of one group (every lateral, or every output convolution): dgamma / dbeta into the gradient arena, g_y into
-        pl.bn_gy."""
-        st, ch = self.fpn_stages, self.fpn_ch
-        convs = self.lateral if kind == "lateral" else self.output
-        geo = {s: pl.blk[pl.res[s]].gout for s in st}
-        for s, g, gg in zip(st, gs, ggeos):
-            n = convs[s].norm
-            ops.bn_bwd_reduce(g, gg, pl.bn_y[kind, s], geo[s], n.mean, n.inv_std, ch, n.g_gamma, n.g_beta, pl.bn_ws)
-            ops.bn_bwd_apply(g, gg, pl.bn_y[kind, s], geo[s], n.mean, n.inv_std, n.gamma, n.g_gamma, n.g_beta, n.sums[0], pl.bn_gy[kind, s],
-                             geo[s], ch)
 
     def _relu_level(self, src, geo, dst):
         """dst (dense, per level) = relu(one pyramid level of src); the level is contiguous per image."""
@@ -1048,13 +980,15 @@ class FPNDetector:
     def _join_wgrads(self):
         self.wgrads.join()
 
-    def _norm_backward(self, n, g, y, geo, gy, pl):
-        """g = dL/dz of norm n (the masked gradient of a post-ReLU tensor IS that) -> dgamma / dbeta into the gradient arena and
-        gy = dL/dy, the gradient the convolution's weight and data gradient read."""
-        ops.bn_bwd_reduce(g, geo, y, geo, n.mean, n.inv_std, n.C, n.g_gamma, n.g_beta, pl.bn_ws)
-        return ops.bn_bwd_apply(g, geo, y, geo, n.mean, n.inv_std, n.gamma, n.g_gamma, n.g_beta, n.sums[0], gy, geo, n.C)
+    def _norm_backward(self, n, g, gg, pl):
+        """g = dL/dz of norm n at geometry gg (the masked gradient of a post-ReLU tensor IS that; an FPN output norm reads a level of
+        g_P) -> dgamma / dbeta into the gradient arena and gy = dL/dy (pl.norm_gy, dense), the gradient the convolution's weight and data
+        gradient read."""
+        y, gy, geo = pl.norm_y[n.name], pl.norm_gy[n.name], pl.norm_geo[n.name]
+        ops.bn_bwd_reduce(g, gg, y, geo, n.mean, n.inv_std, n.C, n.g_gamma, n.g_beta, pl.bn_ws)
+        return ops.bn_bwd_apply(g, gg, y, geo, n.mean, n.inv_std, n.gamma, n.g_gamma, n.g_beta, n.sums[0], gy, geo, n.C)
 
-    def _block_backward_norm(self, bi, pl, ws):
+    def _block_backward_norm(self, bi, pl, ws, cws):
         """One block of the backbone loop of backward() under a live backbone norm: the same gradient convention and residual fan-out,
         with every convolution's weight and data gradient reading its norm's g_y.  The block-output gradient G feeds bn3's (bn2's)
         backward and the shortcut: the identity add, or downsample.1's backward and the shortcut convolution.  The shortcut's data
@@ -1066,15 +1000,15 @@ class FPNDetector:
         G = b.g_out
         g_ds = None
         if ds is not None:
-            g_ds = self._norm_backward(ds.norm, G, b.y_ds, b.gout, b.gy_ds, pl)
+            g_ds = self._norm_backward(ds.norm, G, b.gout, pl)
             self._wgrad(ds, xin, g_ds, b.gin, b.gout, ws)
         g = G
         for ci in range(len(convs) - 1, 0, -1):
-            gy = self._norm_backward(convs[ci].norm, g, b.ys[ci], geos[ci + 1], b.gys[ci], pl)
+            gy = self._norm_backward(convs[ci].norm, g, geos[ci + 1], pl)
             self._wgrad(convs[ci], b.mids[ci - 1], gy, geos[ci], geos[ci + 1], ws)
             convs[ci].dgrad(gy, geos[ci], geos[ci + 1], b.g_mids[ci - 1], mask=b.mids[ci - 1])
             g = b.g_mids[ci - 1]
-        gy = self._norm_backward(convs[0].norm, g, b.ys[0], geos[1], b.gys[0], pl)
+        gy = self._norm_backward(convs[0].norm, g, geos[1], pl)
         self._wgrad(convs[0], xin, gy, geos[0], geos[1], ws)
         if bi > 0:
             gx = pl.blk[bi - 1].g_out
@@ -1092,6 +1026,75 @@ class FPNDetector:
             convs[0].dgrad(gy, geos[0], geos[1], pl.grad_pool, first=False)
         else:
             convs[0].dgrad(gy, geos[0], geos[1], pl.grad_pool, add_before=G)
+
+    def _block_backward(self, bi, pl, ws, cws):
+        """One block of the backbone loop of backward() under FrozenBN (folded into the convolutions)."""
+        blk, b = self.blocks[bi], pl.blk[bi]
+        st = self.fpn_stages
+        convs = blk["convs"]
+        geos = [b.gin] + b.mid_geo + [b.gout]
+        xin = pl.blk[bi - 1].out if bi > 0 else pl.pool_out
+        prev_tr = bi > 0 and self.blocks[bi - 1]["trainable"]
+        G = b.g_out
+        # the shortcut convolution's weight gradient needs only the block's input and output gradient: first in the side
+        # stream's queue, not last (after the final block nothing is left on the main stream to hide it)
+        if blk["ds"] is not None:
+            self._wgrad(blk["ds"], xin, G, b.gin, b.gout, ws)
+        # main branch, last conv backwards
+        g = G
+        # fp8 mode: the e5m2 twin of the block's output gradient, written by the next block's conv1 data gradient (its last writer)
+        g8 = b.g_out8 if (b.g_out8 is not None and b.g_out8_ready) else None
+        for ci in range(len(convs) - 1, 0, -1):
+            # conv2's weight gradient from the twins both neighbours wrote (conv1's forward output, conv3's data gradient)
+            wx8 = b.mid8 if (ci == 1 and len(convs) == 3) else None
+            self._wgrad(convs[ci], b.mids[ci - 1], g, geos[ci], geos[ci + 1], ws, x8=wx8, g8=g8 if wx8 is not None else None)
+            # conv3's (dense 1x1) data gradient also writes the e5m2 twin that conv2's fp8 data gradient reads, conv2's the one
+            # conv1's reads
+            nxt = None
+            if len(convs) == 3:
+                nxt = b.g_mid8 if ci == 2 else b.g_mid8a
+            if nxt is not None and not convs[ci].dgrad_writes_twin(geos[ci], geos[ci + 1]):
+                nxt = None
+            wrote = convs[ci].dgrad(g, geos[ci], geos[ci + 1], b.g_mids[ci - 1], mask=b.mids[ci - 1], g8=g8, dx8=nxt,
+                                    q_scale=convs[ci - 1].grad_scale)
+            g, g8 = b.g_mids[ci - 1], (nxt if wrote else None)
+        self._wgrad(convs[0], xin, g, geos[0], geos[1], ws)
+        if prev_tr:
+            gx = pl.blk[bi - 1].g_out
+            xbits = pl.blk[bi - 1].out_bits if ops.dense_1x1_bits_ok(convs[0].desc(geos[0], geos[1])) else None
+            # has the input already received a contribution (FPN lateral of res3/res4)?
+            tapped = any(pl.res[s] == bi - 1 for s in st)
+            # conv1's data gradient is the LAST writer of the previous block's output gradient: it also writes that gradient's e5m2
+            # twin (fp8 mode) for the previous block's conv3
+            pb = pl.blk[bi - 1]
+            gx8 = pb.g_out8
+            # ... written with the scale of its consumer, the previous block's conv3 (another scale group at a layer boundary)
+            kw = dict(mask=xin, maskbits=xbits, g8=g8, dx8=gx8, q_scale=self.blocks[bi - 1]["convs"][-1].grad_scale)
+            if blk["ds"] is not None and gx8 is None and self.sparse_shortcut_grad:
+                # conv1 first (writes every pixel, gated), then the stride-2 shortcut adds its gradient IN PLACE at the quarter of
+                # the pixels it reaches ((a m + b) m = (a + b) m for a 0 / 1 gate m): instead of a full-resolution tensor that is
+                # three quarters zeros being written, read back and summed
+                wrote = convs[0].dgrad(g, geos[0], geos[1], gx, first=not tapped, **kw)
+                blk["ds"].dgrad(G, b.gin, b.gout, gx, first=False, mask=xin, sparse=True)
+            elif blk["ds"] is not None:         # (the last writer must be the launch that can write the e5m2 twin)
+                blk["ds"].dgrad(G, b.gin, b.gout, gx, first=not tapped)
+                wrote = convs[0].dgrad(g, geos[0], geos[1], gx, first=False, **kw)
+            else:
+                if tapped:
+                    ops.add_bf16(gx, G, gx)
+                    wrote = convs[0].dgrad(g, geos[0], geos[1], gx, first=False, **kw)
+                else:
+                    # identity skip: gx = (dgrad + G) * mask
+                    wrote = convs[0].dgrad(g, geos[0], geos[1], gx, add_before=G, **kw)
+            pb.g_out8_ready = gx8 is not None and bool(wrote)     # what the launch actually did (a bf16 fallback drops the twin)
+        elif bi == 0 and self.stem is not None:
+            # dL/d(pool_out): the same residual fan-in, without a gate -- pool_out is a max-pool output, the stem's ReLU gate is
+            # applied by bd_maxpool3x3s2_bwd below
+            if blk["ds"] is not None:
+                blk["ds"].dgrad(G, b.gin, b.gout, pl.grad_pool, first=True)
+                convs[0].dgrad(g, geos[0], geos[1], pl.grad_pool, first=False)
+            else:                    # BasicBlock, identity shortcut
+                convs[0].dgrad(g, geos[0], geos[1], pl.grad_pool, add_before=G)
 
     def backward(self, on_bucket_ready=None):
         pl = self._cur
@@ -1139,23 +1142,20 @@ class FPNDetector:
                     join(top)
                 # (under a live backbone norm the gate bits are not written: bd_bn_apply_act_fwd produces the block output)
                 self.lateral[s].dgrad(g, b.gout, b.gout, b.g_out, first=pool_top, mask=b.out,
-                                      maskbits=None if self.backbone_norms else b.out_bits)
+                                      maskbits=None if self.backbone_norm is not None else b.out_bits)
             else:
                 self.lateral[s].dgrad(g, b.gout, b.gout, b.g_out, first=True)
 
-        normed = bool(self.fpn_norms)
+        normed = self.fpn_norm is not None
         if normed:       # dL/d(conv output) of every output convolution first: nothing below reads the P3.. levels of g_P again
-            self._bn_backward("output", [pl.g_P] * nl, [pyr.level(li) for li in range(nl)], pl)
+            g_out = [self._norm_backward(self.output[s].norm, pl.g_P, pyr.level(li), pl) for li, s in enumerate(st)]
         for li in range(nl):
             s = st[li]
             b = pl.blk[pl.res[s]]
-            lvl = pyr.level(li)
-            if normed:
-                self._wgrad(self.output[s], pl.lat[s], pl.bn_gy["output", s], b.gout, b.gout, ws, cws)
-                self.output[s].dgrad(pl.bn_gy["output", s], b.gout, b.gout, pl.g_lat[s], first=True)
-            else:
-                self._wgrad(self.output[s], pl.lat[s], pl.g_P, b.gout, lvl, ws, cws)
-                self.output[s].dgrad(pl.g_P, b.gout, lvl, pl.g_lat[s], first=True, g8=pl.g_P8 if pl.g_P8_ready else None)
+            # the output convolution's gradient: its level of g_P, or (dense) what the norm's backward made of it
+            g, gg, g8 = (g_out[li], b.gout, None) if normed else (pl.g_P, pyr.level(li), pl.g_P8 if pl.g_P8_ready else None)
+            self._wgrad(self.output[s], pl.lat[s], g, b.gout, gg, ws, cws)
+            self.output[s].dgrad(g, b.gout, gg, pl.g_lat[s], first=True, g8=g8)
             if li > 0:   # gradient arriving through the top-down path from the finer level
                 sf = st[li - 1]
                 if self.fpn_deconv:
@@ -1171,9 +1171,9 @@ class FPNDetector:
         if normed:
             # every g_lat is complete (the un-normalised gradient the top-down path read): through the laterals' norms, then their
             # convolutions on the gradient with respect to the convolution's output
-            self._bn_backward("lateral", [pl.g_lat[s] for s in st], [pl.blk[pl.res[s]].gout for s in st], pl)
+            g_lat = [self._norm_backward(self.lateral[s].norm, pl.g_lat[s], pl.blk[pl.res[s]].gout, pl) for s in st]
             for li in range(nl):
-                lateral_backward(li, pl.bn_gy["lateral", st[li]])
+                lateral_backward(li, g_lat[li])
         self._flush_wgrads()
         if on_bucket_ready:
             on_bucket_ready("fpn", side)
@@ -1184,77 +1184,7 @@ class FPNDetector:
             blk, b = self.blocks[bi], pl.blk[bi]
             if not blk["trainable"]:
                 break
-            if self.backbone_norms:
-                self._block_backward_norm(bi, pl, ws)
-                if bi == 0 or self.blocks[bi - 1]["layer"] != blk["layer"]:
-                    self._flush_wgrads()
-                    if on_bucket_ready:
-                        on_bucket_ready(f"layer{blk['layer']}", side)
-                continue
-            convs = blk["convs"]
-            geos = [b.gin] + b.mid_geo + [b.gout]
-            xin = pl.blk[bi - 1].out if bi > 0 else pl.pool_out
-            prev_tr = bi > 0 and self.blocks[bi - 1]["trainable"]
-            G = b.g_out
-            # the shortcut convolution's weight gradient needs only the block's input and output gradient: first in the side
-            # stream's queue, not last (after the final block nothing is left on the main stream to hide it)
-            if blk["ds"] is not None:
-                self._wgrad(blk["ds"], xin, G, b.gin, b.gout, ws)
-            # main branch, last conv backwards
-            g = G
-            # fp8 mode: the e5m2 twin of the block's output gradient, written by the next block's conv1 data gradient (its last writer)
-            g8 = b.g_out8 if (b.g_out8 is not None and b.g_out8_ready) else None
-            for ci in range(len(convs) - 1, 0, -1):
-                # conv2's weight gradient from the twins both neighbours wrote (conv1's forward output, conv3's data gradient)
-                wx8 = b.mid8 if (ci == 1 and len(convs) == 3) else None
-                self._wgrad(convs[ci], b.mids[ci - 1], g, geos[ci], geos[ci + 1], ws, x8=wx8, g8=g8 if wx8 is not None else None)
-                # conv3's (dense 1x1) data gradient also writes the e5m2 twin that conv2's fp8 data gradient reads, conv2's the one
-                # conv1's reads
-                nxt = None
-                if len(convs) == 3:
-                    nxt = b.g_mid8 if ci == 2 else b.g_mid8a
-                if nxt is not None and not convs[ci].dgrad_writes_twin(geos[ci], geos[ci + 1]):
-                    nxt = None
-                wrote = convs[ci].dgrad(g, geos[ci], geos[ci + 1], b.g_mids[ci - 1], mask=b.mids[ci - 1], g8=g8, dx8=nxt,
-                                        q_scale=convs[ci - 1].grad_scale)
-                g, g8 = b.g_mids[ci - 1], (nxt if wrote else None)
-            self._wgrad(convs[0], xin, g, geos[0], geos[1], ws)
-            if prev_tr:
-                gx = pl.blk[bi - 1].g_out
-                xbits = pl.blk[bi - 1].out_bits if ops.dense_1x1_bits_ok(convs[0].desc(geos[0], geos[1])) else None
-                # has the input already received a contribution (FPN lateral of res3/res4)?
-                tapped = any(pl.res[s] == bi - 1 for s in st)
-                # conv1's data gradient is the LAST writer of the previous block's output gradient: it also writes that gradient's e5m2
-                # twin (fp8 mode) for the previous block's conv3
-                pb = pl.blk[bi - 1]
-                gx8 = pb.g_out8
-                # ... written with the scale of its consumer, the previous block's conv3 (another scale group at a layer boundary)
-                kw = dict(mask=xin, maskbits=xbits, g8=g8, dx8=gx8, q_scale=self.blocks[bi - 1]["convs"][-1].grad_scale)
-                if blk["ds"] is not None and gx8 is None and self.sparse_shortcut_grad:
-                    # conv1 first (writes every pixel, gated), then the stride-2 shortcut adds its gradient IN PLACE at the quarter of
-                    # the pixels it reaches ((a m + b) m = (a + b) m for a 0 / 1 gate m): instead of a full-resolution tensor that is
-                    # three quarters zeros being written, read back and summed
-                    wrote = convs[0].dgrad(g, geos[0], geos[1], gx, first=not tapped, **kw)
-                    blk["ds"].dgrad(G, b.gin, b.gout, gx, first=False, mask=xin, sparse=True)
-                elif blk["ds"] is not None:         # (the last writer must be the launch that can write the e5m2 twin)
-                    blk["ds"].dgrad(G, b.gin, b.gout, gx, first=not tapped)
-                    wrote = convs[0].dgrad(g, geos[0], geos[1], gx, first=False, **kw)
-                else:
-                    if tapped:
-                        ops.add_bf16(gx, G, gx)
-                        wrote = convs[0].dgrad(g, geos[0], geos[1], gx, first=False, **kw)
-                    else:
-                        # identity skip: gx = (dgrad + G) * mask
-                        wrote = convs[0].dgrad(g, geos[0], geos[1], gx, add_before=G, **kw)
-                pb.g_out8_ready = gx8 is not None and bool(wrote)     # what the launch actually did (a bf16 fallback drops the twin)
-            elif bi == 0 and self.stem is not None:
-                # dL/d(pool_out): the same residual fan-in, without a gate -- pool_out is a max-pool output, the stem's ReLU gate is
-                # applied by bd_maxpool3x3s2_bwd below
-                if blk["ds"] is not None:
-                    blk["ds"].dgrad(G, b.gin, b.gout, pl.grad_pool, first=True)
-                    convs[0].dgrad(g, geos[0], geos[1], pl.grad_pool, first=False)
-                else:                    # BasicBlock, identity shortcut
-                    convs[0].dgrad(g, geos[0], geos[1], pl.grad_pool, add_before=G)
+            (self._block_backward_norm if self.backbone_norm is not None else self._block_backward)(bi, pl, ws, cws)
             if bi == 0 or self.blocks[bi - 1]["layer"] != blk["layer"]:
                 self._flush_wgrads()
                 if on_bucket_ready:
@@ -1263,8 +1193,8 @@ class FPNDetector:
             gs = pl.g_stem
             ops.maxpool3x3s2_bwd(pl.grad_pool, pl.stem_out, pl.pool_out, pl.N, gs.H[0], gs.W[0], 64, pl.grad_stem)
             g_stem = pl.grad_stem
-            if self.backbone_norms:     # grad_stem is dL/dz of bn1 (gated by stem_out > 0): through the norm, no folded row scale
-                g_stem = self._norm_backward(self.stem.norm, pl.grad_stem, pl.stem_y, gs, pl.stem_gy, pl)
+            if self.stem.norm is not None:     # grad_stem is dL/dz of bn1 (gated by stem_out > 0): through the norm, no folded row scale
+                g_stem = self._norm_backward(self.stem.norm, pl.grad_stem, gs, pl)
             self._wgrad(self.stem, pl.x_halo, g_stem, pl.g_image, gs, ws)
             self._flush_wgrads()
             if on_bucket_ready:

@@ -907,14 +907,9 @@ def bn_stats_fwd(y, geom: Geom, Cn, eps, momentum, mean, inv_std, sums, running_
                               ptr(running_mean), ptr(running_var), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "bd_bn_stats_fwd")
 
 
-def bn_apply_fwd(y, gy: Geom, mean, inv_std, gamma, beta, z, gz: Geom, Cn):
-    check(L().bd_bn_apply_fwd(ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), ptr(z), *_lvl(gz), gy.N,
-                              gy.H[0] * gy.W[0], Cn, stream_ptr()), "bd_bn_apply_fwd")
-    return z
-
-
 def bn_apply_act_fwd(y, gy: Geom, mean, inv_std, gamma, beta, z, gz: Geom, Cn, residual=None, gr: Geom = None, relu=True):
-    """z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]) in one pass (the backbone's epilogue under MODEL.BACKBONE.NORM)."""
+    """z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]) in one pass: the epilogue of every normalised convolution (the
+    backbone's under MODEL.BACKBONE.NORM; the FPN's without residual and ReLU, z then possibly a level of the pyramid)."""
     rl = _lvl(gr if gr is not None else gz) if residual is not None else (0, 0)
     check(L().bd_bn_apply_act_fwd(ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), ptr(residual), *rl, ptr(z), *_lvl(gz),
                                   gy.N, gy.H[0] * gy.W[0], Cn, int(bool(relu)), stream_ptr()), "bd_bn_apply_act_fwd")

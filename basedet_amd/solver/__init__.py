@@ -396,8 +396,6 @@ def broadcast_parameters(model, src=0):
     c = _comm.get_comm()
     if c is not None and c.world > 1:
         c.bcast(model.arena.w, root=src)
-        if getattr(model, "fpn_norms", None):      # buffers: the FPN norm's running statistics
-            c.bcast(model.bn_running, root=src)
-        if getattr(model, "backbone_norms", None):      # and the backbone norm's
-            c.bcast(model.bbn_running, root=src)
+        if getattr(model, "norms", None):      # buffers: the running statistics of every live norm (backbone and FPN)
+            c.bcast(model.norms.running, root=src)
         model.repack_trainable()

@@ -619,15 +619,13 @@ int bd_groupnorm_bwd(const void* dz, const void* y, const float* gamma, const fl
 size_t bd_bn_workspace_bytes(int64_t rows, int C);
 int bd_bn_stats_fwd(const void* y, int N, int64_t pix_per_img, int64_t off, int64_t n, int C, float eps, float momentum, float* mean,
                     float* inv_std, float* sums, float* running_mean, float* running_var, void* ws, size_t ws_bytes, bd_stream_t stream);
-/* z = gamma * (y - mean) * inv_std + beta, evaluated in fp64 on the fp32 statistics and rounded once to bf16; z must not be y (the
- * backward pass reads y).  The FPN's top-down term is added by the launch that follows (bd_upsample2x_add_fwd / bd_fpn_deconv_fwd). */
-int bd_bn_apply_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
-                    const float* beta, void* z, int64_t z_pix_per_img, int64_t z_off, int N, int64_t n, int C,
-                    bd_stream_t stream);
-/* The backbone's epilogue under MODEL.BACKBONE.NORM = "BN" / "SyncBN" (bd_version() >= 110; models/cls/resnet.py:42-52, 94-113, 238-240):
- * z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]) in one pass over y (and the residual, NULL = none; bf16, its own
- * (pix_per_img, off)).  Evaluated as bd_bn_apply_fwd: fp64 on the fp32 statistics, the residual added in fp64, ONE rounding to bf16, then
- * the ReLU (relu != 0).  z must be neither y nor the residual: the backward pass reads both. */
+/* The epilogue of every normalised convolution (bd_version() >= 110; since 111 the only apply entry: bd_bn_apply_fwd was its residual = NULL,
+ * relu = 0 case): z = [relu](gamma * (y - mean) * inv_std + beta [+ residual]) in one pass over y (and the residual, NULL = none; bf16,
+ * its own (pix_per_img, off)).  The backbone under MODEL.BACKBONE.NORM (models/cls/resnet.py:42-52, 94-113, 238-240) takes the ReLU and,
+ * in a block's last stage, the residual; the FPN takes neither: its top-down term is added by the launch that follows
+ * (bd_upsample2x_add_fwd / bd_fpn_deconv_fwd), and z may be a level of the pyramid.  Evaluated in fp64 on the fp32 statistics, the
+ * residual added in fp64, ONE rounding to bf16, then the ReLU (relu != 0).  z must be neither y nor the residual: the backward pass
+ * reads both. */
 int bd_bn_apply_act_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
                         const float* beta, const void* residual, int64_t r_pix_per_img, int64_t r_off, void* z, int64_t z_pix_per_img,
                         int64_t z_off, int N, int64_t n, int C, int relu, bd_stream_t stream);

@@ -43,7 +43,7 @@ def main():
         t = M * C * 2          # bytes of one bf16 tensor
         runs = {
             "stats_fwd": (lambda: ops.bn_stats_fwd(y, geo, C, 1e-5, 0.1, mean, inv_std, sums, rm, rv, ws), t),
-            "apply_fwd": (lambda: ops.bn_apply_fwd(y, geo, mean, inv_std, gamma, beta, z, geo, C), 2 * t),
+            "apply_fwd": (lambda: ops.bn_apply_act_fwd(y, geo, mean, inv_std, gamma, beta, z, geo, C, relu=False), 2 * t),
             "bwd_reduce": (lambda: ops.bn_bwd_reduce(g, geo, y, geo, mean, inv_std, C, dg, db, ws), 2 * t),
             "bwd_apply": (lambda: ops.bn_bwd_apply(g, geo, y, geo, mean, inv_std, gamma, dg, db, sums[0], gy, geo, C), 3 * t),
         }

@@ -153,13 +153,9 @@ def test_faster_rcnn_step_matches_oracle(monkeypatch):
 
 def _norm_tensors(model, pl):
     """name -> stored pre-norm tensor (M, C) of the stem, one norm per layer and one downsample.1."""
-    out = {BU + ".bn1": pl.stem_y}
-    for blk, b in zip(model.blocks, pl.blk):
-        if blk["prefix"].endswith(".0"):
-            out[blk["prefix"] + ".bn1"] = b.ys[0]
-    blk, b = next((blk, b) for blk, b in zip(model.blocks, pl.blk) if blk["ds"] is not None)
-    out[blk["prefix"] + ".downsample.1"] = b.y_ds
-    return out
+    names = [BU + ".bn1"] + [blk["prefix"] + ".bn1" for blk in model.blocks if blk["prefix"].endswith(".0")]
+    names.append(next(blk["prefix"] for blk in model.blocks if blk["ds"] is not None) + ".downsample.1")
+    return {k: pl.norm_y[k] for k in names}
 
 
 def test_norm_state_is_live_after_two_steps():
@@ -256,7 +252,7 @@ def test_syncbn_at_world_one_is_bn_and_runs_repeat():
         out = model(batch)
         model.backward()
         torch.cuda.synchronize()
-        res.append(({k: float(v) for k, v in out.items()}, model.arena.g.clone(), model.bbn_running.clone()))
+        res.append(({k: float(v) for k, v in out.items()}, model.arena.g.clone(), model.norms.running.clone()))
     for other in res[1:]:
         assert other[0] == res[0][0]
         assert torch.equal(bits_of(other[1]), bits_of(res[0][1])) and torch.equal(bits_of(other[2]), bits_of(res[0][2]))

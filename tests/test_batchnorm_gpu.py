@@ -48,7 +48,7 @@ def _run(ops, y, gy, g, gg, z, gz, gout, go, C, gamma, beta, rm0, rv0):
              rv=torch.from_numpy(rv0).to(dev), dgamma=f(), dbeta=f())
     gam, bet = torch.from_numpy(gamma).to(dev), torch.from_numpy(beta).to(dev)
     ops.bn_stats_fwd(y, gy, C, EPS, MOM, o["mean"], o["inv_std"], o["sums"], o["rm"], o["rv"], ws)
-    ops.bn_apply_fwd(y, gy, o["mean"], o["inv_std"], gam, bet, z, gz, C)
+    ops.bn_apply_act_fwd(y, gy, o["mean"], o["inv_std"], gam, bet, z, gz, C, relu=False)
     ops.bn_bwd_reduce(g, gg, y, gy, o["mean"], o["inv_std"], C, o["dgamma"], o["dbeta"], ws)
     ops.bn_bwd_apply(g, gg, y, gy, o["mean"], o["inv_std"], gam, o["dgamma"], o["dbeta"], o["sums"][0], gout, go, C)
     torch.cuda.synchronize()

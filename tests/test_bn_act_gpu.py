@@ -4,7 +4,8 @@
 bd_bn_apply_act_fwd, z = [relu](gamma (y - mean) inv_std + beta [+ residual]), against float64 NumPy on the same bf16 inputs and the kernel's
 own fp32 statistics: every output within one bf16 ulp (tests/test_batchnorm_gpu.py's bound for the apply kernels), over residual x ReLU, on
 that file's hard channels (mean 100 sigma, constant, all zero, gamma < 0) and a residual that cancels gamma xhat + beta to near zero; two
-runs give the same bits; one run inside guarded, gapped buffers.  The raw stem launch against conv2d of the bf16-rounded operands with no
+runs give the same bits; one run inside guarded, gapped buffers; the FPN's form (no residual, no ReLU, a dense y into one level of a
+pyramid z).  The raw stem launch against conv2d of the bf16-rounded operands with no
 affine and no ReLU at tests/test_conv_gpu.py's TOL (1e-2 rel-L2), its output guarded."""
 import numpy as np
 import pytest
@@ -112,6 +113,44 @@ def test_bn_apply_act_inside_gapped_guarded_buffers():
     assert torch.equal(bits_of(zb).cpu()[other], before[other])
     ref = _ref(y, res, mean.cpu().double().numpy(), inv_std.cpu().double().numpy(), gamma, beta, True)
     assert int(bf16_ulps(zb.cpu()[rows], ref).max()) <= 1
+
+
+@pytest.mark.parametrize("C", [8, 264])
+def test_bn_apply_act_dense_into_pyramid_levels(C):
+    """What the FPN's output norms launch: no residual, no ReLU, a dense y written into ONE level of a two-level pyramid z -- level 1, then
+    level 0.  C = 8 is one chunk; C = 264 crosses the 256-channel tile (blockIdx.y = 1 runs with one live chunk lane).  Each level within
+    one bf16 ulp of float64 NumPy; the level not written, the rows between the levels and between the images and the guards keep their
+    sentinel bits, and the second launch leaves the first one's level alone."""
+    from basedet_amd import ops
+    N, levels = 2, [(5, 7), (3, 4)]
+    geom, kind = gapped_geom(N, levels, gap=16)
+    zb, zh = guarded(geom.pixels, C, torch.bfloat16, "cuda", fill="sentinel", name="z")
+    zh.set_gaps(kind).snapshot()
+    before = zh._snap.view(-1, C)[zh.g:zh.g + geom.pixels].cpu()
+    rows = [(torch.arange(N).view(-1, 1) * geom.pix_per_img + geom.off[li] + torch.arange(h * w).view(1, -1)).view(-1)
+            for li, (h, w) in enumerate(levels)]
+    done = {}
+    for li in (1, 0):
+        H, W = levels[li]
+        M = N * H * W
+        y, _, gamma, beta, _, _ = _inputs(M, C, seed=31 + li + C)
+        dense = ops.single(N, H, W)
+        yd, gam, bet = y.cuda(), torch.from_numpy(gamma).cuda(), torch.from_numpy(beta).cuda()
+        mean, inv_std = _stats(ops, yd, dense, C)
+        ops.bn_apply_act_fwd(yd, dense, mean, inv_std, gam, bet, zb, geom.level(li), C, residual=None, relu=False)
+        torch.cuda.synchronize()
+        zh.check()
+        got = zb.cpu()
+        ref = _ref(y, None, mean.cpu().double().numpy(), inv_std.cpu().double().numpy(), gamma, beta, False)
+        ulps = int(bf16_ulps(got[rows[li]], ref).max())
+        print("C", C, "level", li, "max bf16 ulps", ulps)
+        assert ulps <= 1, (li, ulps)
+        done[li] = bits_of(got[rows[li]]).clone()
+        for lj in (0, 1):
+            if lj in done:
+                assert torch.equal(bits_of(got[rows[lj]]), done[lj]), lj
+            else:
+                assert torch.equal(bits_of(got[rows[lj]]), before[rows[lj]]), lj
 
 
 def test_bn_apply_act_refuses_bad_arguments():

@@ -112,7 +112,7 @@ def test_norm_state_is_live_after_two_steps():
     model = RetinaNet(cfg, params=params)
     solver = DetSolver.build(cfg, model)
     run = {n.name: (params[n.name + ".running_mean"].astype(np.float64), params[n.name + ".running_var"].astype(np.float64))
-           for n in model.fpn_norms}
+           for n in model.norms if n.name.startswith("backbone.fpn_")}
     scale = {k: (np.zeros_like(v[0]), np.zeros_like(v[0])) for k, v in run.items()}
     for _ in range(2):
         solver.minimize(model, batch)
@@ -121,7 +121,7 @@ def test_norm_state_is_live_after_two_steps():
         for kind in ("lateral", "output"):
             for s in model.fpn_stages:
                 k = f"backbone.fpn_{kind}{s}.norm"
-                y = pl.bn_y[kind, s].double().cpu().numpy()
+                y = pl.norm_y[k].double().cpu().numpy()
                 M = y.shape[0]
                 mu, var = y.mean(0), y.var(0)
                 rm, rv = run[k]
@@ -187,7 +187,7 @@ def test_syncbn_at_world_one_is_bn_bit_for_bit():
         out = model(batch)
         model.backward()
         torch.cuda.synchronize()
-        res.append((float(out["total_loss"]), model.arena.g.clone(), model.bn_running.clone(), model._cur.P.clone()))
+        res.append((float(out["total_loss"]), model.arena.g.clone(), model.norms.running.clone(), model._cur.P.clone()))
     assert res[0][0] == res[1][0]
     for a, b in zip(res[0][1:], res[1][1:]):
         assert torch.equal(bits_of(a), bits_of(b))
@@ -199,7 +199,7 @@ def test_default_config_is_untouched():
     cfg, params, batch = _setup("resnet18", 2, SIZE)
     model = RetinaNet(cfg, params=params)
     names = model.trainable_parameter_names()
-    assert not any(".norm." in n for n in names) and "backbone.fpn_lateral3.bias" in names and not model.fpn_norms
+    assert not any(".norm." in n for n in names) and "backbone.fpn_lateral3.bias" in names and not model.norms
     cfg2, params2, _ = _setup("resnet18", 2, SIZE)
     cfg2.MODEL.FPN.pop("NORM")
     other = RetinaNet(cfg2, params=params2)
