@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 111              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd; 111: bd_bn_apply_fwd removed, bd_bn_apply_act_fwd serves its callers)
+ABI_VERSION = 112              # bd_version() of the library this binding matches (101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd; 111: bd_bn_apply_fwd removed, bd_bn_apply_act_fwd serves its callers; 112: one entry per operator -- the *_ld, _general, _batched and _joint twins and the giou forwarder folded into the base names, which take their arguments)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -119,25 +119,19 @@ SIGNATURES = {
     "bd_retina_assign_encode": (_I, [_P, _I, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_fcos_assign": (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bd_ota_assign_workspace_bytes": (_Z, [_I, _I]),
-    "bd_ota_assign": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
-    "bd_ota_assign_ld": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "bd_ota_assign": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_ota_sinkhorn_workspace_bytes": (_Z, [_I, _I, _I]),
-    "bd_ota_assign_sinkhorn": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
-    "bd_ota_assign_sinkhorn_ld": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "bd_ota_assign_sinkhorn": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_freeanchor_workspace_bytes": (_Z, [_I, _I, _I, _I]),
-    "bd_freeanchor_loss_fwd_bwd": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _F, _I, _F, _F, _F, _F, _P, _P, _P, _P, _Z, _P]),
-    "bd_freeanchor_loss_fwd_bwd_ld": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _F, _I, _F, _F, _F, _F, _P, _P, _P, _P, _Z, _P]),
+    "bd_freeanchor_loss_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _F, _I, _F, _F, _F, _F, _P, _P, _P, _P, _Z, _P]),
     "bd_atss_assign_workspace_bytes": (_Z, [_I, _I]),
     "bd_atss_assign": (_I, [_P, _I, _P, _P, _I, _I, _F, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_nms_workspace_bytes": (_Z, [_I]),
     "bd_batched_nms": (_I, [_P, _P, _P, _I, _F, _I, _P, _P, _P, _Z, _P]),
-    "bd_focal_loss_fwd_bwd": (_I, [_P, _P, _L, _I, _F, _F, _P, _I, _F, _P, _P, _P]),
-    "bd_focal_loss_fwd_bwd_general": (_I, [_P, _P, _L, _I, _F, _F, _P, _I, _F, _P, _P, _P]),
-    "bd_focal_loss_fwd_bwd_ld": (_I, [_P, _P, _L, _I, _I, _F, _F, _P, _I, _F, _P, _P, _I, _P]),
+    "bd_focal_loss_fwd_bwd": (_I, [_P, _P, _L, _I, _I, _F, _F, _P, _I, _F, _P, _P, _I, _P]),
     "bd_smooth_l1_fwd_bwd": (_I, [_P, _P, _P, _L, _I, _I, _F, _P, _I, _F, _P, _P, _P]),
     "bd_loss_grid_cap": (_I, []),
     "bd_iou_ltrb_fwd_bwd": (_I, [_P, _P, _P, _P, _L, _I, _P, _F, _P, _P, _P]),
-    "bd_giou_ltrb_fwd_bwd": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _P, _P]),
     "bd_bce_logits_fwd_bwd": (_I, [_P, _I, _I, _P, _P, _L, _P, _P, _P, _P]),
     "bd_groupnorm_workspace_bytes": (_Z, [_I, _I, _I, _L]),
     "bd_groupnorm_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _L, _I, _F, _I, _P, _P, _P, _Z, _P]),
@@ -159,8 +153,7 @@ SIGNATURES = {
     "bd_nms_batched_workspace_bytes": (_Z, [_I, _I]),
     "bd_nms_batched": (_I, [_P, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _Z, _P]),
     "bd_rpn_proposals_workspace_bytes": (_Z, [_I, _I, _P, _I, _I, _I]),
-    "bd_rpn_proposals": (_I, [_P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _I, _P, _P, _I, _F, _I, _P, _P, _P, _Z, _P]),
-    "bd_rpn_proposals_joint": (_I, [_P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _I, _P, _P, _I, _F, _I, _P, _P, _P, _Z, _P]),
+    "bd_rpn_proposals": (_I, [_P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _I, _P, _P, _I, _F, _I, _P, _P, _P, _Z, _I, _P]),
     "bd_rcnn_sample_targets": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "bd_roi_align_fwd": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "bd_conv1x1_thin_bwd_workspace_bytes": (_Z, []),
@@ -178,16 +171,12 @@ SIGNATURES = {
     "bd_f32_to_bf16_add": (_I, [_P, _P, _L, _P]),
     "bd_rpn_loss_fwd_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _L, _F, _P, _P, _P, _P]),
     "bd_rcnn_loss_fwd_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P]),
-    "bd_det_scores": (_I, [_P, _P, _I, _I, _L, _I, _P, _P]),
-    "bd_det_scores_ld": (_I, [_P, _I, _P, _I, _I, _L, _I, _P, _P]),
+    "bd_det_scores": (_I, [_P, _I, _P, _I, _I, _L, _I, _P, _P]),
     "bd_det_select_workspace_bytes": (_Z, [_I, _I, _L, _I, _I]),
-    "bd_det_select": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
-    "bd_det_select_ld": (_I, [_P, _I, _P, _I, _I, _I, _L, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
+    "bd_det_select": (_I, [_P, _I, _P, _I, _I, _I, _L, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
     "bd_rcnn_predict": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
-    "bd_det_candidates": (_I, [_I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "bd_det_finalize": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
-    "bd_det_candidates_batched": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P]),
-    "bd_det_finalize_batched": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "bd_det_candidates": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P]),
+    "bd_det_finalize": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "bd_sgd_momentum_step": (_I, [_P, _P, _P, _L, _F, _F, _F, _F, _P]),
     "bd_ema_update": (_I, [_P, _P, _L, _F, _F, _P]),
     "bd_sgd_momentum_ema_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P]),

@@ -242,10 +242,10 @@ extern "C" size_t bd_det_select_workspace_bytes(int B, int L, int64_t rows, int 
 }
 
 // logits [B][rows][ld], ld = K or round_up(K, 8) (the slots >= K of a row are padding and never selected); the indices are the compact
-// row * K + class of bd_det_select whatever ld is.  SelSegs.item0 / count / chunk0 walk the PADDED items (rows * ld < 2^31).
-extern "C" int bd_det_select_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
-                                const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
-                                float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream) {
+// row * K + class whatever ld is.  SelSegs.item0 / count / chunk0 walk the PADDED items (rows * ld < 2^31).
+extern "C" int bd_det_select(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
+                             const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
+                             float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream) {
     BD_REQUIRE(logits && seg_start_host && seg_rows_host && out_idx && out_score && out_cnt && ws, "det_select: null pointer");
     BD_REQUIRE(K > 0 && (ld == K || (ld % 8 == 0 && ld > K && ld - K < 8)), "det_select: ld=%d must be K=%d or K rounded up to a multiple of 8", ld, K);
     BD_REQUIRE(B > 0 && L > 0 && L <= BD_MAX_SEGS && rows >= 0 && rows * ld < (1ll << 31), "det_select: bad sizes");
@@ -294,11 +294,4 @@ extern "C" int bd_det_select_ld(const void* logits, int ld, const void* ctr, int
     hipLaunchKernelGGL(det_select_sort_kernel, dim3(B * L), dim3(1024), 0, st, w.st, w.cand, k, key_lo, out_idx, out_score, out_cnt);
     BD_CHECK_LAUNCH("bd_det_select");
     return BD_OK;
-}
-
-extern "C" int bd_det_select(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
-                             const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
-                             float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream) {
-    return bd_det_select_ld(logits, K, ctr, ctr_ld, ctr_off, B, rows, K, L, seg_start_host, seg_rows_host, k, min_score, out_idx, out_score,
-                            out_cnt, ws, ws_bytes, stream);
 }

@@ -459,7 +459,7 @@ extern "C" size_t bd_freeanchor_workspace_bytes(int N, int Gmax, int bucket, int
 }
 
 // cls_ld: slots between the class rows of two anchors -- K (compact, any K) or K rounded up to a multiple of 8 (pad slots: no loss, +0 gradient)
-extern "C" int bd_freeanchor_loss_fwd_bwd_ld(const void* logits, int cls_ld, const void* offsets, int box_ld, int anchors_per_pix,
+extern "C" int bd_freeanchor_loss_fwd_bwd(const void* logits, int cls_ld, const void* offsets, int box_ld, int anchors_per_pix,
                                           const float* anchors, int A, int K, const float* gt, const int32_t* num_gt, int N,
                                           int Gmax, const float* mean4, const float* std4, float iou_thresh, int bucket,
                                           float beta, float reg_weight, float alpha, float gamma, float* loss_out,
@@ -501,14 +501,4 @@ extern "C" int bd_freeanchor_loss_fwd_bwd_ld(const void* logits, int cls_ld, con
                        coder, iou_thresh, alpha, gamma, (const float*)thresh2, stage, (bf16_raw*)d_logits, (bf16_raw*)d_offsets, loss_out);
     BD_CHECK_LAUNCH("bd_freeanchor_loss_fwd_bwd");
     return BD_OK;
-}
-
-extern "C" int bd_freeanchor_loss_fwd_bwd(const void* logits, const void* offsets, int box_ld, int anchors_per_pix,
-                                          const float* anchors, int A, int K, const float* gt, const int32_t* num_gt, int N,
-                                          int Gmax, const float* mean4, const float* std4, float iou_thresh, int bucket,
-                                          float beta, float reg_weight, float alpha, float gamma, float* loss_out,
-                                          void* d_logits, void* d_offsets, void* ws, size_t ws_bytes, bd_stream_t stream) {
-    return bd_freeanchor_loss_fwd_bwd_ld(logits, K, offsets, box_ld, anchors_per_pix, anchors, A, K, gt, num_gt, N, Gmax, mean4, std4,
-                                         iou_thresh, bucket, beta, reg_weight, alpha, gamma, loss_out, d_logits, d_offsets, ws, ws_bytes,
-                                         stream);
 }

@@ -562,8 +562,11 @@ static void loss_finalize(const float* partial, int n, int slots, float* loss, b
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, n, slots, loss);
 }
 
-static int focal_launch(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma, const void* norm,
-                        int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, bool general, bd_stream_t stream) {
+// any class count: rows of ld = round_up(K, 8) slots, the first K the classes, the rest padding (no loss, gradient +0); ld == K is the
+// compact layout.  general != 0: the general-gamma kernel whatever gamma is (the gamma == 2 instance is checked against it).
+extern "C" int bd_focal_loss_fwd_bwd(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma,
+                                     const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, int general,
+                                     bd_stream_t stream) {
     BD_REQUIRE(logits && labels && norm && loss_sum && dlogits, "focal_loss: null pointer");
     BD_REQUIRE(K > 0 && ld % 8 == 0 && ld >= K && ld - K < 8, "focal_loss: the row stride ld=%d must be K=%d rounded up to a multiple of 8", ld, K);
     if (rows == 0) return BD_OK;
@@ -580,29 +583,6 @@ static int focal_launch(const void* logits, const int32_t* labels, int64_t rows,
     loss_finalize(part, grid, 1, loss_sum, stream);
     BD_CHECK_LAUNCH("bd_focal_loss_fwd_bwd");
     return BD_OK;
-}
-
-extern "C" int bd_focal_loss_fwd_bwd(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha, float gamma,
-                                     const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits,
-                                     bd_stream_t stream) {
-    BD_REQUIRE(K > 0 && K % 8 == 0, "focal_loss: K=%d must be a multiple of 8 (bd_focal_loss_fwd_bwd_ld takes any K)", K);
-    return focal_launch(logits, labels, rows, K, K, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, false, stream);
-}
-
-// any class count: rows of ld = round_up(K, 8) slots, the first K the classes, the rest padding (no loss, gradient +0).  general != 0:
-// the general-gamma kernel whatever gamma is.  ld == K is bd_focal_loss_fwd_bwd / _general, bit for bit.
-extern "C" int bd_focal_loss_fwd_bwd_ld(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma,
-                                        const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, int general,
-                                        bd_stream_t stream) {
-    return focal_launch(logits, labels, rows, K, ld, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, general != 0, stream);
-}
-
-// the general-gamma kernel whatever gamma is (the gamma == 2 instance of bd_focal_loss_fwd_bwd is checked against it)
-extern "C" int bd_focal_loss_fwd_bwd_general(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha, float gamma,
-                                             const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits,
-                                             bd_stream_t stream) {
-    BD_REQUIRE(K > 0 && K % 8 == 0, "focal_loss: K=%d must be a multiple of 8 (bd_focal_loss_fwd_bwd_ld takes any K)", K);
-    return focal_launch(logits, labels, rows, K, K, alpha, gamma, norm, norm_is_float, grad_scale, loss_sum, dlogits, true, stream);
 }
 
 extern "C" int bd_smooth_l1_fwd_bwd(const void* pred, const float* target, const int32_t* labels, int64_t pixels, int A,
@@ -638,13 +618,6 @@ extern "C" int bd_iou_ltrb_fwd_bwd(const void* pred, const float* target, const 
     loss_finalize(part, grid, 1, loss_sum, stream);
     BD_CHECK_LAUNCH("bd_iou_ltrb_fwd_bwd");
     return BD_OK;
-}
-
-// loss_type "giou" of bd_iou_ltrb_fwd_bwd
-extern "C" int bd_giou_ltrb_fwd_bwd(const void* pred, const float* target, const float* weight, const int32_t* labels,
-                                    int64_t rows, const float* norm, float loss_weight, float* loss_sum, void* dpred,
-                                    bd_stream_t stream) {
-    return bd_iou_ltrb_fwd_bwd(pred, target, weight, labels, rows, IOU_LT_GIOU, norm, loss_weight, loss_sum, dpred, stream);
 }
 
 extern "C" int bd_bce_logits_fwd_bwd(const void* pred, int ld, int off, const float* target, const int32_t* labels, int64_t rows,

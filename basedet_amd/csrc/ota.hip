@@ -366,7 +366,8 @@ extern "C" size_t bd_ota_sinkhorn_workspace_bytes(int N, int P, int Gmax) {
     return (size_t)N * P * 8 + (size_t)N * (Gmax + 1) * P * 4 + (size_t)N * (Gmax + 1) * 4 + 1024;
 }
 
-extern "C" int bd_ota_assign_sinkhorn_ld(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L,
+// logits [N * P][ld], ld = round_up(K, 8); ld == K is the compact layout
+extern "C" int bd_ota_assign_sinkhorn(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L,
                                       const void* logits, int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N,
                                       int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps,
                                       int iters, int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
@@ -409,7 +410,7 @@ extern "C" size_t bd_ota_assign_workspace_bytes(int N, int P) {
     return (size_t)N * P * 12 + 256;
 }
 
-extern "C" int bd_ota_assign_ld(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L, const void* logits,
+extern "C" int bd_ota_assign(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L, const void* logits,
                              int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
                              float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
                              float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream) {
@@ -440,24 +441,4 @@ extern "C" int bd_ota_assign_ld(const float* points, int P, const int32_t* lvl_s
                        targets, gt_ious, stats);
     BD_CHECK_LAUNCH("bd_ota_assign");
     return BD_OK;
-}
-
-// the entry points without a row stride: compact [N * P][K] logits, K a multiple of 8
-extern "C" int bd_ota_assign_sinkhorn(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L,
-                                      const void* logits, int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N,
-                                      int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps,
-                                      int iters, int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
-                                      bd_stream_t stream) {
-    BD_REQUIRE(K > 0 && K % 8 == 0, "ota_assign_sinkhorn: K=%d must be a multiple of 8 (bd_ota_assign_sinkhorn_ld takes any K)", K);
-    return bd_ota_assign_sinkhorn_ld(points, P, lvl_start, strides, L, logits, K, K, pred_ltrb, gt_boxes, num_gt, N, Gmax, alpha, gamma,
-                                     reg_weight, center_radius, topq, eps, iters, labels, targets, gt_ious, stats, ws, ws_bytes, stream);
-}
-
-extern "C" int bd_ota_assign(const float* points, int P, const int32_t* lvl_start, const int32_t* strides, int L, const void* logits,
-                             int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
-                             float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
-                             float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream) {
-    BD_REQUIRE(K > 0 && K % 8 == 0, "ota_assign: K=%d must be a multiple of 8 (bd_ota_assign_ld takes any K)", K);
-    return bd_ota_assign_ld(points, P, lvl_start, strides, L, logits, K, K, pred_ltrb, gt_boxes, num_gt, N, Gmax, alpha, gamma, reg_weight,
-                            center_radius, candidate_k, labels, targets, gt_ious, stats, ws, ws_bytes, stream);
 }

@@ -11,7 +11,7 @@ __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-
 
 // scores[r*K + k] = sigmoid(logit)  or  sqrt(sigmoid(logit) * sigmoid(ctr[r]))   (fcos.py:194); logits [rows][ld], ld >= K: the slots
 // behind a row's K classes are padding and get no score (the output is the compact [rows][K]; ld != K pays a 64-bit division per element
-// for the row, which this single-image reference chain can afford: the batched path is bd_det_select_ld)
+// for the row, which this single-image reference chain can afford: the batched path is bd_det_select)
 __global__ __launch_bounds__(256) void det_scores_kernel(const bf16_raw* __restrict__ logits, int ld, const bf16_raw* __restrict__ ctr,
                                                          int ctr_ld, int ctr_off, long long rows, int K, float* __restrict__ scores) {
     const long long total = rows * K;
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(256) void det_finalize_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" int bd_det_scores_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
-                                bd_stream_t stream) {
+extern "C" int bd_det_scores(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
+                             bd_stream_t stream) {
     BD_REQUIRE(logits && scores && K > 0 && rows >= 0, "det_scores: bad arguments");
     BD_REQUIRE(ld == K || (ld % 8 == 0 && ld > K && ld - K < 8), "det_scores: ld=%d must be K=%d or K rounded up to a multiple of 8", ld, K);
     if (rows == 0) return BD_OK;
@@ -142,11 +142,6 @@ extern "C" int bd_det_scores_ld(const void* logits, int ld, const void* ctr, int
                        (const bf16_raw*)ctr, ctr_ld, ctr_off, (long long)rows, K, scores);
     BD_CHECK_LAUNCH("bd_det_scores");
     return BD_OK;
-}
-
-extern "C" int bd_det_scores(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
-                             bd_stream_t stream) {
-    return bd_det_scores_ld(logits, K, ctr, ctr_ld, ctr_off, rows, K, scores, stream);
 }
 
 extern "C" int bd_rcnn_predict(const void* raw, int ld, int K, int box_off, const float* rois, const int32_t* num_rois,
@@ -161,62 +156,35 @@ extern "C" int bd_rcnn_predict(const void* raw, int ld, int K, int box_off, cons
     return BD_OK;
 }
 
-extern "C" int bd_det_candidates(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int L, int k,
-                                 const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets, int off_ld, int A,
-                                 const float* mean4_host, const float* std4_host, const float* item_boxes, float* boxes, float* scores,
-                                 int32_t* labels, bd_stream_t stream) {
+// one image is B = 1 (grid.y = 1; the image strides are then never applied)
+extern "C" int bd_det_candidates(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int B, int L,
+                                 int k, const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets,
+                                 int64_t off_stride, int off_ld, int A, const float* mean4_host, const float* std4_host,
+                                 const float* item_boxes, int64_t item_stride, float* boxes, float* scores, int32_t* labels,
+                                 bd_stream_t stream) {
     BD_REQUIRE(topk_idx && topk_score && topk_cnt && lvl_row_off_host && boxes && scores && labels, "det_candidates: null pointer");
-    BD_REQUIRE(mode >= 0 && mode <= 2 && L > 0 && L <= BD_MAX_SEGS && k > 0 && K > 0 && A > 0, "det_candidates: bad sizes");
-    BD_REQUIRE(mode == 2 ? item_boxes != nullptr : (anchors && offsets), "det_candidates: missing inputs for mode %d", mode);
-    CandLevels lv{};
-    lv.L = L;
-    for (int l = 0; l < L; ++l) lv.row_off[l] = lvl_row_off_host[l];
-    hipLaunchKernelGGL(det_candidates_kernel, dim3(cdiv(L * k, 256)), dim3(256), 0, (hipStream_t)stream, mode, topk_idx, topk_score,
-                       topk_cnt, lv, k, K, anchors, (const bf16_raw*)offsets, 0ll, off_ld, A, make_coder(mean4_host, std4_host), item_boxes,
-                       0ll, boxes, scores, labels);
-    BD_CHECK_LAUNCH("bd_det_candidates");
-    return BD_OK;
-}
-
-extern "C" int bd_det_candidates_batched(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int B, int L,
-                                         int k, const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets,
-                                         int64_t off_stride, int off_ld, int A, const float* mean4_host, const float* std4_host,
-                                         const float* item_boxes, int64_t item_stride, float* boxes, float* scores, int32_t* labels,
-                                         bd_stream_t stream) {
-    BD_REQUIRE(topk_idx && topk_score && topk_cnt && lvl_row_off_host && boxes && scores && labels, "det_candidates_batched: null pointer");
     BD_REQUIRE(mode >= 0 && mode <= 2 && B > 0 && B <= 65535 && L > 0 && L <= BD_MAX_SEGS && k > 0 && K > 0 && A > 0,
-               "det_candidates_batched: bad sizes");
-    BD_REQUIRE(mode == 2 ? item_boxes != nullptr : (anchors && offsets), "det_candidates_batched: missing inputs for mode %d", mode);
-    BD_REQUIRE(off_stride >= 0 && item_stride >= 0, "det_candidates_batched: negative image stride");
+               "det_candidates: bad sizes");
+    BD_REQUIRE(mode == 2 ? item_boxes != nullptr : (anchors && offsets), "det_candidates: missing inputs for mode %d", mode);
+    BD_REQUIRE(off_stride >= 0 && item_stride >= 0, "det_candidates: negative image stride");
     CandLevels lv{};
     lv.L = L;
     for (int l = 0; l < L; ++l) lv.row_off[l] = lvl_row_off_host[l];
     hipLaunchKernelGGL(det_candidates_kernel, dim3(cdiv(L * k, 256), B), dim3(256), 0, (hipStream_t)stream, mode, topk_idx, topk_score,
                        topk_cnt, lv, k, K, anchors, (const bf16_raw*)offsets, (long long)off_stride, off_ld, A,
                        make_coder(mean4_host, std4_host), item_boxes, (long long)item_stride, boxes, scores, labels);
-    BD_CHECK_LAUNCH("bd_det_candidates_batched");
+    BD_CHECK_LAUNCH("bd_det_candidates");
     return BD_OK;
 }
 
 extern "C" int bd_det_finalize(const float* boxes, const float* scores, const int32_t* labels, const int32_t* keep,
-                               const int32_t* num_keep, int max_out, const float* im_info, float* out_boxes, float* out_scores,
-                               int32_t* out_labels, bd_stream_t stream) {
-    BD_REQUIRE(boxes && scores && labels && keep && num_keep && im_info && out_boxes && out_scores && out_labels && max_out > 0,
-               "det_finalize: bad arguments");
-    hipLaunchKernelGGL(det_finalize_kernel, dim3(cdiv(max_out, 256)), dim3(256), 0, (hipStream_t)stream, boxes, scores, labels, keep,
-                       num_keep, max_out, im_info, 0, 0, out_boxes, out_scores, out_labels);
-    BD_CHECK_LAUNCH("bd_det_finalize");
-    return BD_OK;
-}
-
-extern "C" int bd_det_finalize_batched(const float* boxes, const float* scores, const int32_t* labels, const int32_t* keep,
-                                       const int32_t* num_keep, int B, int C, int max_out, const float* im_info, int info_ld,
-                                       float* out_boxes, float* out_scores, int32_t* out_labels, bd_stream_t stream) {
+                               const int32_t* num_keep, int B, int C, int max_out, const float* im_info, int info_ld,
+                               float* out_boxes, float* out_scores, int32_t* out_labels, bd_stream_t stream) {
     BD_REQUIRE(boxes && scores && labels && keep && num_keep && im_info && out_boxes && out_scores && out_labels,
-               "det_finalize_batched: null pointer");
-    BD_REQUIRE(B > 0 && B <= 65535 && C > 0 && max_out > 0 && info_ld >= 4, "det_finalize_batched: bad sizes");
+               "det_finalize: null pointer");
+    BD_REQUIRE(B > 0 && B <= 65535 && C > 0 && max_out > 0 && info_ld >= 4, "det_finalize: bad sizes");
     hipLaunchKernelGGL(det_finalize_kernel, dim3(cdiv(max_out, 256), B), dim3(256), 0, (hipStream_t)stream, boxes, scores, labels, keep,
                        num_keep, max_out, im_info, C, info_ld, out_boxes, out_scores, out_labels);
-    BD_CHECK_LAUNCH("bd_det_finalize_batched");
+    BD_CHECK_LAUNCH("bd_det_finalize");
     return BD_OK;
 }

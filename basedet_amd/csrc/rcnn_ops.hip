@@ -1098,11 +1098,12 @@ extern "C" size_t bd_rpn_proposals_workspace_bytes(int N, int L, const int32_t* 
     return rpn_ws_layout(N, rpn_capacity(L, lvl_pixels_host, A, pre_k), L, pre_k, post_k).total;
 }
 
-static int rpn_proposals_impl(const void* raw, int ldc, int A, int cls_off, int box_off, int N, int64_t pix_per_img, int L,
-                              const int32_t* lvl_pix_off_host, const int32_t* lvl_pixels_host, const float* anchors,
-                              const float* im_info, int info_ld, const float* mean4_host, const float* std4_host, int pre_k,
-                              float nms_thresh, int post_k, float* rois, int32_t* num_rois, void* ws, size_t ws_bytes,
-                              bool nms_per_level, bd_stream_t stream) {
+// joint_nms != 0: the batched NMS as ONE problem per image (rounds 1-4) instead of level by level + merge: the same proposals bit for bit (tests)
+extern "C" int bd_rpn_proposals(const void* raw, int ldc, int A, int cls_off, int box_off, int N, int64_t pix_per_img, int L,
+                                const int32_t* lvl_pix_off_host, const int32_t* lvl_pixels_host, const float* anchors,
+                                const float* im_info, int info_ld, const float* mean4_host, const float* std4_host, int pre_k,
+                                float nms_thresh, int post_k, float* rois, int32_t* num_rois, void* ws, size_t ws_bytes,
+                                int joint_nms, bd_stream_t stream) {
     BD_REQUIRE(raw && lvl_pix_off_host && lvl_pixels_host && anchors && im_info && rois && num_rois && ws, "rpn_proposals: null pointer");
     BD_REQUIRE(N > 0 && L > 0 && L <= BD_MAX_SEGS && A > 0 && pre_k > 0 && pre_k <= TOPK_MAX && post_k > 0, "rpn_proposals: bad sizes");
     BD_REQUIRE(cls_off >= 0 && box_off >= 0 && cls_off + A <= ldc && box_off + 4 * A <= ldc, "rpn_proposals: bad channel layout");
@@ -1141,32 +1142,13 @@ static int rpn_proposals_impl(const void* raw, int ldc, int A, int cls_off, int 
     hipLaunchKernelGGL(rpn_decode_kernel, dim3(cdiv(C, 256), N), dim3(256), 0, st, (const bf16_raw*)raw, (long long)pix_per_img, ldc,
                        A, box_off, anchors, lv, pre_k, tk_idx, tk_score, tk_cnt, im_info, info_ld, make_coder(mean4_host, std4_host),
                        C, boxes, scores, levels);
-    if (nms_per_level)
+    if (!joint_nms)
         bd_nms_levels_run(boxes, scores, lv, N, C, nms_thresh, post_k, keep, num_rois, wb + w.nms, st);
     else
         bd_nms_joint_run(boxes, scores, levels, N, C, nms_thresh, post_k, post_k, keep, num_rois, wb + w.nms, st);
     hipLaunchKernelGGL(rpn_gather_kernel, dim3(cdiv(post_k, 256), N), dim3(256), 0, st, boxes, keep, num_rois, C, post_k, rois);
     BD_CHECK_LAUNCH("bd_rpn_proposals");
     return BD_OK;
-}
-
-extern "C" int bd_rpn_proposals(const void* raw, int ldc, int A, int cls_off, int box_off, int N, int64_t pix_per_img, int L,
-                                const int32_t* lvl_pix_off_host, const int32_t* lvl_pixels_host, const float* anchors,
-                                const float* im_info, int info_ld, const float* mean4_host, const float* std4_host, int pre_k,
-                                float nms_thresh, int post_k, float* rois, int32_t* num_rois, void* ws, size_t ws_bytes,
-                                bd_stream_t stream) {
-    return rpn_proposals_impl(raw, ldc, A, cls_off, box_off, N, pix_per_img, L, lvl_pix_off_host, lvl_pixels_host, anchors, im_info, info_ld,
-                              mean4_host, std4_host, pre_k, nms_thresh, post_k, rois, num_rois, ws, ws_bytes, true, stream);
-}
-
-// the batched NMS as ONE problem per image (rounds 1-4) instead of level by level + merge: the same proposals bit for bit (tests)
-extern "C" int bd_rpn_proposals_joint(const void* raw, int ldc, int A, int cls_off, int box_off, int N, int64_t pix_per_img, int L,
-                                      const int32_t* lvl_pix_off_host, const int32_t* lvl_pixels_host, const float* anchors,
-                                      const float* im_info, int info_ld, const float* mean4_host, const float* std4_host, int pre_k,
-                                      float nms_thresh, int post_k, float* rois, int32_t* num_rois, void* ws, size_t ws_bytes,
-                                      bd_stream_t stream) {
-    return rpn_proposals_impl(raw, ldc, A, cls_off, box_off, N, pix_per_img, L, lvl_pix_off_host, lvl_pixels_host, anchors, im_info, info_ld,
-                              mean4_host, std4_host, pre_k, nms_thresh, post_k, rois, num_rois, ws, ws_bytes, false, stream);
 }
 
 extern "C" int bd_sample_labels(int32_t* labels, const float* keys_pos, const float* keys_neg, int N, int A, int num_pos_max,

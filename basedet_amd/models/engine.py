@@ -445,7 +445,7 @@ class PaddedClsConv(ConvLayer):
     mapping is the identity and this is a plain ConvLayer.
 
     INVARIANT: the pad rows of the weight, the bias, their gradients and the momentum are exactly zero for a whole run.  bind zeroes
-    them; every loss writes a zero gradient into the pad slots of d_logits (bd_focal_loss_fwd_bwd_ld, bd_freeanchor_loss_fwd_bwd_ld), so
+    them; every loss writes a zero gradient into the pad slots of d_logits (bd_focal_loss_fwd_bwd, bd_freeanchor_loss_fwd_bwd), so
     the weight and bias gradients of the pad rows are sums of zeros; SGD with momentum and weight decay, gradient clipping, the EMA and
     the gradient all-reduce map zero to zero.  tests/test_class_count_gpu.py::test_pad_rows_stay_zero holds this."""
 

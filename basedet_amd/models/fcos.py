@@ -166,16 +166,12 @@ class FCOS(FPNDetector):
         pl.loss_buf.zero_()
         rows = pl.N * pl.pyr.pix_per_img
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA,
-                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self._ld())
+                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self.cls_ld)
         ops.iou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, pl.gt_ctr, pl.labels, rows, self.iou_loss_type, pl.stats[1:2],
                              m.LOSSES.REG_LOSS_WEIGHT, pl.loss_buf[1:2], pl.d_off)
         ops.bce_logits_fwd_bwd(pl.raw, pl.gt_ctr, pl.labels, rows, pl.stats[0:1], pl.loss_buf[2:3], pl.d_ctr, ld=8, off=4)
         cls_loss, reg_loss, ctr_loss = pl.loss_buf[0], pl.loss_buf[1], pl.loss_buf[2]
         return {"total_loss": cls_loss + reg_loss + ctr_loss, "cls_loss": cls_loss, "reg_loss": reg_loss, "ctr_loss": ctr_loss}
-
-    def _ld(self):
-        """The class stride for the ops that take one: None (the compact entry points) when K is a multiple of 8."""
-        return self.cls_ld if self.cls_ld != self.num_classes else None
 
     @staticmethod
     def _allreduce_stats(c, stats):
@@ -288,11 +284,11 @@ class OTA(FCOS):
             ws = pl.ota_ws if pl.ota_ws.numel() >= need else self._scratch("ota_sinkhorn", need)
             ops.ota_assign_sinkhorn(pl.points, pl.lvl_start, self.strides, pl.logits, self.num_classes, pl.offsets, gt, num_gt,
                                     m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA, m.HEAD.get("COST_REG_WEIGHTS", 1.5), 2.5,
-                                    pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, ws, ld=self._ld())
+                                    pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, ws, ld=self.cls_ld)
             return
         ops.ota_assign(pl.points, pl.lvl_start, self.strides, pl.logits, self.num_classes, pl.offsets, gt, num_gt,
                        m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA, m.HEAD.get("COST_REG_WEIGHTS", 1.5), 2.5,
-                       m.HEAD.get("CANDIDATE_K", 10), pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, pl.ota_ws, ld=self._ld())
+                       m.HEAD.get("CANDIDATE_K", 10), pl.labels, pl.gt_offsets, pl.gt_ctr, pl.stats, pl.ota_ws, ld=self.cls_ld)
 
     def get_losses(self, inputs):
         """OTA.get_losses (ota.py:62-74) + emd_losses (:183-233); pl.gt_ctr holds the IoU targets, pl.stats = (num_fg, 2 num_fg)."""
@@ -311,7 +307,7 @@ class OTA(FCOS):
         pl.loss_buf.zero_()
         rows = pl.N * pl.pyr.pix_per_img
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA,
-                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self._ld())
+                               pl.stats[0:1], 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self.cls_ld)
         ops.iou_ltrb_fwd_bwd(pl.offsets, pl.gt_offsets, None, pl.labels, rows, self.iou_loss_type, pl.stats[0:1], 2.0, pl.loss_buf[1:2],
                              pl.d_off)
         ops.bce_logits_fwd_bwd(pl.raw, pl.gt_ctr, pl.labels, rows, pl.stats[1:2], pl.loss_buf[2:3], pl.d_ctr, ld=8, off=4)

@@ -932,19 +932,13 @@ class FPNDetector:
         s = self._detect_scratch(N, Ln, k, (rows, K) if logits is not None else None)
         if logits is not None:
             ops.det_select(logits, N, rows, K, row_off, lvl_rows, k, t.CLS_THRESHOLD, s["tk_idx"], s["tk_sc"], s["tk_cnt"], s["sel_ws"],
-                           ctr=ctr, ctr_ld=ctr_ld, ctr_off=ctr_off, ld=cls_ld if cls_ld not in (None, K) else None)
+                           ctr=ctr, ctr_ld=ctr_ld, ctr_off=ctr_off, ld=cls_ld)
         else:
             ops.segment_topk(scores, N, rows * K, 1, 1, 0, [r * K for r in row_off], [r * K for r in lvl_rows], k, s["tk_idx"], s["tk_sc"],
                              s["tk_cnt"], min_score=t.CLS_THRESHOLD)
-        # One image goes through the single-image entries of the C ABI: they launch the same two kernels with a one-image grid, and the
-        # launch audit of single-image inference (tests/test_frcnn_audit_gpu.py) names every entry that path may reach.
-        if N == 1:
-            ops.det_candidates(mode, s["tk_idx"], s["tk_sc"], s["tk_cnt"], Ln, k, row_off, K, anchors, offsets, off_ld, A, mean, std,
-                               item_boxes, s["boxes"], s["sc"], s["labels"])
-        else:
-            ops.det_candidates_batched(mode, s["tk_idx"], s["tk_sc"], s["tk_cnt"], N, Ln, k, row_off, K, anchors, offsets,
-                                       offsets.numel() // N if offsets is not None else 0, off_ld, A, mean, std, item_boxes, rows * K,
-                                       s["boxes"], s["sc"], s["labels"])
+        ops.det_candidates(mode, s["tk_idx"], s["tk_sc"], s["tk_cnt"], N, Ln, k, row_off, K, anchors, offsets,
+                           offsets.numel() // N if offsets is not None else 0, off_ld, A, mean, std, item_boxes, rows * K,
+                           s["boxes"], s["sc"], s["labels"])
         max_out = t.MAX_BOXES_PER_IMAGE
         s["num"].zero_()
         ops.nms_batched(s["boxes"], s["sc"], s["labels"], t.IOU_THRESHOLD, max_out, s["keep"], s["num"], s["nms_ws"])
@@ -952,10 +946,7 @@ class FPNDetector:
         ob = torch.empty((N, max_out, 4), dtype=torch.float32, device=dev)
         osc = torch.empty((N, max_out), dtype=torch.float32, device=dev)
         ol = torch.empty((N, max_out), dtype=torch.int32, device=dev)
-        if N == 1:
-            ops.det_finalize(s["boxes"], s["sc"], s["labels"], s["keep"], s["num"], max_out, info[0].contiguous(), ob, osc, ol)
-        else:
-            ops.det_finalize_batched(s["boxes"], s["sc"], s["labels"], s["keep"], s["num"], max_out, info, ob, osc, ol)
+        ops.det_finalize(s["boxes"], s["sc"], s["labels"], s["keep"], s["num"], max_out, info, ob, osc, ol)
         outs = []
         for i, n in enumerate(s["num"].tolist()):
             if n == 0:

@@ -37,6 +37,6 @@ class FreeAnchor(RetinaNet):
         ops.freeanchor_loss_fwd_bwd(pl.logits, pl.offsets, self.box_ld, self.num_anchors, pl.anchors, self.num_classes, gt, num_gt,
                                     m.BOX_REG.MEAN, m.BOX_REG.STD, m.BUCKET.BOX_IOU_THRESH, bucket, m.LOSSES.SMOOTH_L1_BETA,
                                     m.LOSSES.REG_LOSS_WEIGHT, m.LOSSES.FOCAL_LOSS_ALPHA, m.LOSSES.FOCAL_LOSS_GAMMA, pl.loss_buf,
-                                    pl.d_logits, pl.d_offsets, ws, cls_ld=self.cls_ld if self.cls_ld != self.num_classes else None)
+                                    pl.d_logits, pl.d_offsets, ws, cls_ld=self.cls_ld)
         pos_loss, neg_loss = pl.loss_buf[0], pl.loss_buf[1]
         return {"total_loss": pos_loss + neg_loss, "pos_loss": pos_loss, "neg_loss": neg_loss}

@@ -194,8 +194,7 @@ class RetinaNet(FPNDetector):
         pl.loss_buf.zero_()
         rows = N * pl.A_total
         ops.focal_loss_fwd_bwd(pl.logits, pl.labels, rows, self.num_classes, m.LOSSES.FOCAL_LOSS_ALPHA,
-                               m.LOSSES.FOCAL_LOSS_GAMMA, pl.num_fg, 1.0, pl.loss_buf[0:1], pl.d_logits,
-                               ld=self.cls_ld if self.cls_ld != self.num_classes else None)
+                               m.LOSSES.FOCAL_LOSS_GAMMA, pl.num_fg, 1.0, pl.loss_buf[0:1], pl.d_logits, ld=self.cls_ld)
         ops.smooth_l1_fwd_bwd(pl.offsets, pl.gt_offsets, pl.labels, pl.pyr.pixels, self.num_anchors, self.box_ld,
                               m.LOSSES.SMOOTH_L1_BETA, pl.num_fg, m.LOSSES.REG_LOSS_WEIGHT, pl.loss_buf[1:2], pl.d_offsets)
         cls_loss, reg_loss = pl.loss_buf[0], pl.loss_buf[1]

@@ -526,17 +526,11 @@ def ota_assign_workspace_bytes(N, P):
 
 def ota_assign(points, lvl_start, strides, logits, K, pred_ltrb, gt_boxes, num_gt, alpha, gamma, reg_weight, center_radius,
                candidate_k, labels, targets, gt_ious, stats, ws, ld=None):
-    """OTA.get_ground_truth, top-k matcher (models/det/ota.py:76-181).  ld: slots per row of `logits` (round_up(K, 8)) when they are padded."""
+    """OTA.get_ground_truth, top-k matcher (models/det/ota.py:76-181).  ld: slots per row of `logits` (round_up(K, 8)); None: compact, K."""
     P = points.shape[0]
     N, Gmax = gt_boxes.shape[0], gt_boxes.shape[1]
-    if ld is not None:
-        check(L().bd_ota_assign_ld(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), int(ld), ptr(pred_ltrb),
-                                   ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight), float(center_radius),
-                                   int(candidate_k), ptr(labels), ptr(targets), ptr(gt_ious), ptr(stats), ptr(ws),
-                                   ws.numel() * ws.element_size(), stream_ptr()), "bd_ota_assign_ld")
-        return
-    check(L().bd_ota_assign(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), ptr(pred_ltrb),
-                            ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight), float(center_radius),
+    check(L().bd_ota_assign(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K),
+                            int(K if ld is None else ld), ptr(pred_ltrb), ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight), float(center_radius),
                             int(candidate_k), ptr(labels), ptr(targets), ptr(gt_ious), ptr(stats), ptr(ws),
                             ws.numel() * ws.element_size(), stream_ptr()), "bd_ota_assign")
 
@@ -550,14 +544,8 @@ def ota_assign_sinkhorn(points, lvl_start, strides, logits, K, pred_ltrb, gt_box
     """OTA.get_ground_truth with the SinkhornMatcher (models/det/ota.py:153-157, layers/common/matcher.py:106-121).  ld: as ota_assign."""
     P = points.shape[0]
     N, Gmax = gt_boxes.shape[0], gt_boxes.shape[1]
-    if ld is not None:
-        check(L().bd_ota_assign_sinkhorn_ld(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), int(ld),
-                                            ptr(pred_ltrb), ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight),
-                                            float(center_radius), int(topq), float(eps), int(iters), ptr(labels), ptr(targets), ptr(gt_ious),
-                                            ptr(stats), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "bd_ota_assign_sinkhorn_ld")
-        return
-    check(L().bd_ota_assign_sinkhorn(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K), ptr(pred_ltrb),
-                                     ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight),
+    check(L().bd_ota_assign_sinkhorn(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(logits), int(K),
+                                     int(K if ld is None else ld), ptr(pred_ltrb), ptr(gt_boxes), ptr(num_gt), N, Gmax, float(alpha), float(gamma), float(reg_weight),
                                      float(center_radius), int(topq), float(eps), int(iters), ptr(labels), ptr(targets), ptr(gt_ious),
                                      ptr(stats), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), "bd_ota_assign_sinkhorn")
 
@@ -569,18 +557,11 @@ def freeanchor_workspace_bytes(N, Gmax, bucket, A):
 def freeanchor_loss_fwd_bwd(logits, offsets, box_ld, anchors_per_pix, anchors, K, gt_boxes, num_gt, mean, std, iou_thresh, bucket,
                             beta, reg_weight, alpha, gamma, loss_out, d_logits, d_offsets, ws, cls_ld=None):
     """FreeAnchor bag losses + gradients (models/det/free_anchor.py:38-142); loss_out: fp32[2] = (pos_loss, neg_loss).
-    cls_ld: slots per anchor row of logits / d_logits (round_up(K, 8)) when they are padded."""
+    cls_ld: slots per anchor row of logits / d_logits (K or round_up(K, 8)); None: compact, K."""
     A = anchors.shape[0]
     N, Gmax = gt_boxes.shape[0], gt_boxes.shape[1]
-    if cls_ld is not None:
-        check(L().bd_freeanchor_loss_fwd_bwd_ld(ptr(logits), int(cls_ld), ptr(offsets), int(box_ld), int(anchors_per_pix), ptr(anchors), A,
-                                                int(K), ptr(gt_boxes), ptr(num_gt), N, Gmax, f32arr(mean), f32arr(std), float(iou_thresh),
-                                                int(bucket), float(beta), float(reg_weight), float(alpha), float(gamma), ptr(loss_out),
-                                                ptr(d_logits), ptr(d_offsets), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
-              "bd_freeanchor_loss_fwd_bwd_ld")
-        return
-    check(L().bd_freeanchor_loss_fwd_bwd(ptr(logits), ptr(offsets), int(box_ld), int(anchors_per_pix), ptr(anchors), A, int(K),
-                                         ptr(gt_boxes), ptr(num_gt), N, Gmax, f32arr(mean), f32arr(std), float(iou_thresh),
+    check(L().bd_freeanchor_loss_fwd_bwd(ptr(logits), int(K if cls_ld is None else cls_ld), ptr(offsets), int(box_ld),
+                                         int(anchors_per_pix), ptr(anchors), A, int(K), ptr(gt_boxes), ptr(num_gt), N, Gmax, f32arr(mean), f32arr(std), float(iou_thresh),
                                          int(bucket), float(beta), float(reg_weight), float(alpha), float(gamma), ptr(loss_out),
                                          ptr(d_logits), ptr(d_offsets), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
           "bd_freeanchor_loss_fwd_bwd")
@@ -638,13 +619,12 @@ def rpn_proposals_workspace_bytes(N, lvl_pixels, A, pre_k, post_k):
 
 def rpn_proposals(raw, ldc, A, cls_off, box_off, geom: Geom, anchors, im_info, mean, std, pre_k, nms_thresh, post_k, rois, num_rois, ws,
                   joint_nms=False):
-    """joint_nms: the batched NMS as one problem per image (bd_rpn_proposals_joint: rounds 1-4) instead of level by level + merge."""
+    """joint_nms: the batched NMS as one problem per image (rounds 1-4) instead of level by level + merge."""
     lvl_pixels = [h * w for h, w in zip(geom.H, geom.W)]
-    fn = L().bd_rpn_proposals_joint if joint_nms else L().bd_rpn_proposals
-    check(fn(ptr(raw), ldc, A, cls_off, box_off, geom.N, geom.pix_per_img, geom.nlev, i32arr(geom.off),
-             i32arr(lvl_pixels), ptr(anchors), ptr(im_info), im_info.shape[1], f32arr(mean), f32arr(std),
-             int(pre_k), float(nms_thresh), int(post_k), ptr(rois), ptr(num_rois), ptr(ws),
-             ws.numel() * ws.element_size(), stream_ptr()), "bd_rpn_proposals")
+    check(L().bd_rpn_proposals(ptr(raw), ldc, A, cls_off, box_off, geom.N, geom.pix_per_img, geom.nlev, i32arr(geom.off),
+                               i32arr(lvl_pixels), ptr(anchors), ptr(im_info), im_info.shape[1], f32arr(mean), f32arr(std),
+                               int(pre_k), float(nms_thresh), int(post_k), ptr(rois), ptr(num_rois), ptr(ws),
+                               ws.numel() * ws.element_size(), int(bool(joint_nms)), stream_ptr()), "bd_rpn_proposals")
 
 
 def rcnn_sample_targets(rois, num_rois, gt_boxes, num_gt, keys_fg, keys_bg, num_samples, num_fg_max, fg_thresh, bg_hi, bg_lo,
@@ -746,11 +726,9 @@ def rcnn_loss_fwd_bwd(raw, ld, K, box_off, labels, targets, R, beta, num_samples
 
 # ---- inference post-processing ----------------------------------------------------------------------------
 def det_scores(logits, rows, K, scores, ctr=None, ctr_ld=1, ctr_off=0, ld=None):
-    """ld: slots per row of `logits` when they are padded behind the K classes (scores stays [rows][K])."""
-    if ld is not None:
-        check(L().bd_det_scores_ld(ptr(logits), int(ld), ptr(ctr), ctr_ld, ctr_off, rows, K, ptr(scores), stream_ptr()), "bd_det_scores_ld")
-        return
-    check(L().bd_det_scores(ptr(logits), ptr(ctr), ctr_ld, ctr_off, rows, K, ptr(scores), stream_ptr()), "bd_det_scores")
+    """ld: slots per row of `logits` when they are padded behind the K classes (scores stays [rows][K]); None: compact, K."""
+    check(L().bd_det_scores(ptr(logits), int(K if ld is None else ld), ptr(ctr), ctr_ld, ctr_off, rows, K, ptr(scores), stream_ptr()),
+          "bd_det_scores")
 
 
 def rcnn_predict(raw, ld, K, box_off, rois, num_rois, rois_per_img, mean, std, scores, boxes):
@@ -759,16 +737,19 @@ def rcnn_predict(raw, ld, K, box_off, rois, num_rois, rois_per_img, mean, std, s
                               ptr(scores), ptr(boxes), stream_ptr()), "bd_rcnn_predict")
 
 
-def det_candidates(mode, topk_idx, topk_score, topk_cnt, Ln, k, lvl_row_off, K, anchors, offsets, off_ld, A, mean, std, item_boxes,
-                   boxes, scores, labels):
-    check(L().bd_det_candidates(mode, ptr(topk_idx), ptr(topk_score), ptr(topk_cnt), Ln, k, i32arr(lvl_row_off), K, ptr(anchors),
-                                ptr(offsets), off_ld, A, f32arr(mean), f32arr(std), ptr(item_boxes), ptr(boxes), ptr(scores),
-                                ptr(labels), stream_ptr()), "bd_det_candidates")
+def det_candidates(mode, topk_idx, topk_score, topk_cnt, B, Ln, k, lvl_row_off, K, anchors, offsets, off_stride, off_ld, A, mean, std,
+                   item_boxes, item_stride, boxes, scores, labels):
+    """B images in one launch (one image: B = 1); off_stride / item_stride: bf16 elements / boxes between the offsets / item_boxes of two images."""
+    check(L().bd_det_candidates(mode, ptr(topk_idx), ptr(topk_score), ptr(topk_cnt), B, Ln, k, i32arr(lvl_row_off), K, ptr(anchors),
+                                ptr(offsets), off_stride, off_ld, A, f32arr(mean), f32arr(std), ptr(item_boxes), item_stride,
+                                ptr(boxes), ptr(scores), ptr(labels), stream_ptr()), "bd_det_candidates")
 
 
 def det_finalize(boxes, scores, labels, keep, num_keep, max_out, im_info, out_boxes, out_scores, out_labels):
-    check(L().bd_det_finalize(ptr(boxes), ptr(scores), ptr(labels), ptr(keep), ptr(num_keep), max_out, ptr(im_info), ptr(out_boxes),
-                              ptr(out_scores), ptr(out_labels), stream_ptr()), "bd_det_finalize")
+    """scores [B][C], im_info [B][>= 4] (or the one row of B = 1): every image is rescaled and clipped by its own row."""
+    B, Cn = scores.shape
+    check(L().bd_det_finalize(ptr(boxes), ptr(scores), ptr(labels), ptr(keep), ptr(num_keep), B, Cn, max_out, ptr(im_info),
+                              im_info.shape[-1], ptr(out_boxes), ptr(out_scores), ptr(out_labels), stream_ptr()), "bd_det_finalize")
 
 
 def det_select_workspace_bytes(B, Ln, rows, K, k):
@@ -778,43 +759,20 @@ def det_select_workspace_bytes(B, Ln, rows, K, k):
 def det_select(logits, B, rows, K, seg_start, seg_rows, k, min_score, out_idx, out_score, out_cnt, ws, ctr=None, ctr_ld=1, ctr_off=0,
                ld=None):
     """Scores + per-level top-k of B images straight from the bf16 logits [B][rows][K] (= det_scores -> segment_topk(min_score), bit for
-    bit); seg_start / seg_rows in rows.  ld: slots per row of `logits` (round_up(K, 8)) when they are padded: same indices, scores, counts."""
-    if ld is not None:
-        check(L().bd_det_select_ld(ptr(logits), int(ld), ptr(ctr), ctr_ld, ctr_off, B, rows, K, len(seg_start), i32arr(seg_start),
-                                   i32arr(seg_rows), k, float(min_score), ptr(out_idx), ptr(out_score), ptr(out_cnt), ptr(ws),
-                                   ws.numel() * ws.element_size(), stream_ptr()), "bd_det_select_ld")
-        return
-    check(L().bd_det_select(ptr(logits), ptr(ctr), ctr_ld, ctr_off, B, rows, K, len(seg_start), i32arr(seg_start), i32arr(seg_rows), k,
-                            float(min_score), ptr(out_idx), ptr(out_score), ptr(out_cnt), ptr(ws), ws.numel() * ws.element_size(),
-                            stream_ptr()), "bd_det_select")
-
-
-def det_candidates_batched(mode, topk_idx, topk_score, topk_cnt, B, Ln, k, lvl_row_off, K, anchors, offsets, off_stride, off_ld, A, mean, std,
-                           item_boxes, item_stride, boxes, scores, labels):
-    check(L().bd_det_candidates_batched(mode, ptr(topk_idx), ptr(topk_score), ptr(topk_cnt), B, Ln, k, i32arr(lvl_row_off), K, ptr(anchors),
-                                        ptr(offsets), off_stride, off_ld, A, f32arr(mean), f32arr(std), ptr(item_boxes), item_stride,
-                                        ptr(boxes), ptr(scores), ptr(labels), stream_ptr()), "bd_det_candidates_batched")
-
-
-def det_finalize_batched(boxes, scores, labels, keep, num_keep, max_out, im_info, out_boxes, out_scores, out_labels):
-    B, Cn = scores.shape
-    check(L().bd_det_finalize_batched(ptr(boxes), ptr(scores), ptr(labels), ptr(keep), ptr(num_keep), B, Cn, max_out, ptr(im_info),
-                                      im_info.shape[1], ptr(out_boxes), ptr(out_scores), ptr(out_labels), stream_ptr()),
-          "bd_det_finalize_batched")
+    bit); seg_start / seg_rows in rows.  ld: slots per row of `logits` (round_up(K, 8)) when they are padded: same indices, scores, counts;
+    None: compact, K."""
+    check(L().bd_det_select(ptr(logits), int(K if ld is None else ld), ptr(ctr), ctr_ld, ctr_off, B, rows, K, len(seg_start),
+                            i32arr(seg_start), i32arr(seg_rows), k, float(min_score), ptr(out_idx), ptr(out_score), ptr(out_cnt), ptr(ws),
+                            ws.numel() * ws.element_size(), stream_ptr()), "bd_det_select")
 
 
 # ---- losses -----------------------------------------------------------------------------------------------
 def focal_loss_fwd_bwd(logits, labels, rows, K, alpha, gamma, norm, grad_scale, loss_sum, dlogits, general=False, ld=None):
-    """general: the general-gamma kernel also for gamma == 2 (bd_focal_loss_fwd_bwd_general)
-    ld: slots per row of logits / dlogits (round_up(K, 8)) for a K that is no multiple of 8 (bd_focal_loss_fwd_bwd_ld)"""
-    if ld is not None:
-        check(L().bd_focal_loss_fwd_bwd_ld(ptr(logits), ptr(labels), rows, K, int(ld), float(alpha), float(gamma), ptr(norm),
-                                           int(norm.dtype == torch.float32), float(grad_scale), ptr(loss_sum), ptr(dlogits), int(bool(general)),
-                                           stream_ptr()), "bd_focal_loss_fwd_bwd_ld")
-        return
-    fn = L().bd_focal_loss_fwd_bwd_general if general else L().bd_focal_loss_fwd_bwd
-    check(fn(ptr(logits), ptr(labels), rows, K, float(alpha), float(gamma), ptr(norm),
-             int(norm.dtype == torch.float32), float(grad_scale), ptr(loss_sum), ptr(dlogits), stream_ptr()), "bd_focal_loss_fwd_bwd")
+    """general: the general-gamma kernel also for gamma == 2
+    ld: slots per row of logits / dlogits (round_up(K, 8)) for a K that is no multiple of 8; None: compact, K"""
+    check(L().bd_focal_loss_fwd_bwd(ptr(logits), ptr(labels), rows, K, int(K if ld is None else ld), float(alpha), float(gamma), ptr(norm),
+                                    int(norm.dtype == torch.float32), float(grad_scale), ptr(loss_sum), ptr(dlogits), int(bool(general)),
+                                    stream_ptr()), "bd_focal_loss_fwd_bwd")
 
 
 def smooth_l1_fwd_bwd(pred, target, labels, pixels, A, ld, beta, norm, weight, loss_sum, dpred):
@@ -835,11 +793,6 @@ def iou_ltrb_fwd_bwd(pred, target, weight, labels, rows, loss_type, norm, loss_w
     """loss_type: a code of IOU_LOSS_TYPES."""
     check(L().bd_iou_ltrb_fwd_bwd(ptr(pred), ptr(target), ptr(weight), ptr(labels), rows, int(loss_type), ptr(norm), float(loss_weight),
                                   ptr(loss_sum), ptr(dpred), stream_ptr()), "bd_iou_ltrb_fwd_bwd")
-
-
-def giou_ltrb_fwd_bwd(pred, target, weight, labels, rows, norm, loss_weight, loss_sum, dpred):
-    check(L().bd_giou_ltrb_fwd_bwd(ptr(pred), ptr(target), ptr(weight), ptr(labels), rows, ptr(norm), float(loss_weight),
-                                   ptr(loss_sum), ptr(dpred), stream_ptr()), "bd_giou_ltrb_fwd_bwd")
 
 
 def bce_logits_fwd_bwd(pred, target, labels, rows, norm, loss_sum, dpred, ld=1, off=0):

@@ -458,60 +458,44 @@ int bd_atss_assign(const float* points, int P, const int32_t* lvl_start_host, co
 /* OTA.get_ground_truth with the top-k matcher (models/det/ota.py:76-181, layers/common/matcher.py:123-161; cfg MATCHING =
  * "topk", the reference default): per gt the dynamic number k = max(1, int(sum of the `candidate_k` largest IoUs with the predicted
  * boxes)) of lowest-cost points, cost = focal classification cost + reg_weight * -log(IoU) + 1e6 outside the gt / its
- * center_radius*stride centre box; a point taken by several gts goes to the gt of lowest cost.  logits bf16 [N*P][K], pred_ltrb
- * bf16 [N*P][4] (the head's decoded l,t,r,b), points fp32 [P][2].  Outputs: labels int32 [N][P] (class, 0 = background), targets
+ * center_radius*stride centre box; a point taken by several gts goes to the gt of lowest cost.  logits bf16 [N*P][ld], ld = K (DATA.NUM_CLASSES
+ * of the config) rounded up to a multiple of 8: the first K slots of a row are the classes, the rest padding that no cost reads; ld == K is
+ * the compact layout.  pred_ltrb bf16 [N*P][4] (the head's decoded l,t,r,b), points fp32 [P][2].  Outputs: labels int32 [N][P] (class, 0 = background), targets
  * fp32 [N][P][4] (ltrb), gt_ious fp32 [N][P]; stats[0] = number of foreground points, stats[1] = 2 * stats[0] (the normaliser
  * of the 0.5-weighted IoU-branch loss).  Ties: lowest point / gt index.  ws: bd_ota_assign_workspace_bytes. */
 size_t bd_ota_assign_workspace_bytes(int N, int P);
 int bd_ota_assign(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L, const void* logits,
-                  int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
+                  int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
                   float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
                   float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream);
-/* Any class count (bd_version() >= 104; ota.py:76-181 with DATA.NUM_CLASSES of the config): logits bf16 [N*P][ld], ld = K rounded up to a
- * multiple of 8, the first K slots of a row the classes, the rest padding that no cost reads.  ld == K is bd_ota_assign. */
-int bd_ota_assign_ld(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L, const void* logits,
-                     int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, float alpha,
-                     float gamma, float reg_weight, float center_radius, int candidate_k, int32_t* labels, float* targets,
-                     float* gt_ious, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream);
 
 /* The same assignment with the Sinkhorn matcher (cfg MATCHING = "sinkhorn"; layers/common/matcher.py:106-121,
  * layers/blocks/sinkhorn_distance.py:22-50): supplies mu_g = max(1, int(sum of the `topq` = 20 largest in-box IoUs)), background
  * supply P - sum mu, demands 1; `iters` = 50 log-domain Sinkhorn updates with regulariser eps = 0.1 on the (G+1) x P cost (last row:
  * the background focal cost); each point goes to the row of largest plan entry after every row is rescaled by its maximum (ties:
- * lowest row).  gt_ious are the IoUs masked by the in-box test (ota.py:155).  Gmax + 1 <= 512.  Outputs as bd_ota_assign. */
+ * lowest row).  gt_ious are the IoUs masked by the in-box test (ota.py:155).  Gmax + 1 <= 512.  logits [N*P][ld] and
+ * outputs as bd_ota_assign. */
 size_t bd_ota_sinkhorn_workspace_bytes(int N, int P, int Gmax);
 int bd_ota_assign_sinkhorn(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L,
-                           const void* logits, int K, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt, int N,
-                           int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps, int iters,
-                           int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
+                           const void* logits, int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt,
+                           int N, int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps,
+                           int iters, int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
                            bd_stream_t stream);
-/* ... on logits bf16 [N*P][ld] as bd_ota_assign_ld (ota.py:76-181, matcher.py:106-121). */
-int bd_ota_assign_sinkhorn_ld(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L,
-                              const void* logits, int K, int ld, const void* pred_ltrb, const float* gt_boxes, const int32_t* num_gt,
-                              int N, int Gmax, float alpha, float gamma, float reg_weight, float center_radius, int topq, float eps,
-                              int iters, int32_t* labels, float* targets, float* gt_ious, float* stats, void* ws, size_t ws_bytes,
-                              bd_stream_t stream);
 
 /* FreeAnchor.get_losses after the network forward (models/det/free_anchor.py:38-142): positive bag loss over the `bucket`
  * anchors of largest IoU per gt (ties at the boundary: lowest anchor index) and negative loss over every (anchor, class) with the
  * box probabilities of the decoded predictions (two gts of one class claiming an anchor: the later gt's value), both with their
- * gradients.  logits bf16 [N*A][K]; offsets bf16 [N*A/anchors_per_pix][box_ld] (anchor a of a pixel at columns 4a..4a+3);
+ * gradients.  logits / d_logits bf16 [N*A][cls_ld], cls_ld = K (the compact layout) or K rounded up to a multiple of 8 -- the slots >= K of
+ * an anchor's row are padding: no loss, d_logits written as +0; offsets bf16 [N*A/anchors_per_pix][box_ld] (anchor a of a pixel at columns 4a..4a+3);
  * anchors fp32 [A][4]; gt [N][Gmax][5] (class 1-based), num_gt int32 [N].  loss_out[0] = alpha * pos / max(1, sum num_gt),
  * loss_out[1] = (1 - alpha) * neg / max(1, sum num_gt * bucket).  d_logits / d_offsets are overwritten (d_offsets zero outside
  * the bags).  Deterministic: fixed-order reductions, bag gradients applied gt after gt.  ws: bd_freeanchor_workspace_bytes. */
 size_t bd_freeanchor_workspace_bytes(int N, int Gmax, int bucket, int A);
-int bd_freeanchor_loss_fwd_bwd(const void* logits, const void* offsets, int box_ld, int anchors_per_pix, const float* anchors,
-                               int A, int K, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, const float* mean4,
-                               const float* std4, float iou_thresh, int bucket, float beta, float reg_weight, float alpha,
-                               float gamma, float* loss_out, void* d_logits, void* d_offsets, void* ws, size_t ws_bytes,
+int bd_freeanchor_loss_fwd_bwd(const void* logits, int cls_ld, const void* offsets, int box_ld, int anchors_per_pix,
+                               const float* anchors, int A, int K, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax,
+                               const float* mean4, const float* std4, float iou_thresh, int bucket, float beta, float reg_weight,
+                               float alpha, float gamma, float* loss_out, void* d_logits, void* d_offsets, void* ws, size_t ws_bytes,
                                bd_stream_t stream);
-/* The same (free_anchor.py:38-142) on logits / d_logits bf16 [N*A][cls_ld] (bd_version() >= 104): cls_ld = K (bd_freeanchor_loss_fwd_bwd)
- * or K rounded up to a multiple of 8 -- the slots >= K of an anchor's row are padding: no loss, d_logits written as +0. */
-int bd_freeanchor_loss_fwd_bwd_ld(const void* logits, int cls_ld, const void* offsets, int box_ld, int anchors_per_pix,
-                                  const float* anchors, int A, int K, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax,
-                                  const float* mean4, const float* std4, float iou_thresh, int bucket, float beta, float reg_weight,
-                                  float alpha, float gamma, float* loss_out, void* d_logits, void* d_offsets, void* ws, size_t ws_bytes,
-                                  bd_stream_t stream);
 
 /* layers/common/post_processing.py:17-47 batched_nms (class-offset trick + greedy NMS, suppress iff IoU > thr).
  * boxes [n][4], scores [n], idxs [n] (may be NULL = plain NMS).  keep: int32[n] (descending score order),
@@ -528,22 +512,14 @@ int bd_batched_nms(const float* boxes, const float* scores, const int32_t* idxs,
 /* sigmoid_focal_loss (layers/losses/sigmoid_focal_loss.py:9-36) as used at models/det/retinanet.py:148-156:
  * rows with label < 0 ignored, one-hot column = label-1 for label > 0; loss_sum[0] += sum(loss) / max(1,num_fg),
  * dlogits = dloss/dlogit * grad_scale / max(1,num_fg).  norm: device float/int scalar holding num_fg
- * (norm_is_float selects the type).  logits/dlogits bf16 [rows][K]. */
-int bd_focal_loss_fwd_bwd(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha,
-                          float gamma, const void* norm, int norm_is_float, float grad_scale,
-                          float* loss_sum, void* dlogits, bd_stream_t stream);
-/* gamma == 2 takes its own instance (one sigmoid / log per logit, the positive class patched in); bd_focal_loss_fwd_bwd_general runs the
- * general-gamma kernel whatever gamma is (the instance is checked against it). */
-int bd_focal_loss_fwd_bwd_general(const void* logits, const int32_t* labels, int64_t rows, int K, float alpha,
-                                  float gamma, const void* norm, int norm_is_float, float grad_scale,
-                                  float* loss_sum, void* dlogits, bd_stream_t stream);
-/* Any class count (bd_version() >= 104; sigmoid_focal_loss.py:9-36 at retinanet.py:148-156 / fcos.py:146-151 with the config's
- * DATA.NUM_CLASSES): logits / dlogits bf16 [rows][ld], ld = K rounded up to a multiple of 8.  The first K slots of a row are the classes;
- * the others are padding: they add no loss and their gradient is written as +0.  general != 0 selects the general-gamma kernel as
- * bd_focal_loss_fwd_bwd_general does.  ld == K gives the bits of the two entries above. */
-int bd_focal_loss_fwd_bwd_ld(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma,
-                             const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, int general,
-                             bd_stream_t stream);
+ * (norm_is_float selects the type).  Any class count (sigmoid_focal_loss.py:9-36 at retinanet.py:148-156 / fcos.py:146-151 with the
+ * config's DATA.NUM_CLASSES): logits / dlogits bf16 [rows][ld], ld = K rounded up to a multiple of 8; ld == K is the compact layout.  The
+ * first K slots of a row are the classes; the others are padding: they add no loss and their gradient is written as +0.
+ * gamma == 2 takes its own instance (one sigmoid / log per logit, the positive class patched in); general != 0 runs the general-gamma
+ * kernel whatever gamma is (the instance is checked against it). */
+int bd_focal_loss_fwd_bwd(const void* logits, const int32_t* labels, int64_t rows, int K, int ld, float alpha, float gamma,
+                          const void* norm, int norm_is_float, float grad_scale, float* loss_sum, void* dlogits, int general,
+                          bd_stream_t stream);
 
 /* (bd_version() >= 105) The focal, smooth-L1, IoU and BCE launches of this section run at most this many blocks of 256 threads; past
  * 256 x that many work items (rows for the IoU and BCE losses) a thread strides over more than one. */
@@ -560,13 +536,9 @@ int bd_smooth_l1_fwd_bwd(const void* pred, const float* target, const int32_t* l
  * models/det/ota.py:211-216) on the rows with labels > 0: loss_sum[0] = loss_weight / max(1, *norm) * sum(loss * weight), dpred its bf16
  * gradient (zero rows for labels <= 0).  pred [rows][4] bf16 l, t, r, b; weight NULL = 1.  loss_type as bd_iou_loss_ltrb, eps = 1e-8:
  * 0 "iou" (-log max(iou, eps); zero gradient where iou <= eps), 1 "linear_iou" (1 - iou), 2 "giou" (1 - giou), 3 "square_iou" (1 - iou^2);
- * any other code: BD_EINVAL, nothing launched. */
+ * any other code: BD_EINVAL, nothing launched.  norm = max(1, sum_ctr) in FCOS. */
 int bd_iou_ltrb_fwd_bwd(const void* pred, const float* target, const float* weight, const int32_t* labels, int64_t rows, int loss_type,
                         const float* norm, float loss_weight, float* loss_sum, void* dpred, bd_stream_t stream);
-/* bd_iou_ltrb_fwd_bwd with loss_type 2 ("giou"); norm = max(1, sum_ctr) in FCOS. */
-int bd_giou_ltrb_fwd_bwd(const void* pred, const float* target, const float* weight, const int32_t* labels,
-                         int64_t rows, const float* norm, float loss_weight, float* loss_sum, void* dpred,
-                         bd_stream_t stream);
 
 /* binary_cross_entropy with logits over fg rows (layers/losses/cross_entropy.py:7-29, fcos.py:166-170).
  * Logit of row i at pred[i*ld + off] (the centre-ness channel of the fused bbox/ctrness conv output);
@@ -691,21 +663,16 @@ int bd_nms_batched(const float* boxes, const float* scores, const int32_t* idxs,
 /* RPN.find_top_rpn_proposals (rpn.py:134-186) for the whole batch: per image and level top pre_k scores ->
  * BoxCoder.decode -> clip to im_info[:, 0:2] -> drop empty boxes -> NMS across levels (level = NMS class) ->
  * first post_k.  raw: bf16 [N*pix_per_img][ldc], objectness logit of cell anchor a at channel cls_off + a, its
- * offsets at box_off + 4a.  anchors [pix_per_img*A][4].  rois [N][post_k][4] (zero past num_rois[n]). */
+ * offsets at box_off + 4a.  anchors [pix_per_img*A][4].  rois [N][post_k][4] (zero past num_rois[n]).
+ * joint_nms == 0 runs the batched NMS level by level (N x L independent problems of <= pre_k boxes, then a merge into the joint order:
+ * round 5); joint_nms != 0 runs it as one problem per image (rounds 1-4).  The proposals are the same bit for bit: boxes of
+ * different levels never overlap after batched_nms's shift (post_processing.py:44-45), which both forms apply. */
 size_t bd_rpn_proposals_workspace_bytes(int N, int L, const int32_t* lvl_pixels_host, int A, int pre_k, int post_k);
 int bd_rpn_proposals(const void* raw, int ldc, int A, int cls_off, int box_off, int N, int64_t pix_per_img, int L,
                      const int32_t* lvl_pix_off_host, const int32_t* lvl_pixels_host, const float* anchors,
                      const float* im_info, int info_ld, const float* mean4_host, const float* std4_host, int pre_k,
                      float nms_thresh, int post_k, float* rois, int32_t* num_rois, void* ws, size_t ws_bytes,
-                     bd_stream_t stream);
-/* bd_rpn_proposals runs its batched NMS level by level (N x L independent problems of <= pre_k boxes, then a merge into the joint order:
- * round 5); bd_rpn_proposals_joint runs it as one problem per image (rounds 1-4).  The proposals are the same bit for bit: boxes of
- * different levels never overlap after batched_nms's shift (post_processing.py:44-45), which both forms apply. */
-int bd_rpn_proposals_joint(const void* raw, int ldc, int A, int cls_off, int box_off, int N, int64_t pix_per_img, int L,
-                           const int32_t* lvl_pix_off_host, const int32_t* lvl_pixels_host, const float* anchors,
-                           const float* im_info, int info_ld, const float* mean4_host, const float* std4_host, int pre_k,
-                           float nms_thresh, int post_k, float* rois, int32_t* num_rois, void* ws, size_t ws_bytes,
-                           bd_stream_t stream);
+                     int joint_nms, bd_stream_t stream);
 
 /* RCNN.get_ground_truth (rcnn.py:95-147) per image: candidates = proposals + gt boxes, IoU max/argmax over the gts,
  * fg (>= fg_thresh) / bg ([bg_lo, bg_hi)) masks, random subsampling with caller-supplied keys (see
@@ -800,72 +767,57 @@ int bd_rcnn_loss_fwd_bwd(const void* raw, int ld, int K, int box_off, const int3
 /* ---------------------------------------------------------------------------------------------------------
  * Inference post-processing (retinanet.py:172-209, fcos.py:181-216, rcnn.py:84-93, post_processing.py:50-103):
  * bd_det_scores -> bd_segment_topk(min_score = TEST.CLS_THRESHOLD) -> bd_det_candidates -> bd_nms_batched ->
- * bd_det_finalize for one image, as the reference runs it; for a batch of B images of one padded shape
+ * bd_det_finalize for one image (B = 1), as the reference runs it; for a batch of B images of one padded shape
  * bd_det_select (one-stage heads: scores and per-level top-k straight from the bf16 logits) or bd_rcnn_predict ->
- * bd_segment_topk(B) (RCNN head), then bd_det_candidates_batched -> bd_nms_batched(B) -> bd_det_finalize_batched.
+ * bd_segment_topk(B) (RCNN head), then bd_det_candidates -> bd_nms_batched(B) -> bd_det_finalize.
  * The batched chain at B = 1 computes what the single-image chain computes, bit for bit.
  * ------------------------------------------------------------------------------------------------------- */
 
-/* scores[r*K + k] = sigmoid(logits[r*K + k]), or sqrt(sigmoid(logit) * sigmoid(ctr[r*ctr_ld + ctr_off])) when ctr != NULL
- * (fcos.py:194).  logits/ctr bf16, scores fp32. */
-int bd_det_scores(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
+/* scores[r*K + k] = sigmoid(logits[r*ld + k]), or sqrt(sigmoid(logit) * sigmoid(ctr[r*ctr_ld + ctr_off])) when ctr != NULL
+ * (retinanet.py:184, fcos.py:194).  logits bf16 [rows][ld], ld = K (the compact layout) or K rounded up to a multiple of 8: the slots >= K
+ * of a row are padding and get no score; ctr bf16; scores stays the compact fp32 [rows][K]. */
+int bd_det_scores(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
                   bd_stream_t stream);
-/* The same (retinanet.py:184, fcos.py:194) from logits bf16 [rows][ld], ld = K or K rounded up to a multiple of 8 (bd_version() >= 104): the slots >= K of a row are padding
- * and get no score; scores stays the compact fp32 [rows][K]. */
-int bd_det_scores_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int64_t rows, int K, float* scores,
-                     bd_stream_t stream);
 /* bd_det_scores + bd_segment_topk(min_score) in one entry for B images x L levels, without the fp32 score tensor
- * (retinanet.py:183-192, fcos.py:194-204).  logits bf16 [B][rows][K]; ctr (optional) bf16 [B][rows][ctr_ld], centerness of a row at
- * column ctr_off.  Level l is rows [seg_start[l], seg_start[l] + seg_rows[l]) of every image; its item i is logits[b][seg_start[l] +
- * i / K][i % K], seg_rows[l] * K < 2^24.  score = sigmoid(logit), or sqrt(sigmoid(logit) * sigmoid(ctr)), computed as bd_det_scores
+ * (retinanet.py:183-192, fcos.py:194-204).  logits bf16 [B][rows][ld], ld = K (the compact layout) or K rounded up to a multiple of 8;
+ * ctr (optional) bf16 [B][rows][ctr_ld], centerness of a row at column ctr_off.  Level l is rows [seg_start[l], seg_start[l] +
+ * seg_rows[l]) of every image; its item i is logits[b][seg_start[l] + i / K][i % K], seg_rows[l] * K < 2^24.  The slots >= K of a row
+ * are padding (a pad logit of 0 would score 0.5) and never compete; out_idx keeps the compact numbering (row - seg_start[l]) * K + class
+ * whatever ld is, so the results are those on the compacted [B][rows][K] copy, bit for bit.  rows * ld < 2^31.
+ * score = sigmoid(logit), or sqrt(sigmoid(logit) * sigmoid(ctr)), computed as bd_det_scores
  * does; the items with score > min_score compete and the best k (<= 2048) come out in bd_segment_topk's order (score descending,
  * then item index ascending) and layout: out_idx / out_score [B][L][k] (idx -1 past the count), out_cnt [B][L] -- the same bits as
  * the two calls it replaces, whatever the number of items above the threshold.
  * Workspace: B * L * (32 + 8192 * 4 + 8192 * 8) bytes (+ padding to 256): per (image, level) a state record, one 8192-bin
  * histogram and 8192 candidate keys -- independent of rows and K (96 KiB per level against rows * K * 4 bytes of scores). */
 size_t bd_det_select_workspace_bytes(int B, int L, int64_t rows, int K, int k);
-int bd_det_select(const void* logits, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
+int bd_det_select(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
                   const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
                   float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream);
-/* The same (retinanet.py:183-192, fcos.py:194-204) from logits bf16 [B][rows][ld], ld = K or K rounded up to a multiple of 8
- * (bd_version() >= 104).  The slots >= K of a row are padding (a pad logit of 0 would score 0.5) and never compete; out_idx keeps the
- * compact numbering (row - seg_start[l]) * K + class, so the results are those of bd_det_select on the compacted [B][rows][K] copy, bit for
- * bit, and bd_det_candidates* read them unchanged.  rows * ld < 2^31. */
-int bd_det_select_ld(const void* logits, int ld, const void* ctr, int ctr_ld, int ctr_off, int B, int64_t rows, int K, int L,
-                     const int32_t* seg_start_host, const int32_t* seg_rows_host, int k, float min_score, int32_t* out_idx,
-                     float* out_score, int32_t* out_cnt, void* ws, size_t ws_bytes, bd_stream_t stream);
 /* RCNN test branch (rcnn.py:84-93): scores [R][K] = softmax(logits)[:, 1:] (-inf for empty RoI slots),
  * boxes [R][K][4] = BoxCoder.decode(roi, deltas of class k).  raw: bf16 [R][ld] as in bd_rcnn_loss_fwd_bwd. */
 int bd_rcnn_predict(const void* raw, int ld, int K, int box_off, const float* rois, const int32_t* num_rois,
                     int rois_per_img, int R, const float* mean4_host, const float* std4_host, float* scores, float* boxes,
                     bd_stream_t stream);
-/* Candidate list from the per-level top-k (topk_* as written by bd_segment_topk with B = 1, nseg = L): item index i of
- * level l -> label = i % K, row = lvl_row_off[l] + i / K.  mode 0: box = BoxCoder.decode(anchors[row], offsets of row)
- * with offsets bf16 at (row / A)*off_ld + (row % A)*4; mode 1: anchors are points [rows][2], box = PointCoder.decode;
- * mode 2: box = item_boxes[row*K + label].  Outputs [L*k] (score -inf past the per-level count). */
-int bd_det_candidates(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int L, int k,
-                      const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets, int off_ld, int A,
-                      const float* mean4_host, const float* std4_host, const float* item_boxes, float* boxes, float* scores,
-                      int32_t* labels, bd_stream_t stream);
-/* bd_det_candidates for B images in one launch: topk_* [B][L][k] / [B][L] (bd_det_select, or bd_segment_topk with B images).
- * anchors / points (modes 0, 1) are shared by the images; image b reads its offsets at offsets + b * off_stride (bf16 elements)
- * and, in mode 2, its boxes at item_boxes + b * item_stride * 4 (item_stride counted in boxes).  Outputs [B][L*k], the layout
+/* Candidate lists of B images in one launch from the per-level top-k: topk_* [B][L][k] / [B][L] (bd_det_select, or bd_segment_topk
+ * with B images, nseg = L); one image is B = 1.  Item index i of level l -> label = i % K, row = lvl_row_off[l] + i / K.
+ * mode 0: box = BoxCoder.decode(anchors[row], offsets of row) with offsets bf16 at (row / A)*off_ld + (row % A)*4; mode 1: anchors are
+ * points [rows][2], box = PointCoder.decode; mode 2: box = item_boxes[row*K + label].  anchors / points (modes 0, 1) are shared by the
+ * images; image b reads its offsets at offsets + b * off_stride (bf16 elements) and, in mode 2, its boxes at item_boxes +
+ * b * item_stride * 4 (item_stride counted in boxes).  Outputs [B][L*k] (score -inf past the per-level count), the layout
  * bd_nms_batched takes. */
-int bd_det_candidates_batched(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int B, int L,
-                              int k, const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets,
-                              int64_t off_stride, int off_ld, int A, const float* mean4_host, const float* std4_host,
-                              const float* item_boxes, int64_t item_stride, float* boxes, float* scores, int32_t* labels,
-                              bd_stream_t stream);
-/* post_processing.py:93-101: out[j] = candidate keep[j] scaled by (im_info[2]/im_info[0], im_info[3]/im_info[1]) and
- * clipped to (im_info[2], im_info[3]); slots past num_keep[0]: zero box, label -1. */
+int bd_det_candidates(int mode, const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int B, int L,
+                      int k, const int32_t* lvl_row_off_host, int K, const float* anchors, const void* offsets,
+                      int64_t off_stride, int off_ld, int A, const float* mean4_host, const float* std4_host,
+                      const float* item_boxes, int64_t item_stride, float* boxes, float* scores, int32_t* labels,
+                      bd_stream_t stream);
+/* post_processing.py:93-101 for B images in one launch (one image is B = 1): out[b][j] = candidate keep[b][j] scaled by
+ * (im_info[2]/im_info[0], im_info[3]/im_info[1]) and clipped to (im_info[2], im_info[3]) of the image's own row of im_info
+ * [B][info_ld]; slots past num_keep[b]: zero box, label -1.  candidates [B][C], keep [B][max_out] and num_keep [B] as bd_nms_batched
+ * wrote them (keep_ld = max_out).  Outputs [B][max_out]. */
 int bd_det_finalize(const float* boxes, const float* scores, const int32_t* labels, const int32_t* keep,
-                    const int32_t* num_keep, int max_out, const float* im_info, float* out_boxes, float* out_scores,
-                    int32_t* out_labels, bd_stream_t stream);
-/* bd_det_finalize for B images in one launch: candidates [B][C], keep [B][max_out] and num_keep [B] as bd_nms_batched wrote them
- * (keep_ld = max_out), im_info [B][info_ld] -- every image is rescaled and clipped by its own row.  Outputs [B][max_out]. */
-int bd_det_finalize_batched(const float* boxes, const float* scores, const int32_t* labels, const int32_t* keep,
-                            const int32_t* num_keep, int B, int C, int max_out, const float* im_info, int info_ld,
-                            float* out_boxes, float* out_scores, int32_t* out_labels, bd_stream_t stream);
+                    const int32_t* num_keep, int B, int C, int max_out, const float* im_info, int info_ld,
+                    float* out_boxes, float* out_scores, int32_t* out_labels, bd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Optimizer (megengine.optimizer.SGD as configured at solver/default_solver.py:96-114).

@@ -6,7 +6,7 @@ Per model and N, in ONE process (so every figure of a table shares the box and i
   batched    N images in one `inference_batch` call, wall clock around a device synchronisation, img/s of the median run;
   per-image  the loop the evaluator ran before batches existed: N single-image calls.  For RetinaNet the loop runs the chain that
              `inference` was then made of (det_scores -> segment_topk -> det_candidates -> nms_batched -> det_finalize, one count read per
-             image), rebuilt here from the single-image operators, which are all still exported;
+             image), rebuilt here from the same operators at B = 1;
   chain ms   the post-processing chain alone on the plan's tensors of a batch-N forward, between two HIP events: the chain `_detect`
              runs (bd_det_select first for RetinaNet) and, for RetinaNet, the same batched chain with det_scores + segment_topk(B = N)
              in the place of bd_det_select.
@@ -115,19 +115,11 @@ class LegacyRetinaChain:
         ops.segment_topk(s["scores"], N, rows * K, 1, 1, 0, [r * K for r in row_off], [r * K for r in lvl_rows], k, s["idx"], s["sc"], s["cnt"],
                          min_score=t.CLS_THRESHOLD)
         reg = self.cfg.MODEL.BOX_REG
-        if N == 1:
-            ops.det_candidates(0, s["idx"], s["sc"], s["cnt"], len(lvl_rows), k, row_off, K, pl.anchors, pl.offsets, m.box_ld, A, reg.MEAN,
-                               reg.STD, None, s["boxes"], s["csc"], s["lab"])
-        else:
-            ops.det_candidates_batched(0, s["idx"], s["sc"], s["cnt"], N, len(lvl_rows), k, row_off, K, pl.anchors, pl.offsets,
-                                       pl.offsets.numel() // N, m.box_ld, A, reg.MEAN, reg.STD, None, 0, s["boxes"], s["csc"], s["lab"])
+        ops.det_candidates(0, s["idx"], s["sc"], s["cnt"], N, len(lvl_rows), k, row_off, K, pl.anchors, pl.offsets,
+                           pl.offsets.numel() // N, m.box_ld, A, reg.MEAN, reg.STD, None, 0, s["boxes"], s["csc"], s["lab"])
         s["num"].zero_()
         ops.nms_batched(s["boxes"], s["csc"], s["lab"], t.IOU_THRESHOLD, t.MAX_BOXES_PER_IMAGE, s["keep"], s["num"], s["ws"])
-        if N == 1:
-            ops.det_finalize(s["boxes"], s["csc"], s["lab"], s["keep"], s["num"], t.MAX_BOXES_PER_IMAGE, info[0].contiguous(), s["ob"], s["os"],
-                             s["ol"])
-        else:
-            ops.det_finalize_batched(s["boxes"], s["csc"], s["lab"], s["keep"], s["num"], t.MAX_BOXES_PER_IMAGE, info, s["ob"], s["os"], s["ol"])
+        ops.det_finalize(s["boxes"], s["csc"], s["lab"], s["keep"], s["num"], t.MAX_BOXES_PER_IMAGE, info, s["ob"], s["os"], s["ol"])
         return s["num"].tolist() if read_counts else None
 
     def inference_one(self, inputs):

@@ -1,7 +1,7 @@
 """Inference on a batch: N = 3 images of 128x160 through ONE launch chain (bd_det_select or bd_segment_topk(B = N) ->
-bd_det_candidates_batched -> bd_nms_batched(B = N) -> bd_det_finalize_batched) against
+bd_det_candidates(B = N) -> bd_nms_batched(B = N) -> bd_det_finalize(B = N)) against
 
-  * the single-image operators (det_scores -> segment_topk -> det_candidates -> nms_batched -> det_finalize) run on each image's slice
+  * the single-image chain (det_scores -> segment_topk -> det_candidates -> nms_batched -> det_finalize, B = 1) run on each image's slice
     of the SAME batched plan's logits / offsets / RoIs: boxes, scores and labels bit-identical.  The network ran once, at batch 3, for
     both sides, so batch-size-dependent kernel routing inside it cannot enter the comparison;
   * oracle/rcnn_ops.py detect_postprocess per image on the device's own scores and decoded boxes, with the comparison of
@@ -47,7 +47,7 @@ def _data(seed, n=N):
 
 def _single_image_chain(cfg, scores, lvl_rows, K, mode, info_row, k, anchors=None, offsets=None, off_ld=4, A=1, mean=(0, 0, 0, 0),
                         std=(1, 1, 1, 1), item_boxes=None):
-    """FPNDetector._detect as it was for one image: the pre-existing single-image entries only."""
+    """FPNDetector._detect as it was for one image: one launch chain of B = 1 per image."""
     from basedet_amd import ops
     t = cfg.TEST
     Ln = len(lvl_rows)
@@ -61,7 +61,8 @@ def _single_image_chain(cfg, scores, lvl_rows, K, mode, info_row, k, anchors=Non
                      min_score=t.CLS_THRESHOLD)
     C = Ln * k
     boxes = torch.empty((C, 4), **f32); sc = torch.empty((1, C), **f32); labels = torch.empty((1, C), **i32)
-    ops.det_candidates(mode, tk_idx, tk_sc, tk_cnt, Ln, k, row_off, K, anchors, offsets, off_ld, A, mean, std, item_boxes, boxes, sc, labels)
+    ops.det_candidates(mode, tk_idx, tk_sc, tk_cnt, 1, Ln, k, row_off, K, anchors, offsets, 0, off_ld, A, mean, std, item_boxes, 0, boxes, sc,
+                       labels)
     max_out = t.MAX_BOXES_PER_IMAGE
     keep = torch.empty((1, max_out), **i32); num = torch.zeros((1,), **i32)
     ws = torch.empty((ops.nms_batched_workspace_bytes(1, C),), dtype=torch.uint8, device="cuda")
@@ -275,7 +276,7 @@ def test_batched_inference_matches_oracle_per_image(name):
 
 @pytest.mark.parametrize("coder", ["A", "B"])
 def test_batched_retinanet_decodes_with_box_reg(coder):
-    """MODEL.BOX_REG with a non-zero mean (A) and with four different stds (B) through bd_det_candidates_batched: three images, bit-identical
+    """MODEL.BOX_REG with a non-zero mean (A) and with four different stds (B) through bd_det_candidates at B = 3: three images, bit-identical
     to the single-image operators under the same coder and, per image, the oracle's detections (box_decode with that mean and std)."""
     from tests import config_key_cases as C
     cfg, K, outs, per, k, tol = _run_retinanet("retinanet_coder_" + coder, dict(MODEL=dict(BOX_REG=dict(A=C.CODER_A, B=C.CODER_B)[coder])))

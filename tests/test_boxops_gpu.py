@@ -245,7 +245,7 @@ def test_giou_and_bce_losses():
     norm = torch.tensor([float(w[lab > 0].sum())], dtype=torch.float32, device="cuda")
     loss = torch.zeros((1,), dtype=torch.float32, device="cuda")
     dp = torch.empty((rows, 4), dtype=torch.bfloat16, device="cuda")
-    ops.giou_ltrb_fwd_bwd(pred.cuda(), _dev(tgt), _dev(w), _dev(lab), rows, norm, 1.0, loss, dp)
+    ops.iou_ltrb_fwd_bwd(pred.cuda(), _dev(tgt), _dev(w), _dev(lab), rows, ops.IOU_LOSS_TYPES["giou"], norm, 1.0, loss, dp)
     p = pred.float().numpy().astype(np.float64)
     fg = lab > 0
     ref = (ob.iou_loss_ltrb(p[fg], tgt[fg], "giou") * w[fg]).sum() / max(1.0, float(w[fg].sum()))

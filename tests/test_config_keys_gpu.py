@@ -31,7 +31,7 @@ All six
                                 K: det_select / nms_batched / det_finalize (FPNDetector._detect).  T: test_batched_inference_gpu and
                                 test_fullsize_inference_gpu move them; test_postprocess_gpu at kernel level.  Not duplicated here.
 RetinaNet (and FreeAnchor, which shares network, anchors and coder)
-  BOX_REG.MEAN, BOX_REG.STD     K: bd_retina_assign_encode (encode), bd_det_candidates / bd_det_candidates_batched mode 0 (decode),
+  BOX_REG.MEAN, BOX_REG.STD     K: bd_retina_assign_encode (encode), bd_det_candidates mode 0 (decode),
                                 bd_freeanchor_loss_fwd_bwd (decode and encode).
                                 T: test_retinanet_key[BOX_REG], (all), test_retinanet_inference_box_reg; kernel level, coders A and B:
                                 test_assign_edges_gpu (assign_encode), test_boxops_gpu (box_encode / box_decode), test_postprocess_gpu

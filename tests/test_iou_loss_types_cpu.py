@@ -45,9 +45,6 @@ def test_header_and_ctypes_table_carry_the_entry_point():
     assert len(args) == 11 and args[5] == "int loss_type"
     ret, argtypes = _lib.SIGNATURES["bd_iou_ltrb_fwd_bwd"]
     assert len(argtypes) == 11
-    # the giou entry point keeps its ten arguments
-    m = re.search(r"\bint\s+bd_giou_ltrb_fwd_bwd\s*\(([^)]*)\)", header)
-    assert m and len(m.group(1).split(",")) == 10 and len(_lib.SIGNATURES["bd_giou_ltrb_fwd_bwd"][1]) == 10
 
 
 def test_loss_grid_cap_is_exported():

@@ -5,7 +5,7 @@ Reference: the loss values are oracle.box_ops.iou_loss_ltrb (float64 numpy, the 
 autograd through a float64 restatement of the same formula (_loss64), which is first held to the oracle's values.  The prediction is
 rounded to bf16 before either side sees it, so both evaluate the same numbers.
 
-Tolerances are those tests/test_boxops_gpu.py::test_giou_and_bce_losses applies to giou_ltrb_fwd_bwd: 1e-4 relative on the loss sum (fp32
+Tolerances are those tests/test_boxops_gpu.py::test_giou_and_bce_losses applies to the giou type of iou_ltrb_fwd_bwd: 1e-4 relative on the loss sum (fp32
 summation order), rtol 3e-2 / atol 2e-6 on the bf16 gradient.  The normaliser of the kernel tests is a small constant, not the weight sum,
 so that the gradients of a million-row launch stay far above that atol."""
 import ctypes
@@ -120,7 +120,7 @@ def _launch(d, loss_type, weighted, norm=NORM, loss_weight=1.0, lab=None, entry=
     lab = dev["lab"] if lab is None else lab
     w = dev["w"] if weighted else None
     if entry == "giou":
-        ops.giou_ltrb_fwd_bwd(dev["pred"], dev["tgt"], w, lab, rows, nrm, loss_weight, loss, dp)
+        ops.iou_ltrb_fwd_bwd(dev["pred"], dev["tgt"], w, lab, rows, ops.IOU_LOSS_TYPES["giou"], nrm, loss_weight, loss, dp)
     else:
         ops.iou_ltrb_fwd_bwd(dev["pred"], dev["tgt"], w, lab, rows, ops.IOU_LOSS_TYPES[loss_type], nrm, loss_weight, loss, dp)
     torch.cuda.synchronize()

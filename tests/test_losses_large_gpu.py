@@ -228,7 +228,7 @@ def test_giou_and_bce_past_the_grid_cap(rows):
     norm = torch.tensor([wsum], dtype=torch.float32, device="cuda")
     loss = torch.zeros((1,), dtype=torch.float32, device="cuda")
     dp = torch.full((rows, 4), 3.0, dtype=torch.bfloat16, device="cuda")
-    ops.giou_ltrb_fwd_bwd(pred, tgt, w, lab, rows, norm, lw, loss, dp)
+    ops.iou_ltrb_fwd_bwd(pred, tgt, w, lab, rows, ops.IOU_LOSS_TYPES["giou"], norm, lw, loss, dp)
     gs = lw / max(float(np.float32(wsum)), 1.0)
     p = pred.double().requires_grad_(True)
     l64 = _giou_loss64(p, tgt.double()) * w.double() * fg

@@ -189,9 +189,9 @@ def test_det_candidates(mode):
     labels = torch.full((1, L * k), 7, dtype=torch.int32, device="cuda")
     for mean, std in (CODERS if mode == 0 else CODERS[:1]):          # mode 0 is the one that decodes with a box coder (MODEL.BOX_REG)
         boxes.fill_(7.0); scores.fill_(7.0); labels.fill_(7)
-        ops.det_candidates(mode, _dev(tk_idx), _dev(tk_sc), _dev(tk_cnt), L, k, row_off, K,
-                           _dev(anchors) if anchors is not None else None, offsets.cuda() if offsets_np is not None else None, off_ld, A,
-                           mean, std, _dev(item_boxes) if item_boxes is not None else None, boxes, scores, labels)
+        ops.det_candidates(mode, _dev(tk_idx), _dev(tk_sc), _dev(tk_cnt), 1, L, k, row_off, K,
+                           _dev(anchors) if anchors is not None else None, offsets.cuda() if offsets_np is not None else None, 0, off_ld, A,
+                           mean, std, _dev(item_boxes) if item_boxes is not None else None, 0, boxes, scores, labels)
 
         def ref_box(l, idx):
             row = row_off[l] + idx // K
