@@ -105,6 +105,50 @@ def test_retinanet_step_matches_oracle(backbone):
             assert float(got[n].abs().sum()) > 0 and _cos(got[n], g2[n].detach()) > 0.999, n
 
 
+def test_retinanet_deconv_fpn_step_matches_oracle():
+    """MODEL.FPN.UPSAMPLE = "deconv" with BOTH norms live (tests/test_fpn_norm_gpu.py runs deconv under the FPN norm alone): the learned
+    top-down path hands dL/d lat_s from the deconv's data gradient to the lateral norm's backward pass, and below it to the backbone
+    norms.  Labels, losses (2e-2, fp32 oracle), then every trainable parameter -- the deconv weights and the lateral norms' gamma / beta
+    among them -- against the sim_bf16 oracle on the stored activations, rel-L2 1e-2."""
+    from basedet_amd.models import RetinaNet, params as P
+    cfg, params, batch = _setup("resnet18", 2, SIZE, overrides=_over("BN", NORM="BN", UPSAMPLE="deconv"))
+    params = randomise_backbone_norms(randomise_norms(params))
+    model = RetinaNet(cfg, params=params)
+    names = P.trainable_names(params, 0, "BN")
+    assert sorted(names) == sorted(model.state_dict_trainable_names())
+    ups = ["backbone.fpn_upsample4.weight", "backbone.fpn_upsample5.weight"]
+    lats = [f"backbone.fpn_lateral{s}.norm.{k}" for s in (3, 4, 5) for k in ("weight", "bias")]
+    assert all(n in names for n in ups + lats + [BU + ".bn1.weight"])
+    Orc = backbone_norm_oracle_cls(norm_oracle_cls())
+    ref, aux = Orc(params, P.oracle_arch(cfg), trainable=names).retinanet_losses(batch)
+    out = model(batch)
+    pl = model._cur
+    assert np.array_equal(pl.labels.cpu().numpy(), aux["labels"])
+    for k in ("cls_loss", "reg_loss", "total_loss"):
+        got, want = float(out[k]), float(ref[k].detach())
+        print("deconv + both norms", k, "rel", abs(got - want) / abs(want))
+        assert abs(got - want) / abs(want) < 2e-2, (k, got, want)
+    model.backward()
+    torch.cuda.synchronize()
+    got = model.reference_grads()
+    acts = model.debug_activations()
+    for s in model.fpn_stages:
+        g = pl.blk[pl.res[s]].gout
+        acts[f"g_lat{s}"] = pl.g_lat[s].float().cpu().view(pl.N, g.H[0], g.W[0], -1).permute(0, 3, 1, 2).contiguous()
+    orc2 = Orc(params, P.oracle_arch(cfg), trainable=names, sim_bf16=True, inject=acts)
+    l2, _ = orc2.retinanet_losses(batch)
+    g2 = orc2.grads(l2["total_loss"])
+    assert len(orc2.grad_check) == 1 + sum(len(b["convs"]) for b in model.blocks) + len(model.fpn_stages)
+    assert all(v < 1e-2 for v in orc2.grad_check.values()), {k: v for k, v in orc2.grad_check.items() if not v < 1e-2}
+    rels = {n: float((got[n].double().reshape(-1) - g2[n].detach().double().reshape(-1)).norm() / (g2[n].detach().double().norm() + 1e-30))
+            for n in names}
+    bad = {n: r for n, r in rels.items() if not r < 1e-2}
+    print("deconv + both norms: worst per-parameter rel-L2", max(rels.items(), key=lambda t: t[1]), "over 1e-2:", bad)
+    assert not bad, bad
+    for n in ups + lats:
+        assert float(got[n].abs().sum()) > 0 and _cos(got[n], g2[n].detach()) > 0.999, n
+
+
 class _Capture:
     """Keeps the last gradients both sides of check_faster_rcnn_step computed, for the tighter comparison below."""
     oracle = model = None

@@ -138,7 +138,35 @@ REFUSED = [
     ("FasterRCNN", dict(RCNN=dict(IN_FEATURES=["p3", "p4", "p5"], STRIDES=[8, 16, 32])), "MODEL.RCNN.IN_FEATURES"),
     ("FasterRCNN", dict(RPN=dict(TEST_POST_NMS_TOPK=500)), "MODEL.RPN.TEST_POST_NMS_TOPK"),
     ("FasterRCNN", dict(ROI_POOLER=dict(METHOD="roi_warp")), "MODEL.ROI_POOLER.METHOD"),
+    # live norms (FPNDetector.check_config): a value that is no norm of the reference's, a backbone norm above frozen convolutions,
+    # fp8 weights under either key, a FREEZE_AT that is no stage count
+    ("RetinaNet", dict(BACKBONE=dict(NORM="GN", FREEZE_AT=0)), "MODEL.BACKBONE.NORM"),
+    ("FCOS", dict(BACKBONE=dict(NORM=None, FREEZE_AT=0)), "MODEL.BACKBONE.NORM"),
+    ("RetinaNet", dict(BACKBONE=dict(NORM="BN", FREEZE_AT=1)), "MODEL.BACKBONE.NORM"),
+    ("FasterRCNN", dict(BACKBONE=dict(NORM="SyncBN", FREEZE_AT=2)), "MODEL.BACKBONE.NORM"),
+    ("RetinaNet", dict(WEIGHT_DTYPE="fp8_e4m3", BACKBONE=dict(NORM="BN", FREEZE_AT=0)), "MODEL.BACKBONE.NORM"),
+    ("RetinaNet", dict(WEIGHT_DTYPE="fp8_e4m3", FPN=dict(NORM="BN")), "MODEL.FPN.NORM"),
+    ("OTA", dict(FPN=dict(NORM="GN")), "MODEL.FPN.NORM"),
+    ("FasterRCNN", dict(FPN=dict(NORM="FrozenBN")), "MODEL.FPN.NORM"),
+    ("RetinaNet", dict(BACKBONE=dict(FREEZE_AT=-1)), "MODEL.BACKBONE.FREEZE_AT"),
+    ("ATSS", dict(BACKBONE=dict(FREEZE_AT=True)), "MODEL.BACKBONE.FREEZE_AT"),
 ]
+
+LIVE_NORMS = [dict(BACKBONE=dict(NORM="BN", FREEZE_AT=0)), dict(BACKBONE=dict(NORM="SyncBN", FREEZE_AT=0)), dict(FPN=dict(NORM="BN")),
+              dict(FPN=dict(NORM="SyncBN")), dict(BACKBONE=dict(NORM="BN", FREEZE_AT=0), FPN=dict(NORM="BN")),
+              dict(BACKBONE=dict(NORM="FrozenBN", FREEZE_AT=0)), dict(BACKBONE=dict(NORM="FrozenBN", FREEZE_AT=1), FPN=dict(NORM=None))]
+
+
+@pytest.mark.parametrize("name", ["RetinaNet", "FreeAnchor", "FCOS", "ATSS", "OTA", "FasterRCNN"])
+@pytest.mark.parametrize("override", LIVE_NORMS, ids=[str(i) for i in range(len(LIVE_NORMS))])
+def test_live_norm_values_are_accepted(name, override):
+    """MODEL.BACKBONE.NORM / MODEL.FPN.NORM = "BN", and "SyncBN" at world size 1 (this process), by every detector; the backbone norm at
+    FREEZE_AT = 0 only."""
+    from basedet_amd import comm
+    assert comm.world_size() == 1
+    cfg = _cfg(name)
+    cfg.merge(dict(MODEL=override))
+    _model_cls(name).check_config(cfg)
 
 
 @pytest.mark.parametrize("name,override,key", REFUSED, ids=[f"{n}-{k}-{i}" for i, (n, _, k) in enumerate(REFUSED)])

@@ -19,9 +19,15 @@ layers/head/*.py) for the six detectors; "K:" = kernel / host code of ours that 
 All six
   BACKBONE.NAME, OUT_FEATURES, OUT_FEATURE_CHANNELS   K: FPNDetector._build_layers.  T: test_model_gpu (resnet18 / resnet50), test_r101_gpu
   BACKBONE.IMG_MEAN, IMG_STD    K: bd stem normalisation (pre_process).  T: test_raw_input_gpu, test_layers_gpu
-  BACKBONE.NORM                 R: "FrozenBN" only (test_fpn_variants_cpu)
-  BACKBONE.FREEZE_AT            K: trainable set.  accepted: >= 1 (assertion: the 7x7 stem kernel is forward-only)
-  FPN.NORM                      R: None only (test_fpn_variants_cpu)
+  BACKBONE.NORM                 K: LiveNorms / bd_bn_* under every backbone convolution and the stem ("BN"; "SyncBN" at world size 1 is "BN").
+                                T: test_backbone_norm_gpu (RetinaNet R18 / R50, Faster R-CNN), test_live_norm_families_gpu (FCOS, ATSS, OTA,
+                                FreeAnchor), test_fpn_norm_gpu (deconv), test_multiscale_gpu, test_ema_gpu.  R: any value but "FrozenBN" / "BN" /
+                                "SyncBN"; a live norm with FREEZE_AT >= 1, with fp8 weights, "SyncBN" at world size > 1
+  BACKBONE.FREEZE_AT            K: trainable set (0 trains the 7x7 stem, 1 freezes it, >= 2 freezes layer1 too).  T: test_stem_bwd_gpu.
+                                R: not an integer >= 0; >= 1 under a live BACKBONE.NORM
+  FPN.NORM                      K: LiveNorms / bd_bn_* under every lateral and output convolution.  T: test_fpn_norm_gpu and the modules named
+                                at BACKBONE.NORM.  R: any value but None / "BN" / "SyncBN"; a live norm with fp8 weights, "SyncBN" at world
+                                size > 1 (all: test_config_keys_cpu::test_unimplemented_value_is_refused, test_live_norm_values_are_accepted)
   FPN.UPSAMPLE                  K: DeconvLayer.  T: test_fpn_deconv_gpu; R: other than "resize" / "deconv" (not read by Faster R-CNN, as in the reference)
   FPN.STRIDES, OUT_FEATURES, OUT_CHANNELS, TOP_BLOCK_IN_CHANNELS, TOP_BLOCK_IN_FEATURE
                                 K: pyramid geometry.  Out of scope here: they define the network's shape, not a parameter of a kernel; the

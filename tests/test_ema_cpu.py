@@ -159,6 +159,145 @@ def test_det_train_parser_sets_the_config_key():
     assert cfg.TRAINER.EMA.ENABLE is False and cfg.DATA.BUILDER_NAME == "DummyLoader"
 
 
+# ---- live batch norms: the running statistics are buffers outside the arena, averaged in a tensor of their own ---------------------------
+NORM = "backbone.fpn_lateral3.norm"
+
+
+def _normed_model():
+    """_arena_model() plus one live norm of 4 channels (LiveNorms on the CPU) and the three model methods ModelEMA's state calls use."""
+    from basedet_amd.models.live_norm import LiveNorms
+    m = _arena_model()
+    m.norms = LiveNorms(torch.device("cpu"))
+    n = m.norms.add(NORM, 4)
+    m.norms.allocate()
+    m.norms.running.copy_(torch.arange(8, dtype=torch.float32) + 100)
+    m.training = True
+    m.frozen = np.full(3, 7.0, np.float32)
+    m.bound = []
+
+    def state_dict():
+        return {"head.cls_score.weight": m.arena.w.numpy().copy(), NORM + ".running_mean": n.running_mean.numpy().copy(),
+                NORM + ".running_var": n.running_var.numpy().copy(), "backbone.bottom_up.bn1.running_var": m.frozen.copy()}
+
+    def bind(params):
+        m.bound.append(params)
+        m.arena.w.copy_(torch.from_numpy(params["head.cls_score.weight"]))
+        n.running_mean.copy_(torch.from_numpy(params[NORM + ".running_mean"]))
+        n.running_var.copy_(torch.from_numpy(params[NORM + ".running_var"]))
+
+    m.state_dict, m._bind_params = state_dict, bind
+    m.state_dict_trainable_names = lambda: ["head.cls_score.weight"]
+    m.repack_weights = lambda: None
+    return m
+
+
+@pytest.fixture
+def host_ops(monkeypatch):
+    """bd_ema_update / bd_swap_f32 restated on the host, and a log of the tensors they were launched on."""
+    from basedet_amd import ops
+    log = []
+
+    def ema_update(e, w, m):
+        log.append(("ema_update", e.data_ptr(), m))
+        e.copy_(e * np.float32(m) + np.float32(1 - m) * w)
+
+    def swap_f32(a, b):
+        log.append(("swap_f32", a.data_ptr(), b.data_ptr()))
+        t = a.clone()
+        a.copy_(b)
+        b.copy_(t)
+
+    monkeypatch.setattr(ops, "ema_update", ema_update)
+    monkeypatch.setattr(ops, "swap_f32", swap_f32)
+    return log
+
+
+def test_buffer_average_exists_only_with_live_norms():
+    from basedet_amd.layers import ModelEMA
+    from basedet_amd.models.live_norm import LiveNorms
+    model = _normed_model()
+    ema = ModelEMA(model, momentum=0.5)
+    assert torch.equal(ema.r, model.norms.running) and ema.r.data_ptr() != model.norms.running.data_ptr() and ema.r.dtype == torch.float32
+    plain = _arena_model()
+    assert ModelEMA(plain, momentum=0.5).r is None                   # no `norms` at all
+    plain.norms = LiveNorms(torch.device("cpu"))
+    plain.norms.allocate()
+    assert ModelEMA(plain, momentum=0.5).r is None                   # an FPNDetector without a live norm: an empty LiveNorms
+
+
+def test_buffers_are_averaged_on_every_updating_step_fused_or_not(host_ops):
+    """burnin_iter = 2 and four steps, the last two fused into the optimizer launch: the buffers' average takes update(0) + update(m) at
+    step 2 and update(m) at steps 3 and 4 -- on launches of its own in the fused steps too, where the arena's average is left to the
+    optimizer.  m = 0.5 and small integers: the recurrence is exact in fp32."""
+    from basedet_amd.layers import ModelEMA
+    model = _normed_model()
+    ema = ModelEMA(model, momentum=0.5, burnin_iter=2)
+    e_ptr, r_ptr = ema.e.data_ptr(), ema.r.data_ptr()
+    ref = model.norms.running.double().clone()
+    for it in range(1, 5):
+        model.norms.running.add_(8.0 * it)                           # the training forward moves the buffers
+        fused = ema.fused_momentum()
+        assert (fused is not None) == (it > 2)
+        del host_ops[:]
+        ema.step()
+        x = model.norms.running.double()
+        if it == 2:
+            ref = 0.5 * x + 0.5 * x
+        elif it > 2:
+            ref = 0.5 * ref + 0.5 * x
+        want = {1: [], 2: [("ema_update", e_ptr, 0), ("ema_update", r_ptr, 0), ("ema_update", e_ptr, 0.5), ("ema_update", r_ptr, 0.5)]}
+        assert host_ops == want.get(it, [("ema_update", r_ptr, 0.5)]), it
+        assert torch.equal(ema.r.double(), ref), it
+    assert ema.iters == 4 and not torch.equal(ema.r, model.norms.running)
+
+
+def test_a_model_without_live_norms_launches_what_it_launched(host_ops):
+    from basedet_amd.layers import ModelEMA
+    model = _arena_model()
+    ema = ModelEMA(model, momentum=0.5, burnin_iter=1)
+    e_ptr, w_ptr = ema.e.data_ptr(), model.arena.w.data_ptr()
+    ema.step()
+    assert ema.fused_momentum() == 0.5
+    ema.step()
+    with ema.applied():
+        pass
+    assert host_ops == [("ema_update", e_ptr, 0), ("ema_update", e_ptr, 0.5)] + [("swap_f32", e_ptr, w_ptr)] * 2
+    assert model.repacked == 2
+
+
+def test_applied_and_state_dict_swap_the_buffers_too(host_ops):
+    from basedet_amd.layers import ModelEMA
+    model = _normed_model()
+    model.repack_trainable = lambda: None
+    ema = ModelEMA(model, momentum=0.5)
+    model.arena.w.add_(1000)
+    model.norms.running.add_(1000)
+    w, r, e0, r0 = model.arena.w.clone(), model.norms.running.clone(), ema.e.clone(), ema.r.clone()
+    with ema.applied():
+        assert torch.equal(model.arena.w, e0) and torch.equal(model.norms.running, r0)
+        assert torch.equal(ema.e, w) and torch.equal(ema.r, r)
+    assert torch.equal(model.arena.w, w) and torch.equal(model.norms.running, r) and torch.equal(ema.e, e0) and torch.equal(ema.r, r0)
+    sd = ema.state_dict()["model"]
+    assert np.array_equal(sd[NORM + ".running_mean"], r0[:4].numpy()) and np.array_equal(sd[NORM + ".running_var"], r0[4:].numpy())
+    assert np.array_equal(sd["head.cls_score.weight"], e0.numpy())
+    assert torch.equal(model.norms.running, r) and torch.equal(ema.r, r0)
+
+
+def test_load_state_dict_restores_the_buffers_and_ignores_frozen_entries(host_ops):
+    from basedet_amd.layers import ModelEMA
+    model = _normed_model()
+    ema = ModelEMA(model, momentum=0.5)
+    w, r = model.arena.w.clone(), model.norms.running.clone()
+    stored = {"head.cls_score.weight": np.full(model.arena.total, 2.0, np.float32), NORM + ".running_mean": np.full(4, 3.0, np.float32),
+              NORM + ".running_var": np.full(4, 4.0, np.float32), "backbone.bottom_up.bn1.running_var": np.full(3, -1.0, np.float32)}
+    ema.load_state_dict({"iter": 11, "model": stored})
+    assert ema.iters == 11
+    assert torch.equal(ema.e, torch.full_like(w, 2.0))
+    assert torch.equal(ema.r, torch.tensor([3.0] * 4 + [4.0] * 4))
+    assert torch.equal(model.arena.w, w) and torch.equal(model.norms.running, r)          # the live model is untouched
+    assert np.array_equal(model.bound[-1]["backbone.bottom_up.bn1.running_var"], model.frozen)      # frozen: the model's own value
+
+
 def test_ema_coefficients_are_formed_in_double():
     """ema.py:80 casts `1 - m` after the subtraction in Python float64; float32(1) - float32(m) would differ for m = 0.9995."""
     from basedet_amd import ops

@@ -340,3 +340,222 @@ def test_applied_refuses_fp8_weights():
     ema.update(0.5)                                                  # the fp32 masters are all update / step touch: any dtype
     torch.cuda.synchronize()
     assert torch.equal(model.arena.w, w)
+
+
+# ---- a model with live batch norms ------------------------------------------------------------------------------------------------------
+# RetinaNet-R18, FREEZE_AT = 0, MODEL.BACKBONE.NORM = MODEL.FPN.NORM = "BN": every norm's running_mean / running_var is a buffer that
+# moves with each training forward, outside the parameter arena.  ema.py:52-55 averages buffers like parameters.
+N_MOMENTUM, N_BURNIN, N_STEPS = 0.5, 1, 3        # burn-in at the first step: update(0) + update(0.5) there, update(0.5) at steps 2 and 3
+N_UPDATES = N_STEPS + 1
+SIZE = (128, 160)
+
+
+def _is_stat(k):
+    return k.endswith((".running_mean", ".running_var"))
+
+
+def _stats(sd):
+    return {k: np.array(v, np.float32) for k, v in sd.items() if _is_stat(k)}
+
+
+def _norm_setup():
+    """cfg, params (gamma / beta / running statistics of every norm randomised: ignoring any of them moves the result) and three
+    different batches; the second one's pixels are scaled by 0.6 so that its batch statistics stand apart from the others'."""
+    from backbone_norm_oracle import randomise_backbone_norms
+    from fpn_norm_oracle import randomise_norms
+    from basedet_amd.utils import DummyLoader
+    from tests.test_model_gpu import _setup as base
+    over = dict(MODEL=dict(BACKBONE=dict(FREEZE_AT=0, NORM="BN"), FPN=dict(NORM="BN")))
+    cfg, params, _ = base("resnet18", 2, SIZE, seed=5, overrides=over)
+    params = randomise_backbone_norms(randomise_norms(params))
+    params["head.cls_score.bias"] = np.full_like(params["head.cls_score.bias"], -2.5)
+    params["head.cls_score.weight"] = params["head.cls_score.weight"] * 8
+    batches = []
+    for i, scale in enumerate((255.0, 0.6 * 255.0, 255.0)):
+        b = next(DummyLoader(2, SIZE, seed=20 + i))
+        b["data"] = (b["data"] * scale).astype(np.float32)
+        batches.append(b)
+    return cfg, params, batches
+
+
+def _norm_run(cfg, params, batches, fused):
+    """Three solver steps with a ModelEMA next to them.  fused: SGD.step(ema=...) folds the arena's update into its launch past the
+    burn-in (what DetTrainer.model_step does); otherwise ema.step() runs its own launches."""
+    from basedet_amd.layers import ModelEMA
+    from basedet_amd.models import RetinaNet
+    from basedet_amd.solver import DetSolver
+    model = RetinaNet(cfg, params=params)
+    solver = DetSolver.build(cfg, model)
+    ema = ModelEMA(model, N_MOMENTUM, burnin_iter=N_BURNIN)
+    run = dict(model=model, solver=solver, ema=ema, x0=_stats(model.state_dict()), x=[], losses=[])
+    for b in batches:
+        out = solver.minimize(model, b, ema=ema) if fused else solver.minimize(model, b)
+        ema.step()
+        torch.cuda.synchronize()
+        run["losses"].append(_losses(out))
+        run["x"].append(_stats(model.state_dict()))
+    run["sd"] = ema.state_dict()
+    return run
+
+
+@pytest.fixture(scope="module")
+def norm_runs():
+    cfg, params, batches = _norm_setup()
+    return dict(cfg=cfg, params=params, batches=batches, fused=_norm_run(cfg, params, batches, True),
+                plain=_norm_run(cfg, params, batches, False))
+
+
+def _eval_logits(model, batch):
+    """The logits of inference_batch on `batch`, in whatever mode-independent state the caller arranged; the model must be in eval()."""
+    assert not model.training
+    model.inference_batch({"data": batch["data"], "im_info": batch["im_info"]})
+    torch.cuda.synchronize()
+    return model._plan(batch["data"].shape[0], *SIZE).logits.clone()
+
+
+def _same_bits(a, b):
+    from util import bits_of
+    return a.shape == b.shape and bool(torch.equal(bits_of(a), bits_of(b)))
+
+
+def test_live_norm_buffers_follow_the_float64_recurrence(norm_runs):
+    """Every running_mean / running_var of ema.state_dict()["model"] against e = m e + (1 - m) x in float64 over the model's buffers
+    recorded after each step, started from the buffers at construction, with the update(0) of the burn-in step (ema.py:57-69).
+
+    Bound: one update is two fp32 products and one fp32 sum, three roundings of at most 2^-24 relative each on values no larger than
+    max(|e|, |x|); after k = 4 updates that is 3 k 2^-24 max(|e|, |x|) -- asserted at 4 times that (the order of the roundings).  First
+    the fixture: the float64 average must stand more than 1e-2 (rel-L2, from the recorded values alone) away from the model's current
+    buffers, or the raw statistics would pass as the average."""
+    run = norm_runs["fused"]
+    got = _stats(run["sd"]["model"])
+    names = sorted(run["x0"])
+    assert names and sorted(got) == names and len(names) == 2 * len(run["model"].norms)
+    e = {k: run["x0"][k].astype(np.float64) for k in names}
+    scale = {k: np.abs(e[k]) for k in names}
+    updates = 0
+    for it, x in enumerate(run["x"], start=1):
+        for m in ([0.0, N_MOMENTUM] if it == N_BURNIN else [N_MOMENTUM]):
+            for k in names:
+                xk = x[k].astype(np.float64)
+                scale[k] = np.maximum(scale[k], np.maximum(np.abs(e[k]), np.abs(xk)))
+                e[k] = m * e[k] + (1 - m) * xk
+            updates += 1
+    assert updates == N_UPDATES
+    last = run["x"][-1]
+    for kind in (".running_mean", ".running_var"):
+        ks = [k for k in names if k.endswith(kind)]
+        a, b = np.concatenate([e[k] for k in ks]), np.concatenate([last[k].astype(np.float64) for k in ks])
+        away = float(np.linalg.norm(a - b) / np.linalg.norm(b))
+        print(f"{kind}: float64 average vs the model's current buffers, rel-L2 {away:.3e}")
+        assert away > 1e-2, (kind, away)
+    bound = 4 * 3 * N_UPDATES * 2.0 ** -24
+    worst, raw = ("", 0.0), 0
+    for k in names:
+        err = np.abs(got[k].astype(np.float64) - e[k]) / np.maximum(scale[k], 1e-300)
+        if float(err.max()) > worst[1]:
+            worst = (k, float(err.max()))
+        raw += int(np.array_equal(got[k], last[k]))
+    print(f"worst |ema - float64| / max(|e|, |x|) = {worst[1]:.3e} at {worst[0]} (bound {bound:.3e}); "
+          f"{raw} of {len(names)} entries equal the model's own buffers")
+    for k in names:
+        assert np.all(np.abs(got[k].astype(np.float64) - e[k]) <= bound * scale[k]), k
+
+
+def test_live_norm_fused_and_plain_updates_agree(norm_runs):
+    """SGD.step(ema=...) + ema.step() against ema.step() on its own launches: the same training (losses, weights, buffers) and the same
+    average, parameters and buffers, bit for bit."""
+    f, p = norm_runs["fused"], norm_runs["plain"]
+    assert f["losses"] == p["losses"]
+    assert _same_bits(f["model"].arena.w, p["model"].arena.w) and _same_bits(f["model"].norms.running, p["model"].norms.running)
+    assert f["sd"]["iter"] == p["sd"]["iter"] == N_STEPS and sorted(f["sd"]["model"]) == sorted(p["sd"]["model"])
+    bad = [k for k, v in f["sd"]["model"].items() if not np.array_equal(_bits(v), _bits(p["sd"]["model"][k]))]
+    assert not bad, bad[:8]
+    assert any(_is_stat(k) for k in f["sd"]["model"])
+
+
+@pytest.mark.parametrize("order", ["eval_inside", "eval_before"])
+def test_live_norm_applied_is_the_averaged_model(norm_runs, order):
+    """Eval logits inside applied() against those of a fresh model built from ema.state_dict()["model"]: the same weights through the
+    same kernels, so anything but equal bits is a stale fold or a stale packed weight.  eval() is entered inside the block (the fold is
+    made from what is in place) or before it (the repack on entry refolds).  The averaged buffers take part: the fresh model with the
+    live model's own running statistics in their place computes other logits."""
+    from basedet_amd.models import RetinaNet
+    run, batch = norm_runs["fused"], norm_runs["batches"][0]
+    model, ema = run["model"], run["ema"]
+    w_pre, r_pre = model.arena.w.clone(), model.norms.running.clone()
+    if order == "eval_before":
+        model.eval()
+    with ema.applied():
+        model.eval()
+        got = _eval_logits(model, batch)
+    live = _eval_logits(model, batch)                                # after the exit, still in eval(): the live model again
+    model.train()
+    torch.cuda.synchronize()
+    assert _same_bits(model.arena.w, w_pre) and _same_bits(model.norms.running, r_pre)
+    sd = ema.state_dict()["model"]
+    want = _eval_logits(RetinaNet(norm_runs["cfg"], params=sd).eval(), batch)
+    assert bool(torch.isfinite(want.float()).all())
+    assert _same_bits(got, want)
+    own = RetinaNet(norm_runs["cfg"], params=model.state_dict()).eval()
+    assert _same_bits(live, _eval_logits(own, batch))                # the fold on exit is the live model's
+    assert not _same_bits(live, got)
+    mixed = dict(sd)
+    mixed.update(_stats(model.state_dict()))                         # averaged weights through the raw statistics of the last step
+    assert not _same_bits(_eval_logits(RetinaNet(norm_runs["cfg"], params=mixed).eval(), batch), want)
+
+
+def test_live_norm_applied_leaves_training_untouched(norm_runs):
+    """One model evaluates through applied(), its twin (the same three steps, never inside applied()) does not: a fourth step on each
+    gives the same losses, gradients, weights, running statistics and averages, bit for bit."""
+    f, p, batch = norm_runs["fused"], norm_runs["plain"], norm_runs["batches"][1]
+    with f["ema"].applied():
+        f["model"].eval()
+        _eval_logits(f["model"], batch)
+    f["model"].train()
+    outs = []
+    for run in (f, p):
+        model = run["model"]
+        losses = _losses(run["solver"].minimize(model, batch, ema=run["ema"]))
+        run["ema"].step()
+        torch.cuda.synchronize()
+        outs.append((losses, model.arena.g.clone(), model.arena.w.clone(), model.norms.running.clone(), run["ema"].state_dict()))
+    (la, ga, wa, ra, sa), (lb, gb, wb, rb, sb) = outs
+    print("step 4: after applied()", la, " twin", lb)
+    assert la == lb
+    assert _same_bits(ga, gb) and _same_bits(wa, wb) and _same_bits(ra, rb)
+    assert sa["iter"] == sb["iter"]
+    bad = [k for k, v in sa["model"].items() if not np.array_equal(_bits(v), _bits(sb["model"][k]))]
+    assert not bad, bad[:8]
+
+
+def test_live_norm_state_dict_roundtrip(norm_runs):
+    """ema2.load_state_dict(ema.state_dict()) on a second model (the initial parameters): the averaged parameters and buffers and the
+    eval logits under applied() come back bit for bit; the receiving model's own weights and buffers are untouched."""
+    from basedet_amd.layers import ModelEMA
+    from basedet_amd.models import RetinaNet
+    run, batch = norm_runs["fused"], norm_runs["batches"][2]
+    ema = run["ema"]
+    sd = ema.state_dict()
+    other = RetinaNet(norm_runs["cfg"], params=norm_runs["params"])
+    w_other, r_other = other.arena.w.clone(), other.norms.running.clone()
+    ema2 = ModelEMA(other, momentum=0.25)
+    ema2.load_state_dict(sd)
+    torch.cuda.synchronize()
+    assert ema2.iters == ema.iters
+    assert _same_bits(other.arena.w, w_other) and _same_bits(other.norms.running, r_other)
+    sd2 = ema2.state_dict()["model"]
+    assert sorted(sd2) == sorted(sd["model"])
+    stats = [k for k in sd2 if _is_stat(k)]
+    assert len(stats) == 2 * len(other.norms)
+    bad = [k for k in stats if not np.array_equal(_bits(sd2[k]), _bits(sd["model"][k]))]
+    assert not bad, ("buffers", bad[:8], len(bad))
+    bad = [k for k in other.state_dict_trainable_names() if not np.array_equal(_bits(sd2[k]), _bits(sd["model"][k]))]
+    assert not bad, ("parameters", bad[:8], len(bad))
+    assert any(not np.array_equal(sd2[k], v) for k, v in _stats(other.state_dict()).items())      # and they are not the receiver's own
+    logits = []
+    for m, e in ((run["model"], ema), (other, ema2)):
+        with e.applied():
+            m.eval()
+            logits.append(_eval_logits(m, batch))
+        m.train()
+    assert _same_bits(logits[0], logits[1])

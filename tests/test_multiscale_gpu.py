@@ -232,6 +232,67 @@ def test_retinanet_r50_recipe_shape_matches_oracle():
     _check_forward_layers(Oracle(params, P.oracle_arch(cfg), record={"_compare": acts}), batch, "retinanet_losses", "RetinaNet-R50 2x736x1088")
 
 
+NORM_SEQ = [(128, 160), (96, 192), (128, 160)]       # A, B (landscape, another P5 side), A again: 2 x H x W each
+
+
+def _normed_setup():
+    """RetinaNet-R18 with live norms in backbone and FPN (FREEZE_AT = 0), every norm's parameters and running statistics randomised."""
+    from backbone_norm_oracle import randomise_backbone_norms
+    from fpn_norm_oracle import randomise_norms
+    from tests.test_model_gpu import _setup
+    over = dict(MODEL=dict(BACKBONE=dict(FREEZE_AT=0, NORM="BN"), FPN=dict(NORM="BN")))
+    cfg, params, _ = _setup("resnet18", 2, NORM_SEQ[0], overrides=over)
+    return cfg, randomise_backbone_norms(randomise_norms(params))
+
+
+def _solver_step(model, solver, shape, seed):
+    """One solver step; the losses as floats and clones of the gradients, the weights and the running statistics after it."""
+    out = solver.minimize(model, _batch(2, shape, seed))
+    torch.cuda.synchronize()
+    return dict(losses={k: float(v) for k, v in out.items()}, g=model.arena.g.clone(), w=model.arena.w.clone(),
+                running=model.norms.running.clone())
+
+
+def test_live_norm_shape_switches_match_a_chain_of_single_shape_models():
+    """A normalised model takes solver steps at A, B, A: each shape's plan has its own pre-norm tensors (pl.norm_y / pl.norm_gy) while the
+    batch statistics, `sums` and the running statistics are the model's.  The chain: model 1 steps at A and hands its state_dict() and
+    optimizer state to a fresh model 2, which steps at B, and so on -- every model sees one shape.  Losses, gradients, weights and
+    norms.running after every step are equal bit for bit: a plan that read another plan's statistics or gate state would differ.  And
+    the memory bound of this module for this config: the arena is what the larger of the two plans needs (rounded to 2 MiB, as
+    PlanArena.grow rounds), which is the arena of the single-shape model of that shape."""
+    from basedet_amd.models import RetinaNet
+    from basedet_amd.solver import DetSolver
+    from util import bits_of
+    cfg, params = _normed_setup()
+    multi = RetinaNet(cfg, params=params)
+    assert len(multi.norms) > 20
+    solver = DetSolver.build(cfg, multi)
+    got = [_solver_step(multi, solver, s, 50 + i) for i, s in enumerate(NORM_SEQ)]
+    assert len({id(multi._plan(2, *s)) for s in NORM_SEQ}) == 2
+    want, single_arena, state, opt = [], [], params, None
+    for i, s in enumerate(NORM_SEQ):
+        m = RetinaNet(cfg, params=state)
+        sv = DetSolver.build(cfg, m)
+        if opt is not None:
+            sv.optimizer.load_state_dict(opt)
+        want.append(_solver_step(m, sv, s, 50 + i))
+        assert len(m._plans) == 1
+        single_arena.append(m.arena_bytes)
+        state, opt = m.state_dict(), sv.optimizer.state_dict()
+        del m, sv
+    for i, (a, b) in enumerate(zip(got, want)):
+        print(f"step {i} {NORM_SEQ[i]}: multi {a['losses']}  chain {b['losses']}")
+        assert a["losses"] == b["losses"], i
+        for k in ("g", "w", "running"):
+            assert torch.equal(bits_of(a[k]), bits_of(b[k])), (i, k, int((bits_of(a[k]) != bits_of(b[k])).sum()))
+    for k in ("w", "running"):                                       # every step moved the weights and the running statistics
+        assert not torch.equal(got[0][k], got[1][k]) and not torch.equal(got[1][k], got[2][k])
+    plans = [multi.plan_bytes(multi._plan(2, *s)) for s in NORM_SEQ[:2]]
+    print(f"plan bytes A {plans[0]}, B {plans[1]}; arena {multi.arena_bytes}; single-shape arenas {single_arena}")
+    assert multi.arena_bytes == -(-max(plans) // (2 << 20)) * (2 << 20)
+    assert multi.arena_bytes == max(single_arena)
+
+
 def test_fp8_r101_shape_sequence():
     """R101 with the fp8 defaults over [C, A, B, A] at batch 2: finite losses, and held memory <= 1.15 x that of a fresh fp8 model that
     ran only C (no bit-identity: the e5m2 stochastic rounding is seeded per step)."""
