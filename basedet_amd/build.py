@@ -38,6 +38,7 @@ SOURCES = {
     "conv_wgrad1x1.hip": [],
     "conv_wgrad1x1_ring.hip": [],
     "fpn_deconv.hip": [],
+    "deform_conv.hip": [],
     "stem.hip": [],
     "stem_bwd.hip": [],
     "boxops.hip": ["-ffp-contract=off"],

@@ -325,6 +325,41 @@ def fpn_deconv_wgrad(x, dy, dw, ws, N, Hc, Wc, C, accumulate=False):
     return dw
 
 
+_DCN_CONFIG = (3, 1, 1, 1, 1)      # kernel_size, stride, padding, dilation, deformable_groups: the one configuration deform_conv.hip builds
+
+
+def deform_conv_fwd(x, om, w_fwd, bias, y, N, H, W, Cin, Cout, modulated, config=_DCN_CONFIG):
+    """y [N H W][Cout] = bf16(bias + deformable 3x3 conv of x [N H W][Cin]) at the positions (and, modulated, masks) of om [N H W][ld]:
+    the raw offset-conv output (include/basedet_hip.h, bd_deform_conv_fwd); w_fwd = weight_pack's forward layout."""
+    check(L().bd_deform_conv_fwd(ptr(x), ptr(om), ptr(w_fwd), ptr(bias), ptr(y), N, H, W, Cin, Cout, om.shape[-1], int(modulated), *config,
+                                 stream_ptr()), "bd_deform_conv_fwd")
+    return y
+
+
+def deform_conv_wgrad_workspace_bytes(N, H, W, Cin, Cout):
+    return int(L().bd_deform_conv_wgrad_workspace_bytes(N, H, W, Cin, Cout))
+
+
+def deform_conv_wgrad(x, om, dy, dw, dbias, ws, N, H, W, Cin, Cout, modulated, accumulate=False, config=_DCN_CONFIG):
+    """dw [Cout][3][3][Cin] fp32 and dbias [Cout] fp32 (or None) (+)= the parameter gradients of deform_conv_fwd (reproducible)."""
+    check(L().bd_deform_conv_wgrad(ptr(x), ptr(om), ptr(dy), ptr(dw), ptr(dbias), int(accumulate), ptr(ws), ws.numel() * ws.element_size(),
+                                   N, H, W, Cin, Cout, om.shape[-1], int(modulated), *config, stream_ptr()), "bd_deform_conv_wgrad")
+    return dw
+
+
+def deform_conv_bwd_data_workspace_bytes(N, H, W, Cin, Cout):
+    return int(L().bd_deform_conv_bwd_data_workspace_bytes(N, H, W, Cin, Cout))
+
+
+def deform_conv_bwd_data(x, om, dy, w_dgrad, d_x, d_om, ws, N, H, W, Cin, Cout, modulated, add=None, config=_DCN_CONFIG):
+    """d_x [N H W][Cin] = bf16(data gradient [+ add]) and d_om [N H W][ld] = the gradient of the raw offset-conv output (reproducible;
+    d_x's last bits are not: fp32 atomics); w_dgrad = weight_pack's dgrad layout."""
+    check(L().bd_deform_conv_bwd_data(ptr(x), ptr(om), ptr(dy), ptr(w_dgrad), ptr(add), ptr(d_x), ptr(d_om), ptr(ws),
+                                      ws.numel() * ws.element_size(), N, H, W, Cin, Cout, om.shape[-1], int(modulated), *config,
+                                      stream_ptr()), "bd_deform_conv_bwd_data")
+    return d_x, d_om
+
+
 def stem_conv7x7_fwd(N, H, W, x_halo, w_stem, bias, y):
     check(L().bd_stem_conv7x7_fwd(N, H, W, ptr(x_halo), ptr(w_stem), ptr(bias), ptr(y), stream_ptr()), "bd_stem_conv7x7_fwd")
     return y

@@ -399,6 +399,39 @@ size_t bd_fpn_deconv_wgrad_workspace_bytes(int N, int Hc, int Wc, int C);
 int bd_fpn_deconv_wgrad(const void* x, const void* dy, float* dw, int accumulate, void* ws, size_t ws_bytes, int N, int Hc, int Wc,
                         int Hf, int Wf, int C, bd_stream_t stream);
 
+/* Deformable convolution, DCNv1 / DCNv2 (bd_version() >= 113; deform_conv.hip; layers/blocks/deformable.py:24-34,52-63 ->
+ * M.DeformableConv2d), forward and backward.  Only the configuration the reference instantiates (layers/head/center_head.py:22-30) is built:
+ * kernel_size = 3, stride = 1, padding = 1, dilation = 1, deformable_groups = 1 -- every entry takes the five values and answers BD_EINVAL
+ * for any other; Cin % 8 == 0, Cout % 8 == 0, tensors < 2 GB.
+ *   x  [N H W][Cin] bf16;  om [N H W][ld] bf16 = the RAW output of the offset convolution: channel 2k = dy, 2k + 1 = dx of tap k = 3 i + j;
+ *   modulated != 0: channel 18 + k = the mask logit of tap k (sigmoid applied here in fp32), ld % 8 == 0, ld >= 27 (32 in the layer);
+ *   modulated == 0: mask = 1, ld >= 18 (24).  Pad channels are never read; their gradient is written as +0.
+ * Output pixel (y, x), tap (i, j) samples at h = y - 1 + i + dy, w = x - 1 + j + dx: val = bilinear(x zero-extended, h, w), h0 = floor(h),
+ * w0 = floor(w), in fp32; the sample and all its gradients are 0 unless -1 < h < H and -1 < w < W, and inside that range a corner counts
+ * only if it lies in the image.  Coordinate gradients are those of the floor formula (right-hand derivative at an integer coordinate).
+ *   y[p][co] = bf16(bias[co] + sum_{k, ci} w[co][k][ci] m[p][k] val[p][k][ci]);  w_fwd = bd_weight_pack's forward layout [Cout][9][Cin];
+ *   bias may be NULL. */
+int bd_deform_conv_fwd(const void* x, const void* om, const void* w_fwd, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
+                       int ld, int modulated, int kernel_size, int stride, int padding, int dilation, int deformable_groups,
+                       bd_stream_t stream);
+/* Its weight and bias gradient: dw fp32 [Cout][3][3][Cin] (+)= sum_p dy[p][co] (m val)[p][k][ci], dbias fp32 [Cout] (+)= column sums of
+ * dy (dbias may be NULL); accumulate != 0 adds to both.  Pixel-split fp32 slabs in ws reduced in a fixed order, bd_colsum_bf16 for the
+ * bias: both bitwise reproducible. */
+size_t bd_deform_conv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout);
+int bd_deform_conv_wgrad(const void* x, const void* om, const void* dy, float* dw, float* dbias, int accumulate, void* ws, size_t ws_bytes,
+                         int N, int H, int W, int Cin, int Cout, int ld, int modulated, int kernel_size, int stride, int padding,
+                         int dilation, int deformable_groups, bd_stream_t stream);
+/* Its data gradients: d_x [N H W][Cin] = bf16(scatter [+ add]) (add may be NULL or equal to d_x) and d_om [N H W][ld] bf16, the gradient
+ * with respect to the RAW offset-conv output (already multiplied by sigmoid' for the mask logits): the g operand of the offset conv's
+ * bd_conv2d_dgrad / bd_conv2d_wgrad_bias as it stands.  w_dgrad = bd_weight_pack's dgrad layout [Cin][9][Cout].  ws holds the fp32
+ * [N H W][Cin] scatter target and one chunk (<= 64 MB) of the bf16 column gradient.  d_om is bitwise reproducible (fixed-order sums inside
+ * a workgroup); d_x is NOT: its fp32 atomic additions land in an order that depends on the data and the schedule, so its last bits may
+ * differ from run to run. */
+size_t bd_deform_conv_bwd_data_workspace_bytes(int N, int H, int W, int Cin, int Cout);
+int bd_deform_conv_bwd_data(const void* x, const void* om, const void* dy, const void* w_dgrad, const void* add, void* d_x, void* d_om,
+                            void* ws, size_t ws_bytes, int N, int H, int W, int Cin, int Cout, int ld, int modulated, int kernel_size,
+                            int stride, int padding, int dilation, int deformable_groups, bd_stream_t stream);
+
 /* elementwise helpers on bf16 buffers of n elements (n % 8 == 0) */
 int bd_relu_bf16(const void* x, void* y, int64_t n, bd_stream_t stream);
 /* y = (mask > 0 ? g : 0) [+ add] */
