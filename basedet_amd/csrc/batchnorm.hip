@@ -17,19 +17,7 @@ constexpr int BN_PXL = 8;        // pixel lanes of a stage-1 block (x 32 chunk l
 constexpr int BN_FL = 128;       // slot lanes of a stage-2 block (x 8 channels = 1024 threads)
 
 struct BnGeo { long long ppi, off; };            // a tensor's row addressing: row (img, p) = img * ppi + off + p
-struct BnWelford { float n, mean, m2; };
-
-// Chan et al.: the statistics of the union of two disjoint sets
-__device__ __forceinline__ BnWelford bn_combine(BnWelford a, BnWelford b) {
-    const float n = a.n + b.n;
-    if (n == 0.f) return a;
-    const float d = b.mean - a.mean, f = b.n / n;
-    BnWelford o;
-    o.n = n;
-    o.mean = a.mean + d * f;
-    o.m2 = a.m2 + b.m2 + d * d * a.n * f;
-    return o;
-}
+// (BnWelford / bn_combine, Chan et al.'s statistics of the union of two disjoint sets: common.h -- GroupNorm shares them)
 
 __device__ __forceinline__ void unpack8(const u32x4_t v, float* o) {
 #pragma unroll

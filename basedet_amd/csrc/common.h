@@ -102,6 +102,26 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- variance without a raw sum of squares (batchnorm.hip, norm.hip, the GroupNorm epilogue of conv3x3_pp.hip) --------------------------
+// (count, mean, M2 = sum of squared deviations from the mean) of a set of values; bn_combine is Chan et al.'s update for the union of two
+// disjoint sets.  Exact where it has to be: an empty side (n = 0) leaves the other unchanged, equal means add nothing to M2.
+struct BnWelford { float n, mean, m2; };
+__device__ __forceinline__ BnWelford bn_combine(BnWelford a, BnWelford b) {
+    const float n = a.n + b.n;
+    if (n == 0.f) return a;
+    const float d = b.mean - a.mean, f = b.n / n;
+    BnWelford o;
+    o.n = n;
+    o.mean = a.mean + d * f;
+    o.m2 = a.m2 + b.m2 + d * d * a.n * f;
+    return o;
+}
+// a thread's own values, accumulated SHIFTED by the first of them (s = sum of v - K, ss = sum of (v - K)^2 over n values)
+__device__ __forceinline__ BnWelford bn_from_shifted(float n, float K, float s, float ss) {
+    const float inv = n > 0.f ? 1.f / n : 0.f;
+    return BnWelford{n, n > 0.f ? K + s * inv : 0.f, fmaxf(ss - s * s * inv, 0.f)};
+}
+
 // ---- moving average of a weight (ema.hip, and the optimizer launches of ema.hip / optim.hip that fold it in) -----------------------------
 // ema.py:80: v * m + (1 - m) * model_state -- each product rounded to fp32, then the sum; never an FMA (the compiler contracts a * b + c by
 // default, and __fmul_rn / __fadd_rn are plain operators here, so the function switches contraction off).  (1 - m) arrives as an

@@ -57,7 +57,7 @@ struct PParams {
     int tail_end;            // the 64-channel tile of conv3x3_pp128_body.h over patches [total_patches, tail_end)
     float inv_ppi;           // 1 / patches_per_img (the patch indices are < 2^24: exact quotients by a float multiply and one correction)
     PSeg seg[MAX_SEG];
-    float* gn_part;          // GNS instance only: per (patch, group of 8 channels) the (sum, sum of squares) of the fp32 results, [patch][32][2]
+    float* gn_part;          // GNS instance only: per (patch, group of 8 channels) the (mean, M2) of the fp32 results inside the level, [patch][32][2]
     // SPARSE instance only (bd_conv_desc.gskip, gskip.hip): the tiles are cut from the live patches sp_list[0 .. *sp_count) in that order; the
     // other patches (sp_live[q] == 0) are written as +0 behind the tiles, by every workgroup, or left as they are (sp_keep_dead: in-place accumulate)
     const int* sp_live;
@@ -582,7 +582,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
             for (int k = 0; k < 4; ++k) dma_piece(2, 0, 2, k);
         }
         PP_FENCE();
-        float gsum[4] = {0.f, 0.f, 0.f, 0.f}, gsq[4] = {0.f, 0.f, 0.f, 0.f};          // GNS: this lane's (sum, sum of squares) per channel group h
+        // GNS: this lane's sum and sum of squares per channel group h, of its fp32 results SHIFTED by the first of them (gk): a raw sum of
+        // squares loses the variance of a group whose bias is large against its response (norm.hip)
+        float gsum[4] = {0.f, 0.f, 0.f, 0.f}, gsq[4] = {0.f, 0.f, 0.f, 0.f}, gk[4] = {0.f, 0.f, 0.f, 0.f};
         auto unit = [&](int h, int j, const f32x4_t b0, const f32x4_t b1) {
             u32x4_t o;
 #pragma unroll
@@ -592,7 +594,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
                 f32x2_e v = {a[2 * (k & 1)], a[2 * (k & 1) + 1]};
                 v += (f32x2_e){bb[2 * (k & 1)], bb[2 * (k & 1) + 1]};
                 if constexpr (GNS) {
-                    if (okj[j]) { gsum[h] += v[0] + v[1]; gsq[h] += v[0] * v[0] + v[1] * v[1]; }
+                    if (j == 0 && k == 0) gk[h] = v[0];          // (row 0 of a patch is inside the level wherever the lane's column is)
+                    if (okj[j]) {
+                        const float d0 = v[0] - gk[h], d1 = v[1] - gk[h];
+                        gsum[h] += d0 + d1; gsq[h] = __fmaf_rn(d0, d0, __fmaf_rn(d1, d1, gsq[h]));
+                    }
                 }
                 i16x2_e w = __builtin_bit_cast(i16x2_e, __builtin_convertvector(v, bf16x2_e));
                 if (do_mask) {          // keep where the stored activation is > 0: sat(0 - m) >> 15 is all ones exactly for m > 0 (-0.0 = 0x8000 saturates to 32767)
@@ -641,19 +647,32 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const PParams p) {
             }
         }
         if constexpr (GNS) {
-            // the 16 lanes of a row (same channel groups, 16 pixel columns): butterfly over lane bits 3..0 -- a fixed order; lane 0 of the row
-            // stores the four (sum, sum of squares) pairs of the wave's patch: part[(patch * 32 + group) * 2], group = channel / 8
+            // the 16 lanes of a row (same channel groups, 16 pixel columns): butterfly over lane bits 3..0 -- a fixed order -- of Chan's
+            // (count, mean, M2) update (common.h); a lane's count is 8 channels x the patch's rows inside the level, or 0 for a column
+            // outside it, and is the same for the four channel groups.  Lane 0 of the row stores the four (mean, M2) pairs of the wave's
+            // patch: part[(patch * 32 + group) * 2], group = channel / 8; norm.hip derives the patch's count from its position.
             const int pid = pt * NPATCH + wp;
+            const int rows_in = H - oy0 < PH ? H - oy0 : PH;
+            float cn = ox < W && rows_in > 0 ? 8.f * (float)rows_in : 0.f;
+            BnWelford wf[4];
 #pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                float a = gsum[h], b = gsq[h];
+            for (int h = 0; h < 4; ++h) wf[h] = bn_from_shifted(cn, gk[h], gsum[h], gsq[h]);
 #pragma unroll
-                for (int m = 8; m >= 1; m >>= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
+            for (int m = 8; m >= 1; m >>= 1) {
+                const float on = __shfl_xor(cn, m, 64);
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const BnWelford o = {on, __shfl_xor(wf[h].mean, m, 64), __shfl_xor(wf[h].m2, m, 64)};
+                    wf[h] = bn_combine(BnWelford{cn, wf[h].mean, wf[h].m2}, o);
+                }
+                cn += on;
+            }
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
                 if (erow == 0 && pid < p.total_patches && cbase + 32 * h < p.CO) {
                     float* o = p.gn_part + ((long long)pid * 32 + ((cbase + 32 * h) >> 3)) * 2;
-                    *reinterpret_cast<f32x2_t*>(o) = (f32x2_t){a, b};
+                    *reinterpret_cast<f32x2_t*>(o) = (f32x2_t){wf[h].mean, wf[h].m2};
                 }
-            }
         }
     } else {
     // General path (a residual / accumulate operand): the operands of TWO channel groups (eight 16-byte units: up to 64 VGPRs of residuals +
@@ -946,7 +965,8 @@ int bd_conv3x3_pp_launch(const bd_conv_desc* d, int mode, const void* src, const
 
 // The patch layout of this kernel over a multi-level output, for the consumers of the GNS instance's statistics (norm.hip): starts[l] = first
 // patch of level l inside one image, starts[nseg] = patches per image.
-int bd_conv3x3_pp_patch_starts(const bd_conv_desc* d, int* starts) {
+int bd_conv3x3_pp_patch_starts(const bd_conv_desc* d, int* starts, int* patch_hw) {
+    if (patch_hw) { patch_hw[0] = PH; patch_hw[1] = PW; }          // patches tile a level in row-major order, clipped at its right and lower edge
     int ps = 0;
     for (int s = 0; s < d->nseg; ++s) { starts[s] = ps; ps += cdiv(d->Ho[s], PH) * cdiv(d->Wo[s], PW); }
     starts[d->nseg] = ps;
@@ -956,7 +976,7 @@ int bd_conv3x3_pp_patch_starts(const bd_conv_desc* d, int* starts) {
 extern "C" size_t bd_conv2d_fwd_gnstats_bytes(const bd_conv_desc* d) {
     if (!d || d->nseg < 1 || d->nseg > BD_MAX_SEGS) return 0;
     int starts[BD_MAX_SEGS + 1];
-    return (size_t)d->N * bd_conv3x3_pp_patch_starts(d, starts) * 32 * 2 * sizeof(float);
+    return (size_t)d->N * bd_conv3x3_pp_patch_starts(d, starts, nullptr) * 32 * 2 * sizeof(float);
 }
 
 extern "C" int bd_conv2d_fwd_gnstats(const bd_conv_desc* d, const void* x, const void* w_packed, const float* bias, void* y, float* part,

@@ -13,7 +13,12 @@
 //     chunk (stats of chunk c, then apply of chunk c), so that the second kernel re-reads what the first has just pulled through the
 //     256 MB Infinity Cache -- FCOS-R50 batch 16, one box: 622.7 img/s unchunked, 589.1 at 8 / 4 images per chunk, 544.0 at 4 / 2, 520.4
 //     at 2 / 2 (profiles/r05_gn_chunks.txt): the smaller launches lose more in ramps and tails than the cache returns.
-// Reductions are two-stage with a fixed partial order (no float atomics): bitwise reproducible, and independent of the chunking.
+// Reductions are two-stage with a fixed partial order (no float atomics): bitwise reproducible, and independent of the batch size.
+// The variance never goes through a raw sum of squares (var = E[y^2] - mean^2 from fp32 sums lost most of it once |mean| >> std: a
+// tower channel group with a large bias and a small response).  As in batchnorm.hip: a thread accumulates its (at most 128) values SHIFTED
+// by the first of them, and every combination after that -- the eight pixel lanes of a slot, a level's slots, the 32 lanes of the final
+// kernel -- is Chan's pairwise update of (count, mean, M2) (common.h, bn_combine) in the same fixed order the sums had.  The count of a slot
+// or patch follows from its index, so a partial stays two floats: (mean, M2).  A constant group comes out with M2 = 0 exactly.
 #include "common.h"
 
 namespace {
@@ -22,7 +27,19 @@ constexpr int GN_SLOT_PX = 128;   // pixels per partial-stage slot
 constexpr int MAXL = BD_MAX_SEGS;
 
 // slot0[l] = first slot of level l inside an image's slot list (slot0[L] = slots per image)
-struct GnLevels { int L; int off[MAXL]; int cnt[MAXL]; int slot0[MAXL + 1]; };
+// pw == 0: a slot is GN_SLOT_PX consecutive pixels.  pw > 0 (the partials of the convolution's epilogue): a slot is a ph x pw patch of the
+// H[l] x W[l] level, patches in row-major order, each clipped to the level.
+struct GnLevels { int L; int off[MAXL]; int cnt[MAXL]; int slot0[MAXL + 1]; int H[MAXL]; int W[MAXL]; int ph, pw; };
+
+// values (pixels x channels of a group) behind partial j of level l
+__device__ __forceinline__ float gn_slot_count(const GnLevels& lv, int l, int j, int cpg) {
+    if (lv.pw > 0) {
+        const int npw = (lv.W[l] + lv.pw - 1) / lv.pw;
+        const int by = j / npw, bx = j - by * npw;
+        return (float)(min(lv.ph, lv.H[l] - by * lv.ph) * min(lv.pw, lv.W[l] - bx * lv.pw) * cpg);
+    }
+    return (float)(min(GN_SLOT_PX, lv.cnt[l] - j * GN_SLOT_PX) * cpg);
+}
 
 // z = relu(xhat * gamma + beta) with xhat = (y - mean) * rstd: ONE instruction sequence for the forward's value and the backward's gate
 __device__ __forceinline__ float gn_xhat(float y, float mean, float rstd) { return __fmul_rn(__fsub_rn(y, mean), rstd); }
@@ -39,10 +56,10 @@ __device__ __forceinline__ int slot_level(const GnLevels& lv, int slot) {
 }
 
 // block = 256 threads = 32 groups x 8 pixel lanes; grid = (slots per image, images of the chunk)
-// partial[(n * S + slot) * 32 + g][2] = (sum, sumsq)
+// partial[(n * S + slot) * 32 + g][2] = (mean, M2) of the slot's pixels x 8 channels
 __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const bf16_raw* __restrict__ y, GnLevels lv, int ppi, int C,
                                                                float* __restrict__ partial) {
-    __shared__ float red[256][2];
+    __shared__ float red[256][3];
     const int g = threadIdx.x & 31, pl = threadIdx.x >> 5;
     const int slot = blockIdx.x, n = blockIdx.y, S = lv.slot0[lv.L];
     const int l = slot_level(lv, slot);
@@ -51,7 +68,8 @@ __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const bf16_raw* _
     int p1 = p0 + GN_SLOT_PX;
     if (p1 > cnt) p1 = cnt;
     const bf16_raw* base = y + ((long long)n * ppi + lv.off[l]) * C + g * 8;
-    float s = 0.f, ss = 0.f;
+    // shifted by K = the thread's first value (differences of bf16 values are exact in fp32)
+    float s = 0.f, ss = 0.f, K = 0.f;
     // four pixels per thread and trip: four independent 16-byte loads in flight
     for (int p = p0 + pl; p < p1; p += 32) {
         u32x4_t v[4];
@@ -60,50 +78,51 @@ __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const bf16_raw* _
             const int q = p + 8 * u;
             v[u] = q < p1 ? *reinterpret_cast<const u32x4_t*>(base + (long long)q * C) : (u32x4_t){0u, 0u, 0u, 0u};
         }
+        if (p == p0 + pl) K = bf_lo(v[0][0]);
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
+        for (int u = 0; u < 4; ++u) {
+            const bool ok = p + 8 * u < p1;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float a = bf_lo(v[u][k]), b = bf_hi(v[u][k]);
-                s += a + b; ss += a * a + b * b;
+                const float a = ok ? bf_lo(v[u][k]) - K : 0.f, b = ok ? bf_hi(v[u][k]) - K : 0.f;
+                s += a + b; ss = __fmaf_rn(a, a, __fmaf_rn(b, b, ss));
             }
+        }
     }
-    red[threadIdx.x][0] = s; red[threadIdx.x][1] = ss;
+    const int left = p1 - p0 - pl;                                   // this lane's pixels: p0 + pl, + 8, ... below p1
+    const BnWelford t = bn_from_shifted(left > 0 ? (float)(((left + 7) >> 3) * 8) : 0.f, K, s, ss);
+    red[threadIdx.x][0] = t.n; red[threadIdx.x][1] = t.mean; red[threadIdx.x][2] = t.m2;
     __syncthreads();
     if (pl == 0) {
-        float ts = 0.f, tss = 0.f;
-        for (int k = 0; k < 8; ++k) { ts += red[k * 32 + g][0]; tss += red[k * 32 + g][1]; }
+        BnWelford a = {red[g][0], red[g][1], red[g][2]};
+        for (int k = 1; k < 8; ++k) a = bn_combine(a, BnWelford{red[k * 32 + g][0], red[k * 32 + g][1], red[k * 32 + g][2]});
         float* o = partial + (((long long)n * S + slot) * 32 + g) * 2;
-        o[0] = ts; o[1] = tss;
+        o[0] = a.mean; o[1] = a.m2;
     }
 }
 
 // stats[(n*L + l)*32 + g] = (mean, rstd).  One workgroup per (image, level): GN_FQ lanes per group walk the level's slots (lane q: slots q,
-// q + GN_FQ, ...), then the partial sums are added in lane order -- a fixed order; a single thread per (n, l, g) summing the 132 slots
+// q + GN_FQ, ...) combining their (count, mean, M2), then the lanes are combined in lane order -- a fixed order; a single thread per (n, l, g) summing the 132 slots
 // of the largest level one after the other took 37 us per launch (rocprofv3, first form of round 5).  Round 6: 32 lanes per group instead of 8 --
 // the slots of the fused form are the convolution's 4 x 16-pixel patches (275 on the largest level at 800 x 1344): 16 -> 6 us per launch (rocprofv3).
 constexpr int GN_FQ = 32;
 __global__ __launch_bounds__(32 * GN_FQ) void gn_stats_final_kernel(const float* __restrict__ partial, GnLevels lv, int cpg, float eps,
                                                                     float* __restrict__ stats) {
-    __shared__ float red[GN_FQ][32][2];
+    __shared__ float red[GN_FQ][32][3];
     const int g = threadIdx.x & 31, q = threadIdx.x >> 5;
     const int l = blockIdx.x, n = blockIdx.y, S = lv.slot0[lv.L];
-    float s = 0.f, ss = 0.f;
+    BnWelford a = {0.f, 0.f, 0.f};
     for (int c = lv.slot0[l] + q; c < lv.slot0[l + 1]; c += GN_FQ) {
         const float* o = partial + (((long long)n * S + c) * 32 + g) * 2;
-        s += o[0]; ss += o[1];
+        a = bn_combine(a, BnWelford{gn_slot_count(lv, l, c - lv.slot0[l], cpg), o[0], o[1]});
     }
-    red[q][g][0] = s; red[q][g][1] = ss;
+    red[q][g][0] = a.n; red[q][g][1] = a.mean; red[q][g][2] = a.m2;
     __syncthreads();
     if (q == 0) {
-        s = 0.f; ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < GN_FQ; ++k) { s += red[k][g][0]; ss += red[k][g][1]; }
-        const float inv = 1.f / ((float)lv.cnt[l] * (float)cpg);
-        const float mean = s * inv;
-        const float var = fmaxf(ss * inv - mean * mean, 0.f);
+        for (int k = 1; k < GN_FQ; ++k) a = bn_combine(a, BnWelford{red[k][g][0], red[k][g][1], red[k][g][2]});
+        const float var = a.m2 / ((float)lv.cnt[l] * (float)cpg);
         const int i = (n * lv.L + l) * 32 + g;
-        stats[i * 2] = mean;
+        stats[i * 2] = a.mean;
         stats[i * 2 + 1] = rsqrtf(var + eps);
     }
 }
@@ -444,20 +463,23 @@ extern "C" int bd_groupnorm_fwd(const void* y, const float* gamma, const float* 
     return BD_OK;
 }
 
-int bd_conv3x3_pp_patch_starts(const bd_conv_desc* d, int* starts);          // conv3x3_pp.hip
+int bd_conv3x3_pp_patch_starts(const bd_conv_desc* d, int* starts, int* patch_hw);          // conv3x3_pp.hip
 
-// GroupNorm forward from the per-patch statistics the producing convolution left (bd_conv2d_fwd_gnstats): the finalize kernel sums a level's
-// patches exactly as it sums 128-pixel slots (8 lanes per group in patch order, then the eight partial sums in lane order: a fixed order),
-// then the unchanged apply pass.  d = that convolution's descriptor (its output levels are the tensor's levels).
+// GroupNorm forward from the per-patch statistics the producing convolution left (bd_conv2d_fwd_gnstats): (mean, M2) of each patch's valid
+// pixels.  The finalize kernel combines a level's patches exactly as it combines 128-pixel slots (32 lanes per group in patch order, then
+// the lanes in lane order: a fixed order); a patch's count comes from its position in the level (gn_slot_count).  Then the unchanged apply pass.  d = that convolution's descriptor (its output levels are the tensor's levels).
 extern "C" int bd_groupnorm_fwd_parts(const bd_conv_desc* d, const void* y, const float* part, const float* gamma, const float* beta, float eps,
                                       int relu, float* stats, void* z, bd_stream_t stream) {
     BD_REQUIRE(d && y && part && gamma && beta && stats && z, "groupnorm_fwd_parts: null pointer");
     BD_REQUIRE(d->Cout == 256 && d->nseg >= 1 && d->nseg <= MAXL && d->N >= 1, "groupnorm_fwd_parts: 256 channels, 1 .. %d levels", MAXL);
     GnLevels lv{};
     lv.L = d->nseg;
-    int starts[BD_MAX_SEGS + 1];
-    const int S = bd_conv3x3_pp_patch_starts(d, starts);
-    for (int i = 0; i < d->nseg; ++i) { lv.off[i] = d->out_off[i]; lv.cnt[i] = d->Ho[i] * d->Wo[i]; lv.slot0[i] = starts[i]; }
+    int starts[BD_MAX_SEGS + 1], patch_hw[2];
+    const int S = bd_conv3x3_pp_patch_starts(d, starts, patch_hw);
+    lv.ph = patch_hw[0]; lv.pw = patch_hw[1];
+    for (int i = 0; i < d->nseg; ++i) {
+        lv.off[i] = d->out_off[i]; lv.cnt[i] = d->Ho[i] * d->Wo[i]; lv.slot0[i] = starts[i]; lv.H[i] = d->Ho[i]; lv.W[i] = d->Wo[i];
+    }
     for (int i = d->nseg; i <= MAXL; ++i) lv.slot0[i] = S;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(gn_stats_final_kernel, dim3(d->nseg, d->N), dim3(32 * GN_FQ), 0, st, part, lv, 8, eps, stats);

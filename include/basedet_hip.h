@@ -593,9 +593,11 @@ int bd_groupnorm_fwd(const void* y, const float* gamma, const float* beta, int N
                      void* z, void* ws, size_t ws_bytes, bd_stream_t stream);
 /* The tower step conv -> GroupNorm(32) -> ReLU (point_head.py:47-58) with the statistics pass FUSED into the convolution (round 6):
  * bd_conv2d_fwd_gnstats = bd_conv2d_fwd of a 3x3 / stride 1 / pad 1 convolution into 256 channels (bias, no residual / ReLU) that also leaves,
- * per 4 x 16-pixel output patch and group of 8 channels, the (sum, sum of squares) of its fp32 results in `part` (bd_conv2d_fwd_gnstats_bytes;
- * the layout is the kernel's own and only bd_groupnorm_fwd_parts reads it); bd_groupnorm_fwd_parts = bd_groupnorm_fwd without its statistics
- * pass: it sums a level's patches in a fixed order into stats (mean, rstd) and applies.  The statistics come from the UNROUNDED results
+ * per 4 x 16-pixel output patch and group of 8 channels, the (mean, M2 = sum of squared deviations) of its fp32 results inside the level in
+ * `part` (bd_version() >= 114; before: the raw sum and sum of squares, which lost the variance of a group with |mean| >> std;
+ * bd_conv2d_fwd_gnstats_bytes; the layout is the kernel's own and only bd_groupnorm_fwd_parts reads it); bd_groupnorm_fwd_parts =
+ * bd_groupnorm_fwd without its statistics pass: it combines a level's patches in a fixed order (Chan's update; a patch's count follows from
+ * its position) into stats (mean, rstd) and applies.  The statistics come from the UNROUNDED results
  * (within 2e-3 of the separate pass, which reads the bf16 tensor); reproducible bit for bit.  d = the convolution's descriptor for both calls. */
 size_t bd_conv2d_fwd_gnstats_bytes(const bd_conv_desc* d);
 int bd_conv2d_fwd_gnstats(const bd_conv_desc* d, const void* x, const void* w_packed, const float* bias, void* y, float* part,
