@@ -1101,3 +1101,47 @@ def bottleneck_fwd(N, H, W, cin, cmid, cout, x, w1, b1, w2, b2, w3, b3, wd, bd, 
     check(L().bd_bottleneck_fwd(int(N), int(H), int(W), int(cin), int(cmid), int(cout), ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2),
                                 ptr(w3), ptr(b3), ptr(wd), ptr(bd), ptr(y), stream_ptr()), "bd_bottleneck_fwd")
     return y
+
+
+# ---- CenterNet after the last convolution (centernet.hip) -------------------------------------------------------------------------------
+def centernet_targets(gt_boxes, num_gt, K, H, W, T, box_scale, min_overlap):
+    """bd_centernet_targets: gt_boxes fp32 (N, Gmax, 5), num_gt int32 (N,) -> dict of score_map fp32 (N, H*W, K) (pixel-major), wh / reg
+    (N, T, 2), reg_mask (N, T), index int32 (N, T), num_pos fp32 (1,)."""
+    N, G = int(gt_boxes.shape[0]), int(gt_boxes.shape[1])
+    dev = gt_boxes.device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    out = dict(score_map=f(N, H * W, K), wh=f(N, T, 2), reg=f(N, T, 2), reg_mask=f(N, T),
+               index=torch.empty((N, T), dtype=torch.int32, device=dev), num_pos=f(1))
+    ws = torch.empty(int(L().bd_centernet_targets_workspace_bytes(N)), dtype=torch.uint8, device=dev)
+    centernet_targets_into(gt_boxes, num_gt, N, G, K, H, W, T, box_scale, min_overlap, out["score_map"], out["wh"], out["reg"],
+                           out["reg_mask"], out["index"], out["num_pos"], ws)
+    return out
+
+
+def centernet_targets_into(gt_boxes, num_gt, N, G, K, H, W, T, box_scale, min_overlap, score_map, wh, reg, reg_mask, index, num_pos, ws):
+    check(L().bd_centernet_targets(ptr(gt_boxes), ptr(num_gt), N, G, K, H, W, T, float(box_scale), float(min_overlap), ptr(score_map),
+                                   ptr(wh), ptr(reg), ptr(reg_mask), ptr(index), ptr(num_pos), ptr(ws), ws.numel() * ws.element_size(),
+                                   stream_ptr()), "bd_centernet_targets")
+
+
+def centernet_focal_fwd_bwd(logits, score_map, rows, K, ld, norm, weight, grad_scale, loss_sum, dlogits):
+    """logits / dlogits bf16 [rows][ld], score_map fp32 [rows][K], norm = the device num_pos; loss_sum[0] += weight * loss."""
+    check(L().bd_centernet_focal_fwd_bwd(ptr(logits), ptr(score_map), rows, K, ld, ptr(norm), float(weight), float(grad_scale),
+                                         ptr(loss_sum), ptr(dlogits), stream_ptr()), "bd_centernet_focal_fwd_bwd")
+
+
+def centernet_l1_fwd_bwd(pred, ld, off, index, reg_mask, target, N, H, W, T, weight, grad_scale, loss_sum, dpred):
+    """pred / dpred bf16 [N*H*W][ld], the two channels at column off; loss_sum[0] += weight * loss; dpred is written completely."""
+    check(L().bd_centernet_l1_fwd_bwd(ptr(pred), ld, off, ptr(index), ptr(reg_mask), ptr(target), N, H, W, T, float(weight),
+                                      float(grad_scale), ptr(loss_sum), ptr(dpred), stream_ptr()), "bd_centernet_l1_fwd_bwd")
+
+
+def centernet_decode_workspace_bytes(B, K, H, W):
+    return int(L().bd_centernet_decode_workspace_bytes(B, K, H, W))
+
+
+def centernet_decode(logits, ld, wh, wh_ld, wh_off, reg, reg_ld, reg_off, B, K, H, W, k, boxes, scores, classes, ws):
+    """reg may be None (+0.5).  boxes fp32 [B][k][4], scores fp32 [B][k], classes int32 [B][k]."""
+    check(L().bd_centernet_decode(ptr(logits), ld, ptr(wh), wh_ld, wh_off, ptr(reg), reg_ld, reg_off, B, K, H, W, k, ptr(boxes),
+                                  ptr(scores), ptr(classes), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+          "bd_centernet_decode")

@@ -855,6 +855,67 @@ int bd_det_finalize(const float* boxes, const float* scores, const int32_t* labe
                     float* out_boxes, float* out_scores, int32_t* out_labels, bd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * CenterNet after the last convolution (bd_version() >= 115; centernet.hip; models/det/centernet.py): ground-truth maps, the heat-map
+ * focal loss, the gathered L1 losses and the decoder.  Predictions are pixel-major bf16 [N*H*W][ld] as a convolution launch leaves
+ * them; side data fp32 / int32.  Every output is bitwise reproducible (integer atomics and fixed-order sums only).
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* CenterNet.get_ground_truth (centernet.py:74-127) + CenterNetGT.generate_score_map / get_gaussian_radius / gaussian2D / draw_gaussian
+ * (centernet.py:378-452) for a batch.  gt_boxes [N][Gmax][5] (x1,y1,x2,y2 in input pixels, class 1-based), num_gt [N] int32: the batch
+ * contract of bd_retina_assign_encode.  Per image, in the reference's order: the first num_gt boxes; those with w <= 0 or h <= 0 dropped
+ * (Boxes.filter_by_size) and the survivors compacted into slots 0..; coordinates * box_scale (= 1 / HEAD.DOWN_SCALE); centre =
+ * ((x1+x2)/2, (y1+y2)/2), centers_int its truncation; index = cy * W + cx, reg = centre - centers_int, wh = (w, h), reg_mask = 1;
+ * class = label - 1, and a slot of class < 0 keeps its targets and draws nothing (centernet.py:387).  radius = int(max(0, min(r1, r2,
+ * r3))) of get_gaussian_radius -- the reference's "bug version" -- evaluated in float32 exactly as written (one rounding per operation;
+ * (1 - min_overlap), (1 + min_overlap), -2 min_overlap, (min_overlap - 1) and 4 * (4 min_overlap) formed in double from the double
+ * argument and rounded once).  Every in-map pixel of the (2r+1)^2 window around centers_int, clipped as draw_gaussian's left / right /
+ * top / bottom clip it, takes max(old, exp(-(dx^2 + dy^2) / (2 sigma^2))) with sigma = (2r+1)/6 in float32: the centre exactly 1.0f,
+ * everything outside every window exactly +0.  gaussian2D's `eps * max` cut never fires at this sigma (the corner of a window is
+ * exp(-36 r^2 / (2r+1)^2) > e^-9) and is not coded.
+ * Outputs: score_map fp32 [N][H*W][K] -- pixel-major like the logits it is compared with (the reference's (N, K, H, W) is a view of
+ * it) --, wh [N][T][2], reg [N][T][2], reg_mask [N][T], index int32 [N][T] (T = HEAD.TENSOR_DIM <= 1024; unused slots zero), num_pos
+ * fp32 [1] = the number of map elements equal to 1 = the distinct drawn (image, class, index) triples.
+ * Where the reference is undefined: a box whose centers_int lies outside the map gets reg_mask 0 / index 0 and draws nothing; a class
+ * >= K is treated as a class < 0 (slot kept, nothing drawn); of more than T surviving boxes the first T are used.
+ * ws: bd_centernet_targets_workspace_bytes(N) (the per-image counts). */
+size_t bd_centernet_targets_workspace_bytes(int N);
+int bd_centernet_targets(const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, int K, int H, int W, int T, float box_scale,
+                         double min_overlap, float* score_map, float* wh, float* reg, float* reg_mask, int32_t* index, float* num_pos,
+                         void* ws, size_t ws_bytes, bd_stream_t stream);
+
+/* modified_focal_loss (centernet.py:218-242) of sigmoid(logits) (the head's sigmoid, layers/head/center_head.py) against the score map,
+ * with its gradient, in one fused launch + the ordered finish of the other losses.  logits / dlogits bf16 [rows][ld], ld = K rounded up
+ * to a multiple of 8 (pad slots: no loss, gradient +0); score_map fp32 [rows][K]; norm = the device num_pos of bd_centernet_targets.
+ * p = clip(sigmoid(x), 1e-12, fp32(1 - 1e-7)); gt == 1: log(p) (1-p)^2, else log(1-p) p^2 (1-gt)^4; loss = -(pos + neg) / num_pos, or
+ * -neg when num_pos == 0.  loss_sum[0] += weight * loss; dlogits = weight * grad_scale * d loss / d logit (through the sigmoid; zero
+ * where the clip is active, as F.clip's gradient).  1 - p is formed as sigmoid(-x), never as 1.f - p.  At most bd_loss_grid_cap()
+ * blocks; per-block partials summed in index order. */
+int bd_centernet_focal_fwd_bwd(const void* logits, const float* score_map, int64_t rows, int K, int ld, const float* norm, float weight,
+                               float grad_scale, float* loss_sum, void* dlogits, bd_stream_t stream);
+
+/* reg_l1_loss + gather_feature (centernet.py:189-215) with its gradient.  pred / dpred bf16 [N*H*W][ld] (ld a multiple of 8), the two
+ * channels at the even column `off` (wh and reg may share one convolution output); index int32 [N][T], reg_mask fp32 [N][T], target
+ * fp32 [N][T][2] (T <= 1024).  loss_sum[0] += weight * sum |pred m - tgt m| / (sum of m broadcast to (N, T, 2) + 1e-4) -- the
+ * denominator is 2 * sum(m) + 1e-4, as the reference has it.  dpred is written completely: +0 everywhere (pad channels included) but
+ * at the gathered pixels, which hold the sum, in slot order, of sign(pred - tgt) * m * weight * grad_scale / denominator over the
+ * slots that point at them (sign(0) = 0).  A slot with m == 0 or an index outside [0, H*W) reads and writes nothing. */
+int bd_centernet_l1_fwd_bwd(const void* pred, int ld, int off, const int32_t* index, const float* reg_mask, const float* target, int N,
+                            int H, int W, int T, float weight, float grad_scale, float* loss_sum, void* dpred, bd_stream_t stream);
+
+/* CenterNetDecoder.decode with pseudo_nms and topk_score (centernet.py:245-352; cat_spec_wh = False).  logits bf16 [B][H*W][ld], ld = K
+ * rounded up to a multiple of 8; wh / reg bf16 [B][H*W][wh_ld / reg_ld] with their two channels at column wh_off / reg_off; reg may be
+ * NULL (+0.5, centernet.py:269-270).  score = sigmoid(logit) in fp32 as bd_det_scores computes it; an element keeps its score iff it
+ * equals the maximum of the 3x3 window of those fp32 scores in its class plane (out-of-map neighbours do not compete), else it
+ * competes with 0 (fmap * keep).  The best k (<= 2048, <= H*W) of an image over all classes and pixels come out by score descending,
+ * then class ascending, then pixel index ascending -- the set the reference's two-stage top-k selects; the tie order is this
+ * library's.  boxes [B][k][4] = (xs - w/2, ys - h/2, xs + w/2, ys + h/2) in map cells, xs = x + reg_x, ys = y + reg_y; scores [B][k];
+ * classes int32 [B][k].  K * H * W < 2^31.  ws: bd_centernet_decode_workspace_bytes (the fp32 peak map, [B][K][H*W]). */
+size_t bd_centernet_decode_workspace_bytes(int B, int K, int H, int W);
+int bd_centernet_decode(const void* logits, int ld, const void* wh, int wh_ld, int wh_off, const void* reg, int reg_ld, int reg_off,
+                        int B, int K, int H, int W, int k, float* boxes, float* scores, int32_t* classes, void* ws, size_t ws_bytes,
+                        bd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimizer (megengine.optimizer.SGD as configured at solver/default_solver.py:96-114).
  * g' = g*grad_scale + wd*w ; v = momentum*v + g' ; w -= lr*v   (all fp32, n elements)
  * ------------------------------------------------------------------------------------------------------- */
