@@ -100,33 +100,58 @@ class _DeformConvBase:
         return ops.conv_desc(g, g, self.in_channels, self.ld, 3, 3, 1, 1)
 
     # ---- forward / backward ------------------------------------------------------------------------------------------------------------------
+    def params(self):
+        """The fp32 device masters by name (OIHW).  After changing them in place, repack() rebuilds the bf16 operands."""
+        return self._params
+
+    def repack(self):
+        self._pack()
+
     def __call__(self, x):
         N, C, H, W = x.shape
         if C != self.in_channels:
             raise ValueError(f"input has {C} channels, the layer {self.in_channels}")
-        M = N * H * W
-        xp = x.to(self.device).permute(0, 2, 3, 1).reshape(M, C).to(torch.bfloat16).contiguous()
+        xp = x.to(self.device).permute(0, 2, 3, 1).reshape(N * H * W, C).to(torch.bfloat16).contiguous()
+        y = self.forward_pm(xp, N, H, W)
+        return y.float().view(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
+
+    forward = __call__
+
+    def forward_pm(self, xp, N, H, W):
+        """The pixel-major path: xp bf16 [N H W][Cin] on the device -> y bf16 [N H W][Cout]; no NCHW / fp32 round trip."""
+        M, C = N * H * W, self.in_channels
+        if tuple(xp.shape) != (M, C) or xp.dtype != torch.bfloat16:
+            raise ValueError(f"forward_pm: expected bf16 {(M, C)}, got {xp.dtype} {tuple(xp.shape)}")
         om = torch.empty((M, self.ld), dtype=torch.bfloat16, device=self.device)
         ops.conv2d_fwd(self._offset_desc(N, H, W), xp, self._off_wf, self._off_bias, om)
         y = torch.empty((M, self.out_channels), dtype=torch.bfloat16, device=self.device)
         ops.deform_conv_fwd(xp, om, self._dcn_wf, self._dcn_bias, y, N, H, W, C, self.out_channels, self.MODULATED)
         self._saved = (xp, om, N, H, W)
         self.last_offset_mask = om
-        return y.float().view(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
-
-    forward = __call__
+        return y
 
     def backward(self, dy, accumulate=False):
         """Gradient of the last forward's output (NCHW) -> gradient of its input (NCHW fp32); parameter gradients in grads().
         accumulate: add to the parameter gradients of the previous backward instead of overwriting them."""
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
+        _, _, N, H, W = self._saved
+        Cin, Cout, dev = self.in_channels, self.out_channels, self.device
+        if tuple(dy.shape) != (N, Cout, H, W):
+            raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output {(N, Cout, H, W)}")
+        g = dy.to(dev).permute(0, 2, 3, 1).reshape(N * H * W, Cout).to(torch.bfloat16).contiguous()
+        dx = self.backward_pm(g, accumulate)
+        return dx.float().view(N, H, W, Cin).permute(0, 3, 1, 2).contiguous()
+
+    def backward_pm(self, g, accumulate=False):
+        """g bf16 [N H W][Cout] -> d_x bf16 [N H W][Cin]; parameter gradients in grads()."""
+        if self._saved is None:
+            raise RuntimeError("backward() before a forward")
         xp, om, N, H, W = self._saved
         Cin, Cout, ld, dev = self.in_channels, self.out_channels, self.ld, self.device
         M = N * H * W
-        if tuple(dy.shape) != (N, Cout, H, W):
-            raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output {(N, Cout, H, W)}")
-        g = dy.to(dev).permute(0, 2, 3, 1).reshape(M, Cout).to(torch.bfloat16).contiguous()
+        if tuple(g.shape) != (M, Cout) or g.dtype != torch.bfloat16:
+            raise ValueError(f"backward_pm: expected bf16 {(M, Cout)}, got {g.dtype} {tuple(g.shape)}")
         if self._grads is None or not accumulate:
             accumulate = False
             self._grads = dict(off_w=torch.empty((ld, 3, 3, Cin), dtype=torch.float32, device=dev),
@@ -147,7 +172,7 @@ class _DeformConvBase:
         dx = torch.empty_like(dx_dcn)
         ops.conv2d_dgrad(d, d_om, self._off_wd, dx, add=dx_dcn, flags=ops.EPI_ADD_BEFORE)
         self.last_d_offset_mask = d_om
-        return dx.float().view(N, H, W, Cin).permute(0, 3, 1, 2).contiguous()
+        return dx
 
     def grads(self):
         """Parameter gradients of the last backward() under the reference's names, OIHW fp32."""

@@ -1,6 +1,7 @@
 """CenterNet after the network's last convolution, on the kernels of csrc/centernet.hip -- the reference's names and signatures
 (models/det/centernet.py): ground truth (`centernet_ground_truth`, CenterNetGT), `modified_focal_loss`, `reg_l1_loss`, `gather_feature`
-and `CenterNetDecoder`.  The trunk, the deconvolution neck, CenterHead and the CenterNet class itself are not here yet.
+and `CenterNetDecoder`.  The deconvolution neck and CenterHead are layers (basedet_amd/layers/center_head.py); the
+res5-only trunk and the CenterNet class itself are the next step.
 
 Tensors are the reference's: NCHW fp32 on the HIP device (host tensors raise: there is no CPU path).  The kernels read the head's
 convolution output -- pixel-major bf16 LOGITS -- so the functions that take probabilities, as the reference's do, turn them back into

@@ -1145,3 +1145,26 @@ def centernet_decode(logits, ld, wh, wh_ld, wh_off, reg, reg_ld, reg_off, B, K, 
     check(L().bd_centernet_decode(ptr(logits), ld, ptr(wh), wh_ld, wh_off, ptr(reg), reg_ld, reg_off, B, K, H, W, k, ptr(boxes),
                                   ptr(scores), ptr(classes), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
           "bd_centernet_decode")
+
+
+# ---- CenterHead's output convolutions (center_head.hip) -----------------------------------------------------------------------------------
+def center_head_out_fwd(feat, w_cls, b_cls, w_wh, b_wh, w_reg, b_reg, M, C, K, logits, wr):
+    """feat bf16 [M][3C] (cls | wh | reg tower) -> logits bf16 [M][round_up(K, 8)] and wr bf16 [M][8] (wh at 0-1, reg at 2-3); weights the
+    fp32 masters [K][C] / [2][C] / [2][C], biases fp32 or None (include/basedet_hip.h, bd_center_head_out_fwd)."""
+    check(L().bd_center_head_out_fwd(ptr(feat), ptr(w_cls), ptr(b_cls), ptr(w_wh), ptr(b_wh), ptr(w_reg), ptr(b_reg), int(M), C, K,
+                                     logits.shape[-1], ptr(logits), ptr(wr), stream_ptr()), "bd_center_head_out_fwd")
+    return logits, wr
+
+
+def center_head_out_bwd_workspace_bytes(M, C, K):
+    return int(L().bd_center_head_out_bwd_workspace_bytes(int(M), C, K))
+
+
+def center_head_out_bwd(feat, d_logits, d_wr, w_cls, w_wh, w_reg, M, C, K, d_feat, dw_cls, db_cls, dw_wh, db_wh, dw_reg, db_reg, ws,
+                        accumulate=False):
+    """d_feat bf16 [M][3C] (gated by feat > 0) and the fp32 parameter gradients (+)= in the masters' layout, in one pass (reproducible)."""
+    check(L().bd_center_head_out_bwd(ptr(feat), ptr(d_logits), ptr(d_wr), ptr(w_cls), ptr(w_wh), ptr(w_reg), int(M), C, K,
+                                     d_logits.shape[-1], ptr(d_feat), ptr(dw_cls), ptr(db_cls), ptr(dw_wh), ptr(db_wh), ptr(dw_reg),
+                                     ptr(db_reg), int(accumulate), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+          "bd_center_head_out_bwd")
+    return d_feat

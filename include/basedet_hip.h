@@ -915,6 +915,31 @@ int bd_centernet_decode(const void* logits, int ld, const void* wh, int wh_ld, i
                         int B, int K, int H, int W, int k, float* boxes, float* scores, int32_t* classes, void* ws, size_t ws_bytes,
                         bd_stream_t stream);
 
+/* The output convolutions of CenterHead (bd_version() >= 116; center_head.hip; layers/head/center_head.py:91-131: the three
+ * SingleHead.out_conv, 1x1, C -> K / 2 / 2) in one launch per direction.  feat: bf16 [M][3C], the ReLU output of the three feat_convs
+ * run as one 3C-row convolution -- channels [0,C) the cls tower, [C,2C) the wh tower, [2C,3C) the reg tower.  w_cls [K][C], w_wh [2][C],
+ * w_reg [2][C]: the fp32 masters, rounded to bf16 in the kernel (as bd_weight_pack does); biases fp32, each may be NULL.  fp32
+ * accumulation.
+ *   logits bf16 [M][cls_ld], cls_ld = round_up(K, 8): logits[p][o] = b_cls[o] + sum_c feat[p][c] w_cls[o][c]; slots >= K are written +0
+ *   wr     bf16 [M][8]: slots 0-1 = wh, 2-3 = reg (each from its own tower), 4-7 written +0 -- the layout bd_centernet_l1_fwd_bwd
+ *          (ld 8, off 0 / 2) and bd_centernet_decode (wh_ld = reg_ld = 8, offsets 0 / 2) read as it stands
+ * Backward, from d_logits [M][cls_ld] and d_wr [M][8] (their pad slots -- >= K, 4-7 -- are never read and may hold anything):
+ *   d_feat[p][c] = (feat[p][c] > 0) * sum_o g[p][o] w[o][c] per tower block, one rounding to bf16; exactly +0 where feat is 0
+ *   dw_* / db_* fp32 in the masters' layout, (+)= under accumulate != 0; the db pointers may be NULL
+ * Fixed summation order (per-workgroup partials in ws, added in workgroup order), no floating-point atomics: the same bits on every run.
+ * Supported: C a multiple of 16, C <= 128; K >= 1 with the weights / tiles inside the LDS and at most 128 16x16 gradient tiles
+ * ((ceil(K / 16) + 2) (C / 16 + 1)): K <= 368 at C = 64, K <= 192 at C = 128; every tensor < 2 GB; feat, logits, wr, d_logits, d_wr, d_feat
+ * and ws 16-byte aligned.  Anything else: BD_EINVAL with a message, before any launch.  ws: bd_center_head_out_bwd_workspace_bytes
+ * (0 for an unsupported shape). */
+int bd_center_head_out_fwd(const void* feat, const float* w_cls, const float* b_cls, const float* w_wh, const float* b_wh,
+                           const float* w_reg, const float* b_reg, int64_t M, int C, int K, int cls_ld, void* logits, void* wr,
+                           bd_stream_t stream);
+size_t bd_center_head_out_bwd_workspace_bytes(int64_t M, int C, int K);
+int bd_center_head_out_bwd(const void* feat, const void* d_logits, const void* d_wr, const float* w_cls, const float* w_wh,
+                           const float* w_reg, int64_t M, int C, int K, int cls_ld, void* d_feat, float* dw_cls, float* db_cls,
+                           float* dw_wh, float* db_wh, float* dw_reg, float* db_reg, int accumulate, void* ws, size_t ws_bytes,
+                           bd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Optimizer (megengine.optimizer.SGD as configured at solver/default_solver.py:96-114).
  * g' = g*grad_scale + wd*w ; v = momentum*v + g' ; w -= lr*v   (all fp32, n elements)
