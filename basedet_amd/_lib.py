@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 116              # bd_version() of the library this binding matches (116: the bd_center_head_out_* entries of center_head.hip; 115: the bd_centernet_* entries of centernet.hip; 114: the GroupNorm partials of bd_conv2d_fwd_gnstats / bd_groupnorm_fwd hold (mean, M2), not (sum, sum of squares); 113: the bd_deform_conv_* entries of deform_conv.hip;101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd; 111: bd_bn_apply_fwd removed, bd_bn_apply_act_fwd serves its callers; 112: one entry per operator -- the *_ld, _general, _batched and _joint twins and the giou forwarder folded into the base names, which take their arguments)
+ABI_VERSION = 117              # bd_version() of the library this binding matches (117: bd_centernet_boxes_to_image; 116: the bd_center_head_out_* entries of center_head.hip; 115: the bd_centernet_* entries of centernet.hip; 114: the GroupNorm partials of bd_conv2d_fwd_gnstats / bd_groupnorm_fwd hold (mean, M2), not (sum, sum of squares); 113: the bd_deform_conv_* entries of deform_conv.hip;101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd; 111: bd_bn_apply_fwd removed, bd_bn_apply_act_fwd serves its callers; 112: one entry per operator -- the *_ld, _general, _batched and _joint twins and the giou forwarder folded into the base names, which take their arguments)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -188,6 +188,7 @@ SIGNATURES = {
     "bd_centernet_decode_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "bd_centernet_decode": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     # (feat, w_cls, b_cls, w_wh, b_wh, w_reg, b_reg, M, C, K, cls_ld, logits, wr, stream)
+    "bd_centernet_boxes_to_image": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bd_center_head_out_fwd": (_I, [_P] * 7 + [_L, _I, _I, _I, _P, _P, _P]),
     "bd_center_head_out_bwd_workspace_bytes": (_Z, [_L, _I, _I]),
     # (feat, d_logits, d_wr, w_cls, w_wh, w_reg, M, C, K, cls_ld, d_feat, dw_cls, db_cls, dw_wh, db_wh, dw_reg, db_reg, accumulate, ws, ws_bytes, stream)

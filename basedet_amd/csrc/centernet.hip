@@ -462,6 +462,31 @@ __global__ __launch_bounds__(1024) void cn_topk_kernel(const float* __restrict__
     }
 }
 
+// ---- boxes to image coordinates ----------------------------------------------------------------------------------------------------------
+// CenterNet.post_process's transform_boxes (centernet.py:163-186, 293-311) for a whole batch: one thread per box, one 16-byte load and
+// store.  affine [B][6] = the image's 2 x 3 map (a b c / d e f) from output-map to image coordinates, solved on the host in float64 and
+// rounded once.  The order is fixed: x' = fma(a, x, fma(b, y, c)), y' = fma(d, x, fma(e, y, f)) -- two roundings in the chain (a third is the rounding of the
+// coefficients), written as explicit fmaf calls (the file is compiled with contraction off, so nothing else fuses).  scores and classes pass through into the
+// caller's dense per-image tensors in the same launch.
+__global__ __launch_bounds__(256) void cn_boxes_to_image_kernel(const float* __restrict__ boxes, const float* __restrict__ affine,
+                                                                const float* __restrict__ scores, const int* __restrict__ classes, int k,
+                                                                long long total, float* __restrict__ boxes_out,
+                                                                float* __restrict__ scores_out, int* __restrict__ labels_out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const float* m = affine + (i / k) * 6;
+    const float a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5];
+    const f32x4_t v = *reinterpret_cast<const f32x4_t*>(boxes + i * 4);
+    f32x4_t o;
+    o[0] = fmaf(a, v[0], fmaf(b, v[1], c));
+    o[1] = fmaf(d, v[0], fmaf(e, v[1], f));
+    o[2] = fmaf(a, v[2], fmaf(b, v[3], c));
+    o[3] = fmaf(d, v[2], fmaf(e, v[3], f));
+    *reinterpret_cast<f32x4_t*>(boxes_out + i * 4) = o;
+    scores_out[i] = scores[i];
+    labels_out[i] = classes[i];
+}
+
 }  // namespace
 
 // Scratch of the loss partials: one grow-only buffer per (device, stream), as losses.hip keeps for its launches.
@@ -576,5 +601,18 @@ extern "C" int bd_centernet_decode(const void* logits, int ld, const void* wh, i
     hipLaunchKernelGGL(cn_topk_kernel, dim3(B), dim3(1024), 0, st, (const float*)ws, K, H, W, k, (const bf16_raw*)wh, wh_ld, wh_off,
                        (const bf16_raw*)reg, reg_ld, reg_off, boxes, scores, classes);
     BD_CHECK_LAUNCH("bd_centernet_decode");
+    return BD_OK;
+}
+
+extern "C" int bd_centernet_boxes_to_image(const float* boxes, const float* affine, const float* scores, const int32_t* classes, int B, int k,
+                                           float* boxes_out, float* scores_out, int32_t* labels_out, bd_stream_t stream) {
+    BD_REQUIRE(B > 0 && k > 0, "centernet_boxes_to_image: B=%d and k=%d must be positive", B, k);
+    BD_REQUIRE(boxes && affine && scores && classes && boxes_out && scores_out && labels_out, "centernet_boxes_to_image: null pointer");
+    BD_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)boxes_out & 15) == 0, "centernet_boxes_to_image: boxes and boxes_out must be 16-byte aligned");
+    const long long total = (long long)B * k;
+    BD_REQUIRE(total < (1ll << 31) * 256, "centernet_boxes_to_image: B * k too large");
+    hipLaunchKernelGGL(cn_boxes_to_image_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, boxes, affine, scores,
+                       classes, k, total, boxes_out, scores_out, labels_out);
+    BD_CHECK_LAUNCH("bd_centernet_boxes_to_image");
     return BD_OK;
 }

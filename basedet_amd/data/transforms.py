@@ -8,7 +8,7 @@ values of the resize are cv2-style bilinear (half-pixel centres, edge clamp); pa
 unpinned (cv2 is not installed here).  Pure numpy, no device work: what leaves this module is the sample the collator pads."""
 import numpy as np
 
-__all__ = ["ShortestEdgeResize", "RandomHorizontalFlip", "ToMode", "Compose", "TestTimeCompose", "build_transform"]
+__all__ = ["ShortestEdgeResize", "RandomHorizontalFlip", "ToMode", "Compose", "TestTimeCompose", "TestTimeCenterPad", "build_transform"]
 
 
 def resize_bilinear(img, out_h, out_w):
@@ -127,6 +127,20 @@ class ToMode(_Transform):
         return np.ascontiguousarray(image.transpose(2, 0, 1)[None], dtype=np.float32)
 
 
+class TestTimeCenterPad(_Transform):
+    """CenterNet's test-time padding (`data/transforms/centernet_transform.py:101-114`): the HWC image centred in a float64 canvas of zeros
+    of ((h | 31) + 1, (w | 31) + 1) -- the next multiple of 32 ABOVE the size, so a size already a multiple of 32 grows by 32 too."""
+    __test__ = False          # not a pytest class
+
+    def _apply_image(self, image):
+        h, w, c = image.shape
+        th, tw = (h | 31) + 1, (w | 31) + 1
+        pw, ph = -((w - tw) // 2), -((h - th) // 2)          # ceil((target - size) / 2)
+        out = np.zeros((th, tw, c))
+        out[ph:h + ph, pw:w + pw, ...] = image
+        return out
+
+
 class Compose:
     def __init__(self, transforms, order=("image", "boxes", "boxes_category")):
         self.transforms, self.order = list(transforms), tuple(order)
@@ -159,7 +173,10 @@ class TestTimeCompose(Compose):
 
 
 _BY_NAME = {"MGE_ShortestEdgeResize": ShortestEdgeResize, "MGE_RandomHorizontalFlip": RandomHorizontalFlip, "MGE_ToMode": ToMode,
-            "ShortestEdgeResize": ShortestEdgeResize, "RandomHorizontalFlip": RandomHorizontalFlip, "ToMode": ToMode}
+            "ShortestEdgeResize": ShortestEdgeResize, "RandomHorizontalFlip": RandomHorizontalFlip, "ToMode": ToMode,
+            "TestTimeCenterPad": TestTimeCenterPad}
+# transforms of the reference's configs that this build does not have (CenterNetConfig.AUG.TRAIN_VALUE): refused by name
+_NOT_BUILT = ("CenterAffine", "MGE_BrightnessTransform", "MGE_ContrastTransform", "MGE_SaturationTransform", "MGE_Lighting")
 
 TRAIN_AUG = (("MGE_ShortestEdgeResize", dict(min_size=(640, 672, 704, 736, 768, 800), max_size=1333, sample_style="choice")),
              ("MGE_RandomHorizontalFlip", dict(prob=0.5)), ("MGE_ToMode", dict(mode="CHW")))
@@ -172,6 +189,9 @@ def build_transform(spec=None, mode="train", rng=None):
     spec = spec if spec is not None else (TRAIN_AUG if mode == "train" else TEST_AUG)
     ts = []
     for name, kw in spec:
+        if name not in _BY_NAME:
+            what = "is not built (CenterNet's affine crop and colour augmentations are out of scope)" if name in _NOT_BUILT else "is unknown"
+            raise ValueError(f"build_transform: the transform {name!r} {what}; built: {sorted(_BY_NAME)}")
         cls = _BY_NAME[name]
         kw = dict(kw)
         if cls in (ShortestEdgeResize, RandomHorizontalFlip):

@@ -83,6 +83,24 @@ class _BatchNorm:
         self.mean, self.inv_std, self.sums = torch.empty(C, **f), torch.empty(C, **f), torch.empty((3, C), **f)
         self.g = None
         self._saved = None
+        self._ext = False
+        self._eval_inv_std = None
+
+    def adopt(self, state):
+        """Live on a model's norm record (models/live_norm.py BatchNormState): gamma / beta and their gradients are its arena views, the
+        running statistics and the batch statistics its buffers -- where the optimizer, the EMA's buffer average and the parameter
+        broadcast find them.  The current values move in."""
+        old = self.p
+        self.p = {"weight": state.gamma, "bias": state.beta, "running_mean": state.running_mean, "running_var": state.running_var}
+        for k, v in old.items():
+            self.p[k].copy_(v)
+        self.mean, self.inv_std, self.sums = state.mean, state.inv_std, state.sums
+        self.g = {"weight": state.g_gamma, "bias": state.g_beta}
+        self._ext = True
+
+    def refresh_eval(self):
+        """1 / sqrt(running_var + eps) for the eval() forward, computed once (at eval() / after a load) instead of per call."""
+        self._eval_inv_std = 1.0 / torch.sqrt(self.p["running_var"] + BN_EPS)
 
     SHAPES = ("weight", "bias", "running_mean", "running_var")
 
@@ -94,7 +112,8 @@ class _BatchNorm:
                              self.p["running_var"], ws)
             mean, inv_std = self.mean, self.inv_std
         else:
-            mean, inv_std = self.p["running_mean"], 1.0 / torch.sqrt(self.p["running_var"] + BN_EPS)
+            mean = self.p["running_mean"]
+            inv_std = self._eval_inv_std if self._eval_inv_std is not None else 1.0 / torch.sqrt(self.p["running_var"] + BN_EPS)
         z = torch.empty_like(y)
         ops.bn_apply_act_fwd(y, geom, mean, inv_std, self.p["weight"], self.p["bias"], z, geom, self.C, relu=True)
         self._saved = (y, z, geom, self.training)
@@ -106,12 +125,19 @@ class _BatchNorm:
             raise RuntimeError("backward() through a norm in eval() mode is not built")
         gm = ops.relu_bwd_bf16(g, z, torch.empty_like(g))
         f = dict(dtype=F32, device=self.device)
-        dgamma, dbeta = torch.empty(self.C, **f), torch.empty(self.C, **f)
+        if self._ext:          # adopted: the reduce writes the arena's gradient views
+            if accumulate:
+                raise RuntimeError("accumulate=True is not built for a norm on adopted storage")
+            dgamma, dbeta = self.g["weight"], self.g["bias"]
+        else:
+            dgamma, dbeta = torch.empty(self.C, **f), torch.empty(self.C, **f)
         ws = torch.empty(ops.bn_workspace_bytes(y.shape[0], self.C), dtype=torch.uint8, device=self.device)
         ops.bn_bwd_reduce(gm, geom, y, geom, self.mean, self.inv_std, self.C, dgamma, dbeta, ws)
         gy = ops.bn_bwd_apply(gm, geom, y, geom, self.mean, self.inv_std, self.p["weight"], dgamma, dbeta, self.sums[0], torch.empty_like(g),
                               geom, self.C)
-        if accumulate and self.g is not None:
+        if self._ext:
+            pass
+        elif accumulate and self.g is not None:
             self.g = {"weight": self.g["weight"] + dgamma, "bias": self.g["bias"] + dbeta}
         else:
             self.g = {"weight": dgamma, "bias": dbeta}
@@ -185,8 +211,39 @@ class DeconvLayer:
         self._up_w = torch.from_numpy(up_sample_init(C, np.random.default_rng(seed + 1))).to(self.device)        # (in, out, 4, 4)
         self._g_up = None
         self._saved = None
+        self._ext = None
         self.training = True
         self.repack()
+
+    def arena_shapes(self):
+        """name -> shape of the fp32 masters in the kernels' layouts (deformable.py arena_shapes; up_sample.weight as the OHWI conv view
+        (C, 4, 4, C) that bd_fpn_deconv_pack reads and bd_fpn_deconv_wgrad writes).  The norms' vectors are not listed: adopt() takes a
+        norm record for each."""
+        C = self.out_planes
+        out = {"dcn." + k: v for k, v in self.dcn.arena_shapes().items()}
+        out["up_sample.weight"] = (C, 4, 4, C)
+        return out
+
+    def adopt(self, w, g, dcn_bn, up_bn):
+        """Live on the caller's storage (a model's parameter arena): w / g = {name: fp32 view} in arena_shapes()' layouts, dcn_bn / up_bn
+        the model's norm records.  Standalone use is unchanged; see deformable.py adopt."""
+        C = self.out_planes
+        if tuple(w["up_sample.weight"].shape) != (C, 4, 4, C) or tuple(g["up_sample.weight"].shape) != (C, 4, 4, C):
+            raise ValueError(f"adopt: 'up_sample.weight' needs fp32 views of shape {(C, 4, 4, C)}")
+        self.dcn.adopt({k[4:]: v for k, v in w.items() if k.startswith("dcn.")}, {k[4:]: v for k, v in g.items() if k.startswith("dcn.")})
+        self.dcn_bn.adopt(dcn_bn)
+        self.up_bn.adopt(up_bn)
+        w["up_sample.weight"].copy_(self._up_w.permute(0, 2, 3, 1))
+        self._ext = w["up_sample.weight"]
+        self._up_w = self._ext.permute(0, 3, 1, 2)          # the (in, out, 4, 4) view params() / state_dict() hand out
+        self._g_up = g["up_sample.weight"]
+        self._up_wf = torch.empty(16 * C * C, dtype=BF16, device=self.device)
+        self._up_wd = torch.empty(16 * C * C, dtype=BF16, device=self.device)
+        self.repack()
+
+    def refresh_eval(self):
+        self.dcn_bn.refresh_eval()
+        self.up_bn.refresh_eval()
 
     # ---- parameters ------------------------------------------------------------------------------------------------------------------------
     def _shapes(self):
@@ -205,6 +262,9 @@ class DeconvLayer:
     def repack(self):
         C = self.out_planes
         self.dcn.repack()
+        if self._ext is not None:          # the master is the conv view already; the operands keep their place
+            ops.fpn_deconv_pack(self._ext, C, self._up_wf, self._up_wd)
+            return
         self._up_wf = torch.empty(16 * C * C, dtype=BF16, device=self.device)
         self._up_wd = torch.empty(16 * C * C, dtype=BF16, device=self.device)
         ops.fpn_deconv_pack(self._up_w.permute(0, 2, 3, 1).contiguous(), C, self._up_wf, self._up_wd)
@@ -221,8 +281,17 @@ class DeconvLayer:
         p = _load(state, self._shapes(), self.device)
         self.dcn.load_state_dict({k[4:]: v for k, v in p.items() if k.startswith("dcn.")})
         for name, bn in (("dcn_bn", self.dcn_bn), ("up_bn", self.up_bn)):
-            bn.p = {k: p[f"{name}.{k}"] for k in _BatchNorm.SHAPES}
-        self._up_w = p["up_sample.weight"]
+            if self._ext is not None:
+                for k in _BatchNorm.SHAPES:
+                    bn.p[k].copy_(p[f"{name}.{k}"])
+                if bn._eval_inv_std is not None:
+                    bn.refresh_eval()
+            else:
+                bn.p = {k: p[f"{name}.{k}"] for k in _BatchNorm.SHAPES}
+        if self._ext is not None:
+            self._up_w.copy_(p["up_sample.weight"])
+        else:
+            self._up_w = p["up_sample.weight"]
         self.repack()
 
     def train(self, mode=True):
@@ -253,7 +322,9 @@ class DeconvLayer:
         z0, N, H, W = self._saved
         C = self.out_planes
         g_y1 = self.up_bn.backward_pm(g, accumulate)
-        if self._g_up is None or not accumulate:
+        if self._ext is not None:
+            pass                           # (the adopted gradient view)
+        elif self._g_up is None or not accumulate:
             accumulate = False
             self._g_up = torch.empty((C, 4, 4, C), dtype=F32, device=self.device)
         ws = torch.empty(ops.fpn_deconv_wgrad_workspace_bytes(N, H, W, C), dtype=torch.uint8, device=self.device)
@@ -337,6 +408,19 @@ class CenternetDeconv:
         for _, l in self.layers():
             l.repack()
 
+    def arena_shapes(self):
+        return self._merge(lambda l: l.arena_shapes())
+
+    def adopt(self, w, g, norms):
+        """norms: {"deconvI.dcn_bn" / "deconvI.up_bn": norm record}.  See DeconvLayer.adopt."""
+        for n, l in self.layers():
+            cut = lambda d: {k[len(n) + 1:]: v for k, v in d.items() if k.startswith(n + ".")}
+            l.adopt(cut(w), cut(g), norms[n + ".dcn_bn"], norms[n + ".up_bn"])
+
+    def refresh_eval(self):
+        for _, l in self.layers():
+            l.refresh_eval()
+
     def train(self, mode=True):
         for _, l in self.layers():
             l.train(mode)
@@ -398,16 +482,30 @@ class SingleHead:
         return {k: tuple(v.shape) for k, v in self.state.items()}
 
 
+def validate_head(in_channels, num_classes):
+    """What bd_center_head_out_* builds; ValueError before the device is touched."""
+    C, K = in_channels, num_classes
+    if not (isinstance(C, int) and C > 0 and C % 16 == 0 and C <= 128):
+        raise ValueError(f"CenterHead: in_channels={C!r} must be a multiple of 16 up to 128 (bd_center_head_out_*)")
+    if not (isinstance(K, int) and K >= 1 and (-(-K // 16) + 2) * (C // 16 + 1) <= 128):
+        raise ValueError(f"CenterHead: num_classes={K!r} is outside what bd_center_head_out_* builds at in_channels={C}")
+
+
+def validate_neck(channels, deconv_kernel_sizes):
+    """CenternetDeconv's argument checks; ValueError before the device is touched."""
+    if len(channels) != len(deconv_kernel_sizes) + 1:
+        raise ValueError(f"CenternetDeconv: {len(channels)} channel counts for {len(deconv_kernel_sizes)} layers")
+    for i in range(len(deconv_kernel_sizes)):
+        _validate_deconv(channels[i], channels[i + 1], deconv_kernel_sizes[i], 2, 1, 0)
+
+
 class CenterHead:
     """center_head.py:106-131."""
     BRANCHES = ("cls", "wh", "reg")
 
     def __init__(self, in_channels=64, num_classes=80, prior_prob=0.1, seed=0, device="cuda"):
         C, K = in_channels, num_classes
-        if not (isinstance(C, int) and C > 0 and C % 16 == 0 and C <= 128):
-            raise ValueError(f"CenterHead: in_channels={C!r} must be a multiple of 16 up to 128 (bd_center_head_out_*)")
-        if not (isinstance(K, int) and K >= 1 and (-(-K // 16) + 2) * (C // 16 + 1) <= 128):
-            raise ValueError(f"CenterHead: num_classes={K!r} is outside what bd_center_head_out_* builds at in_channels={C}")
+        validate_head(C, K)
         self.in_channels, self.num_classes, self.prior_prob, self.device = C, K, prior_prob, torch.device(device)
         self.cls_ld = (K + 7) // 8 * 8
         self.cls_head, self.wh_head, self.reg_head = SingleHead(C, K, seed), SingleHead(C, 2, seed + 1), SingleHead(C, 2, seed + 2)
@@ -415,8 +513,43 @@ class CenterHead:
         state = {f"{b}_head.{k}": v for b in self.BRANCHES for k, v in getattr(self, b + "_head").state.items()}
         self._g = None
         self._saved = None
+        self._ext = None
         self.training = True
         self.load_state_dict(state)
+
+    def arena_shapes(self):
+        """name -> shape of the fp32 masters in the kernels' layouts: the three feat_convs as ONE OHWI (3C, 3, 3, C) weight and (3C,) bias
+        (cls | wh | reg, what repack() concatenated per step before), the output convolutions as they are."""
+        C, K = self.in_channels, self.num_classes
+        out = {"feat_conv.weight": (3 * C, 3, 3, C), "feat_conv.bias": (3 * C,)}
+        for b, n in (("cls", K), ("wh", 2), ("reg", 2)):
+            out[f"{b}_head.out_conv.weight"] = (n, C, 1, 1)
+            out[f"{b}_head.out_conv.bias"] = (n,)
+        return out
+
+    def adopt(self, w, g):
+        """Live on the caller's storage (a model's parameter arena); see deformable.py adopt.  params() / state_dict() / grads() keep the
+        reference's per-branch names as views."""
+        C, old = self.in_channels, self._params
+        for name, shape in self.arena_shapes().items():
+            if tuple(w[name].shape) != shape or tuple(g[name].shape) != shape:
+                raise ValueError(f"adopt: {name!r} needs fp32 views of shape {shape}")
+        p = {}
+        for i, b in enumerate(self.BRANCHES):
+            p[f"{b}_head.feat_conv.weight"] = w["feat_conv.weight"][i * C:(i + 1) * C].permute(0, 3, 1, 2)
+            p[f"{b}_head.feat_conv.bias"] = w["feat_conv.bias"][i * C:(i + 1) * C]
+            p[f"{b}_head.out_conv.weight"] = w[f"{b}_head.out_conv.weight"]
+            p[f"{b}_head.out_conv.bias"] = w[f"{b}_head.out_conv.bias"]
+        for k, v in p.items():
+            v.copy_(old[k])
+        self._params = {k: p[k] for k in old}          # (the reference's order)
+        self._ext = w
+        self._g = dict(feat_w=g["feat_conv.weight"], feat_b=g["feat_conv.bias"], cls_w=g["cls_head.out_conv.weight"],
+                       cls_b=g["cls_head.out_conv.bias"], wh_w=g["wh_head.out_conv.weight"], wh_b=g["wh_head.out_conv.bias"],
+                       reg_w=g["reg_head.out_conv.weight"], reg_b=g["reg_head.out_conv.bias"])
+        self._feat_wf = torch.empty((3 * C, 9, C), dtype=BF16, device=self.device)
+        self._feat_wd = torch.empty((C, 9, 3 * C), dtype=BF16, device=self.device)
+        self.repack()
 
     # ---- parameters ------------------------------------------------------------------------------------------------------------------------
     def _shapes(self):
@@ -432,12 +565,21 @@ class CenterHead:
         return {k: v.detach().cpu().clone() for k, v in self._params.items()}
 
     def load_state_dict(self, state):
-        self._params = _load(state, self._shapes(), self.device)
+        p = _load(state, self._shapes(), self.device)
+        if self._ext is not None:
+            for k, v in p.items():
+                self._params[k].copy_(v)
+        else:
+            self._params = p
         self.repack()
 
     def repack(self):
         """The three feat_convs as one 3C-row convolution (cls | wh | reg); the output convolutions are read as fp32 masters by the kernel."""
         C, p, dev = self.in_channels, self._params, self.device
+        if self._ext is not None:          # one fused master in the kernel's layout: no concatenation, the operands keep their place
+            self._feat_bias = self._ext["feat_conv.bias"]
+            ops.weight_pack(self._ext["feat_conv.weight"], None, self._feat_wf, self._feat_wd, 3 * C, 9, C)
+            return
         w = torch.cat([p[f"{b}_head.feat_conv.weight"] for b in self.BRANCHES], 0).permute(0, 2, 3, 1).contiguous()
         self._feat_bias = torch.cat([p[f"{b}_head.feat_conv.bias"] for b in self.BRANCHES], 0).contiguous()
         self._feat_wf = torch.empty((3 * C, 9, C), dtype=BF16, device=dev)
@@ -478,7 +620,9 @@ class CenterHead:
             raise RuntimeError("backward() before a forward")
         x, feat, N, H, W = self._saved
         C, K, M, dev, p = self.in_channels, self.num_classes, N * H * W, self.device, self._params
-        if self._g is None or not accumulate:
+        if self._ext is not None:
+            pass                           # (the adopted gradient views)
+        elif self._g is None or not accumulate:
             accumulate = False
             f = lambda *s: torch.empty(s, dtype=F32, device=dev)
             self._g = dict(feat_w=f(3 * C, 3, 3, C), feat_b=f(3 * C), cls_w=f(K, C, 1, 1), cls_b=f(K), wh_w=f(2, C, 1, 1), wh_b=f(2),

@@ -54,6 +54,7 @@ class _DeformConvBase:
             state[name + ".bias"] = torch.zeros(co, dtype=torch.float32)
         self._grads = None
         self._saved = None
+        self._ext = None               # adopt(): (masters, gradients) on the caller's storage, in the kernels' layouts
         self.last_offset_mask = None
         self.load_state_dict(state)
 
@@ -63,6 +64,35 @@ class _DeformConvBase:
 
     def state_dict(self):
         return {k: v.detach().cpu().clone() for k, v in self._params.items()}
+
+    def arena_shapes(self):
+        """name -> shape of the fp32 masters in the kernels' own layouts (OHWI, the offset convolution's rows padded to ld): what a caller
+        that provides the storage (adopt) reserves, for the masters and for the gradients alike."""
+        ld, Cin = self.ld, self.in_channels
+        return {self.OFFSET_NAME + ".weight": (ld, 3, 3, Cin), self.OFFSET_NAME + ".bias": (ld,),
+                self.DCN_NAME + ".weight": (self.out_channels, 3, 3, Cin), self.DCN_NAME + ".bias": (self.out_channels,)}
+
+    def adopt(self, w, g):
+        """Live on storage the caller provides (a model's parameter arena): w / g = {name: fp32 device view} in arena_shapes()' layouts.
+        The current values move into w; from here on the masters ARE those views (an optimizer step over the arena, then repack()),
+        backward writes every parameter gradient straight into g, and params() / state_dict() / grads() keep the reference's OIHW
+        layouts as views.  The pad rows of the offset convolution are zero and stay zero (their gradients are sums of zeros)."""
+        k = self.off_channels
+        old = self._params
+        for name, shape in self.arena_shapes().items():
+            if tuple(w[name].shape) != shape or tuple(g[name].shape) != shape:
+                raise ValueError(f"adopt: {name!r} needs fp32 views of shape {shape}")
+            w[name].zero_()
+        on, dn = self.OFFSET_NAME, self.DCN_NAME
+        w[on + ".weight"][:k].copy_(old[on + ".weight"].permute(0, 2, 3, 1))
+        w[on + ".bias"][:k].copy_(old[on + ".bias"])
+        w[dn + ".weight"].copy_(old[dn + ".weight"].permute(0, 2, 3, 1))
+        w[dn + ".bias"].copy_(old[dn + ".bias"])
+        self._ext = (w, g)
+        self._params = {on + ".weight": w[on + ".weight"][:k].permute(0, 3, 1, 2), on + ".bias": w[on + ".bias"][:k],
+                        dn + ".weight": w[dn + ".weight"].permute(0, 3, 1, 2), dn + ".bias": w[dn + ".bias"]}
+        self._grads = dict(off_w=g[on + ".weight"], off_b=g[on + ".bias"], dcn_w=g[dn + ".weight"], dcn_b=g[dn + ".bias"])
+        self._pack()
 
     def load_state_dict(self, state):
         want = {self.OFFSET_NAME + ".weight": (self.off_channels, self.in_channels, 3, 3), self.OFFSET_NAME + ".bias": (self.off_channels,),
@@ -75,13 +105,29 @@ class _DeformConvBase:
             if tuple(v.shape) != shape:
                 raise ValueError(f"parameter {k!r}: shape {tuple(v.shape)}, expected {shape}")
             params[k] = v.to(self.device).contiguous()
-        self._params = params
+        if self._ext is not None:          # the masters stay where they are: the values move in
+            for k, v in params.items():
+                self._params[k].copy_(v)
+        else:
+            self._params = params
         self._pack()
 
     def _pack(self):
         """fp32 masters (OIHW) -> the bf16 operands of the kernels; the offset conv's rows padded with zero rows to ld."""
         dev, Cin, ld = self.device, self.in_channels, self.ld
         p = self._params
+        if self._ext is not None:          # the masters already have the kernels' layouts: no copies, the packed operands keep their place
+            w = self._ext[0]
+            self._off_bias, self._dcn_bias = w[self.OFFSET_NAME + ".bias"], w[self.DCN_NAME + ".bias"]
+            if getattr(self, "_ext_packed", False) is False:
+                self._off_wf = torch.empty((ld, 9, Cin), dtype=torch.bfloat16, device=dev)
+                self._off_wd = torch.empty((Cin, 9, ld), dtype=torch.bfloat16, device=dev)
+                self._dcn_wf = torch.empty((self.out_channels, 9, Cin), dtype=torch.bfloat16, device=dev)
+                self._dcn_wd = torch.empty((Cin, 9, self.out_channels), dtype=torch.bfloat16, device=dev)
+                self._ext_packed = True
+            ops.weight_pack(w[self.OFFSET_NAME + ".weight"], None, self._off_wf, self._off_wd, ld, 9, Cin)
+            ops.weight_pack(w[self.DCN_NAME + ".weight"], None, self._dcn_wf, self._dcn_wd, self.out_channels, 9, Cin)
+            return
         w_off = torch.zeros((ld, 3, 3, Cin), dtype=torch.float32, device=dev)
         w_off[: self.off_channels] = p[self.OFFSET_NAME + ".weight"].permute(0, 2, 3, 1)
         self._off_bias = torch.zeros(ld, dtype=torch.float32, device=dev)
@@ -152,7 +198,9 @@ class _DeformConvBase:
         M = N * H * W
         if tuple(g.shape) != (M, Cout) or g.dtype != torch.bfloat16:
             raise ValueError(f"backward_pm: expected bf16 {(M, Cout)}, got {g.dtype} {tuple(g.shape)}")
-        if self._grads is None or not accumulate:
+        if self._ext is not None:
+            pass                           # (the gradients are the adopted views: nothing is allocated per step)
+        elif self._grads is None or not accumulate:
             accumulate = False
             self._grads = dict(off_w=torch.empty((ld, 3, 3, Cin), dtype=torch.float32, device=dev),
                                off_b=torch.empty(ld, dtype=torch.float32, device=dev),

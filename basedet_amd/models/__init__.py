@@ -3,4 +3,4 @@ from .free_anchor import FreeAnchor  # noqa: F401
 from .fcos import ATSS, FCOS, OTA  # noqa: F401
 from .faster_rcnn import FasterRCNN  # noqa: F401
 from . import centernet  # noqa: F401
-from .centernet import CenterNetDecoder, CenterNetGT  # noqa: F401
+from .centernet import CenterNet, CenterNetDecoder, CenterNetGT  # noqa: F401

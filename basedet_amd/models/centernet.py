@@ -1,7 +1,17 @@
 """CenterNet after the network's last convolution, on the kernels of csrc/centernet.hip -- the reference's names and signatures
 (models/det/centernet.py): ground truth (`centernet_ground_truth`, CenterNetGT), `modified_focal_loss`, `reg_l1_loss`, `gather_feature`
-and `CenterNetDecoder`.  The deconvolution neck and CenterHead are layers (basedet_amd/layers/center_head.py); the
-res5-only trunk and the CenterNet class itself are the next step.
+and `CenterNetDecoder`, and the detector itself: `CenterNet` = the ResNet trunk ending at res5 (FPNDetector with HAS_FPN = False: the
+same stem, block loops, norms and plan, no pyramid) -> layers.CenternetDeconv -> layers.CenterHead, three losses and the decoder.
+
+The seams of the detector are pixel-major bf16 with no NCHW / fp32 round trip: res5's stored block output is what the neck's forward_pm
+reads, the neck's output what the head reads, the head's raw logits_pm / wr_pm what the loss and decode kernels read.  Backward: the
+neck's d_x through ops.relu_bwd_bf16 against res5's output is res5's g_out in the trunk's convention (dL/d(pre-activation), masked), then
+the trunk's own backward loop.  The neck's and head's fp32 masters, gradients and norm statistics live in the model's parameter arena
+and LiveNorms (the layers' adopt()), so the fused optimizer launch, ModelEMA, GradClip, GradBuckets, broadcast_parameters and checkpoints
+see them; their activations and workspaces stay layer-owned, and their weight gradients run on the main stream.
+Inference decodes the raw head outputs (K = 100, reg given) and maps the boxes to the image for the whole batch in one launch
+(bd_centernet_boxes_to_image) from six host-built floats per image.  Not built: fp8 weights, CenterAffine and the colour augmentations
+of AUG.TRAIN_VALUE.
 
 Tensors are the reference's: NCHW fp32 on the HIP device (host tensors raise: there is no CPU path).  The kernels read the head's
 convolution output -- pixel-major bf16 LOGITS -- so the functions that take probabilities, as the reference's do, turn them back into
@@ -18,8 +28,12 @@ import torch.nn.functional as TF
 
 from basedet_amd import ops
 from basedet_amd._lib import BasedetHipError
+from basedet_amd.utils.registry import registers
 
-__all__ = ["CenterNetGT", "CenterNetDecoder", "centernet_ground_truth", "gather_feature", "modified_focal_loss", "reg_l1_loss"]
+from . import params as P
+from .fpn_base import FPNDetector
+
+__all__ = ["CenterNet", "CenterNetGT", "CenterNetDecoder", "centernet_ground_truth", "gather_feature", "modified_focal_loss", "reg_l1_loss"]
 
 
 def _dev(*tensors):
@@ -164,11 +178,16 @@ class CenterNetDecoder:
         if isinstance(boxes, torch.Tensor):
             boxes = boxes.detach().cpu().numpy()
         boxes = np.asarray(boxes).reshape(-1, 4)
-        src, dst = CenterNetDecoder.generate_src_and_dst(center, size, output_size)
-        a = np.column_stack((np.float32(dst).astype(np.float64), np.ones(3)))
-        trans = np.linalg.solve(a, np.float32(src).astype(np.float64)).T            # (2, 3): trans @ (x, y, 1) of dst = src
+        trans = CenterNetDecoder.affine_matrix(center, size, output_size)
         pts = boxes.reshape(-1, 2).astype(np.float64)
         return (pts @ trans[:, :2].T + trans[:, 2]).reshape(-1, 4)
+
+    @staticmethod
+    def affine_matrix(center, size, output_size):
+        """The float64 (2, 3) map of transform_boxes: trans @ (x, y, 1) takes an output-map point to the source image."""
+        src, dst = CenterNetDecoder.generate_src_and_dst(center, size, output_size)
+        a = np.column_stack((np.float32(dst).astype(np.float64), np.ones(3)))
+        return np.linalg.solve(a, np.float32(src).astype(np.float64)).T
 
     @staticmethod
     def pseudo_nms(fmap, pool_size=3):
@@ -265,3 +284,293 @@ class CenterNetGT:
             win = g[y0 - cy + radius:y1 - cy + radius, x0 - cx + radius:x1 - cx + radius]
             fmap[y0:y1, x0:x1] = np.maximum(fmap[y0:y1, x0:x1], win * k)
         return fmap
+
+
+@registers.models.register()
+class CenterNet(FPNDetector):
+    """models/det/centernet.py:17-186 (module docstring: the seams, the arena, what stays layer-owned)."""
+
+    HAS_FPN = False
+    TOP_BLOCK = None
+    BOTTOM_UP = "backbone"            # CenterNet holds the bare ResNet: backbone.conv1, backbone.layerL.B.* (no bottom_up, no fc)
+    TOPK = 100                        # CenterNetDecoder.decode's default K
+
+    @staticmethod
+    def init_params(cfg, seed=0):
+        """The backbone's parameters (models/cls/resnet.py's initialisers); the neck and head initialise themselves (layers/center_head.py)."""
+        p = {}
+        P.init_resnet(p, np.random.default_rng(seed), cfg.MODEL.BACKBONE.NAME, prefix="backbone")
+        return p
+
+    @classmethod
+    def check_config(cls, cfg):
+        from ..layers.center_head import validate_head, validate_neck
+        m = cfg.MODEL
+        if m.get("WEIGHT_DTYPE", "bf16") != "bf16":
+            raise ValueError(f"MODEL.WEIGHT_DTYPE = {m.WEIGHT_DTYPE!r} is not supported by CenterNet: the fp8 paths of the neck and head are not built; use 'bf16'")
+        if m.BACKBONE.NAME not in P.RESNET_SPECS:
+            raise ValueError(f"MODEL.BACKBONE.NAME = {m.BACKBONE.NAME!r} is not supported: one of {sorted(P.RESNET_SPECS)}")
+        super().check_config(cfg)
+        h = m.HEAD
+        ch, kern = list(h.DECONV_CHANNEL), list(h.DECONV_KERNEL)
+        c5 = 512 * (4 if P.RESNET_SPECS[m.BACKBONE.NAME][0] == "bottleneck" else 1)
+        if not ch or ch[0] != c5:
+            raise ValueError(f"MODEL.HEAD.DECONV_CHANNEL[0] = {ch[:1]!r} must equal res5's channel count of {m.BACKBONE.NAME}, {c5}")
+        if h.IN_CHANNELS != ch[-1]:
+            raise ValueError(f"MODEL.HEAD.IN_CHANNELS = {h.IN_CHANNELS!r} must equal MODEL.HEAD.DECONV_CHANNEL[-1] = {ch[-1]}")
+        if h.DOWN_SCALE != 32 / 2 ** len(kern):
+            raise ValueError(f"MODEL.HEAD.DOWN_SCALE = {h.DOWN_SCALE!r} must be 32 / 2 ** len(MODEL.HEAD.DECONV_KERNEL) = {32 / 2 ** len(kern):g}")
+        try:
+            validate_neck(ch, kern)
+        except ValueError as e:
+            raise ValueError(f"MODEL.HEAD.DECONV_CHANNEL / DECONV_KERNEL: {e}") from e
+        try:
+            validate_head(h.IN_CHANNELS, cfg.DATA.NUM_CLASSES)
+        except ValueError as e:
+            raise ValueError(f"MODEL.HEAD.IN_CHANNELS / DATA.NUM_CLASSES: {e}") from e
+        size = m.OUTPUT_SIZE
+        if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and v > 0 for v in size)):
+            raise ValueError(f"MODEL.OUTPUT_SIZE = {size!r} is not supported: (H, W), two positive integers")
+        if not (isinstance(h.TENSOR_DIM, int) and 1 <= h.TENSOR_DIM <= 1024):
+            raise ValueError(f"MODEL.HEAD.TENSOR_DIM = {h.TENSOR_DIM!r} is not supported: an integer from 1 to 1024 (bd_centernet_targets)")
+
+    @staticmethod
+    def param_shapes(cfg):
+        """{state_dict name: shape} of the detector a config describes, without touching the device: backbone.* (the bare ResNet, no fc),
+        upsample.deconvI.*, head.{cls,wh,reg}_head.*."""
+        from ..layers.center_head import head_param_shapes, neck_param_shapes
+        h = cfg.MODEL.HEAD
+        out = {k: tuple(v.shape) for k, v in CenterNet.init_params(cfg).items()}
+        out.update({"upsample." + k: tuple(v) for k, v in neck_param_shapes(list(h.DECONV_CHANNEL), bool(h.MODULATE_DEFORM)).items()})
+        out.update({"head." + k: tuple(v) for k, v in head_param_shapes(h.IN_CHANNELS, cfg.DATA.NUM_CLASSES).items()})
+        return out
+
+    @classmethod
+    def check_batch(cls, cfg, image_hw, gt_slots=None):
+        """What only a training batch can tell, from host shapes alone: MODEL.OUTPUT_SIZE (the targets' map) = the padded input size /
+        DOWN_SCALE, and the gt slots fit HEAD.TENSOR_DIM.  Inference reads neither key."""
+        m = cfg.MODEL
+        ds = m.HEAD.DOWN_SCALE
+        hp, wp = ((int(v) + 31) // 32 * 32 for v in image_hw)
+        want = (int(hp // ds), int(wp // ds))
+        if tuple(m.OUTPUT_SIZE) != want:
+            raise ValueError(f"MODEL.OUTPUT_SIZE = {tuple(m.OUTPUT_SIZE)!r} does not match this batch: the padded input {hp} x {wp} / "
+                             f"HEAD.DOWN_SCALE {ds} gives (H, W) = {want}")
+        if gt_slots is not None and gt_slots > m.HEAD.TENSOR_DIM:
+            raise ValueError(f"MODEL.HEAD.TENSOR_DIM = {m.HEAD.TENSOR_DIM} is smaller than the batch's {gt_slots} gt slots")
+
+    # ---- construction ----------------------------------------------------------------------------------------------------------------------
+    def _build_head(self, add, params):
+        from ..layers.center_head import CenterHead, CenternetDeconv
+        m, h = self.cfg.MODEL, self.cfg.MODEL.HEAD
+        self.neck = CenternetDeconv(list(h.DECONV_CHANNEL), list(h.DECONV_KERNEL), bool(h.MODULATE_DEFORM), device=self.device)
+        self.head = CenterHead(h.IN_CHANNELS, self.num_classes, h.CLS_PRIOR_PROB, device=self.device)
+        self.cls_ld = self.head.cls_ld
+        # the neck's norms are records of the model's LiveNorms: running statistics in norms.running (broadcast, EMA buffer average)
+        self._neck_norms = {f"{n}.{b}": self.norms.add(f"upsample.{n}.{b}", l.out_planes) for n, l in self.neck.layers()
+                            for b in ("dcn_bn", "up_bn")}
+
+    def _reserve_head(self, arena):
+        """Neck, then head, behind the trunk: one contiguous "head" bucket.  Norm vectors sit right behind their convolution's slots."""
+        self._neck_slots, self._head_slots = {}, {}
+        for n, l in self.neck.layers():
+            for k, shape in l.arena_shapes().items():
+                self._neck_slots[f"{n}.{k}"] = arena.reserve(f"upsample.{n}.{k}", shape)
+                if k.endswith("dcn.%s.bias" % l.dcn.DCN_NAME):
+                    self._neck_norms[n + ".dcn_bn"].reserve(arena)
+                elif k == "up_sample.weight":
+                    self._neck_norms[n + ".up_bn"].reserve(arena)
+        for k, shape in self.head.arena_shapes().items():
+            self._head_slots[k] = arena.reserve("head." + k, shape)
+
+    def _finish_layers(self, params):
+        a = self.arena
+        for n in self._neck_norms.values():
+            n.gamma, n.g_gamma = a.view("w", n._gi), a.view("g", n._gi)
+            n.beta, n.g_beta = a.view("w", n._bi), a.view("g", n._bi)
+        views = lambda slots, which: {k: a.view(which, i) for k, i in slots.items()}
+        self.neck.adopt(views(self._neck_slots, "w"), views(self._neck_slots, "g"), self._neck_norms)
+        self.head.adopt(views(self._head_slots, "w"), views(self._head_slots, "g"))
+        self._post = {}
+        super()._finish_layers(params)
+
+    def _head_convs(self):
+        return []
+
+    def _head_wgrad_ws_bytes(self, pl):
+        return 0           # (the neck and head own their workspaces)
+
+    def _debug_head(self, pl, out, lvl):
+        pass
+
+    # ---- parameters --------------------------------------------------------------------------------------------------------------------------
+    def _bind_params(self, params):
+        """FPNDetector._bind_params for the trunk; the neck's and head's entries, when the dict has them (a backbone-only classification
+        checkpoint does not: load_weights(strict=False) leaves them as they are), go in through the layers' strict load_state_dict."""
+        for layer, pre in ((self.neck, "upsample."), (self.head, "head.")):
+            own = {k[len(pre):]: v for k, v in params.items() if k.startswith(pre)}
+            if own:
+                layer.load_state_dict(own)
+        super()._bind_params({k: v for k, v in params.items() if k.startswith("backbone.")})
+
+    def repack_weights(self):
+        super().repack_weights()
+        self._repack_head()
+
+    def repack_trainable(self):
+        super().repack_trainable()
+        self._repack_head()
+
+    def _repack_head(self):
+        self.neck.repack()
+        self.head.repack()
+        if not self.training:
+            self.neck.refresh_eval()
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.neck.train(mode)
+        self.head.train(mode)
+        if not mode:
+            self.neck.refresh_eval()
+        return self
+
+    def state_dict(self):
+        out = super().state_dict()
+        out.update({"upsample." + k: v.numpy() for k, v in self.neck.state_dict().items()})
+        out.update({"head." + k: v.numpy() for k, v in self.head.state_dict().items()})
+        return out
+
+    def reference_grads(self):
+        out = super().reference_grads()
+        out.update({"upsample." + k: v.detach().cpu().clone() for k, v in self.neck.grads().items()})
+        out.update({"head." + k: v.detach().cpu().clone() for k, v in self.head.grads().items()})
+        return out
+
+    def reference_grads_names(self):
+        return super().reference_grads_names() + ["upsample." + k for k in self.neck.names() if "running_" not in k] \
+            + ["head." + k for k in self.head.names()]
+
+    # ---- plan ----------------------------------------------------------------------------------------------------------------------------------
+    def _plan_head(self, pl):
+        """Targets, loss gradients and loss sums of one padded shape (the neck's and head's activations are layer-owned)."""
+        C = pl._carve
+        f32, bf = torch.float32, torch.bfloat16
+        N, T, K = pl.N, int(self.cfg.MODEL.HEAD.TENSOR_DIM), self.num_classes
+        g5 = pl.blk[-1].gout
+        s = 2 ** self.neck.num_layers
+        pl.H5, pl.W5 = g5.H[0], g5.W[0]
+        pl.Ho, pl.Wo = s * pl.H5, s * pl.W5
+        M = N * pl.Ho * pl.Wo
+        pl.tgt = dict(score_map=C.empty((N, pl.Ho * pl.Wo, K), f32), wh=C.empty((N, T, 2), f32), reg=C.empty((N, T, 2), f32),
+                      reg_mask=C.empty((N, T), f32), index=C.empty((N, T), torch.int32), num_pos=C.empty((1,), f32))
+        pl.tgt_ws = C.empty((ops.centernet_targets_workspace_bytes(N),), torch.uint8)
+        pl.d_logits = C.empty((M, self.cls_ld), bf)
+        pl.d_wh, pl.d_reg, pl.d_wr = C.empty((M, 8), bf), C.empty((M, 8), bf), C.empty((M, 8), bf)
+        pl.loss_buf = C.zeros((3,), f32)
+
+    # ---- forward / losses ------------------------------------------------------------------------------------------------------------------
+    def head_forward(self, pl):
+        """res5's stored block output -> neck -> head, pixel-major bf16 all the way."""
+        b5 = pl.blk[-1]
+        pl.neck_in = b5.out
+        pl.neck_out = self.neck.forward_pm(b5.out, pl.N, pl.H5, pl.W5)
+        pl.logits, pl.wr = self.head.forward_pm(pl.neck_out, pl.N, pl.Ho, pl.Wo)
+
+    @staticmethod
+    def _host_shape(inputs):
+        image = inputs["data"] if isinstance(inputs, dict) else inputs
+        if hasattr(image, "Hmax"):
+            return image.N, image.Hmax, image.Wmax
+        return image.shape[0], image.shape[-2], image.shape[-1]
+
+    def get_losses(self, inputs):
+        """CenterNet.get_losses (centernet.py:129-155): one target launch, the focal loss and the two L1 losses with their gradients; the
+        LOSS.* weights go in as the kernels' `weight`, so the gradients arrive weighted.  Device scalars, no host synchronisation."""
+        assert self.training
+        m = self.cfg.MODEL
+        _, H, W = self._host_shape(inputs)
+        self.check_batch(self.cfg, (H, W), inputs["gt_boxes"].shape[1])
+        pre = self.pre_process(inputs)
+        pl = pre["plan"]
+        self._cur = pl
+        gt = pre["gt_boxes"]
+        num_gt = pre["img_info"][:, -1].to(torch.int32).contiguous()
+        self.network_forward(pl)
+        t, N, K, T = pl.tgt, pl.N, self.num_classes, int(m.HEAD.TENSOR_DIM)
+        ops.centernet_targets_into(gt, num_gt, N, gt.shape[1], K, pl.Ho, pl.Wo, T, 1 / m.HEAD.DOWN_SCALE, m.HEAD.MIN_OVERLAP,
+                                   t["score_map"], t["wh"], t["reg"], t["reg_mask"], t["index"], t["num_pos"], pl.tgt_ws)
+        pl.loss_buf.zero_()
+        ops.centernet_focal_fwd_bwd(pl.logits, t["score_map"], N * pl.Ho * pl.Wo, K, self.cls_ld, t["num_pos"], m.LOSS.CLS_WEIGHT, 1.0,
+                                    pl.loss_buf[0:1], pl.d_logits)
+        # (each L1 call writes all of its gradient buffer: two buffers, summed in head_backward)
+        ops.centernet_l1_fwd_bwd(pl.wr, 8, 0, t["index"], t["reg_mask"], t["wh"], N, pl.Ho, pl.Wo, T, m.LOSS.WH_WEIGHT, 1.0,
+                                 pl.loss_buf[1:2], pl.d_wh)
+        ops.centernet_l1_fwd_bwd(pl.wr, 8, 2, t["index"], t["reg_mask"], t["reg"], N, pl.Ho, pl.Wo, T, m.LOSS.REG_WEIGHT, 1.0,
+                                 pl.loss_buf[2:3], pl.d_reg)
+        loss_cls, loss_wh, loss_reg = pl.loss_buf[0], pl.loss_buf[1], pl.loss_buf[2]
+        return {"total_loss": loss_cls + loss_wh + loss_reg, "loss_cls": loss_cls, "loss_box_wh": loss_wh, "loss_center_reg": loss_reg}
+
+    # ---- backward ----------------------------------------------------------------------------------------------------------------------------
+    def head_backward(self, pl, ws, cws):
+        """Head, then neck (their weight gradients on the main stream, into the arena), then the seam: the neck's d_x gated by res5's
+        output is res5's g_out, dL/d(pre-activation)."""
+        ops.add_bf16(pl.d_wh, pl.d_reg, pl.d_wr)
+        g_f = self.head.backward_pm(pl.d_logits, pl.d_wr)
+        pl.neck_dx = self.neck.backward_pm(g_f)
+        b5 = pl.blk[-1]
+        ops.relu_bwd_bf16(pl.neck_dx, b5.out, b5.g_out)
+
+    # ---- inference -----------------------------------------------------------------------------------------------------------------------------
+    def _affines(self, inputs, N, H, W, dst):
+        """Per image the 2 x 3 map of CenterNet.post_process (centernet.py:175-178) as six float32 in dst [N][6], from the batch's
+        im_info rows [pad_h, pad_w, origin_h, origin_w, ...] (absent: pre_process's default, the padded and the given size).
+        Host im_info (the loaders'): float64 generate_src_and_dst + solve, rounded once, copied with the batch.  A device im_info is never
+        read back: the same map in closed form -- the three point pairs differ by a scale s = pad_w / out_w on both axes, so
+        a = e = s, b = d = 0, c = cx - s out_w / 2, f = cy - s out_h / 2 -- in float64 on the device, rounded once."""
+        info = inputs.get("im_info") if isinstance(inputs, dict) else None
+        ds = self.cfg.MODEL.HEAD.DOWN_SCALE
+        if torch.is_tensor(info) and info.is_cuda:
+            r = info.reshape(N, -1).double()
+            s_h, s_w, o_h, o_w = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+            cx, cy = torch.floor(o_w / 2), torch.floor(o_h / 2)
+            dw, dh = torch.floor(s_w / ds), torch.floor(s_h / ds)
+            s = s_w / dw
+            z = torch.zeros_like(s)
+            dst.copy_(torch.stack([s, z, cx - s * dw / 2, z, s, cy - s * dh / 2], 1))
+            return
+        if info is None:
+            info = np.asarray([[(H + 31) // 32 * 32, (W + 31) // 32 * 32, H, W]] * N, np.float64)
+        else:
+            info = (info.numpy() if torch.is_tensor(info) else np.asarray(info)).astype(np.float64).reshape(N, -1)[:, :4]
+        out = np.empty((N, 6), np.float32)
+        for i, row in enumerate(info):
+            flipped = row[::-1]                                  # (origin_w, origin_h, pad_w, pad_h)
+            out[i] = CenterNetDecoder.affine_matrix(flipped[:2] // 2, flipped[-2:], flipped[-2:] // ds).reshape(6)
+        dst.copy_(torch.from_numpy(out), non_blocking=True)
+
+    def inference_batch(self, inputs):
+        """CenterNet.inference + post_process (centernet.py:157-186) for every image of the batch: decode on the raw head outputs, the
+        boxes to image coordinates in one launch; a list of N Containers of TOPK rows each."""
+        from ..structures import Boxes, Container
+        assert not self.training
+        N, H, W = self._host_shape(inputs)          # (any size: MODEL.OUTPUT_SIZE describes the training targets only)
+        pre = self.pre_process(inputs)
+        pl = self._cur = pre["plan"]          # (the plan whose head outputs this call leaves behind)
+        self.network_forward(pl)
+        K, k, dev = self.num_classes, self.TOPK, self.device
+        sc = self._post.get((N, pl.Ho, pl.Wo))
+        if sc is None:
+            f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+            sc = self._post[(N, pl.Ho, pl.Wo)] = dict(
+                boxes=f(N, k, 4), scores=f(N, k), classes=torch.empty((N, k), dtype=torch.int32, device=dev), aff=f(N, 6),
+                ws=torch.empty(ops.centernet_decode_workspace_bytes(N, K, pl.Ho, pl.Wo), dtype=torch.uint8, device=dev))
+        self._affines(inputs, N, H, W, sc["aff"])
+        ops.centernet_decode(pl.logits, self.cls_ld, pl.wr, 8, 0, pl.wr, 8, 2, N, K, pl.Ho, pl.Wo, k, sc["boxes"], sc["scores"],
+                             sc["classes"], sc["ws"])
+        # (the results are the caller's: not part of the cached scratch)
+        ob = torch.empty((N, k, 4), dtype=torch.float32, device=dev)
+        osc = torch.empty((N, k), dtype=torch.float32, device=dev)
+        ol = torch.empty((N, k), dtype=torch.int32, device=dev)
+        ops.centernet_boxes_to_image(sc["boxes"], sc["aff"], sc["scores"], sc["classes"], N, k, ob, osc, ol)
+        return [Container(boxes=Boxes(ob[i]), box_scores=osc[i], box_labels=ol[i]) for i in range(N)]

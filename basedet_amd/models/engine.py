@@ -379,9 +379,11 @@ class TrainableStem:
     [64][7][7][3] like every ConvLayer master (what bd_stem_weight_pack reads and bd_stem_conv7x7_wgrad writes); state_dict, checkpoints and
     reference_grads see the reference's OIHW (64, 3, 7, 7).  The object WgradScheduler.run takes: the weight gradient runs on the side stream."""
 
-    name = "backbone.bottom_up.conv1"
     fp8_wgrad = False
-    norm = None          # BatchNormState "backbone.bottom_up.bn1" under MODEL.BACKBONE.NORM = "BN" / "SyncBN": right behind the weight
+    norm = None          # BatchNormState "<prefix>.bn1" (backbone.bottom_up.bn1; CenterNet: backbone.bn1) under MODEL.BACKBONE.NORM = "BN" / "SyncBN": right behind the weight
+
+    def __init__(self, name="backbone.bottom_up.conv1"):
+        self.name = name          # (a bare ResNet, CenterNet's: "backbone.conv1")
 
     def reserve(self, arena):
         self._wi = arena.reserve(self.name + ".weight", (64, 7, 7, 3))

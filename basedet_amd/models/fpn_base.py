@@ -51,6 +51,8 @@ class FPNDetector:
     """Backbone + FPN forward/backward and the BaseNet module protocol; heads and losses live in subclasses."""
 
     TOP_BLOCK = "p6p7"      # LastLevelP6P7 (RetinaNet / FCOS); "pool" = FPNP6 (Faster R-CNN)
+    HAS_FPN = True          # False: the bare ResNet trunk ending at res5 (CenterNet) -- no pyramid, lateral, P / g_P / lat buffers or top block
+    BOTTOM_UP = "backbone.bottom_up"    # the ResNet's name prefix (the FPN backbone holds it as bottom_up; a bare ResNet is "backbone")
     READS_FPN_UPSAMPLE = True   # MODEL.FPN.UPSAMPLE (retinanet.py:57, fcos.py:53); Faster R-CNN's FPN does not read it (faster_rcnn.py:30-36)
 
     @classmethod
@@ -71,6 +73,8 @@ class FPNDetector:
                                  "would train through a data gradient without weight gradients -- that backward pass is not built; a live "
                                  "backbone norm runs at FREEZE_AT = 0")
             cls._check_live_norm("MODEL.BACKBONE.NORM", norm, m)
+        if not cls.HAS_FPN:
+            return
         fnorm = m.FPN.get("NORM", None)
         if fnorm not in (None, "BN", "SyncBN"):
             raise ValueError(f"MODEL.FPN.NORM = {fnorm!r} is not supported: None (no FPN norm), 'BN' and 'SyncBN' are implemented")
@@ -119,8 +123,8 @@ class FPNDetector:
         m = cfg.MODEL
         self.training = True
         self.num_classes = cfg.DATA.NUM_CLASSES
-        self.strides = list(m.FPN.STRIDES)
-        self.fpn_ch = m.FPN.OUT_CHANNELS
+        self.strides = list(m.FPN.STRIDES) if self.HAS_FPN else []
+        self.fpn_ch = m.FPN.OUT_CHANNELS if self.HAS_FPN else None
         self.freeze_at = m.BACKBONE.FREEZE_AT
         self.img_mean, self.img_std = list(m.BACKBONE.IMG_MEAN), list(m.BACKBONE.IMG_STD)
         if params is None:
@@ -152,8 +156,8 @@ class FPNDetector:
         dev = self.device
         m = self.cfg.MODEL
         self.arena = ParamArena(dev)
-        bu = "backbone.bottom_up"
-        self.blocks = P.resnet_conv_table(m.BACKBONE.NAME)
+        bu = self.BOTTOM_UP
+        self.blocks = P.resnet_conv_table(m.BACKBONE.NAME, bu)
         self.convs = {}
 
         def add(name, cin, cout, k, stride, pad, bn=None, bias=False, trainable=True, cout_pad=None, norm=None):
@@ -163,7 +167,7 @@ class FPNDetector:
 
         # stem: frozen when FREEZE_AT >= 1 (solver/default_solver.py:83-94); at 0 its master weight and gradient live in the arena
         # (first: the arena follows the forward order) and the backward pass ends with the kernels of csrc/stem_bwd.hip
-        self.stem = TrainableStem() if self.freeze_at < 1 else None
+        self.stem = TrainableStem(bu + ".conv1") if self.freeze_at < 1 else None
         # MODEL.BACKBONE.NORM = "BN" / "SyncBN" (layers/backbone/build.py:27-30; FREEZE_AT = 0 only, check_config): every bnK / downsample.1
         # and the stem's bn1 is a live BatchNorm2d under the FrozenBN's name.  self.norms owns every live norm of the model, the FPN's
         # below too, and their buffers (live_norm.py): in forward order, allocated once every layer is known
@@ -198,9 +202,28 @@ class FPNDetector:
             blk["ds"] = add(pre + ".downsample.0", blk["cin"], blk["cout"], 1, blk["stride"], 0, trainable=tr,
                             **bb_norm(pre + ".downsample.1", blk["cout"])) if blk["has_ds"] else None
 
-        self.fpn_stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES]          # [3, 4, 5]
+        self.fpn_stages = [int(f[-1]) for f in m.BACKBONE.OUT_FEATURES] if self.HAS_FPN else []          # [3, 4, 5]
+        self.lateral, self.output, self.upsample = {}, {}, {}
+        self.fpn_norm, self.fpn_deconv = None, False
+        if self.HAS_FPN:
+            self._build_fpn(add)
+        self.vparams = {}
+        self._build_head(add, params)
+
+        for c in list(self.convs.values()) + list(self.vparams.values()):
+            c.reserve(self.arena)
+        self._reserve_head(self.arena)
+        self.arena.allocate()
+        self.norms.allocate()
+        self._finish_layers(params)
+
+    def _reserve_head(self, arena):
+        """Arena slots of head parameters that are not ConvLayers / VecParams (after every other slot: the arena follows the bucket order)."""
+
+    def _build_fpn(self, add):
+        m = self.cfg.MODEL
+        dev = self.device
         ch = self.fpn_ch
-        self.lateral, self.output = {}, {}
         # MODEL.FPN.NORM = "BN" / "SyncBN" (fpn_backbone.py:49-76): biasless lateral / output convolutions, each followed by a BatchNorm2d
         # (in self.norms: every lateral's, then every output convolution's)
         self.fpn_norm = m.FPN.get("NORM", None)
@@ -211,20 +234,16 @@ class FPNDetector:
             self.output[s] = add(f"backbone.fpn_output{s}", ch, ch, 3, 1, 1, bias=self.fpn_norm is None, norm=nrm.get(("output", s)))
         # MODEL.FPN.UPSAMPLE = "deconv": a learned 2x upsampling per merge, named after the coarse stage it reads (fpn_backbone.py:92-103)
         self.fpn_deconv = self.READS_FPN_UPSAMPLE and m.FPN.get("UPSAMPLE", "resize") == "deconv"
-        self.upsample = {}
         if self.fpn_deconv:
             for s in self.fpn_stages[1:]:
                 self.upsample[s] = self.convs[f"backbone.fpn_upsample{s}"] = DeconvLayer(f"backbone.fpn_upsample{s}", ch, dev)
         if self.TOP_BLOCK == "p6p7":
             self.p6 = add("backbone.top_block.p6", m.FPN.TOP_BLOCK_IN_CHANNELS, ch, 3, 2, 1, bias=True)
             self.p7 = add("backbone.top_block.p7", ch, ch, 3, 2, 1, bias=True)
-        self.vparams = {}
-        self._build_head(add, params)
 
-        for c in list(self.convs.values()) + list(self.vparams.values()):
-            c.reserve(self.arena)
-        self.arena.allocate()
-        self.norms.allocate()
+    def _finish_layers(self, params):
+        m = self.cfg.MODEL
+        dev = self.device
         # (a trainable stem needs its half-resolution output in the backward pass: FREEZE_AT = 0 always runs the two launches)
         self.fuse_stem_pool = bool(m.get("FUSE_STEM_POOL", True)) and self.stem is None
         # frozen bottleneck blocks (layer1 under FREEZE_AT = 2) in one launch each: the two mid tensors and the residual re-read never
@@ -315,7 +334,7 @@ class FPNDetector:
     def _bind_params(self, params):
         """(Re)load every parameter from a reference-layout dict (name -> numpy) and refresh the packed bf16 copies."""
         dev = self.device
-        bu = "backbone.bottom_up"
+        bu = self.BOTTOM_UP
         self.stem_w = torch.from_numpy(np.asarray(params[bu + ".conv1.weight"], np.float32)).permute(0, 2, 3, 1).contiguous().to(dev)
         g, b = params[bu + ".bn1.weight"], params[bu + ".bn1.bias"]
         mu, var = params[bu + ".bn1.running_mean"], params[bu + ".bn1.running_var"]
@@ -430,7 +449,7 @@ class FPNDetector:
         out = {}
         for c in list(self.convs.values()) + list(self.vparams.values()):
             c.export(out)
-        out["backbone.bottom_up.conv1.weight"] = self.stem_w.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+        out[self.BOTTOM_UP + ".conv1.weight"] = self.stem_w.permute(0, 3, 1, 2).contiguous().cpu().numpy()
         if getattr(self.stem, "norm", None) is not None:
             self.stem.norm.export(out)
         out.update({k: v.copy() for k, v in self._bn_params.items()})
@@ -472,7 +491,7 @@ class FPNDetector:
             out[pre + ".out"] = nchw(b.out, b.gout)
         for s in self.fpn_stages:
             out[f"lat{s}"] = nchw(pl.lat[s], pl.blk[pl.res[s]].gout)
-        for i in range(pl.pyr.nlev):
+        for i in range(pl.pyr.nlev if self.HAS_FPN else 0):
             out[f"P{self.fpn_stages[0] + i}"] = lvl(pl.P, i)
         self._debug_head(pl, out, lvl)
         return out
@@ -611,6 +630,14 @@ class FPNDetector:
             last = i + 1 == len(self.blocks) or self.blocks[i + 1]["layer"] != blk["layer"]
             if last:
                 pl.res[blk["layer"] + 1] = i
+        if self.HAS_FPN:
+            self._plan_fpn(pl, C, act, normed)
+        self._plan_tail(pl, C, act, normed)
+        return pl
+
+    def _plan_fpn(self, pl, C, act, normed):
+        """The pyramid's buffers: P / g_P, the laterals and their gradients (the P6 ReLU copy follows the norm buffers, in _plan_tail)."""
+        N = pl.N
         # pyramid
         sizes = [(pl.blk[pl.res[s]].gout.H[0], pl.blk[pl.res[s]].gout.W[0]) for s in self.fpn_stages]
         h5, w5 = sizes[-1]
@@ -630,6 +657,10 @@ class FPNDetector:
         pl.lat = {s: act(pl.blk[pl.res[s]].gout, ch) for s in self.fpn_stages}
         pl.g_lat = {s: C.like(pl.lat[s]) for s in self.fpn_stages}
         normed += [(c[s].norm, pl.blk[pl.res[s]].gout) for c in (self.lateral, self.output) for s in self.fpn_stages if c[s].norm is not None]
+
+    def _plan_tail(self, pl, C, act, normed):
+        """Norm buffers of every live norm, the head's plan, the workspaces; places the plan in the arena."""
+        N, Hp, Wp = pl.N, pl.Hp, pl.Wp
         # the pre-norm output of every normalised convolution, kept for the backward pass, and the gradient with respect to it: buffers of
         # their own, never reused within a step (the FPN's top-down path still reads g_lat, the side stream's weight gradients read g_y
         # late); the reduction workspace fits the largest
@@ -638,9 +669,10 @@ class FPNDetector:
             pl.norm_y[n.name], pl.norm_gy[n.name], pl.norm_geo[n.name] = act(g, n.C), act(g, n.C), g
         if normed:
             pl.bn_ws = C.empty((max(ops.bn_workspace_bytes(g.pixels, n.C) for n, g in normed) // 4 + 64,), torch.float32)
-        g6 = pl.pyr.level(len(self.fpn_stages))
-        pl.p6_relu = C.empty((N * h6 * w6, ch), bf)
-        pl.g_p6r = ops.single(N, h6, w6)
+        if self.HAS_FPN:
+            h6, w6 = pl.sizes[len(self.fpn_stages)]
+            pl.p6_relu = C.empty((N * h6 * w6, self.fpn_ch), torch.bfloat16)
+            pl.g_p6r = ops.single(N, h6, w6)
         self._plan_head(pl)
         # workspaces
         need = self.stem.wgrad_ws_bytes(pl.g_image, pl.g_stem) if self.stem is not None else 0
@@ -658,16 +690,15 @@ class FPNDetector:
         for li, s in enumerate(self.fpn_stages[1:]):
             gc, gf = pl.blk[pl.res[s]].gout, pl.blk[pl.res[self.fpn_stages[li]]].gout
             need = max(need, self.upsample[s].wgrad_ws_bytes(gf, gc)) if s in self.upsample else need
-        g5 = pl.blk[pl.res[self.fpn_stages[-1]]].gout
         if self.TOP_BLOCK == "p6p7":
+            g5, g6 = pl.blk[pl.res[self.fpn_stages[-1]]].gout, pl.pyr.level(len(self.fpn_stages))
             need = max(need, self.p6.wgrad_ws_bytes(g5, g6), self.p7.wgrad_ws_bytes(pl.g_p6r, pl.pyr.level(len(self.fpn_stages) + 1)))
         need = max(need, self._head_wgrad_ws_bytes(pl))
         pl.wgrad_ws = C.empty((need // 4 + 64,), torch.float32)
         cmax = max([2048] + [c.cout for c in self.convs.values() if c.trainable and c.has_bias])      # (a class predictor may be wider)
         pl.colsum_ws = C.empty((ops.colsum_workspace_bytes(cmax) // 4,), torch.float32)
         self.plan_arena.place(pl)
-        self._plans[key] = pl
-        return pl
+        self._plans[(N, Hp, Wp)] = pl
 
     # ------------------------------------------------------------------------------------------------
     # plan arena
@@ -838,6 +869,8 @@ class FPNDetector:
         for blk, b in zip(self.blocks, pl.blk):
             x = self._block_forward_norm(blk, b, x, pl) if live else self._block_forward(blk, b, x, x8)
             x8 = b.out8
+        if not self.HAS_FPN:
+            return self.head_forward(pl)
         # FPN (fpn_backbone.py:123-160): top-down from the coarsest level
         st = self.fpn_stages
         nl = len(st)
@@ -1092,7 +1125,6 @@ class FPNDetector:
         probing = self.fp8_scaler.begin_step()
         self._begin_wgrads()
         ws, cws = pl.wgrad_ws, pl.colsum_ws
-        pyr = pl.pyr
         pl.g_P8_ready = False                       # set by a head whose last data gradients wrote the e5m2 twin of dL/dP
         for b in pl.blk:
             b.g_out8_ready = False
@@ -1102,7 +1134,18 @@ class FPNDetector:
         self._flush_wgrads()
         if on_bucket_ready:
             on_bucket_ready("head", side)
-        # ---- FPN
+        if self.HAS_FPN:
+            self._fpn_backward(pl, ws, cws)
+            self._flush_wgrads()
+            if on_bucket_ready:
+                on_bucket_ready("fpn", side)
+        self._trunk_backward(pl, ws, cws, on_bucket_ready, side)
+        self._join_wgrads()
+        self.fp8_scaler.end_step(probing)
+
+    def _fpn_backward(self, pl, ws, cws):
+        """From dL/dP (the head wrote g_P) to the masked gradients of res3..res5's outputs."""
+        pyr = pl.pyr
         st = self.fpn_stages
         nl = len(st)
         b5 = pl.blk[pl.res[st[-1]]]
@@ -1165,9 +1208,8 @@ class FPNDetector:
             g_lat = [self._norm_backward(self.lateral[s].norm, pl.g_lat[s], pl.blk[pl.res[s]].gout, pl) for s in st]
             for li in range(nl):
                 lateral_backward(li, g_lat[li])
-        self._flush_wgrads()
-        if on_bucket_ready:
-            on_bucket_ready("fpn", side)
+
+    def _trunk_backward(self, pl, ws, cws, on_bucket_ready, side):
         # ---- backbone, last block first.  g_out of a block holds the masked gradient once all consumers are done:
         # res5: done above.  res3/res4 (and every inner block output): the next block's dgrads finish it.
         nb = len(self.blocks)
@@ -1190,6 +1232,4 @@ class FPNDetector:
             self._flush_wgrads()
             if on_bucket_ready:
                 on_bucket_ready("conv1", side)
-        self._join_wgrads()
-        self.fp8_scaler.end_step(probing)
 

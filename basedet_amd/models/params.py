@@ -20,7 +20,7 @@ RESNET_SPECS = {
 }
 
 
-def resnet_conv_table(name):
+def resnet_conv_table(name, prefix="backbone.bottom_up"):
     """[(prefix, cin, cout, k, stride, pad, bn_prefix)] in forward order + per-block structure."""
     kind, layers = RESNET_SPECS[name]
     exp = 4 if kind == "bottleneck" else 1
@@ -30,7 +30,7 @@ def resnet_conv_table(name):
         ch = 64 * 2 ** li
         for b in range(nblk):
             stride = 2 if (b == 0 and li > 0) else 1
-            pre = f"backbone.bottom_up.layer{li + 1}.{b}"
+            pre = f"{prefix}.layer{li + 1}.{b}"
             has_ds = (cin != ch * exp) or stride != 1
             blocks.append(dict(prefix=pre, kind=kind, cin=cin, ch=ch, cout=ch * exp, stride=stride, has_ds=has_ds, layer=li + 1))
             cin = ch * exp
@@ -50,14 +50,14 @@ def _bn(p, prefix, c):
     p[prefix + ".running_var"] = np.ones(c, np.float32)
 
 
-def init_resnet(p, rng, name, residual_gamma=None):
+def init_resnet(p, rng, name, residual_gamma=None, prefix="backbone.bottom_up"):
     """residual_gamma: optional FrozenBN gamma for the last BN of every residual branch.  The reference always
     starts from ImageNet statistics (retinanet_cfg.py:8); with identity BN a random-init ResNet-50 overflows, so the
     benchmark's synthetic weights use a damped value (same FLOPs / bytes, finite activations)."""
-    bu = "backbone.bottom_up"
+    bu = prefix
     p[bu + ".conv1.weight"] = _msra_normal(rng, (64, 3, 7, 7), "fan_out")
     _bn(p, bu + ".bn1", 64)
-    for blk in resnet_conv_table(name):
+    for blk in resnet_conv_table(name, prefix):
         pre = blk["prefix"]
         if blk["kind"] == "bottleneck":
             specs = [("conv1", blk["cin"], blk["ch"], 1), ("conv2", blk["ch"], blk["ch"], 3), ("conv3", blk["ch"], blk["cout"], 1)]

@@ -1118,6 +1118,10 @@ def centernet_targets(gt_boxes, num_gt, K, H, W, T, box_scale, min_overlap):
     return out
 
 
+def centernet_targets_workspace_bytes(N):
+    return int(L().bd_centernet_targets_workspace_bytes(N))
+
+
 def centernet_targets_into(gt_boxes, num_gt, N, G, K, H, W, T, box_scale, min_overlap, score_map, wh, reg, reg_mask, index, num_pos, ws):
     check(L().bd_centernet_targets(ptr(gt_boxes), ptr(num_gt), N, G, K, H, W, T, float(box_scale), float(min_overlap), ptr(score_map),
                                    ptr(wh), ptr(reg), ptr(reg_mask), ptr(index), ptr(num_pos), ptr(ws), ws.numel() * ws.element_size(),
@@ -1145,6 +1149,13 @@ def centernet_decode(logits, ld, wh, wh_ld, wh_off, reg, reg_ld, reg_off, B, K, 
     check(L().bd_centernet_decode(ptr(logits), ld, ptr(wh), wh_ld, wh_off, ptr(reg), reg_ld, reg_off, B, K, H, W, k, ptr(boxes),
                                   ptr(scores), ptr(classes), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
           "bd_centernet_decode")
+
+
+def centernet_boxes_to_image(boxes, affine, scores, classes, B, k, boxes_out, scores_out, labels_out):
+    """bd_centernet_boxes_to_image: boxes fp32 [B][k][4] through the per-image 2 x 3 maps affine fp32 [B][6] into boxes_out; scores and
+    classes pass through into scores_out / labels_out."""
+    check(L().bd_centernet_boxes_to_image(ptr(boxes), ptr(affine), ptr(scores), ptr(classes), int(B), int(k), ptr(boxes_out),
+                                          ptr(scores_out), ptr(labels_out), stream_ptr()), "bd_centernet_boxes_to_image")
 
 
 # ---- CenterHead's output convolutions (center_head.hip) -----------------------------------------------------------------------------------

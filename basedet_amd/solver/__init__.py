@@ -191,12 +191,13 @@ class GradBuckets:
         ent = self.model.arena.entries
         groups = {}
         for name, _, off, n in ent:
-            if name.startswith(("head.", "rpn.", "rcnn.")):
+            if name.startswith(("head.", "rpn.", "rcnn.", "upsample.")):       # (upsample.: CenterNet's neck, finished with its head)
                 k = "head"
             elif "fpn_" in name or "top_block" in name:
                 k = "fpn"
             else:
-                k = name.split(".")[2]     # backbone.bottom_up.layerX...
+                parts = name.split(".")    # backbone.bottom_up.layerX... (CenterNet holds the bare ResNet: backbone.layerX...)
+                k = parts[2] if parts[1] == "bottom_up" else parts[1]
                 if k == "bn1":             # the stem's live norm (MODEL.BACKBONE.NORM): finished with conv1's weight gradient
                     k = "conv1"
             lo, hi = groups.get(k, (off, off))

@@ -915,6 +915,15 @@ int bd_centernet_decode(const void* logits, int ld, const void* wh, int wh_ld, i
                         int B, int K, int H, int W, int k, float* boxes, float* scores, int32_t* classes, void* ws, size_t ws_bytes,
                         bd_stream_t stream);
 
+/* CenterNet.post_process's transform_boxes (centernet.py:163-186, 293-311) for a whole batch (bd_version() >= 117): the decoded boxes
+ * from output-map cells to the original image, one thread per box.  boxes fp32 [B][k][4] as bd_centernet_decode wrote them (16-byte
+ * aligned); affine fp32 [B][6] = per image the 2 x 3 map (a b c / d e f), solved on the host in float64 and rounded once.  The order of
+ * the arithmetic is fixed: x' = fma(a, x, fma(b, y, c)), y' = fma(d, x, fma(e, y, f)) for both corners.  scores [B][k] and classes
+ * int32 [B][k] pass through into scores_out / labels_out, the caller's dense per-image tensors, in the same launch.  boxes_out must not
+ * overlap boxes.  BD_EINVAL before any launch for B <= 0, k <= 0 or a null pointer. */
+int bd_centernet_boxes_to_image(const float* boxes, const float* affine, const float* scores, const int32_t* classes, int B, int k,
+                                float* boxes_out, float* scores_out, int32_t* labels_out, bd_stream_t stream);
+
 /* The output convolutions of CenterHead (bd_version() >= 116; center_head.hip; layers/head/center_head.py:91-131: the three
  * SingleHead.out_conv, 1x1, C -> K / 2 / 2) in one launch per direction.  feat: bf16 [M][3C], the ReLU output of the three feat_convs
  * run as one 3C-row convolution -- channels [0,C) the cls tower, [C,2C) the wh tower, [2C,3C) the reg tower.  w_cls [K][C], w_wh [2][C],
