@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BASEDET_HIP_LIB") or os.path.join(_HERE, "lib", "libbasedet_hip.so")   # override: A/B of two builds
 
 BD_MAX_SEGS = 8
-ABI_VERSION = 117              # bd_version() of the library this binding matches (117: bd_centernet_boxes_to_image; 116: the bd_center_head_out_* entries of center_head.hip; 115: the bd_centernet_* entries of centernet.hip; 114: the GroupNorm partials of bd_conv2d_fwd_gnstats / bd_groupnorm_fwd hold (mean, M2), not (sum, sum of squares); 113: the bd_deform_conv_* entries of deform_conv.hip;101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd; 111: bd_bn_apply_fwd removed, bd_bn_apply_act_fwd serves its callers; 112: one entry per operator -- the *_ld, _general, _batched and _joint twins and the giou forwarder folded into the base names, which take their arguments)
+ABI_VERSION = 118              # bd_version() of the library this binding matches (118: bd_affine_jitter_normalize of image_affine.hip; 117: bd_centernet_boxes_to_image; 116: the bd_center_head_out_* entries of center_head.hip; 115: the bd_centernet_* entries of centernet.hip; 114: the GroupNorm partials of bd_conv2d_fwd_gnstats / bd_groupnorm_fwd hold (mean, M2), not (sum, sum of squares); 113: the bd_deform_conv_* entries of deform_conv.hip;101: the liveness-map fields; 102: the EMA entries; 103: raw-image input; 104: the *_ld entries; 105: bd_iou_ltrb_fwd_bwd, bd_loss_grid_cap; 106: the Adam / Nesterov entries of optim.hip; 107: the forward liveness maps; 108: the stem backward entries of stem_bwd.hip; 109: the bd_bn_* entries of batchnorm.hip; 110: bd_bn_apply_act_fwd, bd_stem_conv7x7_raw_fwd; 111: bd_bn_apply_fwd removed, bd_bn_apply_act_fwd serves its callers; 112: one entry per operator -- the *_ld, _general, _batched and _joint twins and the giou forwarder folded into the base names, which take their arguments)
 EPI_RELU, EPI_ADD_BEFORE, EPI_ADD_AFTER, EPI_MASK, EPI_SPARSE = 1, 2, 4, 8, 16
 
 
@@ -47,6 +47,17 @@ class ImageDesc(C.Structure):
     """bd_image_desc: one image of a packed raw batch (bd_resize_pad_normalize)."""
     _fields_ = [("offset", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("dst_h", C.c_int32), ("dst_w", C.c_int32),
                 ("flip", C.c_int32), ("reserved_", C.c_int32 * 1)]
+
+
+AFFINE_BRIGHTNESS, AFFINE_CONTRAST, AFFINE_SATURATION, AFFINE_LIGHTING = 1, 2, 4, 8          # bd_affine_desc.stages
+
+
+class AffineDesc(C.Structure):
+    """bd_affine_desc: one image of a packed raw batch and what CenterNet's training pipeline does to it (bd_affine_jitter_normalize);
+    inv = the row-major 2 x 3 map from an output pixel to the source image."""
+    _fields_ = [("offset", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("inv", C.c_double * 6), ("flip", C.c_int32),
+                ("stages", C.c_uint32), ("alpha_brightness", C.c_float), ("alpha_contrast", C.c_float), ("alpha_saturation", C.c_float),
+                ("delta", C.c_float * 3)]
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -111,6 +122,8 @@ SIGNATURES = {
     "bd_h2d_destroy": (_I, [_P]),
     "bd_pad_normalize_nchw": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "bd_resize_pad_normalize": (_I, [_P, _L, C.POINTER(ImageDesc), _I, _I, _I, _P, _P, _P, _P]),
+    "bd_affine_jitter_workspace_bytes": (_Z, [_I, _I, _I]),
+    "bd_affine_jitter_normalize": (_I, [_P, _L, C.POINTER(AffineDesc), _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_maxpool3x3s2_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "bd_upsample2x_add_fwd": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _P]),
     "bd_upsample2x_add_bwd": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _P]),

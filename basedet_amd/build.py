@@ -15,6 +15,7 @@ ARCH = "gfx950"
 SOURCES = {
     "image_ops.hip": [],
     "image_resize.hip": ["-ffp-contract=off"],
+    "image_affine.hip": ["-ffp-contract=off"],
     "ema.hip": [],
     # one fp32 rounding per operation (tests/test_optim_gpu.py compares bits with numpy): no FMA contraction, IEEE division and square
     # root (hipcc's default, stated because the tests depend on it)

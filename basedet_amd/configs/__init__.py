@@ -252,8 +252,9 @@ class OTAConfig(FCOSConfig):
 
 
 class CenterNetConfig(DetectionConfig):
-    """basedet/configs/det_model/centernet_cfg.py:5-67.  AUG.TRAIN_VALUE keeps the reference's value; CenterAffine and the colour
-    augmentations are not built (data/transforms.py build_transform raises on them), so a run names its own AUG or a synthetic loader."""
+    """basedet/configs/det_model/centernet_cfg.py:5-67.  AUG.TRAIN_VALUE keeps the reference's value; its pipeline (CenterAffine, flip and the
+    colour augmentations) runs on the device from raw uint8 images: basedet.data.CenterNetRawCollator(cfg.AUG.TRAIN_VALUE, rng) is the entry
+    (data/raw.py, bd_affine_jitter_normalize).  data/transforms.py build_transform has no host pixel path for it and still raises."""
 
     def __init__(self, cfg=None, **kwargs):
         super().__init__()

@@ -34,7 +34,7 @@ extern "C" const char* bd_last_error_string(void) { return g_bd_error.c_str(); }
 static thread_local const char* g_bd_last_kernel = "";
 void bd_note_kernel(const char* name) { g_bd_last_kernel = name; }
 extern "C" const char* bd_conv_last_kernel(void) { return g_bd_last_kernel; }
-extern "C" int bd_version(void) { return 117; }
+extern "C" int bd_version(void) { return 118; }
 
 namespace {
 

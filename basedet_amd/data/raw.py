@@ -10,10 +10,13 @@ writes into the plan is bit for bit what the existing path writes from the same 
 import numpy as np
 import torch
 
-from .._lib import ImageDesc
+from .. import _lib
+from .._lib import AffineDesc, ImageDesc
+from .centernet_transforms import (BrightnessTransform, CenterAffine, ContrastTransform, Lighting, SaturationTransform,
+                                   invert_affine)
 from .transforms import Compose, RandomHorizontalFlip, ShortestEdgeResize, TestTimeCompose, ToMode
 
-__all__ = ["RawImageBatch", "RawBatchCollator"]
+__all__ = ["RawImageBatch", "AffineImageBatch", "RawBatchCollator", "CenterNetRawCollator"]
 
 
 class RawImageBatch:
@@ -30,6 +33,10 @@ class RawImageBatch:
             self._owner._pending = event
 
 
+class AffineImageBatch(RawImageBatch):
+    """A RawImageBatch whose descs are _lib.AffineDesc records (bd_affine_jitter_normalize): every image comes out Hmax x Wmax."""
+
+
 class _Shape:
     """What the transforms' _get_params read of an image: its shape (the pixels stay where they are)."""
     __slots__ = ("shape",)
@@ -38,7 +45,21 @@ class _Shape:
         self.shape = (int(h), int(w), 3)
 
 
-class RawBatchCollator:
+class _PackedOwner:
+    """The grow-only pinned buffer of a raw collator and the handshake that guards it (RawImageBatch.copied)."""
+    _buf = None                  # grow-only packed buffer
+    _pending = None              # event of the previous batch's copy
+
+    def _packed(self, nbytes):
+        if self._pending is not None:        # the previous batch's copy still reads the buffer
+            self._pending.synchronize()
+            self._pending = None
+        if self._buf is None or self._buf.numel() < nbytes:
+            self._buf = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        return self._buf[:nbytes]
+
+
+class RawBatchCollator(_PackedOwner):
     """transform: the Compose / TestTimeCompose of build_transform.  One batch is in flight per collator: ``apply`` waits for the previous
     batch's copy (RawImageBatch.copied) before it overwrites the packed buffer."""
 
@@ -60,8 +81,6 @@ class RawBatchCollator:
             seen_flip = seen_flip or type(t) is RandomHorizontalFlip
         self.transform, self.pad_value = transform, pad_value
         self.test_mode = isinstance(transform, TestTimeCompose)
-        self._buf = None             # grow-only packed buffer
-        self._pending = None         # event of the previous batch's copy
 
     def _params(self, image, boxes):
         """One sample through the transform list without touching a pixel: (dst_h, dst_w, flip, boxes)."""
@@ -117,10 +136,99 @@ class RawBatchCollator:
 
     __call__ = apply
 
-    def _packed(self, nbytes):
-        if self._pending is not None:        # the previous batch's copy still reads the buffer
-            self._pending.synchronize()
-            self._pending = None
-        if self._buf is None or self._buf.numel() < nbytes:
-            self._buf = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-        return self._buf[:nbytes]
+
+class CenterNetRawCollator(_PackedOwner):
+    """The pipeline of CenterNetConfig.AUG.TRAIN_VALUE over raw images: spec_or_transforms is that (name, kwargs) list (every transform
+    then draws from `rng`) or a list of transform objects.  The order is the one the device runs: CenterAffine, RandomHorizontalFlip
+    (optional), then any of Brightness -> Contrast -> Saturation -> Lighting in that order, then ToMode("CHW").  Parameters are drawn
+    per sample through the transforms' own _get_params, boxes move on the host, boxes left without width or height are dropped
+    (models/det/centernet.py:93 filter_by_size), and the pixels wait for bd_affine_jitter_normalize (FPNDetector.pre_process)."""
+    _BY_NAME = {"CenterAffine": CenterAffine, "MGE_RandomHorizontalFlip": RandomHorizontalFlip, "RandomHorizontalFlip": RandomHorizontalFlip,
+                "MGE_BrightnessTransform": BrightnessTransform, "MGE_ContrastTransform": ContrastTransform,
+                "MGE_SaturationTransform": SaturationTransform, "MGE_Lighting": Lighting, "MGE_ToMode": ToMode, "ToMode": ToMode}
+    _ORDER = (CenterAffine, RandomHorizontalFlip, BrightnessTransform, ContrastTransform, SaturationTransform, Lighting, ToMode)
+
+    def __init__(self, spec_or_transforms, rng=None):
+        ts = []
+        for item in spec_or_transforms:
+            if isinstance(item, (tuple, list)):
+                name, kw = item
+                if name not in self._BY_NAME:
+                    raise ValueError(f"CenterNetRawCollator: the transform {name!r} is unknown; built: {sorted(self._BY_NAME)}")
+                cls = self._BY_NAME[name]
+                item = cls(**kw) if cls is ToMode else cls(**kw, rng=rng)
+            ts.append(item)
+        last = -1
+        for t in ts:
+            # exact types: a subclass may redefine what happens to the pixels, and the device would silently not do it
+            if type(t) not in self._ORDER:
+                raise ValueError(f"CenterNetRawCollator cannot run {type(t).__name__} on the device "
+                                 f"({', '.join(c.__name__ for c in self._ORDER)} only)")
+            rank = self._ORDER.index(type(t))
+            if rank <= last or (last < 0 and rank != 0):
+                raise ValueError(f"CenterNetRawCollator: {type(t).__name__} is out of order or repeated: the device runs "
+                                 f"{' -> '.join(c.__name__ for c in self._ORDER)}, each at most once, CenterAffine first")
+            last = rank
+        if not ts or type(ts[-1]) is not ToMode or ts[-1].mode != "CHW":
+            raise ValueError('CenterNetRawCollator: the pipeline ends with ToMode("CHW")')
+        self.affine = ts[0]
+        if not self.affine.random_aug:
+            raise NotImplementedError("Non-random augmentation not implemented")
+        w, h = self.affine.output_size
+        if w <= 0 or h <= 0 or w % 32 or h % 32:
+            raise ValueError(f"CenterNetRawCollator: CenterAffine's output_size {(w, h)} must be positive multiples of 32")
+        self.transforms = ts
+
+    def _params(self, image, boxes):
+        """One sample through the transform list without touching a pixel: (AffineDesc without its offset, boxes)."""
+        w, h = self.affine.output_size
+        d = AffineDesc(src_h=image.shape[0], src_w=image.shape[1], alpha_brightness=1.0, alpha_contrast=1.0, alpha_saturation=1.0)
+        for t in self.transforms:
+            t._get_params(_Shape(*image.shape[:2]) if type(t) is CenterAffine else _Shape(h, w))
+            if type(t) is CenterAffine:
+                d.inv[:] = invert_affine(t.affine).reshape(6).tolist()
+            elif type(t) is RandomHorizontalFlip:
+                d.flip = int(t._flip)
+            elif type(t) is BrightnessTransform and t.value != 0:
+                d.stages, d.alpha_brightness = d.stages | _lib.AFFINE_BRIGHTNESS, t._alpha
+            elif type(t) is ContrastTransform and t.value != 0:
+                d.stages, d.alpha_contrast = d.stages | _lib.AFFINE_CONTRAST, t._alpha
+            elif type(t) is SaturationTransform and t.value != 0:
+                d.stages, d.alpha_saturation = d.stages | _lib.AFFINE_SATURATION, t._alpha
+            elif type(t) is Lighting and t.scale != 0:
+                d.stages = d.stages | _lib.AFFINE_LIGHTING
+                d.delta[:] = t._delta.tolist()
+            boxes = t._apply_boxes(boxes)
+        return d, boxes
+
+    def apply(self, samples):
+        """samples: (image HWC uint8, boxes (n, 4), boxes_category (n,), info with info[0:2] = original (H, W)) per image."""
+        w, h = self.affine.output_size
+        rows, nbytes = [], 0
+        for image, boxes, category, info in samples:
+            image = np.asarray(image)
+            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
+                raise ValueError(f"CenterNetRawCollator needs uint8 (H, W, 3) images, got {image.dtype} {image.shape}")
+            boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+            category = np.asarray(category, np.float32).reshape(-1)
+            assert len(boxes) == len(category)
+            d, boxes = self._params(image, boxes)
+            keep = (boxes[:, 2] - boxes[:, 0] > 0) & (boxes[:, 3] - boxes[:, 1] > 0)
+            d.offset = nbytes
+            orig = image.shape[:2] if info is None else (info[0], info[1])
+            rows.append((image, d, boxes[keep], category[keep], orig))
+            nbytes += image.size
+        n = len(rows)
+        flat = (packed := self._packed(nbytes)).numpy()
+        gmax = max((len(r[2]) for r in rows), default=0)
+        gt_boxes = np.zeros((n, gmax, 5), np.float32)
+        im_info = np.empty((n, 5), np.float32)
+        for i, (image, d, boxes, category, orig) in enumerate(rows):
+            np.copyto(flat[d.offset:d.offset + image.size].reshape(image.shape), image)
+            g = len(boxes)
+            gt_boxes[i, :g, :4] = boxes
+            gt_boxes[i, :g, 4] = category
+            im_info[i] = (h, w, orig[0], orig[1], g)
+        return {"data": AffineImageBatch(packed, [r[1] for r in rows], h, w, owner=self), "gt_boxes": gt_boxes, "im_info": im_info}
+
+    __call__ = apply

@@ -10,8 +10,8 @@ the trunk's own backward loop.  The neck's and head's fp32 masters, gradients an
 and LiveNorms (the layers' adopt()), so the fused optimizer launch, ModelEMA, GradClip, GradBuckets, broadcast_parameters and checkpoints
 see them; their activations and workspaces stay layer-owned, and their weight gradients run on the main stream.
 Inference decodes the raw head outputs (K = 100, reg given) and maps the boxes to the image for the whole batch in one launch
-(bd_centernet_boxes_to_image) from six host-built floats per image.  Not built: fp8 weights, CenterAffine and the colour augmentations
-of AUG.TRAIN_VALUE.
+(bd_centernet_boxes_to_image) from six host-built floats per image.  Not built: fp8 weights.  The pipeline of AUG.TRAIN_VALUE (CenterAffine and the
+colour augmentations) reaches pre_process as a data/raw.py CenterNetRawCollator batch and runs in bd_affine_jitter_normalize.
 
 Tensors are the reference's: NCHW fp32 on the HIP device (host tensors raise: there is no CPU path).  The kernels read the head's
 convolution output -- pixel-major bf16 LOGITS -- so the functions that take probabilities, as the reference's do, turn them back into

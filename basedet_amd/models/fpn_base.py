@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..data.raw import RawImageBatch
+from ..data.raw import AffineImageBatch, RawImageBatch
 from ..ops import Geom
 from ..streams import SideStreams, fork, join
 from . import params as P
@@ -743,7 +743,11 @@ class FPNDetector:
         Hp, Wp = _round_up(H, 32), _round_up(W, 32)
         pl = self._plan(N, Hp, Wp)
         self._bind_plan(pl)
-        if isinstance(image, RawImageBatch):
+        if isinstance(image, AffineImageBatch):
+            # CenterNet's training pipeline (data/raw.py CenterNetRawCollator): warp, flip, colour passes and normalise, one or two launches
+            ws = self._scratch("affine_jitter", ops.affine_jitter_workspace_bytes(N, Hp, Wp))
+            ops.affine_jitter_normalize(packed, image.descs, Hp, Wp, self.img_mean, self.img_std, pl.x_halo, ws)
+        elif isinstance(image, RawImageBatch):
             ops.resize_pad_normalize(packed, image.descs, Hp, Wp, self.img_mean, self.img_std, pl.x_halo)
         else:
             ops.pad_normalize(image, Hp, Wp, self.img_mean, self.img_std, pl.x_halo)

@@ -460,6 +460,25 @@ def resize_pad_normalize(packed, descs, Hp, Wp, mean, std, out):
     return out
 
 
+def affine_jitter_workspace_bytes(N, out_h, out_w):
+    return int(L().bd_affine_jitter_workspace_bytes(int(N), int(out_h), int(out_w)))
+
+
+def affine_jitter_normalize(packed, descs, out_h, out_w, mean, std, out, ws=None, u8_out=None):
+    """bd_affine_jitter_normalize: packed = uint8 device tensor holding the raw HWC images, descs = their _lib.AffineDesc records (host);
+    out = bf16 (N, out_h + 6, out_w + 8, 4), written whole; ws = uint8 workspace of affine_jitter_workspace_bytes (needed when an image
+    has contrast enabled); u8_out = optional uint8 (N, out_h, out_w, 3) for the bytes before normalisation."""
+    N = len(descs)
+    assert packed.dtype == torch.uint8 and out.dtype == torch.bfloat16 and out.numel() == N * (out_h + 6) * (out_w + 8) * 4
+    assert u8_out is None or (u8_out.dtype == torch.uint8 and u8_out.numel() == N * out_h * out_w * 3)
+    assert ws is None or ws.dtype == torch.uint8
+    arr = descs if isinstance(descs, C.Array) else (_lib.AffineDesc * N)(*descs)
+    check(L().bd_affine_jitter_normalize(ptr(packed), packed.numel(), arr, N, int(out_h), int(out_w), f32arr(mean), f32arr(std), ptr(out),
+                                         ptr(u8_out), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()),
+          "bd_affine_jitter_normalize")
+    return out
+
+
 def stem_pool_fwd(N, H, W, x_halo, w_stem, bias, y_pool):
     """stem_conv7x7_fwd + maxpool3x3s2_fwd in one launch (bit-identical; the half-resolution tensor is never written)."""
     check(L().bd_stem_pool_fwd(N, H, W, ptr(x_halo), ptr(w_stem), ptr(bias), ptr(y_pool), stream_ptr()), "bd_stem_pool_fwd")

@@ -366,6 +366,46 @@ typedef struct bd_image_desc {
 int bd_resize_pad_normalize(const uint8_t* packed_dev, int64_t packed_bytes, const bd_image_desc* descs_host, int N, int Hp, int Wp,
                             const float* mean3, const float* std3, void* x_halo, bd_stream_t stream);
 
+/* CenterNet's training input (bd_version() >= 118; image_affine.hip; CenterNetConfig.AUG.TRAIN_VALUE: CenterAffine, horizontal flip,
+ * brightness, contrast, saturation, lighting): N raw uint8 images packed as above -> the same layout (bf16 [N][out_h+6][out_w+8][4],
+ * zero halo, channel 3 = 0, every element written), bit for bit what tests/center_affine_oracle.py computes:
+ *   warp        cv2.warpAffine(INTER_LINEAR, constant border 0) in fixed point: inv maps an output pixel to the source image; source
+ *               coordinates in 1/1024 pixel from lrint(inv[0] x 1024) per column and lrint((inv[1] y + inv[2]) 1024) per row (float64),
+ *               plus 16, >> 5; integer bilinear weights that sum to 32768; (sum w p + 16384) >> 15; taps outside the source read 0
+ *   flip        output column x holds warped column out_w - 1 - x
+ *   brightness  trunc(clip(p alpha, 0, 255)) per byte, fp32
+ *   contrast    trunc(clip(p alpha + mean (1 - alpha), 0, 255)); mean = (0.114f S0 + 0.587f S1 + 0.299f S2) / (out_h out_w) from the exact
+ *               integer channel sums of the image after brightness, combined in float64 and rounded once to fp32
+ *   saturation  grey = 0.114f p0 + 0.587f p1 + 0.299f p2 (fp32, left to right); trunc(clip(p alpha + grey (1 - alpha), 0, 255))
+ *   lighting    trunc(clip(p + delta[c], 0, 255))
+ *   normalise   (p - mean3[c]) / std3[c]
+ * in this order; a colour stage runs where its bit of `stages` is set; no multiply-add contraction anywhere.  Channels in the order of
+ * mean3 / std3 (the grey weights are those of a BGR image).  u8_out (NULL: not wanted) receives the bytes before normalisation,
+ * [N][out_h][out_w][3].  descs_host is a HOST array, read before the call returns; it travels by value, 32 images per launch.
+ * With contrast enabled for any image: one memset of the channel-sum counters and two launches per 32 images, through a workspace of
+ * bd_affine_jitter_workspace_bytes bytes (8-byte aligned; its contents on entry do not matter); otherwise one launch per 32 images and
+ * ws may be NULL.  BD_EINVAL, with nothing launched, unless out_h, out_w are multiples of 32 (at most 16384), 0 < src_h, src_w <= 32767,
+ * offset + src_h * src_w * 3 <= packed_bytes, the map is finite, not singular, |inv[0,1,3,4]| max(out_h, out_w) <= 2^18 and
+ * |inv[2,5]| <= 2^18, the colour parameters are finite and the workspace is large enough. */
+#define BD_AFFINE_BRIGHTNESS 1
+#define BD_AFFINE_CONTRAST 2
+#define BD_AFFINE_SATURATION 4
+#define BD_AFFINE_LIGHTING 8
+#define BD_AFFINE_ALL 15
+typedef struct bd_affine_desc {
+    int64_t offset;
+    int32_t src_h, src_w;
+    double inv[6];                              /* the INVERSE map, row-major 2 x 3: source = inv (x, y, 1) of an output pixel */
+    int32_t flip;
+    uint32_t stages;                            /* BD_AFFINE_* bits */
+    float alpha_brightness, alpha_contrast, alpha_saturation;
+    float delta[3];                             /* 96 bytes */
+} bd_affine_desc;
+size_t bd_affine_jitter_workspace_bytes(int N, int out_h, int out_w);
+int bd_affine_jitter_normalize(const uint8_t* packed_dev, int64_t packed_bytes, const bd_affine_desc* descs_host, int N, int out_h,
+                               int out_w, const float* mean3, const float* std3, void* x_halo, uint8_t* u8_out, void* ws, size_t ws_bytes,
+                               bd_stream_t stream);
+
 /* M.MaxPool2d(3, 2, 1) (models/cls/resnet.py:146) on NHWC bf16. */
 int bd_maxpool3x3s2_fwd(const void* x, int N, int H, int W, int C, void* y, bd_stream_t stream);
 
