@@ -206,6 +206,15 @@ SIGNATURES = {
     "bd_center_head_out_bwd_workspace_bytes": (_Z, [_L, _I, _I]),
     # (feat, d_logits, d_wr, w_cls, w_wh, w_reg, M, C, K, cls_ld, d_feat, dw_cls, db_cls, dw_wh, db_wh, dw_reg, db_reg, accumulate, ws, ws_bytes, stream)
     "bd_center_head_out_bwd": (_I, [_P] * 6 + [_L, _I, _I, _I] + [_P] * 7 + [_I, _P, _Z, _P]),
+    "bd_yolox_assign_workspace_bytes": (_Z, [_I, _I]),
+    # (points, P, lvl_start, strides, L, cls, K, ld, box_obj, gt_boxes, num_gt, N, Gmax, matched, iou_t, stats, ws, ws_bytes, stream)
+    "bd_yolox_assign": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "bd_yolox_loss_workspace_bytes": (_Z, []),
+    # (points, P, lvl_start, strides, L, cls, K, ld, box_obj, gt_boxes, N, Gmax, matched, iou_t, stats, use_l1, grad_scale, loss_out, d_cls,
+    #  d_box_obj, ws, ws_bytes, stream)
+    "bd_yolox_loss_fwd_bwd": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
+    # (topk_idx, topk_score, topk_cnt, B, L, k, lvl_start, strides, K, points, P, box_obj, boxes, scores, labels, stream)
+    "bd_yolox_candidates": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "bd_rcnn_predict": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bd_det_candidates": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P]),
     "bd_det_finalize": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
@@ -269,7 +278,10 @@ def load():
     lib.bd_version.restype = C.c_int
     check_version(int(lib.bd_version()))
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:      # entries added without an ABI break (the bd_yolox_* entries of yolox.hip) keep bd_version() as it is
+            raise BasedetHipError(f"{LIB_PATH} does not export {name}: rebuild it with `python -m basedet_amd.build`") from None
         fn.restype = res
         fn.argtypes = args
     _lib = lib

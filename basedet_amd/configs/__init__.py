@@ -279,3 +279,42 @@ class CenterNetConfig(DetectionConfig):
             SOLVER=dict(MAX_EPOCH=140, BASIC_LR=0.02 / (8 * 16), WEIGHT_DECAY=1e-4, LR_DECAY_RATE=0.1, LR_DECAY_STAGES=[90, 120],
                         WARM_ITERS=1000, NUM_IMAGE_PER_EPOCH=115200)))
         self._override(cfg, kwargs)
+
+
+class YOLOXConfig(DetectionConfig):
+    """basedet/configs/det_model/yolox_cfg.py:6-117, key for key (the reference deletes DetectionConfig's MODEL section and
+    SOLVER.WARM_ITERS before / after merging its own).  What this build has of YOLOX so far is everything behind the head's last
+    convolutions (models/yolox.py); the model class, CSPDarknet / YOLOPAFPN and the mosaic input are not built yet."""
+
+    TEST_SIZE = 416
+
+    def __init__(self, cfg=None, **kwargs):
+        super().__init__()
+        del self["MODEL"]
+        batch = 8
+        self.merge(dict(
+            MODEL=dict(NAME="YOLOX", WEIGHTS="", DEPTH_FACTOR=1.0, WIDTH_FACTOR=1.0, DEPTHWISE=False, ACTIVATION="silu", BN_EPS=1e-3,
+                       BN_MOMENTUM=0.97, BACKBONE=dict(NAME="csp_darknet", OUT_FEATURES=["dark3", "dark4", "dark5"]),
+                       FPN=dict(CONF_THRESHOLD=0.01, NMS_THRESHOLD=0.5), BATCHSIZE=batch),
+            SOLVER=dict(BUILDER_NAME="YOLOXSolver", REDUCE_MODE="MEAN", BASIC_LR=0.01 / (batch * 8), MIN_LR_RATIO=0.05, MOMENTUM=0.9,
+                        WEIGHT_DECAY=0.0005, WARM_EPOCH=5, NUM_IMAGE_PER_EPOCH=120000, MAX_EPOCH=300, LR_DECAY_RATE=0.1),
+            DATA=dict(BUILDER_NAME="YOLOXDataloaderBuilder",
+                      TRAIN=dict(name="coco_2017_train", remove_images_without_annotations=True,
+                                 order=("image", "boxes", "boxes_category", "info")),
+                      TEST=dict(name="coco_2017_val", remove_images_without_annotations=False, order=("image", "info")),
+                      NUM_CLASSES=80, NUM_WORKERS=4, ENABLE_INFINITE_SAMPLER=True),
+            TRAINER=dict(EMA=dict(ENABLE=True)),
+            HOOKS=dict(BUILDER_NAME="YOLOXHookList"),
+            AUG=dict(TRAIN_VALUE=(),
+                     TRAIN_SETTING=dict(INPUT_SIZE=(640, 640), MULTISCALE_RANGE=(14, 26), SYNC_ITER=10, MOSAIC_PROB=1.0, MOSAIC_SCALE=(0.1, 2),
+                                        ENABLE_MIXUP=True, MIXUP_PROB=1.0, MIXUP_SCALE=(0.5, 1.5), HSV_PROB=1.0, FLIP_PROB=0.5, DEGREES=10.0,
+                                        TRANSLATE=0.1, SHEAR=2.0, NO_AUG_EPOCH=15),
+                     TRAIN_WRAPPER=(("MGE_Compose", dict(order=("image", "boxes", "boxes_category"))),)),
+            TEST=dict(CLS_THRESHOLD=0.001, IMG_MIN_SIZE=self.TEST_SIZE, IMG_MAX_SIZE=self.TEST_SIZE,
+                      AUG=dict(VALUE=(
+                          ("MGE_ShortestEdgeResize", dict(min_size=self.TEST_SIZE, max_size=self.TEST_SIZE, sample_style="choice")),
+                          ("PadToTargetSize", dict(target_size=(self.TEST_SIZE, self.TEST_SIZE), pad_value=114.0)),
+                          ("ToMode", dict(mode="NCHW")))))))
+        self.GLOBAL.LOG_INTERVAL = 10
+        del self.SOLVER["WARM_ITERS"]
+        self._override(cfg, kwargs)

@@ -1,6 +1,6 @@
 """Operator surface mirroring ``basedet.layers`` for the hot path (HIP kernels behind the same names)."""
 from .box_ops import (  # noqa: F401
-    DefaultAnchorGenerator, AnchorPointGenerator, Matcher, batched_nms, post_processing,
+    DefaultAnchorGenerator, AnchorPointGenerator, FastPointGenerator, Matcher, batched_nms, post_processing,
     post_process_with_empty_input, data_to_input, get_padded_tensor, get_multiple_size, permute_to_N_Any_K,
 )
 from .losses import (  # noqa: F401

@@ -82,6 +82,38 @@ class AnchorPointGenerator:
         return self.generate_anchors_by_features([tuple(f.shape[-2:]) for f in featmaps], featmaps[0].device)
 
 
+class FastPointGenerator:
+    """layers/common/anchor_generator.py:169-182 (YOLOX): per level the points (col * stride, row * stride) in row-major order of the
+    H x W map, no 0.5 offset.  The reference's meshgrid(arange(h), arange(w)) transposes non-square maps; on square maps the two agree.
+    `grid` is the host form (numpy: shapes are constants of a model), `__call__` fills device tensors with bd_points_generate."""
+
+    def __init__(self, strides=(8, 16, 32)):
+        self.strides = tuple(strides)
+
+    def grid(self, sizes):
+        import numpy as np
+        assert len(sizes) == len(self.strides), "input features expected {}, got {}".format(len(self.strides), len(sizes))
+        out = []
+        for (h, w), s in zip(sizes, self.strides):
+            ys, xs = np.divmod(np.arange(h * w), w)
+            out.append(np.stack([xs * s, ys * s], 1).astype(np.float32))
+        return out
+
+    def level_starts(self, sizes):
+        starts = [0]
+        for h, w in sizes:
+            starts.append(starts[-1] + h * w)
+        return starts
+
+    def __call__(self, featmaps):
+        assert len(featmaps) == len(self.strides), "input features expected {}, got {}".format(len(self.strides), len(featmaps))
+        out = []
+        for f, s in zip(featmaps, self.strides):
+            h, w = (int(v) for v in f.shape[-2:])
+            out.append(ops.points_generate(h, w, int(s), 0.0, 1, torch.empty((h * w, 2), dtype=torch.float32, device=f.device)))
+        return out
+
+
 class Matcher:
     """layers/common/matcher.py:19-51.  `matcher(matrix)` with a (G, A) similarity matrix -> (match_indices, labels), any number of
     thresholds / labels (bd_matcher_matrix).  `match(gt_boxes, anchors)` is the fused form the training step uses: IoU, matching

@@ -1,0 +1,164 @@
+"""YOLOX behind the head's last convolutions, on the kernels of csrc/yolox.hip (models/det/yolox.py:119-135, 150-408 of the reference):
+the SimOTA assignment (`yolox_assignments`), the four losses with gradients back to the head outputs (`yolox_losses`) and the inference
+chain (`yolox_inference`: bd_det_select -> bd_yolox_candidates -> bd_nms_batched -> bd_det_finalize).  The model class, CSPDarknet /
+YOLOPAFPN, the decoupled head and the mosaic input are not built yet; what is here is what they will call.
+
+The kernels read the layout a fused head will write -- cls bf16 (N*P, round_up(K, 8)) and box_obj bf16 (N*P, 8): raw reg 0-3, obj logit
+4 -- with the P points of an image level after level, row-major inside a level.  `yolox_losses` and `yolox_inference` take the
+reference's three per-level NCHW fp32 lists and pack them into that layout on the way in (one rounding to bf16); a model step hands the
+head's output to basedet_amd.ops directly.  Tensors live on the HIP device: host tensors raise BasedetHipError, there is no CPU path.
+
+One departure from the reference: the gt is xyxy everywhere, and both IoUs are between the gt box and the predicted box."""
+import torch
+
+from basedet_amd import ops
+from basedet_amd._lib import BasedetHipError
+from basedet_amd.layers.box_ops import FastPointGenerator
+
+__all__ = ["yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs"]
+
+
+def _dev(*tensors):
+    for t in tensors:
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise BasedetHipError("basedet_amd.models.yolox needs tensors on a HIP device; there is no CPU fallback")
+
+
+def _ld(K):
+    return (K + 7) // 8 * 8
+
+
+def _check_levels(logits, offsets, objs, strides):
+    if not (len(logits) == len(offsets) == len(objs) == len(strides)) or not logits:
+        raise ValueError("yolox: logits, offsets, objs and strides must be lists of one length, one entry per level")
+    if len(strides) > ops._lib.BD_MAX_SEGS:
+        raise ValueError(f"yolox: at most {ops._lib.BD_MAX_SEGS} levels")
+    for x, o, b in zip(logits, offsets, objs):
+        if x.dim() != 4 or o.dim() != 4 or b.dim() != 4 or o.shape[1] != 4 or b.shape[1] != 1 or x.shape[1] != logits[0].shape[1]:
+            raise ValueError("yolox: per level logits (N, K, H, W), offsets (N, 4, H, W) and objs (N, 1, H, W)")
+        if x.shape[0] != logits[0].shape[0] or x.shape[2:] != o.shape[2:] or x.shape[2:] != b.shape[2:] or o.shape[0] != x.shape[0] or b.shape[0] != x.shape[0]:
+            raise ValueError("yolox: the three outputs of a level must share N, H and W")
+
+
+def pack_head_outputs(logits, offsets, objs):
+    """The reference's per-level NCHW lists -> (cls bf16 (N*P, round_up(K, 8)), box_obj bf16 (N*P, 8), sizes [(H, W)]); pad slots zero."""
+    N, K = int(logits[0].shape[0]), int(logits[0].shape[1])
+    sizes = [(int(x.shape[2]), int(x.shape[3])) for x in logits]
+    P = sum(h * w for h, w in sizes)
+    dev = logits[0].device
+    cls = torch.zeros((N, P, _ld(K)), dtype=torch.bfloat16, device=dev)
+    box_obj = torch.zeros((N, P, 8), dtype=torch.bfloat16, device=dev)
+    p0 = 0
+    for x, o, b, (h, w) in zip(logits, offsets, objs, sizes):
+        cls[:, p0:p0 + h * w, :K] = x.permute(0, 2, 3, 1).reshape(N, h * w, K)
+        box_obj[:, p0:p0 + h * w, :4] = o.permute(0, 2, 3, 1).reshape(N, h * w, 4)
+        box_obj[:, p0:p0 + h * w, 4] = b.reshape(N, h * w)
+        p0 += h * w
+    return cls.view(N * P, -1), box_obj.view(N * P, 8), sizes
+
+
+def _unpack(d_cls, d_box_obj, N, K, sizes, dtype):
+    P = sum(h * w for h, w in sizes)
+    dc, db = d_cls.view(N, P, -1), d_box_obj.view(N, P, 8)
+    gl, go, gb = [], [], []
+    p0 = 0
+    for h, w in sizes:
+        gl.append(dc[:, p0:p0 + h * w, :K].to(dtype).reshape(N, h, w, K).permute(0, 3, 1, 2))
+        go.append(db[:, p0:p0 + h * w, :4].to(dtype).reshape(N, h, w, 4).permute(0, 3, 1, 2))
+        gb.append(db[:, p0:p0 + h * w, 4:5].to(dtype).reshape(N, h, w, 1).permute(0, 3, 1, 2))
+        p0 += h * w
+    return gl, go, gb
+
+
+def _points(sizes, strides, device):
+    gen = FastPointGenerator(strides)
+    pts = torch.cat(gen([torch.empty((1, 1, h, w), device=device) for h, w in sizes]), 0)
+    return pts, gen.level_starts(sizes)
+
+
+def yolox_assignments(cls, box_obj, points, strides, gt_boxes, num_gt, K=None, lvl_start=None):
+    """get_assignments for a batch (yolox.py:296-408): cls bf16 (N*P, round_up(K, 8)), box_obj bf16 (N*P, 8), points fp32 (P, 2) or the
+    per-level list FastPointGenerator returns, gt_boxes fp32 (N, Gmax, 5) xyxy + 1-based label, num_gt int32 (N,) -> (matched int32
+    (N, P): gt index or -1, iou_t fp32 (N, P): pred_ious_this_matching, stats fp32 (1,): the foreground count).  K defaults to the row
+    width of cls; lvl_start is needed only when points is one tensor."""
+    if isinstance(points, (list, tuple)):
+        lvl_start = [0]
+        for p in points:
+            lvl_start.append(lvl_start[-1] + int(p.shape[0]))
+        points = torch.cat(list(points), 0)
+    if lvl_start is None:
+        raise ValueError("yolox_assignments: points given as one tensor need lvl_start")
+    _dev(cls, box_obj, points, gt_boxes, num_gt)
+    K = int(cls.shape[1]) if K is None else int(K)
+    return ops.yolox_assign(cls, K, box_obj, points.float().contiguous(), lvl_start, list(strides), gt_boxes.float().contiguous(),
+                            num_gt.to(torch.int32).contiguous())
+
+
+class _Losses(torch.autograd.Function):
+    """total_loss and its four parts from one assignment and one loss launch; the kernel's gradient of the total is what backward hands
+    out (times the incoming gradient)."""
+
+    @staticmethod
+    def forward(ctx, gt_boxes, num_gt, strides, use_l1, nlev, *heads):
+        logits, offsets, objs = heads[:nlev], heads[nlev:2 * nlev], heads[2 * nlev:]
+        N, K = int(logits[0].shape[0]), int(logits[0].shape[1])
+        cls, box_obj, sizes = pack_head_outputs(logits, offsets, objs)
+        points, lvl_start = _points(sizes, strides, cls.device)
+        gt = gt_boxes.float().contiguous()
+        matched, iou_t, stats = ops.yolox_assign(cls, K, box_obj, points, lvl_start, list(strides), gt, num_gt.to(torch.int32).contiguous())
+        parts, d_cls, d_box_obj = ops.yolox_loss_fwd_bwd(cls, K, box_obj, points, lvl_start, list(strides), gt, matched, iou_t, stats,
+                                                        use_l1=use_l1, grad_scale=1.0)
+        gl, go, gb = _unpack(d_cls, d_box_obj, N, K, sizes, logits[0].dtype)
+        ctx.save_for_backward(*gl, *go, *gb)
+        ctx.mark_non_differentiable(parts)
+        return parts.sum(), parts
+
+    @staticmethod
+    def backward(ctx, gout, _gparts):
+        return (None, None, None, None, None, *[g * gout for g in ctx.saved_tensors])
+
+
+def yolox_losses(logits, offsets, objs, gt_boxes, num_gt, strides, use_l1=False):
+    """YOLOX.get_losses behind network_forward (yolox.py:155-265): the reference's three per-level NCHW lists, gt_boxes (N, Gmax, 5) and
+    num_gt (N,) -> {total_loss, iou_loss (times 5), l1_loss, obj_loss, cls_loss}.  total_loss carries the gradient to the inputs."""
+    _check_levels(logits, offsets, objs, strides)
+    _dev(*logits, *offsets, *objs, gt_boxes, num_gt)
+    total, parts = _Losses.apply(gt_boxes, num_gt, tuple(int(s) for s in strides), bool(use_l1), len(logits), *logits, *offsets, *objs)
+    return {"total_loss": total, "iou_loss": parts[0], "l1_loss": parts[3], "obj_loss": parts[1], "cls_loss": parts[2]}
+
+
+def yolox_inference(logits, offsets, objs, img_info, cfg, strides=(8, 16, 32), k=1000):
+    """YOLOX.inference behind network_forward (yolox.py:112-148) for a batch: per image and level score = sqrt(sigmoid(cls) sigmoid(obj))
+    > TEST.CLS_THRESHOLD -> top-k -> decode -> batched NMS by label (TEST.IOU_THRESHOLD) -> the first TEST.MAX_BOXES_PER_IMAGE, scaled
+    and clipped by the image's img_info row (h, w, original h, original w).  Returns the list of per-image Containers (boxes,
+    box_scores, box_labels)."""
+    from ..structures import Boxes, Container
+    _check_levels(logits, offsets, objs, strides)
+    _dev(*logits, *offsets, *objs, img_info)
+    t = cfg.TEST
+    B, K = int(logits[0].shape[0]), int(logits[0].shape[1])
+    cls, box_obj, sizes = pack_head_outputs(logits, offsets, objs)
+    dev = cls.device
+    points, lvl_start = _points(sizes, strides, dev)
+    Ln, P = len(sizes), lvl_start[-1]
+    lvl_rows = [h * w for h, w in sizes]
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    tk_idx, tk_sc, tk_cnt = torch.empty((B, Ln, k), **i32), torch.empty((B, Ln, k), **f32), torch.empty((B, Ln), **i32)
+    ws = torch.empty((ops.det_select_workspace_bytes(B, Ln, P, K, k),), dtype=torch.uint8, device=dev)
+    ops.det_select(cls, B, P, K, lvl_start[:-1], lvl_rows, k, t.CLS_THRESHOLD, tk_idx, tk_sc, tk_cnt, ws, ctr=box_obj, ctr_ld=8, ctr_off=4,
+                   ld=_ld(K))
+    boxes, scores, labels = ops.yolox_candidates(tk_idx, tk_sc, tk_cnt, K, points, lvl_start, list(strides), box_obj)
+    max_out = int(t.MAX_BOXES_PER_IMAGE)
+    keep, num = torch.empty((B, max_out), **i32), torch.zeros((B,), **i32)
+    nms_ws = torch.empty((ops.nms_batched_workspace_bytes(B, Ln * k),), dtype=torch.uint8, device=dev)
+    ops.nms_batched(boxes, scores, labels, t.IOU_THRESHOLD, max_out, keep, num, nms_ws)
+    ob, osc, ol = torch.empty((B, max_out, 4), **f32), torch.empty((B, max_out), **f32), torch.empty((B, max_out), **i32)
+    ops.det_finalize(boxes, scores, labels, keep, num, max_out, img_info.float().contiguous(), ob, osc, ol)
+    outs = []
+    for i, n in enumerate(num.tolist()):
+        if n == 0:
+            e = torch.zeros((0,))
+            outs.append(Container(boxes=e, box_scores=e, box_labels=e))
+        else:
+            outs.append(Container(boxes=Boxes(ob[i, :n]), box_scores=osc[i, :n], box_labels=ol[i, :n]))
+    return outs

@@ -1198,3 +1198,81 @@ def center_head_out_bwd(feat, d_logits, d_wr, w_cls, w_wh, w_reg, M, C, K, d_fea
                                      ptr(db_reg), int(accumulate), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
           "bd_center_head_out_bwd")
     return d_feat
+
+
+# ---- YOLOX behind the head's last convolutions (yolox.hip) -----------------------------------------------------------------------------------
+def yolox_assign_workspace_bytes(N, P):
+    return int(L().bd_yolox_assign_workspace_bytes(N, P))
+
+
+def yolox_loss_workspace_bytes():
+    return int(L().bd_yolox_loss_workspace_bytes())
+
+
+def _yolox_dims(cls, box_obj, points, gt_boxes):
+    P, (N, Gmax) = int(points.shape[0]), (int(gt_boxes.shape[0]), int(gt_boxes.shape[1]))
+    if cls.dim() != 2 or box_obj.dim() != 2 or cls.shape[0] != N * P or tuple(box_obj.shape) != (N * P, 8):
+        raise ValueError(f"yolox: cls must be (N*P, ld) and box_obj (N*P, 8) with N*P = {N * P}; got {tuple(cls.shape)}, {tuple(box_obj.shape)}")
+    return N, P, Gmax
+
+
+def yolox_assign_into(cls, K, box_obj, points, lvl_start, strides, gt_boxes, num_gt, matched, iou_t, stats, ws):
+    """bd_yolox_assign: cls bf16 (N*P, round_up(K, 8)), box_obj bf16 (N*P, 8), points fp32 (P, 2), gt_boxes fp32 (N, Gmax, 5), num_gt int32
+    (N,) -> matched int32 (N, P) (gt index, -1 = background), iou_t fp32 (N, P), stats[0] = the foreground count."""
+    N, P, Gmax = _yolox_dims(cls, box_obj, points, gt_boxes)
+    check(L().bd_yolox_assign(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(cls), int(K), int(cls.shape[1]),
+                              ptr(box_obj), ptr(gt_boxes), ptr(num_gt), N, Gmax, ptr(matched), ptr(iou_t), ptr(stats), ptr(ws),
+                              ws.numel() * ws.element_size(), stream_ptr()), "bd_yolox_assign")
+
+
+def yolox_assign(cls, K, box_obj, points, lvl_start, strides, gt_boxes, num_gt):
+    """yolox_assign_into with its outputs and workspace allocated here: (matched, iou_t, stats)."""
+    N, P, _ = _yolox_dims(cls, box_obj, points, gt_boxes)
+    dev = cls.device
+    matched = torch.empty((N, P), dtype=torch.int32, device=dev)
+    iou_t = torch.empty((N, P), dtype=torch.float32, device=dev)
+    stats = torch.zeros(1, dtype=torch.float32, device=dev)
+    ws = torch.empty(yolox_assign_workspace_bytes(N, P), dtype=torch.uint8, device=dev)
+    yolox_assign_into(cls, K, box_obj, points, lvl_start, strides, gt_boxes, num_gt, matched, iou_t, stats, ws)
+    return matched, iou_t, stats
+
+
+def yolox_loss_fwd_bwd_into(cls, K, box_obj, points, lvl_start, strides, gt_boxes, matched, iou_t, stats, use_l1, grad_scale, loss_out,
+                            d_cls, d_box_obj, ws):
+    """bd_yolox_loss_fwd_bwd: loss_out fp32 (4,) = (5 * iou, obj, cls, l1) and the gradients of their sum times grad_scale, d_cls /
+    d_box_obj bf16 in the input layouts (written completely)."""
+    N, P, Gmax = _yolox_dims(cls, box_obj, points, gt_boxes)
+    check(L().bd_yolox_loss_fwd_bwd(ptr(points), P, i32arr(lvl_start), i32arr(strides), len(strides), ptr(cls), int(K), int(cls.shape[1]),
+                                    ptr(box_obj), ptr(gt_boxes), N, Gmax, ptr(matched), ptr(iou_t), ptr(stats), int(bool(use_l1)),
+                                    float(grad_scale), ptr(loss_out), ptr(d_cls), ptr(d_box_obj), ptr(ws),
+                                    ws.numel() * ws.element_size(), stream_ptr()), "bd_yolox_loss_fwd_bwd")
+
+
+def yolox_loss_fwd_bwd(cls, K, box_obj, points, lvl_start, strides, gt_boxes, matched, iou_t, stats, use_l1=False, grad_scale=1.0):
+    """yolox_loss_fwd_bwd_into with its outputs and workspace allocated here: (loss_out, d_cls, d_box_obj)."""
+    dev = cls.device
+    loss_out = torch.empty(4, dtype=torch.float32, device=dev)
+    d_cls, d_box_obj = torch.empty_like(cls), torch.empty_like(box_obj)
+    ws = torch.empty(yolox_loss_workspace_bytes(), dtype=torch.uint8, device=dev)
+    yolox_loss_fwd_bwd_into(cls, K, box_obj, points, lvl_start, strides, gt_boxes, matched, iou_t, stats, use_l1, grad_scale, loss_out,
+                            d_cls, d_box_obj, ws)
+    return loss_out, d_cls, d_box_obj
+
+
+def yolox_candidates_into(topk_idx, topk_score, topk_cnt, K, points, lvl_start, strides, box_obj, boxes, scores, labels):
+    """bd_yolox_candidates: the (B, L, k) output of det_select -> boxes fp32 (B, L*k, 4), scores (B, L*k), labels int32 (B, L*k)."""
+    B, Ln, k = (int(s) for s in topk_idx.shape)
+    check(L().bd_yolox_candidates(ptr(topk_idx), ptr(topk_score), ptr(topk_cnt), B, Ln, k, i32arr(lvl_start), i32arr(strides), int(K),
+                                  ptr(points), int(points.shape[0]), ptr(box_obj), ptr(boxes), ptr(scores), ptr(labels), stream_ptr()),
+          "bd_yolox_candidates")
+
+
+def yolox_candidates(topk_idx, topk_score, topk_cnt, K, points, lvl_start, strides, box_obj):
+    """yolox_candidates_into with its outputs allocated here: (boxes, scores, labels)."""
+    B, Ln, k = (int(s) for s in topk_idx.shape)
+    dev = topk_idx.device
+    boxes = torch.empty((B, Ln * k, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, Ln * k), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, Ln * k), dtype=torch.int32, device=dev)
+    yolox_candidates_into(topk_idx, topk_score, topk_cnt, K, points, lvl_start, strides, box_obj, boxes, scores, labels)
+    return boxes, scores, labels

@@ -964,6 +964,66 @@ int bd_centernet_decode(const void* logits, int ld, const void* wh, int wh_ld, i
 int bd_centernet_boxes_to_image(const float* boxes, const float* affine, const float* scores, const int32_t* classes, int B, int k,
                                 float* boxes_out, float* scores_out, int32_t* labels_out, bd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * YOLOX behind the head's last convolutions (yolox.hip; models/det/yolox.py:119-135, 150-408): SimOTA assignment, the four losses with
+ * gradients, the inference decode.  The entries are additions: bd_version() stays 118, a library without them fails to load in the
+ * binding by name.  Common layout, whole batches, no host synchronisation, fp32 arithmetic, bitwise reproducible outputs (fixed-order
+ * sums, integer atomics only):
+ *   cls      bf16 [N*P][ld], ld = K rounded up to a multiple of 8; slots >= K are padding: never read by a cost or loss, gradient +0
+ *   box_obj  bf16 [N*P][8]: slots 0-3 the raw reg_preds output, slot 4 the obj_preds logit, slots 5-7 padding (gradient +0)
+ *   points   fp32 [P][2] = (col * stride, row * stride), row-major per level, no 0.5 offset; lvl_start_host [L + 1] rises from 0 to P,
+ *            strides_host [L], L <= BD_MAX_SEGS
+ *   gt_boxes fp32 [N][Gmax][5] = x1, y1, x2, y2, 1-based label; num_gt int32 [N] (clamped to 0..Gmax)
+ * Decode (yolox.py:162-164): xc = raw0 * stride + px, yc = raw1 * stride + py, w = stride * exp(raw2), h = stride * exp(raw3).
+ * The gt is xyxy everywhere: the reference reads it as xyxy in get_in_boxes_info / get_l1_target and as xc,yc,w,h in tlbr_iou /
+ * iou_loss (the conversion of the original YOLOX was lost); both IoUs here are between the gt box and the predicted box.
+ * Every entry returns BD_EINVAL before any launch for ld not K rounded up to a multiple of 8, L outside 1..BD_MAX_SEGS, a workspace that
+ * is too small, a null pointer, or operands that are not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* get_assignments + get_in_boxes_info + dynamic_k_matching (yolox.py:296-408).  Candidates of an image: points strictly inside some gt
+ * (min(px - x1, py - y1, x2 - px, y2 - py) > 0) or strictly within 2.5 * stride of some gt's centre in x and y (the centre box is not
+ * clipped to the gt).  iou(g, p) = tlbr_iou between the gt and the decoded prediction (strict tl < br mask, no epsilon).
+ * cost(g, p) = sum_k BCE(s_k, onehot_g) + 3 * -log(iou + 1e-8) + 1e5 * [p not inside both g's box and g's centre box],
+ * s_k = sqrt(sigmoid(cls_k) * sigmoid(obj)); the class sum is evaluated as (S_bg(p) - bce0(s_c)) + bce1(s_c) with the per-point
+ * S_bg = sum_k bce0(s_k); log(s) and 1 - s are formed from sigmoid(-x) without cancellation and the argument of log(1 - s) is clamped
+ * at 1e-30, so the cost is finite at any logit.  A label outside 1..K matches no class column.  k_g = max(1, int(sum of the min(10, C)
+ * largest IoUs of g over the image's C candidates)); g takes its k_g candidates of smallest cost; a point taken by several gts goes to
+ * the gt of smallest cost over all gts of the image.  Ties: lowest point / gt index.  Images with num_gt == 0 or without a candidate
+ * have no foreground.  matched int32 [N][P] (gt index, -1 = background), iou_t fp32 [N][P] (pred_ious_this_matching, 0 on background),
+ * stats[0] = the number of foreground points.  ws: bd_yolox_assign_workspace_bytes(N, P), 16-byte aligned. */
+size_t bd_yolox_assign_workspace_bytes(int N, int P);
+int bd_yolox_assign(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L, const void* cls, int K,
+                    int ld, const void* box_obj, const float* gt_boxes, const int32_t* num_gt, int N, int Gmax, int32_t* matched,
+                    float* iou_t, float* stats, void* ws, size_t ws_bytes, bd_stream_t stream);
+
+/* The losses of yolox.py:225-265 and their gradients with respect to cls and box_obj, from matched / iou_t / stats as bd_yolox_assign
+ * wrote them (a matched index outside 0..Gmax-1 is background).  nf = max(stats[0], 1), read on the device.
+ *   loss_out[0] = 5 * sum_fg (1 - iou^2) / nf, iou = box_iou (structures/op_patch.py:36-76: clamped intersection, max(iou, 0)) between
+ *                 the decoded prediction and the matched gt; its gradient is chained through the decode
+ *                 (d raw_xy = stride * d xc, d raw_wh = w * d w)
+ *   loss_out[1] = sum_all BCEWithLogits(obj, [fg]) / nf
+ *   loss_out[2] = sum_fg sum_k BCEWithLogits(cls_k, iou_t * onehot) / nf (iou_t a constant)
+ *   loss_out[3] = use_l1 ? sum_fg |raw - l1_target| / nf : 0, l1_target = ((x1+x2)/2 - p) / stride, log((x2-x1) / stride + 1e-8)
+ * d_cls bf16 [N*P][ld] and d_box_obj bf16 [N*P][8] are written completely: grad_scale * d(loss_out[0] + .. + loss_out[3]) / d input;
+ * background rows of d_cls, every pad slot and slots 5-7 hold +0.  At the kinks the kernel takes torch.autograd's side: a min / max tie
+ * sends half the gradient to each argument, max(., 0) passes the gradient where its argument is >= 0, |x| has derivative 0 at 0.
+ * ws: bd_yolox_loss_workspace_bytes() (per-workgroup partial sums, added in workgroup order), 16-byte aligned. */
+size_t bd_yolox_loss_workspace_bytes(void);
+int bd_yolox_loss_fwd_bwd(const float* points, int P, const int32_t* lvl_start_host, const int32_t* strides_host, int L, const void* cls,
+                          int K, int ld, const void* box_obj, const float* gt_boxes, int N, int Gmax, const int32_t* matched,
+                          const float* iou_t, const float* stats, int use_l1, float grad_scale, float* loss_out, void* d_cls,
+                          void* d_box_obj, void* ws, size_t ws_bytes, bd_stream_t stream);
+
+/* The inference decode (yolox.py:119-135): bd_det_candidates mode 1 with YOLOX's decode in place of PointCoder.decode.  topk_idx /
+ * topk_score [B][L][k] and topk_cnt [B][L] as bd_det_select wrote them (called with ctr = box_obj, ctr_ld = 8, ctr_off = 4, k = 1000,
+ * min_score = TEST.CLS_THRESHOLD): item i of level l -> label = i % K, point = lvl_start[l] + i / K; box = (xc - w/2, yc - h/2,
+ * xc + w/2, yc + h/2) of the decode above.  box_obj bf16 [B*P][8].  Outputs [B][L*k] (zero box, score -inf, label 0 past the
+ * per-level count): the layout bd_nms_batched takes; bd_nms_batched and bd_det_finalize follow unchanged. */
+int bd_yolox_candidates(const int32_t* topk_idx, const float* topk_score, const int32_t* topk_cnt, int B, int L, int k,
+                        const int32_t* lvl_start_host, const int32_t* strides_host, int K, const float* points, int P, const void* box_obj,
+                        float* boxes, float* scores, int32_t* labels, bd_stream_t stream);
+
 /* The output convolutions of CenterHead (bd_version() >= 116; center_head.hip; layers/head/center_head.py:91-131: the three
  * SingleHead.out_conv, 1x1, C -> K / 2 / 2) in one launch per direction.  feat: bf16 [M][3C], the ReLU output of the three feat_convs
  * run as one 3C-row convolution -- channels [0,C) the cls tower, [C,2C) the wh tower, [2C,3C) the reg tower.  w_cls [K][C], w_wh [2][C],
