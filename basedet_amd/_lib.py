@@ -163,6 +163,10 @@ SIGNATURES = {
     "bd_bn_apply_act_fwd": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _I, _L, _I, _I, _P]),
     "bd_bn_bwd_reduce": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _I, _L, _I, _P, _P, _P, _Z, _P]),
     "bd_bn_bwd_apply": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _I, _P]),
+    # conv -> BN -> SiLU (added without an ABI break, as the bd_yolox_* entries were)
+    "bd_bn_silu_fwd": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _I, _L, _I, _P]),
+    "bd_bn_silu_bwd_reduce": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _I, _L, _I, _P, _P, _P, _Z, _P]),
+    "bd_bn_silu_bwd_apply": (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _I, _P]),
     "bd_fcos_offsets_fwd": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _L, _P, _P]),
     "bd_fcos_offsets_workspace_bytes": (_Z, []),
     "bd_fcos_offsets_bwd": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _Z, _P]),

@@ -244,6 +244,156 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_raw* __res
     }
 }
 
+// ---- conv -> BatchNorm -> SiLU (YOLOX: every convolution of the head, the PAFPN and CSPDarknet) --------------------------------------
+// SiLU's derivative is a function of the activation input u = gamma * xhat + beta alone, and u follows from the pre-norm y the norm's
+// backward reads anyway: the gate folds into the reduce and the apply pass (five tensor passes instead of the ReLU chain's seven, no gated
+// gradient tensor, the forward output z is not kept).  ONE device function forms u for the three kernels, exactly as
+// bn_apply_act_fwd_kernel does: fp64 on the fp32 statistics, one rounding to fp32.
+__device__ __forceinline__ double bn_silu_u64(float y, float mu, double A, float bt) { return ((double)y - (double)mu) * A + (double)bt; }
+__device__ __forceinline__ float bn_silu_u(float y, float mu, double A, float bt) { return (float)bn_silu_u64(y, mu, A, bt); }
+
+// s = sigma(u), sm = sigma(-u), both from e = exp(-|u|) <= 1: nothing overflows at |u| ~ 100, and 1 - sigma(u) is never a subtraction
+__device__ __forceinline__ void bn_sigmoid_pair(float u, float& s, float& sm) {
+    const float e = expf(-fabsf(u));
+    const float r = 1.f / (1.f + e);
+    const float big = r, small = e * r;          // sigma(|u|), sigma(-|u|)
+    s = u >= 0.f ? big : small;
+    sm = u >= 0.f ? small : big;
+}
+
+__device__ __forceinline__ float bn_silu(float u) {
+    float s, sm;
+    bn_sigmoid_pair(u, s, sm);
+    return u * s;
+}
+
+// d silu / du = sigma(u) (1 + u sigma(-u)); exactly 1 where sigma(u) and 1 + u sigma(-u) round to 1 (u > ~ 21), exactly 0 where exp(u) underflows
+__device__ __forceinline__ float bn_silu_grad(float u) {
+    float s, sm;
+    bn_sigmoid_pair(u, s, sm);
+    return s * (1.f + u * sm);
+}
+
+// The same derivative in fp64 on the UNROUNDED u, for the backward apply: there g_u meets -B - (y - mean) E, and where the three cancel an
+// fp32 gate (relative error ~ 1e-7 of g_u) is off by several bf16 steps of the small result (measured: 21 steps at 129 x 264, 3 at
+// 1030 x 24) -- the reason bn_bwd_apply_kernel is fp64 throughout.  Exactly 1 where exp(-u) and u exp(-u) vanish against 1 (u > ~ 40).
+__device__ __forceinline__ double bn_silu_grad64(double u) {
+    const double e = exp(-fabs(u));
+    const double r = 1.0 / (1.0 + e);
+    const double big = r, small = e * r;
+    const double s = u >= 0.0 ? big : small, sm = u >= 0.0 ? small : big;
+    return s * (1.0 + u * sm);
+}
+
+// z = silu(u): bn_apply_act_fwd_kernel's layout; SiLU in fp32, one rounding to bf16
+__global__ __launch_bounds__(256) void bn_silu_fwd_kernel(const bf16_raw* __restrict__ y, BnGeo gy, const float* __restrict__ mean,
+                                                          const float* __restrict__ inv_std, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, bf16_raw* __restrict__ z, BnGeo gz, long long n,
+                                                          long long M, int C) {
+    const int cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
+    const int c0 = (blockIdx.y * 32 + cl) * 8;
+    if (c0 >= C) return;
+    double A[8];
+    float mu[8], bt[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { A[k] = (double)gamma[c0 + k] * (double)inv_std[c0 + k]; mu[k] = mean[c0 + k]; bt[k] = beta[c0 + k]; }
+    for (long long r = (long long)blockIdx.x * BN_PXL + pl; r < M; r += (long long)gridDim.x * BN_PXL) {
+        float v[8], o[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(y + bn_row_addr(r, n, gy) * C + c0), v);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = bn_silu(bn_silu_u(v[k], mu[k], A[k], bt[k]));
+        u32x4_t w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = pack_bf2(o[2 * k], o[2 * k + 1]);
+        *reinterpret_cast<u32x4_t*>(z + bn_row_addr(r, n, gz) * C + c0) = w;
+    }
+}
+
+// stage 1 of the SiLU backward sums: bn_bwd_partial_kernel on g_u = g * silu'(u); part[(slot * C + c) * 2] = (sum g_u * xhat, sum g_u).
+// Stage 2 is bn_bwd_final_kernel.
+__global__ __launch_bounds__(256) void bn_silu_bwd_partial_kernel(const bf16_raw* __restrict__ g, BnGeo gg, const bf16_raw* __restrict__ y,
+                                                                  BnGeo gy, const float* __restrict__ mean, const float* __restrict__ inv_std,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta, long long n,
+                                                                  long long M, int C, float* __restrict__ part) {
+    __shared__ float red[BN_PXL][32][8][2];
+    const int cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
+    const int c0 = (blockIdx.y * 32 + cl) * 8;
+    const long long r0 = (long long)blockIdx.x * BN_SLOT;
+    long long r1 = r0 + BN_SLOT;
+    if (r1 > M) r1 = M;
+    float dg[8], db[8], mu[8], rs[8], bt[8];
+    double A[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { dg[k] = 0.f; db[k] = 0.f; mu[k] = 0.f; rs[k] = 0.f; bt[k] = 0.f; A[k] = 0.0; }
+    if (c0 < C) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            mu[k] = mean[c0 + k]; rs[k] = inv_std[c0 + k]; bt[k] = beta[c0 + k];
+            A[k] = (double)gamma[c0 + k] * (double)rs[k];
+        }
+        for (long long r = r0 + pl; r < r1; r += BN_PXL) {
+            float vg[8], vy[8];
+            unpack8(*reinterpret_cast<const u32x4_t*>(g + bn_row_addr(r, n, gg) * C + c0), vg);
+            unpack8(*reinterpret_cast<const u32x4_t*>(y + bn_row_addr(r, n, gy) * C + c0), vy);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float gu = vg[k] * bn_silu_grad(bn_silu_u(vy[k], mu[k], A[k], bt[k]));
+                dg[k] = __fmaf_rn(gu, (vy[k] - mu[k]) * rs[k], dg[k]);
+                db[k] += gu;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { red[pl][cl][k][0] = dg[k]; red[pl][cl][k][1] = db[k]; }
+    __syncthreads();
+    if (pl == 0 && c0 < C) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float a = red[0][cl][k][0], b = red[0][cl][k][1];
+            for (int q = 1; q < BN_PXL; ++q) { a += red[q][cl][k][0]; b += red[q][cl][k][1]; }
+            float* o = part + ((long long)blockIdx.x * C + c0 + k) * 2;
+            o[0] = a; o[1] = b;
+        }
+    }
+}
+
+// g_y = A * (g_u - B - (y - mean) * E): bn_bwd_apply_kernel with g_u = g * silu'(u) recomputed (fp64, see bn_silu_grad64) in place of g
+__global__ __launch_bounds__(256) void bn_silu_bwd_apply_kernel(const bf16_raw* __restrict__ g, BnGeo gg, const bf16_raw* __restrict__ y, BnGeo gy,
+                                                                const float* __restrict__ mean, const float* __restrict__ inv_std,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                const float* __restrict__ dgamma, const float* __restrict__ dbeta,
+                                                                const float* __restrict__ count, bf16_raw* __restrict__ out, BnGeo go,
+                                                                long long n, long long M, int C) {
+    const int cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
+    const int c0 = (blockIdx.y * 32 + cl) * 8;
+    if (c0 >= C) return;
+    double A[8], B[8], E[8];
+    float mu[8], bt[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const double rs = (double)inv_std[c0 + k], m = (double)count[c0 + k];
+        A[k] = (double)gamma[c0 + k] * rs;
+        B[k] = (double)dbeta[c0 + k] / m;
+        E[k] = rs * ((double)dgamma[c0 + k] / m);
+        mu[k] = mean[c0 + k];
+        bt[k] = beta[c0 + k];
+    }
+    for (long long r = (long long)blockIdx.x * BN_PXL + pl; r < M; r += (long long)gridDim.x * BN_PXL) {
+        float vg[8], vy[8], o[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(g + bn_row_addr(r, n, gg) * C + c0), vg);
+        unpack8(*reinterpret_cast<const u32x4_t*>(y + bn_row_addr(r, n, gy) * C + c0), vy);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const double gu = (double)vg[k] * bn_silu_grad64(bn_silu_u64(vy[k], mu[k], A[k], bt[k]));
+            o[k] = (float)(A[k] * (gu - B[k] - ((double)vy[k] - (double)mu[k]) * E[k]));
+        }
+        u32x4_t w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = pack_bf2(o[2 * k], o[2 * k + 1]);
+        *reinterpret_cast<u32x4_t*>(out + bn_row_addr(r, n, go) * C + c0) = w;
+    }
+}
+
 inline bool bn_geo_ok(int64_t ppi, int64_t off, int64_t n) { return off >= 0 && n >= 1 && off + n <= ppi; }
 inline int bn_slots(int64_t M) { return (int)cdiv64(M, BN_SLOT); }
 // blocks along the rows of an apply launch: four rows per thread until the cap (the grid-stride loop takes the rest)
@@ -322,5 +472,51 @@ extern "C" int bd_bn_bwd_apply(const void* g, int64_t g_pix_per_img, int64_t g_o
                        BnGeo{g_pix_per_img, g_off}, (const bf16_raw*)y, BnGeo{y_pix_per_img, y_off}, mean, inv_std, gamma, dgamma, dbeta, count,
                        (bf16_raw*)gy, BnGeo{gy_pix_per_img, gy_off}, (long long)n, M, C);
     BD_CHECK_LAUNCH("bd_bn_bwd_apply");
+    return BD_OK;
+}
+
+extern "C" int bd_bn_silu_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
+                              const float* beta, void* z, int64_t z_pix_per_img, int64_t z_off, int N, int64_t n, int C, bd_stream_t stream) {
+    BD_REQUIRE(y && mean && inv_std && gamma && beta && z, "bn_silu_fwd: null pointer");
+    BD_REQUIRE(N >= 1 && C >= 8 && C % 8 == 0 && bn_geo_ok(y_pix_per_img, y_off, n) && bn_geo_ok(z_pix_per_img, z_off, n),
+               "bn_silu_fwd: bad shape (N=%d C=%d)", N, C);
+    BD_REQUIRE(z != y, "bn_silu_fwd: the backward pass reads the pre-norm tensor: z needs a buffer of its own");
+    const long long M = (long long)N * n;
+    hipLaunchKernelGGL(bn_silu_fwd_kernel, bn_apply_grid(M, C), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)y,
+                       BnGeo{y_pix_per_img, y_off}, mean, inv_std, gamma, beta, (bf16_raw*)z, BnGeo{z_pix_per_img, z_off}, (long long)n, M, C);
+    BD_CHECK_LAUNCH("bd_bn_silu_fwd");
+    return BD_OK;
+}
+
+extern "C" int bd_bn_silu_bwd_reduce(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
+                                     const float* mean, const float* inv_std, const float* gamma, const float* beta, int N, int64_t n, int C,
+                                     float* dgamma, float* dbeta, void* ws, size_t ws_bytes, bd_stream_t stream) {
+    BD_REQUIRE(g && y && mean && inv_std && gamma && beta && dgamma && dbeta && ws, "bn_silu_bwd_reduce: null pointer");
+    BD_REQUIRE(N >= 1 && C >= 8 && C % 8 == 0 && bn_geo_ok(g_pix_per_img, g_off, n) && bn_geo_ok(y_pix_per_img, y_off, n),
+               "bn_silu_bwd_reduce: bad shape (N=%d C=%d)", N, C);
+    const long long M = (long long)N * n;
+    if (ws_bytes < bd_bn_workspace_bytes(M, C)) { bd_set_error("bn_silu_bwd_reduce: workspace too small"); return BD_EWORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    const int S = bn_slots(M);
+    hipLaunchKernelGGL(bn_silu_bwd_partial_kernel, dim3(S, cdiv(C, 256)), dim3(256), 0, st, (const bf16_raw*)g, BnGeo{g_pix_per_img, g_off},
+                       (const bf16_raw*)y, BnGeo{y_pix_per_img, y_off}, mean, inv_std, gamma, beta, (long long)n, M, C, (float*)ws);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 8)), dim3(8 * BN_FL), 0, st, (const float*)ws, S, C, dgamma, dbeta);
+    BD_CHECK_LAUNCH("bd_bn_silu_bwd_reduce");
+    return BD_OK;
+}
+
+extern "C" int bd_bn_silu_bwd_apply(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
+                                    const float* mean, const float* inv_std, const float* gamma, const float* beta, const float* dgamma,
+                                    const float* dbeta, const float* count, void* gy, int64_t gy_pix_per_img, int64_t gy_off, int N, int64_t n,
+                                    int C, bd_stream_t stream) {
+    BD_REQUIRE(g && y && mean && inv_std && gamma && beta && dgamma && dbeta && count && gy, "bn_silu_bwd_apply: null pointer");
+    BD_REQUIRE(N >= 1 && C >= 8 && C % 8 == 0 && bn_geo_ok(g_pix_per_img, g_off, n) && bn_geo_ok(y_pix_per_img, y_off, n)
+               && bn_geo_ok(gy_pix_per_img, gy_off, n), "bn_silu_bwd_apply: bad shape (N=%d C=%d)", N, C);
+    BD_REQUIRE(gy != g && gy != y, "bn_silu_bwd_apply: the result needs a buffer of its own (a second tower may still read g; y is re-read per step)");
+    const long long M = (long long)N * n;
+    hipLaunchKernelGGL(bn_silu_bwd_apply_kernel, bn_apply_grid(M, C), dim3(256), 0, (hipStream_t)stream, (const bf16_raw*)g,
+                       BnGeo{g_pix_per_img, g_off}, (const bf16_raw*)y, BnGeo{y_pix_per_img, y_off}, mean, inv_std, gamma, beta, dgamma, dbeta,
+                       count, (bf16_raw*)gy, BnGeo{gy_pix_per_img, gy_off}, (long long)n, M, C);
+    BD_CHECK_LAUNCH("bd_bn_silu_bwd_apply");
     return BD_OK;
 }

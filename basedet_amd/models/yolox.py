@@ -1,7 +1,8 @@
 """YOLOX behind the head's last convolutions, on the kernels of csrc/yolox.hip (models/det/yolox.py:119-135, 150-408 of the reference):
 the SimOTA assignment (`yolox_assignments`), the four losses with gradients back to the head outputs (`yolox_losses`) and the inference
 chain (`yolox_inference`: bd_det_select -> bd_yolox_candidates -> bd_nms_batched -> bd_det_finalize).  The model class, CSPDarknet /
-YOLOPAFPN, the decoupled head and the mosaic input are not built yet; what is here is what they will call.
+YOLOPAFPN and the mosaic input are not built yet; what is here is what they will call.  The decoupled head is layers.YOLOXHead, and
+`yolox_head_step` runs it against the kernels here with no repack.
 
 The kernels read the layout a fused head will write -- cls bf16 (N*P, round_up(K, 8)) and box_obj bf16 (N*P, 8): raw reg 0-3, obj logit
 4 -- with the P points of an image level after level, row-major inside a level.  `yolox_losses` and `yolox_inference` take the
@@ -15,7 +16,7 @@ from basedet_amd import ops
 from basedet_amd._lib import BasedetHipError
 from basedet_amd.layers.box_ops import FastPointGenerator
 
-__all__ = ["yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs"]
+__all__ = ["yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs", "yolox_head_step"]
 
 
 def _dev(*tensors):
@@ -125,6 +126,21 @@ def yolox_losses(logits, offsets, objs, gt_boxes, num_gt, strides, use_l1=False)
     _dev(*logits, *offsets, *objs, gt_boxes, num_gt)
     total, parts = _Losses.apply(gt_boxes, num_gt, tuple(int(s) for s in strides), bool(use_l1), len(logits), *logits, *offsets, *objs)
     return {"total_loss": total, "iou_loss": parts[0], "l1_loss": parts[3], "obj_loss": parts[1], "cls_loss": parts[2]}
+
+
+def yolox_head_step(head, feats, N, sizes, gt_boxes, num_gt, strides, use_l1=False):
+    """One training step of a layers.YOLOXHead on its own layout, no repack: forward_pm -> ops.yolox_assign -> ops.yolox_loss_fwd_bwd ->
+    backward_pm.  feats: per level bf16 (N H_l W_l, C_l); sizes [(H_l, W_l)].  Returns (parts fp32 (4,) = 5 * iou, obj, cls, l1;
+    d_feats per level; (matched, iou_t, stats))."""
+    _dev(*feats, gt_boxes, num_gt)
+    cls, box_obj = head.forward_pm(feats, N, sizes)
+    points, lvl_start = _points(sizes, strides, cls.device)
+    gt = gt_boxes.float().contiguous()
+    K = head.num_classes
+    matched, iou_t, stats = ops.yolox_assign(cls, K, box_obj, points, lvl_start, list(strides), gt, num_gt.to(torch.int32).contiguous())
+    parts, d_cls, d_box_obj = ops.yolox_loss_fwd_bwd(cls, K, box_obj, points, lvl_start, list(strides), gt, matched, iou_t, stats,
+                                                    use_l1=use_l1, grad_scale=1.0)
+    return parts, head.backward_pm(d_cls, d_box_obj), (matched, iou_t, stats)
 
 
 def yolox_inference(logits, offsets, objs, img_info, cfg, strides=(8, 16, 32), k=1000):

@@ -934,6 +934,28 @@ def bn_bwd_apply(g, gg: Geom, y, gy: Geom, mean, inv_std, gamma, dgamma, dbeta, 
     return out
 
 
+def bn_silu_fwd(y, gy: Geom, mean, inv_std, gamma, beta, z, gz: Geom, Cn):
+    """z = silu(gamma * (y - mean) * inv_std + beta) in one pass: the epilogue of every YOLOX convolution (eval(): mean / inv_std are
+    running_mean and 1 / sqrt(running_var + eps))."""
+    check(L().bd_bn_silu_fwd(ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), ptr(z), *_lvl(gz), gy.N, gy.H[0] * gy.W[0],
+                             Cn, stream_ptr()), "bd_bn_silu_fwd")
+    return z
+
+
+def bn_silu_bwd_reduce(g, gg: Geom, y, gy: Geom, mean, inv_std, gamma, beta, Cn, dgamma, dbeta, ws):
+    """dgamma / dbeta of conv -> BN -> SiLU from the gradient of the SiLU OUTPUT: the gate is recomputed from the pre-norm y."""
+    check(L().bd_bn_silu_bwd_reduce(ptr(g), *_lvl(gg), ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), gy.N,
+                                    gy.H[0] * gy.W[0], Cn, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+          "bd_bn_silu_bwd_reduce")
+
+
+def bn_silu_bwd_apply(g, gg: Geom, y, gy: Geom, mean, inv_std, gamma, beta, dgamma, dbeta, count, out, go: Geom, Cn):
+    check(L().bd_bn_silu_bwd_apply(ptr(g), *_lvl(gg), ptr(y), *_lvl(gy), ptr(mean), ptr(inv_std), ptr(gamma), ptr(beta), ptr(dgamma),
+                                   ptr(dbeta), ptr(count), ptr(out), *_lvl(go), gy.N, gy.H[0] * gy.W[0], Cn, stream_ptr()),
+          "bd_bn_silu_bwd_apply")
+    return out
+
+
 def fcos_offsets_fwd(raw, ld, scales, geom: Geom, strides, out):
     off, cnt = _lvl_arrays(geom)
     check(L().bd_fcos_offsets_fwd(ptr(raw), ld, ptr(scales), geom.N, geom.nlev, off, cnt, i32arr(strides), geom.pix_per_img, ptr(out),

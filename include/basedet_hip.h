@@ -685,6 +685,29 @@ int bd_bn_bwd_reduce(const void* g, int64_t g_pix_per_img, int64_t g_off, const 
 int bd_bn_bwd_apply(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
                     const float* mean, const float* inv_std, const float* gamma, const float* dgamma, const float* dbeta, const float* count,
                     void* gy, int64_t gy_pix_per_img, int64_t gy_off, int N, int64_t n, int C, bd_stream_t stream);
+/* conv -> BatchNorm -> SiLU, the operator every YOLOX convolution ends in (layers/yolox_head.py; added without an ABI break: bd_version()
+ * stays as it is and the binding refuses a library without these symbols by name).  Addressing, workspace and refusals are those of the
+ * entries above.  u = gamma * (y - mean) * inv_std + beta is formed as bd_bn_apply_act_fwd forms it (fp64 on the fp32 statistics, one
+ * rounding to fp32) by ONE device function for the three entries; sigma(u) and sigma(-u) both come from exp(-|u|) in fp32, so nothing
+ * overflows and 1 - sigma(u) is never a subtraction.
+ *   bd_bn_silu_fwd: z = u * sigma(u), one rounding to bf16; z must not be y.  In eval() the caller hands running_mean and
+ *     1 / sqrt(running_var + eps) as mean / inv_std.
+ *   bd_bn_silu_bwd_reduce: dbeta[c] = sum g_u, dgamma[c] = sum g_u * xhat with g_u = g * sigma(u) * (1 + u * sigma(-u)), u recomputed from
+ *     the pre-norm y: neither the forward output z nor a gated gradient tensor is read.  Same slots, order and bits-per-run as
+ *     bd_bn_bwd_reduce; both overwritten.
+ *   bd_bn_silu_bwd_apply: gy = gamma * inv_std * (g_u - dbeta / M - xhat * dgamma / M), M = count[c]; fp64 throughout, the gate
+ *     included (on the unrounded u: where the three terms cancel, an fp32 gate is off by several bf16 steps of the small result), one
+ *     rounding to bf16.  gy must be neither g nor y.  Where the gate is exactly 1 (u > ~ 40) the result has the bits of
+ *     bd_bn_bwd_apply. */
+int bd_bn_silu_fwd(const void* y, int64_t y_pix_per_img, int64_t y_off, const float* mean, const float* inv_std, const float* gamma,
+                   const float* beta, void* z, int64_t z_pix_per_img, int64_t z_off, int N, int64_t n, int C, bd_stream_t stream);
+int bd_bn_silu_bwd_reduce(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
+                          const float* mean, const float* inv_std, const float* gamma, const float* beta, int N, int64_t n, int C,
+                          float* dgamma, float* dbeta, void* ws, size_t ws_bytes, bd_stream_t stream);
+int bd_bn_silu_bwd_apply(const void* g, int64_t g_pix_per_img, int64_t g_off, const void* y, int64_t y_pix_per_img, int64_t y_off,
+                         const float* mean, const float* inv_std, const float* gamma, const float* beta, const float* dgamma,
+                         const float* dbeta, const float* count, void* gy, int64_t gy_pix_per_img, int64_t gy_off, int N, int64_t n, int C,
+                         bd_stream_t stream);
 
 /* offsets = relu(bbox_pred * scale_l) * stride_l (point_head.py:143).  raw: bf16 [pixels][ld = 8] (channels 0-3 =
  * bbox_pred, 4 = ctrness logit, 5-7 = 0), scales: device fp32 [L]; out: bf16 [pixels][4]. */
