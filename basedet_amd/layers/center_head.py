@@ -26,122 +26,23 @@ training path.
 Reproducibility: every forward output, and everything the head's backward writes, is bitwise reproducible.  Neck gradients downstream of a
 deformable convolution's d_x are not (fp32 atomics in bd_deform_conv_bwd_data): they hold their bounds, not their bits.
 
-The layers own their buffers, as deformable.py does; the plan arena, the wgrad side stream, optimizers and EMA belong to the model."""
+Storage, as in deformable.py (layers/_pm.py ParamStore): fp32 masters in the kernels' layouts and the bf16 operands are allocated once;
+params() hands out views under the reference's names, load_state_dict() copies into them, repack() packs in place, grads() returns
+copies.  adopt() moves a layer onto a model's parameter arena and norm records -- the same path on other storage.  The activations are
+the layers' own; the plan arena, the wgrad side stream, optimizers and EMA belong to the model."""
 import math
 
 import numpy as np
 import torch
 
 from .. import ops
-from .._lib import BasedetHipError
+from ._pm import BF16, F32, ParamStore, load_strict, need_device, round_up8, to_nchw, to_pm, workspace
+from .batch_norm import BatchNormAct
 from .deformable import DeformConvWithOff, ModulatedDeformConvWithOff
 
 __all__ = ["DeconvLayer", "CenternetDeconv", "SingleHead", "CenterHead"]
 
-BF16, F32 = torch.bfloat16, torch.float32
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
-
-
-def _need_device(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise BasedetHipError(f"{what}: needs a tensor on a HIP device (got a host tensor); there is no CPU fallback")
-
-
-def _to_pm(x):
-    N, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(N * H * W, C).to(BF16).contiguous()
-
-
-def _to_nchw(t, N, H, W):
-    return t.float().view(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
-
-
-def _load(state, want, device):
-    """Strict names and shapes -> fp32 device tensors."""
-    extra = sorted(set(state) - set(want))
-    if extra:
-        raise KeyError(f"unexpected parameter(s) {extra}")
-    out = {}
-    for k, shape in want.items():
-        if k not in state:
-            raise KeyError(f"missing parameter {k!r}")
-        v = torch.as_tensor(np.asarray(state[k]) if not torch.is_tensor(state[k]) else state[k]).detach().float()
-        if tuple(v.shape) != tuple(shape):
-            raise ValueError(f"parameter {k!r}: shape {tuple(v.shape)}, expected {tuple(shape)}")
-        out[k] = v.to(device).contiguous()
-    return out
-
-
-class _BatchNorm:
-    """M.BatchNorm2d + ReLU on csrc/batchnorm.hip over one dense pixel-major tensor."""
-
-    def __init__(self, C, device):
-        self.C, self.device, self.training = C, device, True
-        f = dict(dtype=F32, device=device)
-        self.p = {"weight": torch.ones(C, **f), "bias": torch.zeros(C, **f), "running_mean": torch.zeros(C, **f),
-                  "running_var": torch.ones(C, **f)}
-        self.mean, self.inv_std, self.sums = torch.empty(C, **f), torch.empty(C, **f), torch.empty((3, C), **f)
-        self.g = None
-        self._saved = None
-        self._ext = False
-        self._eval_inv_std = None
-
-    def adopt(self, state):
-        """Live on a model's norm record (models/live_norm.py BatchNormState): gamma / beta and their gradients are its arena views, the
-        running statistics and the batch statistics its buffers -- where the optimizer, the EMA's buffer average and the parameter
-        broadcast find them.  The current values move in."""
-        old = self.p
-        self.p = {"weight": state.gamma, "bias": state.beta, "running_mean": state.running_mean, "running_var": state.running_var}
-        for k, v in old.items():
-            self.p[k].copy_(v)
-        self.mean, self.inv_std, self.sums = state.mean, state.inv_std, state.sums
-        self.g = {"weight": state.g_gamma, "bias": state.g_beta}
-        self._ext = True
-
-    def refresh_eval(self):
-        """1 / sqrt(running_var + eps) for the eval() forward, computed once (at eval() / after a load) instead of per call."""
-        self._eval_inv_std = 1.0 / torch.sqrt(self.p["running_var"] + BN_EPS)
-
-    SHAPES = ("weight", "bias", "running_mean", "running_var")
-
-    def forward_pm(self, y, N, H, W):
-        geom = ops.single(N, H, W)
-        if self.training:
-            ws = torch.empty(ops.bn_workspace_bytes(N * H * W, self.C), dtype=torch.uint8, device=self.device)
-            ops.bn_stats_fwd(y, geom, self.C, BN_EPS, BN_MOMENTUM, self.mean, self.inv_std, self.sums, self.p["running_mean"],
-                             self.p["running_var"], ws)
-            mean, inv_std = self.mean, self.inv_std
-        else:
-            mean = self.p["running_mean"]
-            inv_std = self._eval_inv_std if self._eval_inv_std is not None else 1.0 / torch.sqrt(self.p["running_var"] + BN_EPS)
-        z = torch.empty_like(y)
-        ops.bn_apply_act_fwd(y, geom, mean, inv_std, self.p["weight"], self.p["bias"], z, geom, self.C, relu=True)
-        self._saved = (y, z, geom, self.training)
-        return z
-
-    def backward_pm(self, g, accumulate=False):
-        y, z, geom, training = self._saved
-        if not training:
-            raise RuntimeError("backward() through a norm in eval() mode is not built")
-        gm = ops.relu_bwd_bf16(g, z, torch.empty_like(g))
-        f = dict(dtype=F32, device=self.device)
-        if self._ext:          # adopted: the reduce writes the arena's gradient views
-            if accumulate:
-                raise RuntimeError("accumulate=True is not built for a norm on adopted storage")
-            dgamma, dbeta = self.g["weight"], self.g["bias"]
-        else:
-            dgamma, dbeta = torch.empty(self.C, **f), torch.empty(self.C, **f)
-        ws = torch.empty(ops.bn_workspace_bytes(y.shape[0], self.C), dtype=torch.uint8, device=self.device)
-        ops.bn_bwd_reduce(gm, geom, y, geom, self.mean, self.inv_std, self.C, dgamma, dbeta, ws)
-        gy = ops.bn_bwd_apply(gm, geom, y, geom, self.mean, self.inv_std, self.p["weight"], dgamma, dbeta, self.sums[0], torch.empty_like(g),
-                              geom, self.C)
-        if self._ext:
-            pass
-        elif accumulate and self.g is not None:
-            self.g = {"weight": self.g["weight"] + dgamma, "bias": self.g["bias"] + dbeta}
-        else:
-            self.g = {"weight": dgamma, "bias": dbeta}
-        return gy
 
 
 def bilinear_stencil(k):
@@ -178,9 +79,9 @@ def deconv_param_shapes(in_planes, out_planes, modulate_deform):
     k, C = (27 if cls.MODULATED else 18), out_planes
     want = {f"dcn.{cls.OFFSET_NAME}.weight": (k, in_planes, 3, 3), f"dcn.{cls.OFFSET_NAME}.bias": (k,),
             f"dcn.{cls.DCN_NAME}.weight": (C, in_planes, 3, 3), f"dcn.{cls.DCN_NAME}.bias": (C,)}
-    want.update({f"dcn_bn.{k}": (C,) for k in _BatchNorm.SHAPES})
+    want.update({f"dcn_bn.{k}": (C,) for k in BatchNormAct.KEYS})
     want["up_sample.weight"] = (C, C, 4, 4)
-    want.update({f"up_bn.{k}": (C,) for k in _BatchNorm.SHAPES})
+    want.update({f"up_bn.{k}": (C,) for k in BatchNormAct.KEYS})
     return want
 
 
@@ -205,15 +106,19 @@ class DeconvLayer:
         C = out_planes
         cls = ModulatedDeformConvWithOff if modulate_deform else DeformConvWithOff
         self.dcn = cls(in_planes, out_planes, kernel_size=3, deformable_groups=1, seed=seed, device=device)
-        self.dcn_bn, self.up_bn = _BatchNorm(C, self.device), _BatchNorm(C, self.device)
-        # M.ConvTranspose2d's default init: N(0, sqrt(1 / fan_in)), fan_in = 16 C; then init_module
+        self.dcn_bn, self.up_bn = (BatchNormAct(C, "relu", BN_EPS, BN_MOMENTUM, self.device) for _ in range(2))
         self.modulate_deform = bool(modulate_deform)
-        self._up_w = torch.from_numpy(up_sample_init(C, np.random.default_rng(seed + 1))).to(self.device)        # (in, out, 4, 4)
-        self._g_up = None
+        self._store = ParamStore({"up_sample.weight": (C, 4, 4, C)}, self.device)
+        self._up_wf, self._up_wd = (torch.empty(16 * C * C, dtype=BF16, device=self.device) for _ in range(2))
+        # M.ConvTranspose2d's default init: N(0, sqrt(1 / fan_in)), fan_in = 16 C; then init_module
+        self._up_w().copy_(torch.from_numpy(up_sample_init(C, np.random.default_rng(seed + 1))))
         self._saved = None
-        self._ext = None
         self.training = True
         self.repack()
+
+    def _up_w(self):
+        """up_sample.weight as M.ConvTranspose2d has it, (in, out, 4, 4): a view of the OHWI master."""
+        return self._store.w["up_sample.weight"].permute(0, 3, 1, 2)
 
     def arena_shapes(self):
         """name -> shape of the fp32 masters in the kernels' layouts (deformable.py arena_shapes; up_sample.weight as the OHWI conv view
@@ -226,19 +131,12 @@ class DeconvLayer:
 
     def adopt(self, w, g, dcn_bn, up_bn):
         """Live on the caller's storage (a model's parameter arena): w / g = {name: fp32 view} in arena_shapes()' layouts, dcn_bn / up_bn
-        the model's norm records.  Standalone use is unchanged; see deformable.py adopt."""
-        C = self.out_planes
-        if tuple(w["up_sample.weight"].shape) != (C, 4, 4, C) or tuple(g["up_sample.weight"].shape) != (C, 4, 4, C):
-            raise ValueError(f"adopt: 'up_sample.weight' needs fp32 views of shape {(C, 4, 4, C)}")
+        the model's norm records.  See deformable.py adopt.  Every shape is checked before anything moves."""
+        self._store.check(w, g)
         self.dcn.adopt({k[4:]: v for k, v in w.items() if k.startswith("dcn.")}, {k[4:]: v for k, v in g.items() if k.startswith("dcn.")})
+        self._store.move(w, g)
         self.dcn_bn.adopt(dcn_bn)
         self.up_bn.adopt(up_bn)
-        w["up_sample.weight"].copy_(self._up_w.permute(0, 2, 3, 1))
-        self._ext = w["up_sample.weight"]
-        self._up_w = self._ext.permute(0, 3, 1, 2)          # the (in, out, 4, 4) view params() / state_dict() hand out
-        self._g_up = g["up_sample.weight"]
-        self._up_wf = torch.empty(16 * C * C, dtype=BF16, device=self.device)
-        self._up_wd = torch.empty(16 * C * C, dtype=BF16, device=self.device)
         self.repack()
 
     def refresh_eval(self):
@@ -255,43 +153,27 @@ class DeconvLayer:
     def params(self):
         """The trainable fp32 device masters by name."""
         p = {"dcn." + k: v for k, v in self.dcn.params().items()}
-        p.update({"dcn_bn.weight": self.dcn_bn.p["weight"], "dcn_bn.bias": self.dcn_bn.p["bias"], "up_sample.weight": self._up_w,
+        p.update({"dcn_bn.weight": self.dcn_bn.p["weight"], "dcn_bn.bias": self.dcn_bn.p["bias"], "up_sample.weight": self._up_w(),
                   "up_bn.weight": self.up_bn.p["weight"], "up_bn.bias": self.up_bn.p["bias"]})
         return p
 
     def repack(self):
-        C = self.out_planes
         self.dcn.repack()
-        if self._ext is not None:          # the master is the conv view already; the operands keep their place
-            ops.fpn_deconv_pack(self._ext, C, self._up_wf, self._up_wd)
-            return
-        self._up_wf = torch.empty(16 * C * C, dtype=BF16, device=self.device)
-        self._up_wd = torch.empty(16 * C * C, dtype=BF16, device=self.device)
-        ops.fpn_deconv_pack(self._up_w.permute(0, 2, 3, 1).contiguous(), C, self._up_wf, self._up_wd)
+        ops.fpn_deconv_pack(self._store.w["up_sample.weight"], self.out_planes, self._up_wf, self._up_wd)
 
     def state_dict(self):
         out = {"dcn." + k: v for k, v in self.dcn.state_dict().items()}
-        for name, bn in (("dcn_bn", self.dcn_bn), ("up_bn", self.up_bn)):
-            out.update({f"{name}.{k}": bn.p[k].detach().cpu().clone() for k in _BatchNorm.SHAPES})
-            if name == "dcn_bn":
-                out["up_sample.weight"] = self._up_w.detach().cpu().clone()
+        out.update(self.dcn_bn.state("dcn_bn."))
+        out["up_sample.weight"] = self._up_w().detach().contiguous().cpu()
+        out.update(self.up_bn.state("up_bn."))
         return out
 
     def load_state_dict(self, state):
-        p = _load(state, self._shapes(), self.device)
+        p = load_strict(state, self._shapes(), self.device)
         self.dcn.load_state_dict({k[4:]: v for k, v in p.items() if k.startswith("dcn.")})
-        for name, bn in (("dcn_bn", self.dcn_bn), ("up_bn", self.up_bn)):
-            if self._ext is not None:
-                for k in _BatchNorm.SHAPES:
-                    bn.p[k].copy_(p[f"{name}.{k}"])
-                if bn._eval_inv_std is not None:
-                    bn.refresh_eval()
-            else:
-                bn.p = {k: p[f"{name}.{k}"] for k in _BatchNorm.SHAPES}
-        if self._ext is not None:
-            self._up_w.copy_(p["up_sample.weight"])
-        else:
-            self._up_w = p["up_sample.weight"]
+        self.dcn_bn.load(p, "dcn_bn.")
+        self.up_bn.load(p, "up_bn.")
+        self._up_w().copy_(p["up_sample.weight"])
         self.repack()
 
     def train(self, mode=True):
@@ -322,13 +204,9 @@ class DeconvLayer:
         z0, N, H, W = self._saved
         C = self.out_planes
         g_y1 = self.up_bn.backward_pm(g, accumulate)
-        if self._ext is not None:
-            pass                           # (the adopted gradient view)
-        elif self._g_up is None or not accumulate:
-            accumulate = False
-            self._g_up = torch.empty((C, 4, 4, C), dtype=F32, device=self.device)
-        ws = torch.empty(ops.fpn_deconv_wgrad_workspace_bytes(N, H, W, C), dtype=torch.uint8, device=self.device)
-        ops.fpn_deconv_wgrad(z0, g_y1, self._g_up, ws, N, H, W, C, accumulate=accumulate)
+        gr, acc = self._store.grad(accumulate)
+        ws = workspace(ops.fpn_deconv_wgrad_workspace_bytes(N, H, W, C), self.device)
+        ops.fpn_deconv_wgrad(z0, g_y1, gr["up_sample.weight"], ws, N, H, W, C, accumulate=acc)
         g_z0 = ops.fpn_deconv_dgrad(g_y1, self._up_wd, torch.empty_like(z0), N, H, W, C)
         g_y0 = self.dcn_bn.backward_pm(g_z0, accumulate)
         g_x = self.dcn.backward_pm(g_y0, accumulate)
@@ -336,31 +214,32 @@ class DeconvLayer:
         return g_x
 
     def __call__(self, x):
-        _need_device(x, "DeconvLayer")
+        need_device(x, "DeconvLayer")
         N, C, H, W = x.shape
         if C != self.in_planes:
             raise ValueError(f"input has {C} channels, the layer {self.in_planes}")
-        return _to_nchw(self.forward_pm(_to_pm(x), N, H, W), N, 2 * H, 2 * W)
+        return to_nchw(self.forward_pm(to_pm(x), N, H, W), N, 2 * H, 2 * W)
 
     forward = __call__
 
     def backward(self, dy, accumulate=False):
-        _need_device(dy, "DeconvLayer.backward")
+        need_device(dy, "DeconvLayer.backward")
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         _, N, H, W = self._saved
         if tuple(dy.shape) != (N, self.out_planes, 2 * H, 2 * W):
             raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output {(N, self.out_planes, 2 * H, 2 * W)}")
-        return _to_nchw(self.backward_pm(_to_pm(dy), accumulate), N, H, W)
+        return to_nchw(self.backward_pm(to_pm(dy), accumulate), N, H, W)
 
     def grads(self):
-        """Parameter gradients of the last backward() under the reference's names, in the state_dict's layouts."""
-        if self._g_up is None:
+        """Parameter gradients of the last backward() under the reference's names, in the state_dict's layouts: copies, not views of the
+        storage the next backward writes."""
+        if self._store.g is None:
             raise RuntimeError("grads() before a backward")
         out = {"dcn." + k: v for k, v in self.dcn.grads().items()}
-        out.update({"dcn_bn.weight": self.dcn_bn.g["weight"], "dcn_bn.bias": self.dcn_bn.g["bias"],
-                    "up_sample.weight": self._g_up.permute(0, 3, 1, 2).contiguous(),
-                    "up_bn.weight": self.up_bn.g["weight"], "up_bn.bias": self.up_bn.g["bias"]})
+        out.update({"dcn_bn.weight": self.dcn_bn.g["weight"].clone(), "dcn_bn.bias": self.dcn_bn.g["bias"].clone(),
+                    "up_sample.weight": self._store.g["up_sample.weight"].permute(0, 3, 1, 2).contiguous(),
+                    "up_bn.weight": self.up_bn.g["weight"].clone(), "up_bn.bias": self.up_bn.g["bias"].clone()})
         return out
 
 
@@ -441,25 +320,25 @@ class CenternetDeconv:
         return g
 
     def __call__(self, x):
-        _need_device(x, "CenternetDeconv")
+        need_device(x, "CenternetDeconv")
         N, C, H, W = x.shape
         if C != self.channels[0]:
             raise ValueError(f"input has {C} channels, the neck {self.channels[0]}")
         self._saved = (N, H, W)
         s = 2 ** self.num_layers
-        return _to_nchw(self.forward_pm(_to_pm(x), N, H, W), N, s * H, s * W)
+        return to_nchw(self.forward_pm(to_pm(x), N, H, W), N, s * H, s * W)
 
     forward = __call__
 
     def backward(self, dy, accumulate=False):
-        _need_device(dy, "CenternetDeconv.backward")
+        need_device(dy, "CenternetDeconv.backward")
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         N, H, W = self._saved
         s = 2 ** self.num_layers
         if tuple(dy.shape) != (N, self.channels[-1], s * H, s * W):
             raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output")
-        return _to_nchw(self.backward_pm(_to_pm(dy), accumulate), N, H, W)
+        return to_nchw(self.backward_pm(to_pm(dy), accumulate), N, H, W)
 
 
 class SingleHead:
@@ -507,19 +386,23 @@ class CenterHead:
         C, K = in_channels, num_classes
         validate_head(C, K)
         self.in_channels, self.num_classes, self.prior_prob, self.device = C, K, prior_prob, torch.device(device)
-        self.cls_ld = (K + 7) // 8 * 8
+        self.cls_ld = round_up8(K)
         self.cls_head, self.wh_head, self.reg_head = SingleHead(C, K, seed), SingleHead(C, 2, seed + 1), SingleHead(C, 2, seed + 2)
         self.cls_head.state["out_conv.bias"].fill_(-math.log((1 - prior_prob) / prior_prob))
-        state = {f"{b}_head.{k}": v for b in self.BRANCHES for k, v in getattr(self, b + "_head").state.items()}
-        self._g = None
+        self._store = ParamStore(self.arena_shapes(), self.device)
+        self._feat_wf = torch.empty((3 * C, 9, C), dtype=BF16, device=self.device)
+        self._feat_wd = torch.empty((C, 9, 3 * C), dtype=BF16, device=self.device)
         self._saved = None
-        self._ext = None
         self.training = True
-        self.load_state_dict(state)
+        p = self.params()
+        for b in self.BRANCHES:
+            for k, v in getattr(self, b + "_head").state.items():
+                p[f"{b}_head.{k}"].copy_(v)
+        self.repack()
 
     def arena_shapes(self):
         """name -> shape of the fp32 masters in the kernels' layouts: the three feat_convs as ONE OHWI (3C, 3, 3, C) weight and (3C,) bias
-        (cls | wh | reg, what repack() concatenated per step before), the output convolutions as they are."""
+        (cls | wh | reg), the output convolutions as they are."""
         C, K = self.in_channels, self.num_classes
         out = {"feat_conv.weight": (3 * C, 3, 3, C), "feat_conv.bias": (3 * C,)}
         for b, n in (("cls", K), ("wh", 2), ("reg", 2)):
@@ -528,27 +411,8 @@ class CenterHead:
         return out
 
     def adopt(self, w, g):
-        """Live on the caller's storage (a model's parameter arena); see deformable.py adopt.  params() / state_dict() / grads() keep the
-        reference's per-branch names as views."""
-        C, old = self.in_channels, self._params
-        for name, shape in self.arena_shapes().items():
-            if tuple(w[name].shape) != shape or tuple(g[name].shape) != shape:
-                raise ValueError(f"adopt: {name!r} needs fp32 views of shape {shape}")
-        p = {}
-        for i, b in enumerate(self.BRANCHES):
-            p[f"{b}_head.feat_conv.weight"] = w["feat_conv.weight"][i * C:(i + 1) * C].permute(0, 3, 1, 2)
-            p[f"{b}_head.feat_conv.bias"] = w["feat_conv.bias"][i * C:(i + 1) * C]
-            p[f"{b}_head.out_conv.weight"] = w[f"{b}_head.out_conv.weight"]
-            p[f"{b}_head.out_conv.bias"] = w[f"{b}_head.out_conv.bias"]
-        for k, v in p.items():
-            v.copy_(old[k])
-        self._params = {k: p[k] for k in old}          # (the reference's order)
-        self._ext = w
-        self._g = dict(feat_w=g["feat_conv.weight"], feat_b=g["feat_conv.bias"], cls_w=g["cls_head.out_conv.weight"],
-                       cls_b=g["cls_head.out_conv.bias"], wh_w=g["wh_head.out_conv.weight"], wh_b=g["wh_head.out_conv.bias"],
-                       reg_w=g["reg_head.out_conv.weight"], reg_b=g["reg_head.out_conv.bias"])
-        self._feat_wf = torch.empty((3 * C, 9, C), dtype=BF16, device=self.device)
-        self._feat_wd = torch.empty((C, 9, 3 * C), dtype=BF16, device=self.device)
+        """Live on the caller's storage (a model's parameter arena); see deformable.py adopt."""
+        self._store.move(w, g)
         self.repack()
 
     # ---- parameters ------------------------------------------------------------------------------------------------------------------------
@@ -558,33 +422,33 @@ class CenterHead:
     def names(self):
         return list(self._shapes())
 
+    def _branches(self, t):
+        """The reference's per-branch names and OIHW shapes, in its order, as views of masters or gradients `t`."""
+        C, out = self.in_channels, {}
+        for i, b in enumerate(self.BRANCHES):
+            out[f"{b}_head.feat_conv.weight"] = t["feat_conv.weight"][i * C:(i + 1) * C].permute(0, 3, 1, 2)
+            out[f"{b}_head.feat_conv.bias"] = t["feat_conv.bias"][i * C:(i + 1) * C]
+            out[f"{b}_head.out_conv.weight"] = t[f"{b}_head.out_conv.weight"]
+            out[f"{b}_head.out_conv.bias"] = t[f"{b}_head.out_conv.bias"]
+        return out
+
     def params(self):
-        return self._params
+        """The fp32 device masters by name (views).  After changing them in place, repack() rebuilds the bf16 operands."""
+        return self._branches(self._store.w)
 
     def state_dict(self):
-        return {k: v.detach().cpu().clone() for k, v in self._params.items()}
+        return {k: v.detach().contiguous().cpu() for k, v in self.params().items()}
 
     def load_state_dict(self, state):
-        p = _load(state, self._shapes(), self.device)
-        if self._ext is not None:
-            for k, v in p.items():
-                self._params[k].copy_(v)
-        else:
-            self._params = p
+        p = load_strict(state, self._shapes(), self.device)
+        for k, v in self.params().items():
+            v.copy_(p[k])
         self.repack()
 
     def repack(self):
-        """The three feat_convs as one 3C-row convolution (cls | wh | reg); the output convolutions are read as fp32 masters by the kernel."""
-        C, p, dev = self.in_channels, self._params, self.device
-        if self._ext is not None:          # one fused master in the kernel's layout: no concatenation, the operands keep their place
-            self._feat_bias = self._ext["feat_conv.bias"]
-            ops.weight_pack(self._ext["feat_conv.weight"], None, self._feat_wf, self._feat_wd, 3 * C, 9, C)
-            return
-        w = torch.cat([p[f"{b}_head.feat_conv.weight"] for b in self.BRANCHES], 0).permute(0, 2, 3, 1).contiguous()
-        self._feat_bias = torch.cat([p[f"{b}_head.feat_conv.bias"] for b in self.BRANCHES], 0).contiguous()
-        self._feat_wf = torch.empty((3 * C, 9, C), dtype=BF16, device=dev)
-        self._feat_wd = torch.empty((C, 9, 3 * C), dtype=BF16, device=dev)
-        ops.weight_pack(w, None, self._feat_wf, self._feat_wd, 3 * C, 9, C)
+        """The three feat_convs are one 3C-row convolution (cls | wh | reg); the output convolutions are read as fp32 masters by the kernel."""
+        C = self.in_channels
+        ops.weight_pack(self._store.w["feat_conv.weight"], None, self._feat_wf, self._feat_wd, 3 * C, 9, C)
 
     def train(self, mode=True):
         self.training = bool(mode)
@@ -600,11 +464,11 @@ class CenterHead:
     # ---- forward / backward ------------------------------------------------------------------------------------------------------------------
     def forward_pm(self, x, N, H, W):
         """x bf16 [N H W][C] -> (logits_pm bf16 [M][round_up(K, 8)], wr_pm bf16 [M][8]): the raw outputs (no sigmoid)."""
-        C, K, M, dev, p = self.in_channels, self.num_classes, N * H * W, self.device, self._params
+        C, K, M, dev, p = self.in_channels, self.num_classes, N * H * W, self.device, self._store.w
         if tuple(x.shape) != (M, C) or x.dtype != BF16:
             raise ValueError(f"forward_pm: expected bf16 {(M, C)}, got {x.dtype} {tuple(x.shape)}")
         feat = torch.empty((M, 3 * C), dtype=BF16, device=dev)
-        ops.conv2d_fwd(self._desc(N, H, W), x, self._feat_wf, self._feat_bias, feat, flags=ops.EPI_RELU)
+        ops.conv2d_fwd(self._desc(N, H, W), x, self._feat_wf, p["feat_conv.bias"], feat, flags=ops.EPI_RELU)
         self.logits_pm = torch.empty((M, self.cls_ld), dtype=BF16, device=dev)
         self.wr_pm = torch.empty((M, 8), dtype=BF16, device=dev)
         ops.center_head_out_fwd(feat, p["cls_head.out_conv.weight"], p["cls_head.out_conv.bias"], p["wh_head.out_conv.weight"],
@@ -619,43 +483,35 @@ class CenterHead:
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         x, feat, N, H, W = self._saved
-        C, K, M, dev, p = self.in_channels, self.num_classes, N * H * W, self.device, self._params
-        if self._ext is not None:
-            pass                           # (the adopted gradient views)
-        elif self._g is None or not accumulate:
-            accumulate = False
-            f = lambda *s: torch.empty(s, dtype=F32, device=dev)
-            self._g = dict(feat_w=f(3 * C, 3, 3, C), feat_b=f(3 * C), cls_w=f(K, C, 1, 1), cls_b=f(K), wh_w=f(2, C, 1, 1), wh_b=f(2),
-                           reg_w=f(2, C, 1, 1), reg_b=f(2))
-        g = self._g
+        C, K, M, dev, p = self.in_channels, self.num_classes, N * H * W, self.device, self._store.w
+        g, accumulate = self._store.grad(accumulate)
         d = self._desc(N, H, W)
-        nbytes = max(ops.center_head_out_bwd_workspace_bytes(M, C, K), ops.conv2d_wgrad_bias_workspace_bytes(d))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = workspace(max(ops.center_head_out_bwd_workspace_bytes(M, C, K), ops.conv2d_wgrad_bias_workspace_bytes(d)), dev)
         d_feat = torch.empty_like(feat)
         ops.center_head_out_bwd(feat, d_logits, d_wr, p["cls_head.out_conv.weight"], p["wh_head.out_conv.weight"],
-                                p["reg_head.out_conv.weight"], M, C, K, d_feat, g["cls_w"], g["cls_b"], g["wh_w"], g["wh_b"], g["reg_w"],
-                                g["reg_b"], ws, accumulate=accumulate)
-        ops.conv2d_wgrad_bias(d, x, d_feat, g["feat_w"], g["feat_b"], ws, accumulate=accumulate)
+                                p["reg_head.out_conv.weight"], M, C, K, d_feat,
+                                *[g[f"{b}_head.out_conv.{s}"] for b in self.BRANCHES for s in ("weight", "bias")], ws, accumulate=accumulate)
+        ops.conv2d_wgrad_bias(d, x, d_feat, g["feat_conv.weight"], g["feat_conv.bias"], ws, accumulate=accumulate)
         d_x = ops.conv2d_dgrad(d, d_feat, self._feat_wd, torch.empty_like(x))
         self.d_feat_pm = d_feat
         return d_x
 
     def __call__(self, x):
-        _need_device(x, "CenterHead")
+        need_device(x, "CenterHead")
         N, C, H, W = x.shape
         if C != self.in_channels:
             raise ValueError(f"input has {C} channels, the head {self.in_channels}")
-        logits, wr = self.forward_pm(_to_pm(x), N, H, W)
+        logits, wr = self.forward_pm(to_pm(x), N, H, W)
         K = self.num_classes
-        return {"cls": torch.sigmoid(_to_nchw(logits[:, :K], N, H, W)), "wh": _to_nchw(wr[:, 0:2], N, H, W),
-                "reg": _to_nchw(wr[:, 2:4], N, H, W)}
+        return {"cls": torch.sigmoid(to_nchw(logits[:, :K], N, H, W)), "wh": to_nchw(wr[:, 0:2], N, H, W),
+                "reg": to_nchw(wr[:, 2:4], N, H, W)}
 
     forward = __call__
 
     def backward(self, d_cls, d_wh, d_reg, accumulate=False):
         """Gradients with respect to the returned outputs (d_cls reaches the logits through p (1 - p)) -> d_x NCHW fp32."""
         for t in (d_cls, d_wh, d_reg):
-            _need_device(t, "CenterHead.backward")
+            need_device(t, "CenterHead.backward")
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         _, _, N, H, W = self._saved
@@ -666,16 +522,10 @@ class CenterHead:
         d_wr = torch.zeros((M, 8), dtype=BF16, device=self.device)
         d_wr[:, 0:2] = d_wh.permute(0, 2, 3, 1).reshape(M, 2).to(BF16)
         d_wr[:, 2:4] = d_reg.permute(0, 2, 3, 1).reshape(M, 2).to(BF16)
-        return _to_nchw(self.backward_pm(d_logits, d_wr, accumulate), N, H, W)
+        return to_nchw(self.backward_pm(d_logits, d_wr, accumulate), N, H, W)
 
     def grads(self):
-        if self._g is None:
+        """Parameter gradients of the last backward() under the reference's names: copies, not views of the storage."""
+        if self._store.g is None:
             raise RuntimeError("grads() before a backward")
-        g, C = self._g, self.in_channels
-        out = {}
-        for i, b in enumerate(self.BRANCHES):
-            out[f"{b}_head.feat_conv.weight"] = g["feat_w"][i * C:(i + 1) * C].permute(0, 3, 1, 2).contiguous()
-            out[f"{b}_head.feat_conv.bias"] = g["feat_b"][i * C:(i + 1) * C].clone()
-            out[f"{b}_head.out_conv.weight"] = g[b + "_w"]
-            out[f"{b}_head.out_conv.bias"] = g[b + "_b"]
-        return out
+        return {k: v.clone(memory_format=torch.contiguous_format) for k, v in self._branches(self._store.g).items()}

@@ -8,13 +8,19 @@ dilation=1, deformable_groups=1; anything else raises ValueError before the devi
 Calling convention of layers/modules.py's heads: `layer(x)` takes and returns NCHW fp32; `layer.backward(dy)` returns dx and leaves the
 parameter gradients in `layer.grads()` under the reference's names (OIHW); `state_dict()` / `load_state_dict()` carry those names too.
 The offset convolution's 18 / 27 output rows are padded with zero rows to ld = 24 / 32 (as PaddedClsConv pads class rows): the pad
-channels of the offset tensor are never read as data and get a +0 gradient, so the pad rows' gradients are sums of zeros."""
+channels of the offset tensor are never read as data and get a +0 gradient, so the pad rows' gradients are sums of zeros.
+
+Storage (layers/_pm.py ParamStore): the fp32 masters are allocated once, in the kernels' own layouts (arena_shapes(): OHWI, padded rows),
+and so are the bf16 operands repack() writes; params() hands out OIHW views of the masters and load_state_dict() copies into them, so a
+view taken once stays valid.  adopt() moves the masters and gradients onto a caller's storage; nothing else differs between a layer on
+its own storage and one on a model's arena."""
 import math
 
 import numpy as np
 import torch
 
 from .. import ops
+from ._pm import BF16, ParamStore, load_strict, round_up8, to_nchw, to_pm, workspace
 
 __all__ = ["DeformConvWithOff", "ModulatedDeformConvWithOff"]
 
@@ -43,27 +49,32 @@ class _DeformConvBase:
         _validate(in_channels, out_channels, kernel_size, stride, padding, dilation, deformable_groups)
         self.in_channels, self.out_channels = in_channels, out_channels
         self.off_channels = 27 if self.MODULATED else 18          # deformable_groups * (2 | 3) * kernel_size^2
-        self.ld = (self.off_channels + 7) // 8 * 8
+        self.ld = round_up8(self.off_channels)
         self.device = torch.device(device)
         # MegEngine's M.Conv2d default: N(0, sqrt(1 / fan_in)), zero bias (models/params.py states it for P6 / P7)
         rng = np.random.default_rng(seed)
         std = math.sqrt(1.0 / (in_channels * 9))
-        state = {}
-        for name, co in ((self.OFFSET_NAME, self.off_channels), (self.DCN_NAME, out_channels)):
-            state[name + ".weight"] = torch.from_numpy((rng.standard_normal((co, in_channels, 3, 3)) * std).astype(np.float32))
-            state[name + ".bias"] = torch.zeros(co, dtype=torch.float32)
-        self._grads = None
+        init = {name + ".weight": torch.from_numpy((rng.standard_normal((co, in_channels, 3, 3)) * std).astype(np.float32))
+                for name, co in ((self.OFFSET_NAME, self.off_channels), (self.DCN_NAME, out_channels))}
+        self._store = ParamStore(self.arena_shapes(), self.device)          # (zeros: the biases, the offset convolution's pad rows)
+        bf = dict(dtype=BF16, device=self.device)
+        self._off_wf, self._off_wd = torch.empty((self.ld, 9, in_channels), **bf), torch.empty((in_channels, 9, self.ld), **bf)
+        self._dcn_wf, self._dcn_wd = torch.empty((out_channels, 9, in_channels), **bf), torch.empty((in_channels, 9, out_channels), **bf)
         self._saved = None
-        self._ext = None               # adopt(): (masters, gradients) on the caller's storage, in the kernels' layouts
         self.last_offset_mask = None
-        self.load_state_dict(state)
+        p = self.params()
+        for k, v in init.items():
+            p[k].copy_(v)
+        self.repack()
 
     # ---- parameters ------------------------------------------------------------------------------------------------------------------------
     def names(self):
         return [n + s for n in (self.OFFSET_NAME, self.DCN_NAME) for s in (".weight", ".bias")]
 
-    def state_dict(self):
-        return {k: v.detach().cpu().clone() for k, v in self._params.items()}
+    def _shapes(self):
+        k, Cin, Cout = self.off_channels, self.in_channels, self.out_channels
+        return {self.OFFSET_NAME + ".weight": (k, Cin, 3, 3), self.OFFSET_NAME + ".bias": (k,),
+                self.DCN_NAME + ".weight": (Cout, Cin, 3, 3), self.DCN_NAME + ".bias": (Cout,)}
 
     def arena_shapes(self):
         """name -> shape of the fp32 masters in the kernels' own layouts (OHWI, the offset convolution's rows padded to ld): what a caller
@@ -74,104 +85,60 @@ class _DeformConvBase:
 
     def adopt(self, w, g):
         """Live on storage the caller provides (a model's parameter arena): w / g = {name: fp32 device view} in arena_shapes()' layouts.
-        The current values move into w; from here on the masters ARE those views (an optimizer step over the arena, then repack()),
-        backward writes every parameter gradient straight into g, and params() / state_dict() / grads() keep the reference's OIHW
-        layouts as views.  The pad rows of the offset convolution are zero and stay zero (their gradients are sums of zeros)."""
-        k = self.off_channels
-        old = self._params
-        for name, shape in self.arena_shapes().items():
-            if tuple(w[name].shape) != shape or tuple(g[name].shape) != shape:
-                raise ValueError(f"adopt: {name!r} needs fp32 views of shape {shape}")
-            w[name].zero_()
-        on, dn = self.OFFSET_NAME, self.DCN_NAME
-        w[on + ".weight"][:k].copy_(old[on + ".weight"].permute(0, 2, 3, 1))
-        w[on + ".bias"][:k].copy_(old[on + ".bias"])
-        w[dn + ".weight"].copy_(old[dn + ".weight"].permute(0, 2, 3, 1))
-        w[dn + ".bias"].copy_(old[dn + ".bias"])
-        self._ext = (w, g)
-        self._params = {on + ".weight": w[on + ".weight"][:k].permute(0, 3, 1, 2), on + ".bias": w[on + ".bias"][:k],
-                        dn + ".weight": w[dn + ".weight"].permute(0, 3, 1, 2), dn + ".bias": w[dn + ".bias"]}
-        self._grads = dict(off_w=g[on + ".weight"], off_b=g[on + ".bias"], dcn_w=g[dn + ".weight"], dcn_b=g[dn + ".bias"])
-        self._pack()
+        The current values move into w; from here on the masters ARE those views (an optimizer step over the arena, then repack()) and
+        backward writes every parameter gradient straight into g.  The pad rows of the offset convolution are zero and stay zero (their
+        gradients are sums of zeros)."""
+        self._store.move(w, g)
+        self.repack()
+
+    def _oihw(self, t):
+        """The reference's names and OIHW shapes as views of masters or gradients `t` (the real rows of the offset convolution)."""
+        k, on, dn = self.off_channels, self.OFFSET_NAME, self.DCN_NAME
+        return {on + ".weight": t[on + ".weight"][:k].permute(0, 3, 1, 2), on + ".bias": t[on + ".bias"][:k],
+                dn + ".weight": t[dn + ".weight"].permute(0, 3, 1, 2), dn + ".bias": t[dn + ".bias"]}
+
+    def params(self):
+        """The fp32 device masters by name (OIHW views).  After changing them in place, repack() rebuilds the bf16 operands."""
+        return self._oihw(self._store.w)
+
+    def state_dict(self):
+        return {k: v.detach().contiguous().cpu() for k, v in self.params().items()}
 
     def load_state_dict(self, state):
-        want = {self.OFFSET_NAME + ".weight": (self.off_channels, self.in_channels, 3, 3), self.OFFSET_NAME + ".bias": (self.off_channels,),
-                self.DCN_NAME + ".weight": (self.out_channels, self.in_channels, 3, 3), self.DCN_NAME + ".bias": (self.out_channels,)}
-        params = {}
-        for k, shape in want.items():
-            if k not in state:
-                raise KeyError(f"missing parameter {k!r}")
-            v = torch.as_tensor(np.asarray(state[k]) if not torch.is_tensor(state[k]) else state[k]).detach().float()
-            if tuple(v.shape) != shape:
-                raise ValueError(f"parameter {k!r}: shape {tuple(v.shape)}, expected {shape}")
-            params[k] = v.to(self.device).contiguous()
-        if self._ext is not None:          # the masters stay where they are: the values move in
-            for k, v in params.items():
-                self._params[k].copy_(v)
-        else:
-            self._params = params
-        self._pack()
+        """The values move into the masters, which stay where they are (extra keys are ignored)."""
+        p = load_strict(state, self._shapes(), self.device, extra_ok=True)
+        for k, v in self.params().items():
+            v.copy_(p[k])
+        self.repack()
 
-    def _pack(self):
-        """fp32 masters (OIHW) -> the bf16 operands of the kernels; the offset conv's rows padded with zero rows to ld."""
-        dev, Cin, ld = self.device, self.in_channels, self.ld
-        p = self._params
-        if self._ext is not None:          # the masters already have the kernels' layouts: no copies, the packed operands keep their place
-            w = self._ext[0]
-            self._off_bias, self._dcn_bias = w[self.OFFSET_NAME + ".bias"], w[self.DCN_NAME + ".bias"]
-            if getattr(self, "_ext_packed", False) is False:
-                self._off_wf = torch.empty((ld, 9, Cin), dtype=torch.bfloat16, device=dev)
-                self._off_wd = torch.empty((Cin, 9, ld), dtype=torch.bfloat16, device=dev)
-                self._dcn_wf = torch.empty((self.out_channels, 9, Cin), dtype=torch.bfloat16, device=dev)
-                self._dcn_wd = torch.empty((Cin, 9, self.out_channels), dtype=torch.bfloat16, device=dev)
-                self._ext_packed = True
-            ops.weight_pack(w[self.OFFSET_NAME + ".weight"], None, self._off_wf, self._off_wd, ld, 9, Cin)
-            ops.weight_pack(w[self.DCN_NAME + ".weight"], None, self._dcn_wf, self._dcn_wd, self.out_channels, 9, Cin)
-            return
-        w_off = torch.zeros((ld, 3, 3, Cin), dtype=torch.float32, device=dev)
-        w_off[: self.off_channels] = p[self.OFFSET_NAME + ".weight"].permute(0, 2, 3, 1)
-        self._off_bias = torch.zeros(ld, dtype=torch.float32, device=dev)
-        self._off_bias[: self.off_channels] = p[self.OFFSET_NAME + ".bias"]
-        self._off_wf = torch.empty((ld, 9, Cin), dtype=torch.bfloat16, device=dev)
-        self._off_wd = torch.empty((Cin, 9, ld), dtype=torch.bfloat16, device=dev)
-        ops.weight_pack(w_off, None, self._off_wf, self._off_wd, ld, 9, Cin)
-        w_dcn = p[self.DCN_NAME + ".weight"].permute(0, 2, 3, 1).contiguous()
-        self._dcn_bias = p[self.DCN_NAME + ".bias"]
-        self._dcn_wf = torch.empty((self.out_channels, 9, Cin), dtype=torch.bfloat16, device=dev)
-        self._dcn_wd = torch.empty((Cin, 9, self.out_channels), dtype=torch.bfloat16, device=dev)
-        ops.weight_pack(w_dcn, None, self._dcn_wf, self._dcn_wd, self.out_channels, 9, Cin)
+    def repack(self):
+        """fp32 masters -> the bf16 operands of the kernels, in place."""
+        w, Cin = self._store.w, self.in_channels
+        ops.weight_pack(w[self.OFFSET_NAME + ".weight"], None, self._off_wf, self._off_wd, self.ld, 9, Cin)
+        ops.weight_pack(w[self.DCN_NAME + ".weight"], None, self._dcn_wf, self._dcn_wd, self.out_channels, 9, Cin)
 
     def _offset_desc(self, N, H, W):
         g = ops.single(N, H, W)
         return ops.conv_desc(g, g, self.in_channels, self.ld, 3, 3, 1, 1)
 
     # ---- forward / backward ------------------------------------------------------------------------------------------------------------------
-    def params(self):
-        """The fp32 device masters by name (OIHW).  After changing them in place, repack() rebuilds the bf16 operands."""
-        return self._params
-
-    def repack(self):
-        self._pack()
-
     def __call__(self, x):
         N, C, H, W = x.shape
         if C != self.in_channels:
             raise ValueError(f"input has {C} channels, the layer {self.in_channels}")
-        xp = x.to(self.device).permute(0, 2, 3, 1).reshape(N * H * W, C).to(torch.bfloat16).contiguous()
-        y = self.forward_pm(xp, N, H, W)
-        return y.float().view(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
+        return to_nchw(self.forward_pm(to_pm(x.to(self.device)), N, H, W), N, H, W)
 
     forward = __call__
 
     def forward_pm(self, xp, N, H, W):
         """The pixel-major path: xp bf16 [N H W][Cin] on the device -> y bf16 [N H W][Cout]; no NCHW / fp32 round trip."""
-        M, C = N * H * W, self.in_channels
+        M, C, w = N * H * W, self.in_channels, self._store.w
         if tuple(xp.shape) != (M, C) or xp.dtype != torch.bfloat16:
             raise ValueError(f"forward_pm: expected bf16 {(M, C)}, got {xp.dtype} {tuple(xp.shape)}")
         om = torch.empty((M, self.ld), dtype=torch.bfloat16, device=self.device)
-        ops.conv2d_fwd(self._offset_desc(N, H, W), xp, self._off_wf, self._off_bias, om)
+        ops.conv2d_fwd(self._offset_desc(N, H, W), xp, self._off_wf, w[self.OFFSET_NAME + ".bias"], om)
         y = torch.empty((M, self.out_channels), dtype=torch.bfloat16, device=self.device)
-        ops.deform_conv_fwd(xp, om, self._dcn_wf, self._dcn_bias, y, N, H, W, C, self.out_channels, self.MODULATED)
+        ops.deform_conv_fwd(xp, om, self._dcn_wf, w[self.DCN_NAME + ".bias"], y, N, H, W, C, self.out_channels, self.MODULATED)
         self._saved = (xp, om, N, H, W)
         self.last_offset_mask = om
         return y
@@ -182,12 +149,9 @@ class _DeformConvBase:
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         _, _, N, H, W = self._saved
-        Cin, Cout, dev = self.in_channels, self.out_channels, self.device
-        if tuple(dy.shape) != (N, Cout, H, W):
-            raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output {(N, Cout, H, W)}")
-        g = dy.to(dev).permute(0, 2, 3, 1).reshape(N * H * W, Cout).to(torch.bfloat16).contiguous()
-        dx = self.backward_pm(g, accumulate)
-        return dx.float().view(N, H, W, Cin).permute(0, 3, 1, 2).contiguous()
+        if tuple(dy.shape) != (N, self.out_channels, H, W):
+            raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output {(N, self.out_channels, H, W)}")
+        return to_nchw(self.backward_pm(to_pm(dy.to(self.device)), accumulate), N, H, W)
 
     def backward_pm(self, g, accumulate=False):
         """g bf16 [N H W][Cout] -> d_x bf16 [N H W][Cin]; parameter gradients in grads()."""
@@ -198,37 +162,27 @@ class _DeformConvBase:
         M = N * H * W
         if tuple(g.shape) != (M, Cout) or g.dtype != torch.bfloat16:
             raise ValueError(f"backward_pm: expected bf16 {(M, Cout)}, got {g.dtype} {tuple(g.shape)}")
-        if self._ext is not None:
-            pass                           # (the gradients are the adopted views: nothing is allocated per step)
-        elif self._grads is None or not accumulate:
-            accumulate = False
-            self._grads = dict(off_w=torch.empty((ld, 3, 3, Cin), dtype=torch.float32, device=dev),
-                               off_b=torch.empty(ld, dtype=torch.float32, device=dev),
-                               dcn_w=torch.empty((Cout, 3, 3, Cin), dtype=torch.float32, device=dev),
-                               dcn_b=torch.empty(Cout, dtype=torch.float32, device=dev))
-        gr = self._grads
+        gr, accumulate = self._store.grad(accumulate)
+        on, dn = self.OFFSET_NAME, self.DCN_NAME
         d = self._offset_desc(N, H, W)
-        nbytes = max(ops.deform_conv_wgrad_workspace_bytes(N, H, W, Cin, Cout), ops.deform_conv_bwd_data_workspace_bytes(N, H, W, Cin, Cout),
-                     ops.conv2d_wgrad_bias_workspace_bytes(d))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ops.deform_conv_wgrad(xp, om, g, gr["dcn_w"], gr["dcn_b"], ws, N, H, W, Cin, Cout, self.MODULATED, accumulate=accumulate)
+        ws = workspace(max(ops.deform_conv_wgrad_workspace_bytes(N, H, W, Cin, Cout), ops.deform_conv_bwd_data_workspace_bytes(N, H, W, Cin, Cout),
+                           ops.conv2d_wgrad_bias_workspace_bytes(d)), dev)
+        ops.deform_conv_wgrad(xp, om, g, gr[dn + ".weight"], gr[dn + ".bias"], ws, N, H, W, Cin, Cout, self.MODULATED, accumulate=accumulate)
         dx_dcn = torch.empty((M, Cin), dtype=torch.bfloat16, device=dev)
         d_om = torch.empty((M, ld), dtype=torch.bfloat16, device=dev)
         ops.deform_conv_bwd_data(xp, om, g, self._dcn_wd, dx_dcn, d_om, ws, N, H, W, Cin, Cout, self.MODULATED)
         # the offset convolution reads the same input: its data gradient lands on top of the deformable part
-        ops.conv2d_wgrad_bias(d, xp, d_om, gr["off_w"], gr["off_b"], ws, accumulate=accumulate)
+        ops.conv2d_wgrad_bias(d, xp, d_om, gr[on + ".weight"], gr[on + ".bias"], ws, accumulate=accumulate)
         dx = torch.empty_like(dx_dcn)
         ops.conv2d_dgrad(d, d_om, self._off_wd, dx, add=dx_dcn, flags=ops.EPI_ADD_BEFORE)
         self.last_d_offset_mask = d_om
         return dx
 
     def grads(self):
-        """Parameter gradients of the last backward() under the reference's names, OIHW fp32."""
-        if self._grads is None:
+        """Parameter gradients of the last backward() under the reference's names, OIHW fp32: copies, not views of the storage."""
+        if self._store.g is None:
             raise RuntimeError("grads() before a backward")
-        gr, k = self._grads, self.off_channels
-        return {self.OFFSET_NAME + ".weight": gr["off_w"][:k].permute(0, 3, 1, 2).contiguous(), self.OFFSET_NAME + ".bias": gr["off_b"][:k].clone(),
-                self.DCN_NAME + ".weight": gr["dcn_w"].permute(0, 3, 1, 2).contiguous(), self.DCN_NAME + ".bias": gr["dcn_b"].clone()}
+        return {k: v.clone(memory_format=torch.contiguous_format) for k, v in self._oihw(self._store.g).items()}
 
 
 class DeformConvWithOff(_DeformConvBase):

@@ -3,8 +3,9 @@ operator every YOLOX convolution ends in, and the decoupled head that writes the
 
 Calling convention of layers/center_head.py: `layer(x)` takes and returns NCHW fp32 DEVICE tensors (a host tensor raises BasedetHipError:
 no CPU fallback); `forward_pm` / `backward_pm` on pixel-major bf16; `params()` (fp32 device masters by name, views an optimizer may update
-in place) / `repack()` / `grads()`; strict `state_dict()` / `load_state_dict()` under the reference's names; `train()` / `eval()`.  The
-layers own their buffers; `adopt()` onto a model arena belongs to the detector.
+in place) / `repack()` / `grads()` (copies); strict `state_dict()` / `load_state_dict()` under the reference's names; `train()` /
+`eval()`.  The masters are kept in the kernels' layouts and loaded in place: one path, so an `adopt()` onto a model arena (the detector's,
+not built) will be a move as it is for center_head.py's layers.  The norm is layers/batch_norm.py BatchNormAct("silu").
 
 ConvBNSiLU = bd_conv2d_fwd (no bias, no epilogue) -> bd_bn_stats_fwd -> bd_bn_silu_fwd; backward = bd_bn_silu_bwd_reduce ->
 bd_bn_silu_bwd_apply -> bd_conv2d_wgrad + bd_conv2d_dgrad.  The SiLU gate is recomputed from the pre-norm tensor inside the norm's two
@@ -29,47 +30,12 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._lib import BasedetHipError
+from ._pm import BF16, F32, load_strict, need_device, round_up8, to_nchw, to_pm, workspace
+from .batch_norm import BatchNormAct
 
 __all__ = ["ConvBNSiLU", "YOLOXHead"]
 
-BF16, F32 = torch.bfloat16, torch.float32
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03
-NORM_KEYS = ("weight", "bias", "running_mean", "running_var")
-
-
-def _need_device(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise BasedetHipError(f"{what}: needs a tensor on a HIP device (got a host tensor); there is no CPU fallback")
-
-
-def _to_pm(x):
-    N, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(N * H * W, C).to(BF16).contiguous()
-
-
-def _to_nchw(t, N, H, W):
-    return t.float().reshape(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
-
-
-def _load(state, want, device):
-    """Strict names and shapes -> fp32 device tensors."""
-    extra = sorted(set(state) - set(want))
-    if extra:
-        raise KeyError(f"unexpected parameter(s) {extra}")
-    out = {}
-    for k, shape in want.items():
-        if k not in state:
-            raise KeyError(f"missing parameter {k!r}")
-        v = torch.as_tensor(np.asarray(state[k]) if not torch.is_tensor(state[k]) else state[k]).detach().float()
-        if tuple(v.shape) != tuple(shape):
-            raise ValueError(f"parameter {k!r}: shape {tuple(v.shape)}, expected {tuple(shape)}")
-        out[k] = v.to(device).contiguous()
-    return out
-
-
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
 def validate_conv(cin, cout, k, stride):
@@ -86,7 +52,7 @@ def validate_conv(cin, cout, k, stride):
 def conv_param_shapes(cin, cout, k):
     """name -> shape of one ConvBNSiLU's state, in the reference's order."""
     out = {"weight": (cout, cin, k, k)}
-    out.update({f"norm.{n}": (cout,) for n in NORM_KEYS})
+    out.update({f"norm.{n}": (cout,) for n in BatchNormAct.KEYS})
     return out
 
 
@@ -113,21 +79,21 @@ class ConvBNSiLU:
         validate_conv(cin, cout, k, stride)
         self.cin, self.cout, self.k, self.stride, self.pad = cin, cout, k, stride, k // 2
         self.eps, self.momentum, self.device, self.training = float(eps), float(momentum), torch.device(device), True
-        f = dict(dtype=F32, device=self.device)
         rng = np.random.default_rng(seed)
         # M.Conv2d's default init as layers/center_head.py SingleHead takes it: N(0, sqrt(1 / fan_in)); the master is OHWI, what
         # bd_weight_pack reads and bd_conv2d_wgrad writes
         w = (rng.standard_normal((cout, cin, k, k)) * math.sqrt(1.0 / (cin * k * k))).astype(np.float32)
         self._w = torch.from_numpy(w).permute(0, 2, 3, 1).contiguous().to(self.device)
-        self._norm = {"weight": torch.ones(cout, **f), "bias": torch.zeros(cout, **f), "running_mean": torch.zeros(cout, **f),
-                      "running_var": torch.ones(cout, **f)}
-        self.mean, self.inv_std, self.sums = torch.empty(cout, **f), torch.empty(cout, **f), torch.empty((3, cout), **f)
+        self.norm = BatchNormAct(cout, "silu", self.eps, self.momentum, self.device)
         self._wf = torch.empty((cout, k * k, cin), dtype=BF16, device=self.device)
         self._wd = torch.empty((cin, k * k, cout), dtype=BF16, device=self.device)
-        self._g = None
+        self._gw = None
         self._saved = None
-        self._eval_inv_std = None
         self.repack()
+
+    mean = property(lambda self: self.norm.mean)          # the batch statistics of the last training forward
+    inv_std = property(lambda self: self.norm.inv_std)
+    sums = property(lambda self: self.norm.sums)
 
     # ---- parameters ------------------------------------------------------------------------------------------------------------------------
     def _shapes(self):
@@ -138,31 +104,25 @@ class ConvBNSiLU:
 
     def params(self):
         """The trainable fp32 device masters by name (weight: the OIHW view of the OHWI master)."""
-        return {"weight": self._w.permute(0, 3, 1, 2), "norm.weight": self._norm["weight"], "norm.bias": self._norm["bias"]}
+        return {"weight": self._w.permute(0, 3, 1, 2), "norm.weight": self.norm.p["weight"], "norm.bias": self.norm.p["bias"]}
 
     def repack(self):
         ops.weight_pack(self._w, None, self._wf, self._wd, self.cout, self.k * self.k, self.cin)
-        if self._eval_inv_std is not None:
-            self.refresh_eval()
 
     def refresh_eval(self):
-        """1 / sqrt(running_var + eps) for the eval() forward, computed once (at eval() / after a load) instead of per call."""
-        self._eval_inv_std = 1.0 / torch.sqrt(self._norm["running_var"] + self.eps)
+        self.norm.refresh_eval()
 
     def state_dict(self):
-        out = {"weight": self._w.permute(0, 3, 1, 2).contiguous().cpu()}
-        out.update({f"norm.{k}": self._norm[k].detach().cpu().clone() for k in NORM_KEYS})
-        return out
+        return {"weight": self._w.permute(0, 3, 1, 2).contiguous().cpu(), **self.norm.state("norm.")}
 
     def load_state_dict(self, state):
-        p = _load(state, self._shapes(), self.device)
+        p = load_strict(state, self._shapes(), self.device)
         self._w.copy_(p["weight"].permute(0, 2, 3, 1))
-        for k in NORM_KEYS:
-            self._norm[k].copy_(p[f"norm.{k}"])
+        self.norm.load(p, "norm.")
         self.repack()
 
     def train(self, mode=True):
-        self.training = bool(mode)
+        self.training = self.norm.training = bool(mode)
         if not self.training:
             self.refresh_eval()
         return self
@@ -171,9 +131,11 @@ class ConvBNSiLU:
         return self.train(False)
 
     def grads(self):
-        if self._g is None:
+        """Copies, not views of the storage the next backward writes."""
+        if self._gw is None:
             raise RuntimeError("grads() before a backward")
-        return {"weight": self._g["w"].permute(0, 3, 1, 2).contiguous(), "norm.weight": self._g["gamma"], "norm.bias": self._g["beta"]}
+        return {"weight": self._gw.permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format),
+                "norm.weight": self.norm.g["weight"].clone(), "norm.bias": self.norm.g["bias"].clone()}
 
     # ---- forward / backward ------------------------------------------------------------------------------------------------------------------
     def out_size(self, H, W):
@@ -186,17 +148,10 @@ class ConvBNSiLU:
         Ho, Wo = self.out_size(H, W)
         gin, gout = ops.single(N, H, W), ops.single(N, Ho, Wo)
         d = ops.conv_desc(gin, gout, self.cin, self.cout, self.k, self.k, self.stride, self.pad)
-        C, M, n = self.cout, N * Ho * Wo, self._norm
-        y = torch.empty((M, C), dtype=BF16, device=self.device)
+        y = torch.empty((N * Ho * Wo, self.cout), dtype=BF16, device=self.device)
         ops.conv2d_fwd(d, x, self._wf, None, y)
-        if self.training:
-            ops.bn_stats_fwd(y, gout, C, self.eps, self.momentum, self.mean, self.inv_std, self.sums, n["running_mean"], n["running_var"],
-                             _ws(ops.bn_workspace_bytes(M, C), self.device))
-            mean, inv_std = self.mean, self.inv_std
-        else:
-            mean, inv_std = n["running_mean"], self._eval_inv_std
-        z = ops.bn_silu_fwd(y, gout, mean, inv_std, n["weight"], n["bias"], torch.empty_like(y), gout, C)
-        self._saved = (x, y, d, gout, self.training)
+        z = self.norm.forward_pm(y, N, Ho, Wo)          # (the norm keeps y for its backward: the same tensor as y_pm)
+        self._saved = (x, d, self.training)
         self.y_pm = y
         return z
 
@@ -205,23 +160,17 @@ class ConvBNSiLU:
         second reader of a shared input).  accumulate=True adds the parameter gradients onto those of the previous backward."""
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
-        x, y, d, gout, training = self._saved
+        x, d, training = self._saved
         if not training:
             raise RuntimeError("backward() through a norm in eval() mode is not built")
-        C, M, n, f = self.cout, y.shape[0], self._norm, dict(dtype=F32, device=self.device)
+        M, C = self.y_pm.shape
         if tuple(g.shape) != (M, C) or g.dtype != BF16:
             raise ValueError(f"backward_pm: expected bf16 {(M, C)}, got {g.dtype} {tuple(g.shape)}")
-        dgamma, dbeta = torch.empty(C, **f), torch.empty(C, **f)
-        ops.bn_silu_bwd_reduce(g, gout, y, gout, self.mean, self.inv_std, n["weight"], n["bias"], C, dgamma, dbeta,
-                               _ws(ops.bn_workspace_bytes(M, C), self.device))
-        gy = ops.bn_silu_bwd_apply(g, gout, y, gout, self.mean, self.inv_std, n["weight"], n["bias"], dgamma, dbeta, self.sums[0],
-                                   torch.empty_like(g), gout, C)
-        if self._g is None or not accumulate:
+        gy = self.norm.backward_pm(g, accumulate)
+        if self._gw is None:
             accumulate = False
-            self._g = {"w": torch.empty_like(self._w), "gamma": dgamma, "beta": dbeta}
-        else:
-            self._g["gamma"], self._g["beta"] = self._g["gamma"] + dgamma, self._g["beta"] + dbeta
-        ops.conv2d_wgrad(d, x, gy, self._g["w"], _ws(ops.conv2d_wgrad_workspace_bytes(d), self.device), accumulate=accumulate)
+            self._gw = torch.empty_like(self._w)
+        ops.conv2d_wgrad(d, x, gy, self._gw, workspace(ops.conv2d_wgrad_workspace_bytes(d), self.device), accumulate=accumulate)
         if dx is None:
             dx = ops.conv2d_dgrad(d, gy, self._wd, torch.empty_like(x))
         else:
@@ -232,23 +181,23 @@ class ConvBNSiLU:
         return dx
 
     def __call__(self, x):
-        _need_device(x, "ConvBNSiLU")
+        need_device(x, "ConvBNSiLU")
         N, C, H, W = x.shape
         if C != self.cin:
             raise ValueError(f"input has {C} channels, the layer {self.cin}")
         self._in_size = (N, H, W)
-        return _to_nchw(self.forward_pm(_to_pm(x), N, H, W), N, *self.out_size(H, W))
+        return to_nchw(self.forward_pm(to_pm(x), N, H, W), N, *self.out_size(H, W))
 
     forward = __call__
 
     def backward(self, dy, accumulate=False):
-        _need_device(dy, "ConvBNSiLU.backward")
+        need_device(dy, "ConvBNSiLU.backward")
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         N, H, W = self._in_size
         if tuple(dy.shape) != (N, self.cout, *self.out_size(H, W)):
             raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output")
-        return _to_nchw(self.backward_pm(_to_pm(dy), accumulate), N, H, W)
+        return to_nchw(self.backward_pm(to_pm(dy), accumulate), N, H, W)
 
 
 class _PredConv:
@@ -278,7 +227,7 @@ class _PredConv:
         if self.gw is None or not accumulate:
             accumulate = False
             self.gw, self.gb = torch.empty_like(self.w), torch.empty_like(self.b)
-        ops.conv2d_wgrad_bias(d, x, g, self.gw, self.gb, _ws(ops.conv2d_wgrad_bias_workspace_bytes(d), self.device), accumulate=accumulate)
+        ops.conv2d_wgrad_bias(d, x, g, self.gw, self.gb, workspace(ops.conv2d_wgrad_bias_workspace_bytes(d), self.device), accumulate=accumulate)
         return ops.conv2d_dgrad(d, g, self.wd, torch.empty_like(x))
 
 
@@ -302,7 +251,7 @@ class YOLOXHead:
         K, mid = num_classes, mid_channels
         self.num_anchors, self.num_classes, self.prior_prob = 1, K, prior_prob
         self.in_channels, self.mid_channels, self.device, self.training = in_channels, mid, torch.device(device), True
-        self.cls_ld = (K + 7) // 8 * 8
+        self.cls_ld = round_up8(K)
         self.stems, self.cls_convs, self.reg_convs, self.cls_preds, self.regobj_preds = [], [], [], [], []
         bias_value = -math.log((1 - prior_prob) / prior_prob)
         for l, c in enumerate(in_channels):
@@ -359,8 +308,7 @@ class YOLOXHead:
         if self.cls_preds[0].gw is None:
             raise RuntimeError("grads() before a backward")
         g = {f"{n}.{k}": v for n, b in self._blocks() for k, v in b.grads().items()}
-        g.update(self._pred_views("gw"))
-        g.update(self._pred_views("gb"))
+        g.update({k: v.clone() for which in ("gw", "gb") for k, v in self._pred_views(which).items()})
         return self._ordered(g)
 
     def state_dict(self):
@@ -369,7 +317,7 @@ class YOLOXHead:
         return self._ordered(s)
 
     def load_state_dict(self, state):
-        p = _load(state, self._shapes(), self.device)
+        p = load_strict(state, self._shapes(), self.device)
         for n, b in self._blocks():
             b.load_state_dict({k[len(n) + 1:]: v for k, v in p.items() if k.startswith(n + ".")})
         for w in ("w", "b"):
@@ -435,20 +383,20 @@ class YOLOXHead:
 
     def __call__(self, feats):
         for x in feats:
-            _need_device(x, "YOLOXHead")
+            need_device(x, "YOLOXHead")
         N = int(feats[0].shape[0])
         for x, c in zip(feats, self.in_channels):
             if x.dim() != 4 or x.shape[1] != c or x.shape[0] != N:
                 raise ValueError(f"YOLOXHead: level input {tuple(x.shape)}, expected (N, {c}, H, W)")
         sizes = [(int(x.shape[2]), int(x.shape[3])) for x in feats]
-        cls, box_obj = self.forward_pm([_to_pm(x) for x in feats], N, sizes)
+        cls, box_obj = self.forward_pm([to_pm(x) for x in feats], N, sizes)
         K, P = self.num_classes, sum(h * w for h, w in sizes)
         c3, b3 = cls.view(N, P, -1), box_obj.view(N, P, 8)
         logits, offsets, objs, p0 = [], [], [], 0
         for h, w in sizes:
-            logits.append(_to_nchw(c3[:, p0:p0 + h * w, :K], N, h, w))
-            offsets.append(_to_nchw(b3[:, p0:p0 + h * w, 0:4], N, h, w))
-            objs.append(_to_nchw(b3[:, p0:p0 + h * w, 4:5], N, h, w))
+            logits.append(to_nchw(c3[:, p0:p0 + h * w, :K], N, h, w))
+            offsets.append(to_nchw(b3[:, p0:p0 + h * w, 0:4], N, h, w))
+            objs.append(to_nchw(b3[:, p0:p0 + h * w, 4:5], N, h, w))
             p0 += h * w
         return logits, offsets, objs
 
@@ -457,7 +405,7 @@ class YOLOXHead:
     def backward(self, d_logits, d_offsets, d_objs, accumulate=False):
         """Gradients with respect to the three returned lists -> the per-level d_feats, NCHW fp32."""
         for t in (*d_logits, *d_offsets, *d_objs):
-            _need_device(t, "YOLOXHead.backward")
+            need_device(t, "YOLOXHead.backward")
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         _, N, sizes, P = self._saved
@@ -473,4 +421,4 @@ class YOLOXHead:
             d_bo[:, p0:p0 + h * w, 4] = gb.reshape(N, h * w)
             p0 += h * w
         d_feats = self.backward_pm(d_cls.view(N * P, -1), d_bo.view(N * P, 8), accumulate)
-        return [_to_nchw(g, N, h, w) for g, (h, w) in zip(d_feats, sizes)]
+        return [to_nchw(g, N, h, w) for g, (h, w) in zip(d_feats, sizes)]

@@ -27,7 +27,7 @@ import torch
 import torch.nn.functional as TF
 
 from basedet_amd import ops
-from basedet_amd._lib import BasedetHipError
+from basedet_amd.layers._pm import need_device_all, round_up8
 from basedet_amd.utils.registry import registers
 
 from . import params as P
@@ -35,15 +35,7 @@ from .fpn_base import FPNDetector
 
 __all__ = ["CenterNet", "CenterNetGT", "CenterNetDecoder", "centernet_ground_truth", "gather_feature", "modified_focal_loss", "reg_l1_loss"]
 
-
-def _dev(*tensors):
-    for t in tensors:
-        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise BasedetHipError("basedet_amd.models.centernet needs tensors on a HIP device; there is no CPU fallback")
-
-
-def _ld(K):
-    return (K + 7) // 8 * 8
+_MODULE = "basedet_amd.models.centernet"          # (named in the refusal of a host tensor)
 
 
 def _to_pm(x, ld):
@@ -62,7 +54,7 @@ def centernet_ground_truth(gt_boxes, num_gt, cfg):
     """CenterNet.get_ground_truth (centernet.py:74-127): gt_boxes fp32 (N, G, 5) xyxy + 1-based label, num_gt int32 (N,) -- the img_info
     count of the reference -- and the config -> gt_dict {score_map (N, K, H, W), wh, reg (N, T, 2), reg_mask (N, T), index int32 (N, T)}
     plus num_pos (1,), the number of map elements equal to 1.  score_map is a view of the kernel's pixel-major (N, H*W, K) map."""
-    _dev(gt_boxes, num_gt)
+    need_device_all((gt_boxes, num_gt), _MODULE)
     m = cfg.MODEL
     K, T = int(cfg.DATA.NUM_CLASSES), int(m.HEAD.TENSOR_DIM)
     H, W = (int(v) for v in m.OUTPUT_SIZE)
@@ -75,7 +67,7 @@ def centernet_ground_truth(gt_boxes, num_gt, cfg):
 def gather_feature(fmap, index, mask=None, use_transform=False):
     """centernet.py:189-205: rows `index` (B, T) of fmap (B, P, C) -- or of an NCHW map with use_transform -- optionally only the rows
     where mask is set, flattened to (-1, C)."""
-    _dev(fmap, index, mask)
+    need_device_all((fmap, index, mask), _MODULE)
     if use_transform:
         fmap = fmap.flatten(2).transpose(1, 2)
     C = fmap.shape[-1]
@@ -89,7 +81,7 @@ class _Focal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt):
         n, k, h, w = pred.shape
-        ld = _ld(k)
+        ld = round_up8(k)
         p = pred.float()
         logits = _to_pm(torch.log(p) - torch.log1p(-p), ld)
         gmap = gt.float().permute(0, 2, 3, 1).reshape(n * h * w, k).contiguous()
@@ -113,7 +105,7 @@ def modified_focal_loss(pred, gt):
     """centernet.py:218-242: pred the head's probabilities (N, K, H, W), gt the score map."""
     if pred.shape != gt.shape or pred.dim() != 4:
         raise ValueError("modified_focal_loss: pred and gt are (N, K, H, W) tensors of one shape")
-    _dev(pred, gt)
+    need_device_all((pred, gt), _MODULE)
     return _Focal.apply(pred, gt)
 
 
@@ -141,7 +133,7 @@ def reg_l1_loss(output, mask, index, target):
     """centernet.py:208-215: output (N, 2, H, W), mask (N, T), index (N, T), target (N, T, 2)."""
     if output.shape[1] != 2 or tuple(target.shape) != tuple(index.shape) + (2,) or mask.shape != index.shape:
         raise ValueError("reg_l1_loss: output (N, 2, H, W), mask and index (N, T), target (N, T, 2)")
-    _dev(output, mask, index, target)
+    need_device_all((output, mask, index, target), _MODULE)
     return _RegL1.apply(output, mask, index, target)
 
 
@@ -158,8 +150,8 @@ class CenterNetDecoder:
             raise ValueError("CenterNetDecoder.decode: wh and reg have two channels")
         if not 0 < K <= min(2048, h * w):
             raise ValueError(f"CenterNetDecoder.decode: K={K} must lie in 1..min(2048, H*W)")
-        _dev(fmap, wh, reg)
-        ld = _ld(c)
+        need_device_all((fmap, wh, reg), _MODULE)
+        ld = round_up8(c)
         p = fmap.float()
         logits = _to_pm(torch.log(p) - torch.log1p(-p), ld)
         whp = _to_pm(wh.float(), 8)
@@ -192,7 +184,7 @@ class CenterNetDecoder:
     @staticmethod
     def pseudo_nms(fmap, pool_size=3):
         """centernet.py:313-325: keep the elements that equal the maximum of their pool_size window, zero the others."""
-        _dev(fmap)
+        need_device_all((fmap,), _MODULE)
         f = fmap.float()
         peak = TF.max_pool2d(f, pool_size, stride=1, padding=(pool_size - 1) // 2) == f
         return f * peak.float()
@@ -201,7 +193,7 @@ class CenterNetDecoder:
     def topk_score(scores, K=40):
         """centernet.py:327-352: the K best per class plane, then the K best of those per image -> (scores, pixel index, class, y, x),
         each (batch, K)."""
-        _dev(scores)
+        need_device_all((scores,), _MODULE)
         b, c, h, w = scores.shape
         per_cls, pix = torch.topk(scores.reshape(b, c, h * w), K)
         best, pos = torch.topk(per_cls.reshape(b, c * K), K)

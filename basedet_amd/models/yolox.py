@@ -13,20 +13,12 @@ One departure from the reference: the gt is xyxy everywhere, and 
 import torch
 
 from basedet_amd import ops
-from basedet_amd._lib import BasedetHipError
+from basedet_amd.layers._pm import need_device_all, round_up8
 from basedet_amd.layers.box_ops import FastPointGenerator
 
 __all__ = ["yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs", "yolox_head_step"]
 
-
-def _dev(*tensors):
-    for t in tensors:
-        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise BasedetHipError("basedet_amd.models.yolox needs tensors on a HIP device; there is no CPU fallback")
-
-
-def _ld(K):
-    return (K + 7) // 8 * 8
+_MODULE = "basedet_amd.models.yolox"          # (named in the refusal of a host tensor)
 
 
 def _check_levels(logits, offsets, objs, strides):
@@ -47,7 +39,7 @@ def pack_head_outputs(logits, offsets, objs):
     sizes = [(int(x.shape[2]), int(x.shape[3])) for x in logits]
     P = sum(h * w for h, w in sizes)
     dev = logits[0].device
-    cls = torch.zeros((N, P, _ld(K)), dtype=torch.bfloat16, device=dev)
+    cls = torch.zeros((N, P, round_up8(K)), dtype=torch.bfloat16, device=dev)
     box_obj = torch.zeros((N, P, 8), dtype=torch.bfloat16, device=dev)
     p0 = 0
     for x, o, b, (h, w) in zip(logits, offsets, objs, sizes):
@@ -89,7 +81,7 @@ def yolox_assignments(cls, box_obj, points, strides, gt_boxes, num_gt, K=None, l
         points = torch.cat(list(points), 0)
     if lvl_start is None:
         raise ValueError("yolox_assignments: points given as one tensor need lvl_start")
-    _dev(cls, box_obj, points, gt_boxes, num_gt)
+    need_device_all((cls, box_obj, points, gt_boxes, num_gt), _MODULE)
     K = int(cls.shape[1]) if K is None else int(K)
     return ops.yolox_assign(cls, K, box_obj, points.float().contiguous(), lvl_start, list(strides), gt_boxes.float().contiguous(),
                             num_gt.to(torch.int32).contiguous())
@@ -123,7 +115,7 @@ def yolox_losses(logits, offsets, objs, gt_boxes, num_gt, strides, use_l1=False)
     """YOLOX.get_losses behind network_forward (yolox.py:155-265): the reference's three per-level NCHW lists, gt_boxes (N, Gmax, 5) and
     num_gt (N,) -> {total_loss, iou_loss (times 5), l1_loss, obj_loss, cls_loss}.  total_loss carries the gradient to the inputs."""
     _check_levels(logits, offsets, objs, strides)
-    _dev(*logits, *offsets, *objs, gt_boxes, num_gt)
+    need_device_all((*logits, *offsets, *objs, gt_boxes, num_gt), _MODULE)
     total, parts = _Losses.apply(gt_boxes, num_gt, tuple(int(s) for s in strides), bool(use_l1), len(logits), *logits, *offsets, *objs)
     return {"total_loss": total, "iou_loss": parts[0], "l1_loss": parts[3], "obj_loss": parts[1], "cls_loss": parts[2]}
 
@@ -132,7 +124,7 @@ def yolox_head_step(head, feats, N, sizes, gt_boxes, num_gt, strides, use_l1=Fal
     """One training step of a layers.YOLOXHead on its own layout, no repack: forward_pm -> ops.yolox_assign -> ops.yolox_loss_fwd_bwd ->
     backward_pm.  feats: per level bf16 (N H_l W_l, C_l); sizes [(H_l, W_l)].  Returns (parts fp32 (4,) = 5 * iou, obj, cls, l1;
     d_feats per level; (matched, iou_t, stats))."""
-    _dev(*feats, gt_boxes, num_gt)
+    need_device_all((*feats, gt_boxes, num_gt), _MODULE)
     cls, box_obj = head.forward_pm(feats, N, sizes)
     points, lvl_start = _points(sizes, strides, cls.device)
     gt = gt_boxes.float().contiguous()
@@ -150,7 +142,7 @@ def yolox_inference(logits, offsets, objs, img_info, cfg, strides=(8, 16, 32), k
     box_scores, box_labels)."""
     from ..structures import Boxes, Container
     _check_levels(logits, offsets, objs, strides)
-    _dev(*logits, *offsets, *objs, img_info)
+    need_device_all((*logits, *offsets, *objs, img_info), _MODULE)
     t = cfg.TEST
     B, K = int(logits[0].shape[0]), int(logits[0].shape[1])
     cls, box_obj, sizes = pack_head_outputs(logits, offsets, objs)
@@ -162,7 +154,7 @@ def yolox_inference(logits, offsets, objs, img_info, cfg, strides=(8, 16, 32), k
     tk_idx, tk_sc, tk_cnt = torch.empty((B, Ln, k), **i32), torch.empty((B, Ln, k), **f32), torch.empty((B, Ln), **i32)
     ws = torch.empty((ops.det_select_workspace_bytes(B, Ln, P, K, k),), dtype=torch.uint8, device=dev)
     ops.det_select(cls, B, P, K, lvl_start[:-1], lvl_rows, k, t.CLS_THRESHOLD, tk_idx, tk_sc, tk_cnt, ws, ctr=box_obj, ctr_ld=8, ctr_off=4,
-                   ld=_ld(K))
+                   ld=round_up8(K))
     boxes, scores, labels = ops.yolox_candidates(tk_idx, tk_sc, tk_cnt, K, points, lvl_start, list(strides), box_obj)
     max_out = int(t.MAX_BOXES_PER_IMAGE)
     keep, num = torch.empty((B, max_out), **i32), torch.zeros((B,), **i32)

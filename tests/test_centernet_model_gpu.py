@@ -211,7 +211,11 @@ def test_neck_and_head_gradients_in_the_arena():
     assert f"upsample.deconv3.dcn.{dcn}.weight" in ref
     # the arena holds them: every gradient view lies inside arena.g, nothing was allocated beside it
     lo, hi = model.arena.g.data_ptr(), model.arena.g.data_ptr() + 4 * model.arena.g.numel()
-    for t in list(model.head._g.values()) + [model.neck.deconv1._g_up, model.neck.deconv1.dcn._grads["dcn_w"], model.neck.deconv2.up_bn.g["weight"]]:
+    held = list(model.head._store.g.values())
+    for _, l in model.neck.layers():
+        held += [*l._store.g.values(), *l.dcn._store.g.values(), *l.dcn_bn.g.values(), *l.up_bn.g.values()]
+    assert len(held) == 8 + 3 * (1 + 4 + 2 + 2)
+    for t in held:
         assert lo <= t.data_ptr() < hi
 
 

@@ -302,3 +302,69 @@ def test_layer_against_composed_oracle(modulated):
 def nchw_pm(t):
     """NCHW fp32 -> NHWC (the oracle's layout)."""
     return t.permute(0, 2, 3, 1)
+
+
+# ---- one storage path: a layer on its own storage and one adopt()ed onto a caller's -------------------------------------------------------
+def _pair(modulated, seed=3):
+    """Two layers of one seed at LAYER_SHAPE: `own` on the storage it allocated, `ad` adopted onto flat fp32 tensors."""
+    import basedet.layers as BL
+    _, _, _, Cin, Cout = LAYER_SHAPE
+    cls = BL.ModulatedDeformConvWithOff if modulated else BL.DeformConvWithOff
+    own, ad = cls(Cin, Cout, seed=seed), cls(Cin, Cout, seed=seed)
+    w_flat, g_flat, w, g = util.flat_storage(ad.arena_shapes())
+    ad.adopt(w, g)
+    return own, ad, w_flat, g_flat
+
+
+def _other_state(layer, seed):
+    g = torch.Generator().manual_seed(seed)
+    return {k: v + 0.05 * torch.randn(v.shape, generator=g) for k, v in layer.state_dict().items()}
+
+
+@pytest.mark.parametrize("modulated", [False, True], ids=["dcnv1", "dcnv2"])
+def test_layer_standalone_equals_adopted(modulated):
+    """The same forward and backward on both: y and every entry of grads() are the same bits -- the offset convolution's gradients are
+    bd_conv2d_wgrad_bias of d_om, which repeats bit for bit (above).  Only d_x, which bd_deform_conv_bwd_data sums with fp32 atomics
+    (DESIGN 4t), is held to the rel-L2 bound of two runs of one build, 2^-10
+    (tests/test_centernet_model_gpu.py::test_neck_and_head_gradients_in_the_arena)."""
+    c = _layer_case(modulated)
+    own, ad, w_flat, g_flat = _pair(modulated)
+    x, dy = c["x"].cuda(), c["dy"].cuda()
+    ya, yb = own(x), ad(x)
+    assert torch.equal(ya, yb)
+    da, db = own.backward(dy), ad.backward(dy)
+    ga, gb = own.grads(), ad.grads()
+    assert list(ga) == list(gb) == own.names()
+    for k in ga:
+        assert ga[k].shape == gb[k].shape and torch.equal(ga[k], gb[k]), k
+    assert util.rel_l2(da, db) <= 2.0 ** -10
+    assert all(util.lies_inside(t, g_flat) for t in ad._store.g.values()) and all(util.lies_inside(t, w_flat) for t in ad.params().values())
+    assert not any(bool(torch.isnan(t).any()) for t in ad._store.g.values()), "a backward writes every gradient element, pad rows included"
+
+
+@pytest.mark.parametrize("adopted", [False, True], ids=["own", "adopted"])
+@pytest.mark.parametrize("modulated", [False, True], ids=["dcnv1", "dcnv2"])
+def test_layer_loads_and_repacks_in_place(modulated, adopted):
+    """load_state_dict() copies into the masters (a params() view taken before shows the loaded values, at the same address) and the next
+    forward is that of a fresh layer loaded with the same state; repack() writes the bf16 operands where they are, and after an in-place
+    change through params() gives the forward of a fresh layer loaded with the changed state."""
+    c = _layer_case(modulated)
+    own, ad, _, _ = _pair(modulated)
+    layer, x = (ad if adopted else own), c["x"].cuda()
+    held = layer.params()
+    ptrs = {k: v.data_ptr() for k, v in held.items()}
+    state = _other_state(layer, 5)
+    layer.load_state_dict(state)
+    assert {k: v.data_ptr() for k, v in layer.params().items()} == ptrs
+    assert all(torch.equal(held[k].cpu(), state[k]) for k in state)
+    fresh = type(layer)(*LAYER_SHAPE[3:], seed=11)
+    fresh.load_state_dict(state)
+    assert torch.equal(layer(x), fresh(x))
+    packed = [layer._off_wf, layer._off_wd, layer._dcn_wf, layer._dcn_wd]
+    where = [t.data_ptr() for t in packed]
+    for k, v in held.items():
+        v.mul_(0.5 if k.endswith(".weight") else -1.0)
+    layer.repack()
+    assert [t.data_ptr() for t in (layer._off_wf, layer._off_wd, layer._dcn_wf, layer._dcn_wd)] == where
+    fresh.load_state_dict(layer.state_dict())
+    assert torch.equal(layer(x), fresh(x)) and not torch.equal(layer.state_dict()[layer.DCN_NAME + ".weight"], state[layer.DCN_NAME + ".weight"])

@@ -290,6 +290,27 @@ def test_conv_bn_silu_layer(k):
         _ratio(got[name], o64[name], of[name], f"k={k} {name}")
 
 
+@pytest.mark.parametrize("k,stride", [(1, 1), (3, 2)])
+def test_conv_bn_silu_grads_do_not_alias_the_storage(k, stride):
+    """What grads() returned after one backward does not change at the next, which overwrites the same storage (k = 1: the OIHW view of
+    the OHWI weight gradient is contiguous as it stands, so only a copy keeps it).  The norm's batch statistics are the layer's."""
+    import basedet.layers as BL
+    N, C, H, W = 2, 16, 5, 7
+    g = torch.Generator().manual_seed(50 + k)
+    x = torch.randn(N, C, H, W, generator=g).cuda()
+    layer = BL.ConvBNSiLU(C, C, k, stride=stride, seed=9)
+    z = layer(x)
+    dy = (0.1 * torch.randn(z.shape, generator=g)).to(BF).float().cuda()
+    layer.backward(dy)
+    assert layer.mean is layer.norm.mean and layer.inv_std is layer.norm.inv_std and layer.sums is layer.norm.sums
+    kept = layer.grads()
+    copy = {k_: v.clone() for k_, v in kept.items()}
+    layer.backward(2 * dy)
+    again = layer.grads()
+    assert list(kept) == ["weight", "norm.weight", "norm.bias"]
+    assert all(torch.equal(kept[k_], copy[k_]) and not torch.equal(again[k_], kept[k_]) for k_ in kept)
+
+
 # ---- YOLOXHead -----------------------------------------------------------------------------------------------------------------------------------
 def _pm(feats):
     return [util.nchw_to_pm(x) for x in feats]

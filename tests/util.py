@@ -31,6 +31,37 @@ def rel_l2(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
+def flat_storage(shapes, device="cuda"):
+    """What a model's parameter arena gives a layer's adopt(): one flat fp32 tensor for the masters and one for the gradients, and
+    {name: view} of each in `shapes` (the layer's arena_shapes()), in 256-byte aligned slices like ParamArena's.
+    -> (w_flat, g_flat, w_views, g_views); the gradients start at NaN."""
+    pad = lambda s: (math.prod(s) + 63) // 64 * 64
+    total = sum(pad(s) for s in shapes.values())
+    flats, views = [], []
+    for fill in (0.0, float("nan")):
+        f, v, o = torch.full((total,), fill, dtype=torch.float32, device=device), {}, 0
+        for k, s in shapes.items():
+            v[k] = f[o:o + math.prod(s)].view(s)
+            o += pad(s)
+        flats.append(f)
+        views.append(v)
+    return flats[0], flats[1], views[0], views[1]
+
+
+def lies_inside(t, flat):
+    return flat.data_ptr() <= t.data_ptr() and t.data_ptr() + t.numel() * t.element_size() <= flat.data_ptr() + flat.numel() * flat.element_size()
+
+
+def norm_record(C, device="cuda"):
+    """A hand-filled record with models/live_norm.py BatchNormState's fields, for BatchNormAct.adopt: every vector a view of one tensor
+    (zeros, as LiveNorms.allocate leaves them; the two gradient vectors start at NaN)."""
+    import types
+    buf = torch.zeros((11, C), dtype=torch.float32, device=device)
+    buf[9:] = float("nan")
+    return types.SimpleNamespace(buf=buf, gamma=buf[0], beta=buf[1], running_mean=buf[2], running_var=buf[3], mean=buf[4], inv_std=buf[5],
+                                 sums=buf[6:9], g_gamma=buf[9], g_beta=buf[10])
+
+
 def pack_weights(ops, w_oihw, row_scale=None):
     """fp32 OIHW (cpu) -> (w_fwd, w_dgrad) bf16 packed device tensors via bd_weight_pack."""
     co, ci, r, s = w_oihw.shape
