@@ -219,6 +219,14 @@ SIGNATURES = {
     "bd_yolox_loss_fwd_bwd": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
     # (topk_idx, topk_score, topk_cnt, B, L, k, lvl_start, strides, K, points, P, box_obj, boxes, scores, labels, stream)
     "bd_yolox_candidates": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    # CSPDarknet / YOLOPAFPN glue (yolox_neck.hip; added without an ABI break, as the bd_yolox_* entries were)
+    "bd_spp_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "bd_spp_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    # (a, b, M, Ca, Cb, up, N, H, W, out, stream)
+    "bd_cat2_fwd": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
+    # (g, M, Ca, Cb, up, N, H, W, d_a, acc_a, d_b, acc_b, stream)
+    "bd_cat2_bwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P]),
+    "bd_focus_fwd": (_I, [_P, _I, _I, _I, _P, _P]),
     "bd_rcnn_predict": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bd_det_candidates": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P]),
     "bd_det_finalize": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),

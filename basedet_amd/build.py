@@ -53,6 +53,7 @@ SOURCES = {
     # the Gaussian radius is the float32 evaluation of the reference's expressions, one rounding per operation (tests/test_centernet_gpu.py)
     "centernet.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "yolox.hip": ["-ffp-contract=off"],
+    "yolox_neck.hip": [],
     "center_head.hip": [],
     "norm.hip": [],
     # IEEE division and square root for the statistics (inv_std of a constant channel is 1 / sqrt(eps) to the last bit)

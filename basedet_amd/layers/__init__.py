@@ -11,5 +11,6 @@ from .roi_pool import assign_rois, roi_pool, sample_labels  # noqa: F401
 from .deformable import DeformConvWithOff, ModulatedDeformConvWithOff  # noqa: F401
 from .center_head import CenterHead, CenternetDeconv, DeconvLayer, SingleHead  # noqa: F401
 from .yolox_head import ConvBNSiLU, YOLOXHead  # noqa: F401
+from .yolox_blocks import Bottleneck, CSPDarknet, CSPLayer, Focus, SPPBottleneck, YOLOPAFPN  # noqa: F401
 from .modules import FPN, PointHead, RetinaNetHead, build_backbone, resnet18, resnet34, resnet50, resnet101  # noqa: F401
 from ..structures import box_center, box_ioa, box_iou  # noqa: F401

@@ -155,9 +155,11 @@ class ConvBNSiLU:
         self.y_pm = y
         return z
 
-    def backward_pm(self, g, accumulate=False, dx=None):
+    def backward_pm(self, g, accumulate=False, dx=None, add=None, need_dx=True):
         """g bf16 [N Ho Wo][cout] -> the data gradient bf16 [N H W][cin]: a new tensor, or ADDED onto `dx` in place where one is given (the
-        second reader of a shared input).  accumulate=True adds the parameter gradients onto those of the previous backward."""
+        second reader of a shared input).  accumulate=True adds the parameter gradients onto those of the previous backward.  add: a
+        bf16 [N H W][cin] gradient the input received from another reader; the NEW tensor returned is the sum and `add` keeps its bits.
+        need_dx=False: no data gradient (the input is the image); returns None."""
         if self._saved is None:
             raise RuntimeError("backward() before a forward")
         x, d, training = self._saved
@@ -171,7 +173,13 @@ class ConvBNSiLU:
             accumulate = False
             self._gw = torch.empty_like(self._w)
         ops.conv2d_wgrad(d, x, gy, self._gw, workspace(ops.conv2d_wgrad_workspace_bytes(d), self.device), accumulate=accumulate)
-        if dx is None:
+        if add is not None and (dx is not None or tuple(add.shape) != tuple(x.shape) or add.dtype != BF16):
+            raise ValueError(f"backward_pm: add must be bf16 {tuple(x.shape)}, and is given without dx")
+        if not need_dx:
+            dx = None
+        elif add is not None:
+            dx = ops.conv2d_dgrad(d, gy, self._wd, torch.empty_like(x), add=add, flags=ops.EPI_ADD_BEFORE)
+        elif dx is None:
             dx = ops.conv2d_dgrad(d, gy, self._wd, torch.empty_like(x))
         else:
             if tuple(dx.shape) != tuple(x.shape) or dx.dtype != BF16:

@@ -1,8 +1,10 @@
 """YOLOX behind the head's last convolutions, on the kernels of csrc/yolox.hip (models/det/yolox.py:119-135, 150-408 of the reference):
 the SimOTA assignment (`yolox_assignments`), the four losses with gradients back to the head outputs (`yolox_losses`) and the inference
-chain (`yolox_inference`: bd_det_select -> bd_yolox_candidates -> bd_nms_batched -> bd_det_finalize).  The model class, CSPDarknet /
-YOLOPAFPN and the mosaic input are not built yet; what is here is what they will call.  The decoupled head is layers.YOLOXHead, and
-`yolox_head_step` runs it against the kernels here with no repack.
+chain (`yolox_inference`: bd_det_select -> bd_yolox_candidates -> bd_nms_batched -> bd_det_finalize).  The decoupled head is
+layers.YOLOXHead, and `yolox_head_step` runs it against the kernels here with no repack; the feature extractor is layers.YOLOPAFPN on
+layers.CSPDarknet, and `yolox_network_step` is one training step of the whole network from the normalised image down to the stem's
+parameter gradients.  The model class (arena, adopt(), inference from an image), the solver and the mosaic / mixup input are not built
+yet; what is here is what they will call.
 
 The kernels read the layout a fused head will write -- cls bf16 (N*P, round_up(K, 8)) and box_obj bf16 (N*P, 8): raw reg 0-3, obj logit
 4 -- with the P points of an image level after level, row-major inside a level.  `yolox_losses` and `yolox_inference` take the
@@ -16,7 +18,7 @@ from basedet_amd import ops
 from basedet_amd.layers._pm import need_device_all, round_up8
 from basedet_amd.layers.box_ops import FastPointGenerator
 
-__all__ = ["yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs", "yolox_head_step"]
+__all__ = ["yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs", "yolox_head_step", "yolox_network_step"]
 
 _MODULE = "basedet_amd.models.yolox"          # (named in the refusal of a host tensor)
 
@@ -133,6 +135,18 @@ def yolox_head_step(head, feats, N, sizes, gt_boxes, num_gt, strides, use_l1=Fal
     parts, d_cls, d_box_obj = ops.yolox_loss_fwd_bwd(cls, K, box_obj, points, lvl_start, list(strides), gt, matched, iou_t, stats,
                                                     use_l1=use_l1, grad_scale=1.0)
     return parts, head.backward_pm(d_cls, d_box_obj), (matched, iou_t, stats)
+
+
+def yolox_network_step(fpn, head, x_halo, N, H, W, gt_boxes, num_gt, strides=(8, 16, 32), use_l1=False):
+    """One training step of layers.YOLOPAFPN + layers.YOLOXHead: PAFPN forward -> yolox_head_step -> PAFPN backward, pixel-major bf16
+    throughout.  x_halo: the bf16 (N, H + 6, W + 8, 4) image bd_pad_normalize / bd_resize_pad_normalize / bd_affine_jitter_normalize
+    write, H and W multiples of 32.  Returns (parts fp32 (4,) = 5 * iou, obj, cls, l1; (matched, iou_t, stats)); the parameter gradients
+    are in fpn.grads() and head.grads()."""
+    need_device_all((x_halo, gt_boxes, num_gt), _MODULE)
+    feats, sizes = fpn.forward_pm(x_halo, N, H, W)
+    parts, d_feats, assigned = yolox_head_step(head, list(feats), N, sizes, gt_boxes, num_gt, strides, use_l1)
+    fpn.backward_pm(d_feats)
+    return parts, assigned
 
 
 def yolox_inference(logits, offsets, objs, img_info, cfg, strides=(8, 16, 32), k=1000):

@@ -1298,3 +1298,35 @@ def yolox_candidates(topk_idx, topk_score, topk_cnt, K, points, lvl_start, strid
     labels = torch.empty((B, Ln * k), dtype=torch.int32, device=dev)
     yolox_candidates_into(topk_idx, topk_score, topk_cnt, K, points, lvl_start, strides, box_obj, boxes, scores, labels)
     return boxes, scores, labels
+
+
+# ---- CSPDarknet / YOLOPAFPN glue (yolox_neck.hip) -------------------------------------------------------------------------------------------
+def spp_fwd(x, N, H, W, Cn, cat):
+    """x bf16 (N*H*W, Cn) -> cat bf16 (N*H*W, 4 Cn) = (x, maxpool5, maxpool9, maxpool13), stride 1; H * W <= 4096."""
+    check(L().bd_spp_fwd(ptr(x), N, H, W, Cn, ptr(cat), stream_ptr()), "bd_spp_fwd")
+    return cat
+
+
+def spp_bwd(g_cat, x, N, H, W, Cn, d_x):
+    """Adjoint of spp_fwd (first-maximum rule, fixed fp32 summation order, no atomics): d_x bf16 (N*H*W, Cn)."""
+    check(L().bd_spp_bwd(ptr(g_cat), ptr(x), N, H, W, Cn, ptr(d_x), stream_ptr()), "bd_spp_bwd")
+    return d_x
+
+
+def cat2_fwd(a, b, M, Ca, Cb, out, up=False, N=0, H=0, W=0):
+    """out bf16 (M, Ca + Cb) = (a, b); up: a is (N*(H/2)*(W/2), Ca), read through a nearest 2x upsample (M = N*H*W)."""
+    check(L().bd_cat2_fwd(ptr(a), ptr(b), M, Ca, Cb, int(bool(up)), N, H, W, ptr(out), stream_ptr()), "bd_cat2_fwd")
+    return out
+
+
+def cat2_bwd(g, M, Ca, Cb, d_a, d_b, up=False, N=0, H=0, W=0, acc_a=False, acc_b=False):
+    """The split of g bf16 (M, Ca + Cb): d_a (the 2x2 sums under `up`) and d_b, each written or, under its acc flag, added onto."""
+    check(L().bd_cat2_bwd(ptr(g), M, Ca, Cb, int(bool(up)), N, H, W, ptr(d_a), int(bool(acc_a)), ptr(d_b), int(bool(acc_b)), stream_ptr()),
+          "bd_cat2_bwd")
+    return d_a, d_b
+
+
+def focus_fwd(x_halo, N, H, W, out):
+    """x_halo bf16 (N, H+6, W+8, 4) -> out bf16 (N*(H/2)*(W/2), 16): Focus's space-to-depth, channels 12-15 zero."""
+    check(L().bd_focus_fwd(ptr(x_halo), N, H, W, ptr(out), stream_ptr()), "bd_focus_fwd")
+    return out

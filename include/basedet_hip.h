@@ -1047,6 +1047,37 @@ int bd_yolox_candidates(const int32_t* topk_idx, const float* topk_score, const 
                         const int32_t* lvl_start_host, const int32_t* strides_host, int K, const float* points, int P, const void* box_obj,
                         float* boxes, float* scores, int32_t* labels, bd_stream_t stream);
 
+/* The glue between the convolutions of CSPDarknet and YOLOPAFPN (yolox_neck.hip; layers/yolox_blocks.py; added without an ABI break, as
+ * the bd_yolox_* and bd_bn_silu_* entries were: bd_version() stays as it is and the binding refuses a library without these symbols by
+ * name).  Operands are bf16 pixel-major [rows][C], 16-byte aligned, every channel count a positive multiple of 8.  No atomics: every
+ * output has the same bits on every run.  A bad argument returns BD_EINVAL with a message and nothing is launched.
+ *
+ * bd_spp_fwd (yolo_block.py:36-60 between conv1 and conv2): x [N H W][C] -> cat [N H W][4C] = (x, maxpool5(x), maxpool9(x), maxpool13(x)),
+ *   stride 1, padding k/2, padding never wins (windows are clipped to the image).  max returns one of its operands, so the result is
+ *   torch.nn.functional.max_pool2d's on the same bf16 values bit for bit (+0 and -0 compare equal: which of the two a window that holds
+ *   both returns is not specified).  One workgroup holds an image's plane of 8 channels in LDS: H * W <= 4096 (64 x 64), else BD_EINVAL.
+ * bd_spp_bwd: its adjoint.  g_cat [N H W][4C], x as the forward read it -> d_x [N H W][C].  A pixel takes a window's gradient iff it is
+ *   the window's FIRST maximum in row-major order (strict > while scanning the clipped window row by row: bd_maxpool3x3s2_bwd's rule and
+ *   torch's CPU max_pool2d backward's).  d_x[p] = g_cat[p][0:C] + every taken gradient, summed in fp32 in this order: the identity
+ *   term, then k = 5, then 9, then 13, inside a k the window centres that contain p in row-major order; one rounding to bf16.  Gather
+ *   form.  Same plane limit.
+ * bd_cat2_fwd: out [M][Ca + Cb] = (a, b); a [M][Ca], b [M][Cb].  up != 0: M = N * H * W, a is [N (H/2) (W/2)][Ca] and is read through a
+ *   nearest-neighbour 2x upsample, out[n, y, x][0:Ca] = a[n, y/2, x/2]; H and W must be even.  up == 0: N, H, W are not read.  Bitwise.
+ * bd_cat2_bwd: the split of g [M][Ca + Cb].  d_b [M][Cb] = g[:, Ca:].  d_a = g[:, :Ca] (up == 0), or with up != 0 d_a [N (H/2) (W/2)][Ca] =
+ *   ((g[2y][2x] + g[2y][2x+1]) + g[2y+1][2x]) + g[2y+1][2x+1] in fp32.  acc_a / acc_b != 0: the bf16 value the output holds is added LAST
+ *   in fp32 (the second reader of a tensor adds its gradient onto the first's without an add pass).  Every element is rounded once; a
+ *   plain copy keeps its bits.
+ * bd_focus_fwd (basic_block.py:25-31): x_halo bf16 [N][H+6][W+8][4] as bd_pad_normalize, bd_resize_pad_normalize and
+ *   bd_affine_jitter_normalize write it (the image starts at row 3, column 4) -> out [N (H/2) (W/2)][16]: channels 0-2 the top-left pixel
+ *   of the 2x2 block, 3-5 bottom-left, 6-8 top-right, 9-11 bottom-right, 12-15 +0.  H and W even.  Bitwise; the halo is never read.  No
+ *   backward: the image has no gradient. */
+int bd_spp_fwd(const void* x, int N, int H, int W, int C, void* cat, bd_stream_t stream);
+int bd_spp_bwd(const void* g_cat, const void* x, int N, int H, int W, int C, void* d_x, bd_stream_t stream);
+int bd_cat2_fwd(const void* a, const void* b, int64_t M, int Ca, int Cb, int up, int N, int H, int W, void* out, bd_stream_t stream);
+int bd_cat2_bwd(const void* g, int64_t M, int Ca, int Cb, int up, int N, int H, int W, void* d_a, int acc_a, void* d_b, int acc_b,
+                bd_stream_t stream);
+int bd_focus_fwd(const void* x_halo, int N, int H, int W, void* out, bd_stream_t stream);
+
 /* The output convolutions of CenterHead (bd_version() >= 116; center_head.hip; layers/head/center_head.py:91-131: the three
  * SingleHead.out_conv, 1x1, C -> K / 2 / 2) in one launch per direction.  feat: bf16 [M][3C], the ReLU output of the three feat_convs
  * run as one 3C-row convolution -- channels [0,C) the cls tower, [C,2C) the wh tower, [2C,3C) the reg tower.  w_cls [K][C], w_wh [2][C],
