@@ -122,6 +122,7 @@ SIGNATURES = {
     "bd_h2d_destroy": (_I, [_P]),
     "bd_pad_normalize_nchw": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "bd_resize_pad_normalize": (_I, [_P, _L, C.POINTER(ImageDesc), _I, _I, _I, _P, _P, _P, _P]),
+    "bd_resize_bilinear_normalize": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "bd_affine_jitter_workspace_bytes": (_Z, [_I, _I, _I]),
     "bd_affine_jitter_normalize": (_I, [_P, _L, C.POINTER(AffineDesc), _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bd_maxpool3x3s2_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P]),

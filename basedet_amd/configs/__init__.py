@@ -283,9 +283,9 @@ class CenterNetConfig(DetectionConfig):
 
 class YOLOXConfig(DetectionConfig):
     """basedet/configs/det_model/yolox_cfg.py:6-117, key for key (the reference deletes DetectionConfig's MODEL section and
-    SOLVER.WARM_ITERS before / after merging its own).  What this build has of YOLOX so far is everything behind the head's last
-    convolutions (models/yolox.py), the head and the feature extractor (layers/yolox_head.py, layers/yolox_blocks.py); the model class,
-    the solver and the mosaic input are not built yet."""
+    SOLVER.WARM_ITERS before / after merging its own).  build_model() gives models.yolox.YOLOX, build_solver() solver.YOLOXSolver;
+    HOOKS.BUILDER_NAME selects YoloxLR and SyncSizeHook in DetTrainer.  The mosaic / mixup input (AUG.TRAIN_SETTING's MOSAIC_* / MIXUP_* /
+    HSV_* keys) is not built yet."""
 
     TEST_SIZE = 416
 

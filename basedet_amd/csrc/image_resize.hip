@@ -89,6 +89,59 @@ __global__ __launch_bounds__(256) void resize_pad_normalize_kernel(const uint8_t
     *reinterpret_cast<u32x4_t*>(out + px * 4) = o;
 }
 
+// ---- bd_resize_bilinear_normalize: a dense fp32 NCHW batch resized to one size (YOLOX's multi-scale pre_process) ------------------------
+// The sampling rule of torch.nn.functional.interpolate(mode="bilinear", align_corners=False), which is MegEngine's
+// F.vision.interpolate: src = max(0, (dst + 0.5) * in / out - 0.5), neighbours floor(src) and min(floor(src) + 1, in - 1).  The source
+// coordinate is float64 (in fp32 its rounding alone, ~800 * 2^-24 of a pixel, would move a blend of bytes by 1e-2); the fraction is cast
+// to fp32 once, and a blend is a + f (b - a) written as two explicit FMAs, fma(f, b, fma(-f, a, a)): two roundings per blend instead of the
+// four of a (1 - f) + b f, exact (= a) at f = 0 -- which makes dst == (H, W) bd_pad_normalize's bits.  Error against the float64 rule, for
+// values in [0, 255] (one rounding there is at most 2^-17): per blend the fraction's cast (255 * 2^-25) and two roundings, so 3 * 2^-17
+// after the horizontal pass and 6 * 2^-17 after the vertical one, under 4 * 2^-24 * 255.
+//
+// HBM-bound: 8 bytes written per output pixel, and the source is read once when upscaling (neighbouring lanes share taps in L1 / L2).  One
+// lane owns one output pixel of the halo buffer: its two column taps and two row taps are computed once and serve the three planes; a
+// wave reads runs of neighbouring columns of one source row per tap (coalesced up to the scale factor).
+struct LinTap { int i0, i1; float f; };
+
+__device__ __forceinline__ LinTap lin_tap(int o, double scale, int src) {
+    double c = ((double)o + 0.5) * scale - 0.5;
+    c = c < 0.0 ? 0.0 : c;
+    const double fl = floor(c);
+    LinTap t;
+    t.i0 = min((int)fl, src - 1);
+    t.i1 = min(t.i0 + 1, src - 1);
+    t.f = (float)(c - fl);
+    return t;
+}
+
+__device__ __forceinline__ float lerp_fma(float a, float b, float f) { return fmaf(f, b, fmaf(-f, a, a)); }
+
+__global__ __launch_bounds__(256) void resize_bilinear_normalize_kernel(const float* __restrict__ in, int H, int W, int dst_h, int dst_w,
+                                                                        int Hp, int Wp, double sy, double sx, float m0, float m1, float m2,
+                                                                        float s0, float s1, float s2, bf16_raw* __restrict__ out) {
+    const int Wb = Wp + 2 * HALO_X;
+    const int xb = blockIdx.x * 256 + threadIdx.x;
+    if (xb >= Wb) return;
+    const int yb = blockIdx.y, n = blockIdx.z;
+    const int y = yb - HALO_Y, x = xb - HALO_X;
+    u32x2_t o = {0u, 0u};
+    if (y >= 0 && y < Hp && x >= 0 && x < Wp) {
+        float v[3] = {0.f, 0.f, 0.f};          // beyond (dst_h, dst_w): the zero pad, normalised like bd_pad_normalize's
+        if (y < dst_h && x < dst_w) {
+            const LinTap ty = lin_tap(y, sy, H), tx = lin_tap(x, sx, W);
+            const long long plane = (long long)H * W, r0 = (long long)ty.i0 * W, r1 = (long long)ty.i1 * W;
+            const float* __restrict__ p = in + (long long)n * 3 * plane;
+#pragma unroll
+            for (int c = 0; c < 3; ++c, p += plane)
+                v[c] = lerp_fma(lerp_fma(p[r0 + tx.i0], p[r0 + tx.i1], tx.f), lerp_fma(p[r1 + tx.i0], p[r1 + tx.i1], tx.f), ty.f);
+        }
+        o[0] = pack_bf2((v[0] - m0) / s0, (v[1] - m1) / s1);
+        o[1] = pack_bf2((v[2] - m2) / s2, 0.f);
+    }
+    const long long px = ((long long)n * gridDim.y + yb) * Wb + xb;
+    *reinterpret_cast<u32x2_t*>(out + px * 4) = o;
+}
+
 }  // namespace
 
 extern "C" int bd_resize_pad_normalize(const uint8_t* packed_dev, int64_t packed_bytes, const bd_image_desc* descs_host, int N, int Hp,
@@ -117,5 +170,22 @@ extern "C" int bd_resize_pad_normalize(const uint8_t* packed_dev, int64_t packed
                            (bf16_raw*)x_halo + (long long)g0 * Hb * Wb * 4);
         BD_CHECK_LAUNCH("bd_resize_pad_normalize");
     }
+    return BD_OK;
+}
+
+extern "C" int bd_resize_bilinear_normalize(const float* in, int N, int H, int W, int dst_h, int dst_w, int Hp, int Wp, const float* mean3,
+                                            const float* std3, void* x_halo, bd_stream_t stream) {
+    BD_REQUIRE(in && mean3 && std3 && x_halo, "resize_bilinear_normalize: null pointer");
+    BD_REQUIRE((uintptr_t)in % 4 == 0 && (uintptr_t)x_halo % 8 == 0, "resize_bilinear_normalize: in must be 4-byte and x_halo 8-byte aligned");
+    BD_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && dst_h > 0 && dst_w > 0, "resize_bilinear_normalize: N=%d, %d x %d -> %d x %d", N, H, W,
+               dst_h, dst_w);
+    BD_REQUIRE(Hp > 0 && Wp > 0 && Hp % 32 == 0 && Wp % 32 == 0 && Hp + 2 * HALO_Y <= 65535,
+               "resize_bilinear_normalize: padded size %d x %d must be positive multiples of 32 (at most 65504 rows)", Hp, Wp);
+    BD_REQUIRE(dst_h <= Hp && dst_w <= Wp, "resize_bilinear_normalize: resized %d x %d exceeds the padded %d x %d", dst_h, dst_w, Hp, Wp);
+    const int Hb = Hp + 2 * HALO_Y, Wb = Wp + 2 * HALO_X;
+    hipLaunchKernelGGL(resize_bilinear_normalize_kernel, dim3(cdiv(Wb, 256), Hb, N), dim3(256), 0, (hipStream_t)stream, in, H, W, dst_h, dst_w,
+                       Hp, Wp, (double)H / (double)dst_h, (double)W / (double)dst_w, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2],
+                       (bf16_raw*)x_halo);
+    BD_CHECK_LAUNCH("bd_resize_bilinear_normalize");
     return BD_OK;
 }

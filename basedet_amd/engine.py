@@ -6,7 +6,7 @@ import time
 
 from . import comm as _comm
 from .layers.ema import ModelEMA, calculate_momentum
-from .solver import WarmupMultiStepLR, clip_grad
+from .solver import SyncSizeHook, WarmupMultiStepLR, YoloxLR, clip_grad
 from .utils.registry import registers
 
 
@@ -30,7 +30,14 @@ class DetTrainer:
         s = cfg.SOLVER
         max_iter = int(s.NUM_IMAGE_PER_EPOCH / _comm.world_size() / cfg.MODEL.BATCHSIZE)          # trainer.py:45-48
         self.progress = Progress(s.MAX_EPOCH, max_iter)
-        self.lr_scheduler = WarmupMultiStepLR(solver.optimizer, cfg, _comm.world_size())
+        # HOOKS.BUILDER_NAME = "YOLOXHookList" (engine/build.py:45-69): YOLOX's schedule and its multi-scale size hook
+        self.yolox_hooks = cfg.get("HOOKS", {}).get("BUILDER_NAME") == "YOLOXHookList"
+        if self.yolox_hooks:
+            self.lr_scheduler = YoloxLR(solver.optimizer, cfg, _comm.world_size())
+            self.size_hook = SyncSizeHook.build(cfg, model, seed=cfg.get("GLOBAL", {}).get("SEED", 0) or 0)
+        else:
+            self.lr_scheduler = WarmupMultiStepLR(solver.optimizer, cfg, _comm.world_size())
+            self.size_hook = None
         t = cfg.get("TRAINER", {})
         if t.get("AMP", {}).get("ENABLE", False):                              # trainer.py:52-54
             assert self.solver.grad_scaler is not None, "enable AMP but grad_scaler is None"
@@ -73,7 +80,12 @@ class DetTrainer:
         p = self.progress
         for p.epoch in range(1, p.max_epoch + 1):
             for p.iter in range(1, p.max_iter + 1):
-                self.lr_scheduler.step(p.global_iter)                          # LRSchedulerHook.before_iter
+                if self.yolox_hooks:                                           # YoloxLRSchedulerHook / SyncSizeHook.before_iter
+                    self.lr_scheduler.step(p.epoch, p.iter)
+                    if self.size_hook is not None:
+                        self.size_hook.before_iter(p.epoch, p.iter, p.max_iter)
+                else:
+                    self.lr_scheduler.step(p.global_iter)                      # LRSchedulerHook.before_iter
                 self.train_one_iter()
                 done += 1
                 if log and _comm.rank() == 0 and (done % self.log_interval == 0 or done == max_iters):

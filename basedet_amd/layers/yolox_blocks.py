@@ -141,6 +141,20 @@ class _Module:
         for _, c in self._leaves():
             c.repack()
 
+    def arena_shapes(self):
+        """name -> shape of the fp32 masters in the kernels' layouts: "<leaf>.weight", OHWI (Focus's with its 16 input channels)."""
+        return {f"{n}.weight": c.arena_shapes()["weight"] for n, c in self._leaves()}
+
+    def adopt(self, w, g, norms):
+        """Live on the caller's storage (a model's parameter arena): w / g = {"<leaf>.weight": fp32 view} of arena_shapes(), norms =
+        {"<leaf>.norm": the model's norm record}.  See ConvBNSiLU.adopt."""
+        for n, c in self._leaves():
+            c.adopt({"weight": w[n + ".weight"]}, {"weight": g[n + ".weight"]}, norms[n + ".norm"])
+
+    def refresh_eval(self):
+        for _, c in self._leaves():
+            c.refresh_eval()
+
     def train(self, mode=True):
         self.training = bool(mode)
         for _, c in self._leaves():

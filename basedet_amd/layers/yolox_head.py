@@ -4,8 +4,8 @@ operator every YOLOX convolution ends in, and the decoupled head that writes the
 Calling convention of layers/center_head.py: `layer(x)` takes and returns NCHW fp32 DEVICE tensors (a host tensor raises BasedetHipError:
 no CPU fallback); `forward_pm` / `backward_pm` on pixel-major bf16; `params()` (fp32 device masters by name, views an optimizer may update
 in place) / `repack()` / `grads()` (copies); strict `state_dict()` / `load_state_dict()` under the reference's names; `train()` /
-`eval()`.  The masters are kept in the kernels' layouts and loaded in place: one path, so an `adopt()` onto a model arena (the detector's,
-not built) will be a move as it is for center_head.py's layers.  The norm is layers/batch_norm.py BatchNormAct("silu").
+`eval()`.  The masters are kept in the kernels' layouts and loaded in place: one path, so `adopt()` onto a model arena (models/yolox.py
+YOLOX) is a move as it is for center_head.py's layers.  The norm is layers/batch_norm.py BatchNormAct("silu").
 
 ConvBNSiLU = bd_conv2d_fwd (no bias, no epilogue) -> bd_bn_stats_fwd -> bd_bn_silu_fwd; backward = bd_bn_silu_bwd_reduce ->
 bd_bn_silu_bwd_apply -> bd_conv2d_wgrad + bd_conv2d_dgrad.  The SiLU gate is recomputed from the pre-norm tensor inside the norm's two
@@ -111,6 +111,21 @@ class ConvBNSiLU:
 
     def refresh_eval(self):
         self.norm.refresh_eval()
+
+    def arena_shapes(self):
+        """name -> shape of the fp32 master in the kernels' layout (OHWI).  The norm's vectors are not listed: adopt() takes a norm record."""
+        return {"weight": tuple(self._w.shape)}
+
+    def adopt(self, w, g, norm_state):
+        """Live on the caller's storage (a model's parameter arena): w / g = {"weight": fp32 view of arena_shapes()}, norm_state the
+        model's norm record (BatchNormAct.adopt).  The current values move in; the same path on other storage (center_head.py adopt)."""
+        shape = tuple(self._w.shape)
+        if tuple(w["weight"].shape) != shape or tuple(g["weight"].shape) != shape:
+            raise ValueError(f"adopt: 'weight' needs fp32 views of shape {shape}")
+        w["weight"].copy_(self._w)
+        self._w, self._gw = w["weight"], g["weight"]
+        self.norm.adopt(norm_state)
+        self.repack()
 
     def state_dict(self):
         return {"weight": self._w.permute(0, 3, 1, 2).contiguous().cpu(), **self.norm.state("norm.")}
@@ -225,6 +240,19 @@ class _PredConv:
     def repack(self):
         ops.weight_pack(self.w, None, self.wf, self.wd, self.ld, 1, self.cin)
 
+    def arena_shapes(self):
+        return {"weight": tuple(self.w.shape), "bias": tuple(self.b.shape)}
+
+    def adopt(self, w, g):
+        """Live on the caller's storage: w / g = {"weight", "bias"} fp32 views of the padded masters (ConvBNSiLU.adopt)."""
+        for k, shape in self.arena_shapes().items():
+            if tuple(w[k].shape) != shape or tuple(g[k].shape) != shape:
+                raise ValueError(f"adopt: {k!r} needs fp32 views of shape {shape}")
+        w["weight"].copy_(self.w)
+        w["bias"].copy_(self.b)
+        self.w, self.b, self.gw, self.gb = w["weight"], w["bias"], g["weight"], g["bias"]
+        self.repack()
+
     def desc(self, N, H, W, off, P):
         return ops.conv_desc(ops.single(N, H, W), ops.Geom(N, [H], [W], [off], P), self.cin, self.ld, 1, 1, 1, 0)
 
@@ -232,7 +260,7 @@ class _PredConv:
         ops.conv2d_fwd(d, x, self.wf, self.b, out)
 
     def backward(self, d, x, g, accumulate):
-        if self.gw is None or not accumulate:
+        if self.gw is None:          # (allocated once, like ConvBNSiLU's: a backward without `accumulate` overwrites every element)
             accumulate = False
             self.gw, self.gb = torch.empty_like(self.w), torch.empty_like(self.b)
         ops.conv2d_wgrad_bias(d, x, g, self.gw, self.gb, workspace(ops.conv2d_wgrad_bias_workspace_bytes(d), self.device), accumulate=accumulate)
@@ -338,6 +366,30 @@ class YOLOXHead:
             b.repack()
         for c in self.cls_preds + self.regobj_preds:
             c.repack()
+
+    def _preds(self):
+        """[(prefix, _PredConv)]: per level the padded class predictor and the fused reg + obj predictor."""
+        L = range(len(self.in_channels))
+        return [(f"cls_preds.{l}", self.cls_preds[l]) for l in L] + [(f"regobj_preds.{l}", self.regobj_preds[l]) for l in L]
+
+    def arena_shapes(self):
+        """name -> shape of the fp32 masters in the kernels' layouts: every block's OHWI weight, then the predictors' padded weights and
+        biases (cls_preds.l: round_up(K, 8) rows; regobj_preds.l: reg 0-3, obj 4, 5-7 zero).  The norms' vectors are not listed."""
+        out = {f"{n}.weight": b.arena_shapes()["weight"] for n, b in self._blocks()}
+        out.update({f"{n}.{k}": v for n, p in self._preds() for k, v in p.arena_shapes().items()})
+        return out
+
+    def adopt(self, w, g, norms):
+        """Live on the caller's storage (a model's parameter arena): w / g = {name: fp32 view} of arena_shapes(), norms =
+        {"<block>.norm": the model's norm record}.  See ConvBNSiLU.adopt."""
+        for n, b in self._blocks():
+            b.adopt({"weight": w[n + ".weight"]}, {"weight": g[n + ".weight"]}, norms[n + ".norm"])
+        for n, p in self._preds():
+            p.adopt({k: w[f"{n}.{k}"] for k in ("weight", "bias")}, {k: g[f"{n}.{k}"] for k in ("weight", "bias")})
+
+    def refresh_eval(self):
+        for _, b in self._blocks():
+            b.refresh_eval()
 
     def train(self, mode=True):
         self.training = bool(mode)

@@ -5,4 +5,4 @@ from .faster_rcnn import FasterRCNN  # noqa: F401
 from . import centernet  # noqa: F401
 from .centernet import CenterNet, CenterNetDecoder, CenterNetGT  # noqa: F401
 from . import yolox  # noqa: F401
-from .yolox import yolox_assignments, yolox_inference, yolox_losses  # noqa: F401
+from .yolox import YOLOX, yolox_assignments, yolox_inference, yolox_losses  # noqa: F401

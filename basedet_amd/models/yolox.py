@@ -3,8 +3,9 @@ the SimOTA assignment (`yolox_assignments`), the four losses with gradients back
 chain (`yolox_inference`: bd_det_select -> bd_yolox_candidates -> bd_nms_batched -> bd_det_finalize).  The decoupled head is
 layers.YOLOXHead, and `yolox_head_step` runs it against the kernels here with no repack; the feature extractor is layers.YOLOPAFPN on
 layers.CSPDarknet, and `yolox_network_step` is one training step of the whole network from the normalised image down to the stem's
-parameter gradients.  The model class (arena, adopt(), inference from an image), the solver and the mosaic / mixup input are not built
-yet; what is here is what they will call.
+parameter gradients.  `YOLOX` is the detector: those layers adopt()ed onto one parameter arena and one LiveNorms,
+pre_process with the multi-scale resize (bd_resize_bilinear_normalize), get_losses / backward for Solver.minimize, and inference from an
+image batch; solver.YOLOXSolver trains it.  The mosaic / mixup input is not built yet.
 
 The kernels read the layout a fused head will write -- cls bf16 (N*P, round_up(K, 8)) and box_obj bf16 (N*P, 8): raw reg 0-3, obj logit
 4 -- with the P points of an image level after level, row-major inside a level.  `yolox_losses` and `yolox_inference` take the
@@ -18,7 +19,7 @@ from basedet_amd import ops
 from basedet_amd.layers._pm import need_device_all, round_up8
 from basedet_amd.layers.box_ops import FastPointGenerator
 
-__all__ = ["yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs", "yolox_head_step", "yolox_network_step"]
+__all__ = ["YOLOX", "yolox_assignments", "yolox_losses", "yolox_inference", "pack_head_outputs", "yolox_head_step", "yolox_network_step"]
 
 _MODULE = "basedet_amd.models.yolox"          # (named in the refusal of a host tensor)
 
@@ -122,19 +123,26 @@ def yolox_losses(logits, offsets, objs, gt_boxes, num_gt, strides, use_l1=False)
     return {"total_loss": total, "iou_loss": parts[0], "l1_loss": parts[3], "obj_loss": parts[1], "cls_loss": parts[2]}
 
 
-def yolox_head_step(head, feats, N, sizes, gt_boxes, num_gt, strides, use_l1=False):
-    """One training step of a layers.YOLOXHead on its own layout, no repack: forward_pm -> ops.yolox_assign -> ops.yolox_loss_fwd_bwd ->
-    backward_pm.  feats: per level bf16 (N H_l W_l, C_l); sizes [(H_l, W_l)].  Returns (parts fp32 (4,) = 5 * iou, obj, cls, l1;
-    d_feats per level; (matched, iou_t, stats))."""
-    need_device_all((*feats, gt_boxes, num_gt), _MODULE)
+def _head_losses(head, feats, N, sizes, gt_boxes, num_gt, strides, use_l1=False, points=None):
+    """The forward half of a head step: forward_pm -> ops.yolox_assign -> ops.yolox_loss_fwd_bwd.  Returns (parts, d_cls, d_box_obj,
+    (matched, iou_t, stats)); points = a cached (points, lvl_start) of these sizes."""
     cls, box_obj = head.forward_pm(feats, N, sizes)
-    points, lvl_start = _points(sizes, strides, cls.device)
+    points, lvl_start = points if points is not None else _points(sizes, strides, cls.device)
     gt = gt_boxes.float().contiguous()
     K = head.num_classes
     matched, iou_t, stats = ops.yolox_assign(cls, K, box_obj, points, lvl_start, list(strides), gt, num_gt.to(torch.int32).contiguous())
     parts, d_cls, d_box_obj = ops.yolox_loss_fwd_bwd(cls, K, box_obj, points, lvl_start, list(strides), gt, matched, iou_t, stats,
                                                     use_l1=use_l1, grad_scale=1.0)
-    return parts, head.backward_pm(d_cls, d_box_obj), (matched, iou_t, stats)
+    return parts, d_cls, d_box_obj, (matched, iou_t, stats)
+
+
+def yolox_head_step(head, feats, N, sizes, gt_boxes, num_gt, strides, use_l1=False):
+    """One training step of a layers.YOLOXHead on its own layout, no repack: forward_pm -> ops.yolox_assign -> ops.yolox_loss_fwd_bwd ->
+    backward_pm.  feats: per level bf16 (N H_l W_l, C_l); sizes [(H_l, W_l)].  Returns (parts fp32 (4,) = 5 * iou, obj, cls, l1;
+    d_feats per level; (matched, iou_t, stats))."""
+    need_device_all((*feats, gt_boxes, num_gt), _MODULE)
+    parts, d_cls, d_box_obj, assigned = _head_losses(head, feats, N, sizes, gt_boxes, num_gt, strides, use_l1)
+    return parts, head.backward_pm(d_cls, d_box_obj), assigned
 
 
 def yolox_network_step(fpn, head, x_halo, N, H, W, gt_boxes, num_gt, strides=(8, 16, 32), use_l1=False):
@@ -149,38 +157,59 @@ def yolox_network_step(fpn, head, x_halo, N, H, W, gt_boxes, num_gt, strides=(8,
     return parts, assigned
 
 
-def yolox_inference(logits, offsets, objs, img_info, cfg, strides=(8, 16, 32), k=1000):
-    """YOLOX.inference behind network_forward (yolox.py:112-148) for a batch: per image and level score = sqrt(sigmoid(cls) sigmoid(obj))
-    > TEST.CLS_THRESHOLD -> top-k -> decode -> batched NMS by label (TEST.IOU_THRESHOLD) -> the first TEST.MAX_BOXES_PER_IMAGE, scaled
-    and clipped by the image's img_info row (h, w, original h, original w).  Returns the list of per-image Containers (boxes,
-    box_scores, box_labels)."""
-    from ..structures import Boxes, Container
-    _check_levels(logits, offsets, objs, strides)
-    need_device_all((*logits, *offsets, *objs, img_info), _MODULE)
+def _detect_packed(cls, box_obj, K, sizes, img_info, cfg, strides, k, cache=None):
+    """The inference chain behind the pack, for B images: cls bf16 (B*P, round_up(K, 8)) and box_obj bf16 (B*P, 8) as the head writes
+    them -> bd_det_select -> bd_yolox_candidates -> bd_nms_batched -> bd_det_finalize.  cache: a dict that keeps the scratch of a
+    (B, sizes, k) between calls (the model's); the results are new tensors, the caller's, either way."""
+    from basedet_amd.structures import Boxes, Container
     t = cfg.TEST
-    B, K = int(logits[0].shape[0]), int(logits[0].shape[1])
-    cls, box_obj, sizes = pack_head_outputs(logits, offsets, objs)
     dev = cls.device
-    points, lvl_start = _points(sizes, strides, dev)
-    Ln, P = len(sizes), lvl_start[-1]
-    lvl_rows = [h * w for h, w in sizes]
+    Ln, max_out = len(sizes), int(t.MAX_BOXES_PER_IMAGE)
+    P = sum(h * w for h, w in sizes)
+    B = int(cls.shape[0]) // P
     i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
-    tk_idx, tk_sc, tk_cnt = torch.empty((B, Ln, k), **i32), torch.empty((B, Ln, k), **f32), torch.empty((B, Ln), **i32)
-    ws = torch.empty((ops.det_select_workspace_bytes(B, Ln, P, K, k),), dtype=torch.uint8, device=dev)
-    ops.det_select(cls, B, P, K, lvl_start[:-1], lvl_rows, k, t.CLS_THRESHOLD, tk_idx, tk_sc, tk_cnt, ws, ctr=box_obj, ctr_ld=8, ctr_off=4,
-                   ld=round_up8(K))
-    boxes, scores, labels = ops.yolox_candidates(tk_idx, tk_sc, tk_cnt, K, points, lvl_start, list(strides), box_obj)
-    max_out = int(t.MAX_BOXES_PER_IMAGE)
-    keep, num = torch.empty((B, max_out), **i32), torch.zeros((B,), **i32)
-    nms_ws = torch.empty((ops.nms_batched_workspace_bytes(B, Ln * k),), dtype=torch.uint8, device=dev)
-    ops.nms_batched(boxes, scores, labels, t.IOU_THRESHOLD, max_out, keep, num, nms_ws)
+    key = (B, tuple(sizes), k, K)
+    sc = cache.get(key) if cache is not None else None
+    if sc is None:
+        points, lvl_start = _points(sizes, strides, dev)
+        sc = dict(points=points, lvl_start=lvl_start, tk_idx=torch.empty((B, Ln, k), **i32), tk_sc=torch.empty((B, Ln, k), **f32),
+                  tk_cnt=torch.empty((B, Ln), **i32),
+                  ws=torch.empty((ops.det_select_workspace_bytes(B, Ln, P, K, k),), dtype=torch.uint8, device=dev),
+                  boxes=torch.empty((B, Ln * k, 4), **f32), scores=torch.empty((B, Ln * k), **f32), labels=torch.empty((B, Ln * k), **i32),
+                  keep=torch.empty((B, max_out), **i32), num=torch.zeros((B,), **i32),
+                  nms_ws=torch.empty((ops.nms_batched_workspace_bytes(B, Ln * k),), dtype=torch.uint8, device=dev))
+        if cache is not None:
+            cache[key] = sc
+    lvl_start = sc["lvl_start"]
+    ops.det_select(cls, B, P, K, lvl_start[:-1], [h * w for h, w in sizes], k, t.CLS_THRESHOLD, sc["tk_idx"], sc["tk_sc"], sc["tk_cnt"],
+                   sc["ws"], ctr=box_obj, ctr_ld=8, ctr_off=4, ld=round_up8(K))
+    ops.yolox_candidates_into(sc["tk_idx"], sc["tk_sc"], sc["tk_cnt"], K, sc["points"], lvl_start, list(strides), box_obj, sc["boxes"],
+                              sc["scores"], sc["labels"])
+    sc["num"].zero_()
+    ops.nms_batched(sc["boxes"], sc["scores"], sc["labels"], t.IOU_THRESHOLD, max_out, sc["keep"], sc["num"], sc["nms_ws"])
     ob, osc, ol = torch.empty((B, max_out, 4), **f32), torch.empty((B, max_out), **f32), torch.empty((B, max_out), **i32)
-    ops.det_finalize(boxes, scores, labels, keep, num, max_out, img_info.float().contiguous(), ob, osc, ol)
+    ops.det_finalize(sc["boxes"], sc["scores"], sc["labels"], sc["keep"], sc["num"], max_out, img_info.float().contiguous(), ob, osc, ol)
     outs = []
-    for i, n in enumerate(num.tolist()):
+    for i, n in enumerate(sc["num"].tolist()):
         if n == 0:
             e = torch.zeros((0,))
             outs.append(Container(boxes=e, box_scores=e, box_labels=e))
         else:
             outs.append(Container(boxes=Boxes(ob[i, :n]), box_scores=osc[i, :n], box_labels=ol[i, :n]))
     return outs
+
+
+def yolox_inference(logits, offsets, objs, img_info, cfg, strides=(8, 16, 32), k=1000):
+    """YOLOX.inference behind network_forward (yolox.py:112-148) for a batch: per image and level score = sqrt(sigmoid(cls) sigmoid(obj))
+    > TEST.CLS_THRESHOLD -> top-k -> decode -> batched NMS by label (TEST.IOU_THRESHOLD) -> the first TEST.MAX_BOXES_PER_IMAGE, scaled
+    and clipped by the image's img_info row (h, w, original h, original w).  Returns the list of per-image Containers (boxes,
+    box_scores, box_labels).  The body behind the pack is the one YOLOX.inference_batch runs on the head's own outputs."""
+    _check_levels(logits, offsets, objs, strides)
+    need_device_all((*logits, *offsets, *objs, img_info), _MODULE)
+    cls, box_obj, sizes = pack_head_outputs(logits, offsets, objs)
+    return _detect_packed(cls, box_obj, int(logits[0].shape[1]), sizes, img_info, cfg, strides, k)
+
+
+# the detector lives in a module of its own, imported by its absolute name: `basedet.models.yolox` (the alias package) and this module
+# then hold ONE class, the one registers.models has
+from basedet_amd.models.yolox_detector import YOLOX  # noqa: E402, F401

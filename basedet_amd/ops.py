@@ -460,6 +460,15 @@ def resize_pad_normalize(packed, descs, Hp, Wp, mean, std, out):
     return out
 
 
+def resize_bilinear_normalize(x, dst_h, dst_w, Hp, Wp, mean, std, out):
+    """bd_resize_bilinear_normalize: x fp32 (N, 3, H, W) on the device -> out bf16 (N, Hp + 6, Wp + 8, 4), written whole: the batch resized
+    to (dst_h, dst_w) by torch.nn.functional.interpolate's bilinear rule (align_corners=False), padded and normalised."""
+    N, _, H, W = x.shape
+    check(L().bd_resize_bilinear_normalize(ptr(x), N, H, W, int(dst_h), int(dst_w), int(Hp), int(Wp), f32arr(mean), f32arr(std), ptr(out),
+                                           stream_ptr()), "bd_resize_bilinear_normalize")
+    return out
+
+
 def affine_jitter_workspace_bytes(N, out_h, out_w):
     return int(L().bd_affine_jitter_workspace_bytes(int(N), int(out_h), int(out_w)))
 

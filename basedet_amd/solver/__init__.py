@@ -5,6 +5,9 @@ trainable parameter arena in ONE fused launch; gradients are all-reduced (mean) 
 follow the backward order (head -> FPN -> layer4 -> ... -> layer2) on the communicator's stream, overlapped with backward.
 The collectives are the bd_comm_* entry points of the C ABI (basedet_amd/comm.py); no c10d process group is involved.
 """
+import math
+
+import numpy as np
 import torch
 
 from .. import comm as _comm
@@ -187,7 +190,10 @@ class GradBuckets:
         self.ranges = self._ranges()
 
     def _ranges(self):
-        """name of the backward phase -> (start, end) element range of the arena."""
+        """name of the backward phase -> (start, end) element range of the arena.  A model that defines grad_buckets() (YOLOX: one
+        bucket) supplies its own."""
+        if hasattr(self.model, "grad_buckets"):
+            return dict(self.model.grad_buckets())
         ent = self.model.arena.entries
         groups = {}
         for name, _, off, n in ent:
@@ -390,6 +396,113 @@ class DetSolver:
             dyn = bool(amp.get("DYNAMIC_SCALE", False))
             scaler = GradScaler(65536.0 if dyn else 128.0, 2000 if dyn else 0)
         return Solver(opt, GradBuckets(model, mode, wire_dtype=str(solver_cfg.get("ALLREDUCE_DTYPE", "fp32"))), grad_scaler=scaler)
+
+
+class YOLOXSGD(SGD):
+    """The optimizer of solver/yolox_solver.py: Nesterov SGD whose weight decay reaches the convolution weights only.  The model's arena
+    holds them in front -- elements [0, model.decay_end) -- and every 1-D parameter (BN gamma / beta, the predictor biases) behind, so
+    the step is the existing launch run on the two slices, with the moment and EMA buffers sliced likewise: no new kernel.  Two
+    param_groups in arena order ("range": their element range); a scheduler sets `lr` on both."""
+
+    def __init__(self, model, lr, weight_decay, momentum=0.9):
+        super().__init__(model, lr, weight_decay, momentum=momentum, nesterov=True)
+        cut, total = int(model.decay_end), int(model.arena.total)
+        assert 0 <= cut <= total and cut % 64 == 0, (cut, total)
+        self.param_groups = [_ParamGroupView(lr=lr, weight_decay=weight_decay, momentum=momentum, range=(0, cut)),
+                             _ParamGroupView(lr=lr, weight_decay=0.0, momentum=momentum, range=(cut, total))]
+
+    def step(self, grad_scale=1.0, ema=None):
+        a = self.model.arena
+        m = ema.fused_momentum() if ema is not None else None
+        for g in self.param_groups:
+            lo, hi = g["range"]
+            if hi == lo:
+                continue
+            if m is None:
+                ops.sgd_nesterov_step(a.w[lo:hi], a.v[lo:hi], a.g[lo:hi], g["lr"], g["momentum"], g["weight_decay"], grad_scale)
+            else:
+                ops.sgd_nesterov_ema_step(a.w[lo:hi], a.v[lo:hi], a.g[lo:hi], ema.e[lo:hi], g["lr"], g["momentum"], g["weight_decay"],
+                                          grad_scale, m)
+        self.step_count += 1
+        self.model.repack_trainable()
+        return self
+
+
+class YoloxLR:
+    """YoloxLRSchedulerHook (engine/yolo_hooks.py:15-59): quadratic warm-up over SOLVER.WARM_EPOCH epochs from lr * MIN_LR_RATIO, a
+    cosine down to lr * MIN_LR_RATIO, and that rate held for the last AUG.TRAIN_SETTING.NO_AUG_EPOCH epochs.  `epoch` and `it` count from
+    1, as basecore's Progress does; every param_group follows the one rate."""
+
+    def __init__(self, optimizer, cfg, world_size=1):
+        s = cfg.SOLVER
+        self.optimizer = optimizer
+        self.lr = optimizer.param_groups[0]["lr"]
+        self.min_lr = self.lr * s.MIN_LR_RATIO
+        self.warm_epoch, self.no_aug_epoch = int(s.WARM_EPOCH), int(cfg.AUG.TRAIN_SETTING.NO_AUG_EPOCH)
+        self.max_epoch = int(s.MAX_EPOCH)
+        self.max_iter = int(s.NUM_IMAGE_PER_EPOCH / world_size / cfg.MODEL.BATCHSIZE)          # engine/trainer.py:48
+
+    def lr_at(self, epoch, it):
+        if epoch <= self.warm_epoch:
+            cur = (epoch - 1) * self.max_iter + it
+            return (self.lr - self.min_lr) * pow(cur / float(self.warm_epoch * self.max_iter), 2) + self.min_lr
+        if epoch > self.max_epoch - self.no_aug_epoch:
+            return self.min_lr
+        cur = (epoch - self.warm_epoch) * self.max_iter + it
+        span = (self.max_epoch - self.warm_epoch - self.no_aug_epoch) * self.max_iter
+        return self.min_lr + 0.5 * (self.lr - self.min_lr) * (1.0 + math.cos(math.pi * (cur - self.warm_epoch * self.max_iter) / span))
+
+    def step(self, epoch, it):
+        lr = self.lr_at(epoch, it)
+        for g in self.optimizer.param_groups:
+            g["lr"] = lr
+
+
+class SyncSizeHook:
+    """engine/yolo_hooks.py:62-89: every `change_iter` iterations rank 0 draws the training size from `sizes`, the draw is broadcast,
+    and the model's target_size is set; the model's pre_process resizes the next batches to it.  The draw comes from a generator seeded
+    here (the reference uses numpy's global one), so a run can be repeated."""
+
+    def __init__(self, model, sizes, change_iter=10, seed=0):
+        self.model, self.sizes, self.change_iter = model, [int(v) for v in sizes], int(change_iter)
+        self.rng = np.random.default_rng(seed)
+
+    @classmethod
+    def build(cls, cfg, model, seed=0):
+        """engine/build.py:63-69; None when AUG.TRAIN_SETTING.MULTISCALE_RANGE is empty."""
+        t = cfg.AUG.TRAIN_SETTING
+        rng = tuple(t.get("MULTISCALE_RANGE", ()) or ())
+        if not rng:
+            return None
+        lo, hi = rng
+        return cls(model, [32 * x for x in range(lo, hi + 1)], t.SYNC_ITER, seed)
+
+    def before_iter(self, epoch, it, max_iter):
+        cur = (epoch - 1) * max_iter + it
+        if not self.model.training or cur % self.change_iter:
+            return
+        size = int(self.rng.choice(self.sizes)) if _comm.rank() == 0 else 0
+        c = _comm.get_comm()
+        if c is not None and c.world > 1:
+            t = torch.tensor([size], dtype=torch.int32, device=self.model.device)
+            c.bcast(t, root=0)
+            size = int(t.item())
+        self.model.target_size = (size, size)
+
+
+@registers.solvers.register()
+class YOLOXSolver:
+    """solver/yolox_solver.py: lr = BASIC_LR * BATCHSIZE * world, Nesterov SGD with SOLVER.MOMENTUM, WEIGHT_DECAY on the convolution
+    weights only (YOLOXSGD)."""
+
+    @classmethod
+    def build(cls, cfg, model):
+        s = cfg.SOLVER
+        if not hasattr(model, "decay_end"):
+            raise ValueError("YOLOXSolver needs a model whose arena separates the decayed weights (decay_end): YOLOX")
+        lr = s.BASIC_LR * cfg.MODEL.BATCHSIZE * _comm.world_size()
+        opt = YOLOXSGD(model, lr=float(lr), weight_decay=s.WEIGHT_DECAY, momentum=s.MOMENTUM)
+        return Solver(opt, GradBuckets(model, s.get("REDUCE_MODE", "MEAN"), wire_dtype=str(s.get("ALLREDUCE_DTYPE", "fp32"))))
 
 
 def broadcast_parameters(model, src=0):

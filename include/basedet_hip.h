@@ -366,6 +366,19 @@ typedef struct bd_image_desc {
 int bd_resize_pad_normalize(const uint8_t* packed_dev, int64_t packed_bytes, const bd_image_desc* descs_host, int N, int Hp, int Wp,
                             const float* mean3, const float* std3, void* x_halo, bd_stream_t stream);
 
+/* YOLOX's multi-scale pre_process (models/det/yolox.py:71-98; library addition, bd_version() stays 118): a dense fp32 NCHW batch
+ * [N][3][H][W] resized bilinearly to (dst_h, dst_w) and written straight into the layout bd_pad_normalize writes (bf16
+ * [N][Hp+6][Wp+8][4], zero halo, channel 3 = 0, every element written; beyond (dst_h, dst_w) the zero pad normalised, (0 - mean) / std,
+ * which is zero under the mean 0 YOLOX passes) -- no fp32 intermediate image.  The sampling rule is
+ * F.vision.interpolate(mode="bilinear", align_corners=False) = torch.nn.functional.interpolate's: src = max(0, (dst + 0.5) in / out - 0.5)
+ * in float64, neighbours floor(src) and min(floor(src) + 1, in - 1), fp32 blends (two FMAs each), no antialiasing; then (x - mean) / std.
+ * Against the float64 rule a blended value in [0, 255] errs by at most 6 * 2^-17 < 4 * 2^-24 * 255 (image_resize.hip).
+ * dst == (H, W) gives the bits of bd_pad_normalize.  No atomics, no workspace; bitwise reproducible.
+ * BD_EINVAL, with nothing launched: a null pointer, `in` not 4-byte or x_halo not 8-byte aligned, a size <= 0, N > 65535,
+ * dst_h > Hp or dst_w > Wp, Hp or Wp not a multiple of 32 (or Hp > 65504). */
+int bd_resize_bilinear_normalize(const float* in, int N, int H, int W, int dst_h, int dst_w, int Hp, int Wp, const float* mean3,
+                                 const float* std3, void* x_halo, bd_stream_t stream);
+
 /* CenterNet's training input (bd_version() >= 118; image_affine.hip; CenterNetConfig.AUG.TRAIN_VALUE: CenterAffine, horizontal flip,
  * brightness, contrast, saturation, lighting): N raw uint8 images packed as above -> the same layout (bf16 [N][out_h+6][out_w+8][4],
  * zero halo, channel 3 = 0, every element written), bit for bit what tests/center_affine_oracle.py computes:
