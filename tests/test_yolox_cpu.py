@@ -228,3 +228,102 @@ def test_python_surface_refusals():
         Y.yolox_losses(lg, of, [torch.zeros(1, 2, 4, 4), torch.zeros(1, 1, 2, 2)], gt, num, (8, 16))
     with pytest.raises(ValueError):
         Y.yolox_assignments(torch.zeros(20, 8), torch.zeros(20, 8), torch.zeros(20, 2), (8, 16), gt, num)      # one tensor, no lvl_start
+
+
+# ---- the problems of tests/test_yolox_edges_gpu.py ----------------------------------------------------------------------------------------
+def test_big_loss_problem_passes_the_grid_cap():
+    """More 8-slot vectors than one trip of the capped loss launch takes; about 2 % foreground, every matched entry a valid gt of its
+    image, every iou_t a float32 in (0, 1)."""
+    prob, m, u = O.big_loss_problem()
+    N, P, ld = prob["cls"].shape
+    assert (N, prob["H"], prob["W"], prob["K"], prob["gt"].shape[1]) == O.BIG_SHAPE and P == 8400 and ld == 368
+    assert N * P * ld // 8 == 1159200 > 4096 * 256                       # YX_GRID_CAP workgroups of 256 threads
+    fg = m >= 0
+    assert 0.015 < fg.mean() < 0.025 and fg.any(1).all()
+    assert (m < prob["num"][:, None]).all() and np.isfinite(prob["gt"][0, :int(prob["num"][0])]).all()
+    assert ((u[fg] > 0) & (u[fg] < 1)).all() and (u[~fg] == 0).all() and np.array_equal(u, u.astype(np.float32).astype(np.float64))
+    assert np.array_equal(prob["cls"], O.bf16(prob["cls"])) and np.array_equal(prob["box_obj"], O.bf16(prob["box_obj"]))
+
+
+def test_kink_problem_holds_its_cases():
+    """Each named point is what its name says, exactly, in float32 and float64 and in both frames; the oracle takes matched = Gmax as
+    background and gives the half weights at the ties."""
+    prob = O.kink_problem()
+    m, u, cases = prob["matched"], prob["iou_t"], prob["cases"]
+    K, G = prob["K"], prob["gt"].shape[1]
+    assert set(cases) == set(O.KINK_CASES) and len(set(cases.values())) == G and m[0, prob["bg_gmax"]] == G
+    assert ((m >= 0) & (m < G)).sum() == G and (m == -1).sum() == m.size - G - 1
+    pred = O.boxes_xyxy(prob)[0]
+    ties = {}
+    for name, p in cases.items():
+        g = prob["gt"][0, m[0, p]].astype(np.float64)
+        b = pred[p]
+        raw = prob["box_obj"][0, p]
+        assert raw[2] == 0 and raw[3] == 0 and (raw[:2] * 8 == np.round(raw[:2] * 8)).all() and (g[:4] * 4 == np.round(g[:4] * 4)).all()
+        rel32 = (prob["gt"][0, m[0, p], :4] - np.tile(prob["pts"][p], 2)).astype(np.float32)           # the kernel's frame, in float32
+        assert np.array_equal(rel32.astype(np.float64), g[:4] - np.tile(prob["pts"][p].astype(np.float64), 2))
+        assert np.array_equal(b, b.astype(np.float32).astype(np.float64)) and (b[2:] - b[:2] == 8).all()
+        ties[name] = [bool(b[j] == g[j]) for j in range(4)]
+        iw, ih = min(b[2], g[2]) - max(b[0], g[0]), min(b[3], g[3]) - max(b[1], g[1])
+        if name == "disjoint":
+            assert iw < 0 and ih < 0
+        elif name == "zero_area":
+            assert g[0] == g[2] and g[1] == g[3] and b[0] < g[0] < b[2] and b[1] < g[1] < b[3] and iw == 0 and ih == 0
+        else:
+            assert iw > 0 and ih > 0
+        assert int(g[4]) == {"label_0": 0, "label_K+1": K + 1}.get(name, int(g[4])) and (1 <= g[4] <= K) == (not name.startswith("label_"))
+    assert ties["equal"] == [True] * 4 and ties["two_edges"] == [True, False, False, True]
+    for j, name in enumerate(("edge_x1", "edge_y1", "edge_x2", "edge_y2")):
+        assert ties[name] == [i == j for i in range(4)], name
+    for name in ("disjoint", "inside", "label_0", "label_K+1", "zero_area"):
+        assert ties[name] == [False] * 4, name
+    g, b = prob["gt"][0, m[0, cases["inside"]]], pred[cases["inside"]]
+    assert g[0] < b[0] and g[1] < b[1] and b[2] < g[2] and b[3] < g[3]
+    # the oracle: matched = Gmax is background; prediction = gt has a zero box gradient only because each tie sends half each way
+    loss, dc, db = O.losses(prob, m, u, 4.0, True)
+    m2 = m.copy()
+    m2[0, prob["bg_gmax"]] = -1
+    loss2, dc2, db2 = O.losses(prob, m2, u, 4.0, True)
+    assert np.array_equal(loss, loss2) and np.array_equal(dc, dc2) and np.array_equal(db, db2)
+    assert (dc[0, prob["bg_gmax"]] == 0).all() and (db[0, prob["bg_gmax"], :4] == 0).all() and db[0, prob["bg_gmax"], 4] > 0
+    # (with the L1 term, prediction = gt: raw dx, dy equal their targets, |x|' = 0 there; raw w, h miss theirs by the 1e-8 inside the log)
+    assert np.allclose(db[0, cases["equal"], :2], 0, atol=1e-12) and np.allclose(db[0, cases["equal"], 2:4], -0.25, atol=1e-12)
+    no_l1 = O.losses(prob, m, u, 4.0, False)[2]
+    assert np.abs(no_l1[0, cases["equal"], :4]).max() < 1e-12 and np.abs(no_l1[0, cases["disjoint"], :4]).max() == 0
+    assert np.abs(no_l1[0, cases["edge_x1"], :4]).max() > 1e-3
+    for name in ("label_0", "label_K+1"):                             # every class column is a background term: the gradient is sigmoid(x) / nf
+        x = prob["cls"][0, cases[name], :K]
+        np.testing.assert_allclose(dc[0, cases[name]], 1 / (1 + np.exp(-x)) / 4.0, rtol=1e-12)
+    assert loss[3] > 2 * 18.0 / 4.0                                   # two targets of log(1e-8) = -18.4 in the L1 sum
+
+
+def test_tie_problem_is_decided_by_ties_alone():
+    """The float32 restatement with the kernel's class-cost form agrees exactly with float64; within a gt two costs are equal or more than
+    100 cost_tol apart; gt 1 of image 0 has its k-th and (k+1)-th cheapest candidates tied across the two 1024-point chunks; gts tie at
+    the top-10 IoU cut; image 1's gt has fewer than 10 candidates."""
+    prob = O.tie_problem()
+    assert prob["pts"].shape[0] == 1344 and prob["lvl_start"][1] == 1024
+    m, u, aux = O.assign(prob)
+    m32, u32, _ = O.assign(prob, np.float32, True)
+    assert np.array_equal(m, m32) and np.abs(u - u32).max() < 2.0 ** -20
+    spans, iou_cut = [], []
+    for n, a in enumerate(aux):
+        for g in range(a["G"]):
+            cost, k = a["cost"][g], int(a["dyn"][g])
+            vals = np.unique(cost)
+            assert all(vals[i + 1] - vals[i] > 100 * O.cost_tol(vals[i + 1]) for i in range(len(vals) - 1)), (n, g)
+            s = float(a["sums"][g])                                   # (a sum of zeros is exact; any other stays clear of the integers)
+            assert s == 0 or abs(s - round(s)) > 1e-3                 # compare()'s excuse c starts at 1e-4
+            order = np.argsort(cost, kind="stable")
+            if k < cost.size and cost[order[k - 1]] == cost[order[k]]:
+                tied = a["cand"][cost == cost[order[k - 1]]]
+                spans.append((n, g, bool((tied < 1024).any() and (tied >= 1024).any())))
+            top = -np.sort(-a["iou"][g])
+            if top.size > 10 and top[9] == top[10]:
+                iou_cut.append((n, g, float(top[9])))
+    assert (0, 1, True) in spans and (0, 0, False) in spans, spans
+    assert {(n, g) for n, g, _ in iou_cut} == {(0, 0), (0, 1), (0, 2)} and (0, 0, 1 / 16) in iou_cut, iou_cut
+    assert aux[1]["cand"].size == 8 and aux[0]["dyn"].tolist() == [1, 1, 1]
+    # lowest point index, then lowest gt index
+    assert np.argwhere(m >= 0).tolist() == [[0, 66], [0, 132], [0, 1316], [1, 1280]] and m[m >= 0].tolist() == [2, 1, 0, 0]
+    assert u[0, 132] == 0.5 and u[0, 1316] == 1 / 16 and u[0, 66] == 0 and m[0, 1058] == -1

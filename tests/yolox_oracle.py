@@ -193,7 +193,8 @@ def compare(prob, ref, matched_x):
 
 # ---- losses -----------------------------------------------------------------------------------------------------------------------------
 def losses(prob, matched, iou_t, nf, use_l1):
-    """float64 autograd: (loss4 = 5 * iou, obj, cls, l1; d_cls (N, P, K); d_box_obj (N, P, 5)) of the sum of the four."""
+    """float64 autograd: (loss4 = 5 * iou, obj, cls, l1; d_cls (N, P, K); d_box_obj (N, P, 5)) of the sum of the four.  A matched entry
+    outside 0 .. Gmax - 1 is background, as in the kernel."""
     K = prob["K"]
     cls = torch.tensor(prob["cls"][..., :K], dtype=torch.float64, requires_grad=True)
     bo = torch.tensor(prob["box_obj"][..., :5], dtype=torch.float64, requires_grad=True)
@@ -201,7 +202,7 @@ def losses(prob, matched, iou_t, nf, use_l1):
     st = torch.tensor(prob["stride"], dtype=torch.float64)
     gt = torch.tensor(prob["gt"], dtype=torch.float64)
     m = torch.tensor(matched)
-    fg = m >= 0
+    fg = (m >= 0) & (m < gt.shape[1])
     nf = max(float(nf), 1.0)
     n_idx = torch.nonzero(fg)[:, 0]
     g = gt[n_idx, m[fg]]                                   # (F, 5)
@@ -375,3 +376,96 @@ def inference_problem(B, H, W, K, seed=21):
     prob["box_obj"][..., 4] = rng.normal(0.0, 2.0, prob["box_obj"].shape[:2])
     prob["box_obj"][..., 2:4] = rng.normal(1.0, 0.5, prob["box_obj"].shape[:2] + (2,))
     return _finish(prob, rng)
+
+
+# ---- problems past the loss kernel's grid cap, on the kinks of the IoU loss and on exact cost ties (tests/test_yolox_edges_gpu.py) -------
+BIG_SHAPE = (3, 640, 640, 365, 40)
+
+
+@functools.lru_cache(maxsize=None)
+def big_loss_problem():
+    """(prob, matched, iou_t) at BIG_SHAPE: 3 x 8400 rows of 46 vectors.  The assignment is drawn, not computed: about 2 % of the points
+    are foreground with a valid gt index of their image and an iou_t in (0, 1) that float32 holds exactly."""
+    N, H, W, K, Gmax = BIG_SHAPE
+    rng = np.random.default_rng(31)
+    prob = _base(N, H, W, K, Gmax, rng)
+    for n, G in enumerate((Gmax, 17, 1)):
+        prob["num"][n] = G
+        prob["gt"][n, :G] = _rand_gts(rng, G, H, W, K)
+    prob = _finish(prob, rng)
+    P = prob["pts"].shape[0]
+    fg = rng.random((N, P)) < 0.02
+    matched = np.where(fg, rng.integers(0, prob["num"][:, None], (N, P)), -1).astype(np.int64)
+    iou_t = np.where(fg, rng.uniform(0.02, 0.98, (N, P)).astype(np.float32), np.float32(0)).astype(np.float64)
+    return prob, matched, iou_t
+
+
+KINK_CASES = ("equal", "edge_x1", "edge_y1", "edge_x2", "edge_y2", "two_edges", "disjoint", "inside", "label_0", "label_K+1", "zero_area")
+
+
+@functools.lru_cache(maxsize=None)
+def kink_problem():
+    """One image, one level of 12 x 12 points at stride 8, K = 3, one gt per foreground point.  Foreground rows have raw w = h = 0 (the
+    decoded box is 8 x 8) and raw dx, dy in eighths; gts lie on quarter pixels: every coordinate is exact in float32 and float64, in the
+    image frame and relative to the point.  With (X1, Y1, X2, Y2) the decoded prediction, prob["cases"] names the point of
+      equal       gt = prediction: all four min / max tie, iou = 1;
+      edge_x1, edge_y1, edge_x2, edge_y2   gt shares exactly that edge with the prediction, the other three differ, the overlap is positive;
+      two_edges   gt shares x1 and y2;
+      disjoint    gt and prediction do not meet: q = 0, iou loss 1, no box gradient from the IoU term;
+      inside      the prediction lies strictly inside its gt;
+      label_0, label_K+1   an overlapping gt whose label matches no class column: every class column is a background term;
+      zero_area   a gt with x1 = x2 and y1 = y2 inside the prediction: the L1 target is log(0 + 1e-8).
+    prob["bg_gmax"] is a background row whose matched entry is Gmax; every other row has matched = -1.  prob["matched"], prob["iou_t"]
+    (1, P) go with it."""
+    K, S, side = 3, 8, 12
+    rng = np.random.default_rng(41)
+    sizes = [(side, side)]
+    pts, lvl_start, stride = points(sizes, (S,))
+    P, G = side * side, len(KINK_CASES)
+    cls, box_obj = rng.normal(-2.0, 1.5, (1, P, 8)), rng.normal(0, 0.6, (1, P, 8))
+    cls[..., K:], box_obj[..., 5:] = 3.0, 3.0
+    # name -> (raw dx, raw dy, what is added to (X1, Y1, X2, Y2), label)
+    spec = {"equal": (0.25, -0.125, (0, 0, 0, 0), 1), "edge_x1": (0, 0.125, (0, -1.25, 2.5, -1.75), 2),
+            "edge_y1": (-0.125, 0, (1.5, 0, 3.25, 2), 3), "edge_x2": (0.375, 0.25, (-2.25, 0.75, 0, 1.5), 1),
+            "edge_y2": (0, -0.25, (-1.5, -3, -2.75, 0), 2), "two_edges": (0.125, 0.125, (0, -2.5, 1.25, 0), 3),
+            "disjoint": (0, 0, (11.25, 9.5, 13.25, 9.75), 1), "inside": (-0.25, 0.125, (-2.5, -1.25, 3.75, 0.5), 2),
+            "label_0": (0.125, 0, (-1.25, 1.5, 2.25, 2.75), 0), "label_K+1": (0, -0.125, (1.75, -2.25, 3.5, 1.25), K + 1)}
+    gt = np.zeros((1, G, 5), np.float32)
+    matched, iou_t, cases = np.full((1, P), -1, np.int64), np.zeros((1, P)), {}
+    for i, name in enumerate(KINK_CASES):
+        p = (1 + 3 * (i // 5)) * side + 1 + 2 * (i % 5)
+        dx, dy, add, lab = spec.get(name, (0, 0.125, None, 2))
+        cx, cy = pts[p, 0] + S * dx, pts[p, 1] + S * dy
+        box = np.array([cx - 4, cy - 4, cx + 4, cy + 4]) + add if add is not None else np.array([cx + 1.25, cy - 0.75, cx + 1.25, cy - 0.75])
+        gt[0, i] = list(box) + [lab]
+        box_obj[0, p, :4] = [dx, dy, 0, 0]
+        matched[0, p], iou_t[0, p], cases[name] = i, (i + 1) / 16, p
+    matched[0, 0] = G
+    return dict(N=1, H=side * S, W=side * S, K=K, sizes=sizes, pts=pts, lvl_start=lvl_start, stride=stride, strides=[S], gt=gt,
+                num=np.array([G], np.int32), cls=bf16(cls).astype(np.float64), box_obj=bf16(box_obj).astype(np.float64), matched=matched,
+                iou_t=iou_t, cases=cases, bg_gmax=0)
+
+
+@functools.lru_cache(maxsize=None)
+def tie_problem():
+    """Two 256 x 256 images, K = 3, P = 1344: the workgroup of a gt walks the points in two chunks, [0, 1024) = the stride-8 level and
+    [1024, 1344).  Every class logit is -2, every obj logit 0.5, every raw box 0: the prediction of a point is the stride x stride box
+    around it, IoUs are quotients of small integers, and the cost of a (gt, point) pair depends on that IoU and on the two inside tests
+    alone -- equal IoUs are equal costs, bit for bit, in float32 and float64.  Image 0:
+      gt 0  128 x 128 around the stride-8 point (176, 176): 225 + 49 + 16 points inside, IoU 1/256, 1/64 or 1/16; the 16 stride-32 points
+            tie at the top-10 cut and at the cost cut (k = 1);
+      gt 1  16 x 8 around (32, 32): the stride-8 point 132 (its 8 x 8 box inside the gt) and the stride-16 point 1058 (its box around the
+            gt) both have IoU 1/2 and no penalty: with k = 1 the k-th and (k+1)-th cheapest candidates tie across the two chunks;
+      gt 2  a zero-area gt: every IoU is 0, so its top-10 IoUs are all equal and every candidate of the image costs the same.
+    Image 1: a gt outside the image with 8 candidates (fewer than the 10 the dynamic k reads).  Rows >= num_gt hold NaN."""
+    N, H, W, K, Gmax = 2, 256, 256, 3, 4
+    sizes = level_sizes(H, W)
+    pts, lvl_start, stride = points(sizes)
+    P = pts.shape[0]
+    cls, box_obj = np.full((N, P, 8), -2.0), np.zeros((N, P, 8))
+    cls[..., K:], box_obj[..., 4], box_obj[..., 5:] = 3.0, 0.5, 3.0
+    gt = np.full((N, Gmax, 5), np.nan, np.float32)
+    gt[0, :3] = [[112, 112, 240, 240, 1], [24, 28, 40, 36, 2], [40.5, 200.5, 40.5, 200.5, 3]]
+    gt[1, 0] = [-30, -30, -14, -14, 1]
+    return dict(N=N, H=H, W=W, K=K, sizes=sizes, pts=pts, lvl_start=lvl_start, stride=stride, strides=list(STRIDES), gt=gt,
+                num=np.array([3, 1], np.int32), cls=cls, box_obj=box_obj)
