@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ._pm import BF16, F32, ParamStore, load_strict, need_device, round_up8, to_nchw, to_pm, workspace
+from ._pm import BF16, F32, Container, ParamStore, cut, load_strict, need_device, round_up8, to_nchw, to_pm, workspace
 from .batch_norm import BatchNormAct
 from .deformable import DeformConvWithOff, ModulatedDeformConvWithOff
 
@@ -98,6 +98,7 @@ def head_param_shapes(in_channels, num_classes):
 
 class DeconvLayer:
     """center_head.py:13-63."""
+    NORMS = ("dcn_bn", "up_bn")
 
     def __init__(self, in_planes, out_planes, deconv_kernel, deconv_stride=2, deconv_pad=1, deconv_out_pad=0, modulate_deform=True, seed=0,
                  device="cuda"):
@@ -133,7 +134,7 @@ class DeconvLayer:
         """Live on the caller's storage (a model's parameter arena): w / g = {name: fp32 view} in arena_shapes()' layouts, dcn_bn / up_bn
         the model's norm records.  See deformable.py adopt.  Every shape is checked before anything moves."""
         self._store.check(w, g)
-        self.dcn.adopt({k[4:]: v for k, v in w.items() if k.startswith("dcn.")}, {k[4:]: v for k, v in g.items() if k.startswith("dcn.")})
+        self.dcn.adopt(cut(w, "dcn"), cut(g, "dcn"))
         self._store.move(w, g)
         self.dcn_bn.adopt(dcn_bn)
         self.up_bn.adopt(up_bn)
@@ -170,7 +171,7 @@ class DeconvLayer:
 
     def load_state_dict(self, state):
         p = load_strict(state, self._shapes(), self.device)
-        self.dcn.load_state_dict({k[4:]: v for k, v in p.items() if k.startswith("dcn.")})
+        self.dcn.load_state_dict(cut(p, "dcn"))
         self.dcn_bn.load(p, "dcn_bn.")
         self.up_bn.load(p, "up_bn.")
         self._up_w().copy_(p["up_sample.weight"])
@@ -243,8 +244,9 @@ class DeconvLayer:
         return out
 
 
-class CenternetDeconv:
-    """center_head.py:66-88: len(deconv_kernel_sizes) DeconvLayers, channels[i] -> channels[i + 1], named deconv1 ..."""
+class CenternetDeconv(Container):
+    """center_head.py:66-88: len(deconv_kernel_sizes) DeconvLayers, channels[i] -> channels[i + 1], named deconv1 ...  adopt()'s norms:
+    {"deconvI.dcn_bn" / "deconvI.up_bn": norm record}."""
 
     def __init__(self, channels, deconv_kernel_sizes, modulate_deform, seed=0, device="cuda"):
         self.num_layers = len(deconv_kernel_sizes)
@@ -252,7 +254,7 @@ class CenternetDeconv:
             raise ValueError(f"CenternetDeconv: {len(channels)} channel counts for {self.num_layers} layers")
         for i in range(self.num_layers):        # every layer is validated before any of them touches the device
             _validate_deconv(channels[i], channels[i + 1], deconv_kernel_sizes[i], 2, 1, 0)
-        self.channels = list(channels)
+        self.channels, self.device = list(channels), torch.device(device)
         for i in range(self.num_layers):
             setattr(self, f"deconv{i + 1}", DeconvLayer(channels[i], channels[i + 1], deconv_kernel=deconv_kernel_sizes[i],
                                                         modulate_deform=modulate_deform, seed=seed + 10 * i, device=device))
@@ -261,52 +263,7 @@ class CenternetDeconv:
     def layers(self):
         return [(f"deconv{i + 1}", getattr(self, f"deconv{i + 1}")) for i in range(self.num_layers)]
 
-    def _merge(self, fn):
-        return {f"{n}.{k}": v for n, l in self.layers() for k, v in fn(l).items()}
-
-    def names(self):
-        return [f"{n}.{k}" for n, l in self.layers() for k in l.names()]
-
-    def params(self):
-        return self._merge(lambda l: l.params())
-
-    def grads(self):
-        return self._merge(lambda l: l.grads())
-
-    def state_dict(self):
-        return self._merge(lambda l: l.state_dict())
-
-    def load_state_dict(self, state):
-        extra = sorted(set(state) - set(self.names()))
-        if extra:
-            raise KeyError(f"unexpected parameter(s) {extra}")
-        for n, l in self.layers():
-            l.load_state_dict({k[len(n) + 1:]: v for k, v in state.items() if k.startswith(n + ".")})
-
-    def repack(self):
-        for _, l in self.layers():
-            l.repack()
-
-    def arena_shapes(self):
-        return self._merge(lambda l: l.arena_shapes())
-
-    def adopt(self, w, g, norms):
-        """norms: {"deconvI.dcn_bn" / "deconvI.up_bn": norm record}.  See DeconvLayer.adopt."""
-        for n, l in self.layers():
-            cut = lambda d: {k[len(n) + 1:]: v for k, v in d.items() if k.startswith(n + ".")}
-            l.adopt(cut(w), cut(g), norms[n + ".dcn_bn"], norms[n + ".up_bn"])
-
-    def refresh_eval(self):
-        for _, l in self.layers():
-            l.refresh_eval()
-
-    def train(self, mode=True):
-        for _, l in self.layers():
-            l.train(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
+    _children = layers
 
     def forward_pm(self, x, N, H, W):
         for _, l in self.layers():
@@ -381,6 +338,7 @@ def validate_neck(channels, deconv_kernel_sizes):
 class CenterHead:
     """center_head.py:106-131."""
     BRANCHES = ("cls", "wh", "reg")
+    NORMS = ()
 
     def __init__(self, in_channels=64, num_classes=80, prior_prob=0.1, seed=0, device="cuda"):
         C, K = in_channels, num_classes
@@ -449,6 +407,9 @@ class CenterHead:
         """The three feat_convs are one 3C-row convolution (cls | wh | reg); the output convolutions are read as fp32 masters by the kernel."""
         C = self.in_channels
         ops.weight_pack(self._store.w["feat_conv.weight"], None, self._feat_wf, self._feat_wd, 3 * C, 9, C)
+
+    def refresh_eval(self):
+        pass
 
     def train(self, mode=True):
         self.training = bool(mode)

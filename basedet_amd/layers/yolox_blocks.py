@@ -2,7 +2,8 @@
 (layers/blocks/yolo_block.py:36-133), CSPDarknet (models/cls/csp_darknet.py) and YOLOPAFPN (layers/backbone/yolo_fpn.py:93-199), forward
 and backward.
 
-Every convolution is layers/yolox_head.py's ConvBNSiLU: one storage path, one norm.  What lies between the convolutions is
+Every convolution is layers/yolox_head.py's ConvBNSiLU (one storage path, layers/_pm.py ParamStore; one norm), every module a
+layers/_pm.py Container of them.  What lies between the convolutions is
 csrc/yolox_neck.hip: bd_focus_fwd (space-to-depth of the halo image into 12 + 4 zero channels), bd_spp_fwd / bd_spp_bwd (the three
 stride-1 max-pools and their adjoint under the first-maximum rule), bd_cat2_fwd / bd_cat2_bwd (channel concatenation and split; PAFPN's
 nearest 2x upsample is folded into the first operand) and bd_add_bf16 for Bottleneck's shortcut.  The convolution and norm entries
@@ -20,7 +21,7 @@ Reproducibility: every forward output, and everything the backward writes, is bi
 import torch
 
 from .. import ops
-from ._pm import BF16, load_strict, need_device, to_nchw, to_pm
+from ._pm import BF16, Block, Container, load_strict, need_device, to_nchw, to_pm
 from .yolox_head import ConvBNSiLU, conv_param_shapes, validate_conv
 
 __all__ = ["Focus", "SPPBottleneck", "Bottleneck", "CSPLayer", "CSPDarknet", "YOLOPAFPN"]
@@ -103,91 +104,6 @@ def pafpn_param_shapes(depth, width, in_channels=(256, 512, 1024), backbone=None
 
 
 # ---- what the modules share -------------------------------------------------------------------------------------------------------------------
-class _Module:
-    """A composition of ConvBNSiLU layers and other _Modules: `_children()` lists them under the reference's names and order."""
-    training = True
-
-    def _children(self):
-        raise NotImplementedError
-
-    def _leaves(self):
-        """[(name, ConvBNSiLU)] in the reference's order."""
-        out = []
-        for n, c in self._children():
-            out += [(n, c)] if isinstance(c, ConvBNSiLU) else [(f"{n}.{k}", v) for k, v in c._leaves()]
-        return out
-
-    def _shapes(self):
-        return {f"{n}.{k}": v for n, c in self._leaves() for k, v in c._shapes().items()}
-
-    def names(self):
-        return list(self._shapes())
-
-    def params(self):
-        return {f"{n}.{k}": v for n, c in self._leaves() for k, v in c.params().items()}
-
-    def grads(self):
-        return {f"{n}.{k}": v for n, c in self._leaves() for k, v in c.grads().items()}
-
-    def state_dict(self):
-        return {f"{n}.{k}": v for n, c in self._leaves() for k, v in c.state_dict().items()}
-
-    def load_state_dict(self, state):
-        p = load_strict(state, self._shapes(), self.device)
-        for n, c in self._leaves():
-            c.load_state_dict({k[len(n) + 1:]: v for k, v in p.items() if k.startswith(n + ".")})
-
-    def repack(self):
-        for _, c in self._leaves():
-            c.repack()
-
-    def arena_shapes(self):
-        """name -> shape of the fp32 masters in the kernels' layouts: "<leaf>.weight", OHWI (Focus's with its 16 input channels)."""
-        return {f"{n}.weight": c.arena_shapes()["weight"] for n, c in self._leaves()}
-
-    def adopt(self, w, g, norms):
-        """Live on the caller's storage (a model's parameter arena): w / g = {"<leaf>.weight": fp32 view} of arena_shapes(), norms =
-        {"<leaf>.norm": the model's norm record}.  See ConvBNSiLU.adopt."""
-        for n, c in self._leaves():
-            c.adopt({"weight": w[n + ".weight"]}, {"weight": g[n + ".weight"]}, norms[n + ".norm"])
-
-    def refresh_eval(self):
-        for _, c in self._leaves():
-            c.refresh_eval()
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        for _, c in self._leaves():
-            c.train(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-
-class _Block(_Module):
-    """A module with one pixel-major input and one output of the same size: the NCHW wrappers."""
-
-    def __call__(self, x):
-        need_device(x, type(self).__name__)
-        N, C, H, W = x.shape
-        if C != self.cin:
-            raise ValueError(f"input has {C} channels, the layer {self.cin}")
-        self._in_size = (N, H, W)
-        return to_nchw(self.forward_pm(to_pm(x), N, H, W), N, H, W)
-
-    forward = __call__
-
-    def backward(self, dy, accumulate=False):
-        need_device(dy, type(self).__name__ + ".backward")
-        if getattr(self, "_in_size", None) is None:
-            raise RuntimeError("backward() before a forward")
-        N, H, W = self._in_size
-        if tuple(dy.shape) != (N, self.cout, H, W):
-            raise ValueError(f"gradient shape {tuple(dy.shape)} does not match the forward output")
-        return to_nchw(self.backward_pm(to_pm(dy), accumulate), N, H, W)
-
-
 def _convs(specs, seed, device):
     """The ConvBNSiLU layers of validated specs by local name; each from its own seed."""
     return {n: ConvBNSiLU(cin, cout, k, stride, seed=seed + i, device=device) for i, (n, cin, cout, k, stride) in enumerate(specs)}
@@ -217,15 +133,16 @@ class _FocusConv(ConvBNSiLU):
 
     def __init__(self, cout, k, seed, device):
         super().__init__(16, cout, k, 1, seed=seed, device=device)
-        self._w[..., self.REAL:] = 0
-        self._w[..., :self.REAL] *= (16 / self.REAL) ** 0.5          # N(0, sqrt(1 / fan_in)) of the 12 real channels
+        w = self._store.w["weight"]
+        w[..., self.REAL:] = 0
+        w[..., :self.REAL] *= (16 / self.REAL) ** 0.5          # N(0, sqrt(1 / fan_in)) of the 12 real channels
         self.repack()
 
     def _shapes(self):
         return conv_param_shapes(self.REAL, self.cout, self.k)
 
     def params(self):
-        return dict(super().params(), weight=self._w.permute(0, 3, 1, 2)[:, :self.REAL])
+        return dict(super().params(), weight=self._store.w["weight"].permute(0, 3, 1, 2)[:, :self.REAL])
 
     def state_dict(self):
         s = super().state_dict()
@@ -233,8 +150,9 @@ class _FocusConv(ConvBNSiLU):
 
     def load_state_dict(self, state):
         p = load_strict(state, self._shapes(), self.device)
-        self._w.zero_()
-        self._w[..., :self.REAL] = p["weight"].permute(0, 2, 3, 1)
+        w = self._store.w["weight"]
+        w.zero_()
+        w[..., :self.REAL] = p["weight"].permute(0, 2, 3, 1)
         self.norm.load(p, "norm.")
         self.repack()
 
@@ -244,10 +162,10 @@ class _FocusConv(ConvBNSiLU):
 
     def pad_grad(self):
         """The 4 pad columns of the weight gradient (a copy): exactly zero."""
-        return self._gw[..., self.REAL:].clone()
+        return self._store.g["weight"][..., self.REAL:].clone()
 
 
-class Focus(_Module):
+class Focus(Container):
     """basic_block.py:13-32 with in_channels = 3: bd_focus_fwd, then ConvBNSiLU(12 + 4 zero channels, cout, ksize)."""
 
     def __init__(self, in_channels=3, out_channels=32, ksize=3, stride=1, activation="silu", seed=0, device="cuda"):
@@ -297,7 +215,7 @@ class Focus(_Module):
         self.backward_pm(to_pm(dy), accumulate)
 
 
-class SPPBottleneck(_Block):
+class SPPBottleneck(Block):
     """yolo_block.py:36-60, kernel_sizes (5, 9, 13): conv1 -> bd_spp_fwd -> conv2."""
 
     def __init__(self, in_channels, out_channels, kernel_sizes=(5, 9, 13), activation="silu", seed=0, device="cuda"):
@@ -332,7 +250,7 @@ class SPPBottleneck(_Block):
         return self.conv1.backward_pm(d_h, accumulate, add=add)
 
 
-class Bottleneck(_Block):
+class Bottleneck(Block):
     """yolo_block.py:63-88: conv1 (1x1) -> conv2 (3x3) [+ x].  With the shortcut, x receives the output gradient and conv1's data
     gradient: conv1's accumulating dgrad adds the two."""
 
@@ -357,7 +275,7 @@ class Bottleneck(_Block):
         return self.conv1.backward_pm(g1, accumulate, add=g if self.use_add else None)
 
 
-class CSPLayer(_Block):
+class CSPLayer(Block):
     """yolo_block.py:91-133: conv3(cat(m(conv1(x)), conv2(x))).  conv1 and conv2 read the same x as two launches, as the head's towers
     do; conv2's data gradient is added onto conv1's."""
 
@@ -389,7 +307,7 @@ class CSPLayer(_Block):
         return self.conv2.backward_pm(d2, accumulate, dx=dx)
 
 
-class CSPDarknet(_Module):
+class CSPDarknet(Container):
     """csp_darknet.py: stem (Focus) and dark2 .. dark5.  forward_pm returns the named features; backward_pm takes their gradients and sums
     them where a feature also feeds the next stage (the next stage's first convolution adds its data gradient onto the feature's)."""
     STAGES = ("dark2", "dark3", "dark4", "dark5")
@@ -465,7 +383,7 @@ class CSPDarknet(_Module):
         self.backward_pm({k: to_pm(v) for k, v in d_feats.items()}, accumulate)
 
 
-class YOLOPAFPN(_Module):
+class YOLOPAFPN(Container):
     """yolo_fpn.py:93-199 on a CSPDarknet.  forward_pm returns (pan_out2, pan_out1, pan_out0) at strides 8 / 16 / 32; backward_pm runs the
     whole graph backwards down to the stem.  The two upsample-and-concatenate steps are bd_cat2_fwd(up=1); fpn_out0 and fpn_out1 (two
     concatenations each), dark3 and dark4 (a concatenation and the next stage), pan_out2 and pan_out1 (an output and a bottom-up

@@ -4,8 +4,9 @@ operator every YOLOX convolution ends in, and the decoupled head that writes the
 Calling convention of layers/center_head.py: `layer(x)` takes and returns NCHW fp32 DEVICE tensors (a host tensor raises BasedetHipError:
 no CPU fallback); `forward_pm` / `backward_pm` on pixel-major bf16; `params()` (fp32 device masters by name, views an optimizer may update
 in place) / `repack()` / `grads()` (copies); strict `state_dict()` / `load_state_dict()` under the reference's names; `train()` /
-`eval()`.  The masters are kept in the kernels' layouts and loaded in place: one path, so `adopt()` onto a model arena (models/yolox.py
-YOLOX) is a move as it is for center_head.py's layers.  The norm is layers/batch_norm.py BatchNormAct("silu").
+`eval()`.  Storage as in center_head.py: ConvBNSiLU and the predictors each hold a layers/_pm.py ParamStore (masters in the kernels'
+layouts, loaded in place; `adopt()` onto a model arena, models/yolox.py YOLOX, is its move()), and YOLOXHead is a _pm.py Container of
+them.  The norm is layers/batch_norm.py BatchNormAct("silu").
 
 ConvBNSiLU = bd_conv2d_fwd (no bias, no epilogue) -> bd_bn_stats_fwd -> bd_bn_silu_fwd; backward = bd_bn_silu_bwd_reduce ->
 bd_bn_silu_bwd_apply -> bd_conv2d_wgrad + bd_conv2d_dgrad.  The SiLU gate is recomputed from the pre-norm tensor inside the norm's two
@@ -30,7 +31,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ._pm import BF16, F32, load_strict, need_device, round_up8, to_nchw, to_pm, workspace
+from ._pm import BF16, Container, ParamStore, cut, load_strict, need_device, round_up8, to_nchw, to_pm, workspace
 from .batch_norm import BatchNormAct
 
 __all__ = ["ConvBNSiLU", "YOLOXHead"]
@@ -74,6 +75,7 @@ def head_param_shapes(num_classes, in_channels, mid_channels):
 
 class ConvBNSiLU:
     """The reference's Conv2d(cin, cout, k, stride, padding=k // 2, bias=False, norm="BN", activation="silu")."""
+    NORMS = ("norm",)
 
     def __init__(self, cin, cout, k, stride=1, seed=0, eps=BN_EPS, momentum=BN_MOMENTUM, device="cuda"):
         validate_conv(cin, cout, k, stride)
@@ -83,11 +85,11 @@ class ConvBNSiLU:
         # M.Conv2d's default init as layers/center_head.py SingleHead takes it: N(0, sqrt(1 / fan_in)); the master is OHWI, what
         # bd_weight_pack reads and bd_conv2d_wgrad writes
         w = (rng.standard_normal((cout, cin, k, k)) * math.sqrt(1.0 / (cin * k * k))).astype(np.float32)
-        self._w = torch.from_numpy(w).permute(0, 2, 3, 1).contiguous().to(self.device)
+        self._store = ParamStore({"weight": (cout, k, k, cin)}, self.device)
+        self._store.w["weight"].copy_(torch.from_numpy(w).permute(0, 2, 3, 1))
         self.norm = BatchNormAct(cout, "silu", self.eps, self.momentum, self.device)
         self._wf = torch.empty((cout, k * k, cin), dtype=BF16, device=self.device)
         self._wd = torch.empty((cin, k * k, cout), dtype=BF16, device=self.device)
-        self._gw = None
         self._saved = None
         self.repack()
 
@@ -104,35 +106,35 @@ class ConvBNSiLU:
 
     def params(self):
         """The trainable fp32 device masters by name (weight: the OIHW view of the OHWI master)."""
-        return {"weight": self._w.permute(0, 3, 1, 2), "norm.weight": self.norm.p["weight"], "norm.bias": self.norm.p["bias"]}
+        return {"weight": self._store.w["weight"].permute(0, 3, 1, 2), "norm.weight": self.norm.p["weight"], "norm.bias": self.norm.p["bias"]}
+
+    def pack_entry(self):
+        """ops.weight_pack's arguments, and this layer's entry of a model's pack table (ops.build_pack_table)."""
+        return self._store.w["weight"], None, self._wf, self._wd, self.cout, self.k * self.k, self.cin
 
     def repack(self):
-        ops.weight_pack(self._w, None, self._wf, self._wd, self.cout, self.k * self.k, self.cin)
+        ops.weight_pack(*self.pack_entry())
 
     def refresh_eval(self):
         self.norm.refresh_eval()
 
     def arena_shapes(self):
         """name -> shape of the fp32 master in the kernels' layout (OHWI).  The norm's vectors are not listed: adopt() takes a norm record."""
-        return {"weight": tuple(self._w.shape)}
+        return dict(self._store.shapes)
 
     def adopt(self, w, g, norm_state):
         """Live on the caller's storage (a model's parameter arena): w / g = {"weight": fp32 view of arena_shapes()}, norm_state the
         model's norm record (BatchNormAct.adopt).  The current values move in; the same path on other storage (center_head.py adopt)."""
-        shape = tuple(self._w.shape)
-        if tuple(w["weight"].shape) != shape or tuple(g["weight"].shape) != shape:
-            raise ValueError(f"adopt: 'weight' needs fp32 views of shape {shape}")
-        w["weight"].copy_(self._w)
-        self._w, self._gw = w["weight"], g["weight"]
+        self._store.move(w, g)
         self.norm.adopt(norm_state)
         self.repack()
 
     def state_dict(self):
-        return {"weight": self._w.permute(0, 3, 1, 2).contiguous().cpu(), **self.norm.state("norm.")}
+        return {"weight": self._store.w["weight"].permute(0, 3, 1, 2).contiguous().cpu(), **self.norm.state("norm.")}
 
     def load_state_dict(self, state):
         p = load_strict(state, self._shapes(), self.device)
-        self._w.copy_(p["weight"].permute(0, 2, 3, 1))
+        self._store.w["weight"].copy_(p["weight"].permute(0, 2, 3, 1))
         self.norm.load(p, "norm.")
         self.repack()
 
@@ -147,9 +149,9 @@ class ConvBNSiLU:
 
     def grads(self):
         """Copies, not views of the storage the next backward writes."""
-        if self._gw is None:
+        if self._store.g is None:
             raise RuntimeError("grads() before a backward")
-        return {"weight": self._gw.permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format),
+        return {"weight": self._store.g["weight"].permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format),
                 "norm.weight": self.norm.g["weight"].clone(), "norm.bias": self.norm.g["bias"].clone()}
 
     # ---- forward / backward ------------------------------------------------------------------------------------------------------------------
@@ -184,10 +186,8 @@ class ConvBNSiLU:
         if tuple(g.shape) != (M, C) or g.dtype != BF16:
             raise ValueError(f"backward_pm: expected bf16 {(M, C)}, got {g.dtype} {tuple(g.shape)}")
         gy = self.norm.backward_pm(g, accumulate)
-        if self._gw is None:
-            accumulate = False
-            self._gw = torch.empty_like(self._w)
-        ops.conv2d_wgrad(d, x, gy, self._gw, workspace(ops.conv2d_wgrad_workspace_bytes(d), self.device), accumulate=accumulate)
+        gr, accumulate = self._store.grad(accumulate)
+        ops.conv2d_wgrad(d, x, gy, gr["weight"], workspace(ops.conv2d_wgrad_workspace_bytes(d), self.device), accumulate=accumulate)
         if add is not None and (dx is not None or tuple(add.shape) != tuple(x.shape) or add.dtype != BF16):
             raise ValueError(f"backward_pm: add must be bf16 {tuple(x.shape)}, and is given without dx")
         if not need_dx:
@@ -227,48 +227,74 @@ class _PredConv:
     """A 1x1 predictor with bias whose `rows` real output rows are padded to `ld` (a multiple of 8) and written in place into one level of
     a [N P][ld] tensor.  The masters are the padded (ld, 1, 1, cin) weight and (ld,) bias; rows >= `rows` are zero and stay zero."""
 
+    NORMS = ()
+
     def __init__(self, cin, rows, ld, rng, device):
         self.cin, self.rows, self.ld, self.device = cin, rows, ld, device
         w = np.zeros((ld, 1, 1, cin), np.float32)
         w[:rows, 0, 0] = rng.standard_normal((rows, cin)) * math.sqrt(1.0 / cin)
-        self.w = torch.from_numpy(w).to(device)
-        self.b = torch.zeros(ld, dtype=F32, device=device)
+        self._store = ParamStore({"weight": (ld, 1, 1, cin), "bias": (ld,)}, device)
+        self._store.w["weight"].copy_(torch.from_numpy(w))
         self.wf = torch.empty((ld, 1, cin), dtype=BF16, device=device)
         self.wd = torch.empty((cin, 1, ld), dtype=BF16, device=device)
-        self.gw = self.gb = None
+
+    # The layer protocol on the padded masters; YOLOXHead presents them under the reference's names (_pred_views).
+    def _shapes(self):
+        return dict(self._store.shapes)
+
+    arena_shapes = _shapes          # (the state is the padded masters themselves)
+
+    def names(self):
+        return list(self._store.shapes)
+
+    def params(self):
+        return dict(self._store.w)
+
+    def grads(self):
+        return {k: v.clone() for k, v in self._store.g.items()}
+
+    def state_dict(self):
+        return {k: v.detach().cpu() for k, v in self._store.w.items()}
+
+    def load_state_dict(self, state):
+        p = load_strict(state, self._store.shapes, self.device)
+        for k, v in self._store.w.items():
+            v.copy_(p[k])
+        self.repack()
+
+    def pack_entry(self):
+        return self._store.w["weight"], None, self.wf, self.wd, self.ld, 1, self.cin
 
     def repack(self):
-        ops.weight_pack(self.w, None, self.wf, self.wd, self.ld, 1, self.cin)
-
-    def arena_shapes(self):
-        return {"weight": tuple(self.w.shape), "bias": tuple(self.b.shape)}
+        ops.weight_pack(*self.pack_entry())
 
     def adopt(self, w, g):
         """Live on the caller's storage: w / g = {"weight", "bias"} fp32 views of the padded masters (ConvBNSiLU.adopt)."""
-        for k, shape in self.arena_shapes().items():
-            if tuple(w[k].shape) != shape or tuple(g[k].shape) != shape:
-                raise ValueError(f"adopt: {k!r} needs fp32 views of shape {shape}")
-        w["weight"].copy_(self.w)
-        w["bias"].copy_(self.b)
-        self.w, self.b, self.gw, self.gb = w["weight"], w["bias"], g["weight"], g["bias"]
+        self._store.move(w, g)
         self.repack()
+
+    def refresh_eval(self):
+        pass
+
+    def train(self, mode=True):
+        return self
 
     def desc(self, N, H, W, off, P):
         return ops.conv_desc(ops.single(N, H, W), ops.Geom(N, [H], [W], [off], P), self.cin, self.ld, 1, 1, 1, 0)
 
     def forward(self, d, x, out):
-        ops.conv2d_fwd(d, x, self.wf, self.b, out)
+        ops.conv2d_fwd(d, x, self.wf, self._store.w["bias"], out)
 
     def backward(self, d, x, g, accumulate):
-        if self.gw is None:          # (allocated once, like ConvBNSiLU's: a backward without `accumulate` overwrites every element)
-            accumulate = False
-            self.gw, self.gb = torch.empty_like(self.w), torch.empty_like(self.b)
-        ops.conv2d_wgrad_bias(d, x, g, self.gw, self.gb, workspace(ops.conv2d_wgrad_bias_workspace_bytes(d), self.device), accumulate=accumulate)
+        gr, accumulate = self._store.grad(accumulate)
+        ops.conv2d_wgrad_bias(d, x, g, gr["weight"], gr["bias"], workspace(ops.conv2d_wgrad_bias_workspace_bytes(d), self.device),
+                              accumulate=accumulate)
         return ops.conv2d_dgrad(d, g, self.wd, torch.empty_like(x))
 
 
-class YOLOXHead:
-    """yolo_head.py:35-121."""
+class YOLOXHead(Container):
+    """yolo_head.py:35-121.  Its children are the stems, the tower blocks and the padded predictors; the reference's predictor names
+    (cls_preds / reg_preds / obj_preds, real rows only) are views of the padded ones (_pred_views)."""
 
     def __init__(self, num_classes, in_channels=(256, 512, 1024), mid_channels=256, act="silu", depthwise=False, prior_prob=0.01, seed=0,
                  device="cuda"):
@@ -297,108 +323,61 @@ class YOLOXHead:
             self.reg_convs.append([ConvBNSiLU(mid, mid, 3, seed=s + 3 + i, device=device) for i in range(2)])
             rng = np.random.default_rng(s + 5)
             cp, rp = _PredConv(mid, K, self.cls_ld, rng, self.device), _PredConv(mid, 5, 8, rng, self.device)
-            cp.b[:K] = bias_value
-            rp.b[4] = bias_value
+            cp._store.w["bias"][:K] = bias_value
+            rp._store.w["bias"][4] = bias_value
             self.cls_preds.append(cp)
             self.regobj_preds.append(rp)
         self._saved = None
         self.repack()
 
     # ---- parameters ------------------------------------------------------------------------------------------------------------------------
-    def _shapes(self):
-        return head_param_shapes(self.num_classes, self.in_channels, self.mid_channels)
-
-    def names(self):
-        return list(self._shapes())
-
-    def _blocks(self):
-        """[(prefix, ConvBNSiLU)] in the reference's order."""
+    def _children(self):
+        """The blocks in the reference's order, then per level the padded class predictor and the fused reg + obj predictor (reg 0-3,
+        obj 4, 5-7 zero).  arena_shapes() lists them in this order: every block's OHWI weight, then the predictors' padded weights and
+        biases."""
         L = range(len(self.in_channels))
         out = [(f"stems.{l}", self.stems[l]) for l in L]
         out += [(f"cls_convs.{l}.{i}", self.cls_convs[l][i]) for l in L for i in range(2)]
         out += [(f"reg_convs.{l}.{i}", self.reg_convs[l][i]) for l in L for i in range(2)]
-        return out
+        return out + [(f"cls_preds.{l}", self.cls_preds[l]) for l in L] + [(f"regobj_preds.{l}", self.regobj_preds[l]) for l in L]
 
-    def _pred_views(self, which):
-        """The reference's predictor tensors as views of the padded masters (which = "w" / "b") or gradients ("gw" / "gb")."""
+    def _shapes(self):
+        return head_param_shapes(self.num_classes, self.in_channels, self.mid_channels)
+
+    def _pred_views(self, d):
+        """The reference's predictor tensors as views of the padded ones in d, a dict by the children's names."""
         K, mid, out = self.num_classes, self.mid_channels, {}
-        wb = "weight" if which in ("w", "gw") else "bias"
-        shape = (lambda r: (r, mid, 1, 1)) if wb == "weight" else (lambda r: (r,))
-        for l in range(len(self.in_channels)):
-            c, r = getattr(self.cls_preds[l], which), getattr(self.regobj_preds[l], which)
-            out[f"cls_preds.{l}.{wb}"] = c[:K].view(shape(K))
-            out[f"reg_preds.{l}.{wb}"] = r[0:4].view(shape(4))
-            out[f"obj_preds.{l}.{wb}"] = r[4:5].view(shape(1))
+        for wb, shape in (("weight", lambda r: (r, mid, 1, 1)), ("bias", lambda r: (r,))):
+            for l in range(len(self.in_channels)):
+                c, r = d[f"cls_preds.{l}.{wb}"], d[f"regobj_preds.{l}.{wb}"]
+                out[f"cls_preds.{l}.{wb}"] = c[:K].view(shape(K))
+                out[f"reg_preds.{l}.{wb}"] = r[0:4].view(shape(4))
+                out[f"obj_preds.{l}.{wb}"] = r[4:5].view(shape(1))
         return out
 
     def _ordered(self, d):
+        """d by the children's names -> by the reference's names, in its order."""
+        d = {**d, **self._pred_views(d)}
         return {k: d[k] for k in self._shapes() if k in d}
 
     def params(self):
-        p = {f"{n}.{k}": v for n, b in self._blocks() for k, v in b.params().items()}
-        p.update(self._pred_views("w"))
-        p.update(self._pred_views("b"))
-        return self._ordered(p)
+        return self._ordered(super().params())
 
     def grads(self):
-        if self.cls_preds[0].gw is None:
-            raise RuntimeError("grads() before a backward")
-        g = {f"{n}.{k}": v for n, b in self._blocks() for k, v in b.grads().items()}
-        g.update({k: v.clone() for which in ("gw", "gb") for k, v in self._pred_views(which).items()})
-        return self._ordered(g)
+        return self._ordered(super().grads())
 
     def state_dict(self):
-        s = {f"{n}.{k}": v for n, b in self._blocks() for k, v in b.state_dict().items()}
-        s.update({k: v.detach().cpu().clone() for w in ("w", "b") for k, v in self._pred_views(w).items()})
-        return self._ordered(s)
+        return self._ordered(super().state_dict())
 
     def load_state_dict(self, state):
+        """Strict, under the reference's names; the predictors load their padded tensors: the real rows from `state`, pad rows zero."""
         p = load_strict(state, self._shapes(), self.device)
-        for n, b in self._blocks():
-            b.load_state_dict({k[len(n) + 1:]: v for k, v in p.items() if k.startswith(n + ".")})
-        for w in ("w", "b"):
-            for k, v in self._pred_views(w).items():
-                v.copy_(p[k])
-        self.repack()
-
-    def repack(self):
-        for _, b in self._blocks():
-            b.repack()
-        for c in self.cls_preds + self.regobj_preds:
-            c.repack()
-
-    def _preds(self):
-        """[(prefix, _PredConv)]: per level the padded class predictor and the fused reg + obj predictor."""
-        L = range(len(self.in_channels))
-        return [(f"cls_preds.{l}", self.cls_preds[l]) for l in L] + [(f"regobj_preds.{l}", self.regobj_preds[l]) for l in L]
-
-    def arena_shapes(self):
-        """name -> shape of the fp32 masters in the kernels' layouts: every block's OHWI weight, then the predictors' padded weights and
-        biases (cls_preds.l: round_up(K, 8) rows; regobj_preds.l: reg 0-3, obj 4, 5-7 zero).  The norms' vectors are not listed."""
-        out = {f"{n}.weight": b.arena_shapes()["weight"] for n, b in self._blocks()}
-        out.update({f"{n}.{k}": v for n, p in self._preds() for k, v in p.arena_shapes().items()})
-        return out
-
-    def adopt(self, w, g, norms):
-        """Live on the caller's storage (a model's parameter arena): w / g = {name: fp32 view} of arena_shapes(), norms =
-        {"<block>.norm": the model's norm record}.  See ConvBNSiLU.adopt."""
-        for n, b in self._blocks():
-            b.adopt({"weight": w[n + ".weight"]}, {"weight": g[n + ".weight"]}, norms[n + ".norm"])
-        for n, p in self._preds():
-            p.adopt({k: w[f"{n}.{k}"] for k in ("weight", "bias")}, {k: g[f"{n}.{k}"] for k in ("weight", "bias")})
-
-    def refresh_eval(self):
-        for _, b in self._blocks():
-            b.refresh_eval()
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        for _, b in self._blocks():
-            b.train(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
+        padded = {k: torch.zeros_like(v) for k, v in super().params().items() if "_preds." in k}
+        for k, v in self._pred_views(padded).items():
+            v.copy_(p[k])
+        p.update(padded)
+        for n, c in self._children():
+            c.load_state_dict(cut(p, n))
 
     # ---- forward / backward ------------------------------------------------------------------------------------------------------------------
     def forward_pm(self, feats, N, sizes):

@@ -27,10 +27,11 @@ import torch
 import torch.nn.functional as TF
 
 from basedet_amd import ops
-from basedet_amd.layers._pm import need_device_all, round_up8
+from basedet_amd.layers._pm import need_device_all, round_up8, round_up32
 from basedet_amd.utils.registry import registers
 
 from . import params as P
+from .adopted import AdoptedParts
 from .fpn_base import FPNDetector
 
 __all__ = ["CenterNet", "CenterNetGT", "CenterNetDecoder", "centernet_ground_truth", "gather_feature", "modified_focal_loss", "reg_l1_loss"]
@@ -343,7 +344,7 @@ class CenterNet(FPNDetector):
         DOWN_SCALE, and the gt slots fit HEAD.TENSOR_DIM.  Inference reads neither key."""
         m = cfg.MODEL
         ds = m.HEAD.DOWN_SCALE
-        hp, wp = ((int(v) + 31) // 32 * 32 for v in image_hw)
+        hp, wp = (round_up32(v) for v in image_hw)
         want = (int(hp // ds), int(wp // ds))
         if tuple(m.OUTPUT_SIZE) != want:
             raise ValueError(f"MODEL.OUTPUT_SIZE = {tuple(m.OUTPUT_SIZE)!r} does not match this batch: the padded input {hp} x {wp} / "
@@ -358,31 +359,23 @@ class CenterNet(FPNDetector):
         self.neck = CenternetDeconv(list(h.DECONV_CHANNEL), list(h.DECONV_KERNEL), bool(h.MODULATE_DEFORM), device=self.device)
         self.head = CenterHead(h.IN_CHANNELS, self.num_classes, h.CLS_PRIOR_PROB, device=self.device)
         self.cls_ld = self.head.cls_ld
+        self._adopted = AdoptedParts([("upsample", self.neck), ("head", self.head)], self.device)
         # the neck's norms are records of the model's LiveNorms: running statistics in norms.running (broadcast, EMA buffer average)
-        self._neck_norms = {f"{n}.{b}": self.norms.add(f"upsample.{n}.{b}", l.out_planes) for n, l in self.neck.layers()
-                            for b in ("dcn_bn", "up_bn")}
+        self._neck_norms = {f"upsample.{n}.{b}": self.norms.add(f"upsample.{n}.{b}", l.out_planes) for n, l in self.neck.layers()
+                            for b in l.NORMS}
 
     def _reserve_head(self, arena):
         """Neck, then head, behind the trunk: one contiguous "head" bucket.  Norm vectors sit right behind their convolution's slots."""
-        self._neck_slots, self._head_slots = {}, {}
         for n, l in self.neck.layers():
-            for k, shape in l.arena_shapes().items():
-                self._neck_slots[f"{n}.{k}"] = arena.reserve(f"upsample.{n}.{k}", shape)
-                if k.endswith("dcn.%s.bias" % l.dcn.DCN_NAME):
-                    self._neck_norms[n + ".dcn_bn"].reserve(arena)
-                elif k == "up_sample.weight":
-                    self._neck_norms[n + ".up_bn"].reserve(arena)
-        for k, shape in self.head.arena_shapes().items():
-            self._head_slots[k] = arena.reserve("head." + k, shape)
+            behind = {f"dcn.{l.dcn.DCN_NAME}.bias": "dcn_bn", "up_sample.weight": "up_bn"}
+            for k in l.arena_shapes():
+                self._adopted.reserve(arena, [f"upsample.{n}.{k}"])
+                if k in behind:
+                    self._neck_norms[f"upsample.{n}.{behind[k]}"].reserve(arena)
+        self._adopted.reserve(arena, ["head." + k for k in self.head.arena_shapes()])
 
     def _finish_layers(self, params):
-        a = self.arena
-        for n in self._neck_norms.values():
-            n.gamma, n.g_gamma = a.view("w", n._gi), a.view("g", n._gi)
-            n.beta, n.g_beta = a.view("w", n._bi), a.view("g", n._bi)
-        views = lambda slots, which: {k: a.view(which, i) for k, i in slots.items()}
-        self.neck.adopt(views(self._neck_slots, "w"), views(self._neck_slots, "g"), self._neck_norms)
-        self.head.adopt(views(self._head_slots, "w"), views(self._head_slots, "g"))
+        self._adopted.adopt_onto(self.arena, self._neck_norms)
         self._post = {}
         super()._finish_layers(params)
 
@@ -399,10 +392,7 @@ class CenterNet(FPNDetector):
     def _bind_params(self, params):
         """FPNDetector._bind_params for the trunk; the neck's and head's entries, when the dict has them (a backbone-only classification
         checkpoint does not: load_weights(strict=False) leaves them as they are), go in through the layers' strict load_state_dict."""
-        for layer, pre in ((self.neck, "upsample."), (self.head, "head.")):
-            own = {k[len(pre):]: v for k, v in params.items() if k.startswith(pre)}
-            if own:
-                layer.load_state_dict(own)
+        self._adopted.bind(params)
         super()._bind_params({k: v for k, v in params.items() if k.startswith("backbone.")})
 
     def repack_weights(self):
@@ -414,34 +404,25 @@ class CenterNet(FPNDetector):
         self._repack_head()
 
     def _repack_head(self):
-        self.neck.repack()
-        self.head.repack()
+        self._adopted.repack()
         if not self.training:
-            self.neck.refresh_eval()
+            self._adopted.refresh_eval()
 
     def train(self, mode=True):
         super().train(mode)
-        self.neck.train(mode)
-        self.head.train(mode)
+        self._adopted.train(mode)
         if not mode:
-            self.neck.refresh_eval()
+            self._adopted.refresh_eval()
         return self
 
     def state_dict(self):
-        out = super().state_dict()
-        out.update({"upsample." + k: v.numpy() for k, v in self.neck.state_dict().items()})
-        out.update({"head." + k: v.numpy() for k, v in self.head.state_dict().items()})
-        return out
+        return {**super().state_dict(), **self._adopted.state_dict()}
 
     def reference_grads(self):
-        out = super().reference_grads()
-        out.update({"upsample." + k: v.detach().cpu().clone() for k, v in self.neck.grads().items()})
-        out.update({"head." + k: v.detach().cpu().clone() for k, v in self.head.grads().items()})
-        return out
+        return {**super().reference_grads(), **self._adopted.grads()}
 
     def reference_grads_names(self):
-        return super().reference_grads_names() + ["upsample." + k for k in self.neck.names() if "running_" not in k] \
-            + ["head." + k for k in self.head.names()]
+        return super().reference_grads_names() + self._adopted.grad_names()
 
     # ---- plan ----------------------------------------------------------------------------------------------------------------------------------
     def _plan_head(self, pl):
@@ -532,7 +513,7 @@ class CenterNet(FPNDetector):
             dst.copy_(torch.stack([s, z, cx - s * dw / 2, z, s, cy - s * dh / 2], 1))
             return
         if info is None:
-            info = np.asarray([[(H + 31) // 32 * 32, (W + 31) // 32 * 32, H, W]] * N, np.float64)
+            info = np.asarray([[round_up32(H), round_up32(W), H, W]] * N, np.float64)
         else:
             info = (info.numpy() if torch.is_tensor(info) else np.asarray(info)).astype(np.float64).reshape(N, -1)[:, :4]
         out = np.empty((N, 6), np.float32)

@@ -40,6 +40,30 @@ class ParamArena:
         return getattr(self, which)[off:off + n].view(shape)
 
 
+class HostToDevice:
+    """data_to_input's `Tensor(image)` (layers/common/pre_processing.py:13): a host batch (the loaders yield float64 / float32 / uint8
+    numpy arrays) becomes the fp32 device tensor through bd_h2d_submit -- the library's worker threads convert it chunk by chunk into
+    pinned memory and every chunk leaves with its own DMA as soon as it is converted (conversion under transfer).  The stager is created
+    by the first host batch; `dst`, the tensor returned, is a view of one grow-only buffer for every input shape (the copies and their
+    reader run on the current stream).  MODEL.H2D_THREADS / H2D_CHUNK_ELEMS are read, at each call, from the `cfg` given here: the model's
+    config object at construction (a model that is given another config object afterwards needs another HostToDevice)."""
+
+    def __init__(self, device, cfg):
+        self.device, self.cfg = device, cfg
+        self.stager = self.buf = self.dst = None
+
+    def __call__(self, image):
+        arr = image.numpy() if torch.is_tensor(image) else np.asarray(image)
+        if self.stager is None:
+            self.stager = ops.HostStager(self.device, int(self.cfg.MODEL.get("H2D_THREADS", 0)))
+        if not self.stager.supports(arr):
+            arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if self.buf is None or self.buf.numel() < arr.size:
+            self.buf = torch.empty((arr.size,), dtype=torch.float32, device=self.device)
+        self.dst = self.buf[: arr.size].view(arr.shape)
+        return self.stager.submit(arr, self.dst, int(self.cfg.MODEL.get("H2D_CHUNK_ELEMS", 0)))
+
+
 class ConvLayer:
     """One convolution (+ folded FrozenBN or bias).  Master weight fp32 [Cout][R][S][Cin] (OHWI);
     bf16 packed copies for the forward ([Cout][RS][Cin], BN scale folded in) and dgrad ([Cin][RS][Cout]) kernels."""

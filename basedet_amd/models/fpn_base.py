@@ -21,7 +21,7 @@ from ..ops import Geom
 from ..streams import SideStreams, fork, join
 from . import params as P
 from .. import comm as _comm
-from .engine import ConvLayer, DeconvLayer, FCLayer, ParamArena, TrainableStem
+from .engine import ConvLayer, DeconvLayer, FCLayer, HostToDevice, ParamArena, TrainableStem
 from .fp8_scaling import Fp8GradScaler, initial_grad_scale
 from .live_norm import BatchNormState, LiveNorms
 from .plan_arena import PlanArena, _Carver, _Plan, _round_up
@@ -130,7 +130,7 @@ class FPNDetector:
         if params is None:
             params = self.init_params(cfg, seed)
         self._pack_table = None            # bd_weight_pack_multi's table: built by the first repack_trainable, dropped by _bind_params
-        self._stager = self._h2d_buf = self._h2d_dst = None        # host-to-device staging, created by the first host batch
+        self._h2d = HostToDevice(self.device, cfg)                 # host-to-device staging (bd_h2d_submit)
         self._raw_buf = None                                       # device copy of a RawImageBatch's packed bytes (grow-only)
         self._build_layers(params)
         self._plans = {}
@@ -737,7 +737,7 @@ class FPNDetector:
             packed = self._raw_to_device(image)
         else:
             if not (torch.is_tensor(image) and image.is_cuda):
-                image = self._host_to_device(image)
+                image = self._h2d(image)
             image = image.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
             N, _, H, W = image.shape
         Hp, Wp = _round_up(H, 32), _round_up(W, 32)
@@ -766,24 +766,6 @@ class FPNDetector:
             info = torch.tensor([[Hp, Wp, H, W, 0]] * N, dtype=torch.float32)
         out["img_info"] = info.to(self.device, dtype=torch.float32).contiguous()
         return out
-
-    def _host_to_device(self, image):
-        """data_to_input's `Tensor(image)` (layers/common/pre_processing.py:13): a host batch (the loaders yield float64 / float32 /
-        uint8 numpy arrays) becomes the fp32 device tensor through bd_h2d_submit -- the library's worker threads convert it chunk by
-        chunk into pinned memory and every chunk leaves with its own DMA as soon as it is converted (conversion under transfer).
-        Round 2 converted the whole batch with one host copy first: 13-20 ms of the reference-protocol step."""
-        arr = image.numpy() if torch.is_tensor(image) else np.asarray(image)
-        st = self._stager
-        if st is None:
-            st = self._stager = ops.HostStager(self.device, int(self.cfg.MODEL.get("H2D_THREADS", 0)))
-        if not st.supports(arr):
-            arr = np.ascontiguousarray(arr, dtype=np.float32)
-        # one grow-only destination for every input shape (the copies and their reader, bd_pad_normalize, run on the current stream)
-        buf = self._h2d_buf
-        if buf is None or buf.numel() < arr.size:
-            buf = self._h2d_buf = torch.empty((arr.size,), dtype=torch.float32, device=self.device)
-        dst = self._h2d_dst = buf[: arr.size].view(arr.shape)
-        return st.submit(arr, dst, int(self.cfg.MODEL.get("H2D_CHUNK_ELEMS", 0)))
 
     def _raw_to_device(self, batch):
         """The packed bytes of a RawImageBatch -> one grow-only uint8 device buffer, in one asynchronous copy on the current stream (its

@@ -24,9 +24,13 @@ class BatchNormState:
         self._gi = arena.reserve(self.name + ".weight", (self.C,))
         self._bi = arena.reserve(self.name + ".bias", (self.C,))
 
-    def bind(self, arena, params):
+    def bind_views(self, arena):
+        """gamma / beta and their gradients: the views of the allocated arena's entries reserve() made."""
         self.gamma, self.g_gamma = arena.view("w", self._gi), arena.view("g", self._gi)
         self.beta, self.g_beta = arena.view("w", self._bi), arena.view("g", self._bi)
+
+    def bind(self, arena, params):
+        self.bind_views(arena)
         for t, k in ((self.gamma, "weight"), (self.beta, "bias"), (self.running_mean, "running_mean"), (self.running_var, "running_var")):
             t.copy_(torch.from_numpy(np.asarray(params[f"{self.name}.{k}"], np.float32).reshape(-1)))
 

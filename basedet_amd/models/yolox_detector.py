@@ -8,9 +8,10 @@ import torch
 
 from basedet_amd import ops
 from basedet_amd.layers import yolox_blocks as B
+from basedet_amd.layers._pm import round_up32
 from basedet_amd.layers.yolox_head import head_param_shapes, validate_conv
-from basedet_amd.models.engine import ParamArena
-from basedet_amd.models.fpn_base import FPNDetector
+from basedet_amd.models.adopted import AdoptedParts
+from basedet_amd.models.engine import HostToDevice, ParamArena
 from basedet_amd.models.live_norm import LiveNorms
 from basedet_amd.utils.registry import registers
 
@@ -21,10 +22,6 @@ def _glue():
     """models/yolox.py (imported late: it imports this module)."""
     from basedet_amd.models import yolox
     return yolox
-
-
-def _round_up32(v):
-    return (int(v) + 31) // 32 * 32
 
 
 @registers.models.register()
@@ -102,12 +99,13 @@ class YOLOX:
         bottom_up = CSPDarknet(d, w, out_features=tuple(m.BACKBONE.OUT_FEATURES), seed=seed, device=device)
         self.backbone = YOLOPAFPN(bottom_up, depth=d, width=w, seed=seed + 1000, device=device)
         self.head = YOLOXHead(self.num_classes, in_channels=in_ch, mid_channels=mid, seed=seed + 2000, device=device)
+        self._parts = AdoptedParts([("backbone", self.backbone), ("head", self.head)], self.device)
         for _, c in self._norm_layers():                     # set_model_hyperparam (yolox.py:65-69); BN_MOMENTUM is MegEngine's convention
             c.eps = c.norm.eps = float(m.BN_EPS)
             c.momentum = c.norm.momentum = 1.0 - float(m.BN_MOMENTUM)
         self._build_arena()
         self._target_size = tuple(cfg.AUG.TRAIN_SETTING.INPUT_SIZE)
-        self._stager = self._h2d_buf = self._h2d_dst = None        # host-to-device staging, created by the first host batch
+        self._h2d = HostToDevice(self.device, cfg)                 # (bd_h2d_submit: the one host-to-device route of the project)
         self._halo, self._pts, self._post = {}, {}, {}             # per shape: the input image, the points, the inference scratch
         self._cur = None
         self._pack_table = None
@@ -117,33 +115,22 @@ class YOLOX:
 
     def _norm_layers(self):
         """[(state_dict prefix, ConvBNSiLU)] in forward order: backbone, PAFPN, head."""
-        return [("backbone." + n, c) for n, c in self.backbone._leaves()] + [("head." + n, c) for n, c in self.head._blocks()]
+        return [(n, c) for n, c in self._parts._leaves() if c.NORMS]
 
     def _build_arena(self):
         a = self.arena = ParamArena(self.device)
         self.norms = LiveNorms(self.device)
-        parts = (("backbone.", self.backbone), ("head.", self.head))
-        slots = {}
-        for pre, layer in parts:
-            for k, shape in layer.arena_shapes().items():
-                if len(shape) == 4:
-                    slots[pre + k] = a.reserve(pre + k, shape)
+        shapes = self._parts.arena_shapes()
+        self._parts.reserve(a, [k for k, shape in shapes.items() if len(shape) == 4])
         self.decay_end = a.total
         recs = {}
         for n, c in self._norm_layers():
             recs[n + ".norm"] = self.norms.add(n + ".norm", c.cout)
             recs[n + ".norm"].reserve(a)
-        for pre, layer in parts:
-            for k, shape in layer.arena_shapes().items():
-                if len(shape) == 1:
-                    slots[pre + k] = a.reserve(pre + k, shape)
+        self._parts.reserve(a, [k for k, shape in shapes.items() if len(shape) == 1])
         a.allocate()
         self.norms.allocate()
-        for r in recs.values():
-            r.gamma, r.g_gamma, r.beta, r.g_beta = a.view("w", r._gi), a.view("g", r._gi), a.view("w", r._bi), a.view("g", r._bi)
-        for pre, layer in parts:
-            cut = lambda d: {k[len(pre):]: v for k, v in d.items() if k.startswith(pre)}
-            layer.adopt(cut({k: a.view("w", i) for k, i in slots.items()}), cut({k: a.view("g", i) for k, i in slots.items()}), cut(recs))
+        self._parts.adopt_onto(a, recs)
 
     def grad_buckets(self):
         """{phase: (lo, hi)} for GradBuckets: one bucket, closed at the end of backward()."""
@@ -159,16 +146,9 @@ class YOLOX:
         self._target_size = size
 
     # ---- parameters --------------------------------------------------------------------------------------------------------------------------
-    def _parts(self):
-        return ((self.backbone, "backbone."), (self.head, "head."))
-
     def _bind_params(self, params):
-        """(Re)load from a reference-layout dict: each part that the dict has entries of goes in through its layer's strict
-        load_state_dict, which copies in place (the arena views stay where they are) and repacks."""
-        for layer, pre in self._parts():
-            own = {k[len(pre):]: v for k, v in params.items() if k.startswith(pre)}
-            if own:
-                layer.load_state_dict(own)
+        """(Re)load from a reference-layout dict (AdoptedParts.bind: strict per part, in place)."""
+        self._parts.bind(params)
         if not self.training:
             self._fold_norms()
 
@@ -180,11 +160,10 @@ class YOLOX:
         return self.load_weights(states, strict=strict)
 
     def state_dict(self):
-        return {pre + k: v.numpy() for layer, pre in self._parts() for k, v in layer.state_dict().items()}
+        return self._parts.state_dict()
 
     def repack_weights(self):
-        self.backbone.repack()
-        self.head.repack()
+        self._parts.repack()
         if not self.training:
             self._fold_norms()
 
@@ -192,32 +171,28 @@ class YOLOX:
         """Every bf16 operand from its fp32 master in ONE launch (bd_weight_pack_multi); the table holds raw pointers into the arena and
         the packed tensors, which never move after construction."""
         if self._pack_table is None:
-            ent = [(c._w, None, c._wf, c._wd, c.cout, c.k * c.k, c.cin) for _, c in self._norm_layers()]
-            ent += [(p.w, None, p.wf, p.wd, p.ld, 1, p.cin) for _, p in self.head._preds()]
-            self._pack_table = ops.build_pack_table(ent, self.device)
+            self._pack_table = ops.build_pack_table([c.pack_entry() for _, c in self._parts._leaves()], self.device)
         ops.weight_pack_multi(self._pack_table)
         if not self.training:
             self._fold_norms()
 
     def _fold_norms(self, pack=True):
         """Evaluation reads 1 / sqrt(running_var + eps) of every norm, computed once here (the layers' refresh_eval)."""
-        self.backbone.refresh_eval()
-        self.head.refresh_eval()
+        self._parts.refresh_eval()
 
     def train(self, mode=True):
         self.training = bool(mode)
-        self.backbone.train(mode)
-        self.head.train(mode)
+        self._parts.train(mode)
         return self
 
     def eval(self):
         return self.train(False)
 
     def reference_grads(self):
-        return {pre + k: v.detach().cpu() for layer, pre in self._parts() for k, v in layer.grads().items()}
+        return self._parts.grads()
 
     def reference_grads_names(self):
-        return [pre + k for layer, pre in self._parts() for k in layer.names() if "running_" not in k]
+        return self._parts.grad_names()
 
     def state_dict_trainable_names(self):
         return list(self.reference_grads_names())
@@ -226,8 +201,6 @@ class YOLOX:
         return [e[0] for e in self.arena.entries]
 
     # ---- forward -------------------------------------------------------------------------------------------------------------------------------
-    _host_to_device = FPNDetector._host_to_device          # (bd_h2d_submit: the one host-to-device route of the project)
-
     def pre_process(self, inputs):
         """yolox.py:71-98.  The loader's fp32 (N, 3, H, W) batch, host or device -> x_halo bf16 (N, Hp + 6, Wp + 8, 4) with mean 0 and std
         1.  Training: a batch whose (H, W) is not target_size is resized to it bilinearly in the launch that writes x_halo
@@ -235,7 +208,7 @@ class YOLOX:
         batch is only padded to a multiple of 32.  Returns {x_halo, N, H, W (of x_halo's image area), img_info[, gt_boxes]}."""
         image = inputs["data"] if isinstance(inputs, dict) else inputs
         if not (torch.is_tensor(image) and image.is_cuda):
-            image = self._host_to_device(image)
+            image = self._h2d(image)
         image = image.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
         N, C, H, W = image.shape
         if C != 3:
@@ -247,7 +220,7 @@ class YOLOX:
             Hp, Wp = h, w
         else:
             h, w = H, W
-            Hp, Wp = _round_up32(H), _round_up32(W)
+            Hp, Wp = round_up32(H), round_up32(W)
             self._check_size("the padded batch size", (Hp, Wp))
         x_halo = self._halo.get((N, Hp, Wp))
         if x_halo is None:

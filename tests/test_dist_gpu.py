@@ -81,7 +81,7 @@ torch.cuda.synchronize()
 assert np.isfinite(float(out["total_loss"]))
 assert torch.cuda.current_device() == int(os.environ.get("LOCAL_RANK", "0"))
 if os.environ.get("BD_TEST_HOST_BATCH") == "1":
-    assert model._stager.device.index == torch.cuda.current_device() and model._h2d_dst.device.index == torch.cuda.current_device()
+    assert model._h2d.stager.device.index == torch.cuda.current_device() and model._h2d.dst.device.index == torch.cuda.current_device()
 w = model.arena.w.cpu().numpy()
 np.save(out_path, np.stack([w0.cpu().numpy(), w]))
 sys.stderr.write("DIGEST " + hashlib.sha256(w.tobytes()).hexdigest() + " " + repr(float(np.abs(w).sum())) + "\n")

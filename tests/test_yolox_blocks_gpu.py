@@ -329,8 +329,8 @@ def test_focus_layer():
     layer = _block_case(lambda: BL.Focus(3, 16, 3), O.focus, 2, 3, 6, 10, seed=1, image=True)
     assert tuple(layer.state_dict()["conv.weight"].shape) == (16, 12, 3, 3) and tuple(layer.params()["conv.weight"].shape) == (16, 12, 3, 3)
     # the pad input channels: zero in the master, exactly zero in the gradient (the input is zero there)
-    assert int(bits_of(layer.conv._w[..., 12:]).abs().max()) == 0 and int(bits_of(layer.conv.pad_grad()).abs().max()) == 0
-    assert float(layer.conv._gw[..., :12].abs().max()) > 0
+    assert int(bits_of(layer.conv._store.w["weight"][..., 12:]).abs().max()) == 0 and int(bits_of(layer.conv.pad_grad()).abs().max()) == 0
+    assert float(layer.conv._store.g["weight"][..., :12].abs().max()) > 0
 
 
 @pytest.mark.parametrize("H,W", [(2, 2), (5, 3)])
@@ -510,4 +510,4 @@ def test_network_descends():
             m.repack()
     print("total loss, step 1 .. 20:", " ".join(f"{v:.4f}" for v in losses))
     assert all(np.isfinite(losses)) and losses[-1] < losses[0]
-    assert int(bits_of(fpn.backbone.stem.conv._w[..., 12:]).abs().max()) == 0          # Focus's pad columns stayed zero
+    assert int(bits_of(fpn.backbone.stem.conv._store.w["weight"][..., 12:]).abs().max()) == 0          # Focus's pad columns stayed zero

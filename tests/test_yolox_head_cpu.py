@@ -109,7 +109,8 @@ def test_initial_pred_biases_and_refusals():
     # the initial biases: -log((1 - p) / p) for cls_preds and obj_preds (init_module), zero for reg_preds -- by hand for p = 0.01: -log(99)
     assert np.isclose(-math.log((1 - 0.01) / 0.01), -4.59511985013459, rtol=1e-14)
     src = open(os.path.join(ROOT, "basedet_amd", "layers", "yolox_head.py")).read()
-    assert "bias_value = -math.log((1 - prior_prob) / prior_prob)" in src and "cp.b[:K] = bias_value" in src and "rp.b[4] = bias_value" in src
+    assert "bias_value = -math.log((1 - prior_prob) / prior_prob)" in src and 'cp._store.w["bias"][:K] = bias_value' in src \
+        and 'rp._store.w["bias"][4] = bias_value' in src
 
 
 def test_new_symbols_in_header_binding_and_abi():

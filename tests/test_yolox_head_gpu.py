@@ -337,9 +337,10 @@ def _head_case(K):
         d_feats = head.backward_pm(d_cls.cuda(), d_bo.cuda())
         torch.cuda.synchronize()
         runs.append(dict(cls=cls.clone(), bo=bo.clone(), d_feats=[t.clone() for t in d_feats], grads={k: v.clone() for k, v in head.grads().items()}))
-    pads = dict(cw=[c.w.clone() for c in head.cls_preds], cb=[c.b.clone() for c in head.cls_preds], cgw=[c.gw.clone() for c in head.cls_preds],
-                cgb=[c.gb.clone() for c in head.cls_preds], rw=[c.w.clone() for c in head.regobj_preds], rb=[c.b.clone() for c in head.regobj_preds],
-                rgw=[c.gw.clone() for c in head.regobj_preds], rgb=[c.gb.clone() for c in head.regobj_preds])
+    held = lambda preds, which, k: [getattr(c._store, which)[k].clone() for c in preds]
+    pads = dict(cw=held(head.cls_preds, "w", "weight"), cb=held(head.cls_preds, "w", "bias"), cgw=held(head.cls_preds, "g", "weight"),
+                cgb=held(head.cls_preds, "g", "bias"), rw=held(head.regobj_preds, "w", "weight"), rb=held(head.regobj_preds, "w", "bias"),
+                rgw=held(head.regobj_preds, "g", "weight"), rgb=held(head.regobj_preds, "g", "bias"))
     orc = {}
     for faithful in (False, True):
         p = O.double_params(p0, True)
@@ -509,5 +510,5 @@ def test_short_training_run():
     assert all(np.isfinite(losses)) and all(bool(torch.isfinite(v).all()) for v in head.state_dict().values())
     assert losses[-1] < losses[0]
     for cp, rp in zip(head.cls_preds, head.regobj_preds):          # the pad rows stayed zero through the optimizer steps
-        assert int(bits_of(cp.w[K:]).abs().sum()) == 0 and int(bits_of(rp.w[5:]).abs().sum()) == 0
+        assert int(bits_of(cp._store.w["weight"][K:]).abs().sum()) == 0 and int(bits_of(rp._store.w["weight"][5:]).abs().sum()) == 0
     head.load_state_dict(c["p0"])

@@ -60,16 +60,10 @@ def _adopt(layer):
     """Move `layer` onto flat storage like a model's arena; returns (w_flat, g_flat)."""
     shapes = layer.arena_shapes()
     w_flat, g_flat, w, g = util.flat_storage(shapes)
-    if hasattr(layer, "_blocks"):
-        names = [n for n, _ in layer._blocks()]
-        couts = [b.cout for _, b in layer._blocks()]
-    elif hasattr(layer, "_leaves"):
-        names = [n for n, _ in layer._leaves()]
-        couts = [c.cout for _, c in layer._leaves()]
+    if hasattr(layer, "_leaves"):
+        layer.adopt(w, g, {n + ".norm": util.norm_record(c.cout) for n, c in layer._leaves() if c.NORMS})
     else:
         layer.adopt(w, g, util.norm_record(layer.cout))
-        return w_flat, g_flat
-    layer.adopt(w, g, {n + ".norm": util.norm_record(c) for n, c in zip(names, couts)})
     return w_flat, g_flat
 
 
@@ -180,11 +174,12 @@ def test_arena_layout_state_round_trip_and_names(model3):
     orig = m.state_dict()
     g = torch.Generator().manual_seed(1)
     st = {k: (torch.rand(v.shape, generator=g) + 0.5).numpy() for k, v in m.state_dict().items()}
-    w_ptr, ptrs = a.w.data_ptr(), [c._w.data_ptr() for _, c in m._norm_layers()]
+    w_ptr, ptrs = a.w.data_ptr(), [c._store.w["weight"].data_ptr() for _, c in m._norm_layers()]
     m.load_state_dict(st)
-    assert a.w.data_ptr() == w_ptr and [c._w.data_ptr() for _, c in m._norm_layers()] == ptrs
-    assert all(util.lies_inside(c._w, a.w) and util.lies_inside(c.norm.p["weight"], a.w) for _, c in m._norm_layers())
-    assert all(util.lies_inside(p.w, a.w) and util.lies_inside(p.b, a.w) and util.lies_inside(p.gw, a.g) for _, p in m.head._preds())
+    assert a.w.data_ptr() == w_ptr and [c._store.w["weight"].data_ptr() for _, c in m._norm_layers()] == ptrs
+    assert all(util.lies_inside(c._store.w["weight"], a.w) and util.lies_inside(c.norm.p["weight"], a.w) for _, c in m._norm_layers())
+    assert all(util.lies_inside(p._store.w["weight"], a.w) and util.lies_inside(p._store.w["bias"], a.w)
+               and util.lies_inside(p._store.g["weight"], a.g) for p in m.head.cls_preds + m.head.regobj_preds)
     assert all(util.lies_inside(c.norm.p["running_var"], m.norms.running) for _, c in m._norm_layers())
     back = m.state_dict()
     assert list(back) == list(st) and all(np.array_equal(back[k], st[k]) for k in st)
@@ -193,8 +188,8 @@ def test_arena_layout_state_round_trip_and_names(model3):
     names = [k for k in st if "running_" not in k]
     assert m.reference_grads_names() == names == m.state_dict_trainable_names()
     # the pad rows of the padded predictors and Focus's pad columns came back as zeros
-    assert int(util.bits_of(m.head.cls_preds[0].w[3:]).abs().max()) == 0 and int(util.bits_of(m.head.regobj_preds[0].b[5:]).abs().max()) == 0
-    assert int(util.bits_of(m.backbone.backbone.stem.conv._w[..., 12:]).abs().max()) == 0
+    assert int(util.bits_of(m.head.cls_preds[0]._store.w["weight"][3:]).abs().max()) == 0 and int(util.bits_of(m.head.regobj_preds[0]._store.w["bias"][5:]).abs().max()) == 0
+    assert int(util.bits_of(m.backbone.backbone.stem.conv._store.w["weight"][..., 12:]).abs().max()) == 0
     with pytest.raises(KeyError):
         m._bind_params({k: v for k, v in st.items() if k != "head.stems.0.weight"})
     m.load_state_dict(orig)          # (the module's model goes on to the other tests with the weights it was built with)
@@ -290,8 +285,8 @@ def test_training_run_descends_through_a_size_change_and_the_all_bucket():
     assert comm.calls == [(m.arena.g.data_ptr(), m.arena.total, "sum"), "wait"] * 20
     assert all(np.isfinite(losses)) and losses[-1] < losses[0]
     assert m._cur["H"] == 96 and (N, 64, 64) in m._halo and (N, 96, 96) in m._halo
-    assert int(util.bits_of(m.backbone.backbone.stem.conv._w[..., 12:]).abs().max()) == 0          # Focus's pad columns stayed zero
-    assert int(util.bits_of(m.head.cls_preds[0].w[3:]).abs().max()) == 0
+    assert int(util.bits_of(m.backbone.backbone.stem.conv._store.w["weight"][..., 12:]).abs().max()) == 0          # Focus's pad columns stayed zero
+    assert int(util.bits_of(m.head.cls_preds[0]._store.w["weight"][3:]).abs().max()) == 0
 
 
 # ---- inference -----------------------------------------------------------------------------------------------------------------------------------
